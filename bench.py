@@ -1,22 +1,26 @@
 #!/usr/bin/env python3
 """Benchmark of the Pocket-TTS decode hot path on MI355X (metric: BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset headline|config4|b1|int8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset headline|config4|b1|int8] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* is one 80 ms frame of every utterance of the batch: one FlowLM autoregressive step plus one Mimi codec
 decode for `--batch` (default 64) concurrent fixed-length utterances per GPU (BASELINE.json configs[2]; SURVEY.md
-section 8d).  An *utterance job* is: voice-state clone + text prefill (32 tokens) + 125 steps (10 s of audio).  The
-timed region consists of WHOLE utterance jobs, whatever `--steps K` is: at least 3 of them, at least ceil(K / 125), and
-enough for >= 1 s of wall time (one untimed job calibrates the count), so the per-utterance costs (clone, prefill,
-pipeline fill and drain) are always amortised over 125 steps each and a 20-step request does not turn into a 20 ms
-measurement.  `steps` in the JSON line is the number of steps actually timed, `ms_per_step` = timed wall / steps, and
-`value` is the MEDIAN per-utterance rate (GPU-timeline events at the utterance boundaries, max over ranks per
-utterance); `value_whole_region` is total audio / total wall.  Inputs (weights, voice KV, token ids) are resident in HBM;
+section 8d).  An *utterance job* is: voice-state clone + text prefill (32 tokens) + 125 steps (10 s of audio); the
+utterances of a run follow each other, so every 125th step starts new ones with a clone + prefill.  After `--warmup W`
+steps exactly `--steps K` steps are timed.  `steps` in the JSON line is K, `ms_per_step` = timed wall / K, and `value`
+is the MEDIAN per-utterance rate over the whole utterances inside the timed region (GPU-timeline events at the
+utterance boundaries, max over ranks per utterance), or total audio / total wall when the region holds no whole
+utterance; `value_whole_region` is total audio / total wall.  Inputs (weights, voice KV, token ids) are resident in HBM;
 every PCM chunk lands in pinned host memory inside the timed region.  A cooperative-kernel timeout inside the timed
-region (`ptts_lm_state_error`) makes the run exit non-zero without a JSON line.
+region (`ptts_lm_state_error`) makes the run exit non-zero without a JSON line.  `--dump-outputs DIR` writes what the
+last timed step handed to its caller (PCM chunk, latent, EOS logit) as float32 `DIR/<name>.npy`; the same arguments give
+the same files bit for bit when the committed tile table covers the run's GEMM shapes (tiles tuned live may differ
+from run to run and round differently).
 
-`api_batch` in the line (N = 1 only) is the throughput a USER of the drop-in surface gets for 64 concurrent requests:
+A plain run does only the above.  `--full` adds the secondary measurements to the same line (N = 1 only unless noted):
+the eager per-kernel profile and `roofline` (any N), `latency_b1`, `one_voice`, `api_batch` and `cpu_baseline`.
+`api_batch` is the throughput a USER of the drop-in surface gets for 64 concurrent requests:
 `TTSModel.generate_audio_batch` and `ContinuousBatcher` (64 slots), per-row EOS bookkeeping on, every PCM chunk handed to
 the caller, tokenisation, voice clone and prefill inside the timed calls.
 
@@ -65,7 +69,10 @@ PRESETS = {
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=125)
+    ap.add_argument("--steps", type=int, default=125,
+                    help="timed steps.  `value` is the median over the WHOLE utterances among them: there is one only when "
+                         "--steps >= 125 + (-warmup mod 125), e.g. >= 225 at --warmup 25 or >= 125 at --warmup 125; "
+                         "below that `value` is the whole-region rate (utterances_timed 0)")
     ap.add_argument("--warmup", type=int, default=25)
     ap.add_argument("--preset", choices=sorted(PRESETS), default="headline")
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU (default 64)")
@@ -93,14 +100,20 @@ def parse(argv=None):
     ap.add_argument("--voices", choices=("distinct", "one"), default="distinct",
                     help="distinct: every utterance of the batch has its own voice state (SURVEY 8d: conditioning f32[B,126,1024]; "
                          "the headline); one: all clone ONE resident voice state, whose keys they then share (`one_voice` object)")
-    ap.add_argument("--quick", action="store_true", help="A/B runs: only the timed region (no cpu baseline, latency, API, kernel profile)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="lower bound of the timed region's wall time")
-    ap.add_argument("--min-utterances", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: kernel profile + roofline, b1 latency, one-voice leg, API, cpu baseline")
+    ap.add_argument("--quick", action="store_true", help="only the timed region, also with --full (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (PCM chunk, latent, EOS logit) as float32 DIR/<name>.npy")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="--full: lower bound of the one-voice leg's wall time")
+    ap.add_argument("--min-utterances", type=int, default=3, help="--full: lower bound of the one-voice leg's utterances")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     for k, v in PRESETS[args.preset].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
-    if args.quick:
+    if args.quick or not args.full:
         args.no_cpu_baseline = args.no_latency = args.no_api = args.no_profile = True
     args.batch = 64 if args.batch is None else args.batch
     args.config = args.config or "en100m"
@@ -550,6 +563,30 @@ def cpu_baseline(args, cfg, W):
     return out
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much over all ranks
+
+
+def dump_outputs(job, out_dir, rank, world):
+    """--dump-outputs: what the last timed step handed to its caller, float32 `<name>.npy` (rank r > 0:
+    `<name>_rank<r>.npy`): `pcm` [B, frame_samples] from the pinned host buffer, `latent` [B, ldim] that fed the codec,
+    `eos_logit` [B].  Beyond DUMP_BYTES in all, the same seeded sample of rows is written for every array."""
+    import numpy as np
+
+    P = job.pipe
+    last = P.t - 1  # the FlowLM step of the last timed step; its codec frame wrote pcm_of(last)
+    q = last % P.nb
+    arrays = {"pcm": P.pcm_of(last).numpy(), "latent": P.lat[q].cpu().numpy(), "eos_logit": P.logit[q].cpu().numpy()}
+    rows = len(arrays["pcm"])
+    per_row = sum(a[0].size for a in arrays.values()) * 4
+    if rows * per_row > DUMP_BYTES // world:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // world // per_row, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def dryrun(args):
     """`PTTS_BENCH_DRYRUN=1`: the multi-rank plumbing of this file WITHOUT a GPU (tests/test_host_cpu.py, world_size 2
     over gloo): rendezvous, barriers, whole-job aggregation (sum of units over ranks / max wall over ranks), per-rank
@@ -590,16 +627,15 @@ def main():
 
     # Tile choices come from the table measured on an MI355X and committed with the profiles (so kernel names in this
     # run, in profiles/*_kernel_stats.csv and in profiles/*_pmc_traffic.json mean the same configurations); shapes
-    # missing from it are tuned live and written to an UNTRACKED file.  PTTS_TUNE_CACHE= (empty) tunes everything live.
+    # missing from it are tuned live.  PTTS_TUNE_CACHE= (empty) tunes everything live.  The run writes nothing into the
+    # tree (the checkout may be read-only): live-tuned shapes are kept only where PTTS_TUNE_CACHE_OUT=<file> says.
     os.environ.setdefault("PTTS_TUNE_CACHE", os.path.join(REPO, "profiles", "tune_cache_mi355x.txt"))
     if not os.environ["PTTS_TUNE_CACHE"]:
         del os.environ["PTTS_TUNE_CACHE"]
-    scratch = os.path.join(REPO, "gpurun_out")
-    os.makedirs(scratch, exist_ok=True)
+    os.environ.setdefault("PTTS_TUNE_CACHE_OUT", "")  # empty: Engine.tune writes no file
     from pocket_tts_amd import parallel
 
     rank, local, world = parallel.env_ranks()
-    os.environ.setdefault("PTTS_TUNE_CACHE_OUT", os.path.join(scratch, f"tune_additions_rank{rank}.txt"))
     if world != args.gpus and rank == 0:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; using the launcher's world size", file=sys.stderr)
     torch.cuda.set_device(local)
@@ -629,27 +665,24 @@ def main():
     for _ in range(args.warmup):
         job.step()
     job.pipe.flush()
-    # one untimed whole utterance: warms the prefill path and tells how many utterances make >= --min-seconds
-    barrier()
-    tc = time.perf_counter()
-    job.run_utterance()
-    job.sync()
-    t_utt = time.perf_counter() - tc
-    n_utt = max(args.min_utterances, -(-args.steps // args.frames), int(np.ceil(args.min_seconds / max(t_utt, 1e-6))))
-    if dist is not None:  # every rank times the same number of utterances
-        t = torch.tensor([n_utt], dtype=torch.int64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        n_utt = int(t.item())
-    steps_timed = n_utt * args.frames
+    steps_timed = args.steps
     job.contexts = []
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_utt + 1)]
+    # events on the codec stream at the utterance boundaries inside the timed region (every rank has the same ones):
+    # consecutive marks enclose one whole utterance
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps_timed // args.frames + 2)]
+    n_marks = 0
     barrier()
     eng.timer_start()
     t0 = time.perf_counter()
-    marks[0].record(job.pipe.s2)
-    for u in range(n_utt):
-        job.run_utterance()
-        marks[u + 1].record(job.pipe.s2)  # behind the utterance's last codec frame (the codec stream)
+    if job.frame >= args.frames:  # the region starts with new utterances
+        marks[0].record(job.pipe.s2)
+        n_marks = 1
+    for _ in range(steps_timed):
+        job.step()
+        if job.frame >= args.frames:
+            marks[n_marks].record(job.pipe.s2)  # behind the utterance's last codec frame (the codec stream)
+            n_marks += 1
+    job.pipe.flush()  # the last step's codec frame, when the pipeline mode leaves it pending
     job.sync()
     ev_ms = eng.timer_stop_ms()
     barrier()
@@ -663,6 +696,7 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         sys.exit(3)
+    n_utt = max(n_marks - 1, 0)  # whole utterances inside the timed region
     utt_ms = torch.tensor([marks[u].elapsed_time(marks[u + 1]) for u in range(n_utt)], dtype=torch.float64, device=dev)
     audio_rank = args.batch * steps_timed * FRAME_S
     rate, wall = parallel.job_throughput(audio_rank, wall_rank, dist, dev)
@@ -672,9 +706,12 @@ def main():
         t[rank] = per_rank[0]
         dist.all_reduce(t)
         per_rank = [float(v) for v in t.tolist()]
-        dist.all_reduce(utt_ms, op=dist.ReduceOp.MAX)  # an utterance of the job ends when its slowest rank ends
+        if n_utt:
+            dist.all_reduce(utt_ms, op=dist.ReduceOp.MAX)  # an utterance of the job ends when its slowest rank ends
     utt_ms = [float(v) for v in utt_ms.tolist()]
     utt_rates = [world * args.batch * args.frames * FRAME_S / (m * 1e-3) for m in utt_ms]
+    if args.dump_outputs:
+        dump_outputs(job, args.dump_outputs, rank, world)
 
     if rank == 0:
         L = cfg.flow_lm.transformer.num_layers
@@ -682,7 +719,7 @@ def main():
         restarts = sum(1 for c in job.contexts if c == args.voice_len + args.text_len + 1)
         out = {
             "metric": "audio-seconds/sec (xRT), 100M en model, whole job over all GPUs",
-            "value": float(np.median(utt_rates)),
+            "value": float(np.median(utt_rates)) if utt_rates else rate,
             "unit": "audio-seconds/sec",
             "n_gpus": world,
             "steps": steps_timed,
@@ -692,8 +729,9 @@ def main():
             "value_whole_region": rate,
             "utterances_timed": n_utt,
             "utterance_ms": [round(m, 3) for m in utt_ms],
-            "value_definition": "median over the timed utterances of (GPUs x batch x 10 s) / utterance time; utterance "
-                                "time from HIP events behind each utterance's last codec frame (codec stream), max over ranks",
+            "value_definition": "median over the whole utterances in the timed region of (GPUs x batch x 10 s) / utterance "
+                                "time; utterance time from HIP events behind each utterance's last codec frame (codec "
+                                "stream), max over ranks; value_whole_region when the region holds no whole utterance",
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -713,8 +751,8 @@ def main():
                 "preset": args.preset,
                 "batch_per_gpu": args.batch,
                 "parallelism": f"replicas x{world} (no collective on the data path)",
-                "timed_region": f"{n_utt} whole utterances = {steps_timed} steps: {restarts} clone+prefill inside, "
-                                f"mean FlowLM context {ctx:.1f} keys, {wall:.3f} s wall",
+                "timed_region": f"{steps_timed} steps after {args.warmup} warmup steps: {n_utt} whole utterances, "
+                                f"{restarts} clone+prefill inside, mean FlowLM context {ctx:.1f} keys, {wall:.3f} s wall",
             },
             "xrt_per_gpu": rate / world,
             "per_rank_xrt": per_rank,
@@ -767,9 +805,12 @@ def main():
             out["latency_b1"] = first_chunk_latency(eng, a1, job1)
             job1 = None
         job_one = None
-        if world == 1 and args.voices == "distinct" and args.batch >= 16 and not args.quick:
+        if args.full and not args.quick and world == 1 and args.voices == "distinct" and args.batch >= 16:
+            # whole utterances: as many as --steps covers, >= --min-utterances, >= --min-seconds at the headline's pace
+            n_one = max(args.min_utterances, -(-args.steps // args.frames),
+                        int(np.ceil(args.min_seconds / max(step_s * args.frames, 1e-6))))
             try:  # a secondary leg must not cost the headline line
-                out["one_voice"], job_one = one_voice_throughput(eng, args, n_utt, rank, out["tune_table_id"], not args.no_profile)
+                out["one_voice"], job_one = one_voice_throughput(eng, args, n_one, rank, out["tune_table_id"], not args.no_profile)
             except Exception as e1:  # noqa: BLE001
                 out["one_voice"] = {"error": f"{type(e1).__name__}: {e1}"}
         if not args.no_api and world == 1 and args.preset in ("headline", "b1") and args.config != "24l" and args.batch > 1:

@@ -312,3 +312,34 @@ def test_continuous_batching_stress_with_noise(model, fx):
         n_tok = len(model.tokenizer.encode(t)) + 8
         assert o.dim() == 1 and o.shape[0] % 1920 == 0 and torch.isfinite(o).all()
         assert 0 < o.shape[0] // 1920 <= estimate_max_gen_len(n_tok, model.config.mimi.frame_rate) + 1
+
+
+@pytest.mark.parametrize("batch,steps,utterances", [(64, 130, 1), (1, 3, 0)])
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path, batch, steps, utterances):
+    """`bench.py --dump-outputs`, run twice with the same arguments, writes the same files bit for bit (batch 64: the
+    "events" pipeline, one whole utterance inside the region; batch 1: the host-synchronised one, whose last codec frame
+    is decoded by the final flush).  Both batches are covered by the committed tile table, so nothing is tuned live."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    bench = str(Path(__file__).resolve().parents[1] / "bench.py")
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    got = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--batch", str(batch), "--steps", str(steps),
+                            "--warmup", "0", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert (line["steps"], line["warmup"], line["utterances_timed"]) == (steps, 0, utterances)
+        got.append({k: np.load(d / f"{k}.npy") for k in ("pcm", "latent", "eos_logit")})
+    a, b = got
+    assert a["pcm"].shape == (batch, 1920) and a["latent"].shape == (batch, 32) and a["eos_logit"].shape == (batch,)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all()
+        assert np.array_equal(a[k], b[k]), k
+    assert np.abs(a["pcm"]).max() > 0

@@ -158,6 +158,9 @@ def test_bench_presets_and_rank_spawning():
     assert (a.config, a.batch, a.gpus, a.quantize) == ("24l", 32, 8, False)
     a = bench.parse([])
     assert (a.config, a.batch, a.gpus, a.steps) == ("en100m", 64, 1, 125)
+    assert not a.full and a.no_profile and a.no_latency and a.no_api and a.no_cpu_baseline  # plain run: headline only
+    f = bench.parse(["--full", "--dump-outputs", "d"])
+    assert f.dump_outputs == "d" and not (f.no_profile or f.no_latency or f.no_api or f.no_cpu_baseline)
     assert bench.parse(["--preset", "int8"]).quantize and bench.parse(["--batch", "4", "--preset", "b1"]).batch == 4
     import torch
 
@@ -182,6 +185,37 @@ def test_bench_presets_and_rank_spawning():
     audio = 5 * 10 * 0.08
     assert d["n_gpus"] == 2 and abs(d["value"] - 2 * audio / 0.2) < 1e-6
     assert [round(v, 6) for v in d["per_rank_xrt"]] == [round(audio / 0.1, 6), round(audio / 0.2, 6)]
+
+
+def test_bench_dump_outputs_last_slot_and_row_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the ring slot of the LAST step ((t - 1) % nb) as float32, `_rank<r>` names on ranks > 0,
+    and beyond the size cap one seeded sample of rows, the same rows in every array.  Each slot holds its row number plus
+    a slot-specific offset, so slot and rows can be read back from the files."""
+    import types
+
+    import bench
+
+    B, nb, t = 6, 4, 7
+    rows = torch.arange(B, dtype=torch.float32)
+    pcm = [rows[:, None] + 1000.0 * i + torch.zeros(B, 5) for i in range(nb)]
+    lat = [rows[:, None] + 100.0 * i + torch.zeros(B, 3) for i in range(nb)]
+    logit = [rows + 10.0 * i for i in range(nb)]
+    job = types.SimpleNamespace(pipe=types.SimpleNamespace(t=t, nb=nb, lat=lat, logit=logit, pcm_of=lambda f: pcm[f % nb]))
+    q = (t - 1) % nb
+
+    bench.dump_outputs(job, str(tmp_path / "all"), 0, 1)
+    for name, ref in (("pcm", pcm[q]), ("latent", lat[q]), ("eos_logit", logit[q])):
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, ref.numpy())
+
+    per_row = (5 + 3 + 1) * 4
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 4 * per_row)  # two ranks: 4 of the 6 rows each
+    bench.dump_outputs(job, str(tmp_path / "cap"), 1, 2)
+    assert sorted(p.name for p in (tmp_path / "cap").iterdir()) == ["eos_logit_rank1.npy", "latent_rank1.npy", "pcm_rank1.npy"]
+    p, la, lo = (np.load(tmp_path / "cap" / f"{n}_rank1.npy") for n in ("pcm", "latent", "eos_logit"))
+    kept = lo - 10.0 * q
+    assert len(kept) == 4 and np.array_equal(kept, np.unique(kept))
+    assert np.array_equal(p[:, 0] - 1000.0 * q, kept) and np.array_equal(la[:, 0] - 100.0 * q, kept)
 
 
 def test_drop_in_package_name():

@@ -13,7 +13,7 @@ case $mode in
   cache) var=PTTS_TUNE_CACHE; vals=$1; shift ;;
   *) echo "usage: tools/ab.sh env|lib|cache ..." >&2; exit 2 ;;
 esac
-flags="--quick"; [ -n "$AB_B1" ] && flags="--no-cpu-baseline --no-api --no-profile"
+flags="--quick --steps 1250 --warmup 125"; [ -n "$AB_B1" ] && flags="--full --steps 1250 --warmup 125 --no-cpu-baseline --no-api --no-profile"
 for i in 1 2; do
   for v in $vals; do
     p=$v; [ "$v" = "-" ] && p=""

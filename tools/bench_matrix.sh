@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/matrix}; mkdir -p $out
 export PTTS_TUNE_CACHE=$PWD/profiles/tune_cache_mi355x.txt
 export PTTS_TUNE_CACHE_OUT=$PWD/$out/tune_additions.txt
-Q="--quick"
+Q="--quick --steps 1250 --warmup 125"   # ten whole utterances after a warm one per line
 python bench.py $Q > $out/headline.json 2> $out/headline.err
 for p in config4 int8 bf16codec config5 fp8codec config5fp8 lmbf16 split; do python bench.py --preset $p $Q > $out/$p.json 2> $out/$p.err; done
 for b in 1 4 16 32 128 256; do python bench.py --batch $b $Q > $out/b$b.json 2> $out/b$b.err; done
