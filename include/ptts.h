@@ -290,6 +290,37 @@ int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
  * d_out (capacity in floats).  Names: see DESIGN.md.  Returns rows*cols or <0. */
 int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi, const char *name, float *d_out,
                         int64_t capacity, int32_t *rows, int32_t *cols, void *stream);
+/* Test hook: ONE GEMM of the hot path's kernel family (gemm_kernel / gemm_lds_kernel), packed by the engine's own
+ * packers and launched through the production dispatcher, on plain row-major device buffers:
+ *   y[m][n] = epilogue( sum_tap sum_c pre(x[row(m, tap)][c]) * w[n][c][tap] ),  row(b * T + t, tap) = b * T * xstride + t * xstride + tap - halo
+ * (ntaps == 1: a Linear, row(m) = m).  Rows before a sequence's start come from x_prev (halo_mode 0: the previous frame,
+ * row b * T * xstride + T * xstride + (t * xstride + tap - halo)), are zero (1) or repeat the sequence's first row (2).
+ * Enumerations as in the kernels: wfmt 0 fp32, 1 int8, 2 bf16, 3 split bf16; pre 0 none, 1 ELU, 2 add + SiLU, 3 LayerNorm
+ * (folded), 4 modulated LayerNorm; epi 0 store, 1 residual (+ layer scale), 2 gate; act 0 none, 1 GELU, 2 SiLU, 3 ELU.
+ * Returns 0 when the GEMM ran, 1 when no kernel exists for the combination (an explicit cfg that the dispatcher does not
+ * admit for it, or a (wfmt, pre) pair no kernel implements), < 0 on an error, e.g. a kernel that wrote past its output.
+ * Tiles the kernel leaves unwritten read back as NaN.  Synchronises `stream`. */
+typedef struct ptts_gemm_case {
+  int32_t M, N, C, ntaps;                  /* output rows, output channels, input channels (% 16 == 0), taps */
+  int32_t T, xstride, halo, halo_mode;     /* convolutions (ntaps > 1): rows per sequence (% 16 == 0, divides M), see above */
+  int32_t wfmt, pre, epi, act;
+  int32_t cfg;                             /* configuration 0..17 of the dispatcher's table, -1 = its own choice */
+  int32_t krot, lds_target;                /* engine option "k_rotate"; dynamic-LDS target of the codec's launches (bytes) */
+  const float *x, *x_prev;                 /* [rows][C], rows = M * xstride (x_prev: halo_mode 0 only) */
+  const float *w, *bias;                   /* [N][C][ntaps], [N] or null */
+  const float *ln_w, *ln_b;                /* pre 3: LayerNorm gain / bias [C]; pre 4: affine [C] or null */
+  const float *prevec;                     /* pre 2: [C] */
+  const float *mod_shift, *mod_scale;      /* pre 4: [M][C] */
+  const float *r, *g, *ls;                 /* epi 1 / 2: residual, gate [M][N]; epi 1: layer scale [N] or null */
+  float *y;                                /* out: [M][N] */
+  float *w_eff, *w_eff_lo;                 /* optional out: [N][ntaps * C] weights the kernel consumed, k = tap * C + c (int8:
+                                              q * scale; bf16: the bf16 values; split: hi in w_eff, lo in w_eff_lo) */
+  float *ln_s, *ln_c;                      /* optional out (pre 3): [N] fold vectors */
+  char *label;                             /* optional out: the launch's profiler label */
+  int32_t label_cap;
+  int32_t cfg_used;                        /* out: the configuration that ran */
+} ptts_gemm_case;
+int ptts_debug_gemm(ptts_engine *e, ptts_gemm_case *c, void *stream);
 /* Per-launch profiler (HIP events around every kernel launch on its own stream, tagged with call site,
  * kernel and algorithmic bytes / flops).  stop() writes text lines "site kernel count total_ms bytes flops"
  * to h_out and returns the length.  Never active inside a captured graph. */

@@ -37,6 +37,17 @@ class PttsTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("d_data", C.c_void_p), ("numel", C.c_int64)]
 
 
+class PttsGemmCase(C.Structure):
+    """ptts_gemm_case: one GEMM for the ptts_debug_gemm test hook"""
+    _fields_ = [
+        *[(f, C.c_int32) for f in ("M", "N", "C", "ntaps", "T", "xstride", "halo", "halo_mode", "wfmt", "pre", "epi", "act",
+                                   "cfg", "krot", "lds_target")],
+        *[(f, C.c_void_p) for f in ("x", "x_prev", "w", "bias", "ln_w", "ln_b", "prevec", "mod_shift", "mod_scale", "r", "g",
+                                    "ls", "y", "w_eff", "w_eff_lo", "ln_s", "ln_c")],
+        ("label", C.c_void_p), ("label_cap", C.c_int32), ("cfg_used", C.c_int32),
+    ]
+
+
 # every symbol include/ptts.h declares: (restype, argtypes)
 _P = C.c_void_p
 PROTOTYPES = {
@@ -97,6 +108,7 @@ PROTOTYPES = {
     "ptts_timer_stop_ms": (C.c_int, [_P, _P, C.POINTER(C.c_float)]),
     "ptts_debug_read": (C.c_int64, [_P, _P, C.c_int32, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), _P]),
+    "ptts_debug_gemm": (C.c_int, [_P, C.POINTER(PttsGemmCase), _P]),
     "ptts_lm_weight_bytes": (C.c_int64, [_P]),
     "ptts_mimi_weight_bytes": (C.c_int64, [_P]),
 }

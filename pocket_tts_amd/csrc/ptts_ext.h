@@ -5,7 +5,7 @@
 
 // ---- ptts_lmh.hip: FlowLM Linear layers with bf16 weights (PTTS_LM_BF16) ------------------------------------------
 // register-staged K-split / 2-D tile configurations of gemm_kernel<.., WF = 2>; `cfg` indexes the same table as
-// launch_by_cfg in ptts.hip (only the q8_cfg() subset exists), `pre` is PRE_NONE or PRE_LNFOLD
+// launch_by_cfg in ptts.hip (only the b16_cfg() subset exists), `pre` is PRE_NONE or PRE_LNFOLD
 void launch_gemm_b16(hipStream_t st, const GemmArgs &a, int pre, int cfg, unsigned dyn_lds);
 // fp32 packed image [NT][KF][64][4] (LayerNorm gain already multiplied in) -> bf16 image [NT][KF/2][64][8]; with
 // ln_s != null also the fold vector s[n] = sum_k W'[n][k] of the ROUNDED weights (NT * 16 floats)

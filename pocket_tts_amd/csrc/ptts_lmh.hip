@@ -19,7 +19,6 @@ static void launch_cfg_b16(hipStream_t st, const GemmArgs &a, int pre, unsigned 
 
 void launch_gemm_b16(hipStream_t st, const GemmArgs &a, int pre, int cfg, unsigned dyn) {
   switch (cfg) {
-    case 0: launch_cfg_b16<1, 1, 8, 1, 1>(st, a, pre, dyn); break;
     case 1: launch_cfg_b16<1, 2, 4, 1, 1>(st, a, pre, dyn); break;
     case 2: launch_cfg_b16<1, 4, 4, 1, 1>(st, a, pre, dyn); break;
     case 7: launch_cfg_b16<2, 4, 4, 1, 1>(st, a, pre, dyn); break;

@@ -497,6 +497,60 @@ class Engine:
         self.sync()
         return buf[: r.value * c.value].view(r.value, c.value).clone()
 
+    _GEMM_INTS = ("T", "xstride", "halo", "halo_mode", "wfmt", "pre", "epi", "act", "cfg", "krot", "lds_target")
+    _GEMM_INS = ("x_prev", "bias", "ln_w", "ln_b", "prevec", "mod_shift", "mod_scale", "r", "g", "ls")
+
+    def debug_gemm(self, x: torch.Tensor, w: torch.Tensor, *, want_weights: bool = False, **kw):
+        """Test hook: one GEMM of the hot path's kernel family through the production dispatcher (ptts_debug_gemm in
+        include/ptts.h).  x: [M * xstride][C] (ntaps = w.shape[2] > 1: M = rows of output), w: [N][C] or [N][C][ntaps];
+        keyword arguments: the case's integer fields (cfg defaults to -1, the dispatcher's choice) and float32 device
+        operands.  Returns None when no kernel exists for the combination, else a dict with y [M][N], the label, the
+        configuration that ran and, with want_weights, the effective weights w_eff (and w_eff_lo) [N][ntaps * C] and the
+        LayerNorm fold vectors ln_s / ln_c."""
+        w3 = w if w.dim() == 3 else w.unsqueeze(2)
+        N, Cin, ntaps = w3.shape
+        c = _lib.PttsGemmCase()
+        c.xstride, c.cfg, c.T = 1, -1, 16
+        for k in self._GEMM_INTS:
+            if k in kw:
+                setattr(c, k, int(kw[k]))
+        c.C, c.N, c.ntaps = Cin, N, ntaps
+        c.M = x.shape[0] // c.xstride if ntaps > 1 else x.shape[0]
+        keep = {}
+
+        def dev(t):
+            t = t.to(self.device, torch.float32).contiguous()
+            keep[id(t)] = t
+            return t.data_ptr()
+
+        c.x, c.w = dev(x), dev(w3)
+        for k in self._GEMM_INS:
+            if kw.get(k) is not None:
+                setattr(c, k, dev(kw[k]))
+        out = {"y": torch.empty((c.M, N), dtype=torch.float32, device=self.device)}
+        c.y = out["y"].data_ptr()
+        if want_weights:
+            out["w_eff"] = torch.empty((N, ntaps * Cin), dtype=torch.float32, device=self.device)
+            c.w_eff = out["w_eff"].data_ptr()
+            if c.wfmt == 3:
+                out["w_eff_lo"] = torch.empty_like(out["w_eff"])
+                c.w_eff_lo = out["w_eff_lo"].data_ptr()
+            if c.pre == 3:
+                out["ln_s"] = torch.empty((N,), dtype=torch.float32, device=self.device)
+                out["ln_c"] = torch.empty((N,), dtype=torch.float32, device=self.device)
+                c.ln_s, c.ln_c = out["ln_s"].data_ptr(), out["ln_c"].data_ptr()
+        label = C.create_string_buffer(256)
+        c.label = C.addressof(label)
+        c.label_cap = 256
+        self._pre()
+        rc = _lib.check(self.lib.ptts_debug_gemm(self.handle, C.byref(c), self._sp))
+        del keep
+        if rc == 1:
+            return None
+        out["label"] = label.value.decode()
+        out["cfg"] = c.cfg_used
+        return out
+
     def close(self):
         """Destroys every state created from this engine, then the engine (order matters: states
         point into the engine)."""
