@@ -107,7 +107,7 @@ void ptts_destroy(ptts_engine *e);
 /* ---- FlowLM state: init_states(flow_lm, B, T) (stateful_module.py:7-16, transformer.py:46-57) */
 int ptts_lm_state_create(ptts_engine *e, int32_t batch, int32_t t_cap, ptts_lm_state **out);
 void ptts_lm_state_destroy(ptts_lm_state *s);
-/* zero offsets (fresh init_states) */
+/* zero offsets (fresh init_states); also clears every row's sampling override (ptts_lm_state_set_row_sampling) */
 int ptts_lm_state_reset(ptts_lm_state *s, void *stream);
 /* Import / export one layer in the reference layout cache f32[2, src_batch, t, H, 64] (device) with
  * `t` valid positions (transformer.py:32-36; voice files tts_model.py:1047-1072).  On import,
@@ -153,6 +153,23 @@ int ptts_lm_decode_step(ptts_engine *e, ptts_lm_state *s, const float *d_latent_
  * counter-based device generator (the reference draws from torch's global CPU generator,
  * flow_lm.py:131-135, which cannot be reproduced on device; parity runs pass d_noise or temp 0). */
 int ptts_lm_set_noise(ptts_lm_state *s, float temp, uint64_t seed);
+/* Per-row sampling override (a server's per-request settings in one continuous batch; the reference takes them per model,
+ * flow_lm.py:131-137, tts_model.py:756-760).  Row `row` of later steps then uses, instead of the state's ptts_lm_set_noise
+ * temperature and the step's eos_threshold argument:
+ *   temp           its own std = sqrt(temp) for the device generator (d_noise == NULL only; external noise is used as
+ *                  given).  Without a clamp the draws are bitwise those of a state whose ptts_lm_set_noise used `temp`
+ *                  (same seed, same row); temp 0 gives zeros.
+ *   noise_clamp    > 0: a truncated normal on [-noise_clamp, noise_clamp], drawn by the inverse CDF like
+ *                  torch.nn.init.trunc_normal_ (flow_lm.py:134-137); <= 0: no clamp
+ *   eos_threshold  the row's EOS flag is logit > eos_threshold
+ * The kernels read the values from device memory at run time: graphs captured before the call pick them up.  The write
+ * is stream-ordered on `stream`, like ptts_lm_state_copy_row_from.  Rejects a row out of range and a temp that is
+ * negative or not finite (-1).  ptts_lm_state_reset clears every override; ptts_lm_state_copy / _copy_row / _copy_row_from
+ * leave the destination's overrides as they are (they copy sequences, not sampling settings). */
+int ptts_lm_state_set_row_sampling(ptts_lm_state *s, int32_t row, float temp, float noise_clamp, float eos_threshold,
+                                   void *stream);
+/* row `row` returns to the state's defaults (ptts_lm_set_noise temperature, the step's eos_threshold); stream-ordered */
+int ptts_lm_state_clear_row_sampling(ptts_lm_state *s, int32_t row, void *stream);
 /* device pointer of the state's own copy of the latest latent f32[B, ldim] */
 const float *ptts_lm_latent_ptr(ptts_lm_state *s);
 
@@ -287,7 +304,9 @@ int ptts_copy_to_host_async(ptts_engine *e, void *h_dst, const void *d_src, int6
 int ptts_timer_start(ptts_engine *e, void *stream);
 int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
 /* Test hook: copies an internal activation buffer, converted to row-major f32[rows, cols], to
- * d_out (capacity in floats).  Names: see DESIGN.md.  Returns rows*cols or <0. */
+ * d_out (capacity in floats).  Names: see DESIGN.md; FlowLM name "noise" = the last step's LSD start point (the noise)
+ * f32[B, ldim] (only kept when that step ran the single-launch flow MLP, "flow_cluster"; -1 otherwise).
+ * Returns rows*cols or <0. */
 int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi, const char *name, float *d_out,
                         int64_t capacity, int32_t *rows, int32_t *cols, void *stream);
 /* Test hook: ONE GEMM of the hot path's kernel family (gemm_kernel / gemm_lds_kernel), packed by the engine's own

@@ -12,12 +12,17 @@ the codec's last kernel (data/audio.py:79).
 
 With temp == 0 every request reproduces `TTSModel.generate_audio` for the same text and voice (same frame
 count, waveform equal up to fp32 summation order: batch tiles differ from batch-1 tiles).
+
+A request may bring its own temperature, noise clamp and EOS threshold (a server's per-request settings): they are
+written to its slot's row of the batch state (`LMState.set_row_sampling`) before the row's first step, and the step's
+kernels read them per row.  A request without any of them runs exactly as the model's settings would.
 """
 
 from __future__ import annotations
 
 import collections
 import logging
+import math
 import queue
 import threading
 
@@ -80,6 +85,26 @@ class Request:
                 return
             yield item
 
+    def iter_batches(self):
+        """Like iterating, but each item is the list of every chunk that has arrived by then (at least one): a consumer
+        that hands chunks to another thread or an event loop pays that hand-off once per batch, not once per frame."""
+        while True:
+            items = [self._q.get()]
+            while items[-1] is not None:
+                try:
+                    items.append(self._q.get_nowait())
+                except queue.Empty:
+                    break
+            done = items[-1] is None  # the sentinel is always the last item of a request
+            if done:
+                items.pop()
+            if items:
+                yield items
+            if done:
+                if self.error is not None:
+                    raise self.error
+                return
+
     def result(self) -> torch.Tensor:
         parts = list(self)
         if not parts:
@@ -90,10 +115,11 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp")
 
-    def __init__(self, req, tokens, voice, gen, fae, last):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
+        self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
         self.start = None      # global step of its first FlowLM step
 
 
@@ -117,8 +143,8 @@ class ContinuousBatcher:
         eng = self.eng
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
-        if model.temp > 0:
-            self.st.set_noise(model.temp, noise_seed)
+        # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
+        self.st.set_noise(model.temp, noise_seed)
         for b in range(slots):
             self.st.set_row_active(b, False)
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
@@ -131,6 +157,10 @@ class ContinuousBatcher:
         self.a_fae = np.zeros(slots, np.int64)
         self.a_eos = np.full(slots, -1, np.int64)
         self.a_emit = np.full(slots, 0, np.int64)         # >= 0: no running job in the slot
+        self.row_samp = [False] * slots                   # the slot's row carries a sampling override
+        # held by the background scheduler around each iteration: other users of the engine (e.g. a voice-prompt encode
+        # on a request thread) take it to run between the scheduler's steps (`exclusive`)
+        self.engine_lock = threading.RLock()
         self.waiting: collections.deque = collections.deque()
         self.g = 0            # global step counter == pipe.t
         self.collected = 0    # frames [0, collected) have been read (EOS flags) and routed (PCM)
@@ -145,9 +175,14 @@ class ContinuousBatcher:
         self._closed = False
 
     # ---- submission (any thread) ---------------------------------------------------------------
-    def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50) -> Request:
+    def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
+               temperature: float | None = None, noise_clamp: float | None = None,
+               eos_threshold: float | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
-        chunks that run one after the other, each from the voice state."""
+        chunks that run one after the other, each from the voice state.
+
+        `temperature`, `noise_clamp` (<= 0: none) and `eos_threshold` apply to this request only; None means the model's
+        value.  A request that gives none of them runs with the model's settings exactly."""
         from .tts_model import _state_current_end
 
         m = self.model
@@ -155,6 +190,19 @@ class ContinuousBatcher:
             raise RuntimeError(f"the batcher has stopped after an error: {self._failed}")
         if not text or not text.strip():
             raise ValueError("Text to generate cannot be empty")
+        samp = None
+        if temperature is not None or noise_clamp is not None or eos_threshold is not None:
+            t = float(m.temp if temperature is None else temperature)
+            c = m.noise_clamp if noise_clamp is None else noise_clamp
+            c = 0.0 if c is None else float(c)
+            e = float(m.eos_threshold if eos_threshold is None else eos_threshold)
+            if not (math.isfinite(t) and t >= 0):
+                raise ValueError(f"temperature must be a finite number >= 0, got {temperature}")
+            if math.isnan(c):
+                raise ValueError("noise_clamp must be a number")
+            if not math.isfinite(e):
+                raise ValueError(f"eos_threshold must be a finite number, got {eos_threshold}")
+            samp = (t, c, e)
         chunks = split_into_best_sentences(m.tokenizer.encode, m.tokenizer.sp, text, max_tokens,
                                            m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
         t_voice = _state_current_end(model_state)
@@ -171,7 +219,8 @@ class ContinuousBatcher:
             need = t_voice + len(ids) + gen + self.pipe.nb + 2  # a row runs up to nb steps past its end before it is parked
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
-            jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1))
+            jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
+                             samp))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -242,6 +291,12 @@ class ContinuousBatcher:
             eng.lm_prefill(grp, eng.embed_text(torch.cat([j.tokens for j in jobs], dim=0)))
             for i, b in enumerate(rows):
                 self.st.copy_row_from(b, grp, i)   # KV rows, position, BOS as the pending input, row active
+            for job, b in zip(jobs, rows):         # the row's sampling settings, before its first step
+                if job.samp is not None:
+                    self.st.set_row_sampling(b, *job.samp)
+                elif self.row_samp[b]:
+                    self.st.clear_row_sampling(b)
+                self.row_samp[b] = job.samp is not None
             eng.sync()  # the group state is freed below; its clone kernels must have run
         finally:
             if grp is not None:
@@ -351,13 +406,15 @@ class ContinuousBatcher:
                 try:
                     if idle:
                         if self.collected < self.g:
-                            self._drain()  # the last frames of the rows that just left; may queue a follow-up chunk
-                            self._check_gpu_error()
+                            with self.engine_lock:
+                                self._drain()  # the last frames of the rows that just left; may queue a follow-up chunk
+                                self._check_gpu_error()
                         with self._wake:
                             if not self._stop and not self.waiting:
                                 self._wake.wait(timeout=0.05)
                     else:
-                        self.step()
+                        with self.engine_lock:
+                            self.step()
                 except Exception as e:  # forward to every waiting consumer, like the reference's result_queue errors
                     self._fail(e)
                     return
@@ -365,6 +422,17 @@ class ContinuousBatcher:
         self._stop = False
         self._thread = threading.Thread(target=loop, daemon=True, name="ptts-batcher")
         self._thread.start()
+
+    @property
+    def failed(self) -> Exception | None:
+        """the error the scheduler stopped on, or None"""
+        return self._failed
+
+    def exclusive(self, fn, *args, **kwargs):
+        """runs `fn` on the calling thread while the background scheduler waits between two of its iterations (work
+        that shares the engine with the scheduler, such as encoding a voice prompt)"""
+        with self.engine_lock:
+            return fn(*args, **kwargs)
 
     def _fail(self, e: Exception):
         """the scheduler cannot continue: every outstanding request - waiting, admitted or mid-admission - gets the

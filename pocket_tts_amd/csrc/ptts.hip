@@ -210,6 +210,13 @@ struct ptts_lm_state {
   float rng_std = 0.f;
   unsigned long long rng_seed = 0;
   int *rng_ctr = nullptr;
+  // per-row sampling overrides (ptts_lm_state_set_row_sampling; RowSampling in ptts_kernels.h): marker, {std, clamp, lo,
+  // width} of the device generator's draw, EOS threshold
+  int *samp_on = nullptr;
+  f32x4 *samp_noise = nullptr;
+  float *samp_eos = nullptr;
+  bool latfm_noise = false;  // the last enqueued step left its LSD start point in latfm (debug_read "noise")
+  RowSampling rsamp() const { return RowSampling{samp_on, samp_noise, samp_eos}; }
   // continuous batching: parked rows (active[b] == 0) keep computing but do not advance their position
   int *active = nullptr;
   std::vector<int> h_active;
@@ -1577,6 +1584,9 @@ static int build_lm_state(ptts_engine *e, ptts_lm_state *s) {
   CHK(dallocT(nullptr, &s->is_eos, B));
   CHK(dallocT(nullptr, &s->rng_ctr, 1));
   CHK(dallocT(nullptr, &s->active, B));
+  CHK(dallocT(nullptr, &s->samp_on, B));
+  CHK(dallocT(nullptr, &s->samp_noise, B));
+  CHK(dallocT(nullptr, &s->samp_eos, B));
   s->h_active.assign(B, 1);
   set_int_kernel<<<cdiv(B, 256), 256, 0, e->stream>>>(s->active, B, 1);
   fill_kernel<<<cdiv(B * c.ldim, 256), 256, 0, e->stream>>>(s->lat_prev, (long)B * c.ldim, NAN);
@@ -1592,6 +1602,7 @@ static void lm_state_free(ptts_lm_state *s) {
   if (s->pre.x) free_scratch(&s->pre);
   hipFree(s->xlat); hipFree(s->latfm); hipFree(s->c); hipFree(s->ce); hipFree(s->mod); hipFree(s->fx);
   hipFree(s->fh); hipFree(s->f1); hipFree(s->lat); hipFree(s->lat_prev); hipFree(s->eos_logit); hipFree(s->is_eos); hipFree(s->rng_ctr); hipFree(s->active); hipFree(s->fstat);
+  hipFree(s->samp_on); hipFree(s->samp_noise); hipFree(s->samp_eos);
   hipFree(s->fexch); hipFree(s->fflags); hipFree(s->ferr); hipFree(s->lexch); hipFree(s->lflags);
   delete s;
 }
@@ -1646,6 +1657,7 @@ extern "C" int ptts_lm_state_reset(ptts_lm_state *s, void *stream) {
   std::fill(s->h_off.begin(), s->h_off.end(), 0);
   std::fill(s->h_active.begin(), s->h_active.end(), 1);
   set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->active, s->B, 1);
+  set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->samp_on, s->B, 0);
   LAUNCHCHK();
   return 0;
 }
@@ -1850,6 +1862,42 @@ extern "C" int ptts_lm_set_noise(ptts_lm_state *s, float temp, uint64_t seed) {
   if (temp < 0) return fail(-1, "temperature must be >= 0");
   s->rng_std = std::sqrt(temp);  // std = temp ** 0.5 (reference flow_lm.py:132)
   s->rng_seed = seed;
+  return 0;
+}
+
+static __global__ void set_row_sampling_kernel(int *on, f32x4 *noise, float *eos, int v_on, f32x4 v_noise, float v_eos) {
+  if (threadIdx.x == 0) {
+    *on = v_on;
+    *noise = v_noise;
+    *eos = v_eos;
+  }
+}
+
+extern "C" int ptts_lm_state_set_row_sampling(ptts_lm_state *s, int32_t row, float temp, float noise_clamp,
+                                              float eos_threshold, void *stream) {
+  if (!s || row < 0 || row >= s->B) return fail(-1, "set_row_sampling: row out of range");
+  if (!std::isfinite(temp) || temp < 0) return fail(-1, "set_row_sampling: temperature must be finite and >= 0");
+  if (std::isnan(noise_clamp) || std::isnan(eos_threshold)) return fail(-1, "set_row_sampling: NaN clamp or EOS threshold");
+  const float sd = std::sqrt(temp);  // as ptts_lm_set_noise: bitwise the same draws at the same temperature
+  f32x4 p = {sd, 0.f, 0.f, 0.f};
+  if (noise_clamp > 0 && sd > 0) {
+    // [2 Phi(-c / std) - 1, 2 Phi(c / std) - 1] = [-a, a] with a = erf(c / (std sqrt 2))
+    const float a = (float)std::erf((double)noise_clamp / ((double)sd * 1.4142135623730950488));
+    p = (f32x4){sd, noise_clamp, -a, 2.f * a};
+  }
+  hipStream_t st = S(s->e, stream);
+  ENGINE_LOCK(s->e);
+  set_row_sampling_kernel<<<1, 64, 0, st>>>(s->samp_on + row, s->samp_noise + row, s->samp_eos + row, 1, p, eos_threshold);
+  LAUNCHCHK();
+  return 0;
+}
+
+extern "C" int ptts_lm_state_clear_row_sampling(ptts_lm_state *s, int32_t row, void *stream) {
+  if (!s || row < 0 || row >= s->B) return fail(-1, "clear_row_sampling: row out of range");
+  hipStream_t st = S(s->e, stream);
+  ENGINE_LOCK(s->e);
+  set_int_kernel<<<1, 64, 0, st>>>(s->samp_on + row, 1, 0);
+  LAUNCHCHK();
   return 0;
 }
 
@@ -2150,14 +2198,14 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
     const int nb_gemm = cdiv(DF * MT, 4), nb_prep = cdiv(MT * LF * 64, 256);
     prep_in_kernel<<<nb_gemm + nb_prep + cdiv(B * 32, 256), 256, 0, st>>>(
         d_latent_in ? d_latent_in : s->lat_prev, e->bos, d_noise, e->in_linear.w, sc.x, s->lat, s->latfm, B, c.ldim, MT, DF, s->rng_std,
-        s->rng_seed, s->rng_ctr, nb_gemm, nb_prep, RopeArgs{s->offset, e->freq_lm, sc.rope, B, 1});
+        s->rng_seed, s->rng_ctr, s->rsamp(), nb_gemm, nb_prep, RopeArgs{s->offset, e->freq_lm, sc.rope, B, 1});
   } else {
     {
       ProfScope ps(st, "prep_lm", 16.0 * B * c.ldim, 0);
       const int nb_prep = cdiv(MT * LF * 64, 256);
       prep_lm_kernel<<<nb_prep + cdiv(B * 32, 256), 256, 0, st>>>(d_latent_in ? d_latent_in : s->lat_prev, e->bos, d_noise,
                                                                    s->xlat, s->lat, s->latfm, B, c.ldim, MT, s->rng_std,
-                                                                   s->rng_seed, s->rng_ctr, nb_prep,
+                                                                   s->rng_seed, s->rng_ctr, s->rsamp(), nb_prep,
                                                                    RopeArgs{s->offset, e->freq_lm, sc.rope, B, 1});
     }
     SITE("lm.in_linear");
@@ -2175,6 +2223,7 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
   SITE("flow.head");  // out_norm is folded into [cond_embed ; out_eos]
   a = mk_gemm(e->head, sc.x, DF, MT, B);
   a.epi = EPI_HEAD; a.Y = s->ce; a.YF = FDF; a.head_nt = FDF; a.eos_thr = eos_thr;
+  a.eos_on = s->samp_on; a.eos_row = s->samp_eos;
   a.eos_logit = s->eos_logit; a.is_eos = s->is_eos;
   a.eos_logit2 = d_eos_logit; a.is_eos2 = d_is_eos;  // caller's buffers are written by the epilogue itself
   a.tail_offset = s->offset; a.tail_ctr = s->rng_ctr; a.tail_active = s->active;  // the step's bookkeeping rides along (was a launch)
@@ -2193,7 +2242,9 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
     }
     SITE("flow.cluster");
     launch_flow_cluster(st, e, s, lsd_steps, d_latent_out);
-  } else
+    s->latfm_noise = true;  // the cluster reads latfm, never writes it
+  } else {
+  s->latfm_noise = false;  // the per-layer path keeps the FM copy of the running latent there
   for (int i = 0; i < lsd_steps; ++i) {
     // all AdaLN modulations of the step in one GEMM on silu(t_emb + cond)  (mlp.py:107,127,210)
     SITE("flow.adaln");
@@ -2231,6 +2282,7 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
     a.epi = EPI_LATENT; a.lat = s->lat; a.ldim = c.ldim; a.inv_steps = 1.0f / (float)lsd_steps; a.Y = s->latfm; a.YF = LF;
     if (i == lsd_steps - 1) { a.lat_out1 = s->lat_prev; a.lat_out2 = d_latent_out; }  // next step's input + caller's copy
     launch_gemm(st, a, PRE_LNMOD);
+  }
   }
   SITE("");
   return 0;
@@ -3245,6 +3297,10 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
     else if (n == "ce") { src = s->ce; M = s->B; K = c.flow_dim; }
     else if (n == "fx") { src = s->fx; M = s->B; K = c.flow_dim; }
     else if (n == "prefill_x") { src = s->pre.x; M = s->pre.MT * 16; K = c.d_model; }
+    else if (n == "noise") {  // the last step's LSD start point (noise), [B][ldim]
+      if (!s->latfm_noise) return fail(-1, "debug_read: noise is only kept by steps that ran the flow cluster");
+      src = s->latfm; M = s->B; K = c.ldim;
+    }
     else return fail(-1, "unknown buffer " + n);
     F = K / 16;
   } else {

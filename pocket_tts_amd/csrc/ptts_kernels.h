@@ -160,6 +160,8 @@ struct GemmArgs {
   float *eos_logit, *eos_logit2;  // state copy, caller's copy (device or pinned host)
   uint8_t *is_eos, *is_eos2;
   float eos_thr;
+  const int *eos_on;     // per-row sampling overrides (RowSampling): eos_on[m] != 0 -> row m compares with eos_row[m]
+  const float *eos_row;  // instead of eos_thr (both null: every row uses eos_thr)
   int head_nt;  // n-tile holding the EOS row
   // end-of-step bookkeeping done by the EOS row's threads (one per sequence, so exactly once): offset[m] += 1 for active rows
   // (increment_steps, stateful_module.py:19-26) and, by row 0, the step counter.  Nothing after the head GEMM reads a position,
@@ -307,7 +309,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int 
         if (a.act == ACT_SILU) acc = act4(acc + *(const f32x4 *)(a.prevec + n0), ACT_SILU);
         *(f32x4 *)(a.Y + (((size_t)mt * a.YF + nt) * 64 + lane) * 4) = acc;
       } else if (g == 0 && m < a.M) {
-        const uint8_t fl = acc.x > a.eos_thr ? 1 : 0;
+        const float thr = (a.eos_on && a.eos_on[m]) ? a.eos_row[m] : a.eos_thr;
+        const uint8_t fl = acc.x > thr ? 1 : 0;
         if (a.eos_logit) a.eos_logit[m] = acc.x;
         if (a.eos_logit2) a.eos_logit2[m] = acc.x;
         if (a.is_eos) a.is_eos[m] = fl;
@@ -1339,6 +1342,52 @@ __device__ __forceinline__ float counter_normal(unsigned long long seed, unsigne
   float u2 = (float)((z >> 8) & 0xFFFFFF) * (1.0f / 16777216.0f);
   return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
 }
+// Truncated N(0, std^2) on [-clamp, clamp] by the inverse CDF, as torch.nn.init.trunc_normal_ builds it: u uniform in
+// [2l - 1, 2h - 1] (l = Phi(-clamp / std), h = Phi(clamp / std): lo = 2l - 1 and width = 2h - 2l come from the host),
+// z = clamp(std * sqrt(2) * erfinv(u), -clamp, clamp).  u01 = (2k + 1) / 2^24 for a 23-bit k of the same hash is exact
+// in fp32 and lies strictly inside (0, 1).
+__device__ __forceinline__ float counter_trunc_normal(unsigned long long seed, unsigned ctr, unsigned idx, float std,
+                                                      float clamp, float lo, float width) {
+  unsigned long long z = mix64(seed + 0x9E3779B97F4A7C15ull * (((unsigned long long)ctr << 32) | idx));
+  const float u01 = (float)(2u * (unsigned)(z >> 41) + 1u) * (1.0f / 16777216.0f);
+  const float u = fmaf(width, u01, lo);
+  return fminf(fmaxf(std * 1.41421356237309505f * erfinvf(u), -clamp), clamp);
+}
+
+// Per-row sampling overrides of a FlowLM state (ptts_lm_state_set_row_sampling), read at run time by the step prologue
+// (noise) and the head GEMM's EOS epilogue, so a captured graph sees values written after its capture.  on[m] != 0:
+// row m draws with noise[m] = {std, clamp (0: none), lo, width} and compares its EOS logit with eos[m].
+struct RowSampling {
+  const int *on;
+  const f32x4 *noise;
+  const float *eos;
+};
+
+// LSD start point of row m, columns base..base+3, on the device-generator path (no external noise): rows without an
+// override draw rng_std * N(0, 1) as they always did; an overridden row draws with its own std, truncated when it has a
+// clamp; std 0 gives exact zeros.
+__device__ __forceinline__ f32x4 device_noise(const RowSampling &rs, int m, float rng_std, unsigned long long rng_seed,
+                                              const int *rng_ctr, unsigned base) {
+  f32x4 z = {0.f, 0.f, 0.f, 0.f}, p = z;
+  float sd = rng_std;
+  if (rs.on && rs.on[m]) {
+    p = rs.noise[m];
+    sd = p.x;
+  }
+  if (sd > 0.f) {
+    const unsigned ctr = (unsigned)*rng_ctr;
+    if (p.y > 0.f) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) z[j] = counter_trunc_normal(rng_seed, ctr, base + j, sd, p.y, p.z, p.w);
+    } else {
+      z.x = sd * counter_normal(rng_seed, ctr, base + 0);
+      z.y = sd * counter_normal(rng_seed, ctr, base + 1);
+      z.z = sd * counter_normal(rng_seed, ctr, base + 2);
+      z.w = sd * counter_normal(rng_seed, ctr, base + 3);
+    }
+  }
+  return z;
+}
 
 // cos / sin of (offset[b] + t) * freq[i] for every row m = b*Tq + t, i < 32 (reference rope.py:28-50):
 // computed once per step instead of once per (layer, n-tile) in the QKV epilogue
@@ -1362,7 +1411,7 @@ __device__ __forceinline__ void rope_table_entry(const RopeArgs &r, int i) {
 // step's RoPE table (the remaining blocks): one launch instead of two.
 static __global__ void prep_lm_kernel(const float *lat_in, const float *bos, const float *noise, float *x_fm, float *lat,
                                float *lat_fm, int B, int ldim, int MT, float rng_std, unsigned long long rng_seed,
-                               const int *rng_ctr, int nb_prep, RopeArgs rope) {
+                               const int *rng_ctr, RowSampling rsamp, int nb_prep, RopeArgs rope) {
   if ((int)blockIdx.x >= nb_prep) {
     rope_table_entry(rope, (blockIdx.x - nb_prep) * blockDim.x + threadIdx.x);
     return;
@@ -1385,12 +1434,8 @@ static __global__ void prep_lm_kernel(const float *lat_in, const float *bos, con
     v.w = v.w != v.w ? b.w : v.w;
     if (noise) {
       z = *(const f32x4 *)(noise + (size_t)m * ldim + k);
-    } else if (rng_std > 0.f) {
-      const unsigned ctr = (unsigned)*rng_ctr, base = (unsigned)(m * ldim + k);
-      z.x = rng_std * counter_normal(rng_seed, ctr, base + 0);
-      z.y = rng_std * counter_normal(rng_seed, ctr, base + 1);
-      z.z = rng_std * counter_normal(rng_seed, ctr, base + 2);
-      z.w = rng_std * counter_normal(rng_seed, ctr, base + 3);
+    } else {
+      z = device_noise(rsamp, m, rng_std, rng_seed, rng_ctr, (unsigned)(m * ldim + k));
     }
   }
   *(f32x4 *)(x_fm + (size_t)i * 4) = v;
@@ -1405,7 +1450,7 @@ static __global__ void prep_lm_kernel(const float *lat_in, const float *bos, con
 static __global__ __launch_bounds__(256) void prep_in_kernel(const float *lat_in, const float *bos, const float *noise, const float *w_in,
                                                              float *x_out, float *lat, float *lat_fm, int B, int ldim, int MT, int DF,
                                                              float rng_std, unsigned long long rng_seed, const int *rng_ctr,
-                                                             int nb_gemm, int nb_prep, RopeArgs rope) {
+                                                             RowSampling rsamp, int nb_gemm, int nb_prep, RopeArgs rope) {
   const int LF = ldim / 16;
   if ((int)blockIdx.x < nb_gemm) {
     const int lane = threadIdx.x & 63, tile = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1441,12 +1486,8 @@ static __global__ __launch_bounds__(256) void prep_in_kernel(const float *lat_in
   if (m < B) {
     if (noise) {
       z = *(const f32x4 *)(noise + (size_t)m * ldim + k);
-    } else if (rng_std > 0.f) {
-      const unsigned ctr = (unsigned)*rng_ctr, base = (unsigned)(m * ldim + k);
-      z.x = rng_std * counter_normal(rng_seed, ctr, base + 0);
-      z.y = rng_std * counter_normal(rng_seed, ctr, base + 1);
-      z.z = rng_std * counter_normal(rng_seed, ctr, base + 2);
-      z.w = rng_std * counter_normal(rng_seed, ctr, base + 3);
+    } else {
+      z = device_noise(rsamp, m, rng_std, rng_seed, rng_ctr, (unsigned)(m * ldim + k));
     }
   }
   *(f32x4 *)(lat_fm + (size_t)i * 4) = z;

@@ -70,6 +70,17 @@ class LMState:
         """device-side N(0, temp) noise for steps called with noise=None (perf runs)"""
         _lib.check(self.engine.lib.ptts_lm_set_noise(self.handle, float(temp), int(seed)))
 
+    def set_row_sampling(self, row: int, temp: float, noise_clamp: float | None = None, eos_threshold: float = -4.0):
+        """Row `row` draws with its own temperature (and, with `noise_clamp` > 0, a truncated normal) and compares its EOS
+        logit with its own threshold; read by the kernels at run time, so captured steps pick it up (include/ptts.h)."""
+        clamp = 0.0 if noise_clamp is None else float(noise_clamp)
+        _lib.check(self.engine.lib.ptts_lm_state_set_row_sampling(self.handle, row, float(temp), clamp,
+                                                                  float(eos_threshold), self.engine._sp))
+
+    def clear_row_sampling(self, row: int):
+        """row `row` returns to the state's temperature (`set_noise`) and the step's EOS threshold"""
+        _lib.check(self.engine.lib.ptts_lm_state_clear_row_sampling(self.handle, row, self.engine._sp))
+
     def error(self) -> bool:
         """True after a cooperative kernel of this state gave up waiting for a peer workgroup"""
         r = self.engine.lib.ptts_lm_state_error(self.handle, self.engine._sp)

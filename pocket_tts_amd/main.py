@@ -1,18 +1,22 @@
-"""`generate` command with the reference's flags (pocket_tts/main.py:222-327) over the MI355X engine.
+"""The reference's commands (pocket_tts/main.py) over the MI355X engine.
 
     python -m pocket_tts_amd generate --config cfg.yaml --voice voice.safetensors --text "..." \
         --output-path out.wav
+    python -m pocket_tts_amd serve --config cfg.yaml --voices-dir voices/ --default-voice alba
+    python -m pocket_tts_amd export-voice prompt.wav voice.safetensors --config cfg.yaml
 
-Output: 24 kHz mono 16-bit WAV followed by 200 ms of silence (reference data/audio.py:69-72,99-107).
-`serve` / `export-voice` (HTTP server, voice encoding) are outside the hot-path scope of this build.
+`generate` writes 24 kHz mono 16-bit WAV followed by 200 ms of silence (reference data/audio.py:69-72,99-107).
+`serve` runs the HTTP server of `server.py` (`GET /health`, `POST /tts` streaming the same WAV bytes) on a continuous
+batcher, with per-request temperature, noise clamp and EOS threshold.  `export-voice` encodes an audio prompt (first 30 s)
+into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
 from __future__ import annotations
 
 import argparse
 import logging
+import struct
 import sys
-import wave
 
 logger = logging.getLogger("pocket_tts_amd")
 
@@ -20,26 +24,46 @@ DEFAULT_TEXT = ("Hello world. I am Kyutai's Pocket TTS. I'm fast enough to run o
                 "I hope you'll like me.")
 
 
+_STREAM_FRAMES = 1_000_000_000  # streaming: the length is not known up front, the header announces this many samples
+
+
+def _wav_header(n_samples: int, sample_rate: int) -> bytes:
+    """44-byte RIFF header of mono 16-bit PCM (the one `wave` writes)"""
+    data = 2 * n_samples
+    return struct.pack("<4sL4s4sLHHLLHH4sL", b"RIFF", 36 + data, b"WAVE", b"fmt ", 16, 1, 1, sample_rate, 2 * sample_rate,
+                       2, 16, b"data", data)
+
+
+def wav_stream_bytes(chunks, sample_rate: int):
+    """The bytes of a streamed WAV: the provisional header, each chunk's 16-bit frames as soon as it arrives, then 200 ms
+    of silence.  fp32 chunks are clamped and converted like data/audio.py:79; int16 chunks (the batcher's
+    `pcm_format="i16"`) are already converted."""
+    import torch
+
+    yield _wav_header(_STREAM_FRAMES, sample_rate)
+    for chunk in chunks:
+        if chunk.dtype != torch.int16:
+            chunk = (chunk.clamp(-1, 1) * 32767).short()
+        yield chunk.cpu().numpy().tobytes()
+    yield bytes(2 * int(sample_rate * 0.2))
+
+
 def write_wav_stream(path, chunks, sample_rate: int) -> int:
-    """fp32 chunks -> clamp, int16, raw frames; 200 ms of trailing silence.  Returns samples written."""
+    """fp32 chunks -> clamp, int16, raw frames; 200 ms of trailing silence.  Returns samples written.  A file gets the
+    real lengths patched into its header at the end; stdout keeps the provisional one."""
     out = sys.stdout.buffer if path == "-" else open(path, "wb")
     n = 0
     with out:
-        w = wave.open(out, "wb")
-        w.setnchannels(1)
-        w.setsampwidth(2)
-        w.setframerate(sample_rate)
-        w.setnframes(1_000_000_000)  # streaming: the length is not known up front
-        for chunk in chunks:
-            pcm = (chunk.clamp(-1, 1) * 32767).short().cpu().numpy()
-            w.writeframesraw(pcm.tobytes())
-            n += pcm.shape[0]
-        silence = int(sample_rate * 0.2)
-        w.writeframesraw(bytes(2 * silence))
-        if path == "-":
-            w._patchheader = lambda: None  # unseekable stream: keep the provisional header
-        w.close()
-    return n + silence
+        for b in wav_stream_bytes(chunks, sample_rate):
+            out.write(b)
+            n += len(b)
+        n = (n - 44) // 2
+        if path != "-":
+            out.seek(4)
+            out.write(struct.pack("<L", 36 + 2 * n))
+            out.seek(40)
+            out.write(struct.pack("<L", 2 * n))
+    return n
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -62,12 +86,70 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--quantize", action="store_true")
     g.add_argument("--codec-bf16", action="store_true",
                    help="bf16 weights + activations in the Mimi codec (fp32 accumulate; not in the reference, ~44 dB SNR)")
+
+    s = sub.add_parser("serve", help="Start the HTTP server (POST /tts streams a WAV)")
+    s.add_argument("--host", default="localhost", help="Host to bind to")
+    s.add_argument("--port", type=int, default=8000, help="Port to bind to")
+    s.add_argument("--language", default=None)
+    s.add_argument("--config", default=None, help="Path to a local model config .yaml")
+    s.add_argument("--quantize", action="store_true")
+    s.add_argument("--codec-bf16", action="store_true")
+    s.add_argument("--device", default="cuda:0")
+    s.add_argument("--temperature", type=float, default=0.7, help="Default temperature of a request")
+    s.add_argument("--lsd-decode-steps", type=int, default=1)
+    s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
+    s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
+    s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
+    s.add_argument("--capacity", type=int, default=1024,
+                   help="KV positions per slot: voice + text chunk + generated frames (a 30 s voice prompt is 376)")
+    s.add_argument("--voices-dir", default=None, help="Directory of <name>.safetensors voice states for voice_url=<name>")
+    s.add_argument("--default-voice", default=None, help="Voice name used when a request names none")
+    s.add_argument("-q", "--quiet", action="store_true", help="Disable logging output")
+
+    x = sub.add_parser("export-voice", help="Encode an audio prompt into a voice-state .safetensors file")
+    x.add_argument("audio_path", help="Audio prompt (WAV; the first 30 s are used)")
+    x.add_argument("export_path", help="Output .safetensors file")
+    x.add_argument("-q", "--quiet", action="store_true", help="Disable logging output")
+    x.add_argument("--language", default=None)
+    x.add_argument("--config", default=None, help="Path to a local model config .yaml")
+    x.add_argument("--device", default="cuda:0")
     return ap
+
+
+def serve_app(args) -> int:
+    import uvicorn
+
+    from .server import create_app
+    from .tts_model import TTSModel
+
+    model = TTSModel.load_model(language=args.language, config=args.config, temp=args.temperature,
+                                lsd_decode_steps=args.lsd_decode_steps, noise_clamp=args.noise_clamp,
+                                eos_threshold=args.eos_threshold, quantize=args.quantize, codec_bf16=args.codec_bf16,
+                                device=args.device)
+    # the model's noise clamp reaches every request as a per-request setting (server.py)
+    app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
+                     default_voice=args.default_voice)
+    uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
+    return 0
+
+
+def export_voice_app(args) -> int:
+    from .tts_model import TTSModel, export_model_state
+
+    model = TTSModel.load_model(language=args.language, config=args.config, device=args.device)
+    state = model.get_state_for_audio_prompt(args.audio_path, truncate=True)
+    export_model_state(state, args.export_path)
+    logger.info("Voice state written in %s", args.export_path)
+    return 0
 
 
 def cli_app(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.ERROR if args.quiet else logging.INFO)
+    if args.command == "serve":
+        return serve_app(args)
+    if args.command == "export-voice":
+        return export_voice_app(args)
     text = DEFAULT_TEXT if args.text is None else args.text
     if text == "-":
         text = sys.stdin.read()

@@ -1,0 +1,249 @@
+"""HTTP server on the continuous batcher: the reference's `pocket-tts serve` (`/health`, `POST /tts` streaming a WAV,
+pocket_tts/main.py:121-214) with every request decoded in one shared batch.
+
+`POST /tts` takes the reference's form fields - `text`, `voice_url` (here: the name of a voice state in the voices
+directory) or the file `voice_wav` - plus this server's optional per-request settings `temperature`, `noise_clamp`,
+`eos_threshold` and `frames_after_eos`.  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
+
+FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
+`urllib.parse` and the standard library's `email` header parser.
+"""
+
+from __future__ import annotations
+
+import email
+import math
+import os
+import re
+import tempfile
+import threading
+import urllib.parse
+from contextlib import asynccontextmanager
+from pathlib import Path
+
+from fastapi import FastAPI, Request
+from fastapi.responses import HTMLResponse, JSONResponse, StreamingResponse
+from starlette.concurrency import run_in_threadpool
+
+OFFLINE_PREFIXES = ("hf://", "http://", "https://")
+_VOICE_NAME = re.compile(r"[A-Za-z0-9_][A-Za-z0-9_.-]*")
+
+INDEX_HTML = """<!doctype html>
+<html><head><meta charset="utf-8"><title>Pocket TTS</title></head>
+<body>
+<h1>Pocket TTS</h1>
+<form action="/tts" method="post" enctype="multipart/form-data">
+<p><textarea name="text" rows="4" cols="60">Hello world.</textarea></p>
+<p>Voice name <input name="voice_url"> or WAV prompt <input type="file" name="voice_wav" accept=".wav"></p>
+<p><button type="submit">Speak</button></p>
+</form>
+</body></html>
+"""
+
+
+class FormError(ValueError):
+    """the request body is not a form this server can read (answered with 400)"""
+
+
+def _header_params(value: str) -> email.message.Message:
+    """a one-header message, so that `get_param` / `get_filename` parse the header's parameters"""
+    return email.message_from_string(f"Content-Type: {value}\n\n")
+
+
+def parse_form(content_type: str | None, body: bytes) -> tuple[dict, dict]:
+    """(fields, files) of an `application/x-www-form-urlencoded` or `multipart/form-data` body: fields maps a name to
+    its first value (str), files maps a name to (filename, bytes).  Raises FormError on anything else."""
+    ctype = (content_type or "").split(";", 1)[0].strip().lower()
+    if ctype == "application/x-www-form-urlencoded":
+        try:
+            text = body.decode("utf-8")
+            pairs = urllib.parse.parse_qsl(text, keep_blank_values=True, strict_parsing=bool(text), errors="strict")
+        except (UnicodeDecodeError, ValueError) as e:
+            raise FormError(f"malformed form body: {e}") from None
+        fields: dict = {}
+        for k, v in pairs:
+            fields.setdefault(k, v)
+        return fields, {}
+    if ctype == "multipart/form-data":
+        boundary = _header_params(content_type).get_param("boundary")
+        if not boundary or not isinstance(boundary, str):
+            raise FormError("multipart body without a boundary")
+        parts = body.split(b"--" + boundary.encode("latin-1"))
+        # preamble, the parts, then the close delimiter "--" (and an optional epilogue)
+        if len(parts) < 2 or not parts[-1].startswith(b"--"):
+            raise FormError("malformed multipart body: no closing boundary")
+        fields, files = {}, {}
+        for raw in parts[1:-1]:
+            head, sep, data = raw.partition(b"\r\n\r\n")
+            if not raw.startswith(b"\r\n") or not sep or not data.endswith(b"\r\n"):
+                raise FormError("malformed multipart body: a part without headers or line breaks")
+            data = data[:-2]
+            try:
+                hdrs = email.message_from_bytes(head[2:] + b"\r\n\r\n")
+            except Exception as e:  # noqa: BLE001  (the parser's errors are not one family)
+                raise FormError(f"malformed multipart part headers: {e}") from None
+            disp = hdrs.get("content-disposition")
+            if disp is None:
+                raise FormError("malformed multipart body: a part without Content-Disposition")
+            params = _header_params(disp)
+            name = params.get_param("name", header="content-type")
+            if not name or not isinstance(name, str):
+                raise FormError("malformed multipart body: a part without a name")
+            filename = params.get_param("filename", header="content-type")
+            if filename is not None:
+                files.setdefault(name, (str(filename), data))
+            else:
+                try:
+                    fields.setdefault(name, data.decode("utf-8"))
+                except UnicodeDecodeError:
+                    raise FormError(f"form field {name!r} is not UTF-8") from None
+        return fields, files
+    raise FormError("expected an application/x-www-form-urlencoded or multipart/form-data body")
+
+
+def parse_settings(fields: dict) -> dict:
+    """the optional per-request settings as `ContinuousBatcher.submit` keywords (absent or empty field: None)"""
+    out = {}
+    for name, lo, integer in (("temperature", 0.0, False), ("noise_clamp", 0.0, False), ("eos_threshold", None, False),
+                              ("frames_after_eos", 0, True)):
+        raw = fields.get(name)
+        if raw is None or raw.strip() == "":
+            out[name] = None
+            continue
+        try:
+            v = int(raw) if integer else float(raw)
+        except ValueError:
+            raise FormError(f"{name} must be {'an integer' if integer else 'a number'}, got {raw!r}") from None
+        if not math.isfinite(v) or (lo is not None and v < lo) or (integer and v > 1000):
+            raise FormError(f"{name} is out of range: {raw!r}")
+        out[name] = v
+    return out
+
+
+def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
+               batcher_factory=None):
+    """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
+    positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
+    once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
+    noise clamp.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    from .main import wav_stream_bytes
+
+    if batcher_factory is None:
+        from .batching import ContinuousBatcher
+
+        def batcher_factory(model, slots, capacity):
+            return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16")
+
+    voices_dir = Path(voices_dir) if voices_dir is not None else None
+    voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
+    voices_lock = threading.Lock()
+
+    @asynccontextmanager
+    async def lifespan(app):
+        import anyio.to_thread
+
+        # every streaming response waits for its frames on a worker thread: let all slots' streams (and as many queued
+        # requests) wait at once instead of capping them at anyio's default of 40
+        limiter = anyio.to_thread.current_default_thread_limiter()
+        limiter.total_tokens = max(limiter.total_tokens, 2 * slots + 8)
+        batcher = batcher_factory(model, slots, capacity)
+        batcher.start()
+        app.state.batcher = batcher
+        try:
+            yield
+        finally:
+            app.state.batcher = None
+            batcher.close()
+
+    app = FastAPI(title="Pocket TTS", lifespan=lifespan)
+    app.state.batcher = None
+
+    def load_voice(name: str) -> dict:
+        if name.startswith(OFFLINE_PREFIXES):
+            raise FormError(f"{name} needs a download; this build runs offline")
+        if name.endswith(".safetensors"):
+            name = name[: -len(".safetensors")]
+        path = voices_dir / f"{name}.safetensors" if voices_dir is not None else None
+        if not _VOICE_NAME.fullmatch(name) or path is None or not path.is_file():
+            raise FormError(f"unknown voice {name!r}")
+        with voices_lock:
+            if name not in voices:
+                voices[name] = model.get_state_for_audio_prompt(str(path))
+            return voices[name]
+
+    def encode_upload(filename: str, data: bytes, batcher) -> dict:
+        suffix = Path(filename).suffix or ".wav"
+        fd, path = tempfile.mkstemp(suffix=suffix)
+        try:
+            with os.fdopen(fd, "wb") as f:
+                f.write(data)
+            # the encoder runs on the engine the scheduler thread drives: between two of its iterations
+            return batcher.exclusive(model.get_state_for_audio_prompt, path, truncate=True)
+        except (OSError, EOFError, ImportError, ValueError) as e:
+            raise FormError(f"could not read the uploaded voice_wav: {e}") from None
+        except Exception as e:  # wave.Error and friends: an unreadable file is the client's error
+            if type(e).__module__ in ("wave", "struct", "numpy"):
+                raise FormError(f"could not read the uploaded voice_wav: {e}") from None
+            raise
+        finally:
+            os.unlink(path)
+
+    def bad(msg) -> JSONResponse:
+        return JSONResponse({"detail": str(msg)}, status_code=400)
+
+    @app.get("/", response_class=HTMLResponse)
+    async def index():
+        return INDEX_HTML
+
+    @app.get("/health")
+    async def health():
+        b = app.state.batcher
+        if b is None:
+            return JSONResponse({"status": "unhealthy", "error": "the batcher is not running"}, status_code=503)
+        if b.failed is not None:
+            return JSONResponse({"status": "unhealthy", "error": str(b.failed)}, status_code=503)
+        return {"status": "healthy"}
+
+    @app.post("/tts")
+    async def tts(request: Request):
+        batcher = app.state.batcher
+        if batcher is None:
+            return JSONResponse({"detail": "the batcher is not running"}, status_code=503)
+        try:
+            fields, files = parse_form(request.headers.get("content-type"), await request.body())
+            text = fields.get("text", "")
+            if not text.strip():
+                raise FormError("Text cannot be empty")
+            settings = parse_settings(fields)
+            voice_url = fields.get("voice_url") or None
+            upload = files.get("voice_wav")
+            if upload is not None and not upload[1]:
+                upload = None  # an empty file input (a browser form sends one when no file is chosen)
+            if voice_url is not None and upload is not None:
+                raise FormError("Cannot provide both voice_url and voice_wav")
+            if upload is not None:
+                state = await run_in_threadpool(encode_upload, upload[0], upload[1], batcher)
+            else:
+                if voice_url is None:
+                    if default_voice is None:
+                        raise FormError("no voice given (voice_url or voice_wav) and the server has no default voice")
+                    voice_url = default_voice
+                state = await run_in_threadpool(load_voice, voice_url)
+            fae = settings.pop("frames_after_eos")
+            if settings["noise_clamp"] is None and model.noise_clamp is not None:
+                settings["noise_clamp"] = model.noise_clamp
+            req = await run_in_threadpool(batcher.submit, state, text, fae, **settings)
+        except ValueError as e:  # FormError, and submit's own (empty text, capacity)
+            return bad(e)
+
+        import torch
+
+        def frames():  # every chunk that has arrived so far as one: one thread hop per batch of frames
+            for chunks in req.iter_batches():
+                yield chunks[0] if len(chunks) == 1 else torch.cat(chunks)
+
+        return StreamingResponse(wav_stream_bytes(frames(), model.sample_rate), media_type="audio/wav",
+                                 headers={"Content-Disposition": "attachment; filename=generated_speech.wav"})
+
+    return app
