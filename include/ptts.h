@@ -340,6 +340,36 @@ typedef struct ptts_gemm_case {
   int32_t cfg_used;                        /* out: the configuration that ran */
 } ptts_gemm_case;
 int ptts_debug_gemm(ptts_engine *e, ptts_gemm_case *c, void *stream);
+/* Test hook: ONE attention launch of the hot path (attn_kernel / attn_decode_kernel / attn_decode2_kernel /
+ * attn_cascade_kernel, + attn_combine_kernel when the keys are split) through the production dispatcher, on plain
+ * row-major device buffers.  Row b's queries sit at positions offset[b] .. offset[b] + Tq - 1; its key / value at
+ * position p is pk / pv[pre_id[b]][p] when p < pre_len[pre_id[b]] (a shared prefix), else k / v[b][p]:
+ *   y[b][t][h * 64 + d] = sum_p softmax_p(q[b][t][h] . key(p) / 8) value(p)[d],  over p <= offset[b] + t and, when ctx > 0,
+ *   offset[b] + t - p < ctx.
+ * The hook writes each row's keys into cache slots (ring > 0: slot p % ring), builds the prefix table over owner caches
+ * of layers 0 .. layer + 1 (the prefix in plane `layer`), and fills every slot a row must not read - and a guard of one
+ * key tile on both sides of each buffer - with poison_k / poison_v.  splits -1 = the production rule for the case's
+ * shape; kernel -1 = the dispatcher's choice, else an index into its table (ptts.hip kAttn).  Returns 0 when the kernel
+ * ran, 1 when the forced kernel does not support the case (nothing launched), < 0 on an error, e.g. a kernel that wrote
+ * past its output or partial buffer.  Queries the kernel leaves unwritten read back as NaN.  Synchronises `stream`. */
+typedef struct ptts_attn_case {
+  int32_t B, Tq, H, T;                     /* rows, queries per row, heads, positions per row in k / v */
+  int32_t cap, ring, ctx, splits, h16;     /* cache slots (% 16 == 0), ring (0: linear cache), window (0: none), key
+                                              splits (-1: production's), bf16 output (rounded, returned widened) */
+  int32_t layer, n_pre, pre_T, pre_cap;    /* prefix plane, prefix banks, positions per bank, owners' capacity (0: cap) */
+  int32_t cascade, kernel;                 /* engine option "prefix_cascade" value; kernel table index or -1 */
+  float poison_k, poison_v;
+  const float *q;                          /* [B][Tq][H][64] */
+  const float *k, *v;                      /* [B][T][H][64] */
+  const float *pk, *pv;                    /* [n_pre][pre_T][H][64] or null */
+  const int32_t *offset;                   /* host [B] */
+  const int32_t *pre_len, *pre_id;         /* host [n_pre] (<= offset of every row using it), host [B] (-1: none) */
+  float *y;                                /* out: [B][Tq][H * 64] */
+  char *label;                             /* optional out: the launch's profiler label */
+  int32_t label_cap;
+  int32_t kernel_used, splits_used;        /* out */
+} ptts_attn_case;
+int ptts_debug_attn(ptts_engine *e, ptts_attn_case *c, void *stream);
 /* Per-launch profiler (HIP events around every kernel launch on its own stream, tagged with call site,
  * kernel and algorithmic bytes / flops).  stop() writes text lines "site kernel count total_ms bytes flops"
  * to h_out and returns the length.  Never active inside a captured graph. */

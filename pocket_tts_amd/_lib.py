@@ -48,6 +48,17 @@ class PttsGemmCase(C.Structure):
     ]
 
 
+class PttsAttnCase(C.Structure):
+    """ptts_attn_case: one attention launch for the ptts_debug_attn test hook"""
+    _fields_ = [
+        *[(f, C.c_int32) for f in ("B", "Tq", "H", "T", "cap", "ring", "ctx", "splits", "h16", "layer", "n_pre", "pre_T",
+                                   "pre_cap", "cascade", "kernel")],
+        ("poison_k", C.c_float), ("poison_v", C.c_float),
+        *[(f, C.c_void_p) for f in ("q", "k", "v", "pk", "pv", "offset", "pre_len", "pre_id", "y", "label")],
+        ("label_cap", C.c_int32), ("kernel_used", C.c_int32), ("splits_used", C.c_int32),
+    ]
+
+
 # every symbol include/ptts.h declares: (restype, argtypes)
 _P = C.c_void_p
 PROTOTYPES = {
@@ -111,6 +122,7 @@ PROTOTYPES = {
     "ptts_debug_read": (C.c_int64, [_P, _P, C.c_int32, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), _P]),
     "ptts_debug_gemm": (C.c_int, [_P, C.POINTER(PttsGemmCase), _P]),
+    "ptts_debug_attn": (C.c_int, [_P, C.POINTER(PttsAttnCase), _P]),
     "ptts_lm_weight_bytes": (C.c_int64, [_P]),
     "ptts_mimi_weight_bytes": (C.c_int64, [_P]),
 }

@@ -910,21 +910,127 @@ static int attn_splits(int base, int max_tiles) {
   int s = std::max(1, cdiv(attn_wave_target(), std::max(1, base * nw)));
   return std::max(1, std::min(s, tiles));
 }
-// attn_cascade_kernel<R, PW, D, NS> shapes selectable with "prefix_cascade" / PTTS_CASCADE besides the default <4, 2, 3, 1>
-// (the parity tests run these; all shapes measured are in profiles/r03_experiments.txt: more waves per workgroup or a fourth
-// register tile lose beside the codec stream)
-#define CASC_SHAPES \
-  CASC(442, 4, 4, 2, 2) CASC(222, 2, 2, 2, 2) CASC(42, 4, 2, 2, 1) CASC(44, 4, 4, 2, 1) CASC(84, 8, 4, 2, 1) CASC(22, 2, 2, 2, 1)
-static void launch_attn(hipStream_t st, const AttnArgs &at, int BH) {
-  const dim3 grid(BH, at.QB, at.splits);
-  const int nw = attn_nw(BH * at.QB);
+// Every compiled attention instantiation: the dispatcher's table (ptts_debug_attn's `kernel` indexes it, tests/
+// test_gpu_attn_matrix.py mirrors it).  family 0 = attn_kernel<nw, depth>, 1 = attn_decode_kernel<nw>, 2 =
+// attn_decode2_kernel<nw, depth>, 3 = attn_cascade_kernel<R = nw, pw, depth, ns>; `code` = the "prefix_cascade" /
+// PTTS_CASCADE value that names a cascade shape (every shape besides the default <4, 2, 3, 1> is an A/B knob: all shapes
+// measured are in profiles/r03_experiments.txt, more waves per workgroup or a fourth register tile lose beside the codec stream)
+struct AttnKernelInfo { int family, nw, pw, depth, ns, code; const char *name; };
+enum {
+  AK_ATTN4, AK_ATTN2, AK_ATTN1, AK_ATTN1_D2, AK_DEC1, AK_DEC2_1_2, AK_DEC2_1_3, AK_DEC2_2_3, AK_DEC2_4_3, AK_DEC2_8_3,
+  AK_CASC, AK_CASC_442, AK_CASC_222, AK_CASC_42, AK_CASC_44, AK_CASC_84, AK_CASC_22, kNumAttn
+};
+static const AttnKernelInfo kAttn[kNumAttn] = {
+    {0, 4, 0, 3, 0, 0, "attn<4,3>"}, {0, 2, 0, 3, 0, 0, "attn<2,3>"}, {0, 1, 0, 3, 0, 0, "attn<1,3>"}, {0, 1, 0, 2, 0, 0, "attn<1,2>"},
+    {1, 1, 0, 3, 0, 0, "attn_decode<1>"}, {2, 1, 0, 2, 0, 0, "attn_decode2<1,2>"}, {2, 1, 0, 3, 0, 0, "attn_decode2<1,3>"},
+    {2, 2, 0, 3, 0, 0, "attn_decode2<2,3>"}, {2, 4, 0, 3, 0, 0, "attn_decode2<4,3>"}, {2, 8, 0, 3, 0, 0, "attn_decode2<8,3>"},
+    {3, 4, 2, 3, 1, 423, "attn_cascade<4,2,3,1>"}, {3, 4, 4, 2, 2, 442, "attn_cascade<4,4,2,2>"},
+    {3, 2, 2, 2, 2, 222, "attn_cascade<2,2,2,2>"}, {3, 4, 2, 2, 1, 42, "attn_cascade<4,2,2,1>"},
+    {3, 4, 4, 2, 1, 44, "attn_cascade<4,4,2,1>"}, {3, 8, 4, 2, 1, 84, "attn_cascade<8,4,2,1>"},
+    {3, 2, 2, 2, 1, 22, "attn_cascade<2,2,2,1>"},
+};
+
+// What each kernel supports (production and ptts_debug_attn both ask this before a launch):
+//   every kernel: Tq >= 1 queries in QB = ceil(Tq / 16) blocks, a cache of cap % 16 == 0 slots per (sequence, head), at
+//   least one split (a partial buffer when more);
+//   a ring (slot = position % ring) holds whole tiles (ring % 16 == 0, ring <= cap), has a window (ctx > 0) and keeps
+//   every key a query block attends (ring >= ctx + Tq - 1); shared prefixes (KvPrefix) are for linear caches only;
+//   decode and cascade kernels: one query per sequence, fp32 output (they ignore h16);
+//   cascade: additionally one split, no ring, no window and a prefix table.
+static bool attn_valid(int k, const AttnArgs &a) {
+  if (k < 0 || k >= kNumAttn) return false;
+  if (a.H < 1 || a.Tq < 1 || a.QB != cdiv(a.Tq, 16) || a.cap < 16 || a.cap % 16 || a.splits < 1 || a.nseq < 1) return false;
+  if (a.splits > 1 && !a.part) return false;
+  if (a.ring && (a.ring % 16 || a.ring > a.cap || a.ctx <= 0 || a.ring < a.ctx + a.Tq - 1 || a.pre)) return false;
+  const AttnKernelInfo &K = kAttn[k];
+  if (K.family != 0 && (a.Tq != 1 || a.h16)) return false;
+  if (K.family == 3 && (a.splits != 1 || a.ring || a.ctx > 0 || !a.pre)) return false;
+  return true;
+}
+
+// The production choice for a launch of BH = nseq * H (sequence, head) pairs; `cascade` = the engine's "prefix_cascade"
+// value when the sequences may share prefixes (0: never the cascade kernel)
+static int choose_attn(const AttnArgs &a, int BH, int cascade) {
+  if (a.Tq == 1 && cascade && a.pre && a.splits == 1 && !a.ring && a.ctx <= 0 && a.nseq >= 16) {
+    // sequences cloned from one voice: prefix keys as MFMA tiles shared by R sequences, private keys per sequence,
+    // merged in LDS.  Tile shape: tools/ab.sh env PTTS_CASCADE
+    for (int k = AK_CASC + 1; k < kNumAttn; ++k)
+      if (kAttn[k].code == cascade) return k;
+    return AK_CASC;
+  }
+  if (a.Tq == 1) {
+    // one query: vector ALU + wave reductions.  The keys of a (sequence, head) are split over the nw waves of ONE
+    // workgroup and merged in LDS, so small batches reach ~1024 waves without partial buffers or a combine launch.
+    // The row-state kernel (no cross-row traffic in its loop).  Small batches: three register tiles (6.0 vs 7.2 us per
+    // layer at batch 1, 221 keys).  >= 1024 (sequence, head) pairs: TWO register tiles - alone it streams at the rate of
+    // the first kernel (attn_decode_kernel, 188 VGPRs, still selectable with PTTS_ATTN_V=1), but at ~110 registers per wave
+    // it leaves the codec stream its occupancy: 0.904 -> 0.877 ms per pipelined step at batch 64 (tools/ab.sh env
+    // PTTS_ATTN_V; three tiles: 0.881)
+    const int nw = decode_attn_waves(BH);
+    if (nw >= 8) return AK_DEC2_8_3;
+    if (nw == 4) return AK_DEC2_4_3;
+    if (nw == 2) return AK_DEC2_2_3;
+    static const int v = [] { const char *e = getenv("PTTS_ATTN_V"); return e ? atoi(e) : 2; }();  // A/B knob
+    return v == 1 ? AK_DEC1 : v == 3 ? AK_DEC2_1_3 : AK_DEC2_1_2;
+  }
+  const int nw = attn_nw(BH * a.QB);
   // large launches (one wave per workgroup) keep two register tiles instead of three: 32 registers less per wave, 0.854 ->
   // 0.850 ms per pipelined step at batch 64 (tools/ab.sh env PTTS_ATTN_DEPTH)
   static const int depth = [] { const char *v = getenv("PTTS_ATTN_DEPTH"); return v ? atoi(v) : 2; }();  // A/B knob
-  if (nw == 4) attn_kernel<4><<<grid, 256, 0, st>>>(at);
-  else if (nw == 2) attn_kernel<2><<<grid, 128, 0, st>>>(at);
-  else if (depth == 2) attn_kernel<1, 2><<<grid, 64, 0, st>>>(at);
-  else attn_kernel<1><<<grid, 64, 0, st>>>(at);
+  if (nw == 4) return AK_ATTN4;
+  if (nw == 2) return AK_ATTN2;
+  return depth == 2 ? AK_ATTN1_D2 : AK_ATTN1;
+}
+
+// Launches kernel `k` (admitted by attn_valid) for BH (sequence, head) pairs, bracketed by the profiler; label = kernel
+// family + "@<work-items>" (what rocprofv3 reports as Grid_Size)
+static void launch_attn_kernel(hipStream_t st, const AttnArgs &at, int BH, int k, double bytes, double flops, std::string *label) {
+  const AttnKernelInfo &K = kAttn[k];
+  const long wgs = K.family == 3 ? (long)cdiv(at.nseq, K.nw) * at.H : K.family == 0 ? (long)BH * at.QB * at.splits : (long)BH * at.splits;
+  const int threads = 64 * (K.family == 3 ? K.nw * K.ns + K.pw : K.nw);
+  const std::string name = std::string(K.family == 0 ? "attn" : K.family == 3 ? "attn_cascade" : "attn_decode") + "@" + std::to_string(wgs * threads);
+  if (label) *label = name;
+  ProfScope ps(st, name, bytes, flops);
+  const dim3 grid(BH, at.QB, at.splits), dgrid(BH, 1, at.splits);
+  switch (k) {
+    case AK_ATTN4: attn_kernel<4><<<grid, threads, 0, st>>>(at); break;
+    case AK_ATTN2: attn_kernel<2><<<grid, threads, 0, st>>>(at); break;
+    case AK_ATTN1: attn_kernel<1><<<grid, threads, 0, st>>>(at); break;
+    case AK_ATTN1_D2: attn_kernel<1, 2><<<grid, threads, 0, st>>>(at); break;
+    case AK_DEC1: attn_decode_kernel<1><<<dgrid, threads, 0, st>>>(at); break;
+    case AK_DEC2_1_2: attn_decode2_kernel<1, 2><<<dgrid, threads, 0, st>>>(at); break;
+    case AK_DEC2_1_3: attn_decode2_kernel<1, 3><<<dgrid, threads, 0, st>>>(at); break;
+    case AK_DEC2_2_3: attn_decode2_kernel<2, 3><<<dgrid, threads, 0, st>>>(at); break;
+    case AK_DEC2_4_3: attn_decode2_kernel<4, 3><<<dgrid, threads, 0, st>>>(at); break;
+    case AK_DEC2_8_3: attn_decode2_kernel<8, 3><<<dgrid, threads, 0, st>>>(at); break;
+    case AK_CASC: attn_cascade_kernel<4, 2, 3, 1><<<wgs, threads, 0, st>>>(at); break;
+    case AK_CASC_442: attn_cascade_kernel<4, 4, 2, 2><<<wgs, threads, 0, st>>>(at); break;
+    case AK_CASC_222: attn_cascade_kernel<2, 2, 2, 2><<<wgs, threads, 0, st>>>(at); break;
+    case AK_CASC_42: attn_cascade_kernel<4, 2, 2, 1><<<wgs, threads, 0, st>>>(at); break;
+    case AK_CASC_44: attn_cascade_kernel<4, 4, 2, 1><<<wgs, threads, 0, st>>>(at); break;
+    case AK_CASC_84: attn_cascade_kernel<8, 4, 2, 1><<<wgs, threads, 0, st>>>(at); break;
+    case AK_CASC_22: attn_cascade_kernel<2, 2, 2, 1><<<wgs, threads, 0, st>>>(at); break;
+  }
+}
+
+// The one attention launch site of the library: kernel `kernel` (-1: choose_attn's choice) on BH (sequence, head) pairs,
+// then the combine kernel when the keys are split.  bytes / flops: the profiler's figures for the attention launch.
+// Returns the kernel launched, or -1 when attn_valid does not admit it (nothing launched, the entry point reports it).
+static int launch_attention(hipStream_t st, const AttnArgs &at, int BH, int cascade, int kernel, double bytes, double flops,
+                            std::string *label = nullptr) {
+  const int k = kernel >= 0 ? kernel : choose_attn(at, BH, cascade);
+  if (!attn_valid(k, at)) {
+    if (g_launch_err.empty())
+      g_launch_err = std::string("no attention kernel ") + (k >= 0 && k < kNumAttn ? kAttn[k].name : std::to_string(k)) + " for Tq " +
+                     std::to_string(at.Tq) + ", ring " + std::to_string(at.ring) + ", splits " + std::to_string(at.splits) + " (site " + g_site + ")";
+    return -1;
+  }
+  launch_attn_kernel(st, at, BH, k, bytes, flops, label);
+  if (at.splits > 1) {
+    ProfScope ps(st, "attn_combine", (double)BH * at.QB * at.splits * 16 * ATT_PSTRIDE * 4, 0);
+    attn_combine_kernel<<<dim3(BH, at.QB), 256, 0, st>>>(at);
+  }
+  return k;
 }
 
 // One pre-LN transformer layer on M rows (reference mimi_transformer.py:39-54, transformer.py:135-158)
@@ -962,58 +1068,13 @@ static void run_tr_layer(hipStream_t st, const TrLayer &T, const TrCtx &c) {
   at.cap = c.cap; at.ring = c.ring; at.ctx = c.ctx; at.splits = c.splits; at.part = c.part; at.Y = c.ao; at.YF = DF; at.h16 = 0;
   at.pre = c.pre; at.layer = c.layer;
   const int BH = (c.M / c.Tq) * c.H;
+  at.nseq = BH / c.H;
   SITE(s3.c_str());
-  {
-    // K and V rows of every attended key once per head + q in + o out
-    const int nseq = BH / c.H;
-    at.nseq = nseq;
-    const bool casc = c.Tq == 1 && c.cascade && at.pre && c.splits == 1 && !c.ring && c.ctx <= 0 && nseq >= 16;
-    int casc_r = 4, casc_threads = 64 * 6;  // the default shape; others are A/B knobs
-    switch (c.cascade) {
-#define CASC(code, R, PW, D, NS) case code: casc_r = R; casc_threads = 64 * (R * NS + PW); break;
-      CASC_SHAPES
-#undef CASC
-    }
-    // bytes: SURVEY 8d's per-sequence figure (every sequence reads all of its keys), also for the cascade kernel, which
-    // fetches a shared prefix once per R sequences - bench.py reports the unique bytes next to it
-    ProfScope ps(st, casc ? "attn_cascade@" + std::to_string((long)cdiv(nseq, casc_r) * c.H * casc_threads)
-                          : std::string(c.Tq == 1 ? "attn_decode" : "attn") + "@" + std::to_string((long)BH * c.QB * c.splits * 64 * (c.Tq == 1 ? decode_attn_waves(BH) : attn_nw(BH * c.QB))),
-                 c.kv_keys * c.H * 64 * 4 * 2 + 8.0 * c.M * c.D, 4.0 * c.kv_keys * c.H * 64 * std::min(c.Tq, 16));
-    if (c.Tq == 1) {
-      // one query: vector ALU + wave reductions.  The keys of a (sequence, head) are split over the nw waves of ONE
-      // workgroup and merged in LDS, so small batches reach ~1024 waves without partial buffers or a combine launch
-      const int nw = decode_attn_waves(BH);
-      if (casc) {
-        // sequences cloned from one voice: prefix keys as MFMA tiles shared by R sequences, private keys per sequence,
-        // merged in LDS (attn_cascade_kernel).  Tile shape: tools/ab.sh env PTTS_CASCADE
-        switch (c.cascade) {
-#define CASC(code, R, PW, D, NS) case code: attn_cascade_kernel<R, PW, D, NS><<<cdiv(nseq, R) * c.H, 64 * (R * NS + PW), 0, st>>>(at); break;
-          CASC_SHAPES
-          default: attn_cascade_kernel<4, 2, 3, 1><<<cdiv(nseq, 4) * c.H, 64 * 6, 0, st>>>(at); break;
-#undef CASC
-        }
-      } else
-      // the row-state kernel (no cross-row traffic in its loop).  Small batches: three register tiles (6.0 vs 7.2 us per
-      // layer at batch 1, 221 keys).  >= 1024 (sequence, head) pairs: TWO register tiles - alone it streams at the rate of
-      // the first kernel (attn_decode_kernel, 188 VGPRs, still selectable with PTTS_ATTN_V=1), but at ~110 registers per wave
-      // it leaves the codec stream its occupancy: 0.904 -> 0.877 ms per pipelined step at batch 64 (tools/ab.sh env
-      // PTTS_ATTN_V; three tiles: 0.881)
-      if (nw >= 8) attn_decode2_kernel<8, 3><<<dim3(BH, 1, c.splits), 512, 0, st>>>(at);
-      else if (nw == 4) attn_decode2_kernel<4, 3><<<dim3(BH, 1, c.splits), 256, 0, st>>>(at);
-      else if (nw == 2) attn_decode2_kernel<2, 3><<<dim3(BH, 1, c.splits), 128, 0, st>>>(at);
-      else {
-        static const int v = [] { const char *e = getenv("PTTS_ATTN_V"); return e ? atoi(e) : 2; }();  // A/B knob
-        if (v == 1) attn_decode_kernel<1><<<dim3(BH, 1, c.splits), 64, 0, st>>>(at);
-        else if (v == 3) attn_decode2_kernel<1, 3><<<dim3(BH, 1, c.splits), 64, 0, st>>>(at);
-        else attn_decode2_kernel<1, 2><<<dim3(BH, 1, c.splits), 64, 0, st>>>(at);
-      }
-    }
-    else launch_attn(st, at, BH);
-  }
-  if (c.splits > 1) {
-    ProfScope ps(st, "attn_combine", (double)BH * c.QB * c.splits * 16 * ATT_PSTRIDE * 4, 0);
-    attn_combine_kernel<<<dim3(BH, c.QB), 256, 0, st>>>(at);
-  }
+  // K and V rows of every attended key once per head + q in + o out.  bytes: SURVEY 8d's per-sequence figure (every
+  // sequence reads all of its keys), also for the cascade kernel, which fetches a shared prefix once per R sequences -
+  // bench.py reports the unique bytes next to it
+  launch_attention(st, at, BH, c.cascade, -1, c.kv_keys * c.H * 64 * 4 * 2 + 8.0 * c.M * c.D,
+                   4.0 * c.kv_keys * c.H * 64 * std::min(c.Tq, 16));
   SITE(s4.c_str());
   a = mk_gemm(T.out, c.ao, DF, c.MT, c.M);
   a.epi = EPI_RES; a.R = c.x_in; a.RF = DF; a.Y = c.x; a.YF = DF; a.ls = T.ls1;
@@ -2522,15 +2583,11 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     at.cap = e->ring; at.ring = e->ring; at.ctx = c.m_context; at.splits = s->splits; at.part = s->part; at.Y = s->ao; at.YF = CB;
     at.h16 = 1;
     const int BH = B * c.m_heads;
+    at.nseq = B;
     SITE("mimi.attn");
     {
       const double keys = (double)B * std::min(e->ring, (s->h_frame + 1) * st16);
-      ProfScope ps(st, "attn@" + std::to_string((long)BH * s->splits * 64 * attn_nw(BH)), keys * c.m_heads * 64 * 4 * 2 + 6.0 * M16 * C, 4.0 * keys * c.m_heads * 64 * 16);
-      launch_attn(st, at, BH);
-    }
-    if (s->splits > 1) {
-      ProfScope ps(st, "attn_combine", (double)BH * s->splits * 16 * ATT_PSTRIDE * 4, 0);
-      attn_combine_kernel<<<dim3(BH, 1), 256, 0, st>>>(at);
+      launch_attention(st, at, BH, 0, -1, keys * c.m_heads * 64 * 4 * 2 + 6.0 * M16 * C, 4.0 * keys * c.m_heads * 64 * 16);
     }
     SITE("mimi.out");
     a = mk_gemm(T.out, s->ao, CB, MT16, M16);
@@ -3530,6 +3587,222 @@ extern "C" int ptts_debug_gemm(ptts_engine *e, ptts_gemm_case *c, void *stream) 
   scr.stream = st;
   scr.device = e->device;
   const int rc = debug_gemm(e, c, st, scr);
+  (void)hipStreamSynchronize(st);
+  for (void *p : scr.allocs) (void)hipFree(p);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ptts_debug_attn (test hook, include/ptts.h): one attention launch (+ combine) through launch_attention, between plain
+// row-major buffers and the kernels' Q block / cache / FM layouts.  Every slot the case must not read holds the case's
+// poison, and every buffer has a poisoned guard of one key tile (1024 floats) on both sides.
+
+static constexpr long kAttnGuard = 16 * 64;
+
+// q [B][Tq][H][64] -> Q blocks [B * H][QB][4][64 lanes][4]: lane c + 16 g of fragment df holds query 16 qb + c, d = 16 df
+// + 4 g + j (queries >= Tq of the last block hold poison)
+static __global__ void dbg_attn_q_kernel(const float *q, float *Q, int B, int Tq, int H, int QB, float poison) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * H * QB * 1024) return;
+  const int j = i & 3, lane = (i >> 2) & 63, df = (i >> 8) & 3;
+  const long r = i >> 10;
+  const int qb = r % QB, bh = r / QB, b = bh / H, h = bh - b * H;
+  const int t = 16 * qb + (lane & 15), d = 16 * df + 4 * (lane >> 4) + j;
+  Q[i] = t < Tq ? q[(((size_t)b * Tq + t) * H + h) * 64 + d] : poison;
+}
+
+// the position whose key a row's cache slot holds when the row's queries are at off .. off + Tq - 1, or -1 (poison):
+// ring slots hold the newest position of their class below off + Tq; keys before every query's window, past the last
+// query, and under a borrowed prefix tile (positions < 16 * (len / 16)) are never read
+static __device__ int dbg_attn_slot_pos(int s, int off, int Tq, int ring, int ctx, int len) {
+  const int top = off + Tq - 1;
+  int p = s;
+  if (ring) {
+    if (s >= ring) return -1;
+    p = top - (((top - s) % ring) + ring) % ring;
+  }
+  if (p < 0 || p > top || (ctx > 0 && p < off - ctx + 1) || p < 16 * (len >> 4)) return -1;
+  return p;
+}
+// K and V caches [B][H][cap][64] of the rows (one thread per float)
+static __global__ void dbg_attn_cache_kernel(const float *k, const float *v, const float *pk, const float *pv, float *Kc,
+                                             float *Vc, const int *offset, const int *pre_len, const int *pre_id, int B,
+                                             int T, int pre_T, int H, int cap, int Tq, int ring, int ctx, float poison_k,
+                                             float poison_v) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * H * cap * 64) return;
+  const int d = i & 63;
+  const long r = i >> 6;
+  const int s = r % cap, bh = r / cap, b = bh / H, h = bh - b * H;
+  const int id = pre_id ? pre_id[b] : -1, len = id >= 0 ? pre_len[id] : 0;
+  const int p = dbg_attn_slot_pos(s, offset[b], Tq, ring, ctx, len);
+  if (p < 0) {
+    Kc[i] = poison_k;
+    Vc[i] = poison_v;
+  } else if (p < len) {  // the part of the prefix's last, partial tile the row holds itself
+    Kc[i] = pk[(((size_t)id * pre_T + p) * H + h) * 64 + d];
+    Vc[i] = pv[(((size_t)id * pre_T + p) * H + h) * 64 + d];
+  } else {
+    Kc[i] = k[(((size_t)b * T + p) * H + h) * 64 + d];
+    Vc[i] = v[(((size_t)b * T + p) * H + h) * 64 + d];
+  }
+}
+// the prefix owners' caches: bank `id` = [L][2][1][H][pcap][64] at bank + id * bstride, layer `layer` positions < len
+// from pk / pv, every other float poison (K planes poison_k, V planes poison_v)
+static __global__ void dbg_attn_owner_kernel(const float *pk, const float *pv, float *bank, long bstride, const int *pre_len,
+                                             int nbank, int L, int layer, int H, int pcap, int pre_T, float poison_k,
+                                             float poison_v) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = (long)L * 2 * H * pcap * 64;
+  if (i >= nbank * per) return;
+  const int id = i / per;
+  const long e = i - id * per;
+  const int d = e & 63;
+  const long r = e >> 6;
+  const int s = r % pcap, pl = r / pcap, h = pl % H, which = (pl / H) & 1, l = pl / (2 * H);
+  float x = which ? poison_v : poison_k;
+  if (l == layer && s < pre_len[id]) x = (which ? pv : pk)[(((size_t)id * pre_T + s) * H + h) * 64 + d];
+  bank[id * bstride + kAttnGuard + e] = x;
+}
+// FMH (bf16, KB 32-column blocks per row tile) -> [M][N] f32
+static __global__ void dbg_from_fmh_kernel(const __bf16 *src, float *dst, int M, int N, int KB) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)M * N) return;
+  const int m = i / N, n = i - (long)m * N;
+  dst[i] = (float)src[fmh_off(m, n & ~3, KB) + (n & 3)];
+}
+
+static int debug_attn(ptts_engine *e, ptts_attn_case *c, hipStream_t st, ptts_engine &scr) {
+  (void)e;
+  const int B = c->B, Tq = c->Tq, H = c->H, T = c->T, cap = c->cap, ring = c->ring, ctx = c->ctx, NB = c->n_pre;
+  const int pcap = c->pre_cap > 0 ? c->pre_cap : cap;
+  c->kernel_used = -1;
+  c->splits_used = 0;
+  if (!c->q || !c->k || !c->v || !c->y || !c->offset) return fail(-1, "debug_attn: q, k, v, offset and y are required");
+  if (B < 1 || Tq < 1 || H < 1 || T < Tq || cap < 16 || c->layer < 0 || NB < 0 || c->splits < -1 || c->splits == 0 ||
+      c->kernel < -1 || c->kernel >= kNumAttn || (c->h16 != 0 && c->h16 != 1))
+    return fail(-1, "debug_attn: bad shape or enumeration");
+  if (NB > 0 && (!c->pk || !c->pv || !c->pre_len || !c->pre_id || c->pre_T < 1 || pcap % 16))
+    return fail(-1, "debug_attn: prefixes need pk, pv, pre_len, pre_id, pre_T and a capacity % 16 == 0");
+  for (int j = 0; j < NB; ++j)
+    if (c->pre_len[j] < 0 || c->pre_len[j] > c->pre_T || c->pre_len[j] > pcap) return fail(-1, "debug_attn: prefix length out of range");
+  for (int b = 0; b < B; ++b) {
+    const int off = c->offset[b];
+    if (off < 0 || off + Tq > T || (!ring && off + Tq > cap)) return fail(-1, "debug_attn: a row's queries lie outside k / v or its cache");
+    if (NB > 0 && (c->pre_id[b] < -1 || c->pre_id[b] >= NB || (c->pre_id[b] >= 0 && c->pre_len[c->pre_id[b]] > off)))
+      return fail(-1, "debug_attn: a row's prefix is unknown or longer than its first query's position");
+  }
+  const int QB = cdiv(Tq, 16), BH = B * H, M = B * Tq, MT = cdiv(M, 16);
+  int splits = c->splits;
+  if (splits < 0) {  // the production rule of the launch shape the case has
+    if (Tq == 1 && !ring) splits = 1;                                                   // FlowLM decode step
+    else if (ring) splits = attn_splits(BH, ring / 16);                                 // codec frame (the state's splits)
+    else if (ctx > 0) splits = attn_splits(BH * QB, std::min(QB, cdiv(ctx, 16) + 2));   // encoder transformer
+    else splits = attn_splits(BH * QB, cdiv(cap, 16));                                  // FlowLM prefill
+  }
+  const long G = kAttnGuard;
+  auto poisoned = [&](long n, float val, float **out) -> int {  // n floats between two guards, all `val`
+    CHK(dallocT(&scr, out, (size_t)(n + 2 * G)));
+    fill_kernel<<<cdiv(n + 2 * G, 256), 256, 0, st>>>(*out, n + 2 * G, val);
+    *out += G;
+    return 0;
+  };
+  auto patterned = [&](long n, unsigned inner, float **out) -> int {  // guards kDbgGuard, inside `inner`
+    CHK(dallocT(&scr, out, (size_t)(n + 2 * G)));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)*out, (int)kDbgGuard, G, st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(*out + G), (int)inner, n, st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(*out + G + n), (int)kDbgGuard, G, st));
+    *out += G;
+    return 0;
+  };
+  int *d_ints = nullptr;  // offset [B], pre_id [B], pre_len [NB]
+  CHK(dallocT(&scr, &d_ints, (size_t)2 * B + NB + 1));
+  HIPCHK(hipMemcpyAsync(d_ints, c->offset, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  if (NB > 0) {
+    HIPCHK(hipMemcpyAsync(d_ints + B, c->pre_id, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ints + 2 * B, c->pre_len, (size_t)NB * 4, hipMemcpyHostToDevice, st));
+  }
+  float *Q, *Kc, *Vc, *Y, *part = nullptr;
+  const long nq = (long)BH * QB * 1024, nkv = (long)BH * cap * 64;
+  CHK(poisoned(nq, c->poison_k, &Q));
+  dbg_attn_q_kernel<<<cdiv(nq, 256), 256, 0, st>>>(c->q, Q, B, Tq, H, QB, c->poison_k);
+  CHK(poisoned(nkv, c->poison_k, &Kc));
+  CHK(poisoned(nkv, c->poison_v, &Vc));
+  dbg_attn_cache_kernel<<<cdiv(nkv, 256), 256, 0, st>>>(c->k, c->v, c->pk, c->pv, Kc, Vc, d_ints, NB > 0 ? d_ints + 2 * B : nullptr,
+                                                         NB > 0 ? d_ints + B : nullptr, B, T, c->pre_T, H, cap, Tq, ring, ctx,
+                                                         c->poison_k, c->poison_v);
+  KvPrefix *d_pre = nullptr;
+  if (NB > 0) {
+    // owners: one allocation, bank id at id * bstride, each bank between guards of poison; layers 0 .. layer + 1
+    const int L = c->layer + 2;
+    const long per = (long)L * 2 * H * pcap * 64, bstride = per + 2 * G;
+    float *bank = nullptr;
+    CHK(dallocT(&scr, &bank, (size_t)NB * bstride));
+    fill_kernel<<<cdiv(NB * bstride, 256), 256, 0, st>>>(bank, NB * bstride, c->poison_k);
+    dbg_attn_owner_kernel<<<cdiv(NB * per, 256), 256, 0, st>>>(c->pk, c->pv, bank, bstride, d_ints + 2 * B, NB, L, c->layer, H,
+                                                               pcap, c->pre_T, c->poison_k, c->poison_v);
+    std::vector<KvPrefix> h_pre(B, KvPrefix{nullptr, 0, 0});
+    for (int b = 0; b < B; ++b)
+      if (c->pre_id[b] >= 0) h_pre[b] = KvPrefix{bank + c->pre_id[b] * bstride + G, pcap, c->pre_len[c->pre_id[b]]};
+    CHK(dallocT(&scr, &d_pre, (size_t)B));
+    HIPCHK(hipMemcpyAsync(d_pre, h_pre.data(), (size_t)B * sizeof(KvPrefix), hipMemcpyHostToDevice, st));
+  }
+  // output: FM (fp32, 4 H fragments per row tile) or FMH (bf16, 2 H blocks), NaN-filled between guards
+  const int YF = c->h16 ? 2 * H : 4 * H;
+  const long ny = (long)MT * YF * 256;  // floats (an FMH block of 32 columns holds 512 bf16)
+  CHK(patterned(ny, c->h16 ? 0x7fc07fc0u : kDbgUnwritten, &Y));
+  const long npart = (long)BH * QB * splits * 16 * ATT_PSTRIDE;
+  if (splits > 1) CHK(patterned(npart, kDbgUnwritten, &part));
+
+  AttnArgs at;
+  at.Q = Q; at.Kc = Kc; at.Vc = Vc; at.pre = d_pre; at.layer = c->layer; at.offset = d_ints;
+  at.H = H; at.Tq = Tq; at.QB = QB; at.cap = cap; at.ring = ring; at.ctx = ctx; at.splits = splits;
+  at.part = part; at.Y = Y; at.YF = YF; at.h16 = c->h16; at.nseq = B;
+  int k = c->kernel >= 0 ? c->kernel : choose_attn(at, BH, c->cascade);
+  if (!attn_valid(k, at)) {
+    HIPCHK(hipStreamSynchronize(st));
+    if (c->kernel >= 0) return 1;
+    return fail(-1, std::string("debug_attn: the dispatcher chose ") + kAttn[k].name + ", which attn_valid rejects");
+  }
+  std::string label;
+  k = launch_attention(st, at, BH, c->cascade, k, 0, 0, &label);
+  LAUNCHCHK();
+  c->kernel_used = k;
+  c->splits_used = splits;
+  if (c->label && c->label_cap > 0) {
+    const size_t n = std::min<size_t>(label.size(), (size_t)c->label_cap - 1);
+    memcpy(c->label, label.data(), n);
+    c->label[n] = 0;
+  }
+  int *bad = nullptr;
+  CHK(dallocT(&scr, &bad, 1));
+  HIPCHK(hipMemsetAsync(bad, 0, 4, st));
+  for (const float *g : {Y - G, Y + ny})
+    dbg_guard_kernel<<<cdiv(G, 256), 256, 0, st>>>((const unsigned *)g, G, kDbgGuard, bad);
+  if (part)
+    for (const float *g : {part - G, part + npart})
+      dbg_guard_kernel<<<cdiv(G, 256), 256, 0, st>>>((const unsigned *)g, G, kDbgGuard, bad);
+  if (c->h16) dbg_from_fmh_kernel<<<cdiv((long)M * H * 64, 256), 256, 0, st>>>((const __bf16 *)Y, c->y, M, H * 64, YF);
+  else dbg_from_fm_kernel<<<cdiv((long)M * H * 64, 256), 256, 0, st>>>(Y, c->y, M, H * 64, YF);
+  LAUNCHCHK();
+  int h_bad = 0;
+  HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (h_bad) return fail(-6, "debug_attn: " + label + " wrote past its output or partial buffer");
+  return 0;
+}
+
+extern "C" int ptts_debug_attn(ptts_engine *e, ptts_attn_case *c, void *stream) {
+  if (!e || !c) return fail(-1, "debug_attn: null argument");
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  bind_engine(e);
+  hipStream_t st = S(e, stream);
+  AllocScope as(st);
+  ptts_engine scr;  // owns the case's buffers, freed here whatever the outcome
+  scr.stream = st;
+  scr.device = e->device;
+  const int rc = debug_attn(e, c, st, scr);
   (void)hipStreamSynchronize(st);
   for (void *p : scr.allocs) (void)hipFree(p);
   return rc;

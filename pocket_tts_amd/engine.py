@@ -562,6 +562,58 @@ class Engine:
         out["cfg"] = c.cfg_used
         return out
 
+    _ATTN_INTS = ("cap", "ring", "ctx", "splits", "h16", "layer", "pre_cap", "cascade", "kernel")
+
+    def debug_attn(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, offset, *, pk=None, pv=None, pre_len=None,
+                   pre_id=None, poison_k: float = 0.0, poison_v: float = 1e6, **kw):
+        """Test hook: one attention launch through the production dispatcher (ptts_debug_attn in include/ptts.h).
+        q [B][Tq][H][64], k / v [B][T][H][64], offset [B] (position of each row's first query); optional prefixes: pk / pv
+        [n_pre][pre_T][H][64], pre_len [n_pre], pre_id [B] (-1: none).  Keyword arguments: the case's integer fields
+        (cap defaults to T rounded up to 16, splits and kernel to -1).  Returns None when the forced kernel does not
+        support the case, else a dict with y [B][Tq][H * 64] (f32; bf16 output widened), the label, the kernel table
+        index and the splits used."""
+        B, Tq, H, _ = q.shape
+        T = k.shape[1]
+        c = _lib.PttsAttnCase()
+        c.B, c.Tq, c.H, c.T = B, Tq, H, T
+        c.cap, c.splits, c.kernel, c.cascade = (T + 15) // 16 * 16, -1, -1, 0
+        for key in self._ATTN_INTS:
+            if key in kw:
+                setattr(c, key, int(kw[key]))
+        c.poison_k, c.poison_v = float(poison_k), float(poison_v)
+        keep = {}
+
+        def dev(t):
+            t = t.to(self.device, torch.float32).contiguous()
+            keep[id(t)] = t
+            return t.data_ptr()
+
+        def host(vals):
+            a = (C.c_int32 * len(vals))(*[int(x) for x in vals])
+            keep[id(a)] = a
+            return C.addressof(a)
+
+        c.q, c.k, c.v = dev(q), dev(k), dev(v)
+        c.offset = host(offset)
+        if pk is not None:
+            c.n_pre, c.pre_T = pk.shape[0], pk.shape[1]
+            c.pk, c.pv = dev(pk), dev(pv)
+            c.pre_len, c.pre_id = host(pre_len), host(pre_id)
+        out = {"y": torch.empty((B, Tq, H * 64), dtype=torch.float32, device=self.device)}
+        c.y = out["y"].data_ptr()
+        label = C.create_string_buffer(256)
+        c.label = C.addressof(label)
+        c.label_cap = 256
+        self._pre()
+        rc = _lib.check(self.lib.ptts_debug_attn(self.handle, C.byref(c), self._sp))
+        del keep
+        if rc == 1:
+            return None
+        out["label"] = label.value.decode()
+        out["kernel"] = c.kernel_used
+        out["splits"] = c.splits_used
+        return out
+
     def close(self):
         """Destroys every state created from this engine, then the engine (order matters: states
         point into the engine)."""
