@@ -340,6 +340,42 @@ typedef struct ptts_gemm_case {
   int32_t cfg_used;                        /* out: the configuration that ran */
 } ptts_gemm_case;
 int ptts_debug_gemm(ptts_engine *e, ptts_gemm_case *c, void *stream);
+/* Test hook: ONE GEMM of the reduced-precision codec (gemm_h_kernel on bf16 operands, fmt 0; gemm_f8_kernel on e4m3
+ * operands, fmt 1) or its last conv (pcm_conv_h_kernel, kind 1), packed by the engine's own packers and launched by the
+ * production launchers, on plain row-major device buffers:
+ *   acc[m][n] = sum_tap sum_c x_eff[row(m, tap)][c] * w_eff[n][tap * C + c],  row(b * T + t, tap) = b * T + t + tap - halo
+ * (ntaps == 1: row(m) = m).  Rows before a sequence's start come from the previous frame x_prev (row + T), rows past
+ * the end of x read as zero.  x goes into parity half `par` of the kernels' frame-parity double buffer, x_prev into the
+ * other, each converted as production converts it (bf16: round to nearest even; e4m3: saturate(x / xs)).
+ * w: mode 0 [N][C][ntaps]; mode 1 (ConvTranspose, ntaps 2, N = stride * cout) [C][cout][2 * stride].
+ * pre 3 = folded LayerNorm (bf16 Linear only).  epi 0 store (act 0 none / 1 GELU / 3 ELU; yraw = bf16 pre-activation;
+ * yf8 = e4m3 output of y * yinv), 1 residual (bf16 r; ls: bf16 only), 3 QKV (bf16 only: RoPE from the table the hook
+ * builds with rope_table_kernel, y = [M][q | k | v] with k / v read back from cache slot pos % ring), 6 ConvTranspose
+ * (output row m * stride + j takes columns j * cout ..; y [M * stride][cout]).  kind 1: y [M] fp32 PCM, y_i16 its int16
+ * twin (widened), w [1][C][ntaps], fmt 0.  cfg: tile 0..3 ({2,4,2,2}, {2,2,2,2}, {1,2,2,2}, {1,1,2,2}), -1 = the
+ * dispatcher's choice.  Returns 0 when the kernel ran, 1 when no kernel implements the combination (nothing launched),
+ * < 0 on an error, e.g. a kernel that wrote past an output.  Outputs the kernel leaves unwritten read back as NaN.
+ * Synchronises `stream`. */
+typedef struct ptts_codec_gemm_case {
+  int32_t M, N, C, ntaps;                  /* output rows, output channels, input channels (% 32 == 0), taps */
+  int32_t T, halo, par;                    /* rows per sequence (ntaps > 1 or kind 1; % 16 == 0, divides M), halo, parity */
+  int32_t fmt, kind, pre, epi, act, cfg;
+  int32_t mode, cout, stride;              /* weight packing mode; ConvTranspose: cout, stride */
+  int32_t yf8, H, Tq, ring, cap;           /* e4m3 output; QKV: heads, rows per sequence, ring (0: linear), cache slots */
+  float xs, yinv;                          /* e4m3: activation scale of x, 1 / scale of an e4m3 y */
+  const float *x, *x_prev;                 /* [M][C] (x_prev: null = zeros) */
+  const float *w, *bias, *ln_w, *ln_b;     /* weights (see above), [N] / [cout] or null, pre 3: LayerNorm gain / bias [C] */
+  const float *r, *ls;                     /* epi 1: residual [M][N] (rounded to bf16), layer scale [N] or null */
+  const int32_t *offset;                   /* QKV: host [M / Tq] positions of each sequence's first row */
+  float *y, *yraw, *y_i16;                 /* out: see above; optional out: yraw (epi 0 / 5), y_i16 (kind 1) */
+  float *x_eff, *xp_eff;                   /* optional out: [M][C] activations the kernel consumed (e4m3: decoded * xs) */
+  float *w_eff, *wscale;                   /* optional out: [N][ntaps * C] weights consumed (e4m3: decoded * wscale), [N] */
+  float *ln_s, *ln_c, *rope;               /* optional out: pre 3 fold vectors [N]; QKV: RoPE table [M][32][2] (cos, sin) */
+  char *label;                             /* optional out: the launch's profiler label */
+  int32_t label_cap;
+  int32_t cfg_used;                        /* out: the tile that ran */
+} ptts_codec_gemm_case;
+int ptts_debug_codec_gemm(ptts_engine *e, ptts_codec_gemm_case *c, void *stream);
 /* Test hook: ONE attention launch of the hot path (attn_kernel / attn_decode_kernel / attn_decode2_kernel /
  * attn_cascade_kernel, + attn_combine_kernel when the keys are split) through the production dispatcher, on plain
  * row-major device buffers.  Row b's queries sit at positions offset[b] .. offset[b] + Tq - 1; its key / value at

@@ -48,6 +48,18 @@ class PttsGemmCase(C.Structure):
     ]
 
 
+class PttsCodecGemmCase(C.Structure):
+    """ptts_codec_gemm_case: one codec GEMM / last conv for the ptts_debug_codec_gemm test hook"""
+    _fields_ = [
+        *[(f, C.c_int32) for f in ("M", "N", "C", "ntaps", "T", "halo", "par", "fmt", "kind", "pre", "epi", "act", "cfg",
+                                   "mode", "cout", "stride", "yf8", "H", "Tq", "ring", "cap")],
+        ("xs", C.c_float), ("yinv", C.c_float),
+        *[(f, C.c_void_p) for f in ("x", "x_prev", "w", "bias", "ln_w", "ln_b", "r", "ls", "offset", "y", "yraw", "y_i16",
+                                    "x_eff", "xp_eff", "w_eff", "wscale", "ln_s", "ln_c", "rope", "label")],
+        ("label_cap", C.c_int32), ("cfg_used", C.c_int32),
+    ]
+
+
 class PttsAttnCase(C.Structure):
     """ptts_attn_case: one attention launch for the ptts_debug_attn test hook"""
     _fields_ = [
@@ -123,6 +135,7 @@ PROTOTYPES = {
                                     C.POINTER(C.c_int32), _P]),
     "ptts_debug_gemm": (C.c_int, [_P, C.POINTER(PttsGemmCase), _P]),
     "ptts_debug_attn": (C.c_int, [_P, C.POINTER(PttsAttnCase), _P]),
+    "ptts_debug_codec_gemm": (C.c_int, [_P, C.POINTER(PttsCodecGemmCase), _P]),
     "ptts_lm_weight_bytes": (C.c_int64, [_P]),
     "ptts_mimi_weight_bytes": (C.c_int64, [_P]),
 }

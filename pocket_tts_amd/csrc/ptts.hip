@@ -2522,33 +2522,57 @@ static void launch_h_cfg(hipStream_t st, const GemmArgs &a, int pre) {
   if (pre == PRE_LNFOLD) gemm_h_kernel<TN, TM, WN, WM, PRE_LNFOLD><<<grid, block, dyn, st>>>(a);
   else gemm_h_kernel<TN, TM, WN, WM, PRE_NONE><<<grid, block, dyn, st>>>(a);
 }
-static void launch_gemm_h(hipStream_t st, const GemmArgs &a_in, int pre, const Lin &L) {
+// The production tile of a bf16 codec GEMM: index into kTileH
+static const int kTileH[4][4] = {{2, 4, 2, 2}, {2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
+static int choose_h_tile(const GemmArgs &a) {
+  int pick = 3;
+  for (int i = 0; i < 4; ++i) {
+    const int *t = kTileH[i];
+    if (t[0] * t[2] > 2 * a.NT && i < 3) continue;  // mostly padding
+    if ((long)cdiv(a.NT, t[0] * t[2]) * cdiv(a.MT, t[1] * t[3]) >= 512 || i == 3) { pick = i; break; }
+  }
+  return pick;
+}
+// Launches tile `cfg` of gemm_h_kernel on operands a (W, CF, KF, ln_s set), bracketed by the profiler under its label;
+// `label` != null receives it
+static void launch_h_tile(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr) {
+  const double K = (double)a.KF * 32, N = (double)a.NT * 16, M = (double)a.M;
+  double bytes = 2.0 * (N * K + M * (double)a.CF * 32 + M * N * (a.Yraw ? 2 : 1)) + (a.epi == EPI_RES ? 2.0 * M * N : 0.0);
+  if (a.epi == EPI_QKV) bytes += 2.0 * M * N;  // q / k / v leave as fp32
+  static const char *const names[4] = {"gemm_h<2,4,2,2>", "gemm_h<2,2,2,2>", "gemm_h<1,2,2,2>", "gemm_h<1,1,2,2>"};
+  const int *t = kTileH[cfg];
+  const std::string name = std::string(names[cfg]) + (pre == PRE_LNFOLD ? "+ln" : "") + "@" +
+                           std::to_string((long)cdiv(a.NT, t[0] * t[2]) * cdiv(a.MT, t[1] * t[3]) * 256);
+  if (label) *label = name;
+  ProfScope ps(st, name, bytes, 2.0 * M * N * K);
+  switch (cfg) {
+    case 0: launch_h_cfg<2, 4, 2, 2>(st, a, pre); break;
+    case 1: launch_h_cfg<2, 2, 2, 2>(st, a, pre); break;
+    case 2: launch_h_cfg<1, 2, 2, 2>(st, a, pre); break;
+    default: launch_h_cfg<1, 1, 2, 2>(st, a, pre); break;
+  }
+}
+static GemmArgs gemm_h_args(const GemmArgs &a_in, int pre, const Lin &L) {
   GemmArgs a = a_in;
   a.W = (const float *)L.wh;
   a.CF = L.C / 32;
   a.KF = a.CF * L.ntaps;
   if (pre == PRE_LNFOLD) a.ln_s = L.ln_s_h;
   a.swz = 0;
-  const double K = (double)a.KF * 32, N = (double)a.NT * 16, M = (double)a.M;
-  double bytes = 2.0 * (N * K + M * (double)a.CF * 32 + M * N * (a.Yraw ? 2 : 1)) + (a.epi == EPI_RES ? 2.0 * M * N : 0.0);
-  if (a.epi == EPI_QKV) bytes += 2.0 * M * N;  // q / k / v leave as fp32
-  static const int tiles[4][4] = {{2, 4, 2, 2}, {2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
-  int pick = 3;
-  for (int i = 0; i < 4; ++i) {
-    const int *t = tiles[i];
-    if (t[0] * t[2] > 2 * a.NT && i < 3) continue;  // mostly padding
-    if ((long)cdiv(a.NT, t[0] * t[2]) * cdiv(a.MT, t[1] * t[3]) >= 512 || i == 3) { pick = i; break; }
-  }
-  static const char *const names[4] = {"gemm_h<2,4,2,2>", "gemm_h<2,2,2,2>", "gemm_h<1,2,2,2>", "gemm_h<1,1,2,2>"};
-  const int *t = tiles[pick];
-  ProfScope ps(st, std::string(names[pick]) + (pre == PRE_LNFOLD ? "+ln" : "") + "@" +
-                       std::to_string((long)cdiv(a.NT, t[0] * t[2]) * cdiv(a.MT, t[1] * t[3]) * 256), bytes, 2.0 * M * N * K);
-  switch (pick) {
-    case 0: launch_h_cfg<2, 4, 2, 2>(st, a, pre); break;
-    case 1: launch_h_cfg<2, 2, 2, 2>(st, a, pre); break;
-    case 2: launch_h_cfg<1, 2, 2, 2>(st, a, pre); break;
-    default: launch_h_cfg<1, 1, 2, 2>(st, a, pre); break;
-  }
+  return a;
+}
+static void launch_gemm_h(hipStream_t st, const GemmArgs &a_in, int pre, const Lin &L) {
+  const GemmArgs a = gemm_h_args(a_in, pre, L);
+  launch_h_tile(st, a, pre, choose_h_tile(a));
+}
+// fp8 conv tile `cfg` (ptts_fp8.hip) on operands g, bracketed by the profiler under its label (one label for every tile)
+static void launch_f8_tile(hipStream_t st, const GemmArgs &g, int cfg, std::string *label = nullptr) {
+  const double K = (double)g.KF * 32, N = (double)g.NT * 16, M = (double)g.M;
+  const std::string name = "gemm_f8@" + std::to_string((long)g.NT * g.MT);
+  if (label) *label = name;
+  ProfScope ps(st, name, N * K + M * g.CF * 32.0 + M * N * (g.yf8 ? 1 : 2) + (g.Yraw ? 2.0 * M * N : 0.0) + (g.epi == EPI_RES ? 2.0 * M * N : 0.0),
+               2.0 * M * N * K);
+  launch_gemm_f8(st, g, cfg, lds_pad(0));
 }
 
 // the codec frame with bf16 activations: same dataflow, buffers and carries as mimi_enqueue (the fp32 buffers are
@@ -2617,10 +2641,7 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     g.xs = f8s[sc_in];
     g.yf8 = sc_out >= 0;
     g.yinv = sc_out >= 0 ? 1.0f / f8s[sc_out] : 1.0f;
-    const double K = (double)g.KF * 32, N = (double)g.NT * 16, M = (double)g.M;
-    ProfScope ps(st, "gemm_f8@" + std::to_string((long)g.NT * g.MT), N * K + M * g.CF * 32.0 + M * N * (g.yf8 ? 1 : 2) + (g.Yraw ? 2.0 * M * N : 0.0) +
-                         (g.epi == EPI_RES ? 2.0 * M * N : 0.0), 2.0 * M * N * K);
-    launch_gemm_f8(st, g, lds_pad(0));
+    launch_f8_tile(st, g, choose_f8_tile(g));
   };
   int mult = 8;
   SITE("seanet.conv0");
@@ -3803,6 +3824,275 @@ extern "C" int ptts_debug_attn(ptts_engine *e, ptts_attn_case *c, void *stream) 
   scr.stream = st;
   scr.device = e->device;
   const int rc = debug_attn(e, c, st, scr);
+  (void)hipStreamSynchronize(st);
+  for (void *p : scr.allocs) (void)hipFree(p);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ptts_debug_codec_gemm (test hook, include/ptts.h): one GEMM of the reduced-precision codec (gemm_h_kernel /
+// gemm_f8_kernel) or its last conv (pcm_conv_h_kernel), packed by pack_lin_h / pack_weight_f8 and launched by
+// launch_h_tile / launch_f8_tile, between plain row-major buffers and the FMH / FM8 layouts
+
+__device__ __forceinline__ float dbg_e4m3(uint8_t b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
+// [M][C] row-major -> FMH (fmt 0) / FM8 (fmt 1, saturate(x * inv_xs)) with `rows` rows (rows >= M are zero); eff != null
+// receives the values the kernel reads (e4m3: decoded times xs).  One thread per 4 columns of a row.
+static __global__ void dbg_to_codec_kernel(const float *src, void *dst, float *eff, int M, int C, int rows, int fmt, float inv_xs, float xs) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)rows * (C / 4)) return;
+  const int m = i / (C / 4), c0 = 4 * (int)(i - (long)m * (C / 4));
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (src && m < M) v = *(const f32x4 *)(src + (size_t)m * C + c0);
+  const size_t o = fmh_off(m, c0, C / 32);
+  f32x4 d;
+  if (fmt == 0) {
+    const bf16x4 h = to_bf16x4(v);
+    *(bf16x4 *)((__bf16 *)dst + o) = h;
+    d = from_bf16x4(h);
+  } else {
+    const unsigned q = to_f8x4(v * inv_xs);
+    *(unsigned *)((uint8_t *)dst + o) = q;
+    d = (f32x4){dbg_e4m3(q & 255), dbg_e4m3((q >> 8) & 255), dbg_e4m3((q >> 16) & 255), dbg_e4m3(q >> 24)} * xs;
+  }
+  if (eff && m < M) *(f32x4 *)(eff + (size_t)m * C + c0) = d;
+}
+// FMH / FM8 -> [M][N] f32 (e4m3 decoded, unscaled)
+static __global__ void dbg_from_codec_kernel(const void *src, float *dst, int M, int N, int KB, int fmt) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)M * N) return;
+  const int m = i / N, n = i - (long)m * N;
+  const size_t o = fmh_off(m, n & ~3, KB) + (n & 3);
+  dst[i] = fmt == 0 ? (float)((const __bf16 *)src)[o] : dbg_e4m3(((const uint8_t *)src)[o]);
+}
+// weights of a codec image [NT][KBt][64][8] as [N][KBt * 32] f32 (k = tap * C + c): fmt 0 bf16, 1 e4m3 times scale[n]
+static __global__ void dbg_unpack_codec_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KBt) {
+  const long K = (long)KBt * 32;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)N * K) return;
+  const int n = i / K, k = i - (long)n * K;
+  const size_t o = (((size_t)(n >> 4) * KBt + (k >> 5)) * 64 + 16 * ((k & 31) >> 3) + (n & 15)) * 8 + (k & 7);
+  dst[i] = fmt == 0 ? (float)((const __bf16 *)img)[o] : dbg_e4m3(((const uint8_t *)img)[o]) * scale[n];
+}
+// EPI_QKV outputs -> [M][3 * H * 64]: q from its block layout, k / v from cache slot pos % ring (ring 0: pos)
+static __global__ void dbg_from_qkv_kernel(const float *Q, const float *Kc, const float *Vc, const int *offset, float *dst, int M,
+                                           int H, int Tq, int QB, int cap, int ring) {
+  const int D = H * 64;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)M * 3 * D) return;
+  const int m = i / (3 * D), n = i - (long)m * 3 * D;
+  const int which = n / D, hn = n - which * D, h = hn >> 6, d = hn & 63;
+  const int b = m / Tq, t = m - b * Tq;
+  const size_t bh = (size_t)b * H + h;
+  if (which == 0) {
+    dst[i] = Q[(((bh * QB + (t >> 4)) * 4 + (d >> 4)) * 64 + 16 * ((d & 15) >> 2) + (t & 15)) * 4 + (d & 3)];
+  } else {
+    const int pos = offset[b] + t, slot = ring ? pos % ring : pos;
+    dst[i] = (which == 1 ? Kc : Vc)[(bh * cap + slot) * 64 + d];
+  }
+}
+
+static int debug_codec_gemm(ptts_engine *e, ptts_codec_gemm_case *c, hipStream_t st, ptts_engine &scr) {
+  const int M = c->M, N = c->N, C = c->C, ntaps = c->ntaps, pre = c->pre, epi = c->epi, fmt = c->fmt;
+  const bool pcm = c->kind == 1;
+  c->cfg_used = -1;
+  if (!c->x || !c->w || !c->y) return fail(-1, "debug_codec_gemm: x, w and y are required");
+  if (fmt < 0 || fmt > 1 || c->kind < 0 || c->kind > 1 || (pre != PRE_NONE && pre != PRE_LNFOLD) || c->act < ACT_NONE || c->act > ACT_ELU ||
+      (epi != EPI_STORE && epi != EPI_RES && epi != EPI_QKV && epi != EPI_CONVTR) || c->cfg < -1 || c->cfg > 3 || c->mode < 0 ||
+      c->mode > 1 || c->par < 0 || c->par > 1)
+    return fail(-1, "debug_codec_gemm: enumeration out of range");
+  if (M < 1 || N < 1 || C < 32 || ntaps < 1) return fail(-1, "debug_codec_gemm: bad shape");
+  if (ntaps > 1 || pcm) {
+    if (c->T < 16 || c->T % 16 || M % c->T || c->halo < 0 || c->halo > ntaps - 1 || c->halo > c->T)
+      return fail(-1, "debug_codec_gemm: bad convolution geometry");
+  } else if (c->halo) {
+    return fail(-1, "debug_codec_gemm: a Linear has halo 0");
+  }
+  if (c->mode == 1 && (ntaps != 2 || c->cout < 1 || c->stride < 1 || N != c->cout * c->stride))
+    return fail(-1, "debug_codec_gemm: a ConvTranspose image needs ntaps 2 and N = stride * cout");
+  if (epi == EPI_CONVTR && (c->cout < 1 || c->stride < 1 || N != c->cout * c->stride)) return fail(-1, "debug_codec_gemm: ConvTranspose needs N = stride * cout");
+  if ((epi == EPI_RES && !c->r) || (pre == PRE_LNFOLD && (!c->ln_w || !c->ln_b))) return fail(-1, "debug_codec_gemm: missing operand");
+  if (epi == EPI_QKV && (c->H < 1 || N != 3 * c->H * 64 || c->Tq < 1 || M % c->Tq || !c->offset || c->cap < 1 || c->ring < 0 ||
+                         c->ring > c->cap || (c->ring && c->Tq > c->ring)))
+    return fail(-1, "debug_codec_gemm: bad QKV geometry");
+  if (fmt == 1 && c->xs <= 0.f) return fail(-1, "debug_codec_gemm: the e4m3 activation scale xs must be positive");
+  if (c->yf8 && c->yinv <= 0.f) return fail(-1, "debug_codec_gemm: yinv must be positive");
+  // combinations no kernel implements: nothing launched
+  const bool unsupported =
+      C % 32 || (pcm ? (fmt != 0 || N != 1 || pre != PRE_NONE) :
+                 (N % 32 || (epi == EPI_CONVTR && c->cout % 32) || (pre == PRE_LNFOLD && (fmt != 0 || ntaps != 1)) ||
+                  (epi == EPI_QKV && (fmt != 0 || c->yf8 || c->yraw || c->act != ACT_NONE)) ||
+                  (epi == EPI_RES && (c->yraw || (c->ls && fmt != 0) || (c->yf8 && fmt == 0))) ||  // gemm_h's RES / CONVTR store bf16 only
+                  (epi == EPI_CONVTR && c->yf8 && fmt == 0)));
+  if (unsupported) return 1;
+
+  const int MT = cdiv(M, 16), CB = C / 32;
+  const int rows_in = 16 * cdiv(M + ntaps, 16);  // rows past the end of x (halo < ntaps - 1) read zeros
+  const long half = (long)rows_in * C;           // elements per parity half
+  const int esz = fmt == 0 ? 2 : 1;
+  void *xbuf = nullptr;
+  CHK(dalloc(&scr, &xbuf, 2 * half * esz));
+  const float inv_xs = fmt == 1 ? 1.0f / c->xs : 1.f;
+  const long nq = (long)rows_in * (C / 4);
+  dbg_to_codec_kernel<<<cdiv(nq, 256), 256, 0, st>>>(c->x, (char *)xbuf + (size_t)c->par * half * esz, c->x_eff, M, C, rows_in, fmt, inv_xs, c->xs);
+  dbg_to_codec_kernel<<<cdiv(nq, 256), 256, 0, st>>>(c->x_prev, (char *)xbuf + (size_t)(c->par ^ 1) * half * esz, c->xp_eff, M, C, rows_in, fmt,
+                                                     inv_xs, c->xs);
+  int *dpar = nullptr;
+  CHK(dallocT(&scr, &dpar, 1));
+  HIPCHK(hipMemcpyAsync(dpar, &c->par, 4, hipMemcpyHostToDevice, st));
+
+  // outputs: NaN-filled (bf16 0x7fc0, e4m3 0x7f, f32 quiet NaN), each followed by a guard
+  std::vector<const unsigned *> guards;
+  auto out_buf = [&](size_t elems, int bytes_per, void **p) -> int {
+    const size_t main = (elems * bytes_per + 255) / 256 * 256;
+    CHK(dalloc(&scr, p, main + kDbgGuardFloats * 4));
+    if (bytes_per == 4) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)*p, (int)kDbgUnwritten, main / 4, st));
+    else if (bytes_per == 2) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)*p, 0x7fc0, main / 2, st));
+    else HIPCHK(hipMemsetD8Async((hipDeviceptr_t)*p, 0x7f, main, st));
+    unsigned *g = (unsigned *)((char *)*p + main);
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)g, (int)kDbgGuard, kDbgGuardFloats, st));
+    guards.push_back(g);
+    return 0;
+  };
+
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  std::string label;
+  Lin L;
+  if (pcm) {
+    a.M = M; a.MT = MT; a.CF = CB; a.XF = CB; a.ntaps = ntaps; a.T = c->T; a.halo = c->halo;
+    a.X = (const float *)xbuf; a.Xdstride = half; a.par = dpar; a.epi = EPI_PCM;
+    void *py = nullptr, *pi = nullptr;
+    CHK(out_buf(M, 4, &py));
+    CHK(out_buf(M, 2, &pi));
+    a.pcm = (float *)py;
+    a.pcm_i16 = (int16_t *)pi;
+    label = "pcm_conv_h";
+    {
+      ProfScope ps(st, label, 2.0 * M * C + 4.0 * M, 2.0 * M * C * ntaps);
+      pcm_conv_h_kernel<<<cdiv(M, 256), 256, 0, st>>>(a, c->w, c->bias);
+    }
+    LAUNCHCHK();
+    c->cfg_used = 0;
+    HIPCHK(hipMemcpyAsync(c->y, py, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+    if (c->y_i16) {
+      std::vector<int16_t> h(M);
+      HIPCHK(hipMemcpyAsync(h.data(), pi, (size_t)M * 2, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      std::vector<float> f(h.begin(), h.end());
+      HIPCHK(hipMemcpyAsync(c->y_i16, f.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+  } else {
+    // pack with the engine's own code: a scratch engine whose tensor map holds the case's operands.  pack_lin builds the
+    // fp32 image as production does; here (as in production) it is only the source of the padded bias and of the
+    // LayerNorm fold's ln_c: the codec kernels read pack_lin_h's bf16 image or pack_weight_f8's e4m3 one
+    const int nb = epi == EPI_CONVTR || c->mode == 1 ? c->cout : N;
+    const ptts_tensor tw{"w", c->w, (int64_t)N * C * ntaps}, tb{"b", c->bias, nb}, tg{"ln_w", c->ln_w, C}, tbe{"ln_b", c->ln_b, C};
+    scr.tmap["w"] = &tw;
+    if (c->bias) scr.tmap["b"] = &tb;
+    const bool fold = pre == PRE_LNFOLD;
+    if (fold) { scr.tmap["ln_w"] = &tg; scr.tmap["ln_b"] = &tbe; }
+    CHK(pack_lin(&scr, &L, {{"w", c->bias ? "b" : "", N}}, C, ntaps, c->mode, c->cout, c->stride, fold ? "ln_w" : "", fold ? "ln_b" : ""));
+    const int KBt = CB * ntaps;
+    if (fmt == 0) {
+      CHK(pack_lin_h(&scr, &L, "w", N, C, ntaps, c->mode, c->cout, c->stride, fold ? "ln_w" : ""));
+    } else {
+      CHK(dalloc(&scr, &L.wf8, (size_t)L.NT * KBt * 512));
+      CHK(dallocT(&scr, &L.wscale8, (size_t)L.NT * 16));
+      pack_weight_f8(st, c->w, L.wf8, L.wscale8, N, C, ntaps, c->mode, c->cout, c->stride);
+    }
+    LAUNCHCHK();
+    a = mk_gemm(L, (const float *)xbuf, CB, MT, M);
+    a.ntaps = ntaps; a.T = ntaps > 1 ? c->T : 16; a.halo = c->halo; a.Xdstride = half; a.par = dpar;
+    a.epi = epi; a.act = c->act;
+    const int YF = (epi == EPI_CONVTR ? c->cout : N) / 32;
+    const long yrows = epi == EPI_CONVTR ? (long)MT * 16 * c->stride : (long)MT * 16, yrows_out = epi == EPI_CONVTR ? (long)M * c->stride : M;
+    void *y = nullptr, *yraw = nullptr;
+    float *Q = nullptr, *Kc = nullptr, *Vc = nullptr, *rope = nullptr, *tmp = nullptr;
+    int *doff = nullptr;
+    const int B = epi == EPI_QKV ? M / c->Tq : 0, QB = epi == EPI_QKV ? cdiv(c->Tq, 16) : 0;
+    if (epi == EPI_QKV) {
+      const size_t qn = (size_t)B * c->H * QB * 4 * 64 * 4, kn = (size_t)B * c->H * c->cap * 64;
+      CHK(out_buf(qn, 4, (void **)&Q));
+      CHK(out_buf(kn, 4, (void **)&Kc));
+      CHK(out_buf(kn, 4, (void **)&Vc));
+      CHK(dallocT(&scr, &doff, (size_t)B));
+      HIPCHK(hipMemcpyAsync(doff, c->offset, (size_t)B * 4, hipMemcpyHostToDevice, st));
+      CHK(dallocT(&scr, &rope, (size_t)MT * 16 * 64));
+      rope_table_kernel<<<cdiv(M * 32, 256), 256, 0, st>>>(doff, e->freq_mimi, rope, M, c->Tq);
+      a.Q = Q; a.Kc = Kc; a.Vc = Vc; a.offset = doff; a.rope = rope;
+      a.H = c->H; a.Tq = c->Tq; a.QB = QB; a.cap = c->cap; a.ring = c->ring;
+    } else {
+      CHK(out_buf((size_t)yrows * YF * 32, c->yf8 ? 1 : 2, &y));
+      a.Y = (float *)y; a.YF = YF;
+      a.yf8 = c->yf8; a.yinv = c->yf8 ? c->yinv : 1.0f;
+      if (c->yraw) { CHK(out_buf((size_t)yrows * YF * 32, 2, &yraw)); a.Yraw = (float *)yraw; }
+      if (epi == EPI_CONVTR) { a.cout = c->cout; a.stride = c->stride; }
+    }
+    if (epi == EPI_RES) {
+      CHK(dalloc(&scr, (void **)&tmp, (size_t)MT * 16 * N * 2));
+      dbg_to_codec_kernel<<<cdiv((long)MT * 16 * (N / 4), 256), 256, 0, st>>>(c->r, tmp, nullptr, M, N, MT * 16, 0, 1.f, 1.f);
+      a.R = tmp; a.RF = N / 32;
+      if (c->ls) {
+        float *ls = nullptr;
+        CHK(dallocT(&scr, &ls, (size_t)L.NT * 16));
+        HIPCHK(hipMemcpyAsync(ls, c->ls, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+        a.ls = ls;
+      }
+    }
+    int cfg = c->cfg;
+    if (fmt == 0) {
+      a = gemm_h_args(a, pre, L);
+      if (cfg < 0) cfg = choose_h_tile(a);
+      launch_h_tile(st, a, pre, cfg, &label);
+    } else {
+      a.W = (const float *)L.wf8; a.wscale = L.wscale8; a.CF = CB; a.KF = KBt; a.swz = 0; a.xs = c->xs;
+      if (cfg < 0) cfg = choose_f8_tile(a);
+      launch_f8_tile(st, a, cfg, &label);
+    }
+    LAUNCHCHK();
+    c->cfg_used = cfg;
+    if (epi == EPI_QKV) {
+      dbg_from_qkv_kernel<<<cdiv((long)M * N, 256), 256, 0, st>>>(Q, Kc, Vc, doff, c->y, M, c->H, c->Tq, QB, c->cap, c->ring);
+      if (c->rope) HIPCHK(hipMemcpyAsync(c->rope, rope, (size_t)M * 64 * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+      const int Nout = YF * 32;
+      dbg_from_codec_kernel<<<cdiv(yrows_out * Nout, 256), 256, 0, st>>>(y, c->y, yrows_out, Nout, YF, c->yf8 ? 1 : 0);
+      if (c->yraw) dbg_from_codec_kernel<<<cdiv(yrows_out * Nout, 256), 256, 0, st>>>(yraw, c->yraw, yrows_out, Nout, YF, 0);
+    }
+    const long nk = (long)N * KBt * 32;
+    if (c->w_eff) dbg_unpack_codec_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(fmt == 0 ? (const void *)L.wh : L.wf8, L.wscale8, fmt, c->w_eff, N, KBt);
+    if (c->wscale && fmt == 1) HIPCHK(hipMemcpyAsync(c->wscale, L.wscale8, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+    if (fold && c->ln_s) HIPCHK(hipMemcpyAsync(c->ln_s, L.ln_s_h, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+    if (fold && c->ln_c) HIPCHK(hipMemcpyAsync(c->ln_c, L.ln_c, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+  }
+  if (c->label && c->label_cap > 0) {
+    const size_t n = std::min<size_t>(label.size(), (size_t)c->label_cap - 1);
+    memcpy(c->label, label.data(), n);
+    c->label[n] = 0;
+  }
+  int *bad = nullptr;
+  CHK(dallocT(&scr, &bad, 1));
+  for (const unsigned *g : guards) dbg_guard_kernel<<<cdiv(kDbgGuardFloats, 256), 256, 0, st>>>(g, kDbgGuardFloats, kDbgGuard, bad);
+  LAUNCHCHK();
+  int h_bad = 0;
+  HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (h_bad) return fail(-6, "debug_codec_gemm: " + label + " wrote past an output");
+  return 0;
+}
+
+extern "C" int ptts_debug_codec_gemm(ptts_engine *e, ptts_codec_gemm_case *c, void *stream) {
+  if (!e || !c) return fail(-1, "debug_codec_gemm: null argument");
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  bind_engine(e);
+  hipStream_t st = S(e, stream);
+  AllocScope as(st);
+  ptts_engine scr;  // owns the case's packed matrix and buffers, freed here whatever the outcome
+  scr.stream = st;
+  scr.device = e->device;
+  const int rc = debug_codec_gemm(e, c, st, scr);
   (void)hipStreamSynchronize(st);
   for (void *p : scr.allocs) (void)hipFree(p);
   return rc;

@@ -16,8 +16,10 @@ void pack_weight_b16(hipStream_t st, const float *src, void *dst, float *ln_s, i
 // NT * 16); same (mode, cout, stride) conventions as pack_weight_kernel
 void pack_weight_f8(hipStream_t st, const float *src, void *dst, float *wscale, int N, int C, int ntaps, int mode, int cout, int stride);
 // implicit GEMM on e4m3 operands (GemmArgs::X = e4m3 activations in the "FM8" layout, W = e4m3 weights, wscale = per-channel
-// weight scale, xs = activation scale of X, yinv = 1 / scale of Y when Y is e4m3 (yf8 = 1), else Y is bf16 FMH)
-void launch_gemm_f8(hipStream_t st, const GemmArgs &a, unsigned dyn_lds);
+// weight scale, xs = activation scale of X, yinv = 1 / scale of Y when Y is e4m3 (yf8 = 1), else Y is bf16 FMH);
+// choose_f8_tile = the production tile (0..3 of {2,4,2,2}, {2,2,2,2}, {1,2,2,2}, {1,1,2,2}), launch_gemm_f8 runs tile `cfg`
+int choose_f8_tile(const GemmArgs &a);
+void launch_gemm_f8(hipStream_t st, const GemmArgs &a, int cfg, unsigned dyn_lds);
 // max |x| over n bf16 values (calibration of the static activation scales), atomically max-ed into *out (as float bits)
 void amax_bf16(hipStream_t st, const void *x, long n, float *out);
 

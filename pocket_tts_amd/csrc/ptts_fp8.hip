@@ -193,9 +193,9 @@ static void launch_f8_cfg(hipStream_t st, const GemmArgs &a, unsigned dyn) {
   const dim3 grid(cdiv8(a.NT, TN * WN), cdiv8(a.MT, TM * WM)), block(64 * WN * WM);
   gemm_f8_kernel<TN, TM, WN, WM><<<grid, block, dyn, st>>>(a);
 }
-// tile choice as for the bf16 codec (launch_gemm_h in ptts.hip): the largest workgroup tile that still yields >= ~2
+// tile choice as for the bf16 codec (choose_h_tile in ptts.hip): the largest workgroup tile that still yields >= ~2
 // workgroups per CU; these kernels are bandwidth / launch bound (the fp8 MFMA runs at the bf16 rate = 16x fp32)
-void launch_gemm_f8(hipStream_t st, const GemmArgs &a, unsigned dyn) {
+int choose_f8_tile(const GemmArgs &a) {
   static const int tiles[4][4] = {{2, 4, 2, 2}, {2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
   int pick = 3;
   for (int i = 0; i < 4; ++i) {
@@ -203,7 +203,10 @@ void launch_gemm_f8(hipStream_t st, const GemmArgs &a, unsigned dyn) {
     if (t[0] * t[2] > 2 * a.NT && i < 3) continue;  // mostly padding
     if ((long)cdiv8(a.NT, t[0] * t[2]) * cdiv8(a.MT, t[1] * t[3]) >= 512 || i == 3) { pick = i; break; }
   }
-  switch (pick) {
+  return pick;
+}
+void launch_gemm_f8(hipStream_t st, const GemmArgs &a, int cfg, unsigned dyn) {
+  switch (cfg) {
     case 0: launch_f8_cfg<2, 4, 2, 2>(st, a, dyn); break;
     case 1: launch_f8_cfg<2, 2, 2, 2>(st, a, dyn); break;
     case 2: launch_f8_cfg<1, 2, 2, 2>(st, a, dyn); break;

@@ -562,6 +562,92 @@ class Engine:
         out["cfg"] = c.cfg_used
         return out
 
+    _CODEC_INTS = ("T", "halo", "par", "fmt", "kind", "pre", "epi", "act", "cfg", "mode", "cout", "stride", "yf8", "H", "Tq",
+                   "ring", "cap")
+    _CODEC_INS = ("x_prev", "bias", "ln_w", "ln_b", "r", "ls")
+
+    def debug_codec_gemm(self, x: torch.Tensor, w: torch.Tensor, *, ntaps: int = 1, xs: float = 1.0, yinv: float = 1.0,
+                         offset=None, yraw: bool = False, want_operands: bool = False, **kw):
+        """Test hook: one GEMM of the reduced-precision codec (gemm_h_kernel / gemm_f8_kernel) or its last conv
+        (pcm_conv_h_kernel, kind=1) through the production launchers (ptts_debug_codec_gemm in include/ptts.h).
+        x: [M][C]; w: mode 0 [N][C] or [N][C][ntaps], mode 1 [C][cout][2 * stride] (ntaps 2).  Keyword arguments: the
+        case's integer fields (cfg defaults to -1, the dispatcher's choice) and float32 device operands; offset: QKV
+        positions per sequence.  Returns None when no kernel implements the combination, else a dict with y (and yraw,
+        y_i16 for kind 1), the label, the tile that ran and, with want_operands, x_eff / xp_eff / w_eff / wscale (fp8) /
+        ln_s / ln_c (pre 3) / rope (QKV)."""
+        c = _lib.PttsCodecGemmCase()
+        c.cfg, c.T = -1, 16
+        for k in self._CODEC_INTS:
+            if k in kw:
+                setattr(c, k, int(kw[k]))
+        M, Cin = x.shape
+        if c.mode == 1:
+            N, ntaps = w.shape[1] * (w.shape[2] // 2), 2
+        else:
+            w = w if w.dim() == 3 else w.unsqueeze(2)
+            N, ntaps = w.shape[0], w.shape[2]
+        c.M, c.N, c.C, c.ntaps = M, N, Cin, ntaps
+        c.xs, c.yinv = float(xs), float(yinv)
+        keep = {}
+
+        def dev(t):
+            t = t.to(self.device, torch.float32).contiguous()
+            keep[id(t)] = t
+            return t.data_ptr()
+
+        def new(*shape):
+            t = torch.empty(shape, dtype=torch.float32, device=self.device)
+            keep[id(t)] = t
+            return t
+
+        c.x, c.w = dev(x), dev(w)
+        for k in self._CODEC_INS:
+            if kw.get(k) is not None:
+                setattr(c, k, dev(kw[k]))
+        if offset is not None:
+            offs = (C.c_int32 * len(offset))(*[int(v) for v in offset])
+            c.offset = C.addressof(offs)
+        out = {}
+        if c.kind == 1:
+            out["y"], out["y_i16"] = new(M), new(M)
+            c.y_i16 = out["y_i16"].data_ptr()
+        elif c.epi == 3:
+            out["y"] = new(M, N)
+        elif c.epi == 6:
+            out["y"] = new(M * c.stride, c.cout)
+        else:
+            out["y"] = new(M, N)
+        c.y = out["y"].data_ptr()
+        if yraw:
+            out["yraw"] = new(*out["y"].shape)
+            c.yraw = out["yraw"].data_ptr()
+        if want_operands:
+            out["x_eff"], out["xp_eff"] = new(M, Cin), new(M, Cin)
+            c.x_eff, c.xp_eff = out["x_eff"].data_ptr(), out["xp_eff"].data_ptr()
+            if c.kind == 0:
+                out["w_eff"] = new(N, ntaps * Cin)
+                c.w_eff = out["w_eff"].data_ptr()
+                if c.fmt == 1:
+                    out["wscale"] = new(N)
+                    c.wscale = out["wscale"].data_ptr()
+                if c.pre == 3:
+                    out["ln_s"], out["ln_c"] = new(N), new(N)
+                    c.ln_s, c.ln_c = out["ln_s"].data_ptr(), out["ln_c"].data_ptr()
+                if c.epi == 3:
+                    out["rope"] = new(M, 32, 2)
+                    c.rope = out["rope"].data_ptr()
+        label = C.create_string_buffer(256)
+        c.label = C.addressof(label)
+        c.label_cap = 256
+        self._pre()
+        rc = _lib.check(self.lib.ptts_debug_codec_gemm(self.handle, C.byref(c), self._sp))
+        del keep
+        if rc == 1:
+            return None
+        out["label"] = label.value.decode()
+        out["cfg"] = c.cfg_used
+        return out
+
     _ATTN_INTS = ("cap", "ring", "ctx", "splits", "h16", "layer", "pre_cap", "cascade", "kernel")
 
     def debug_attn(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, offset, *, pk=None, pv=None, pre_len=None,
