@@ -107,7 +107,8 @@ void ptts_destroy(ptts_engine *e);
 /* ---- FlowLM state: init_states(flow_lm, B, T) (stateful_module.py:7-16, transformer.py:46-57) */
 int ptts_lm_state_create(ptts_engine *e, int32_t batch, int32_t t_cap, ptts_lm_state **out);
 void ptts_lm_state_destroy(ptts_lm_state *s);
-/* zero offsets (fresh init_states); also clears every row's sampling override (ptts_lm_state_set_row_sampling) */
+/* zero offsets (fresh init_states); also clears every row's sampling override (ptts_lm_state_set_row_sampling) and LSD
+ * override (ptts_lm_state_set_row_lsd) */
 int ptts_lm_state_reset(ptts_lm_state *s, void *stream);
 /* Import / export one layer in the reference layout cache f32[2, src_batch, t, H, 64] (device) with
  * `t` valid positions (transformer.py:32-36; voice files tts_model.py:1047-1072).  On import,
@@ -170,6 +171,23 @@ int ptts_lm_state_set_row_sampling(ptts_lm_state *s, int32_t row, float temp, fl
                                    void *stream);
 /* row `row` returns to the state's defaults (ptts_lm_set_noise temperature, the step's eos_threshold); stream-ordered */
 int ptts_lm_state_clear_row_sampling(ptts_lm_state *s, int32_t row, void *stream);
+/* Per-row LSD schedules (a server's per-request lsd_decode_steps in one continuous batch; the reference takes it per model,
+ * flow_lm.py:19-40).  ptts_lm_state_reserve_row_lsd gives the state a capacity K (1 <= K <= 64): its flow buffers are sized
+ * for K Euler steps and the time embeddings of every schedule 1..K are built.  Afterwards
+ * ptts_lm_state_set_row_lsd makes row `row` of later steps run its own `n` Euler steps (1 <= n <= K) instead of the
+ * step's lsd_steps; rows without an override keep the step's lsd_steps.  Each row's latent is bitwise that of a state
+ * without the capacity stepped with lsd_steps = n when n >= 2 (n = 1: within fp32 rounding).  A step of a state with a
+ * capacity takes as long as its slowest group of 16 rows.
+ *   reserve   -1 for K out of range and for a state with captured graphs (reserve before capturing); never shrinks the
+ *             capacity.  A state without a capacity enqueues exactly the steps it did before.
+ *   set       -1 for a row out of range, n < 1, n > K, or a state without a capacity.
+ * The kernels read the counts from device memory at run time: graphs captured after the reservation pick up later
+ * calls.  set / clear are stream-ordered on `stream`.  ptts_lm_state_reset clears every override; the copy calls leave the
+ * destination's overrides as they are. */
+int ptts_lm_state_reserve_row_lsd(ptts_lm_state *s, int32_t K, void *stream);
+int ptts_lm_state_set_row_lsd(ptts_lm_state *s, int32_t row, int32_t n, void *stream);
+/* row `row` returns to the step's lsd_steps; stream-ordered */
+int ptts_lm_state_clear_row_lsd(ptts_lm_state *s, int32_t row, void *stream);
 /* device pointer of the state's own copy of the latest latent f32[B, ldim] */
 const float *ptts_lm_latent_ptr(ptts_lm_state *s);
 

@@ -96,6 +96,9 @@ PROTOTYPES = {
     "ptts_lm_set_noise": (C.c_int, [_P, C.c_float, C.c_uint64]),
     "ptts_lm_state_set_row_sampling": (C.c_int, [_P, C.c_int32, C.c_float, C.c_float, C.c_float, _P]),
     "ptts_lm_state_clear_row_sampling": (C.c_int, [_P, C.c_int32, _P]),
+    "ptts_lm_state_reserve_row_lsd": (C.c_int, [_P, C.c_int32, _P]),
+    "ptts_lm_state_set_row_lsd": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_lm_state_clear_row_lsd": (C.c_int, [_P, C.c_int32, _P]),
     "ptts_profile_start": (C.c_int, [_P]),
     "ptts_profile_stop": (C.c_int64, [_P, C.c_char_p, C.c_int64]),
     "ptts_mimi_state_create": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

@@ -23,6 +23,7 @@ from __future__ import annotations
 import collections
 import logging
 import math
+import numbers
 import queue
 import threading
 
@@ -115,17 +116,23 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
         self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
+        self.lsd = lsd         # the request's lsd_decode_steps, or None: the model's
         self.start = None      # global step of its first FlowLM step
 
 
 class ContinuousBatcher:
-    def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0):
+    def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
+                 max_lsd_decode_steps: int | None = None):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
+
+        `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
+        takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
+        same graphs as before.
 
         The scheduler never waits for the GPU on the step path: FlowLM step g and codec frame g are queued on the two
         streams of the "events" pipeline, and the EOS flags / PCM of a step are read from pinned memory `lag` <= nb steps
@@ -147,6 +154,12 @@ class ContinuousBatcher:
         self.st.set_noise(model.temp, noise_seed)
         for b in range(slots):
             self.st.set_row_active(b, False)
+        if max_lsd_decode_steps is not None:
+            k = int(max_lsd_decode_steps)
+            if k != max_lsd_decode_steps or not 1 <= k <= 64:
+                raise ValueError(f"max_lsd_decode_steps must be an integer in [1, 64], got {max_lsd_decode_steps}")
+            self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
+        self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                  mode="events", pcm_i16=(pcm_format == "i16"))
         self.pipe.restart()
@@ -158,6 +171,7 @@ class ContinuousBatcher:
         self.a_eos = np.full(slots, -1, np.int64)
         self.a_emit = np.full(slots, 0, np.int64)         # >= 0: no running job in the slot
         self.row_samp = [False] * slots                   # the slot's row carries a sampling override
+        self.row_lsd = [False] * slots                    # ... an lsd_decode_steps override
         # held by the background scheduler around each iteration: other users of the engine (e.g. a voice-prompt encode
         # on a request thread) take it to run between the scheduler's steps (`exclusive`)
         self.engine_lock = threading.RLock()
@@ -177,12 +191,14 @@ class ContinuousBatcher:
     # ---- submission (any thread) ---------------------------------------------------------------
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
-               eos_threshold: float | None = None) -> Request:
+               eos_threshold: float | None = None, lsd_decode_steps: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
         `temperature`, `noise_clamp` (<= 0: none) and `eos_threshold` apply to this request only; None means the model's
-        value.  A request that gives none of them runs with the model's settings exactly."""
+        value.  A request that gives none of them runs with the model's settings exactly.  `lsd_decode_steps` (an int in
+        [1, max_lsd_decode_steps]) is the number of Euler steps of this request's flow head; a batcher built without
+        `max_lsd_decode_steps` accepts only the model's value."""
         from .tts_model import _state_current_end
 
         m = self.model
@@ -203,6 +219,20 @@ class ContinuousBatcher:
             if not math.isfinite(e):
                 raise ValueError(f"eos_threshold must be a finite number, got {eos_threshold}")
             samp = (t, c, e)
+        lsd = None
+        if lsd_decode_steps is not None:
+            n = lsd_decode_steps
+            if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+                raise ValueError(f"lsd_decode_steps must be an integer, got {lsd_decode_steps!r}")
+            n = int(n)
+            if self.max_lsd is None:
+                if n != m.lsd_decode_steps:
+                    raise ValueError(f"lsd_decode_steps {n}: this batcher runs every request at {m.lsd_decode_steps} "
+                                     "(build it with max_lsd_decode_steps for per-request values)")
+            elif not 1 <= n <= self.max_lsd:
+                raise ValueError(f"lsd_decode_steps must be in [1, {self.max_lsd}], got {n}")
+            else:
+                lsd = n
         chunks = split_into_best_sentences(m.tokenizer.encode, m.tokenizer.sp, text, max_tokens,
                                            m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
         t_voice = _state_current_end(model_state)
@@ -220,7 +250,7 @@ class ContinuousBatcher:
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp))
+                             samp, lsd))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -297,6 +327,11 @@ class ContinuousBatcher:
                 elif self.row_samp[b]:
                     self.st.clear_row_sampling(b)
                 self.row_samp[b] = job.samp is not None
+                if job.lsd is not None:
+                    self.st.set_row_lsd(b, job.lsd)
+                elif self.row_lsd[b]:
+                    self.st.clear_row_lsd(b)
+                self.row_lsd[b] = job.lsd is not None
             eng.sync()  # the group state is freed below; its clone kernels must have run
         finally:
             if grp is not None:

@@ -124,6 +124,7 @@ struct ptts_engine {
   Lin te_l0[2], te_l2[2];
   float *te_freqs[2], *te_alpha[2];
   std::map<int, float *> tcomb;  // lsd_steps -> [S][flow_dim]
+  std::map<int, float *> tpack;  // K -> the tables of schedules 1..K packed: entry (N, i) at N (N - 1) / 2 + i
   float *te_scratch = nullptr;
   // Mimi
   float *emb_std, *emb_mean, *up_w, *freq_mimi;
@@ -189,6 +190,11 @@ struct ptts_lm_state {
   unsigned long long *fflags = nullptr;
   int *ferr = nullptr;
   int flow_steps = 0, flow_rt = 1, flow_ng = 1;
+  // per-row LSD schedules (ptts_lm_state_reserve_row_lsd): capacity K (0: none), packed time-embedding table of
+  // schedules 1..K, each row's own step count (0: the step's lsd_steps)
+  int lsd_cap = 0;
+  const float *lsd_tab = nullptr;
+  int *lsd_n = nullptr;
   // shared prefixes (KvPrefix): device table read by the attention kernels, its host mirror, and who owns each row's prefix.
   // An owner with borrowers is not freed by ptts_lm_state_destroy until the last borrower lets go (`zombie`).
   KvPrefix *d_pre = nullptr;
@@ -502,7 +508,7 @@ static unsigned lds_pad(int static_bytes) { return g_lds_target > static_bytes ?
 
 template <int TN, int TM, int WK, int WN, int WM>
 static void launch_cfg(hipStream_t st, const GemmArgs &a, int pre) {
-  dim3 grid(cdiv(a.NT, TN * WN), cdiv(a.MT, TM * WM));
+  dim3 grid(cdiv(a.NT, TN * WN), cdiv(a.MT, TM * WM), pre == PRE_ADDSILU_ROW ? std::max(1, a.row_nz) : 1);
   dim3 block(64 * WK * WN * WM);
   const unsigned dyn = lds_pad(WK > 1 ? WK * WN * WM * TN * TM * 1024 : 0);
   switch (pre) {
@@ -510,6 +516,8 @@ static void launch_cfg(hipStream_t st, const GemmArgs &a, int pre) {
     case PRE_LNFOLD: LDS_LAUNCH((gemm_kernel<TN, TM, WK, WN, WM, PRE_LNFOLD>), grid, block, dyn, st, a); break;
     case PRE_LNMOD: LDS_LAUNCH((gemm_kernel<TN, TM, WK, WN, WM, PRE_LNMOD>), grid, block, dyn, st, a); break;
     case PRE_ELU: LDS_LAUNCH((gemm_kernel<TN, TM, WK, WN, WM, PRE_ELU>), grid, block, dyn, st, a); break;
+    case PRE_ADDSILU_ROW: LDS_LAUNCH((gemm_kernel<TN, TM, WK, WN, WM, PRE_ADDSILU_ROW>), grid, block, dyn, st, a); break;
+    case PRE_LNMOD_ROW: LDS_LAUNCH((gemm_kernel<TN, TM, WK, WN, WM, PRE_LNMOD_ROW>), grid, block, dyn, st, a); break;
     default: LDS_LAUNCH((gemm_kernel<TN, TM, WK, WN, WM, PRE_ADDSILU>), grid, block, dyn, st, a); break;
   }
 }
@@ -789,7 +797,7 @@ static void launch_gemm_cfg(hipStream_t st, const GemmArgs &a, int pre, int cfg,
   const long wgs = sh[2] == 0 ? (long)cdiv(a.NT, sh[0]) * cdiv(a.MT, sh[1])
                               : (long)cdiv(a.NT, sh[0] * sh[3]) * cdiv(a.MT, sh[1] * sh[4]);
   const long threads = wgs * (sh[2] == 0 ? 256 : 64 * sh[2] * sh[3] * sh[4]);
-  std::string name = std::string(kCfgName[cfg]) + (pre == PRE_NONE ? "" : pre == PRE_LNFOLD ? "+ln" : pre == PRE_LNMOD ? "+lnmod" : pre == PRE_ELU ? "+elu" : "+addsilu") +
+  std::string name = std::string(kCfgName[cfg]) + (pre == PRE_NONE ? "" : pre == PRE_LNFOLD ? "+ln" : pre == PRE_LNMOD ? "+lnmod" : pre == PRE_ELU ? "+elu" : pre == PRE_ADDSILU_ROW ? "+addsilu_row" : pre == PRE_LNMOD_ROW ? "+lnmod_row" : "+addsilu") +
                      (a.wfmt == 1 ? "+q8" : a.wfmt == 2 ? "+b16" : a.wfmt == 3 ? "+split" : "") + "@" + std::to_string(threads);
   if (label) *label = name;
   ProfScope ps(st, name, bytes, 2.0 * M * N * K);
@@ -806,7 +814,14 @@ static void launch_gemm(hipStream_t st, const GemmArgs &a_in, int pre) {
     pcm_conv_kernel<<<cdiv(a.MT, 4), 256, 0, st>>>(a);
     return;
   }
-  const int cfg = choose_cfg(st, a, pre);
+  int cfg;
+  if (pre == PRE_ADDSILU_ROW || pre == PRE_LNMOD_ROW) {  // the tile of the plain GEMM: per-row schedules sum in the same order
+    GemmArgs b = a;
+    b.row_nz = 0;
+    cfg = choose_cfg(st, b, pre == PRE_LNMOD_ROW ? PRE_LNMOD : PRE_ADDSILU);
+  } else {
+    cfg = choose_cfg(st, a, pre);
+  }
   if (cfg < 0) {
     if (g_launch_err.empty())
       g_launch_err = std::string("no GEMM kernel for weight format ") + std::to_string(a.wfmt) + " with operand pre-processing " +
@@ -1573,6 +1588,21 @@ static int prepare_lsd(ptts_engine *e, int steps) {
   return 0;
 }
 
+// the tables of schedules 1..K in one buffer (per-row LSD schedules): copies of tcomb[N], so bitwise the same values
+static int prepare_lsd_pack(ptts_engine *e, int K) {
+  if (e->tpack.count(K)) return 0;
+  for (int n = 1; n <= K; ++n) CHK(prepare_lsd(e, n));
+  const size_t FD = e->cfg.flow_dim;
+  float *tab;
+  AllocScope alloc_scope(e->stream);
+  CHK(dallocT(e, &tab, (size_t)K * (K + 1) / 2 * FD));
+  for (int n = 1; n <= K; ++n)
+    HIPCHK(hipMemcpyAsync(tab + (size_t)n * (n - 1) / 2 * FD, e->tcomb[n], (size_t)n * FD * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->tpack[K] = tab;
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // FlowLM state
 static int alloc_scratch(ptts_engine *e, Scratch *s, int B, int Tq, int D, int H, int FF, int cap) {
@@ -1648,8 +1678,10 @@ static int build_lm_state(ptts_engine *e, ptts_lm_state *s) {
   CHK(dallocT(nullptr, &s->samp_on, B));
   CHK(dallocT(nullptr, &s->samp_noise, B));
   CHK(dallocT(nullptr, &s->samp_eos, B));
+  CHK(dallocT(nullptr, &s->lsd_n, B));
   s->h_active.assign(B, 1);
   set_int_kernel<<<cdiv(B, 256), 256, 0, e->stream>>>(s->active, B, 1);
+  set_int_kernel<<<cdiv(B, 256), 256, 0, e->stream>>>(s->lsd_n, B, 0);
   fill_kernel<<<cdiv(B * c.ldim, 256), 256, 0, e->stream>>>(s->lat_prev, (long)B * c.ldim, NAN);
   HIPCHK(hipStreamSynchronize(e->stream));
   CHK(ensure_flow(e, s, 1, e->stream));  // AdaLN modulation buffer + flow-cluster exchange slots for lsd_decode_steps = 1
@@ -1663,7 +1695,7 @@ static void lm_state_free(ptts_lm_state *s) {
   if (s->pre.x) free_scratch(&s->pre);
   hipFree(s->xlat); hipFree(s->latfm); hipFree(s->c); hipFree(s->ce); hipFree(s->mod); hipFree(s->fx);
   hipFree(s->fh); hipFree(s->f1); hipFree(s->lat); hipFree(s->lat_prev); hipFree(s->eos_logit); hipFree(s->is_eos); hipFree(s->rng_ctr); hipFree(s->active); hipFree(s->fstat);
-  hipFree(s->samp_on); hipFree(s->samp_noise); hipFree(s->samp_eos);
+  hipFree(s->samp_on); hipFree(s->samp_noise); hipFree(s->samp_eos); hipFree(s->lsd_n);
   hipFree(s->fexch); hipFree(s->fflags); hipFree(s->ferr); hipFree(s->lexch); hipFree(s->lflags);
   delete s;
 }
@@ -1719,6 +1751,7 @@ extern "C" int ptts_lm_state_reset(ptts_lm_state *s, void *stream) {
   std::fill(s->h_active.begin(), s->h_active.end(), 1);
   set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->active, s->B, 1);
   set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->samp_on, s->B, 0);
+  set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->lsd_n, s->B, 0);
   LAUNCHCHK();
   return 0;
 }
@@ -1962,6 +1995,42 @@ extern "C" int ptts_lm_state_clear_row_sampling(ptts_lm_state *s, int32_t row, v
   return 0;
 }
 
+static int ensure_flow(ptts_engine *e, ptts_lm_state *s, int steps, hipStream_t st);
+
+extern "C" int ptts_lm_state_reserve_row_lsd(ptts_lm_state *s, int32_t K, void *stream) {
+  if (!s || K < 1 || K > 64) return fail(-1, "reserve_row_lsd: capacity must be in [1, 64]");
+  ptts_engine *e = s->e;
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  if (s->n_graphs > 0) return fail(-1, "reserve_row_lsd: the state has captured graphs (they hold its flow buffers): reserve before capturing");
+  K = std::max(K, (int32_t)s->lsd_cap);  // never shrinks
+  CHK(ensure_flow(e, s, K, S(e, stream)));
+  CHK(prepare_lsd_pack(e, K));
+  s->lsd_tab = e->tpack[K];
+  s->lsd_cap = K;
+  return 0;
+}
+
+extern "C" int ptts_lm_state_set_row_lsd(ptts_lm_state *s, int32_t row, int32_t n, void *stream) {
+  if (!s || row < 0 || row >= s->B) return fail(-1, "set_row_lsd: row out of range");
+  if (s->lsd_cap < 1) return fail(-1, "set_row_lsd: the state has no per-row LSD capacity (ptts_lm_state_reserve_row_lsd)");
+  if (n < 1 || n > s->lsd_cap) return fail(-1, "set_row_lsd: lsd_decode_steps must be in [1, " + std::to_string(s->lsd_cap) + "]");
+  hipStream_t st = S(s->e, stream);
+  ENGINE_LOCK(s->e);
+  set_int_kernel<<<1, 64, 0, st>>>(s->lsd_n + row, 1, n);
+  LAUNCHCHK();
+  return 0;
+}
+
+extern "C" int ptts_lm_state_clear_row_lsd(ptts_lm_state *s, int32_t row, void *stream) {
+  if (!s || row < 0 || row >= s->B) return fail(-1, "clear_row_lsd: row out of range");
+  hipStream_t st = S(s->e, stream);
+  ENGINE_LOCK(s->e);
+  set_int_kernel<<<1, 64, 0, st>>>(s->lsd_n + row, 1, 0);
+  LAUNCHCHK();
+  return 0;
+}
+
 extern "C" int ptts_profile_start(ptts_engine *e) {
   if (!e) return fail(-1, "null engine");
   ENGINE_LOCK(e);
@@ -2044,23 +2113,29 @@ static int ensure_flow(ptts_engine *e, ptts_lm_state *s, int steps, hipStream_t 
   return 0;
 }
 
-template <int RT>
+template <int RT, bool ROWLSD>
 static void launch_flow_rt(hipStream_t st, const FlowArgs &fa, int kpw) {
   const dim3 grid(fa.NCL * fa.FDF), block(FLOW_THREADS);
   switch (kpw) {
-    case 1: flow_cluster_kernel<RT, 1><<<grid, block, 0, st>>>(fa); break;
-    case 2: flow_cluster_kernel<RT, 2><<<grid, block, 0, st>>>(fa); break;
-    default: flow_cluster_kernel<RT, 4><<<grid, block, 0, st>>>(fa); break;
+    case 1: flow_cluster_kernel<RT, 1, ROWLSD><<<grid, block, 0, st>>>(fa); break;
+    case 2: flow_cluster_kernel<RT, 2, ROWLSD><<<grid, block, 0, st>>>(fa); break;
+    default: flow_cluster_kernel<RT, 4, ROWLSD><<<grid, block, 0, st>>>(fa); break;
   }
 }
 
+// LSD steps the flow buffers of a step must hold: the step's own count, or the per-row capacity when it is larger
+static int flow_steps_of(const ptts_lm_state *s, int lsd_steps) { return std::max(lsd_steps, s->lsd_cap); }
+
+// with per-row schedules (s->lsd_cap > 0) `lsd_steps` is the count of rows without an override and the slots are laid out
+// for flow_steps_of(s, lsd_steps) steps
 static void launch_flow_cluster(hipStream_t st, ptts_engine *e, ptts_lm_state *s, int lsd_steps, float *d_latent_out) {
   const ptts_config &c = e->cfg;
   const int FDF = c.flow_dim / 16, LF = c.ldim / 16;
   FlowArgs fa;
   memset(&fa, 0, sizeof fa);
   fa.MT = s->MT; fa.M = s->B; fa.NG = s->flow_ng; fa.NCL = std::max(1, std::min(s->flow_ng, std::min(e->opt_flow_max_cus, e->n_cus) / FDF)); fa.FDF = FDF; fa.LF = LF; fa.AF = e->adaln.NT;
-  fa.depth = c.flow_depth; fa.steps = lsd_steps; fa.ldim = c.ldim;
+  const bool rowlsd = s->lsd_cap > 0;
+  fa.depth = c.flow_depth; fa.steps = rowlsd ? flow_steps_of(s, lsd_steps) : lsd_steps; fa.ldim = c.ldim;
   fa.w_in = e->input_proj.w; fa.b_in = e->input_proj.bias;
   for (int r = 0; r < c.flow_depth; ++r) {
     fa.w_l0[r] = e->res[r].l0.w; fa.b_l0[r] = e->res[r].l0.bias;
@@ -2073,15 +2148,21 @@ static void launch_flow_cluster(hipStream_t st, ptts_engine *e, ptts_lm_state *s
   fa.lat = s->lat; fa.lat_out1 = s->lat_prev; fa.lat_out2 = d_latent_out;
   fa.inv_steps = 1.0f / (float)lsd_steps;
   fa.exch = s->fexch; fa.flags = s->fflags; fa.ctr = s->rng_ctr; fa.err = s->ferr;
+  fa.row_n = rowlsd ? s->lsd_n : nullptr; fa.row_ndef = lsd_steps;
   // weights of the chain once per cluster-set (L2 / Infinity Cache absorb the clusters' re-reads) + modulations + io
   const double wbytes = 4.0 * 256 * ((double)FDF * LF + 2.0 * c.flow_depth * FDF * FDF + (double)LF * FDF);
   const double flops = 2.0 * s->B * 256.0 * ((double)FDF * LF + 2.0 * c.flow_depth * FDF * FDF + (double)LF * FDF) * lsd_steps;
-  ProfScope ps(st, "flow_cluster@" + std::to_string((long)fa.NCL * FDF * FLOW_THREADS),
+  ProfScope ps(st, std::string(rowlsd ? "flow_cluster_rowlsd@" : "flow_cluster@") + std::to_string((long)fa.NCL * FDF * FLOW_THREADS),
                lsd_steps * (wbytes + 4.0 * s->B * 16.0 * e->adaln.NT), flops);
   const int kpw = cdiv(std::max(FDF, LF), FLOW_WORKERS);
   s->coop_wgs = std::max(s->coop_wgs, fa.NCL * FDF);
-  if (s->flow_rt == 2) launch_flow_rt<2>(st, fa, kpw);
-  else launch_flow_rt<1>(st, fa, kpw);
+  if (rowlsd) {
+    if (s->flow_rt == 2) launch_flow_rt<2, true>(st, fa, kpw);
+    else launch_flow_rt<1, true>(st, fa, kpw);
+  } else {
+    if (s->flow_rt == 2) launch_flow_rt<2, false>(st, fa, kpw);
+    else launch_flow_rt<1, false>(st, fa, kpw);
+  }
 }
 
 
@@ -2233,7 +2314,7 @@ extern "C" int ptts_lm_prefill(ptts_engine *e, ptts_lm_state *s, const float *d_
 static int coop_wgs_of_step(const ptts_engine *e, const ptts_lm_state *s, int lsd_steps) {
   int w = 0;
   const ptts_config &c = e->cfg;
-  if (flow_cluster_ok(e, s) && lsd_steps <= s->flow_steps) {
+  if (flow_cluster_ok(e, s) && flow_steps_of(s, lsd_steps) <= s->flow_steps) {
     const int FDF = c.flow_dim / 16;
     w = std::max(1, std::min(s->flow_ng, std::min(e->opt_flow_max_cus, e->n_cus) / FDF)) * FDF;
   }
@@ -2288,30 +2369,51 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
   a.eos_logit = s->eos_logit; a.is_eos = s->is_eos;
   a.eos_logit2 = d_eos_logit; a.is_eos2 = d_is_eos;  // caller's buffers are written by the epilogue itself
   a.tail_offset = s->offset; a.tail_ctr = s->rng_ctr; a.tail_active = s->active;  // the step's bookkeeping rides along (was a launch)
-  const bool silu_in_head = lsd_steps == 1;  // s->ce then holds silu(t_emb + cond) and the modulation GEMM loads it as is
+  // s->ce then holds silu(t_emb + cond) and the modulation GEMM loads it as is (not with per-row schedules: rows differ)
+  const bool silu_in_head = lsd_steps == 1 && s->lsd_cap == 0;
   if (silu_in_head) { a.act = ACT_SILU; a.prevec = tcomb; }
   launch_gemm(st, a, PRE_LNFOLD);
   const int AF = e->adaln.NT;
-  if (flow_cluster_ok(e, s) && lsd_steps <= s->flow_steps) {
+  const bool rowlsd = s->lsd_cap > 0;
+  const int nit = rowlsd ? flow_steps_of(s, lsd_steps) : lsd_steps;  // LSD iterations enqueued
+  auto row_lsd = [&](GemmArgs &g, int i) {  // per-row schedules of step i (GemmArgs::row_n)
+    g.row_n = s->lsd_n; g.row_tab = s->lsd_tab; g.row_ndef = lsd_steps; g.row_i = i;
+  };
+  if (flow_cluster_ok(e, s) && nit <= s->flow_steps) {
     // the AdaLN modulations of every LSD step (they depend on the step's (s, t) only through t_emb), then the whole
     // chain + Euler loop in ONE launch
-    for (int i = 0; i < lsd_steps; ++i) {
+    if (rowlsd) {  // every step in one launch (grid.z), each row with its own schedule
       SITE("flow.adaln");
       a = mk_gemm(e->adaln, s->ce, FDF, MT, B);
-      a.prevec = tcomb + (size_t)i * FD; a.Y = s->mod + (size_t)i * MT * 256 * AF; a.YF = AF;
-      launch_gemm(st, a, silu_in_head ? PRE_NONE : PRE_ADDSILU);
+      a.prevec = tcomb; a.Y = s->mod; a.YF = AF;
+      row_lsd(a, 0);
+      a.row_nz = nit; a.row_zstride = (long)MT * 256 * AF;
+      launch_gemm(st, a, PRE_ADDSILU_ROW);
+    } else {
+      for (int i = 0; i < lsd_steps; ++i) {
+        SITE("flow.adaln");
+        a = mk_gemm(e->adaln, s->ce, FDF, MT, B);
+        a.prevec = tcomb + (size_t)i * FD; a.Y = s->mod + (size_t)i * MT * 256 * AF; a.YF = AF;
+        launch_gemm(st, a, silu_in_head ? PRE_NONE : PRE_ADDSILU);
+      }
     }
     SITE("flow.cluster");
     launch_flow_cluster(st, e, s, lsd_steps, d_latent_out);
     s->latfm_noise = true;  // the cluster reads latfm, never writes it
   } else {
   s->latfm_noise = false;  // the per-layer path keeps the FM copy of the running latent there
-  for (int i = 0; i < lsd_steps; ++i) {
+  for (int i = 0; i < nit; ++i) {
     // all AdaLN modulations of the step in one GEMM on silu(t_emb + cond)  (mlp.py:107,127,210)
     SITE("flow.adaln");
     a = mk_gemm(e->adaln, s->ce, FDF, MT, B);
     a.prevec = tcomb + (size_t)i * FD; a.Y = s->mod; a.YF = AF;
-    launch_gemm(st, a, silu_in_head ? PRE_NONE : PRE_ADDSILU);
+    if (rowlsd) {  // row m adds its own schedule's embedding of step i (rows past their count: tiles exit or are unused)
+      a.prevec = tcomb;
+      row_lsd(a, i);
+      launch_gemm(st, a, PRE_ADDSILU_ROW);
+    } else {
+      launch_gemm(st, a, silu_in_head ? PRE_NONE : PRE_ADDSILU);
+    }
     SITE("flow.input_proj");
     a = mk_gemm(e->input_proj, s->latfm, LF, MT, B);
     a.Y = s->fx; a.YF = FDF;
@@ -2342,7 +2444,11 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
     a.stat_in = s->fstat; a.stat_nt = FDF;
     a.epi = EPI_LATENT; a.lat = s->lat; a.ldim = c.ldim; a.inv_steps = 1.0f / (float)lsd_steps; a.Y = s->latfm; a.YF = LF;
     if (i == lsd_steps - 1) { a.lat_out1 = s->lat_prev; a.lat_out2 = d_latent_out; }  // next step's input + caller's copy
-    launch_gemm(st, a, PRE_LNMOD);
+    if (rowlsd) {  // every row writes them at its own last step
+      row_lsd(a, i);
+      a.lat_out1 = s->lat_prev; a.lat_out2 = d_latent_out;
+    }
+    launch_gemm(st, a, rowlsd ? PRE_LNMOD_ROW : PRE_LNMOD);
   }
   }
   SITE("");
@@ -2355,7 +2461,7 @@ extern "C" int ptts_lm_decode_step(ptts_engine *e, ptts_lm_state *s, const float
   ENGINE_LOCK(e);
   HIPCHK(hipSetDevice(e->device));
   CHK(prepare_lsd(e, lsd_steps));
-  CHK(ensure_flow(e, s, lsd_steps, S(e, stream)));
+  CHK(ensure_flow(e, s, flow_steps_of(s, lsd_steps), S(e, stream)));
   CHK(ensure_lm_cluster(e, s, S(e, stream)));
   for (int b = 0; b < s->B; ++b)
     if (s->h_off[b] + 1 > s->cap) return fail(-5, "decode: KV cache capacity exceeded");
@@ -3121,7 +3227,7 @@ extern "C" int ptts_graph_capture_lm_step(ptts_engine *e, ptts_lm_state *s, cons
   ENGINE_LOCK(e);
   HIPCHK(hipSetDevice(e->device));
   CHK(prepare_lsd(e, lsd_steps));
-  CHK(ensure_flow(e, s, lsd_steps, e->stream));
+  CHK(ensure_flow(e, s, flow_steps_of(s, lsd_steps), e->stream));
   CHK(ensure_lm_cluster(e, s, e->stream));
   ptts_graph *g = new ptts_graph();
   g->lm = s;
@@ -3157,7 +3263,7 @@ extern "C" int ptts_graph_capture_pipelined(ptts_engine *e, ptts_lm_state *s, pt
   ENGINE_LOCK(e);
   HIPCHK(hipSetDevice(e->device));
   CHK(prepare_lsd(e, lsd_steps));
-  CHK(ensure_flow(e, s, lsd_steps, e->stream));
+  CHK(ensure_flow(e, s, flow_steps_of(s, lsd_steps), e->stream));
   CHK(ensure_lm_cluster(e, s, e->stream));
   ptts_graph *g = new ptts_graph();
   g->lm = s;

@@ -47,6 +47,9 @@ struct FlowArgs {
   u64 *flags;          // [NG][steps * (2 depth + 2)][FDF]
   const int *ctr;      // the state's step counter (incremented by step_tail_kernel after this launch)
   int *err;            // set to 1 when a poll gave up
+  // per-row LSD schedules (flow_cluster_kernel<.., true>): row m runs row_lsd_n(row_n, row_ndef, m) <= steps Euler steps
+  const int *row_n;
+  int row_ndef;
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t flow_rsrc(const void *p) {
@@ -73,8 +76,12 @@ __device__ __forceinline__ bool flow_wait(const u64 *f, int np, u64 epoch, int l
 }
 
 // RT = row tiles per cluster (the host uses 1: one cluster per 16 rows keeps the worker waves within the 168
-// registers a 9-wave workgroup leaves per lane), KPW = k-fragments per worker wave (>= ceil(max(FDF, LF) / 8))
-template <int RT, int KPW>
+// registers a 9-wave workgroup leaves per lane), KPW = k-fragments per worker wave (>= ceil(max(FDF, LF) / 8)).
+// ROWLSD: per-row schedules.  `steps` is then the capacity the slots are laid out for; a row group runs the phases of
+// max n over its rows (every workgroup reads the same words, written before the launch), each row's Euler update uses
+// its own 1 / n, a row past its count is frozen and writes its outputs at its own last step.  Phases past a group's
+// bound never run, so their flags and slots are simply not touched.
+template <int RT, int KPW, bool ROWLSD = false>
 __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int FDF = a.FDF, LF = a.LF;
@@ -100,6 +107,21 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) 
   int mtc[RT];  // clamped row tiles (a partially filled last cluster computes duplicates and stores nothing for them)
 #pragma unroll
   for (int t = 0; t < RT; ++t) mtc[t] = min(mt0 + t, a.MT - 1);
+  int nph = NPH;  // phases this group runs
+  int nrow[RT];   // ROWLSD: LSD steps of this lane's row of each tile
+  if constexpr (ROWLSD) {
+    int mx = 0;
+    const int mg = 16 * mt0 + lane;  // RT * 16 <= 64 rows of the group, one per lane
+    if (lane < RT * 16 && mg < a.M) mx = row_lsd_n(a.row_n, a.row_ndef, mg);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+    nph = __builtin_amdgcn_readfirstlane(mx) * PPS;  // the same in every lane: a scalar loop bound
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const int m = 16 * (mt0 + t) + (lane & 15);
+      nrow[t] = m < a.M ? row_lsd_n(a.row_n, a.row_ndef, m) : 1;
+    }
+  }
 
   // phase p of the launch: kind 0 = input_proj, 1 = block linear 0 (AdaLN-LN on load, SiLU), 2 = block linear 2
   // (gate + residual), 3 = final layer (no-affine LN + modulation on load, Euler update)
@@ -157,7 +179,7 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) 
     load_w(0);
   }
 
-  for (int p = 0; p < NPH; ++p) {
+  for (int p = 0; p < nph; ++p) {
     const int i = p / PPS, ph = p - i * PPS;
     const int kind = kind_of(ph);
     const int KF = kind == 0 ? LF : FDF;
@@ -226,7 +248,7 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) 
           if (lane < 16) { st[wave][t][lane][0] = s1; st[wave][t][lane][1] = s2; }
         }
       }
-    } else if (p + 1 < NPH) {
+    } else if (p + 1 < nph) {
       load_epi(p + 1, n_bias, n_gate);  // lands while the workers compute
     }
     if (lnmod) __syncthreads();  // B: row statistics of all workers are in LDS
@@ -261,12 +283,12 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) 
     }
     __syncthreads();  // C: partial accumulators are in LDS
     if (!coord) {
-      if (p + 1 < NPH) load_w((p + 1) % PPS);  // in flight while the hand-off completes
+      if (p + 1 < nph) load_w((p + 1) % PPS);  // in flight while the hand-off completes
       continue;
     }
     // ---- coordinator: reduce (fixed order), epilogue, publish
     const bool last_step = i == a.steps - 1;
-    const bool publish = p + 1 < NPH && (kind != 3 || j < LF);
+    const bool publish = p + 1 < nph && (kind != 3 || j < LF);
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
       f32x4 s = red[0][t][lane];
@@ -279,10 +301,16 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) 
       else if (kind == 2) { xres[t] = xres[t] + e_gate[t] * s; out = xres[t]; }
       else {
         // Euler update of lsd_decode: current += flow_dir / num_steps (reference flow_lm.py:39)
-        latv[t] = latv[t] + s * a.inv_steps;
+        bool last = last_step;
+        if constexpr (ROWLSD) {
+          if (i < nrow[t]) latv[t] = latv[t] + s * (1.0f / (float)nrow[t]);
+          last = i == nrow[t] - 1;
+        } else {
+          latv[t] = latv[t] + s * a.inv_steps;
+        }
         out = latv[t];
         const int m = 16 * (mt0 + t) + (lane & 15);
-        if (last_step && j < LF && mt0 + t < a.MT && m < a.M) {
+        if (last && j < LF && mt0 + t < a.MT && m < a.M) {
           const size_t o = (size_t)m * a.ldim + 16 * j + 4 * (lane >> 4);
           *(f32x4 *)(a.lat + o) = out;
           if (a.lat_out1) *(f32x4 *)(a.lat_out1 + o) = out;

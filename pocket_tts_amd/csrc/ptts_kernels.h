@@ -61,7 +61,7 @@ __device__ __forceinline__ unsigned to_f8x4(f32x4 v) {
 #define STAMP(i)
 #endif
 
-enum { PRE_NONE = 0, PRE_ELU = 1, PRE_ADDSILU = 2, PRE_LNFOLD = 3, PRE_LNMOD = 4 };
+enum { PRE_NONE = 0, PRE_ELU = 1, PRE_ADDSILU = 2, PRE_LNFOLD = 3, PRE_LNMOD = 4, PRE_ADDSILU_ROW = 5, PRE_LNMOD_ROW = 6 };
 enum { EPI_STORE = 0, EPI_RES, EPI_GATE, EPI_QKV, EPI_HEAD, EPI_LATENT, EPI_CONVTR, EPI_PCM };
 enum { ACT_NONE = 0, ACT_GELU, ACT_SILU, ACT_ELU };
 
@@ -192,6 +192,16 @@ struct GemmArgs {
   const float *pcm_w;
   float *pcm_part, *pcm_carry;
   long pcm_cstride;  // floats between the two frame parities of pcm_carry
+  // per-row LSD schedules (ptts_lm_state_reserve_row_lsd).  row_n[m] = row m's own number of Euler steps, 0: row_ndef.
+  // PRE_ADDSILU_ROW: like PRE_ADDSILU, but row m adds its own time embedding, row_tab entry (n, i) at n (n - 1) / 2 + i
+  // (rows without an override: prevec + i * K, the step's own table), for the LSD step i = row_i + blockIdx.z; grid.z =
+  // row_nz steps in one launch, Y advancing by row_zstride floats per step; a workgroup whose rows are all past their
+  // count exits at once.  PRE_LNMOD_ROW (= PRE_LNMOD with EPI_LATENT): step row_i leaves rows past their count as they
+  // are, scales by the row's own 1 / n and writes lat_out1 / lat_out2 at the row's last step only.
+  const int *row_n;
+  const float *row_tab;
+  int row_ndef, row_i, row_nz;
+  long row_zstride;
 };
 
 // Workgroup -> tile mapping.  Hardware deals consecutive workgroup ids round-robin over the 8 XCDs (ids b and
@@ -221,6 +231,12 @@ __device__ __forceinline__ f32x4 pre4(f32x4 x, const float *prevec, int kf, int 
   return x;
 }
 
+// number of LSD steps of row m under per-row schedules (GemmArgs::row_n, FlowArgs::row_n): its override, else the step's
+__device__ __forceinline__ int row_lsd_n(const int *row_n, int ndef, int m) {
+  const int v = row_n[m];
+  return v > 0 ? v : ndef;
+}
+
 // (sum, sum of squares) of each row over the 16 columns of one output tile: lanes l, l^16, l^32, l^48 hold the row
 __device__ __forceinline__ void tile_row_stats(const GemmArgs &a, f32x4 v, int nt, int mt, int lane) {
   float s1 = (v.x + v.y) + (v.z + v.w);
@@ -241,6 +257,7 @@ struct EpiPre {
   f32x4 bias, r, g, ln_s, ln_c, scale;
 };
 
+template <bool ROWLAT = false>  // EPI_LATENT with per-row schedules (PRE_LNMOD_ROW)
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int nt, int mt, int lane, int par,
                                               const EpiPre *pf = nullptr) {
   const int ml = lane & 15, g = lane >> 4;
@@ -322,7 +339,20 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int 
     case EPI_LATENT: {
       // Euler update of lsd_decode: current += flow_dir / num_steps (reference flow_lm.py:39)
       f32x4 v;
-      if (m < a.M) {
+      if (ROWLAT && m < a.M) {  // per-row schedules: a row past its count is frozen
+        float *p = a.lat + (size_t)m * a.ldim + n0;
+        const int n = row_lsd_n(a.row_n, a.row_ndef, m);
+        if (a.row_i < n) {
+          v = *(f32x4 *)p + acc * (1.0f / (float)n);
+          *(f32x4 *)p = v;
+        } else {
+          v = *(f32x4 *)p;
+        }
+        if (a.row_i == n - 1) {
+          if (a.lat_out1) *(f32x4 *)(a.lat_out1 + (size_t)m * a.ldim + n0) = v;
+          if (a.lat_out2) *(f32x4 *)(a.lat_out2 + (size_t)m * a.ldim + n0) = v;
+        }
+      } else if (m < a.M) {
         float *p = a.lat + (size_t)m * a.ldim + n0;
         v = *(f32x4 *)p + acc * a.inv_steps;
         *(f32x4 *)p = v;
@@ -353,8 +383,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int 
 }
 
 // TN x TM 16x16 tiles per wave; WK waves split K (LDS-reduced), WN x WM waves tile N x M.
-template <int TN, int TM, int WK, int WN, int WM, int PRE, int WF = 0>
+template <int TN, int TM, int WK, int WN, int WM, int PRE_, int WF = 0>
 __global__ __launch_bounds__(64 * WK * WN * WM) void gemm_kernel(GemmArgs a) {
+  constexpr bool ROWLAT = PRE_ == PRE_LNMOD_ROW;  // PRE_LNMOD with the per-row EPI_LATENT
+  constexpr int PRE = ROWLAT ? PRE_LNMOD : PRE_;
   if constexpr (PTTS_ABLATE & 128) return;  // ablation 128 (timing only): empty kernels = launch + boundary cost
   STAMP(0);
   constexpr bool Q8 = WF == 1;   // int8 weights, fp32 activations, fp32 MFMA
@@ -405,6 +437,23 @@ __global__ __launch_bounds__(64 * WK * WN * WM) void gemm_kernel(GemmArgs a) {
     int t = a.ntaps > 1 ? row % a.T : 0;
     tin[j] = t;
     bT[j] = row - t;
+  }
+  // PRE_ADDSILU_ROW: each lane's row's time embedding of LSD step i (see GemmArgs::row_n)
+  const float *prow[TM];
+  if constexpr (PRE == PRE_ADDSILU_ROW) {
+    const int i = a.row_i + (int)blockIdx.z, K = a.KF * 16;
+    int live = 0;
+#pragma unroll
+    for (int j = 0; j < TM; ++j) {
+      const int m = 16 * mtc[j] + (lane & 15);
+      const int own = m < a.M ? a.row_n[m] : 0;
+      const int n = own > 0 ? own : a.row_ndef;
+      live |= (m < a.M && i < n) ? 1 : 0;
+      const int ie = min(i, n - 1);  // rows past their count: an entry of their own schedule (the result is not used)
+      prow[j] = (own > 0 ? a.row_tab + (size_t)(n * (n - 1) / 2 + ie) * K : a.prevec + (size_t)ie * K) + 4 * (lane >> 4);
+    }
+    if (!__syncthreads_or(live)) return;  // every row of the workgroup is past its count
+    a.Y += (size_t)blockIdx.z * a.row_zstride;
   }
   float lmu[TM], lrs[TM];  // PRE_LNMOD row statistics
   if constexpr (PRE == PRE_LNMOD && (PTTS_ABLATE & 64)) {  // ablation 64 (timing only): no statistics pass
@@ -585,6 +634,14 @@ __global__ __launch_bounds__(64 * WK * WN * WM) void gemm_kernel(GemmArgs a) {
     for (int u = 0; u < UU; ++u) {
 #pragma unroll
       for (int j = 0; j < TM; ++j) x[u][j] = pre4<PRE>(x[u][j], a.prevec, kf + u, lane);
+      if constexpr (PRE == PRE_ADDSILU_ROW) {
+#pragma unroll
+        for (int j = 0; j < TM; ++j) {
+          const f32x4 t = *(const f32x4 *)(prow[j] + 16 * (kf + u));
+          f32x4 &v = x[u][j];
+          v.x = silu_f(v.x + t.x); v.y = silu_f(v.y + t.y); v.z = silu_f(v.z + t.z); v.w = silu_f(v.w + t.w);
+        }
+      }
       if constexpr (PRE == PRE_LNMOD) {
         const int k = 16 * (kf + u) + 4 * (lane >> 4);
 #pragma unroll
@@ -783,7 +840,7 @@ __global__ __launch_bounds__(64 * WK * WN * WM) void gemm_kernel(GemmArgs a) {
         f32x4 sum = red[(((0 * WN * WM + grp) * TN + i) * TM + j) * 64 + lane];
         for (int s2 = 1; s2 < WK; ++s2) sum += red[(((s2 * WN * WM + grp) * TN + i) * TM + j) * 64 + lane];
         const EpiPre *pf = &epf[(i * TM + j) / WK];
-        if (nt0 + i < a.NT && mt0 + j < a.MT) gemm_epilogue(a, ln_fix(sum, nt0 + i, j, pf), nt0 + i, mt0 + j, lane, par, pf);
+        if (nt0 + i < a.NT && mt0 + j < a.MT) gemm_epilogue<ROWLAT>(a, ln_fix(sum, nt0 + i, j, pf), nt0 + i, mt0 + j, lane, par, pf);
       }
   } else {
     if constexpr (PRE == PRE_LNFOLD) {
@@ -798,7 +855,7 @@ __global__ __launch_bounds__(64 * WK * WN * WM) void gemm_kernel(GemmArgs a) {
     for (int i = 0; i < TN; ++i)
 #pragma unroll
       for (int j = 0; j < TM; ++j)
-        if (nt0 + i < a.NT && mt0 + j < a.MT) gemm_epilogue(a, ln_fix(accs[i][j], nt0 + i, j, nullptr), nt0 + i, mt0 + j, lane, par);
+        if (nt0 + i < a.NT && mt0 + j < a.MT) gemm_epilogue<ROWLAT>(a, ln_fix(accs[i][j], nt0 + i, j, nullptr), nt0 + i, mt0 + j, lane, par);
   }
   STAMP(4);
   (void)NW;

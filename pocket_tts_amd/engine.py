@@ -81,6 +81,19 @@ class LMState:
         """row `row` returns to the state's temperature (`set_noise`) and the step's EOS threshold"""
         _lib.check(self.engine.lib.ptts_lm_state_clear_row_sampling(self.handle, row, self.engine._sp))
 
+    def reserve_row_lsd(self, K: int):
+        """Per-row LSD schedules of up to `K` Euler steps (include/ptts.h); before any graph of this state is captured"""
+        _lib.check(self.engine.lib.ptts_lm_state_reserve_row_lsd(self.handle, int(K), self.engine._sp))
+
+    def set_row_lsd(self, row: int, n: int):
+        """row `row` runs `n` (1 <= n <= the reserved K) Euler steps of the flow head instead of the step's lsd_steps;
+        read by the kernels at run time, so captured steps pick it up"""
+        _lib.check(self.engine.lib.ptts_lm_state_set_row_lsd(self.handle, row, int(n), self.engine._sp))
+
+    def clear_row_lsd(self, row: int):
+        """row `row` returns to the step's lsd_steps"""
+        _lib.check(self.engine.lib.ptts_lm_state_clear_row_lsd(self.handle, row, self.engine._sp))
+
     def error(self) -> bool:
         """True after a cooperative kernel of this state gave up waiting for a peer workgroup"""
         r = self.engine.lib.ptts_lm_state_error(self.handle, self.engine._sp)

@@ -96,7 +96,10 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--codec-bf16", action="store_true")
     s.add_argument("--device", default="cuda:0")
     s.add_argument("--temperature", type=float, default=0.7, help="Default temperature of a request")
-    s.add_argument("--lsd-decode-steps", type=int, default=1)
+    s.add_argument("--lsd-decode-steps", type=int, default=1, help="Default lsd_decode_steps of a request")
+    s.add_argument("--max-lsd-decode-steps", type=int, default=None,
+                   help="Largest lsd_decode_steps a request may ask for (default: --lsd-decode-steps).  A step takes as "
+                        "long as its slowest rows: one request at a high count slows every request in the batch")
     s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
     s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
     s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
@@ -128,7 +131,7 @@ def serve_app(args) -> int:
                                 device=args.device)
     # the model's noise clamp reaches every request as a per-request setting (server.py)
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
-                     default_voice=args.default_voice)
+                     default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 

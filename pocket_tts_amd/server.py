@@ -36,6 +36,7 @@ INDEX_HTML = """<!doctype html>
 <form action="/tts" method="post" enctype="multipart/form-data">
 <p><textarea name="text" rows="4" cols="60">Hello world.</textarea></p>
 <p>Voice name <input name="voice_url"> or WAV prompt <input type="file" name="voice_wav" accept=".wav"></p>
+<p>LSD decode steps <input name="lsd_decode_steps" size="3"> (empty: the server's default)</p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -121,19 +122,40 @@ def parse_settings(fields: dict) -> dict:
     return out
 
 
+def parse_lsd_steps(fields: dict, max_lsd_decode_steps: int) -> int | None:
+    """the optional `lsd_decode_steps` field: an integer in [1, max_lsd_decode_steps] (absent or empty: None)"""
+    raw = fields.get("lsd_decode_steps")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        v = int(raw)
+    except ValueError:
+        raise FormError(f"lsd_decode_steps must be an integer, got {raw!r}") from None
+    if not 1 <= v <= max_lsd_decode_steps:
+        raise FormError(f"lsd_decode_steps must be in [1, {max_lsd_decode_steps}], got {raw!r}")
+    return v
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
-               batcher_factory=None):
+               batcher_factory=None, max_lsd_decode_steps: int | None = None):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
-    noise clamp.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    noise clamp.  A request's `lsd_decode_steps` may be 1 .. `max_lsd_decode_steps` (default: the model's
+    `lsd_decode_steps`; a larger maximum gives the batcher per-row LSD schedules).  `batcher_factory(model, slots,
+    capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
+    own_lsd = getattr(model, "lsd_decode_steps", 1)
+    max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
     if batcher_factory is None:
         from .batching import ContinuousBatcher
 
+        # no per-row capacity when the maximum is the model's own count: the batcher's graphs are those of before
+        reserve = max_lsd if max_lsd != own_lsd else None
+
         def batcher_factory(model, slots, capacity):
-            return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16")
+            return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -216,6 +238,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             if not text.strip():
                 raise FormError("Text cannot be empty")
             settings = parse_settings(fields)
+            lsd = parse_lsd_steps(fields, max_lsd)
+            if lsd is not None:
+                settings["lsd_decode_steps"] = lsd
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:
