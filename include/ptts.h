@@ -107,8 +107,8 @@ void ptts_destroy(ptts_engine *e);
 /* ---- FlowLM state: init_states(flow_lm, B, T) (stateful_module.py:7-16, transformer.py:46-57) */
 int ptts_lm_state_create(ptts_engine *e, int32_t batch, int32_t t_cap, ptts_lm_state **out);
 void ptts_lm_state_destroy(ptts_lm_state *s);
-/* zero offsets (fresh init_states); also clears every row's sampling override (ptts_lm_state_set_row_sampling) and LSD
- * override (ptts_lm_state_set_row_lsd) */
+/* zero offsets (fresh init_states); also clears every row's sampling override (ptts_lm_state_set_row_sampling), LSD
+ * override (ptts_lm_state_set_row_lsd) and seed (ptts_lm_state_set_row_seed) */
 int ptts_lm_state_reset(ptts_lm_state *s, void *stream);
 /* Import / export one layer in the reference layout cache f32[2, src_batch, t, H, 64] (device) with
  * `t` valid positions (transformer.py:32-36; voice files tts_model.py:1047-1072).  On import,
@@ -154,6 +154,22 @@ int ptts_lm_decode_step(ptts_engine *e, ptts_lm_state *s, const float *d_latent_
  * counter-based device generator (the reference draws from torch's global CPU generator,
  * flow_lm.py:131-135, which cannot be reproduced on device; parity runs pass d_noise or temp 0). */
 int ptts_lm_set_noise(ptts_lm_state *s, float temp, uint64_t seed);
+/* Per-row seeds (a request's own random stream, wherever the request runs).  The generator above keys the draw of row m,
+ * column k by (the state's seed, the state's step counter, m * ldim + k): what a sequence draws depends on the row it sits
+ * in and on how many steps the state has run.  After ptts_lm_state_set_row_seed(s, row, seed) the draws of `row` are
+ * keyed by (seed, j, k) instead, j = the number of steps the row has taken, while active, since the call (the call zeroes
+ * it; it advances once per step whatever the row's number of LSD steps).  The same hash, Box-Muller / inverse-CDF
+ * truncated normal and std / clamp selection (the row's sampling override, else the state's temperature) apply, so a
+ * seeded row at its j-th step draws what row 0 of a one-row state seeded `seed` draws at its step counter j.  The draws do
+ * not depend on the row index, the batch size, the other rows or the state's own seed and counter.  Rows without a seed
+ * draw exactly as before; d_noise != NULL is still used as given, for every row.  The kernels read seed and counter from
+ * device memory at run time: graphs captured before the call pick them up.  set / clear are stream-ordered on `stream`
+ * and reject a row out of range (-1).  ptts_lm_state_reset clears every seed; the copy calls leave the destination's seeds
+ * as they are (set the seed after ptts_lm_state_copy_row_from, before the row's first step).  Seeds that differ by a
+ * multiple of 0x9E3779B97F4A7C15 (mod 2^64) give shifted copies of one stream: derive related seeds by hashing. */
+int ptts_lm_state_set_row_seed(ptts_lm_state *s, int32_t row, uint64_t seed, void *stream);
+/* row `row` returns to the state's seed and step counter; stream-ordered */
+int ptts_lm_state_clear_row_seed(ptts_lm_state *s, int32_t row, void *stream);
 /* Per-row sampling override (a server's per-request settings in one continuous batch; the reference takes them per model,
  * flow_lm.py:131-137, tts_model.py:756-760).  Row `row` of later steps then uses, instead of the state's ptts_lm_set_noise
  * temperature and the step's eos_threshold argument:

@@ -96,6 +96,8 @@ PROTOTYPES = {
     "ptts_lm_set_noise": (C.c_int, [_P, C.c_float, C.c_uint64]),
     "ptts_lm_state_set_row_sampling": (C.c_int, [_P, C.c_int32, C.c_float, C.c_float, C.c_float, _P]),
     "ptts_lm_state_clear_row_sampling": (C.c_int, [_P, C.c_int32, _P]),
+    "ptts_lm_state_set_row_seed": (C.c_int, [_P, C.c_int32, C.c_uint64, _P]),
+    "ptts_lm_state_clear_row_seed": (C.c_int, [_P, C.c_int32, _P]),
     "ptts_lm_state_reserve_row_lsd": (C.c_int, [_P, C.c_int32, _P]),
     "ptts_lm_state_set_row_lsd": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ptts_lm_state_clear_row_lsd": (C.c_int, [_P, C.c_int32, _P]),

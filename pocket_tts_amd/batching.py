@@ -16,6 +16,10 @@ count, waveform equal up to fp32 summation order: batch tiles differ from batch-
 A request may bring its own temperature, noise clamp and EOS threshold (a server's per-request settings): they are
 written to its slot's row of the batch state (`LMState.set_row_sampling`) before the row's first step, and the step's
 kernels read them per row.  A request without any of them runs exactly as the model's settings would.
+
+A request may also bring a `seed`: its slot's row then draws from the request's own stream (`LMState.set_row_seed`, one
+row seed per text chunk from `engine.chunk_seed`), so the noise of the request does not depend on the slot it was dealt,
+on the step at which it joined or on the other requests, and equals what `TTSModel.generate_audio(..., seed=)` draws.
 """
 
 from __future__ import annotations
@@ -116,10 +120,11 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
+        self.seed = seed       # the chunk's row seed (engine.chunk_seed of the request's seed), or None: the state's stream
         self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
         self.lsd = lsd         # the request's lsd_decode_steps, or None: the model's
         self.start = None      # global step of its first FlowLM step
@@ -172,6 +177,7 @@ class ContinuousBatcher:
         self.a_emit = np.full(slots, 0, np.int64)         # >= 0: no running job in the slot
         self.row_samp = [False] * slots                   # the slot's row carries a sampling override
         self.row_lsd = [False] * slots                    # ... an lsd_decode_steps override
+        self.row_seed = [False] * slots                   # ... a seed
         # held by the background scheduler around each iteration: other users of the engine (e.g. a voice-prompt encode
         # on a request thread) take it to run between the scheduler's steps (`exclusive`)
         self.engine_lock = threading.RLock()
@@ -191,14 +197,18 @@ class ContinuousBatcher:
     # ---- submission (any thread) ---------------------------------------------------------------
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
-               eos_threshold: float | None = None, lsd_decode_steps: int | None = None) -> Request:
+               eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
+               seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
         `temperature`, `noise_clamp` (<= 0: none) and `eos_threshold` apply to this request only; None means the model's
         value.  A request that gives none of them runs with the model's settings exactly.  `lsd_decode_steps` (an int in
         [1, max_lsd_decode_steps]) is the number of Euler steps of this request's flow head; a batcher built without
-        `max_lsd_decode_steps` accepts only the model's value."""
+        `max_lsd_decode_steps` accepts only the model's value.  `seed` (an int in [0, 2**63)) makes the request's noise
+        reproducible: the same seed, text and settings draw the same noise in any slot, under any traffic, and in
+        `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream."""
+        from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
         m = self.model
@@ -219,6 +229,11 @@ class ContinuousBatcher:
             if not math.isfinite(e):
                 raise ValueError(f"eos_threshold must be a finite number, got {eos_threshold}")
             samp = (t, c, e)
+        if seed is not None:
+            seed = check_seed(seed)
+            if samp is None and m.noise_clamp is not None:
+                # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
+                samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -250,7 +265,7 @@ class ContinuousBatcher:
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp, lsd))
+                             samp, lsd, None if seed is None else chunk_seed(seed, i)))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -332,6 +347,11 @@ class ContinuousBatcher:
                 elif self.row_lsd[b]:
                     self.st.clear_row_lsd(b)
                 self.row_lsd[b] = job.lsd is not None
+                if job.seed is not None:
+                    self.st.set_row_seed(b, job.seed)
+                elif self.row_seed[b]:
+                    self.st.clear_row_seed(b)
+                self.row_seed[b] = job.seed is not None
             eng.sync()  # the group state is freed below; its clone kernels must have run
         finally:
             if grp is not None:

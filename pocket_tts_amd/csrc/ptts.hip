@@ -221,8 +221,12 @@ struct ptts_lm_state {
   int *samp_on = nullptr;
   f32x4 *samp_noise = nullptr;
   float *samp_eos = nullptr;
+  // per-row seeds (ptts_lm_state_set_row_seed): marker, seed, steps the row has taken since the seed was set
+  int *seed_on = nullptr;
+  unsigned long long *seed_val = nullptr;
+  int *seed_ctr = nullptr;
   bool latfm_noise = false;  // the last enqueued step left its LSD start point in latfm (debug_read "noise")
-  RowSampling rsamp() const { return RowSampling{samp_on, samp_noise, samp_eos}; }
+  RowSampling rsamp() const { return RowSampling{samp_on, samp_noise, samp_eos, seed_on, seed_val, seed_ctr}; }
   // continuous batching: parked rows (active[b] == 0) keep computing but do not advance their position
   int *active = nullptr;
   std::vector<int> h_active;
@@ -1678,6 +1682,9 @@ static int build_lm_state(ptts_engine *e, ptts_lm_state *s) {
   CHK(dallocT(nullptr, &s->samp_on, B));
   CHK(dallocT(nullptr, &s->samp_noise, B));
   CHK(dallocT(nullptr, &s->samp_eos, B));
+  CHK(dallocT(nullptr, &s->seed_on, B));
+  CHK(dallocT(nullptr, &s->seed_val, B));
+  CHK(dallocT(nullptr, &s->seed_ctr, B));
   CHK(dallocT(nullptr, &s->lsd_n, B));
   s->h_active.assign(B, 1);
   set_int_kernel<<<cdiv(B, 256), 256, 0, e->stream>>>(s->active, B, 1);
@@ -1696,6 +1703,7 @@ static void lm_state_free(ptts_lm_state *s) {
   hipFree(s->xlat); hipFree(s->latfm); hipFree(s->c); hipFree(s->ce); hipFree(s->mod); hipFree(s->fx);
   hipFree(s->fh); hipFree(s->f1); hipFree(s->lat); hipFree(s->lat_prev); hipFree(s->eos_logit); hipFree(s->is_eos); hipFree(s->rng_ctr); hipFree(s->active); hipFree(s->fstat);
   hipFree(s->samp_on); hipFree(s->samp_noise); hipFree(s->samp_eos); hipFree(s->lsd_n);
+  hipFree(s->seed_on); hipFree(s->seed_val); hipFree(s->seed_ctr);
   hipFree(s->fexch); hipFree(s->fflags); hipFree(s->ferr); hipFree(s->lexch); hipFree(s->lflags);
   delete s;
 }
@@ -1752,6 +1760,7 @@ extern "C" int ptts_lm_state_reset(ptts_lm_state *s, void *stream) {
   set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->active, s->B, 1);
   set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->samp_on, s->B, 0);
   set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->lsd_n, s->B, 0);
+  set_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->seed_on, s->B, 0);
   LAUNCHCHK();
   return 0;
 }
@@ -1991,6 +2000,32 @@ extern "C" int ptts_lm_state_clear_row_sampling(ptts_lm_state *s, int32_t row, v
   hipStream_t st = S(s->e, stream);
   ENGINE_LOCK(s->e);
   set_int_kernel<<<1, 64, 0, st>>>(s->samp_on + row, 1, 0);
+  LAUNCHCHK();
+  return 0;
+}
+
+static __global__ void set_row_seed_kernel(int *on, unsigned long long *seed, int *ctr, int v_on, unsigned long long v_seed) {
+  if (threadIdx.x == 0) {
+    *on = v_on;
+    *seed = v_seed;
+    *ctr = 0;
+  }
+}
+
+extern "C" int ptts_lm_state_set_row_seed(ptts_lm_state *s, int32_t row, uint64_t seed, void *stream) {
+  if (!s || row < 0 || row >= s->B) return fail(-1, "set_row_seed: row out of range");
+  hipStream_t st = S(s->e, stream);
+  ENGINE_LOCK(s->e);
+  set_row_seed_kernel<<<1, 64, 0, st>>>(s->seed_on + row, s->seed_val + row, s->seed_ctr + row, 1, (unsigned long long)seed);
+  LAUNCHCHK();
+  return 0;
+}
+
+extern "C" int ptts_lm_state_clear_row_seed(ptts_lm_state *s, int32_t row, void *stream) {
+  if (!s || row < 0 || row >= s->B) return fail(-1, "clear_row_seed: row out of range");
+  hipStream_t st = S(s->e, stream);
+  ENGINE_LOCK(s->e);
+  set_int_kernel<<<1, 64, 0, st>>>(s->seed_on + row, 1, 0);
   LAUNCHCHK();
   return 0;
 }
@@ -2368,7 +2403,7 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
   a.eos_on = s->samp_on; a.eos_row = s->samp_eos;
   a.eos_logit = s->eos_logit; a.is_eos = s->is_eos;
   a.eos_logit2 = d_eos_logit; a.is_eos2 = d_is_eos;  // caller's buffers are written by the epilogue itself
-  a.tail_offset = s->offset; a.tail_ctr = s->rng_ctr; a.tail_active = s->active;  // the step's bookkeeping rides along (was a launch)
+  a.tail_offset = s->offset; a.tail_ctr = s->rng_ctr; a.tail_rctr = s->seed_ctr; a.tail_active = s->active;  // the step's bookkeeping rides along (was a launch)
   // s->ce then holds silu(t_emb + cond) and the modulation GEMM loads it as is (not with per-row schedules: rows differ)
   const bool silu_in_head = lsd_steps == 1 && s->lsd_cap == 0;
   if (silu_in_head) { a.act = ACT_SILU; a.prevec = tcomb; }

@@ -165,8 +165,10 @@ struct GemmArgs {
   int head_nt;  // n-tile holding the EOS row
   // end-of-step bookkeeping done by the EOS row's threads (one per sequence, so exactly once): offset[m] += 1 for active rows
   // (increment_steps, stateful_module.py:19-26) and, by row 0, the step counter.  Nothing after the head GEMM reads a position,
-  // and the flow cluster / the next step's prologue only need the counter to have moved once per step.
-  int *tail_offset, *tail_ctr;
+  // and the flow cluster / the next step's prologue only need the counter to have moved once per step.  tail_rctr[m] += 1
+  // for active rows: the row-local draw counter of a seeded row (RowSampling::seed_ctr), once per step whatever the row's
+  // number of LSD steps.
+  int *tail_offset, *tail_ctr, *tail_rctr;
   const int *tail_active;
   // EPI_LATENT
   float *lat;  // plain [M][ldim], updated in place
@@ -332,7 +334,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int 
         if (a.eos_logit2) a.eos_logit2[m] = acc.x;
         if (a.is_eos) a.is_eos[m] = fl;
         if (a.is_eos2) a.is_eos2[m] = fl;
-        if (a.tail_offset && (!a.tail_active || a.tail_active[m])) a.tail_offset[m] += 1;
+        const bool running = !a.tail_active || a.tail_active[m];
+        if (a.tail_offset && running) a.tail_offset[m] += 1;
+        if (a.tail_rctr && running) a.tail_rctr[m] += 1;
         if (a.tail_ctr && m == 0) *a.tail_ctr += 1;
       }
     } break;
@@ -1414,17 +1418,24 @@ __device__ __forceinline__ float counter_trunc_normal(unsigned long long seed, u
 // Per-row sampling overrides of a FlowLM state (ptts_lm_state_set_row_sampling), read at run time by the step prologue
 // (noise) and the head GEMM's EOS epilogue, so a captured graph sees values written after its capture.  on[m] != 0:
 // row m draws with noise[m] = {std, clamp (0: none), lo, width} and compares its EOS logit with eos[m].
+// Per-row seeds (ptts_lm_state_set_row_seed): seed_on[m] != 0: row m's draws are keyed by (seed[m], seed_ctr[m], column),
+// seed_ctr[m] being the number of steps the row has taken since the seed was set (the head epilogue advances it), so what
+// the row draws depends neither on its row index nor on the state's seed and step counter.
 struct RowSampling {
   const int *on;
   const f32x4 *noise;
   const float *eos;
+  const int *seed_on;
+  const unsigned long long *seed;
+  const int *seed_ctr;
 };
 
-// LSD start point of row m, columns base..base+3, on the device-generator path (no external noise): rows without an
+// LSD start point of row m, columns k..k+3, on the device-generator path (no external noise): rows without an
 // override draw rng_std * N(0, 1) as they always did; an overridden row draws with its own std, truncated when it has a
-// clamp; std 0 gives exact zeros.
-__device__ __forceinline__ f32x4 device_noise(const RowSampling &rs, int m, float rng_std, unsigned long long rng_seed,
-                                              const int *rng_ctr, unsigned base) {
+// clamp; std 0 gives exact zeros.  The hash key is (state seed, state step counter, m * ldim + column), or for a seeded
+// row (row seed, row-local counter, column).
+__device__ __forceinline__ f32x4 device_noise(const RowSampling &rs, int m, int k, int ldim, float rng_std,
+                                              unsigned long long rng_seed, const int *rng_ctr) {
   f32x4 z = {0.f, 0.f, 0.f, 0.f}, p = z;
   float sd = rng_std;
   if (rs.on && rs.on[m]) {
@@ -1432,7 +1443,15 @@ __device__ __forceinline__ f32x4 device_noise(const RowSampling &rs, int m, floa
     sd = p.x;
   }
   if (sd > 0.f) {
-    const unsigned ctr = (unsigned)*rng_ctr;
+    unsigned ctr, base;
+    if (rs.seed_on && rs.seed_on[m]) {
+      rng_seed = rs.seed[m];
+      ctr = (unsigned)rs.seed_ctr[m];
+      base = (unsigned)k;
+    } else {
+      ctr = (unsigned)*rng_ctr;
+      base = (unsigned)(m * ldim + k);
+    }
     if (p.y > 0.f) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) z[j] = counter_trunc_normal(rng_seed, ctr, base + j, sd, p.y, p.z, p.w);
@@ -1492,7 +1511,7 @@ static __global__ void prep_lm_kernel(const float *lat_in, const float *bos, con
     if (noise) {
       z = *(const f32x4 *)(noise + (size_t)m * ldim + k);
     } else {
-      z = device_noise(rsamp, m, rng_std, rng_seed, rng_ctr, (unsigned)(m * ldim + k));
+      z = device_noise(rsamp, m, k, ldim, rng_std, rng_seed, rng_ctr);
     }
   }
   *(f32x4 *)(x_fm + (size_t)i * 4) = v;
@@ -1544,7 +1563,7 @@ static __global__ __launch_bounds__(256) void prep_in_kernel(const float *lat_in
     if (noise) {
       z = *(const f32x4 *)(noise + (size_t)m * ldim + k);
     } else {
-      z = device_noise(rsamp, m, rng_std, rng_seed, rng_ctr, (unsigned)(m * ldim + k));
+      z = device_noise(rsamp, m, k, ldim, rng_std, rng_seed, rng_ctr);
     }
   }
   *(f32x4 *)(lat_fm + (size_t)i * 4) = z;

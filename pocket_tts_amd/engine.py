@@ -12,6 +12,7 @@ Mirrors the reference's internal seam:
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 import weakref
 
@@ -48,6 +49,36 @@ def make_ptts_config(cfg: Config) -> _lib.PttsConfig:
     return pc
 
 
+_MASK64 = (1 << 64) - 1
+
+
+def _mix64(z: int) -> int:
+    """the splitmix64 finaliser the device generator hashes with (mix64 in csrc/ptts_kernels.h)"""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+def check_seed(seed, bits: int = 63) -> int:
+    """`seed` as an int in [0, 2**bits), else ValueError (bool, float, negative and too large values are refused)"""
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < (1 << bits):
+        raise ValueError(f"seed must be an integer in [0, 2**{bits}), got {seed!r}")
+    return int(seed)
+
+
+def chunk_seed(seed: int, chunk: int) -> int:
+    """The 64-bit row seed (`LMState.set_row_seed`) of text chunk `chunk` of a request seeded `seed` (an int in
+    [0, 2**63)); every entry point derives its row seeds here.  Chunk 0 uses the request's seed itself.  Later chunks hash
+    seed and index: the generator hashes `seed + C * key` with C = 0x9E3779B97F4A7C15, so seeds an additive step apart
+    could yield shifted copies of one stream."""
+    seed = check_seed(seed)
+    if isinstance(chunk, bool) or not isinstance(chunk, numbers.Integral) or not 0 <= int(chunk) < (1 << 32):
+        raise ValueError(f"chunk index must be an integer in [0, 2**32), got {chunk!r}")
+    if chunk == 0:
+        return seed
+    return _mix64(_mix64(seed) ^ int(chunk))
+
+
 class LMState:
     """FlowLM KV caches of `batch` sequences with capacity `t_cap` positions."""
 
@@ -80,6 +111,17 @@ class LMState:
     def clear_row_sampling(self, row: int):
         """row `row` returns to the state's temperature (`set_noise`) and the step's EOS threshold"""
         _lib.check(self.engine.lib.ptts_lm_state_clear_row_sampling(self.handle, row, self.engine._sp))
+
+    def set_row_seed(self, row: int, seed: int):
+        """Row `row` draws from its own stream: its j-th step from now on is keyed by (seed, j, column), whatever the row
+        index, the batch and the state's own seed and step counter (include/ptts.h).  Restarts the row's stream; read by
+        the kernels at run time, so captured steps pick it up."""
+        _lib.check(self.engine.lib.ptts_lm_state_set_row_seed(self.handle, row, check_seed(seed, bits=64),
+                                                              self.engine._sp))
+
+    def clear_row_seed(self, row: int):
+        """row `row` returns to the state's seed and step counter (`set_noise`)"""
+        _lib.check(self.engine.lib.ptts_lm_state_clear_row_seed(self.handle, row, self.engine._sp))
 
     def reserve_row_lsd(self, K: int):
         """Per-row LSD schedules of up to `K` Euler steps (include/ptts.h); before any graph of this state is captured"""

@@ -7,7 +7,7 @@
 
 `generate` writes 24 kHz mono 16-bit WAV followed by 200 ms of silence (reference data/audio.py:69-72,99-107).
 `serve` runs the HTTP server of `server.py` (`GET /health`, `POST /tts` streaming the same WAV bytes) on a continuous
-batcher, with per-request temperature, noise clamp and EOS threshold.  `export-voice` encodes an audio prompt (first 30 s)
+batcher, with per-request temperature, noise clamp, EOS threshold and seed.  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -80,6 +80,8 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--noise-clamp", type=float, default=None)
     g.add_argument("--eos-threshold", type=float, default=-4.0)
     g.add_argument("--frames-after-eos", type=int, default=None)
+    g.add_argument("--seed", type=int, default=None,
+                   help="Seed of the noise in [0, 2**63): the same seed, text and settings give the same audio again")
     g.add_argument("--output-path", default="./tts_output.wav")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
@@ -167,7 +169,8 @@ def cli_app(argv=None) -> int:
                                 device=args.device)
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
-    chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens)
+    chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
+                                         seed=args.seed)
     write_wav_stream(args.output_path, chunks, model.sample_rate)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)

@@ -3,7 +3,8 @@ pocket_tts/main.py:121-214) with every request decoded in one shared batch.
 
 `POST /tts` takes the reference's form fields - `text`, `voice_url` (here: the name of a voice state in the voices
 directory) or the file `voice_wav` - plus this server's optional per-request settings `temperature`, `noise_clamp`,
-`eos_threshold` and `frames_after_eos`.  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+`eos_threshold`, `frames_after_eos`, `lsd_decode_steps` and `seed` (the same seed, text and settings give the same noise
+again).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
@@ -37,6 +38,7 @@ INDEX_HTML = """<!doctype html>
 <p><textarea name="text" rows="4" cols="60">Hello world.</textarea></p>
 <p>Voice name <input name="voice_url"> or WAV prompt <input type="file" name="voice_wav" accept=".wav"></p>
 <p>LSD decode steps <input name="lsd_decode_steps" size="3"> (empty: the server's default)</p>
+<p>Seed <input name="seed" size="20"> (empty: a take that cannot be repeated)</p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -133,6 +135,20 @@ def parse_lsd_steps(fields: dict, max_lsd_decode_steps: int) -> int | None:
         raise FormError(f"lsd_decode_steps must be an integer, got {raw!r}") from None
     if not 1 <= v <= max_lsd_decode_steps:
         raise FormError(f"lsd_decode_steps must be in [1, {max_lsd_decode_steps}], got {raw!r}")
+    return v
+
+
+def parse_seed(fields: dict) -> int | None:
+    """the optional `seed` field: an integer in [0, 2**63) (absent or empty: None)"""
+    raw = fields.get("seed")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        v = int(raw.strip(), 10)
+    except ValueError:
+        raise FormError(f"seed must be an integer, got {raw!r}") from None
+    if not 0 <= v < 2 ** 63:
+        raise FormError(f"seed must be in [0, 2**63), got {raw!r}")
     return v
 
 
@@ -241,6 +257,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             lsd = parse_lsd_steps(fields, max_lsd)
             if lsd is not None:
                 settings["lsd_decode_steps"] = lsd
+            seed = parse_seed(fields)
+            if seed is not None:
+                settings["seed"] = seed
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:

@@ -23,7 +23,7 @@ import safetensors.torch
 import torch
 
 from .config import CONFIGS_DIR, Config, load_config
-from .engine import Engine
+from .engine import Engine, check_seed, chunk_seed
 from .text import estimate_max_gen_len, prepare_text_prompt, split_into_best_sentences
 from .weights import generate_state_dict
 
@@ -191,26 +191,37 @@ class TTSModel:
     # ---- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                       frames_after_eos: int | None = None, copy_state: bool = True) -> torch.Tensor:
-        chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state))
+                       frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63), not in the reference): see `generate_audio_stream`."""
+        chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
+                                                 seed=seed))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                              frames_after_eos: int | None = None, copy_state: bool = True):
-        """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631)."""
+                              frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None):
+        """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
+
+        `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
+        of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
+        per-step copy, nothing read from torch's global generator - and `generate_audio_batch(seeds=...)` and
+        `ContinuousBatcher.submit(seed=...)` draw the same values for the same request.  Without a seed the noise comes
+        from torch's global CPU generator, as in the reference."""
+        if seed is not None:
+            seed = check_seed(seed)
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
                                            self.pad_with_spaces_for_short_inputs, self.remove_semicolons)
-        for chunk in chunks:
+        for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, self.pad_with_spaces_for_short_inputs, self.remove_semicolons)
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
-            yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state)
+            yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
+                                                              None if seed is None else chunk_seed(seed, i))
 
     @torch.no_grad()
-    def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None) -> list:
+    def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
         """Generate several utterances concurrently on one GPU (not in the reference, which is batch 1 and
         requires equal cache offsets across a batch: tts_model.py:491-492, transformer.py:12-13).
 
@@ -223,7 +234,9 @@ class TTSModel:
         and are read a few steps later, so a row runs at most `StepPipeline.nb` steps past its end (those frames are
         dropped); per-row EOS bookkeeping follows tts_model.py:756-768.  With temp == 0 each waveform equals the
         single-utterance result; with temp > 0 rows draw independent noise (the reference's sequential use of the
-        global generator cannot be reproduced across a batch).  Returns a list of fp32 CPU tensors."""
+        global generator cannot be reproduced across a batch).  `seeds`: one int in [0, 2**63) or None per text; a seeded
+        text draws the noise `generate_audio(..., seed=)` draws for it, whatever its row and its neighbours, and a text
+        without a seed draws as without the argument.  Returns a list of fp32 CPU tensors."""
         from .batching import eos_bookkeeping_rows
         from .engine import StepPipeline
 
@@ -233,6 +246,11 @@ class TTSModel:
             model_states = [model_states] * B
         if len(model_states) != B or B == 0:
             raise ValueError("need one voice state per text")
+        if seeds is None:
+            seeds = [None] * B
+        if len(seeds) != B:
+            raise ValueError("need one seed (or None) per text")
+        seeds = [None if s is None else check_seed(s) for s in seeds]
         # rows of one voice next to each other: they share the voice's keys (KvPrefix), and the decode attention scores a
         # shared prefix once per 4 neighbouring rows (attn_cascade_kernel)
         first: dict = {}
@@ -240,7 +258,8 @@ class TTSModel:
             first.setdefault(id(m), i)
         order = sorted(range(B), key=lambda i: first[id(model_states[i])])
         if order != list(range(B)):
-            got = self.generate_audio_batch([model_states[i] for i in order], [texts[i] for i in order], frames_after_eos)
+            got = self.generate_audio_batch([model_states[i] for i in order], [texts[i] for i in order], frames_after_eos,
+                                            [seeds[i] for i in order])
             res = [None] * B
             for pos, i in enumerate(order):
                 res[i] = got[pos]
@@ -280,7 +299,7 @@ class TTSModel:
                 if use_noise:
                     batch.set_noise(self.temp, int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
                 pipe = StepPipeline(eng, batch, ms, None, self.lsd_decode_steps, float(self.eos_threshold), mode="events")
-                ctx = dict(st=batch, ms=ms, pipe=pipe)
+                ctx = dict(st=batch, ms=ms, pipe=pipe, seeded=[False] * B, clamped=[False] * B)
             batch, ms, pipe = ctx["st"], ctx["ms"], ctx["pipe"]
             nb = pipe.nb
             # group prefill: rows with the same voice and token count share one batched pass (lengths differ across groups)
@@ -296,6 +315,20 @@ class TTSModel:
                 eng.lm_prefill(grp, eng.embed_text(torch.cat([toks[b] for b in rows], dim=0)))
                 for i, b in enumerate(rows):
                     batch.copy_row_from(b, grp, i)
+            for b in range(B):  # the rows' seeds, before their first step (single-chunk texts: chunk 0)
+                on = use_noise and seeds[b] is not None
+                if on:
+                    batch.set_row_seed(b, chunk_seed(seeds[b], 0))
+                elif ctx["seeded"][b]:
+                    batch.clear_row_seed(b)
+                ctx["seeded"][b] = on
+                # a seeded row draws as `generate_audio(seed=)` does: with the model's noise clamp
+                clamp = on and self.noise_clamp is not None
+                if clamp:
+                    batch.set_row_sampling(b, self.temp, self.noise_clamp, float(self.eos_threshold))
+                elif ctx["clamped"][b]:
+                    batch.clear_row_sampling(b)
+                ctx["clamped"][b] = clamp
             pipe.restart()  # zero codec carries, on the codec stream
             gens_a, faes_a = np.asarray(gens), np.asarray(faes)
             eos_step = np.full(B, -1, np.int64)
@@ -419,7 +452,8 @@ class TTSModel:
         else:
             torch.nn.init.trunc_normal_(out, mean=0.0, std=std, a=-self.noise_clamp, b=self.noise_clamp)
 
-    def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool):
+    def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
+                                          row_seed: int | None = None):
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -427,17 +461,19 @@ class TTSModel:
         voice = self._voice_acquire(model_state)  # no device sync when the voice is already resident
         voice_st, t_voice = voice
         use_noise = self.temp > 0
+        # a seeded chunk draws on the device (`LMState.set_row_seed`): its step graphs are captured without a noise buffer
+        seeded = use_noise and row_seed is not None
         t_start = time.monotonic()
         # states, scratch and captured graphs are reused across chunks and calls (capacity rounded up)
         cap = -(-(t_voice + Tt + max_gen_len) // 256) * 256
-        key = (cap, self.lsd_decode_steps, float(self.eos_threshold), use_noise)
+        key = (cap, self.lsd_decode_steps, float(self.eos_threshold), "seeded" if seeded else use_noise)
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
 
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
-            noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise else None
+            noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
             pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync")
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
@@ -449,7 +485,12 @@ class TTSModel:
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         pipe.restart()
-        if use_noise:
+        if seeded:
+            # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
+            # state's own temperature is frozen into the captured step
+            st.set_row_sampling(0, self.temp, self.noise_clamp, float(self.eos_threshold))
+            st.set_row_seed(0, row_seed)  # after the clone; the row's step counter restarts with the chunk
+        elif use_noise:
             # the reference's text prefill runs the whole forward, including one (discarded) noise draw
             # (tts_model.py:722-725 -> flow_lm.py:131-137): consume it to stay on the same generator stream
             self._draw_noise(torch.empty(1, eng.ldim))
@@ -471,7 +512,7 @@ class TTSModel:
                     yielded = 1
                     total += chunk.shape[0]
                     yield chunk
-                if use_noise:
+                if use_noise and not seeded:
                     self._draw_noise(noise_host)
                     with torch.cuda.stream(eng.stream):
                         noise_dev.copy_(noise_host, non_blocking=True)
