@@ -337,6 +337,8 @@ int ptts_copy_to_host_async(ptts_engine *e, void *h_dst, const void *d_src, int6
 /* HIP-event timing on `stream` (bench.py measures on the stream the kernels run on) */
 int ptts_timer_start(ptts_engine *e, void *stream);
 int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
+/* The test hooks from here on (ptts_debug_read / _gemm / _codec_gemm / _attn) are built from csrc/ptts_debug.hip, a unit of
+ * their own beside the production host side (csrc/ptts.hip). */
 /* Test hook: copies an internal activation buffer, converted to row-major f32[rows, cols], to
  * d_out (capacity in floats).  Names: see DESIGN.md; FlowLM name "noise" = the last step's LSD start point (the noise)
  * f32[B, ldim] (only kept when that step ran the single-launch flow MLP, "flow_cluster"; -1 otherwise).

@@ -1,264 +1,46 @@
 // Host side of libptts: engine construction (weight packing), FlowLM / Mimi step orchestration,
 // hipGraph capture and the C ABI declared in include/ptts.h.
-#include "ptts_kernels.h"
+#include "ptts_host.h"
 #include "ptts_flow.h"
 #include "ptts_bf16.h"
 #include "ptts_lm.h"
-#include "ptts_ext.h"
 
 #include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "../../include/ptts.h"
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) {
+int fail(int code, const std::string &msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(x)                                                                                      \
-  do {                                                                                                 \
-    hipError_t e_ = (x);                                                                               \
-    if (e_ != hipSuccess)                                                                              \
-      return fail(-2, std::string(#x) + ": " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
-  } while (0)
-#define CHK(x)            \
-  do {                    \
-    int r_ = (x);         \
-    if (r_ < 0) return r_; \
-  } while (0)
-// A GEMM for which no kernel exists (launch_gemm returns nothing: it records the message and launches nothing), reported
-// by the entry point's LAUNCHCHK, or by the graph capture that enqueued it
-static thread_local std::string g_launch_err;
-static int take_launch_err() {
+static thread_local std::string g_launch_err;  // see LAUNCHCHK (ptts_host.h)
+bool launch_err_pending() { return !g_launch_err.empty(); }
+int take_launch_err() {
   std::string m;
   m.swap(g_launch_err);
   return fail(-4, m);
 }
-#define LAUNCHCHK()                                   \
-  do {                                                \
-    if (!g_launch_err.empty()) return take_launch_err(); \
-    HIPCHK(hipGetLastError());                        \
-  } while (0)
 
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
-// ------------------------------------------------------------------------------------------------
-// Optional per-launch profiler: every kernel launch is bracketed by two HIP events on the stream it is
-// launched on and tagged with its call site, its kernel name and its ALGORITHMIC bytes / flops.
-// Off by default (and always off during graph capture); bench.py switches it on for a few eager steps.
-struct ProfRec { std::string site, kernel; double bytes, flops; hipEvent_t a, b; };
-struct Profiler { bool on = false; std::vector<ProfRec> recs; };
 // Per-call context: every entry point binds its engine's profiler / tuner / zero line in the CALLING thread
 // (bind_engine), so two engines driven from two threads never see each other's state.  One engine is driven by one
 // thread at a time (entry points take the engine mutex; see the threading contract in include/ptts.h).
 static thread_local Profiler *g_prof = nullptr;
 static thread_local const char *g_site = "";
-struct ProfScope {
-  hipStream_t st; Profiler *pr; size_t idx;
-  ProfScope(hipStream_t st_, const std::string &kernel, double bytes, double flops) : st(st_), pr(g_prof && g_prof->on ? g_prof : nullptr), idx(0) {
-    if (!pr) return;
-    ProfRec r{g_site, kernel, bytes, flops, nullptr, nullptr};
-    if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) { pr = nullptr; return; }
-    (void)hipEventRecord(r.a, st);
-    idx = pr->recs.size();
-    pr->recs.push_back(r);
-  }
-  ~ProfScope() { if (pr) (void)hipEventRecord(pr->recs[idx].b, st); }
-};
+ProfScope::ProfScope(hipStream_t st_, const std::string &kernel, double bytes, double flops) : st(st_), pr(g_prof && g_prof->on ? g_prof : nullptr), idx(0) {
+  if (!pr) return;
+  ProfRec r{g_site, kernel, bytes, flops, nullptr, nullptr};
+  if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) { pr = nullptr; return; }
+  (void)hipEventRecord(r.a, st);
+  idx = pr->recs.size();
+  pr->recs.push_back(r);
+}
+ProfScope::~ProfScope() { if (pr) (void)hipEventRecord(pr->recs[idx].b, st); }
 #define SITE(x) g_site = (x)
 
 // ------------------------------------------------------------------------------------------------
-struct Lin {  // one packed weight matrix
-  float *w = nullptr, *bias = nullptr;
-  int N = 0, NT = 0, C = 0, CF = 0, ntaps = 1, KF = 0;
-  int cout = 0, stride = 0;  // transposed-conv view
-  float *ln_s = nullptr, *ln_c = nullptr;  // LayerNorm folded into this matrix (PRE_LNFOLD)
-  // int8 weight-only variant (PTTS_QUANT_*): wq replaces w; ln_g = the LayerNorm gain applied to x on load
-  uint8_t *wq = nullptr;
-  float *wscale = nullptr, *ln_g = nullptr;
-  // bf16 weight variant of a FlowLM Linear (PTTS_LM_BF16): replaces w; packed [NT][KF/2][64][8] (GemmArgs::wfmt == 2)
-  void *wb16 = nullptr;
-  // split-bf16 twin of a codec matrix (PTTS_CODEC_SPLIT): hi = bf16(w), lo = bf16(w - hi) images beside the fp32 one
-  void *wsh = nullptr, *wsl = nullptr;
-  // bf16 twin for the reduced-precision codec path (PTTS_CODEC_BF16): packed [NT][ntaps * C/32][64][8], ln_s from the rounded image
-  __bf16 *wh = nullptr;
-  float *ln_s_h = nullptr;
-  // e4m3 twin of a SEANet conv for the fp8 path (PTTS_CODEC_FP8): packed [NT][ntaps * C/32][64][8 bytes] + per-channel scale
-  void *wf8 = nullptr;
-  float *wscale8 = nullptr;
-  size_t bytes() const { return wq ? (size_t)NT * KF * 256 + (size_t)NT * 64 : wb16 ? (size_t)NT * KF * 512 : (size_t)NT * KF * 1024; }
-};
-
-struct TrLayer {
-  float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ls1 = nullptr, *ls2 = nullptr;
-  Lin qkv, out, ff1, ff2;
-};
-
-struct ptts_engine {
-  ptts_config cfg;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<void *> allocs;
-  std::map<void *, size_t> alloc_bytes;  // engine-owned allocations and their sizes (packed-engine files)
-  size_t n_build_allocs = 0;             // allocs[0 .. n) were made by build_engine, in a deterministic order
-  const ptts_tensor *blob_dummy = nullptr;  // ptts_create_from_file: every checkpoint lookup resolves to this zero tensor
-  int blob_has_encoder = 0;
-  std::map<std::string, const ptts_tensor *> tmap;
-  // FlowLM
-  float *bos = nullptr, *freq_lm = nullptr;
-  Lin in_linear;
-  std::vector<TrLayer> lm;
-  float *outnorm_w, *outnorm_b;
-  Lin head, adaln, input_proj, fin;
-  struct Res { float *ln_w, *ln_b; Lin l0, l2; };
-  std::vector<Res> res;
-  Lin te_l0[2], te_l2[2];
-  float *te_freqs[2], *te_alpha[2];
-  std::map<int, float *> tcomb;  // lsd_steps -> [S][flow_dim]
-  std::map<int, float *> tpack;  // K -> the tables of schedules 1..K packed: entry (N, i) at N (N - 1) / 2 + i
-  float *te_scratch = nullptr;
-  // Mimi
-  float *emb_std, *emb_mean, *up_w, *freq_mimi;
-  float *quant_w = nullptr;  // quantizer.output_proj weight [C][ldim], plain (mimi_prologue_kernel)
-  std::vector<TrLayer> mm;
-  Lin conv0, convtr[3], res_a[3], res_b[3], conv_last;
-  float *conv_last_w = nullptr, *conv_last_b = nullptr;  // plain checkpoint tensors (bf16 path's last conv)
-  bool codec_bf16 = false;
-  int64_t mimi_bytes_h = 0;
-  // fp8 SEANet convolutions: static activation scales (device copy lives in an engine allocation, so packed-engine files
-  // carry it; f8s is its host mirror).  Index: 0 = conv0 output, 1 + 3 i = convtr_i output (ELU'd), 2 + 3 i = hidden
-  // activation of residual block i, 3 + 3 i = output of block i (i < 2: the next transposed conv's input)
-  bool codec_split = false;  // PTTS_CODEC_SPLIT: the fp32 codec's GEMM launches use the split-bf16 images
-  bool codec_fp8 = false;
-  float *d_f8s = nullptr;
-  float f8s[16] = {};
-  int64_t mimi_bytes_f8 = 0;
-  int ring = 0;
-  // voice-prompt encode path (SEANet encoder, encoder transformer, downsample, speaker projection)
-  bool has_encoder = false;
-  Lin enc_conv0, enc_res_a[3], enc_res_b[3], enc_down[3], enc_final, enc_downsample, speaker_proj;
-  std::vector<TrLayer> enc_tr;
-  float *zeros = nullptr;
-  int64_t lm_bytes = 0, mimi_bytes = 0;
-  struct Tuner *tuner = nullptr;
-  Profiler prof;
-  int opt_flow_cluster = 1;
-  int opt_lm_cluster = 0;  // measured slower than five launches per layer: kept as an experiment
-  LmLayerP *lm_table = nullptr;  // device table of the FlowLM layers for lm_cluster_kernel (null: not eligible)
-  int opt_k_rotate = 0;
-  long fuse_res_min_rows = 0;
-  int opt_codec_lds_target = 56 * 1024;  // see lds_pad()
-  int opt_fuse_pcm = 1;      // SEANet's last conv inside the last stage's fused residual block (its output tile never leaves the CU)
-  int opt_debug_taps = 0;    // materialise buffers that fused kernels keep on chip (ptts_debug_read of every stage)
-  int opt_single_store = 1;  // SEANet transposed convs store their raw output once; the next conv applies ELU on its operand read
-  int opt_fuse_res = 1;  // SEANet residual blocks of stages 2 and 3 as one launch each (gemm_lds_kernel<.., NT2>)
-  int opt_flow_max_cus = 128;  // resident workgroups of the single-launch flow MLP (<= the CUs its stream may use)
-  int opt_share_prefix = 1;    // clones of a batch-1 state share its keys / values (KvPrefix) instead of copying them
-  int opt_cascade = 423;       // decode attention of such clones: 10 R + PW of attn_cascade_kernel (0: every sequence on its own)
-  int n_cus = 256;             // hipDeviceProp_t::multiProcessorCount of `device` (cooperative grids never exceed it)
-  std::recursive_mutex mu;  // entry points that enqueue work or touch tuner / profiler / LSD tables hold it
-  int quant_flags = 0;
-};
-#define ENGINE_LOCK(e) std::lock_guard<std::recursive_mutex> lock_((e)->mu)
-
-struct Scratch {
-  float *x = nullptr, *h = nullptr, *ao = nullptr, *ff = nullptr, *q = nullptr, *part = nullptr, *rope = nullptr;
-  int MT = 0, QB = 0, splits_cap = 0;
-};
-
-struct ptts_lm_state {
-  ptts_engine *e;
-  int B, cap, MT;
-  float *kv = nullptr;  // [L][2][B][H][cap][64]
-  int *offset = nullptr;
-  std::vector<int> h_off;
-  Scratch dec, pre;
-  // flow head scratch (FM) + io
-  float *xlat, *c, *ce, *mod, *latfm, *fx, *fh, *f1;
-  float *fstat = nullptr;  // per-tile row statistics of fx (GemmArgs::stat_out / stat_in)
-  // single-launch flow MLP (flow_cluster_kernel): exchange slots, flags, error word; sized for `flow_steps` LSD steps
-  float *fexch = nullptr;
-  unsigned long long *fflags = nullptr;
-  int *ferr = nullptr;
-  int flow_steps = 0, flow_rt = 1, flow_ng = 1;
-  // per-row LSD schedules (ptts_lm_state_reserve_row_lsd): capacity K (0: none), packed time-embedding table of
-  // schedules 1..K, each row's own step count (0: the step's lsd_steps)
-  int lsd_cap = 0;
-  const float *lsd_tab = nullptr;
-  int *lsd_n = nullptr;
-  // shared prefixes (KvPrefix): device table read by the attention kernels, its host mirror, and who owns each row's prefix.
-  // An owner with borrowers is not freed by ptts_lm_state_destroy until the last borrower lets go (`zombie`).
-  KvPrefix *d_pre = nullptr;
-  std::vector<KvPrefix> h_pre;
-  std::vector<ptts_lm_state *> pre_owner;
-  int casc_mode = -1;   // decode attention: -1 = cascade kernel iff rows borrow prefixes now (eager steps), 0 / 1 forced (captures)
-  int n_pre = 0;        // rows of this state that have a prefix
-  int borrowers = 0;    // rows of OTHER states whose prefix is this state's cache
-  bool zombie = false;
-  int n_graphs = 0;   // captured graphs that hold this state's buffer pointers (ensure_flow must not re-allocate under them)
-  int coop_wgs = 0;   // workgroups of the cooperative launch of the last enqueued step (0: per-layer launches)
-  // single-launch transformer stack (lm_cluster_kernel): exchange slots + flags, allocated on first use
-  float *lexch = nullptr;
-  unsigned long long *lflags = nullptr;
-  float *lat, *lat_prev;  // plain [B][ldim]
-  float *eos_logit;
-  uint8_t *is_eos;
-  // device noise source for perf runs (d_noise == NULL and rng_std > 0): N(0, rng_std^2), counter-based
-  float rng_std = 0.f;
-  unsigned long long rng_seed = 0;
-  int *rng_ctr = nullptr;
-  // per-row sampling overrides (ptts_lm_state_set_row_sampling; RowSampling in ptts_kernels.h): marker, {std, clamp, lo,
-  // width} of the device generator's draw, EOS threshold
-  int *samp_on = nullptr;
-  f32x4 *samp_noise = nullptr;
-  float *samp_eos = nullptr;
-  // per-row seeds (ptts_lm_state_set_row_seed): marker, seed, steps the row has taken since the seed was set
-  int *seed_on = nullptr;
-  unsigned long long *seed_val = nullptr;
-  int *seed_ctr = nullptr;
-  bool latfm_noise = false;  // the last enqueued step left its LSD start point in latfm (debug_read "noise")
-  RowSampling rsamp() const { return RowSampling{samp_on, samp_noise, samp_eos, seed_on, seed_val, seed_ctr}; }
-  // continuous batching: parked rows (active[b] == 0) keep computing but do not advance their position
-  int *active = nullptr;
-  std::vector<int> h_active;
-  size_t kv_plane() const { return (size_t)B * e->cfg.num_heads * cap * 64; }
-  float *K(int l) { return kv + (size_t)(2 * l) * kv_plane(); }
-  float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
-};
-
-struct ptts_mimi_state {
-  ptts_engine *e;
-  int B, MTb, MT16;
-  int *frame = nullptr, *offset = nullptr;
-  int h_frame = 0;
-  float *kv = nullptr;  // [ML][2][B][H][ring][64]
-  float *zl, *zq, *u0, *u, *h, *ao, *ff, *q, *part, *tr_out, *rope;
-  long zq_stride, tr_stride;
-  int splits;
-  float *a0;
-  long a0_stride;
-  float *cbuf[3], *craw[3], *rbuf[3], *sbuf[3];  // cbuf/sbuf/rbuf hold ELU'd values, craw the raw skip input
-  long c_stride[3], s_stride[3];
-  int rows[4];  // rows per sequence at each SEANet stage
-  float *pcm_dbg;
-  int16_t *pcm_i16 = nullptr;
-  // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
-  float *pcm_part = nullptr, *pcm_carry = nullptr;
-  long pcm_cstride = 0;
-  size_t kv_plane() const { return (size_t)B * e->cfg.m_heads * e->ring * 64; }
-  float *K(int l) { return kv + (size_t)(2 * l) * kv_plane(); }
-  float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
-};
-
 struct ptts_graph {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -280,12 +62,9 @@ struct ptts_graph {
 // The zero fill is queued on the stream of the innermost AllocScope of the CALLING thread (thread-local: a
 // concurrent call on another engine / thread can no longer redirect it).
 static thread_local hipStream_t t_alloc_stream = nullptr;
-struct AllocScope {
-  hipStream_t prev;
-  explicit AllocScope(hipStream_t st) : prev(t_alloc_stream) { t_alloc_stream = st; }
-  ~AllocScope() { t_alloc_stream = prev; }
-};
-static int dalloc(ptts_engine *e, void **p, size_t bytes) {
+AllocScope::AllocScope(hipStream_t st) : prev(t_alloc_stream) { t_alloc_stream = st; }
+AllocScope::~AllocScope() { t_alloc_stream = prev; }
+int dalloc(ptts_engine *e, void **p, size_t bytes) {
   hipStream_t st = t_alloc_stream ? t_alloc_stream : (e ? e->stream : nullptr);
   if (!st) return fail(-1, "internal: allocation outside an AllocScope");
   if (bytes == 0) bytes = 256;
@@ -300,11 +79,6 @@ static int dalloc(ptts_engine *e, void **p, size_t bytes) {
   if (e) { e->allocs.push_back(*p); e->alloc_bytes[*p] = bytes; }
   return 0;
 }
-template <typename T>
-static int dallocT(ptts_engine *e, T **p, size_t n) {
-  return dalloc(e, (void **)p, n * sizeof(T));
-}
-
 
 static const ptts_tensor *find_tensor(ptts_engine *e, const std::string &name, int64_t numel, int *err) {
   if (e->blob_dummy) return e->blob_dummy;  // loading a packed engine: the packing kernels run on zeros, the real images follow
@@ -331,12 +105,9 @@ static int copy_vec(ptts_engine *e, const std::string &name, int64_t n, float **
   return 0;
 }
 
-struct PackPart { std::string w, b; int N; };
-
 // packs one or several [N_i][C][ntaps] matrices (stacked along N) into one Lin
-static int pack_lin(ptts_engine *e, Lin *L, const std::vector<PackPart> &parts, int C, int ntaps, int mode = 0,
-                    int cout = 0, int stride = 0, const std::string &ln_w = "", const std::string &ln_b = "",
-                    int creal = 0, int wfmt = 0) {
+int pack_lin(ptts_engine *e, Lin *L, const std::vector<PackPart> &parts, int C, int ntaps, int mode, int cout, int stride,
+             const std::string &ln_w, const std::string &ln_b, int creal, int wfmt) {
   const bool q8 = wfmt == 1, b16 = wfmt == 2;
   if (C % 16) return fail(-4, "channel count must be a multiple of 16: " + parts[0].w);
   if (b16 && (parts.size() != 1 || mode != 0 || ntaps != 1 || (C / 16) % 2))
@@ -434,10 +205,9 @@ static int pack_lin(ptts_engine *e, Lin *L, const std::vector<PackPart> &parts, 
   return 0;
 }
 
-
 // bf16 twin of a packed matrix for the reduced-precision codec path (single-part matrices only)
-static int pack_lin_h(ptts_engine *e, Lin *L, const std::string &wname, int N, int C, int ntaps, int mode = 0, int cout = 0,
-                      int stride = 0, const std::string &ln_w = "") {
+int pack_lin_h(ptts_engine *e, Lin *L, const std::string &wname, int N, int C, int ntaps, int mode, int cout, int stride,
+               const std::string &ln_w) {
   if (C % 32) return fail(-4, "bf16 codec path: channel count must be a multiple of 32: " + wname);
   int err = 0;
   const ptts_tensor *t = find_tensor(e, wname, -1, &err);
@@ -576,7 +346,6 @@ static int pick_cfg(const GemmArgs &a) {
   while (tm > 1 && (long)a.NT * cdiv(a.MT, tm) < 256) tm >>= 1;
   return tm == 4 ? 2 : tm == 2 ? 1 : 0;
 }
-static constexpr int kNumCfg = 18;  // 16, 17 appended in round 2 (older cache files stay valid)
 static const char *const kCfgName[kNumCfg] = {
     "gemm<1,1,8,1,1>", "gemm<1,2,4,1,1>", "gemm<1,4,4,1,1>", "gemm<2,4,1,2,2>", "gemm<2,4,1,1,4>", "gemm<1,4,1,1,4>",
     "gemm<1,1,1,1,4>", "gemm<2,4,4,1,1>", "gemm_lds<4,8,2>", "gemm_lds<4,4,2>", "gemm<2,2,4,1,1>", "gemm<1,1,4,1,1>",
@@ -594,7 +363,7 @@ static bool q8_cfg(int cfg) { return cfg == 0 || cfg == 1 || cfg == 2 || cfg == 
 // known, so the instantiation does not exist (launch_gemm_b16).
 static bool b16_cfg(int cfg) { return cfg != 0 && q8_cfg(cfg); }
 
-static bool cfg_valid(int cfg, const GemmArgs &a, int pre) {
+bool cfg_valid(int cfg, const GemmArgs &a, int pre) {
   const int *s = kCfgShape[cfg];
   if (a.wfmt == 3) {  // split bf16: every register-staged configuration, whole pairs of k-fragments per wave
     if (!split_cfg(cfg) || (pre != PRE_NONE && pre != PRE_LNFOLD)) return false;
@@ -689,6 +458,8 @@ static thread_local bool g_use_split = false;  // set around the codec's enqueue
 static thread_local Tuner *g_tuner = nullptr;
 static thread_local const float *g_zeros = nullptr;  // both set by the entry points from the engine
 static thread_local int g_krot = 1;
+KnobScope::KnobScope(int lds_target, int k_rotate) : lds(g_lds_target), krot(g_krot) { g_lds_target = lds_target; g_krot = k_rotate; }
+KnobScope::~KnobScope() { g_lds_target = lds; g_krot = krot; }
 
 static TuneKey tune_key(const GemmArgs &a, int pre) {
   return TuneKey{a.NT, a.KF, a.CF, a.ntaps, a.MT, a.epi, pre, a.act, a.xstride, a.halo_mode, a.Yraw ? 1 : 0, a.R ? 1 : 0, a.wfmt};
@@ -746,11 +517,11 @@ static int tune_one(hipStream_t st, const GemmArgs &a, int pre, Tuner &t) {
 
 // The int8, bf16 and split-bf16 kernels exist for plain and LN-folded operands only: any other operand pre-processing with
 // those weights has no kernel (never a fall-back to one that would ignore `pre`)
-static bool pre_supported(int wfmt, int pre) { return wfmt == 0 || pre == PRE_NONE || pre == PRE_LNFOLD; }
+bool pre_supported(int wfmt, int pre) { return wfmt == 0 || pre == PRE_NONE || pre == PRE_LNFOLD; }
 
 // The dispatcher's configuration for one GEMM: the tuner's table (or a live tuning run), PTTS_FORCE_CFG, else pick_cfg,
 // then the weight formats' fall-backs among the admitted configurations.  -1: no kernel implements (wfmt, pre).
-static int choose_cfg(hipStream_t st, const GemmArgs &a, int pre) {
+int choose_cfg(hipStream_t st, const GemmArgs &a, int pre) {
   if (!pre_supported(a.wfmt, pre)) return -1;
   int cfg = -1;
   if (g_tuner) {
@@ -788,7 +559,7 @@ static int choose_cfg(hipStream_t st, const GemmArgs &a, int pre) {
 }
 
 // Launches configuration `cfg` (admitted by cfg_valid), bracketed by the profiler under its label; `label` != null receives it
-static void launch_gemm_cfg(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr) {
+void launch_gemm_cfg(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label) {
   // algorithmic traffic: weights once + input rows once (x taps re-read from cache, not counted) + output
   const double K = (double)a.KF * 16, N = (double)a.NT * 16, M = (double)a.M;
   double bytes = 4.0 * (N * K + M * (double)a.CF * 16 + M * N);
@@ -857,14 +628,14 @@ static void launch_resblock(hipStream_t st, GemmArgs a, const Lin &Bl, int pre =
   else LDS_LAUNCH((gemm_lds_kernel<4, 4, 2, PRE_NONE, 2, 8>), grid, dim3(256), lds_pad(32 * 1024), st, a);
 }
 
-static void bind_engine(ptts_engine *e) {
+void bind_engine(ptts_engine *e) {
   g_zeros = e->zeros;
   g_tuner = e->tuner;
   g_prof = &e->prof;
   g_krot = e->opt_k_rotate;
 }
 
-static GemmArgs mk_gemm(const Lin &L, const float *X, int XF, int MT, int M) {
+GemmArgs mk_gemm(const Lin &L, const float *X, int XF, int MT, int M) {
   GemmArgs a;
   memset(&a, 0, sizeof(a));
   a.W = L.w;
@@ -920,7 +691,7 @@ static int attn_nw(int base) {
   if (forced) return forced;
   return base <= 128 ? 4 : (base <= 256 ? 2 : 1);
 }
-static int attn_splits(int base, int max_tiles) {
+int attn_splits(int base, int max_tiles) {
   // `base` = (sequence, head, query block) triples.  Keys are split over workgroups only until ~1024 waves exist
   // (measured at batch 64: 1024 -> 1.139 ms/step, 4096 -> 1.168, 8192 -> 1.211; more splits only add combine launches);
   // a wave never gets less than ~1 key tile.  PTTS_ATTN_WAVES overrides the target for experiments.
@@ -934,12 +705,12 @@ static int attn_splits(int base, int max_tiles) {
 // attn_decode2_kernel<nw, depth>, 3 = attn_cascade_kernel<R = nw, pw, depth, ns>; `code` = the "prefix_cascade" /
 // PTTS_CASCADE value that names a cascade shape (every shape besides the default <4, 2, 3, 1> is an A/B knob: all shapes
 // measured are in profiles/r03_experiments.txt, more waves per workgroup or a fourth register tile lose beside the codec stream)
-struct AttnKernelInfo { int family, nw, pw, depth, ns, code; const char *name; };
 enum {
   AK_ATTN4, AK_ATTN2, AK_ATTN1, AK_ATTN1_D2, AK_DEC1, AK_DEC2_1_2, AK_DEC2_1_3, AK_DEC2_2_3, AK_DEC2_4_3, AK_DEC2_8_3,
-  AK_CASC, AK_CASC_442, AK_CASC_222, AK_CASC_42, AK_CASC_44, AK_CASC_84, AK_CASC_22, kNumAttn
+  AK_CASC, AK_CASC_442, AK_CASC_222, AK_CASC_42, AK_CASC_44, AK_CASC_84, AK_CASC_22, AK_COUNT
 };
-static const AttnKernelInfo kAttn[kNumAttn] = {
+static_assert(AK_COUNT == kNumAttn, "ptts_host.h declares the table's size");
+const AttnKernelInfo kAttn[kNumAttn] = {
     {0, 4, 0, 3, 0, 0, "attn<4,3>"}, {0, 2, 0, 3, 0, 0, "attn<2,3>"}, {0, 1, 0, 3, 0, 0, "attn<1,3>"}, {0, 1, 0, 2, 0, 0, "attn<1,2>"},
     {1, 1, 0, 3, 0, 0, "attn_decode<1>"}, {2, 1, 0, 2, 0, 0, "attn_decode2<1,2>"}, {2, 1, 0, 3, 0, 0, "attn_decode2<1,3>"},
     {2, 2, 0, 3, 0, 0, "attn_decode2<2,3>"}, {2, 4, 0, 3, 0, 0, "attn_decode2<4,3>"}, {2, 8, 0, 3, 0, 0, "attn_decode2<8,3>"},
@@ -956,7 +727,7 @@ static const AttnKernelInfo kAttn[kNumAttn] = {
 //   every key a query block attends (ring >= ctx + Tq - 1); shared prefixes (KvPrefix) are for linear caches only;
 //   decode and cascade kernels: one query per sequence, fp32 output (they ignore h16);
 //   cascade: additionally one split, no ring, no window and a prefix table.
-static bool attn_valid(int k, const AttnArgs &a) {
+bool attn_valid(int k, const AttnArgs &a) {
   if (k < 0 || k >= kNumAttn) return false;
   if (a.H < 1 || a.Tq < 1 || a.QB != cdiv(a.Tq, 16) || a.cap < 16 || a.cap % 16 || a.splits < 1 || a.nseq < 1) return false;
   if (a.splits > 1 && !a.part) return false;
@@ -969,7 +740,7 @@ static bool attn_valid(int k, const AttnArgs &a) {
 
 // The production choice for a launch of BH = nseq * H (sequence, head) pairs; `cascade` = the engine's "prefix_cascade"
 // value when the sequences may share prefixes (0: never the cascade kernel)
-static int choose_attn(const AttnArgs &a, int BH, int cascade) {
+int choose_attn(const AttnArgs &a, int BH, int cascade) {
   if (a.Tq == 1 && cascade && a.pre && a.splits == 1 && !a.ring && a.ctx <= 0 && a.nseq >= 16) {
     // sequences cloned from one voice: prefix keys as MFMA tiles shared by R sequences, private keys per sequence,
     // merged in LDS.  Tile shape: tools/ab.sh env PTTS_CASCADE
@@ -1035,8 +806,8 @@ static void launch_attn_kernel(hipStream_t st, const AttnArgs &at, int BH, int k
 // The one attention launch site of the library: kernel `kernel` (-1: choose_attn's choice) on BH (sequence, head) pairs,
 // then the combine kernel when the keys are split.  bytes / flops: the profiler's figures for the attention launch.
 // Returns the kernel launched, or -1 when attn_valid does not admit it (nothing launched, the entry point reports it).
-static int launch_attention(hipStream_t st, const AttnArgs &at, int BH, int cascade, int kernel, double bytes, double flops,
-                            std::string *label = nullptr) {
+int launch_attention(hipStream_t st, const AttnArgs &at, int BH, int cascade, int kernel, double bytes, double flops,
+                     std::string *label) {
   const int k = kernel >= 0 ? kernel : choose_attn(at, BH, cascade);
   if (!attn_valid(k, at)) {
     if (g_launch_err.empty())
@@ -1559,7 +1330,7 @@ extern "C" void ptts_destroy(ptts_engine *e) {
   delete e;
 }
 
-static hipStream_t S(ptts_engine *e, void *stream) { return stream ? (hipStream_t)stream : e->stream; }
+hipStream_t S(ptts_engine *e, void *stream) { return stream ? (hipStream_t)stream : e->stream; }
 
 // time-embedding constant for a given LSD schedule (reference mlp.py:203-206): computed once on device
 static int prepare_lsd(ptts_engine *e, int steps) {
@@ -2665,7 +2436,7 @@ static void launch_h_cfg(hipStream_t st, const GemmArgs &a, int pre) {
 }
 // The production tile of a bf16 codec GEMM: index into kTileH
 static const int kTileH[4][4] = {{2, 4, 2, 2}, {2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};
-static int choose_h_tile(const GemmArgs &a) {
+int choose_h_tile(const GemmArgs &a) {
   int pick = 3;
   for (int i = 0; i < 4; ++i) {
     const int *t = kTileH[i];
@@ -2676,7 +2447,7 @@ static int choose_h_tile(const GemmArgs &a) {
 }
 // Launches tile `cfg` of gemm_h_kernel on operands a (W, CF, KF, ln_s set), bracketed by the profiler under its label;
 // `label` != null receives it
-static void launch_h_tile(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr) {
+void launch_h_tile(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label) {
   const double K = (double)a.KF * 32, N = (double)a.NT * 16, M = (double)a.M;
   double bytes = 2.0 * (N * K + M * (double)a.CF * 32 + M * N * (a.Yraw ? 2 : 1)) + (a.epi == EPI_RES ? 2.0 * M * N : 0.0);
   if (a.epi == EPI_QKV) bytes += 2.0 * M * N;  // q / k / v leave as fp32
@@ -2693,7 +2464,7 @@ static void launch_h_tile(hipStream_t st, const GemmArgs &a, int pre, int cfg, s
     default: launch_h_cfg<1, 1, 2, 2>(st, a, pre); break;
   }
 }
-static GemmArgs gemm_h_args(const GemmArgs &a_in, int pre, const Lin &L) {
+GemmArgs gemm_h_args(const GemmArgs &a_in, int pre, const Lin &L) {
   GemmArgs a = a_in;
   a.W = (const float *)L.wh;
   a.CF = L.C / 32;
@@ -2707,7 +2478,7 @@ static void launch_gemm_h(hipStream_t st, const GemmArgs &a_in, int pre, const L
   launch_h_tile(st, a, pre, choose_h_tile(a));
 }
 // fp8 conv tile `cfg` (ptts_fp8.hip) on operands g, bracketed by the profiler under its label (one label for every tile)
-static void launch_f8_tile(hipStream_t st, const GemmArgs &g, int cfg, std::string *label = nullptr) {
+void launch_f8_tile(hipStream_t st, const GemmArgs &g, int cfg, std::string *label) {
   const double K = (double)g.KF * 32, N = (double)g.NT * 16, M = (double)g.M;
   const std::string name = "gemm_f8@" + std::to_string((long)g.NT * g.MT);
   if (label) *label = name;
@@ -3502,739 +3273,3 @@ extern "C" int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *ms) {
 }
 extern "C" int64_t ptts_lm_weight_bytes(ptts_engine *e) { return e->lm_bytes; }
 extern "C" int64_t ptts_mimi_weight_bytes(ptts_engine *e) { return e->codec_fp8 ? e->mimi_bytes_f8 : e->codec_bf16 ? e->mimi_bytes_h : e->mimi_bytes; }
-
-extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi, const char *name, float *d_out,
-                                   int64_t capacity, int32_t *rows, int32_t *cols, void *stream) {
-  hipStream_t st = S(e, stream);
-  const ptts_config &c = e->cfg;
-  const float *src = nullptr;
-  int M = 0, K = 0, F = 0;
-  std::string n(name);
-  if (!is_mimi) {
-    ptts_lm_state *s = (ptts_lm_state *)state;
-    if (n == "x") { src = s->dec.x; M = s->B; K = c.d_model; }
-    else if (n == "ce") { src = s->ce; M = s->B; K = c.flow_dim; }
-    else if (n == "fx") { src = s->fx; M = s->B; K = c.flow_dim; }
-    else if (n == "prefill_x") { src = s->pre.x; M = s->pre.MT * 16; K = c.d_model; }
-    else if (n == "noise") {  // the last step's LSD start point (noise), [B][ldim]
-      if (!s->latfm_noise) return fail(-1, "debug_read: noise is only kept by steps that ran the flow cluster");
-      src = s->latfm; M = s->B; K = c.ldim;
-    }
-    else return fail(-1, "unknown buffer " + n);
-    F = K / 16;
-  } else {
-    ptts_mimi_state *s = (ptts_mimi_state *)state;
-    const int par = (s->h_frame - 1) & 1;  // parity of the frame decoded last
-    const int B = s->B;
-    if (n == "upsample") { src = s->u0; M = B * 16; K = c.m_dim; }
-    else if (n == "dec_tr") { src = s->tr_out + par * s->tr_stride; M = B * 16; K = c.m_dim; }
-    else if (n == "seanet0") { src = s->a0 + par * s->a0_stride; M = B * 16; K = 8 * c.n_filters; }
-    else if (n == "tr_attn") { src = s->ao; M = B * 16; K = c.m_dim; }       // last layer's attention output
-    else if (n == "tr_resid") { src = s->u; M = B * 16; K = c.m_dim; }       // last layer's stream after attention
-    else if (n == "tr_ff") { src = s->ff; M = B * 16; K = c.m_ff; }          // last layer's GELU(linear1)
-    else if (n == "seanet11") {
-      M = B; K = s->rows[3];
-      if ((int64_t)M * K > capacity) return fail(-1, "capacity");
-      if (hipMemcpyAsync(d_out, s->pcm_dbg, (size_t)M * K * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-2, "memcpy");
-      *rows = M; *cols = K;
-      return (int64_t)M * K;
-    } else {
-      int idx = atoi(n.c_str() + 6);
-      if (n.compare(0, 6, "seanet") != 0 || idx < 2 || idx > 9) return fail(-1, "unknown buffer " + n);
-      int stage = (idx - 2) / 3;
-      bool is_res = (idx - 2) % 3 == 1;
-      if ((idx - 2) % 3 == 2) return fail(-1, "unknown buffer " + n);
-      int mult = 8 >> stage;
-      K = mult * c.n_filters / 2;
-      M = B * s->rows[stage + 1];
-      const ptts_engine *en = s->e;
-      if (is_res && stage == 2 && en->opt_fuse_pcm && !en->opt_debug_taps && !en->codec_split && en->res_a[2].NT == 2 && s->rows[3] % 64 == 0)
-        return fail(-1, "debug_read: " + n + " stays on chip with \"fuse_pcm\"; set the engine option \"debug_taps\" before decoding");
-      const bool single = en->opt_single_store && !en->codec_split && !en->res_a[stage].wq && !en->res_a[stage].wb16;
-      src = is_res ? s->sbuf[stage] + par * s->s_stride[stage] : single ? s->cbuf[stage] + par * s->c_stride[stage] : s->craw[stage];
-    }
-    F = K / 16;
-  }
-  if ((int64_t)M * K > capacity) return fail(-1, "debug_read: capacity too small");
-  long n4 = (long)M * (K / 4);
-  from_fm_kernel<<<cdiv(n4, 256), 256, 0, st>>>(src, d_out, M, K, F, 0);
-  *rows = M;
-  *cols = K;
-  return (int64_t)M * K;
-}
-
-// ------------------------------------------------------------------------------------------------
-// ptts_debug_gemm (test hook, include/ptts.h): one GEMM of the kernel family, packed by pack_lin and launched by
-// launch_gemm_cfg, between plain row-major buffers and the FM layout
-
-// [M][K] row-major -> FM with MT x KF fragments (rows >= M and columns >= K are zero); one thread per float
-static __global__ void dbg_to_fm_kernel(const float *src, float *dst, int M, int K, int MT, int KF) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)MT * KF * 256) return;
-  const int j = i & 3, lane = (i >> 2) & 63;
-  const long f = i >> 8;
-  const int kf = f % KF, mt = f / KF;
-  const int m = 16 * mt + (lane & 15), k = 16 * kf + 4 * (lane >> 4) + j;
-  dst[i] = (m < M && k < K) ? src[(size_t)m * K + k] : 0.f;
-}
-// FM (NF fragments per row tile) -> [M][N] row-major
-static __global__ void dbg_from_fm_kernel(const float *src, float *dst, int M, int N, int NF) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)M * N) return;
-  const int m = i / N, n = i - (long)m * N;
-  dst[i] = src[(((size_t)(m >> 4) * NF + (n >> 4)) * 64 + 16 * ((n & 15) >> 2) + (m & 15)) * 4 + (n & 3)];
-}
-// weights a packed image holds, as [N][KF * 16] fp32 (k = tap * C + c): fmt 0 = fp32 image, 1 = int8 image times its
-// per-row scale, 2 = bf16 image ([NT][KF/2][64][8], also each half of a split pair)
-static __global__ void dbg_unpack_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KF) {
-  const long K = (long)KF * 16;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)N * K) return;
-  const int n = i / K, k = i - (long)n * K;
-  const int nt = n >> 4, kf = k >> 4, j = k & 3, lane = 16 * ((k & 15) >> 2) + (n & 15);
-  float v;
-  if (fmt == 0) v = ((const float *)img)[(((size_t)nt * KF + kf) * 64 + lane) * 4 + j];
-  else if (fmt == 1) v = ((float)((const uint8_t *)img)[(size_t)nt * KF * 256 + (size_t)(kf >> 2) * 1024 + lane * 16 + 4 * (kf & 3) + j] - 128.f) * scale[n];
-  else v = (float)((const __bf16 *)img)[(((size_t)nt * (KF / 2) + (kf >> 1)) * 64 + lane) * 8 + (kf & 1) * 4 + j];
-  dst[i] = v;
-}
-static __global__ void dbg_guard_kernel(const unsigned *p, long n, unsigned pattern, int *bad) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && p[i] != pattern) atomicOr(bad, 1);
-}
-
-static constexpr unsigned kDbgUnwritten = 0x7fc00000u;  // quiet NaN: an output tile the kernel never wrote
-static constexpr unsigned kDbgGuard = 0x7fa5a5a5u;      // the guard region behind the output
-static constexpr long kDbgGuardFloats = 16384;          // 64 KB
-
-static int debug_gemm(ptts_engine *e, ptts_gemm_case *c, hipStream_t st, ptts_engine &scr) {
-  const int M = c->M, N = c->N, C = c->C, ntaps = c->ntaps, pre = c->pre;
-  c->cfg_used = -1;
-  if (!c->x || !c->w || !c->y) return fail(-1, "debug_gemm: x, w and y are required");
-  if (M < 1 || N < 1 || C < 16 || C % 16 || ntaps < 1) return fail(-1, "debug_gemm: bad shape");
-  if (c->wfmt < 0 || c->wfmt > 3 || pre < PRE_NONE || pre > PRE_LNMOD || c->epi < EPI_STORE || c->epi > EPI_GATE ||
-      c->act < ACT_NONE || c->act > ACT_ELU || c->cfg < -1 || c->cfg >= kNumCfg)
-    return fail(-1, "debug_gemm: enumeration out of range");
-  if (c->lds_target < 0 || c->lds_target > 64 * 1024) return fail(-1, "debug_gemm: lds_target above 64 KB");
-  int rows_in = M;
-  if (ntaps > 1) {
-    // every input row the kernel addresses lies in the sequence's own rows of x or x_prev
-    if (c->T < 16 || c->T % 16 || M % c->T || c->xstride < 1 || c->halo < 0 || c->halo > c->T * c->xstride ||
-        ntaps - 1 - c->halo >= c->xstride || c->halo_mode < 0 || c->halo_mode > 2 || (c->halo_mode == 0 && !c->x_prev))
-      return fail(-1, "debug_gemm: bad convolution geometry");
-    if (pre == PRE_LNFOLD || pre == PRE_LNMOD || pre == PRE_ADDSILU) return fail(-1, "debug_gemm: per-channel prologues are for Linear layers");
-    rows_in = M * c->xstride;
-  } else if (c->xstride != 1) {
-    return fail(-1, "debug_gemm: a Linear has xstride 1");
-  }
-  if ((pre == PRE_LNFOLD && (!c->ln_w || !c->ln_b)) || (pre == PRE_ADDSILU && !c->prevec) ||
-      (pre == PRE_LNMOD && (!c->mod_shift || !c->mod_scale || !c->ln_w != !c->ln_b)))
-    return fail(-1, "debug_gemm: missing prologue operand");
-  if ((c->epi == EPI_RES && !c->r) || (c->epi == EPI_GATE && (!c->r || !c->g))) return fail(-1, "debug_gemm: missing epilogue operand");
-  if (c->wfmt >= 2 && (C / 16) * ntaps % 2) return fail(-1, "debug_gemm: bf16 images need an even number of k-fragments");
-
-  // pack with the engine's own code: a scratch engine whose tensor map holds the case's operands
-  const ptts_tensor tw{"w", c->w, (int64_t)N * C * ntaps}, tb{"b", c->bias, N}, tg{"ln_w", c->ln_w, C}, tbe{"ln_b", c->ln_b, C};
-  scr.tmap["w"] = &tw;
-  if (c->bias) scr.tmap["b"] = &tb;
-  if (pre == PRE_LNFOLD) { scr.tmap["ln_w"] = &tg; scr.tmap["ln_b"] = &tbe; }
-  Lin L;
-  const bool fold = pre == PRE_LNFOLD;
-  CHK(pack_lin(&scr, &L, {{"w", c->bias ? "b" : "", N}}, C, ntaps, 0, 0, 0, fold ? "ln_w" : "", fold ? "ln_b" : "", 0,
-               c->wfmt == 3 ? 0 : c->wfmt));
-  if (c->wfmt == 3) {
-    CHK(dalloc(&scr, &L.wsh, (size_t)L.NT * L.KF * 512));
-    CHK(dalloc(&scr, &L.wsl, (size_t)L.NT * L.KF * 512));
-    pack_weight_split(st, L.w, L.wsh, L.wsl, L.NT, L.KF);
-  }
-  const int NT = L.NT, MT = cdiv(M, 16), MTin = cdiv(rows_in, 16), CF = L.CF;
-  // x: current frame, then the previous one (the kernel's frame-parity double buffer with parity 0)
-  float *xfm = nullptr;
-  const long xfl = (long)MTin * CF * 256;
-  CHK(dallocT(&scr, &xfm, 2 * xfl));
-  dbg_to_fm_kernel<<<cdiv(xfl, 256), 256, 0, st>>>(c->x, xfm, rows_in, C, MTin, CF);
-  if (c->x_prev) dbg_to_fm_kernel<<<cdiv(xfl, 256), 256, 0, st>>>(c->x_prev, xfm + xfl, rows_in, C, MTin, CF);
-  auto to_fm = [&](const float *src, int rows, int cols, int mt, int kf, float **out) -> int {
-    CHK(dallocT(&scr, out, (size_t)mt * kf * 256));
-    dbg_to_fm_kernel<<<cdiv((long)mt * kf * 256, 256), 256, 0, st>>>(src, *out, rows, cols, mt, kf);
-    return 0;
-  };
-  auto copy_pad = [&](const float *src, int n, int pad, float **out) -> int {  // [n] -> zero-padded [pad]
-    CHK(dallocT(&scr, out, (size_t)pad));
-    HIPCHK(hipMemcpyAsync(*out, src, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    return 0;
-  };
-  const long yfl = (long)MT * NT * 256;
-  float *yfm = nullptr;
-  CHK(dallocT(&scr, &yfm, yfl + kDbgGuardFloats));
-  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)yfm, (int)kDbgUnwritten, yfl, st));
-  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(yfm + yfl), (int)kDbgGuard, kDbgGuardFloats, st));
-
-  GemmArgs a = mk_gemm(L, xfm, CF, MT, M);
-  if (c->wfmt == 3) { a.Wq = (const uint8_t *)L.wsh; a.W = (const float *)L.wsl; a.wfmt = 3; }
-  a.Xdstride = xfl;
-  a.T = ntaps > 1 ? c->T : 16;
-  a.xstride = c->xstride;
-  a.halo = c->halo;
-  a.halo_mode = c->halo_mode;
-  a.zeros = e->zeros;
-  a.krot = c->krot;
-  a.epi = c->epi;
-  a.act = c->act;
-  a.Y = yfm;
-  a.YF = NT;
-  float *tmp = nullptr;
-  if (pre == PRE_ADDSILU) { CHK(copy_pad(c->prevec, C, C, &tmp)); a.prevec = tmp; }
-  if (pre == PRE_LNMOD) {
-    if (c->ln_w) {
-      CHK(copy_pad(c->ln_w, C, C, &tmp)); a.lnm_w = tmp;
-      CHK(copy_pad(c->ln_b, C, C, &tmp)); a.lnm_b = tmp;
-    }
-    CHK(to_fm(c->mod_shift, M, C, MT, CF, &tmp)); a.mod_shift = tmp;
-    CHK(to_fm(c->mod_scale, M, C, MT, CF, &tmp)); a.mod_scale = tmp;
-    a.modF = CF;
-  }
-  if (c->epi == EPI_RES || c->epi == EPI_GATE) { CHK(to_fm(c->r, M, N, MT, NT, &tmp)); a.R = tmp; a.RF = NT; }
-  if (c->epi == EPI_GATE) { CHK(to_fm(c->g, M, N, MT, NT, &tmp)); a.G = tmp; a.GF = NT; }
-  if (c->epi == EPI_RES && c->ls) { CHK(copy_pad(c->ls, N, NT * 16, &tmp)); a.ls = tmp; }
-
-  struct Knobs {  // the dispatcher's thread-local knobs for this one launch
-    int lds, krot;
-    Knobs(int l, int k) : lds(g_lds_target), krot(g_krot) { g_lds_target = l; g_krot = k; }
-    ~Knobs() { g_lds_target = lds; g_krot = krot; }
-  } knobs(c->lds_target, c->krot);
-  int cfg = c->cfg;
-  if (cfg >= 0 ? !(pre_supported(a.wfmt, pre) && cfg_valid(cfg, a, pre)) : (cfg = choose_cfg(st, a, pre)) < 0) {
-    HIPCHK(hipStreamSynchronize(st));
-    return 1;
-  }
-  std::string label;
-  launch_gemm_cfg(st, a, pre, cfg, &label);
-  LAUNCHCHK();
-  c->cfg_used = cfg;
-  if (c->label && c->label_cap > 0) {
-    const size_t n = std::min<size_t>(label.size(), (size_t)c->label_cap - 1);
-    memcpy(c->label, label.data(), n);
-    c->label[n] = 0;
-  }
-  int *bad = nullptr;
-  CHK(dallocT(&scr, &bad, 1));
-  dbg_guard_kernel<<<cdiv(kDbgGuardFloats, 256), 256, 0, st>>>((const unsigned *)(yfm + yfl), kDbgGuardFloats, kDbgGuard, bad);
-  dbg_from_fm_kernel<<<cdiv((long)M * N, 256), 256, 0, st>>>(yfm, c->y, M, N, NT);
-  const long nk = (long)N * L.KF * 16;
-  if (c->w_eff) {
-    if (c->wfmt == 0) dbg_unpack_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(L.w, nullptr, 0, c->w_eff, N, L.KF);
-    else if (c->wfmt == 1) dbg_unpack_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(L.wq, L.wscale, 1, c->w_eff, N, L.KF);
-    else dbg_unpack_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(c->wfmt == 2 ? L.wb16 : L.wsh, nullptr, 2, c->w_eff, N, L.KF);
-  }
-  if (c->w_eff_lo && c->wfmt == 3) dbg_unpack_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(L.wsl, nullptr, 2, c->w_eff_lo, N, L.KF);
-  if (fold && c->ln_s) HIPCHK(hipMemcpyAsync(c->ln_s, L.ln_s, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-  if (fold && c->ln_c) HIPCHK(hipMemcpyAsync(c->ln_c, L.ln_c, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-  LAUNCHCHK();
-  int h_bad = 0;
-  HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (h_bad) return fail(-6, "debug_gemm: " + label + " wrote past its output");
-  return 0;
-}
-
-extern "C" int ptts_debug_gemm(ptts_engine *e, ptts_gemm_case *c, void *stream) {
-  if (!e || !c) return fail(-1, "debug_gemm: null argument");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  bind_engine(e);
-  hipStream_t st = S(e, stream);
-  AllocScope as(st);
-  ptts_engine scr;  // owns the case's packed matrix and buffers, freed here whatever the outcome
-  scr.stream = st;
-  scr.device = e->device;
-  const int rc = debug_gemm(e, c, st, scr);
-  (void)hipStreamSynchronize(st);
-  for (void *p : scr.allocs) (void)hipFree(p);
-  return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// ptts_debug_attn (test hook, include/ptts.h): one attention launch (+ combine) through launch_attention, between plain
-// row-major buffers and the kernels' Q block / cache / FM layouts.  Every slot the case must not read holds the case's
-// poison, and every buffer has a poisoned guard of one key tile (1024 floats) on both sides.
-
-static constexpr long kAttnGuard = 16 * 64;
-
-// q [B][Tq][H][64] -> Q blocks [B * H][QB][4][64 lanes][4]: lane c + 16 g of fragment df holds query 16 qb + c, d = 16 df
-// + 4 g + j (queries >= Tq of the last block hold poison)
-static __global__ void dbg_attn_q_kernel(const float *q, float *Q, int B, int Tq, int H, int QB, float poison) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)B * H * QB * 1024) return;
-  const int j = i & 3, lane = (i >> 2) & 63, df = (i >> 8) & 3;
-  const long r = i >> 10;
-  const int qb = r % QB, bh = r / QB, b = bh / H, h = bh - b * H;
-  const int t = 16 * qb + (lane & 15), d = 16 * df + 4 * (lane >> 4) + j;
-  Q[i] = t < Tq ? q[(((size_t)b * Tq + t) * H + h) * 64 + d] : poison;
-}
-
-// the position whose key a row's cache slot holds when the row's queries are at off .. off + Tq - 1, or -1 (poison):
-// ring slots hold the newest position of their class below off + Tq; keys before every query's window, past the last
-// query, and under a borrowed prefix tile (positions < 16 * (len / 16)) are never read
-static __device__ int dbg_attn_slot_pos(int s, int off, int Tq, int ring, int ctx, int len) {
-  const int top = off + Tq - 1;
-  int p = s;
-  if (ring) {
-    if (s >= ring) return -1;
-    p = top - (((top - s) % ring) + ring) % ring;
-  }
-  if (p < 0 || p > top || (ctx > 0 && p < off - ctx + 1) || p < 16 * (len >> 4)) return -1;
-  return p;
-}
-// K and V caches [B][H][cap][64] of the rows (one thread per float)
-static __global__ void dbg_attn_cache_kernel(const float *k, const float *v, const float *pk, const float *pv, float *Kc,
-                                             float *Vc, const int *offset, const int *pre_len, const int *pre_id, int B,
-                                             int T, int pre_T, int H, int cap, int Tq, int ring, int ctx, float poison_k,
-                                             float poison_v) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)B * H * cap * 64) return;
-  const int d = i & 63;
-  const long r = i >> 6;
-  const int s = r % cap, bh = r / cap, b = bh / H, h = bh - b * H;
-  const int id = pre_id ? pre_id[b] : -1, len = id >= 0 ? pre_len[id] : 0;
-  const int p = dbg_attn_slot_pos(s, offset[b], Tq, ring, ctx, len);
-  if (p < 0) {
-    Kc[i] = poison_k;
-    Vc[i] = poison_v;
-  } else if (p < len) {  // the part of the prefix's last, partial tile the row holds itself
-    Kc[i] = pk[(((size_t)id * pre_T + p) * H + h) * 64 + d];
-    Vc[i] = pv[(((size_t)id * pre_T + p) * H + h) * 64 + d];
-  } else {
-    Kc[i] = k[(((size_t)b * T + p) * H + h) * 64 + d];
-    Vc[i] = v[(((size_t)b * T + p) * H + h) * 64 + d];
-  }
-}
-// the prefix owners' caches: bank `id` = [L][2][1][H][pcap][64] at bank + id * bstride, layer `layer` positions < len
-// from pk / pv, every other float poison (K planes poison_k, V planes poison_v)
-static __global__ void dbg_attn_owner_kernel(const float *pk, const float *pv, float *bank, long bstride, const int *pre_len,
-                                             int nbank, int L, int layer, int H, int pcap, int pre_T, float poison_k,
-                                             float poison_v) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long per = (long)L * 2 * H * pcap * 64;
-  if (i >= nbank * per) return;
-  const int id = i / per;
-  const long e = i - id * per;
-  const int d = e & 63;
-  const long r = e >> 6;
-  const int s = r % pcap, pl = r / pcap, h = pl % H, which = (pl / H) & 1, l = pl / (2 * H);
-  float x = which ? poison_v : poison_k;
-  if (l == layer && s < pre_len[id]) x = (which ? pv : pk)[(((size_t)id * pre_T + s) * H + h) * 64 + d];
-  bank[id * bstride + kAttnGuard + e] = x;
-}
-// FMH (bf16, KB 32-column blocks per row tile) -> [M][N] f32
-static __global__ void dbg_from_fmh_kernel(const __bf16 *src, float *dst, int M, int N, int KB) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)M * N) return;
-  const int m = i / N, n = i - (long)m * N;
-  dst[i] = (float)src[fmh_off(m, n & ~3, KB) + (n & 3)];
-}
-
-static int debug_attn(ptts_engine *e, ptts_attn_case *c, hipStream_t st, ptts_engine &scr) {
-  (void)e;
-  const int B = c->B, Tq = c->Tq, H = c->H, T = c->T, cap = c->cap, ring = c->ring, ctx = c->ctx, NB = c->n_pre;
-  const int pcap = c->pre_cap > 0 ? c->pre_cap : cap;
-  c->kernel_used = -1;
-  c->splits_used = 0;
-  if (!c->q || !c->k || !c->v || !c->y || !c->offset) return fail(-1, "debug_attn: q, k, v, offset and y are required");
-  if (B < 1 || Tq < 1 || H < 1 || T < Tq || cap < 16 || c->layer < 0 || NB < 0 || c->splits < -1 || c->splits == 0 ||
-      c->kernel < -1 || c->kernel >= kNumAttn || (c->h16 != 0 && c->h16 != 1))
-    return fail(-1, "debug_attn: bad shape or enumeration");
-  if (NB > 0 && (!c->pk || !c->pv || !c->pre_len || !c->pre_id || c->pre_T < 1 || pcap % 16))
-    return fail(-1, "debug_attn: prefixes need pk, pv, pre_len, pre_id, pre_T and a capacity % 16 == 0");
-  for (int j = 0; j < NB; ++j)
-    if (c->pre_len[j] < 0 || c->pre_len[j] > c->pre_T || c->pre_len[j] > pcap) return fail(-1, "debug_attn: prefix length out of range");
-  for (int b = 0; b < B; ++b) {
-    const int off = c->offset[b];
-    if (off < 0 || off + Tq > T || (!ring && off + Tq > cap)) return fail(-1, "debug_attn: a row's queries lie outside k / v or its cache");
-    if (NB > 0 && (c->pre_id[b] < -1 || c->pre_id[b] >= NB || (c->pre_id[b] >= 0 && c->pre_len[c->pre_id[b]] > off)))
-      return fail(-1, "debug_attn: a row's prefix is unknown or longer than its first query's position");
-  }
-  const int QB = cdiv(Tq, 16), BH = B * H, M = B * Tq, MT = cdiv(M, 16);
-  int splits = c->splits;
-  if (splits < 0) {  // the production rule of the launch shape the case has
-    if (Tq == 1 && !ring) splits = 1;                                                   // FlowLM decode step
-    else if (ring) splits = attn_splits(BH, ring / 16);                                 // codec frame (the state's splits)
-    else if (ctx > 0) splits = attn_splits(BH * QB, std::min(QB, cdiv(ctx, 16) + 2));   // encoder transformer
-    else splits = attn_splits(BH * QB, cdiv(cap, 16));                                  // FlowLM prefill
-  }
-  const long G = kAttnGuard;
-  auto poisoned = [&](long n, float val, float **out) -> int {  // n floats between two guards, all `val`
-    CHK(dallocT(&scr, out, (size_t)(n + 2 * G)));
-    fill_kernel<<<cdiv(n + 2 * G, 256), 256, 0, st>>>(*out, n + 2 * G, val);
-    *out += G;
-    return 0;
-  };
-  auto patterned = [&](long n, unsigned inner, float **out) -> int {  // guards kDbgGuard, inside `inner`
-    CHK(dallocT(&scr, out, (size_t)(n + 2 * G)));
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)*out, (int)kDbgGuard, G, st));
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(*out + G), (int)inner, n, st));
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(*out + G + n), (int)kDbgGuard, G, st));
-    *out += G;
-    return 0;
-  };
-  int *d_ints = nullptr;  // offset [B], pre_id [B], pre_len [NB]
-  CHK(dallocT(&scr, &d_ints, (size_t)2 * B + NB + 1));
-  HIPCHK(hipMemcpyAsync(d_ints, c->offset, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  if (NB > 0) {
-    HIPCHK(hipMemcpyAsync(d_ints + B, c->pre_id, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ints + 2 * B, c->pre_len, (size_t)NB * 4, hipMemcpyHostToDevice, st));
-  }
-  float *Q, *Kc, *Vc, *Y, *part = nullptr;
-  const long nq = (long)BH * QB * 1024, nkv = (long)BH * cap * 64;
-  CHK(poisoned(nq, c->poison_k, &Q));
-  dbg_attn_q_kernel<<<cdiv(nq, 256), 256, 0, st>>>(c->q, Q, B, Tq, H, QB, c->poison_k);
-  CHK(poisoned(nkv, c->poison_k, &Kc));
-  CHK(poisoned(nkv, c->poison_v, &Vc));
-  dbg_attn_cache_kernel<<<cdiv(nkv, 256), 256, 0, st>>>(c->k, c->v, c->pk, c->pv, Kc, Vc, d_ints, NB > 0 ? d_ints + 2 * B : nullptr,
-                                                         NB > 0 ? d_ints + B : nullptr, B, T, c->pre_T, H, cap, Tq, ring, ctx,
-                                                         c->poison_k, c->poison_v);
-  KvPrefix *d_pre = nullptr;
-  if (NB > 0) {
-    // owners: one allocation, bank id at id * bstride, each bank between guards of poison; layers 0 .. layer + 1
-    const int L = c->layer + 2;
-    const long per = (long)L * 2 * H * pcap * 64, bstride = per + 2 * G;
-    float *bank = nullptr;
-    CHK(dallocT(&scr, &bank, (size_t)NB * bstride));
-    fill_kernel<<<cdiv(NB * bstride, 256), 256, 0, st>>>(bank, NB * bstride, c->poison_k);
-    dbg_attn_owner_kernel<<<cdiv(NB * per, 256), 256, 0, st>>>(c->pk, c->pv, bank, bstride, d_ints + 2 * B, NB, L, c->layer, H,
-                                                               pcap, c->pre_T, c->poison_k, c->poison_v);
-    std::vector<KvPrefix> h_pre(B, KvPrefix{nullptr, 0, 0});
-    for (int b = 0; b < B; ++b)
-      if (c->pre_id[b] >= 0) h_pre[b] = KvPrefix{bank + c->pre_id[b] * bstride + G, pcap, c->pre_len[c->pre_id[b]]};
-    CHK(dallocT(&scr, &d_pre, (size_t)B));
-    HIPCHK(hipMemcpyAsync(d_pre, h_pre.data(), (size_t)B * sizeof(KvPrefix), hipMemcpyHostToDevice, st));
-  }
-  // output: FM (fp32, 4 H fragments per row tile) or FMH (bf16, 2 H blocks), NaN-filled between guards
-  const int YF = c->h16 ? 2 * H : 4 * H;
-  const long ny = (long)MT * YF * 256;  // floats (an FMH block of 32 columns holds 512 bf16)
-  CHK(patterned(ny, c->h16 ? 0x7fc07fc0u : kDbgUnwritten, &Y));
-  const long npart = (long)BH * QB * splits * 16 * ATT_PSTRIDE;
-  if (splits > 1) CHK(patterned(npart, kDbgUnwritten, &part));
-
-  AttnArgs at;
-  at.Q = Q; at.Kc = Kc; at.Vc = Vc; at.pre = d_pre; at.layer = c->layer; at.offset = d_ints;
-  at.H = H; at.Tq = Tq; at.QB = QB; at.cap = cap; at.ring = ring; at.ctx = ctx; at.splits = splits;
-  at.part = part; at.Y = Y; at.YF = YF; at.h16 = c->h16; at.nseq = B;
-  int k = c->kernel >= 0 ? c->kernel : choose_attn(at, BH, c->cascade);
-  if (!attn_valid(k, at)) {
-    HIPCHK(hipStreamSynchronize(st));
-    if (c->kernel >= 0) return 1;
-    return fail(-1, std::string("debug_attn: the dispatcher chose ") + kAttn[k].name + ", which attn_valid rejects");
-  }
-  std::string label;
-  k = launch_attention(st, at, BH, c->cascade, k, 0, 0, &label);
-  LAUNCHCHK();
-  c->kernel_used = k;
-  c->splits_used = splits;
-  if (c->label && c->label_cap > 0) {
-    const size_t n = std::min<size_t>(label.size(), (size_t)c->label_cap - 1);
-    memcpy(c->label, label.data(), n);
-    c->label[n] = 0;
-  }
-  int *bad = nullptr;
-  CHK(dallocT(&scr, &bad, 1));
-  HIPCHK(hipMemsetAsync(bad, 0, 4, st));
-  for (const float *g : {Y - G, Y + ny})
-    dbg_guard_kernel<<<cdiv(G, 256), 256, 0, st>>>((const unsigned *)g, G, kDbgGuard, bad);
-  if (part)
-    for (const float *g : {part - G, part + npart})
-      dbg_guard_kernel<<<cdiv(G, 256), 256, 0, st>>>((const unsigned *)g, G, kDbgGuard, bad);
-  if (c->h16) dbg_from_fmh_kernel<<<cdiv((long)M * H * 64, 256), 256, 0, st>>>((const __bf16 *)Y, c->y, M, H * 64, YF);
-  else dbg_from_fm_kernel<<<cdiv((long)M * H * 64, 256), 256, 0, st>>>(Y, c->y, M, H * 64, YF);
-  LAUNCHCHK();
-  int h_bad = 0;
-  HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (h_bad) return fail(-6, "debug_attn: " + label + " wrote past its output or partial buffer");
-  return 0;
-}
-
-extern "C" int ptts_debug_attn(ptts_engine *e, ptts_attn_case *c, void *stream) {
-  if (!e || !c) return fail(-1, "debug_attn: null argument");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  bind_engine(e);
-  hipStream_t st = S(e, stream);
-  AllocScope as(st);
-  ptts_engine scr;  // owns the case's buffers, freed here whatever the outcome
-  scr.stream = st;
-  scr.device = e->device;
-  const int rc = debug_attn(e, c, st, scr);
-  (void)hipStreamSynchronize(st);
-  for (void *p : scr.allocs) (void)hipFree(p);
-  return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// ptts_debug_codec_gemm (test hook, include/ptts.h): one GEMM of the reduced-precision codec (gemm_h_kernel /
-// gemm_f8_kernel) or its last conv (pcm_conv_h_kernel), packed by pack_lin_h / pack_weight_f8 and launched by
-// launch_h_tile / launch_f8_tile, between plain row-major buffers and the FMH / FM8 layouts
-
-__device__ __forceinline__ float dbg_e4m3(uint8_t b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
-// [M][C] row-major -> FMH (fmt 0) / FM8 (fmt 1, saturate(x * inv_xs)) with `rows` rows (rows >= M are zero); eff != null
-// receives the values the kernel reads (e4m3: decoded times xs).  One thread per 4 columns of a row.
-static __global__ void dbg_to_codec_kernel(const float *src, void *dst, float *eff, int M, int C, int rows, int fmt, float inv_xs, float xs) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)rows * (C / 4)) return;
-  const int m = i / (C / 4), c0 = 4 * (int)(i - (long)m * (C / 4));
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (src && m < M) v = *(const f32x4 *)(src + (size_t)m * C + c0);
-  const size_t o = fmh_off(m, c0, C / 32);
-  f32x4 d;
-  if (fmt == 0) {
-    const bf16x4 h = to_bf16x4(v);
-    *(bf16x4 *)((__bf16 *)dst + o) = h;
-    d = from_bf16x4(h);
-  } else {
-    const unsigned q = to_f8x4(v * inv_xs);
-    *(unsigned *)((uint8_t *)dst + o) = q;
-    d = (f32x4){dbg_e4m3(q & 255), dbg_e4m3((q >> 8) & 255), dbg_e4m3((q >> 16) & 255), dbg_e4m3(q >> 24)} * xs;
-  }
-  if (eff && m < M) *(f32x4 *)(eff + (size_t)m * C + c0) = d;
-}
-// FMH / FM8 -> [M][N] f32 (e4m3 decoded, unscaled)
-static __global__ void dbg_from_codec_kernel(const void *src, float *dst, int M, int N, int KB, int fmt) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)M * N) return;
-  const int m = i / N, n = i - (long)m * N;
-  const size_t o = fmh_off(m, n & ~3, KB) + (n & 3);
-  dst[i] = fmt == 0 ? (float)((const __bf16 *)src)[o] : dbg_e4m3(((const uint8_t *)src)[o]);
-}
-// weights of a codec image [NT][KBt][64][8] as [N][KBt * 32] f32 (k = tap * C + c): fmt 0 bf16, 1 e4m3 times scale[n]
-static __global__ void dbg_unpack_codec_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KBt) {
-  const long K = (long)KBt * 32;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)N * K) return;
-  const int n = i / K, k = i - (long)n * K;
-  const size_t o = (((size_t)(n >> 4) * KBt + (k >> 5)) * 64 + 16 * ((k & 31) >> 3) + (n & 15)) * 8 + (k & 7);
-  dst[i] = fmt == 0 ? (float)((const __bf16 *)img)[o] : dbg_e4m3(((const uint8_t *)img)[o]) * scale[n];
-}
-// EPI_QKV outputs -> [M][3 * H * 64]: q from its block layout, k / v from cache slot pos % ring (ring 0: pos)
-static __global__ void dbg_from_qkv_kernel(const float *Q, const float *Kc, const float *Vc, const int *offset, float *dst, int M,
-                                           int H, int Tq, int QB, int cap, int ring) {
-  const int D = H * 64;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)M * 3 * D) return;
-  const int m = i / (3 * D), n = i - (long)m * 3 * D;
-  const int which = n / D, hn = n - which * D, h = hn >> 6, d = hn & 63;
-  const int b = m / Tq, t = m - b * Tq;
-  const size_t bh = (size_t)b * H + h;
-  if (which == 0) {
-    dst[i] = Q[(((bh * QB + (t >> 4)) * 4 + (d >> 4)) * 64 + 16 * ((d & 15) >> 2) + (t & 15)) * 4 + (d & 3)];
-  } else {
-    const int pos = offset[b] + t, slot = ring ? pos % ring : pos;
-    dst[i] = (which == 1 ? Kc : Vc)[(bh * cap + slot) * 64 + d];
-  }
-}
-
-static int debug_codec_gemm(ptts_engine *e, ptts_codec_gemm_case *c, hipStream_t st, ptts_engine &scr) {
-  const int M = c->M, N = c->N, C = c->C, ntaps = c->ntaps, pre = c->pre, epi = c->epi, fmt = c->fmt;
-  const bool pcm = c->kind == 1;
-  c->cfg_used = -1;
-  if (!c->x || !c->w || !c->y) return fail(-1, "debug_codec_gemm: x, w and y are required");
-  if (fmt < 0 || fmt > 1 || c->kind < 0 || c->kind > 1 || (pre != PRE_NONE && pre != PRE_LNFOLD) || c->act < ACT_NONE || c->act > ACT_ELU ||
-      (epi != EPI_STORE && epi != EPI_RES && epi != EPI_QKV && epi != EPI_CONVTR) || c->cfg < -1 || c->cfg > 3 || c->mode < 0 ||
-      c->mode > 1 || c->par < 0 || c->par > 1)
-    return fail(-1, "debug_codec_gemm: enumeration out of range");
-  if (M < 1 || N < 1 || C < 32 || ntaps < 1) return fail(-1, "debug_codec_gemm: bad shape");
-  if (ntaps > 1 || pcm) {
-    if (c->T < 16 || c->T % 16 || M % c->T || c->halo < 0 || c->halo > ntaps - 1 || c->halo > c->T)
-      return fail(-1, "debug_codec_gemm: bad convolution geometry");
-  } else if (c->halo) {
-    return fail(-1, "debug_codec_gemm: a Linear has halo 0");
-  }
-  if (c->mode == 1 && (ntaps != 2 || c->cout < 1 || c->stride < 1 || N != c->cout * c->stride))
-    return fail(-1, "debug_codec_gemm: a ConvTranspose image needs ntaps 2 and N = stride * cout");
-  if (epi == EPI_CONVTR && (c->cout < 1 || c->stride < 1 || N != c->cout * c->stride)) return fail(-1, "debug_codec_gemm: ConvTranspose needs N = stride * cout");
-  if ((epi == EPI_RES && !c->r) || (pre == PRE_LNFOLD && (!c->ln_w || !c->ln_b))) return fail(-1, "debug_codec_gemm: missing operand");
-  if (epi == EPI_QKV && (c->H < 1 || N != 3 * c->H * 64 || c->Tq < 1 || M % c->Tq || !c->offset || c->cap < 1 || c->ring < 0 ||
-                         c->ring > c->cap || (c->ring && c->Tq > c->ring)))
-    return fail(-1, "debug_codec_gemm: bad QKV geometry");
-  if (fmt == 1 && c->xs <= 0.f) return fail(-1, "debug_codec_gemm: the e4m3 activation scale xs must be positive");
-  if (c->yf8 && c->yinv <= 0.f) return fail(-1, "debug_codec_gemm: yinv must be positive");
-  // combinations no kernel implements: nothing launched
-  const bool unsupported =
-      C % 32 || (pcm ? (fmt != 0 || N != 1 || pre != PRE_NONE) :
-                 (N % 32 || (epi == EPI_CONVTR && c->cout % 32) || (pre == PRE_LNFOLD && (fmt != 0 || ntaps != 1)) ||
-                  (epi == EPI_QKV && (fmt != 0 || c->yf8 || c->yraw || c->act != ACT_NONE)) ||
-                  (epi == EPI_RES && (c->yraw || (c->ls && fmt != 0) || (c->yf8 && fmt == 0))) ||  // gemm_h's RES / CONVTR store bf16 only
-                  (epi == EPI_CONVTR && c->yf8 && fmt == 0)));
-  if (unsupported) return 1;
-
-  const int MT = cdiv(M, 16), CB = C / 32;
-  const int rows_in = 16 * cdiv(M + ntaps, 16);  // rows past the end of x (halo < ntaps - 1) read zeros
-  const long half = (long)rows_in * C;           // elements per parity half
-  const int esz = fmt == 0 ? 2 : 1;
-  void *xbuf = nullptr;
-  CHK(dalloc(&scr, &xbuf, 2 * half * esz));
-  const float inv_xs = fmt == 1 ? 1.0f / c->xs : 1.f;
-  const long nq = (long)rows_in * (C / 4);
-  dbg_to_codec_kernel<<<cdiv(nq, 256), 256, 0, st>>>(c->x, (char *)xbuf + (size_t)c->par * half * esz, c->x_eff, M, C, rows_in, fmt, inv_xs, c->xs);
-  dbg_to_codec_kernel<<<cdiv(nq, 256), 256, 0, st>>>(c->x_prev, (char *)xbuf + (size_t)(c->par ^ 1) * half * esz, c->xp_eff, M, C, rows_in, fmt,
-                                                     inv_xs, c->xs);
-  int *dpar = nullptr;
-  CHK(dallocT(&scr, &dpar, 1));
-  HIPCHK(hipMemcpyAsync(dpar, &c->par, 4, hipMemcpyHostToDevice, st));
-
-  // outputs: NaN-filled (bf16 0x7fc0, e4m3 0x7f, f32 quiet NaN), each followed by a guard
-  std::vector<const unsigned *> guards;
-  auto out_buf = [&](size_t elems, int bytes_per, void **p) -> int {
-    const size_t main = (elems * bytes_per + 255) / 256 * 256;
-    CHK(dalloc(&scr, p, main + kDbgGuardFloats * 4));
-    if (bytes_per == 4) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)*p, (int)kDbgUnwritten, main / 4, st));
-    else if (bytes_per == 2) HIPCHK(hipMemsetD16Async((hipDeviceptr_t)*p, 0x7fc0, main / 2, st));
-    else HIPCHK(hipMemsetD8Async((hipDeviceptr_t)*p, 0x7f, main, st));
-    unsigned *g = (unsigned *)((char *)*p + main);
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)g, (int)kDbgGuard, kDbgGuardFloats, st));
-    guards.push_back(g);
-    return 0;
-  };
-
-  GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  std::string label;
-  Lin L;
-  if (pcm) {
-    a.M = M; a.MT = MT; a.CF = CB; a.XF = CB; a.ntaps = ntaps; a.T = c->T; a.halo = c->halo;
-    a.X = (const float *)xbuf; a.Xdstride = half; a.par = dpar; a.epi = EPI_PCM;
-    void *py = nullptr, *pi = nullptr;
-    CHK(out_buf(M, 4, &py));
-    CHK(out_buf(M, 2, &pi));
-    a.pcm = (float *)py;
-    a.pcm_i16 = (int16_t *)pi;
-    label = "pcm_conv_h";
-    {
-      ProfScope ps(st, label, 2.0 * M * C + 4.0 * M, 2.0 * M * C * ntaps);
-      pcm_conv_h_kernel<<<cdiv(M, 256), 256, 0, st>>>(a, c->w, c->bias);
-    }
-    LAUNCHCHK();
-    c->cfg_used = 0;
-    HIPCHK(hipMemcpyAsync(c->y, py, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
-    if (c->y_i16) {
-      std::vector<int16_t> h(M);
-      HIPCHK(hipMemcpyAsync(h.data(), pi, (size_t)M * 2, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      std::vector<float> f(h.begin(), h.end());
-      HIPCHK(hipMemcpyAsync(c->y_i16, f.data(), (size_t)M * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-  } else {
-    // pack with the engine's own code: a scratch engine whose tensor map holds the case's operands.  pack_lin builds the
-    // fp32 image as production does; here (as in production) it is only the source of the padded bias and of the
-    // LayerNorm fold's ln_c: the codec kernels read pack_lin_h's bf16 image or pack_weight_f8's e4m3 one
-    const int nb = epi == EPI_CONVTR || c->mode == 1 ? c->cout : N;
-    const ptts_tensor tw{"w", c->w, (int64_t)N * C * ntaps}, tb{"b", c->bias, nb}, tg{"ln_w", c->ln_w, C}, tbe{"ln_b", c->ln_b, C};
-    scr.tmap["w"] = &tw;
-    if (c->bias) scr.tmap["b"] = &tb;
-    const bool fold = pre == PRE_LNFOLD;
-    if (fold) { scr.tmap["ln_w"] = &tg; scr.tmap["ln_b"] = &tbe; }
-    CHK(pack_lin(&scr, &L, {{"w", c->bias ? "b" : "", N}}, C, ntaps, c->mode, c->cout, c->stride, fold ? "ln_w" : "", fold ? "ln_b" : ""));
-    const int KBt = CB * ntaps;
-    if (fmt == 0) {
-      CHK(pack_lin_h(&scr, &L, "w", N, C, ntaps, c->mode, c->cout, c->stride, fold ? "ln_w" : ""));
-    } else {
-      CHK(dalloc(&scr, &L.wf8, (size_t)L.NT * KBt * 512));
-      CHK(dallocT(&scr, &L.wscale8, (size_t)L.NT * 16));
-      pack_weight_f8(st, c->w, L.wf8, L.wscale8, N, C, ntaps, c->mode, c->cout, c->stride);
-    }
-    LAUNCHCHK();
-    a = mk_gemm(L, (const float *)xbuf, CB, MT, M);
-    a.ntaps = ntaps; a.T = ntaps > 1 ? c->T : 16; a.halo = c->halo; a.Xdstride = half; a.par = dpar;
-    a.epi = epi; a.act = c->act;
-    const int YF = (epi == EPI_CONVTR ? c->cout : N) / 32;
-    const long yrows = epi == EPI_CONVTR ? (long)MT * 16 * c->stride : (long)MT * 16, yrows_out = epi == EPI_CONVTR ? (long)M * c->stride : M;
-    void *y = nullptr, *yraw = nullptr;
-    float *Q = nullptr, *Kc = nullptr, *Vc = nullptr, *rope = nullptr, *tmp = nullptr;
-    int *doff = nullptr;
-    const int B = epi == EPI_QKV ? M / c->Tq : 0, QB = epi == EPI_QKV ? cdiv(c->Tq, 16) : 0;
-    if (epi == EPI_QKV) {
-      const size_t qn = (size_t)B * c->H * QB * 4 * 64 * 4, kn = (size_t)B * c->H * c->cap * 64;
-      CHK(out_buf(qn, 4, (void **)&Q));
-      CHK(out_buf(kn, 4, (void **)&Kc));
-      CHK(out_buf(kn, 4, (void **)&Vc));
-      CHK(dallocT(&scr, &doff, (size_t)B));
-      HIPCHK(hipMemcpyAsync(doff, c->offset, (size_t)B * 4, hipMemcpyHostToDevice, st));
-      CHK(dallocT(&scr, &rope, (size_t)MT * 16 * 64));
-      rope_table_kernel<<<cdiv(M * 32, 256), 256, 0, st>>>(doff, e->freq_mimi, rope, M, c->Tq);
-      a.Q = Q; a.Kc = Kc; a.Vc = Vc; a.offset = doff; a.rope = rope;
-      a.H = c->H; a.Tq = c->Tq; a.QB = QB; a.cap = c->cap; a.ring = c->ring;
-    } else {
-      CHK(out_buf((size_t)yrows * YF * 32, c->yf8 ? 1 : 2, &y));
-      a.Y = (float *)y; a.YF = YF;
-      a.yf8 = c->yf8; a.yinv = c->yf8 ? c->yinv : 1.0f;
-      if (c->yraw) { CHK(out_buf((size_t)yrows * YF * 32, 2, &yraw)); a.Yraw = (float *)yraw; }
-      if (epi == EPI_CONVTR) { a.cout = c->cout; a.stride = c->stride; }
-    }
-    if (epi == EPI_RES) {
-      CHK(dalloc(&scr, (void **)&tmp, (size_t)MT * 16 * N * 2));
-      dbg_to_codec_kernel<<<cdiv((long)MT * 16 * (N / 4), 256), 256, 0, st>>>(c->r, tmp, nullptr, M, N, MT * 16, 0, 1.f, 1.f);
-      a.R = tmp; a.RF = N / 32;
-      if (c->ls) {
-        float *ls = nullptr;
-        CHK(dallocT(&scr, &ls, (size_t)L.NT * 16));
-        HIPCHK(hipMemcpyAsync(ls, c->ls, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-        a.ls = ls;
-      }
-    }
-    int cfg = c->cfg;
-    if (fmt == 0) {
-      a = gemm_h_args(a, pre, L);
-      if (cfg < 0) cfg = choose_h_tile(a);
-      launch_h_tile(st, a, pre, cfg, &label);
-    } else {
-      a.W = (const float *)L.wf8; a.wscale = L.wscale8; a.CF = CB; a.KF = KBt; a.swz = 0; a.xs = c->xs;
-      if (cfg < 0) cfg = choose_f8_tile(a);
-      launch_f8_tile(st, a, cfg, &label);
-    }
-    LAUNCHCHK();
-    c->cfg_used = cfg;
-    if (epi == EPI_QKV) {
-      dbg_from_qkv_kernel<<<cdiv((long)M * N, 256), 256, 0, st>>>(Q, Kc, Vc, doff, c->y, M, c->H, c->Tq, QB, c->cap, c->ring);
-      if (c->rope) HIPCHK(hipMemcpyAsync(c->rope, rope, (size_t)M * 64 * 4, hipMemcpyDeviceToDevice, st));
-    } else {
-      const int Nout = YF * 32;
-      dbg_from_codec_kernel<<<cdiv(yrows_out * Nout, 256), 256, 0, st>>>(y, c->y, yrows_out, Nout, YF, c->yf8 ? 1 : 0);
-      if (c->yraw) dbg_from_codec_kernel<<<cdiv(yrows_out * Nout, 256), 256, 0, st>>>(yraw, c->yraw, yrows_out, Nout, YF, 0);
-    }
-    const long nk = (long)N * KBt * 32;
-    if (c->w_eff) dbg_unpack_codec_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(fmt == 0 ? (const void *)L.wh : L.wf8, L.wscale8, fmt, c->w_eff, N, KBt);
-    if (c->wscale && fmt == 1) HIPCHK(hipMemcpyAsync(c->wscale, L.wscale8, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-    if (fold && c->ln_s) HIPCHK(hipMemcpyAsync(c->ln_s, L.ln_s_h, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-    if (fold && c->ln_c) HIPCHK(hipMemcpyAsync(c->ln_c, L.ln_c, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-  }
-  if (c->label && c->label_cap > 0) {
-    const size_t n = std::min<size_t>(label.size(), (size_t)c->label_cap - 1);
-    memcpy(c->label, label.data(), n);
-    c->label[n] = 0;
-  }
-  int *bad = nullptr;
-  CHK(dallocT(&scr, &bad, 1));
-  for (const unsigned *g : guards) dbg_guard_kernel<<<cdiv(kDbgGuardFloats, 256), 256, 0, st>>>(g, kDbgGuardFloats, kDbgGuard, bad);
-  LAUNCHCHK();
-  int h_bad = 0;
-  HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (h_bad) return fail(-6, "debug_codec_gemm: " + label + " wrote past an output");
-  return 0;
-}
-
-extern "C" int ptts_debug_codec_gemm(ptts_engine *e, ptts_codec_gemm_case *c, void *stream) {
-  if (!e || !c) return fail(-1, "debug_codec_gemm: null argument");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  bind_engine(e);
-  hipStream_t st = S(e, stream);
-  AllocScope as(st);
-  ptts_engine scr;  // owns the case's packed matrix and buffers, freed here whatever the outcome
-  scr.stream = st;
-  scr.device = e->device;
-  const int rc = debug_codec_gemm(e, c, st, scr);
-  (void)hipStreamSynchronize(st);
-  for (void *p : scr.allocs) (void)hipFree(p);
-  return rc;
-}

@@ -1,0 +1,291 @@
+// What the test hooks (ptts_debug.hip) use of the host side in ptts.hip, and nothing else: this list is all that test code
+// may reach into.  Internal (never installed, not part of include/ptts.h).  Everything is defined in ptts.hip; its
+// per-thread state (last error, pending launch error, profiler, allocation stream, launch knobs) stays `static` there and
+// is reached through the functions and scopes below, so no unit ever holds a second copy of it.  The kernel templates
+// (gemm_kernel, gemm_h_kernel, gemm_lds_kernel, attn_*) are instantiated by ptts.hip alone: other units go through the
+// dispatchers declared here.
+#pragma once
+#include "ptts_kernels.h"
+#include "ptts_ext.h"
+
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/ptts.h"
+
+#pragma GCC visibility push(hidden)  // links ptts.hip with ptts_debug.hip; libptts.so exports none of it
+
+// ---- error plumbing ---------------------------------------------------------------------------------------------------
+int fail(int code, const std::string &msg);  // records the calling thread's ptts_last_error(), returns code
+#define HIPCHK(x)                                                                                      \
+  do {                                                                                                 \
+    hipError_t e_ = (x);                                                                               \
+    if (e_ != hipSuccess)                                                                              \
+      return fail(-2, std::string(#x) + ": " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
+  } while (0)
+#define CHK(x)            \
+  do {                    \
+    int r_ = (x);         \
+    if (r_ < 0) return r_; \
+  } while (0)
+// A launch for which no kernel exists (the dispatchers return nothing: they record the message and launch nothing),
+// reported by the entry point's LAUNCHCHK, or by the graph capture that enqueued it
+bool launch_err_pending();
+int take_launch_err();
+#define LAUNCHCHK()                                     \
+  do {                                                  \
+    if (launch_err_pending()) return take_launch_err(); \
+    HIPCHK(hipGetLastError());                          \
+  } while (0)
+
+static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ------------------------------------------------------------------------------------------------
+// Optional per-launch profiler: every kernel launch is bracketed by two HIP events on the stream it is
+// launched on and tagged with its call site, its kernel name and its ALGORITHMIC bytes / flops.
+// Off by default (and always off during graph capture); bench.py switches it on for a few eager steps.
+struct ProfRec { std::string site, kernel; double bytes, flops; hipEvent_t a, b; };
+struct Profiler { bool on = false; std::vector<ProfRec> recs; };
+struct ProfScope {
+  hipStream_t st; Profiler *pr; size_t idx;
+  ProfScope(hipStream_t st_, const std::string &kernel, double bytes, double flops);
+  ~ProfScope();
+};
+
+// ------------------------------------------------------------------------------------------------
+struct Lin {  // one packed weight matrix
+  float *w = nullptr, *bias = nullptr;
+  int N = 0, NT = 0, C = 0, CF = 0, ntaps = 1, KF = 0;
+  int cout = 0, stride = 0;  // transposed-conv view
+  float *ln_s = nullptr, *ln_c = nullptr;  // LayerNorm folded into this matrix (PRE_LNFOLD)
+  // int8 weight-only variant (PTTS_QUANT_*): wq replaces w; ln_g = the LayerNorm gain applied to x on load
+  uint8_t *wq = nullptr;
+  float *wscale = nullptr, *ln_g = nullptr;
+  // bf16 weight variant of a FlowLM Linear (PTTS_LM_BF16): replaces w; packed [NT][KF/2][64][8] (GemmArgs::wfmt == 2)
+  void *wb16 = nullptr;
+  // split-bf16 twin of a codec matrix (PTTS_CODEC_SPLIT): hi = bf16(w), lo = bf16(w - hi) images beside the fp32 one
+  void *wsh = nullptr, *wsl = nullptr;
+  // bf16 twin for the reduced-precision codec path (PTTS_CODEC_BF16): packed [NT][ntaps * C/32][64][8], ln_s from the rounded image
+  __bf16 *wh = nullptr;
+  float *ln_s_h = nullptr;
+  // e4m3 twin of a SEANet conv for the fp8 path (PTTS_CODEC_FP8): packed [NT][ntaps * C/32][64][8 bytes] + per-channel scale
+  void *wf8 = nullptr;
+  float *wscale8 = nullptr;
+  size_t bytes() const { return wq ? (size_t)NT * KF * 256 + (size_t)NT * 64 : wb16 ? (size_t)NT * KF * 512 : (size_t)NT * KF * 1024; }
+};
+
+struct TrLayer {
+  float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ls1 = nullptr, *ls2 = nullptr;
+  Lin qkv, out, ff1, ff2;
+};
+
+struct Tuner;     // ptts.hip
+struct LmLayerP;  // ptts_lm.h
+struct ptts_engine {
+  ptts_config cfg;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<void *> allocs;
+  std::map<void *, size_t> alloc_bytes;  // engine-owned allocations and their sizes (packed-engine files)
+  size_t n_build_allocs = 0;             // allocs[0 .. n) were made by build_engine, in a deterministic order
+  const ptts_tensor *blob_dummy = nullptr;  // ptts_create_from_file: every checkpoint lookup resolves to this zero tensor
+  int blob_has_encoder = 0;
+  std::map<std::string, const ptts_tensor *> tmap;
+  // FlowLM
+  float *bos = nullptr, *freq_lm = nullptr;
+  Lin in_linear;
+  std::vector<TrLayer> lm;
+  float *outnorm_w, *outnorm_b;
+  Lin head, adaln, input_proj, fin;
+  struct Res { float *ln_w, *ln_b; Lin l0, l2; };
+  std::vector<Res> res;
+  Lin te_l0[2], te_l2[2];
+  float *te_freqs[2], *te_alpha[2];
+  std::map<int, float *> tcomb;  // lsd_steps -> [S][flow_dim]
+  std::map<int, float *> tpack;  // K -> the tables of schedules 1..K packed: entry (N, i) at N (N - 1) / 2 + i
+  float *te_scratch = nullptr;
+  // Mimi
+  float *emb_std, *emb_mean, *up_w, *freq_mimi;
+  float *quant_w = nullptr;  // quantizer.output_proj weight [C][ldim], plain (mimi_prologue_kernel)
+  std::vector<TrLayer> mm;
+  Lin conv0, convtr[3], res_a[3], res_b[3], conv_last;
+  float *conv_last_w = nullptr, *conv_last_b = nullptr;  // plain checkpoint tensors (bf16 path's last conv)
+  bool codec_bf16 = false;
+  int64_t mimi_bytes_h = 0;
+  // fp8 SEANet convolutions: static activation scales (device copy lives in an engine allocation, so packed-engine files
+  // carry it; f8s is its host mirror).  Index: 0 = conv0 output, 1 + 3 i = convtr_i output (ELU'd), 2 + 3 i = hidden
+  // activation of residual block i, 3 + 3 i = output of block i (i < 2: the next transposed conv's input)
+  bool codec_split = false;  // PTTS_CODEC_SPLIT: the fp32 codec's GEMM launches use the split-bf16 images
+  bool codec_fp8 = false;
+  float *d_f8s = nullptr;
+  float f8s[16] = {};
+  int64_t mimi_bytes_f8 = 0;
+  int ring = 0;
+  // voice-prompt encode path (SEANet encoder, encoder transformer, downsample, speaker projection)
+  bool has_encoder = false;
+  Lin enc_conv0, enc_res_a[3], enc_res_b[3], enc_down[3], enc_final, enc_downsample, speaker_proj;
+  std::vector<TrLayer> enc_tr;
+  float *zeros = nullptr;
+  int64_t lm_bytes = 0, mimi_bytes = 0;
+  Tuner *tuner = nullptr;
+  Profiler prof;
+  int opt_flow_cluster = 1;
+  int opt_lm_cluster = 0;  // measured slower than five launches per layer: kept as an experiment
+  LmLayerP *lm_table = nullptr;  // device table of the FlowLM layers for lm_cluster_kernel (null: not eligible)
+  int opt_k_rotate = 0;
+  long fuse_res_min_rows = 0;
+  int opt_codec_lds_target = 56 * 1024;  // see lds_pad()
+  int opt_fuse_pcm = 1;      // SEANet's last conv inside the last stage's fused residual block (its output tile never leaves the CU)
+  int opt_debug_taps = 0;    // materialise buffers that fused kernels keep on chip (ptts_debug_read of every stage)
+  int opt_single_store = 1;  // SEANet transposed convs store their raw output once; the next conv applies ELU on its operand read
+  int opt_fuse_res = 1;  // SEANet residual blocks of stages 2 and 3 as one launch each (gemm_lds_kernel<.., NT2>)
+  int opt_flow_max_cus = 128;  // resident workgroups of the single-launch flow MLP (<= the CUs its stream may use)
+  int opt_share_prefix = 1;    // clones of a batch-1 state share its keys / values (KvPrefix) instead of copying them
+  int opt_cascade = 423;       // decode attention of such clones: 10 R + PW of attn_cascade_kernel (0: every sequence on its own)
+  int n_cus = 256;             // hipDeviceProp_t::multiProcessorCount of `device` (cooperative grids never exceed it)
+  std::recursive_mutex mu;  // entry points that enqueue work or touch tuner / profiler / LSD tables hold it
+  int quant_flags = 0;
+};
+#define ENGINE_LOCK(e) std::lock_guard<std::recursive_mutex> lock_((e)->mu)
+
+struct Scratch {
+  float *x = nullptr, *h = nullptr, *ao = nullptr, *ff = nullptr, *q = nullptr, *part = nullptr, *rope = nullptr;
+  int MT = 0, QB = 0, splits_cap = 0;
+};
+
+struct ptts_lm_state {
+  ptts_engine *e;
+  int B, cap, MT;
+  float *kv = nullptr;  // [L][2][B][H][cap][64]
+  int *offset = nullptr;
+  std::vector<int> h_off;
+  Scratch dec, pre;
+  // flow head scratch (FM) + io
+  float *xlat, *c, *ce, *mod, *latfm, *fx, *fh, *f1;
+  float *fstat = nullptr;  // per-tile row statistics of fx (GemmArgs::stat_out / stat_in)
+  // single-launch flow MLP (flow_cluster_kernel): exchange slots, flags, error word; sized for `flow_steps` LSD steps
+  float *fexch = nullptr;
+  unsigned long long *fflags = nullptr;
+  int *ferr = nullptr;
+  int flow_steps = 0, flow_rt = 1, flow_ng = 1;
+  // per-row LSD schedules (ptts_lm_state_reserve_row_lsd): capacity K (0: none), packed time-embedding table of
+  // schedules 1..K, each row's own step count (0: the step's lsd_steps)
+  int lsd_cap = 0;
+  const float *lsd_tab = nullptr;
+  int *lsd_n = nullptr;
+  // shared prefixes (KvPrefix): device table read by the attention kernels, its host mirror, and who owns each row's prefix.
+  // An owner with borrowers is not freed by ptts_lm_state_destroy until the last borrower lets go (`zombie`).
+  KvPrefix *d_pre = nullptr;
+  std::vector<KvPrefix> h_pre;
+  std::vector<ptts_lm_state *> pre_owner;
+  int casc_mode = -1;   // decode attention: -1 = cascade kernel iff rows borrow prefixes now (eager steps), 0 / 1 forced (captures)
+  int n_pre = 0;        // rows of this state that have a prefix
+  int borrowers = 0;    // rows of OTHER states whose prefix is this state's cache
+  bool zombie = false;
+  int n_graphs = 0;   // captured graphs that hold this state's buffer pointers (ensure_flow must not re-allocate under them)
+  int coop_wgs = 0;   // workgroups of the cooperative launch of the last enqueued step (0: per-layer launches)
+  // single-launch transformer stack (lm_cluster_kernel): exchange slots + flags, allocated on first use
+  float *lexch = nullptr;
+  unsigned long long *lflags = nullptr;
+  float *lat, *lat_prev;  // plain [B][ldim]
+  float *eos_logit;
+  uint8_t *is_eos;
+  // device noise source for perf runs (d_noise == NULL and rng_std > 0): N(0, rng_std^2), counter-based
+  float rng_std = 0.f;
+  unsigned long long rng_seed = 0;
+  int *rng_ctr = nullptr;
+  // per-row sampling overrides (ptts_lm_state_set_row_sampling; RowSampling in ptts_kernels.h): marker, {std, clamp, lo,
+  // width} of the device generator's draw, EOS threshold
+  int *samp_on = nullptr;
+  f32x4 *samp_noise = nullptr;
+  float *samp_eos = nullptr;
+  // per-row seeds (ptts_lm_state_set_row_seed): marker, seed, steps the row has taken since the seed was set
+  int *seed_on = nullptr;
+  unsigned long long *seed_val = nullptr;
+  int *seed_ctr = nullptr;
+  bool latfm_noise = false;  // the last enqueued step left its LSD start point in latfm (debug_read "noise")
+  RowSampling rsamp() const { return RowSampling{samp_on, samp_noise, samp_eos, seed_on, seed_val, seed_ctr}; }
+  // continuous batching: parked rows (active[b] == 0) keep computing but do not advance their position
+  int *active = nullptr;
+  std::vector<int> h_active;
+  size_t kv_plane() const { return (size_t)B * e->cfg.num_heads * cap * 64; }
+  float *K(int l) { return kv + (size_t)(2 * l) * kv_plane(); }
+  float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
+};
+
+struct ptts_mimi_state {
+  ptts_engine *e;
+  int B, MTb, MT16;
+  int *frame = nullptr, *offset = nullptr;
+  int h_frame = 0;
+  float *kv = nullptr;  // [ML][2][B][H][ring][64]
+  float *zl, *zq, *u0, *u, *h, *ao, *ff, *q, *part, *tr_out, *rope;
+  long zq_stride, tr_stride;
+  int splits;
+  float *a0;
+  long a0_stride;
+  float *cbuf[3], *craw[3], *rbuf[3], *sbuf[3];  // cbuf/sbuf/rbuf hold ELU'd values, craw the raw skip input
+  long c_stride[3], s_stride[3];
+  int rows[4];  // rows per sequence at each SEANet stage
+  float *pcm_dbg;
+  int16_t *pcm_i16 = nullptr;
+  // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
+  float *pcm_part = nullptr, *pcm_carry = nullptr;
+  long pcm_cstride = 0;
+  size_t kv_plane() const { return (size_t)B * e->cfg.m_heads * e->ring * 64; }
+  float *K(int l) { return kv + (size_t)(2 * l) * kv_plane(); }
+  float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
+};
+
+// ---- entry-point frame, allocation and packing ------------------------------------------------------------------------
+hipStream_t S(ptts_engine *e, void *stream);
+void bind_engine(ptts_engine *e);
+struct AllocScope {  // dalloc's zero fill is queued on the stream of the calling thread's innermost AllocScope
+  hipStream_t prev;
+  explicit AllocScope(hipStream_t st);
+  ~AllocScope();
+};
+int dalloc(ptts_engine *e, void **p, size_t bytes);
+template <typename T>
+static int dallocT(ptts_engine *e, T **p, size_t n) {
+  return dalloc(e, (void **)p, n * sizeof(T));
+}
+struct PackPart { std::string w, b; int N; };
+int pack_lin(ptts_engine *e, Lin *L, const std::vector<PackPart> &parts, int C, int ntaps, int mode = 0, int cout = 0,
+             int stride = 0, const std::string &ln_w = "", const std::string &ln_b = "", int creal = 0, int wfmt = 0);
+int pack_lin_h(ptts_engine *e, Lin *L, const std::string &wname, int N, int C, int ntaps, int mode = 0, int cout = 0,
+               int stride = 0, const std::string &ln_w = "");
+
+// ---- the fp32 / int8 / bf16 / split GEMM dispatcher -------------------------------------------------------------------
+constexpr int kNumCfg = 18;  // 16, 17 appended in round 2 (older cache files stay valid)
+struct KnobScope {  // the dispatcher's per-thread knobs (dynamic-LDS target, "k_rotate") for the launches inside it
+  int lds, krot;
+  KnobScope(int lds_target, int k_rotate);
+  ~KnobScope();
+};
+bool pre_supported(int wfmt, int pre);
+bool cfg_valid(int cfg, const GemmArgs &a, int pre);
+int choose_cfg(hipStream_t st, const GemmArgs &a, int pre);
+void launch_gemm_cfg(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr);
+GemmArgs mk_gemm(const Lin &L, const float *X, int XF, int MT, int M);
+
+// ---- the attention dispatcher -----------------------------------------------------------------------------------------
+struct AttnKernelInfo { int family, nw, pw, depth, ns, code; const char *name; };
+constexpr int kNumAttn = 17;
+extern const AttnKernelInfo kAttn[kNumAttn];
+int attn_splits(int base, int max_tiles);
+bool attn_valid(int k, const AttnArgs &a);
+int choose_attn(const AttnArgs &a, int BH, int cascade);
+int launch_attention(hipStream_t st, const AttnArgs &at, int BH, int cascade, int kernel, double bytes, double flops,
+                     std::string *label = nullptr);
+
+// ---- the reduced-precision codec's tiles ------------------------------------------------------------------------------
+int choose_h_tile(const GemmArgs &a);
+GemmArgs gemm_h_args(const GemmArgs &a_in, int pre, const Lin &L);
+void launch_h_tile(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr);
+void launch_f8_tile(hipStream_t st, const GemmArgs &g, int cfg, std::string *label = nullptr);
+
+#pragma GCC visibility pop
