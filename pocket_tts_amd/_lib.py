@@ -148,10 +148,11 @@ PROTOTYPES = {
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile csrc/*.hip for gfx950 in-tree (hipcc cross-compiles without a GPU).  Every .hip file is one translation
-    unit (ptts.hip = host side + the round-1/2 kernels; newer kernel families live in their own files behind plain C++
-    launcher functions declared in ptts_ext.h; ptts_debug.hip = the C ABI's test hooks, which see the host side through
-    ptts_host.h), compiled in parallel to csrc/.obj/*.o and linked into libptts.so; a unit is recompiled when it or any
-    header is newer than its object."""
+    unit (ptts.hip = host side: engine, states, step orchestration, graphs, C ABI; ptts_dispatch.hip = the GEMM / attention
+    dispatchers and the tuner, the only unit that instantiates the round-1/2 kernel templates; newer kernel families live in
+    their own files behind plain C++ launcher functions declared in ptts_ext.h; ptts_debug.hip = the C ABI's test hooks;
+    these three see each other through ptts_host.h), compiled in parallel to csrc/.obj/*.o and linked into libptts.so; a
+    unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = sorted(SRC.parent.glob("*.hip"))

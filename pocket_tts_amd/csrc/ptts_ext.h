@@ -1,11 +1,12 @@
 // Launchers of the kernel families that live in their own translation units (compiled in parallel with ptts.hip, see
-// pocket_tts_amd/_lib.py::build).  Plain C++ functions: ptts.hip never instantiates these kernels itself.
+// pocket_tts_amd/_lib.py::build).  Plain C++ functions: their callers (ptts.hip, ptts_dispatch.hip) never instantiate these
+// kernels themselves.
 #pragma once
 #include "ptts_kernels.h"
 
 // ---- ptts_lmh.hip: FlowLM Linear layers with bf16 weights (PTTS_LM_BF16) ------------------------------------------
 // register-staged K-split / 2-D tile configurations of gemm_kernel<.., WF = 2>; `cfg` indexes the same table as
-// launch_by_cfg in ptts.hip (only the b16_cfg() subset exists), `pre` is PRE_NONE or PRE_LNFOLD
+// launch_by_cfg in ptts_dispatch.hip (only the b16_cfg() subset exists), `pre` is PRE_NONE or PRE_LNFOLD
 void launch_gemm_b16(hipStream_t st, const GemmArgs &a, int pre, int cfg, unsigned dyn_lds);
 // fp32 packed image [NT][KF][64][4] (LayerNorm gain already multiplied in) -> bf16 image [NT][KF/2][64][8]; with
 // ln_s != null also the fold vector s[n] = sum_k W'[n][k] of the ROUNDED weights (NT * 16 floats)
@@ -24,7 +25,7 @@ void launch_gemm_f8(hipStream_t st, const GemmArgs &a, int cfg, unsigned dyn_lds
 void amax_bf16(hipStream_t st, const void *x, long n, float *out);
 
 // ---- ptts_split.hip: codec GEMMs on error-compensated ("split") bf16 (PTTS_CODEC_SPLIT) ----------------------------------
-// every register-staged configuration of gemm_kernel<.., WF = 3> (cfg = index into ptts.hip's table; LDS-staged ones do not exist)
+// every register-staged configuration of gemm_kernel<.., WF = 3> (cfg = index into ptts_dispatch.hip's table; LDS-staged ones do not exist)
 void launch_gemm_split(hipStream_t st, const GemmArgs &a, int pre, int cfg, unsigned dyn_lds);
 bool split_cfg(int cfg);
 // fp32 packed image [NT][KF][64][4] -> hi = bf16(w) and lo = bf16(w - hi) images, each [NT][KF/2][64][8]

@@ -193,7 +193,7 @@ static void launch_f8_cfg(hipStream_t st, const GemmArgs &a, unsigned dyn) {
   const dim3 grid(cdiv8(a.NT, TN * WN), cdiv8(a.MT, TM * WM)), block(64 * WN * WM);
   gemm_f8_kernel<TN, TM, WN, WM><<<grid, block, dyn, st>>>(a);
 }
-// tile choice as for the bf16 codec (choose_h_tile in ptts.hip): the largest workgroup tile that still yields >= ~2
+// tile choice as for the bf16 codec (choose_h_tile in ptts_dispatch.hip): the largest workgroup tile that still yields >= ~2
 // workgroups per CU; these kernels are bandwidth / launch bound (the fp8 MFMA runs at the bf16 rate = 16x fp32)
 int choose_f8_tile(const GemmArgs &a) {
   static const int tiles[4][4] = {{2, 4, 2, 2}, {2, 2, 2, 2}, {1, 2, 2, 2}, {1, 1, 2, 2}};

@@ -1,13 +1,19 @@
-// What the test hooks (ptts_debug.hip) use of the host side in ptts.hip, and nothing else: this list is all that test code
-// may reach into.  Internal (never installed, not part of include/ptts.h).  Everything is defined in ptts.hip; its
-// per-thread state (last error, pending launch error, profiler, allocation stream, launch knobs) stays `static` there and
-// is reached through the functions and scopes below, so no unit ever holds a second copy of it.  The kernel templates
-// (gemm_kernel, gemm_h_kernel, gemm_lds_kernel, attn_*) are instantiated by ptts.hip alone: other units go through the
-// dispatchers declared here.
+// The boundary between the three units that share the engine's structures.  Internal (never installed, not part of
+// include/ptts.h).
+//   ptts.hip           defines the error plumbing, the profiler, the entry-point frame, allocation and packing sections:
+//                      engine construction, the states, step orchestration, graph capture, the C ABI.
+//   ptts_dispatch.hip  defines the dispatcher sections (GEMM, tuner table, attention, reduced-precision codec tiles).  It
+//                      alone instantiates gemm_kernel, gemm_lds_kernel, gemm_h_kernel and attn_*: every other unit launches
+//                      them through the functions declared here.
+//   ptts_debug.hip     the test hooks; defines nothing declared here, and this list is all that test code may reach into.
+// Per-thread state (last error, pending launch error, profiler and site, allocation stream in ptts.hip; launch knobs,
+// bound tuner and zero line in ptts_dispatch.hip) stays `static` in its one unit and is reached through the functions and
+// scopes below, so no unit ever holds a second copy of it.
 #pragma once
 #include "ptts_kernels.h"
 #include "ptts_ext.h"
 
+#include <array>
 #include <map>
 #include <mutex>
 #include <string>
@@ -15,7 +21,7 @@
 
 #include "../../include/ptts.h"
 
-#pragma GCC visibility push(hidden)  // links ptts.hip with ptts_debug.hip; libptts.so exports none of it
+#pragma GCC visibility push(hidden)  // links the three units; libptts.so exports none of it
 
 // ---- error plumbing ---------------------------------------------------------------------------------------------------
 int fail(int code, const std::string &msg);  // records the calling thread's ptts_last_error(), returns code
@@ -34,6 +40,7 @@ int fail(int code, const std::string &msg);  // records the calling thread's ptt
 // reported by the entry point's LAUNCHCHK, or by the graph capture that enqueued it
 bool launch_err_pending();
 int take_launch_err();
+void note_launch_err(const std::string &msg);  // kept if none is pending (the first missing kernel is the one reported)
 #define LAUNCHCHK()                                     \
   do {                                                  \
     if (launch_err_pending()) return take_launch_err(); \
@@ -53,6 +60,7 @@ struct ProfScope {
   ProfScope(hipStream_t st_, const std::string &kernel, double bytes, double flops);
   ~ProfScope();
 };
+const char *launch_site();  // the call site (SITE in ptts.hip) the calling thread is enqueueing for; "" outside one
 
 // ------------------------------------------------------------------------------------------------
 struct Lin {  // one packed weight matrix
@@ -81,7 +89,19 @@ struct TrLayer {
   Lin qkv, out, ff1, ff2;
 };
 
-struct Tuner;     // ptts.hip
+// Per-engine table of measured tile choices.  `ptts_tune` runs one FlowLM step and one codec frame of a given
+// batch on scratch states with `active` set: every GEMM shape met for the first time is timed with every valid
+// configuration (caches flushed before each timed launch, as in the real step where ~1 GB streams between two
+// uses of a weight) and the fastest is remembered.  Shapes never tuned fall back to pick_cfg.
+typedef std::array<int, 13> TuneKey;
+struct Tuner {
+  std::map<TuneKey, int> table;
+  bool active = false;
+  void *flush = nullptr;
+  size_t flush_bytes = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  std::string log;
+};
 struct LmLayerP;  // ptts_lm.h
 struct ptts_engine {
   ptts_config cfg;
@@ -261,16 +281,24 @@ int pack_lin_h(ptts_engine *e, Lin *L, const std::string &wname, int N, int C, i
 
 // ---- the fp32 / int8 / bf16 / split GEMM dispatcher -------------------------------------------------------------------
 constexpr int kNumCfg = 18;  // 16, 17 appended in round 2 (older cache files stay valid)
-struct KnobScope {  // the dispatcher's per-thread knobs (dynamic-LDS target, "k_rotate") for the launches inside it
+// the dispatcher's per-thread knobs for the launches inside the scope: dynamic-LDS target (see lds_pad), "k_rotate", and
+// whether mk_gemm hands out the split-bf16 images of a PTTS_CODEC_SPLIT engine; the previous values return at its end
+struct KnobScope {
   int lds, krot;
-  KnobScope(int lds_target, int k_rotate);
+  bool split;
+  KnobScope(int lds_target, int k_rotate, bool use_split = false);
   ~KnobScope();
 };
+void bind_dispatch(const ptts_engine *e);    // the calling thread's tuner, zero line and "k_rotate" (bind_engine calls it)
+void unbind_dispatch(const ptts_engine *e);  // ptts_destroy: the calling thread forgets e's tuner
 bool pre_supported(int wfmt, int pre);
 bool cfg_valid(int cfg, const GemmArgs &a, int pre);
 int choose_cfg(hipStream_t st, const GemmArgs &a, int pre);
 void launch_gemm_cfg(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr);
 GemmArgs mk_gemm(const Lin &L, const float *X, int XF, int MT, int M);
+void launch_gemm(hipStream_t st, const GemmArgs &a_in, int pre);  // choose_cfg + launch_gemm_cfg, or the launch error
+bool resblock_fusable(const Lin &A, const Lin &Bl, int MT);
+void launch_resblock(hipStream_t st, GemmArgs a, const Lin &Bl, int pre = PRE_NONE);
 
 // ---- the attention dispatcher -----------------------------------------------------------------------------------------
 struct AttnKernelInfo { int family, nw, pw, depth, ns, code; const char *name; };
@@ -286,6 +314,7 @@ int launch_attention(hipStream_t st, const AttnArgs &at, int BH, int cascade, in
 int choose_h_tile(const GemmArgs &a);
 GemmArgs gemm_h_args(const GemmArgs &a_in, int pre, const Lin &L);
 void launch_h_tile(hipStream_t st, const GemmArgs &a, int pre, int cfg, std::string *label = nullptr);
+void launch_gemm_h(hipStream_t st, const GemmArgs &a_in, int pre, const Lin &L);  // gemm_h_args + choose_h_tile + launch_h_tile
 void launch_f8_tile(hipStream_t st, const GemmArgs &g, int cfg, std::string *label = nullptr);
 
 #pragma GCC visibility pop

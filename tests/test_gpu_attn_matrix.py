@@ -26,7 +26,7 @@ from attn_ref import attn_ref, bf16_round, bf16_ulp, bound, histories
 
 pytestmark = pytest.mark.gpu
 
-# mirror of kAttn in ptts.hip: (family, nw or R, pw, depth, ns, cascade code); family 0 attn_kernel, 1 attn_decode_kernel,
+# mirror of kAttn in ptts_dispatch.hip: (family, nw or R, pw, depth, ns, cascade code); family 0 attn_kernel, 1 attn_decode_kernel,
 # 2 attn_decode2_kernel, 3 attn_cascade_kernel
 KERNELS = [
     ("attn<4,3>", 0, 4, 0, 3, 0, 0), ("attn<2,3>", 0, 2, 0, 3, 0, 0), ("attn<1,3>", 0, 1, 0, 3, 0, 0),
@@ -50,7 +50,7 @@ def cdiv(a, b):
     return (a + b - 1) // b
 
 
-# ---- Python mirror of the dispatcher's rules (ptts.hip: decode_attn_waves, attn_nw, attn_splits, choose_attn, attn_valid)
+# ---- Python mirror of the dispatcher's rules (ptts_dispatch.hip: decode_attn_waves, attn_nw, attn_splits, choose_attn, attn_valid)
 def decode_attn_waves(BH):
     nw = 1
     while nw < 8 and BH * nw * 2 <= 1024:

@@ -48,7 +48,7 @@ def cdiv(a, b):
 
 
 def prod_tile(NT, MT):
-    """mirror of choose_h_tile (ptts.hip) / choose_f8_tile (ptts_fp8.hip)"""
+    """mirror of choose_h_tile (ptts_dispatch.hip) / choose_f8_tile (ptts_fp8.hip)"""
     for i, t in enumerate(TILES):
         if t[0] * t[2] > 2 * NT and i < 3:
             continue

@@ -19,7 +19,7 @@ REPO = Path(__file__).resolve().parents[1]
 TOL = 2.0 ** -18
 REF_MACS = 2 ** 28  # above this many multiply-adds the reference covers a fixed subset of row tiles
 
-# mirror of kCfgName / kCfgShape in ptts.hip: {TN, TM, WK, WN, WM} of the register-staged configurations,
+# mirror of kCfgName / kCfgShape in ptts_dispatch.hip: {TN, TM, WK, WN, WM} of the register-staged configurations,
 # {BNT, BMT, 0, 0, 0} of the LDS-staged ones
 CFG_NAME = ["gemm<1,1,8,1,1>", "gemm<1,2,4,1,1>", "gemm<1,4,4,1,1>", "gemm<2,4,1,2,2>", "gemm<2,4,1,1,4>", "gemm<1,4,1,1,4>",
             "gemm<1,1,1,1,4>", "gemm<2,4,4,1,1>", "gemm_lds<4,8,2>", "gemm_lds<4,4,2>", "gemm<2,2,4,1,1>", "gemm<1,1,4,1,1>",
@@ -32,7 +32,7 @@ NCFG = len(CFG_NAME)
 ADMITTED = {
     0: set(range(NCFG)),
     1: {0, 1, 2, 3, 7, 10, 11},
-    2: {1, 2, 3, 7, 10, 11},  # no 8-wave bf16 kernel (b16_cfg in ptts.hip)
+    2: {1, 2, 3, 7, 10, 11},  # no 8-wave bf16 kernel (b16_cfg in ptts_dispatch.hip)
     3: {1, 2, 3, 4, 5, 6, 7, 10, 11, 13, 14},
 }
 PRE_SFX = {PRE_NONE: "", PRE_LNFOLD: "+ln", PRE_LNMOD: "+lnmod", PRE_ELU: "+elu", PRE_ADDSILU: "+addsilu"}
