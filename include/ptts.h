@@ -135,6 +135,22 @@ int ptts_lm_state_offsets(ptts_lm_state *s, int32_t *h_offsets, void *stream);
  * is kept.  Replaces _run_flow_lm_and_increment_step(text_tokens=.. | audio_conditioning=..)
  * (tts_model.py:317-346, call sites :723, :899). */
 int ptts_lm_prefill(ptts_engine *e, ptts_lm_state *s, const float *d_emb, int32_t t, void *stream);
+/* Ragged prefill: rows of different lengths in one pass.  d_emb f32[B, t_max, d_model]; h_len = HOST array [B] with
+ * 0 <= h_len[b] <= t_max.  The first h_len[b] positions of row b are real, the rest is padding whose contents are arbitrary.
+ *   Result: row b ends as if ptts_lm_prefill had run on it alone with t = h_len[b]: its keys and values land at positions
+ *     [offset[b], offset[b] + h_len[b]), and offset[b] and its host mirror advance by h_len[b].
+ *   Zero length: a row with h_len[b] == 0 is not touched at all.
+ *   Cache isolation: no cache slot at or beyond offset[b] + h_len[b] is written, and none of another row or head.
+ *   Padding independence: padding never influences a real position or the cache; the valid outputs are bitwise independent
+ *     of what the padding of d_emb holds (any bit pattern, NaN included).
+ *   Capacity: checked per row, offset[b] + h_len[b] <= capacity, else -5 and nothing is enqueued; t_max plays no part in it.
+ *     A row that ends exactly at the capacity while offset[b] + t_max lies past it works, and nothing past the capacity is read.
+ *   Errors: -1 for an h_len[b] outside [0, t_max] or t_max < 1.  All lengths 0: returns 0 and enqueues nothing.
+ *   Ordering: asynchronous on `stream`, like ptts_lm_prefill; h_len may be freed or overwritten as soon as the call returns.
+ * The layer stack still runs on B * t_max rows (padding rows cost GEMM time, no weight traffic); ptts_lm_prefill itself,
+ * its launches and its results are unchanged. */
+int ptts_lm_prefill_ragged(ptts_engine *e, ptts_lm_state *s, const float *d_emb, const int32_t *h_len, int32_t t_max,
+                           void *stream);
 /* The text-embedding gather in front of a text prefill (LUTConditioner._get_condition, conditioners/text.py:74-76):
  * d_out f32[n, d_model] <- d_table[d_tokens[i]] for int64 ids; d_table = the checkpoint tensor
  * "flow_lm.conditioner.embed.weight" f32[n_bins, d_model], which stays the caller's.  Asynchronous on `stream`; an id outside

@@ -91,6 +91,7 @@ PROTOTYPES = {
     "ptts_lm_state_copy_row_from": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P]),
     "ptts_lm_state_offsets": (C.c_int, [_P, C.POINTER(C.c_int32), _P]),
     "ptts_lm_prefill": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "ptts_lm_prefill_ragged": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P]),
     "ptts_lm_decode_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_float, _P, _P, _P, _P]),
     "ptts_lm_latent_ptr": (_P, [_P]),
     "ptts_lm_set_noise": (C.c_int, [_P, C.c_float, C.c_uint64]),

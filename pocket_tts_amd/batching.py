@@ -280,9 +280,9 @@ class ContinuousBatcher:
 
     # ---- scheduler (one thread) ----------------------------------------------------------------
     def _admit(self):
-        """Waiting jobs join the free slots.  Jobs with the same voice state and token count are prefilled as ONE batch
-        (voice KV cloned from its device-resident copy, one GEMM pass for the group) and dealt to their slots; nothing
-        synchronises with the host."""
+        """Waiting jobs join the free slots.  All jobs of one admit round, whatever their voices and token counts, are
+        prefilled as ONE batch (each row's voice KV cloned from its device-resident copy, one ragged pass through the
+        layers: `Engine.prefill_group`) and dealt to their slots."""
         eng = self.eng
         with self._lock:
             free = [b for b in range(self.B) if self.slot[b] is None and self.a_emit[b] >= 0]
@@ -291,9 +291,10 @@ class ContinuousBatcher:
                 take.append(self.waiting.popleft())
         if not take:
             return
-        groups: dict = {}
+        order: dict = {}
         for job in take:
-            groups.setdefault((id(job.voice), job.tokens.shape[1]), []).append(job)
+            order.setdefault(id(job.voice), len(order))
+        jobs = sorted(take, key=lambda j: order[id(j.voice)])  # rows of one voice next to each other, as they arrived
         # slots: rows of one voice share its keys (KvPrefix) and the decode attention scores a shared prefix once per 4
         # NEIGHBOURING rows (attn_cascade_kernel), so a job prefers a 4-row group that holds only its own voice
         voice_of = {b: id(self.slot[b].voice) for b in range(self.B) if self.slot[b] is not None}
@@ -307,33 +308,31 @@ class ContinuousBatcher:
             voice_of[b] = vid
             return b
 
-        for (vid, _), jobs in sorted(groups.items(), key=lambda kv: kv[0][0]):
-            try:
-                self._admit_group(jobs, [pick(vid) for _ in jobs])
-            except (ValueError, KeyError, IndexError, TypeError) as e:
-                if len(jobs) == 1:
-                    # a bad request (malformed voice state, capacity): fail THIS request, keep serving the others.  The
-                    # job is in no list any more, so it is notified here (its consumer would block forever).
-                    self._end_request(jobs[0].req, e)
-                    continue
-                for job in jobs:  # find the bad one(s): admit the group's members one by one
-                    with self._lock:
-                        b = next(b for b in range(self.B) if self.slot[b] is None and self.a_emit[b] >= 0)
-                    try:
-                        self._admit_group([job], [b])
-                    except (ValueError, KeyError, IndexError, TypeError) as e1:
-                        self._end_request(job.req, e1)
+        try:
+            self._admit_group(jobs, [pick(id(job.voice)) for job in jobs])
+        except (ValueError, KeyError, IndexError, TypeError) as e:
+            if len(jobs) == 1:
+                # a bad request (malformed voice state, capacity): fail THIS request, keep serving the others.  The
+                # job is in no list any more, so it is notified here (its consumer would block forever).
+                self._end_request(jobs[0].req, e)
+                return
+            for job in jobs:  # find the bad one(s): admit the group's members one by one
+                with self._lock:
+                    b = next(b for b in range(self.B) if self.slot[b] is None and self.a_emit[b] >= 0)
+                try:
+                    self._admit_group([job], [b])
+                except (ValueError, KeyError, IndexError, TypeError) as e1:
+                    self._end_request(job.req, e1)
 
     def _admit_group(self, jobs, rows):
         eng, model = self.eng, self.model
-        voice = model._voice_acquire(jobs[0].voice)  # device-resident voice, no host sync on a hit
+        voices: dict = {}  # each distinct voice once: device-resident, no host sync on a hit
         grp = None
         try:
-            voice_st, t_voice = voice
-            Tt = jobs[0].tokens.shape[1]
-            grp = eng.new_lm_state(len(jobs), t_voice + Tt)
-            grp.copy_from(voice_st)
-            eng.lm_prefill(grp, eng.embed_text(torch.cat([j.tokens for j in jobs], dim=0)))
+            for job in jobs:
+                if id(job.voice) not in voices:
+                    voices[id(job.voice)] = model._voice_acquire(job.voice)
+            grp = eng.prefill_group([voices[id(j.voice)] for j in jobs], [j.tokens for j in jobs])
             for i, b in enumerate(rows):
                 self.st.copy_row_from(b, grp, i)   # KV rows, position, BOS as the pending input, row active
             for job, b in zip(jobs, rows):         # the row's sampling settings, before its first step
@@ -356,7 +355,8 @@ class ContinuousBatcher:
         finally:
             if grp is not None:
                 grp.close()
-            model._voice_release(voice)
+            for voice in voices.values():
+                model._voice_release(voice)
         for job, b in zip(jobs, rows):
             # the slot's codec carries: zero on the codec stream, behind the frames already queued there
             self.ms.reset_row(b, self.pipe.s2)

@@ -281,6 +281,7 @@ struct TrCtx {
   const KvPrefix *pre = nullptr;  // shared voice prefixes of the sequences (FlowLM states) or null
   int layer = 0;
   int cascade = 0;                // decode steps: attn_cascade_kernel tile shape (10 R + PW) or 0
+  const int *qlen = nullptr;      // ragged prefill: real rows of each sequence (GemmArgs::qlen, AttnArgs::qlen) or null
   const float *rope;  // [M][32][2]
   double kv_keys;  // sum over sequences of the keys attended (profiling only)
   const char *tag;
@@ -295,12 +296,12 @@ static void run_tr_layer(hipStream_t st, const TrLayer &T, const TrCtx &c) {
   GemmArgs a = mk_gemm(T.qkv, c.x_in, DF, c.MT, c.M);
   a.epi = EPI_QKV;
   a.Q = c.q; a.Kc = c.Kc; a.Vc = c.Vc; a.offset = c.offset; a.rope = c.rope;
-  a.H = c.H; a.Tq = c.Tq; a.QB = c.QB; a.cap = c.cap; a.ring = c.ring;
+  a.H = c.H; a.Tq = c.Tq; a.QB = c.QB; a.cap = c.cap; a.ring = c.ring; a.qlen = c.qlen;
   launch_gemm(st, a, PRE_LNFOLD);
   AttnArgs at;
   at.Q = c.q; at.Kc = c.Kc; at.Vc = c.Vc; at.offset = c.offset; at.H = c.H; at.Tq = c.Tq; at.QB = c.QB;
   at.cap = c.cap; at.ring = c.ring; at.ctx = c.ctx; at.splits = c.splits; at.part = c.part; at.Y = c.ao; at.YF = DF; at.h16 = 0;
-  at.pre = c.pre; at.layer = c.layer;
+  at.pre = c.pre; at.layer = c.layer; at.qlen = c.qlen;
   const int BH = (c.M / c.Tq) * c.H;
   at.nseq = BH / c.H;
   SITE(s3.c_str());
@@ -872,6 +873,7 @@ static int build_lm_state(ptts_engine *e, ptts_lm_state *s) {
   AllocScope alloc_scope(e->stream);
   CHK(dallocT(nullptr, &s->kv, (size_t)c.num_layers * 2 * s->kv_plane()));
   CHK(dallocT(nullptr, &s->offset, B));
+  CHK(dallocT(nullptr, &s->qlen, B));
   s->h_off.assign(B, 0);
   CHK(dalloc(nullptr, (void **)&s->d_pre, (size_t)B * sizeof(KvPrefix)));
   s->h_pre.assign(B, KvPrefix{nullptr, 0, 0});
@@ -912,7 +914,7 @@ static int build_lm_state(ptts_engine *e, ptts_lm_state *s) {
 
 // ---- shared prefixes: bookkeeping (host side; the device table is updated by set_prefix_kernel on the caller's stream)
 static void lm_state_free(ptts_lm_state *s) {
-  hipFree(s->kv); hipFree(s->offset); hipFree(s->d_pre);
+  hipFree(s->kv); hipFree(s->offset); hipFree(s->qlen); hipFree(s->d_pre);
   free_scratch(&s->dec);
   if (s->pre.x) free_scratch(&s->pre);
   hipFree(s->xlat); hipFree(s->latfm); hipFree(s->c); hipFree(s->ce); hipFree(s->mod); hipFree(s->fx);
@@ -1508,7 +1510,9 @@ static int stream_cu_count(hipStream_t st, int n_cus) {
   return bits > 0 ? std::min(bits, n_cus) : n_cus;
 }
 
-static void lm_layers(hipStream_t st, ptts_engine *e, ptts_lm_state *s, Scratch &sc, int M, int Tq, bool rope_done = false) {
+// qlen / h_len (ragged prefill): device and host copy of the real rows per sequence, the other Tq - len are padding
+static void lm_layers(hipStream_t st, ptts_engine *e, ptts_lm_state *s, Scratch &sc, int M, int Tq, bool rope_done = false,
+                      const int *qlen = nullptr, const int32_t *h_len = nullptr) {
   const ptts_config &c = e->cfg;
   bind_engine(e);
   if (!rope_done) {  // decode steps build the table in their prologue kernel
@@ -1527,7 +1531,8 @@ static void lm_layers(hipStream_t st, ptts_engine *e, ptts_lm_state *s, Scratch 
     t.Kc = s->K(l); t.Vc = s->V(l); t.offset = s->offset; t.rope = sc.rope;
     t.pre = s->d_pre; t.layer = l; t.cascade = e->opt_share_prefix && (s->casc_mode < 0 ? s->n_pre > 0 : s->casc_mode > 0) ? e->opt_cascade : 0;
     t.kv_keys = 0;
-    for (int b = 0; b < s->B; ++b) t.kv_keys += s->h_off[b] + Tq;
+    for (int b = 0; b < s->B; ++b) t.kv_keys += h_len ? (h_len[b] ? s->h_off[b] + h_len[b] : 0) : s->h_off[b] + Tq;
+    t.qlen = qlen;
     t.tag = "lm";
     run_tr_layer(st, e->lm[l], t);
   }
@@ -1556,6 +1561,52 @@ extern "C" int ptts_lm_prefill(ptts_engine *e, ptts_lm_state *s, const float *d_
   lm_layers(st, e, s, sc, M, T);
   add_int_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->offset, s->B, T);
   for (auto &o : s->h_off) o += T;
+  LAUNCHCHK();
+  return 0;
+}
+
+// Rows of different lengths in one pass (include/ptts.h).  The layer stack runs on B * t_max rows; the padding behind a row's
+// h_len[b] real positions stores no key or value, is attended by nobody and attends nothing (GemmArgs::qlen, AttnArgs::qlen),
+// and every other kernel of the stack is row-independent, so what the padding holds never reaches a real row.
+extern "C" int ptts_lm_prefill_ragged(ptts_engine *e, ptts_lm_state *s, const float *d_emb, const int32_t *h_len, int32_t t_max,
+                                      void *stream) {
+  if (!e || !s || !h_len) return fail(-1, "prefill_ragged: null argument");
+  ENGINE_LOCK(e);
+  if (t_max < 1) return fail(-1, "prefill_ragged: t_max must be >= 1");
+  bool any = false;
+  for (int b = 0; b < s->B; ++b) {
+    if (h_len[b] < 0 || h_len[b] > t_max) return fail(-1, "prefill_ragged: row " + std::to_string(b) + " has length " + std::to_string(h_len[b]) +
+                                                              ", expected 0 .. " + std::to_string(t_max));
+    any |= h_len[b] > 0;
+  }
+  for (int b = 0; b < s->B; ++b)
+    if (s->h_off[b] + h_len[b] > s->cap) return fail(-5, "prefill: KV cache capacity exceeded");
+  if (!any) return 0;
+  if (!d_emb) return fail(-1, "prefill_ragged: null argument");
+  HIPCHK(hipSetDevice(e->device));
+  const ptts_config &c = e->cfg;
+  hipStream_t st = S(e, stream);
+  const int M = s->B * t_max;
+  if (!s->pre.x || s->pre.MT < cdiv(M, 16) || s->pre.QB != cdiv(t_max, 16)) {
+    HIPCHK(hipStreamSynchronize(st));
+    if (s->pre.x) free_scratch(&s->pre);
+    AllocScope alloc_scope(st);
+    CHK(alloc_scratch(e, &s->pre, s->B, t_max, c.d_model, c.num_heads, c.ff_dim, s->cap));
+  }
+  Scratch &sc = s->pre;
+  const int MT = cdiv(M, 16);
+  sc.MT = MT;
+  for (int b0 = 0; b0 < s->B; b0 += 64) {  // the lengths ride in the launch arguments: h_len is free on return
+    IntPack pk;
+    const int n = std::min(64, s->B - b0);
+    for (int i = 0; i < 64; ++i) pk.v[i] = i < n ? h_len[b0 + i] : 0;
+    set_ints_kernel<<<1, 64, 0, st>>>(s->qlen + b0, n, pk);
+  }
+  long n4 = (long)MT * (c.d_model / 16) * 64;
+  to_fm_kernel<<<cdiv(n4, 256), 256, 0, st>>>(d_emb, sc.x, M, c.d_model, MT);
+  lm_layers(st, e, s, sc, M, t_max, false, s->qlen, h_len);
+  add_rows_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->offset, s->qlen, s->B);
+  for (int b = 0; b < s->B; ++b) s->h_off[b] += h_len[b];
   LAUNCHCHK();
   return 0;
 }

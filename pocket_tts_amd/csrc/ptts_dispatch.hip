@@ -463,7 +463,7 @@ const AttnKernelInfo kAttn[kNumAttn] = {
 //   least one split (a partial buffer when more);
 //   a ring (slot = position % ring) holds whole tiles (ring % 16 == 0, ring <= cap), has a window (ctx > 0) and keeps
 //   every key a query block attends (ring >= ctx + Tq - 1); shared prefixes (KvPrefix) are for linear caches only;
-//   decode and cascade kernels: one query per sequence, fp32 output (they ignore h16);
+//   decode and cascade kernels: one query per sequence, fp32 output (they ignore h16), no per-sequence query count (qlen);
 //   cascade: additionally one split, no ring, no window and a prefix table.
 bool attn_valid(int k, const AttnArgs &a) {
   if (k < 0 || k >= kNumAttn) return false;
@@ -471,7 +471,7 @@ bool attn_valid(int k, const AttnArgs &a) {
   if (a.splits > 1 && !a.part) return false;
   if (a.ring && (a.ring % 16 || a.ring > a.cap || a.ctx <= 0 || a.ring < a.ctx + a.Tq - 1 || a.pre)) return false;
   const AttnKernelInfo &K = kAttn[k];
-  if (K.family != 0 && (a.Tq != 1 || a.h16)) return false;
+  if (K.family != 0 && (a.Tq != 1 || a.h16 || a.qlen)) return false;
   if (K.family == 3 && (a.splits != 1 || a.ring || a.ctx > 0 || !a.pre)) return false;
   return true;
 }
@@ -479,14 +479,14 @@ bool attn_valid(int k, const AttnArgs &a) {
 // The production choice for a launch of BH = nseq * H (sequence, head) pairs; `cascade` = the engine's "prefix_cascade"
 // value when the sequences may share prefixes (0: never the cascade kernel)
 int choose_attn(const AttnArgs &a, int BH, int cascade) {
-  if (a.Tq == 1 && cascade && a.pre && a.splits == 1 && !a.ring && a.ctx <= 0 && a.nseq >= 16) {
+  if (a.Tq == 1 && !a.qlen && cascade && a.pre && a.splits == 1 && !a.ring && a.ctx <= 0 && a.nseq >= 16) {
     // sequences cloned from one voice: prefix keys as MFMA tiles shared by R sequences, private keys per sequence,
     // merged in LDS.  Tile shape: tools/ab.sh env PTTS_CASCADE
     for (int k = AK_CASC + 1; k < kNumAttn; ++k)
       if (kAttn[k].code == cascade) return k;
     return AK_CASC;
   }
-  if (a.Tq == 1) {
+  if (a.Tq == 1 && !a.qlen) {  // (a ragged prefill of one position: attn_kernel, which skips the sequences without a query)
     // one query: vector ALU + wave reductions.  The keys of a (sequence, head) are split over the nw waves of ONE
     // workgroup and merged in LDS, so small batches reach ~1024 waves without partial buffers or a combine launch.
     // The row-state kernel (no cross-row traffic in its loop).  Small batches: three register tiles (6.0 vs 7.2 us per

@@ -181,6 +181,7 @@ struct ptts_lm_state {
   int B, cap, MT;
   float *kv = nullptr;  // [L][2][B][H][cap][64]
   int *offset = nullptr;
+  int *qlen = nullptr;  // [B] row lengths of the last ragged prefill (ptts_lm_prefill_ragged)
   std::vector<int> h_off;
   Scratch dec, pre;
   // flow head scratch (FM) + io

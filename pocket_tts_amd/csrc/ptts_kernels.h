@@ -156,6 +156,7 @@ struct GemmArgs {
   const int *offset;
   const float *rope;  // [M][32][2] (cos, sin) of pos * freq, built once per step by rope_table_kernel
   int H, Tq, QB, cap, ring;
+  const int *qlen;  // ragged prefill: only the first qlen[b] of sequence b's Tq rows are real, the K / V of the rest are not stored (null: all)
   // EPI_HEAD
   float *eos_logit, *eos_logit2;  // state copy, caller's copy (device or pinned host)
   uint8_t *is_eos, *is_eos2;
@@ -315,7 +316,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int 
       if (which == 0) {
         float *q = a.Q + (((bh * a.QB + (t >> 4)) * 4 + (d >> 4)) * 64 + 16 * g + (t & 15)) * 4;
         *(f32x4 *)q = acc;
-      } else {
+      } else if (!a.qlen || t < a.qlen[b]) {  // a padding row's position may lie past the cache
         const int slot = a.ring ? (pos % a.ring) : pos;
         float *c = (which == 1 ? a.Kc : a.Vc) + (bh * a.cap + slot) * 64 + d;
         *(f32x4 *)c = acc;
@@ -1636,6 +1637,16 @@ static __global__ void add_int_kernel(int *p, int n, int inc) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] += inc;
 }
+// ragged prefill: every row advances by its own length
+static __global__ void add_rows_kernel(int *p, const int *inc, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] += inc[i];
+}
+// up to 64 host integers travel as the launch's own argument: nothing of the caller's array is read after the launch call
+struct IntPack { int v[64]; };
+static __global__ void set_ints_kernel(int *p, int n, IntPack src) {
+  if ((int)threadIdx.x < n) p[threadIdx.x] = src.v[threadIdx.x];
+}
 // end-of-step bookkeeping in one launch: offsets of all rows += inc (increment_steps, reference
 // stateful_module.py:19-26) and one scalar counter (noise counter / frame parity) += 1
 // `active` (optional): parked rows of a continuously batched state keep their offset
@@ -1734,6 +1745,9 @@ struct AttnArgs {
   int YF;
   int h16;  // output as bf16 FMH (YF = 32-column blocks) instead of fp32 FM
   int nseq = 0;  // sequences in the launch (attn_cascade_kernel: its groups of R may overhang)
+  // ragged prefill (attn_kernel + attn_combine_kernel only): sequence b has qlen[b] <= Tq real queries.  The queries behind
+  // them load no keys and their output rows are stored as zeros.  null: every sequence has Tq queries
+  const int *qlen = nullptr;
 };
 #define ATT_PSTRIDE 80
 // key tiles [0, ptl) of (sequence b, head h) come from Kp / Vp (the prefix owner's cache), the rest from the sequence's own
@@ -1792,6 +1806,19 @@ __device__ __forceinline__ void attn_store_out(const AttnArgs &a, int b, int h, 
   }
 }
 
+// ragged prefill: zeros for the output rows of queries [lo, hi) of a query block (the padding behind a sequence's real queries)
+__device__ __forceinline__ void attn_store_zero(const AttnArgs &a, int b, int h, int qb, int lo, int hi, int lane) {
+  const int c = lane & 15, g = lane >> 4;
+  if (c < lo || c >= hi) return;
+  const size_t m = (size_t)b * a.Tq + 16 * qb + c;
+  const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    if (a.h16) *(bf16x4 *)((__bf16 *)a.Y + fmh_off(m, h * 64 + 16 * g + 4 * rr, a.YF)) = to_bf16x4(z);
+    else *(f32x4 *)(a.Y + (((m >> 4) * a.YF + 4 * h + g) * 64 + 16 * rr + (m & 15)) * 4) = z;
+  }
+}
+
 // NW waves of a workgroup share one (sequence, head, query block, key split): each streams a contiguous run of the
 // split's key tiles and the partial (o, m, l) meet in LDS in fixed wave order (as in attn_decode_kernel), so a codec
 // frame reaches ~2048 waves without partial buffers and without the combine launch.
@@ -1807,7 +1834,12 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(AttnArgs a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int off = a.offset[b];
   const int q0 = off + 16 * qb;
-  const int nq = min(16, a.Tq - 16 * qb);
+  const int nq_all = min(16, a.Tq - 16 * qb);
+  const int nq = a.qlen ? min(nq_all, a.qlen[b] - 16 * qb) : nq_all;
+  if (a.qlen && nq < nq_all) {  // padding queries (uniform over the workgroup): zeros instead of stale scratch; the combine
+    if (a.splits == 1 && wave == 0) attn_store_zero(a, b, h, qb, max(nq, 0), nq_all, lane);  // kernel does it for split keys
+    if (nq <= 0) return;  // a block of padding only: no key is loaded (its positions may lie past the cache)
+  }
   const int klo = a.ctx > 0 ? max(0, q0 - a.ctx + 1) : 0;
   const int khi = q0 + nq;
   const int tile_lo = klo >> 4, tile_hi = (khi + 15) >> 4;
@@ -2462,8 +2494,15 @@ static __global__ __launch_bounds__(256) void attn_combine_kernel(AttnArgs a) {
   const int bh = blockIdx.x, qb = blockIdx.y;
   const int b = bh / a.H, h = bh - b * a.H;
   const int qi = threadIdx.x >> 4, c = threadIdx.x & 15;
-  const int nq = min(16, a.Tq - 16 * qb);
-  if (qi >= nq) return;
+  const int nq_all = min(16, a.Tq - 16 * qb);
+  if (qi >= nq_all) return;
+  if (a.qlen && qi >= a.qlen[b] - 16 * qb) {  // ragged prefill, a padding query: zeros (its partials were never written)
+    const size_t m = (size_t)b * a.Tq + 16 * qb + qi;
+    const f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (a.h16) *(bf16x4 *)((__bf16 *)a.Y + fmh_off(m, h * 64 + 4 * c, a.YF)) = to_bf16x4(z);
+    else *(f32x4 *)(a.Y + (((m >> 4) * a.YF + 4 * h + (c >> 2)) * 64 + 16 * (c & 3) + (m & 15)) * 4) = z;
+    return;
+  }
   const float *pp = a.part + (((size_t)bh * a.QB + qb) * a.splits) * 16 * ATT_PSTRIDE + qi * ATT_PSTRIDE;
   float M = NEG_BIG;
   for (int s = 0; s < a.splits; ++s) M = fmaxf(M, pp[(size_t)s * 16 * ATT_PSTRIDE + 64]);

@@ -79,6 +79,20 @@ def chunk_seed(seed: int, chunk: int) -> int:
     return _mix64(_mix64(seed) ^ int(chunk))
 
 
+def pad_token_rows(rows, pad_id: int = 0):
+    """Token rows of different lengths -> (ids int64 [n, t_max], lengths): row i holds `rows[i]` (a tensor or sequence of
+    ids, [T] or [1, T]) followed by `pad_id`, which must be a valid id (`Engine.embed_text` refuses ids outside the
+    table); the padding's embeddings are what `Engine.lm_prefill(..., lengths=)` ignores."""
+    flat = [torch.as_tensor(r, dtype=torch.int64).reshape(-1) for r in rows]
+    if not flat:
+        raise ValueError("need at least one token row")
+    lengths = [int(r.numel()) for r in flat]
+    ids = torch.full((len(flat), max(max(lengths), 1)), int(pad_id), dtype=torch.int64)
+    for i, r in enumerate(flat):
+        ids[i, :lengths[i]] = r
+    return ids, lengths
+
+
 class LMState:
     """FlowLM KV caches of `batch` sequences with capacity `t_cap` positions."""
 
@@ -462,15 +476,45 @@ class Engine:
         self._post()
         return out
 
-    def lm_prefill(self, state: LMState, emb: torch.Tensor):
-        """emb f32[B, T, D]: text embeddings or voice conditioning (reference tts_model.py:722-725,899)."""
+    def lm_prefill(self, state: LMState, emb: torch.Tensor, lengths=None):
+        """emb f32[B, T, D]: text embeddings or voice conditioning (reference tts_model.py:722-725,899).  `lengths` (one
+        int in [0, T] per row): ragged prefill - only the first lengths[b] positions of row b are real, each row ends as
+        if prefilled alone with its own length and whatever the rest of `emb` holds is ignored (include/ptts.h)."""
         emb = emb.to(self.device, torch.float32).contiguous()
         if emb.dim() != 3 or emb.shape[0] != state.batch or emb.shape[2] != self.D:
             raise ValueError(f"prefill expects [B={state.batch}, T, {self.D}], got {tuple(emb.shape)}")
         self._pre()
-        _lib.check(self.lib.ptts_lm_prefill(self.handle, state.handle, _ptr(emb), emb.shape[1], self._sp))
+        if lengths is None:
+            _lib.check(self.lib.ptts_lm_prefill(self.handle, state.handle, _ptr(emb), emb.shape[1], self._sp))
+        else:
+            if len(lengths) != state.batch:
+                raise ValueError(f"prefill expects one length per row ({state.batch}), got {len(lengths)}")
+            h_len = (C.c_int32 * state.batch)(*[int(n) for n in lengths])
+            _lib.check(self.lib.ptts_lm_prefill_ragged(self.handle, state.handle, _ptr(emb), h_len, emb.shape[1], self._sp))
         emb.record_stream(self.stream)
         self._post()
+
+    def prefill_group(self, voices, tokens) -> LMState:
+        """One group state whose row i is voice i's sequence followed by `tokens[i]`: `voices` = one (batch-1 LMState,
+        its length) per row, any mix of voices and token counts.  Rows of one voice borrow its keys (KvPrefix), the text
+        of all rows runs through the layers in ONE (ragged) pass.  The caller deals the rows out with `copy_row_from` and
+        closes the state once those copies have run."""
+        ids, lengths = pad_token_rows(tokens)
+        if len(voices) != len(lengths):
+            raise ValueError("need one voice per token row")
+        grp = self.new_lm_state(len(lengths), max(t + n for (_, t), n in zip(voices, lengths)))
+        try:
+            if all(v[0] is voices[0][0] for v in voices):
+                grp.copy_from(voices[0][0])  # one voice: one clone launch for all rows (what the per-row copies add up to)
+            else:
+                for i, v in enumerate(voices):
+                    grp.copy_row_from(i, v[0], 0)
+            # equal lengths need no padding: the plain entry point, launch for launch
+            self.lm_prefill(grp, self.embed_text(ids), None if min(lengths) == ids.shape[1] else lengths)
+        except Exception:
+            grp.close()
+            raise
+        return grp
 
     def lm_decode_step(self, state: LMState, latent_in=None, noise=None, lsd_steps: int = 1,
                        eos_threshold: float = -4.0, out_latent=None, out_logit=None, out_eos=None):

@@ -226,8 +226,8 @@ class TTSModel:
         requires equal cache offsets across a batch: tts_model.py:491-492, transformer.py:12-13).
 
         `model_states`: one voice state or a list (one per text); `texts`: list of short texts (each must
-        fit one chunk of `MAX_TOKEN_PER_CHUNK` tokens; split longer texts first).  Utterances that share a voice
-        state and a token count are prefilled together as one batch (one GEMM pass per group, the voice's KV cloned
+        fit one chunk of `MAX_TOKEN_PER_CHUNK` tokens; split longer texts first).  All utterances, whatever their
+        voices and token counts, are prefilled together as one batch (one ragged pass, each row's voice KV cloned
         from its device-resident copy), every utterance then owns one row of a batch state, and all rows are decoded
         in lock-step with per-row positions on the two-stream step pipeline (FlowLM step t+1 overlaps codec frame t).
         The host never waits for the GPU inside the loop: the EOS flags and the PCM of a step land in pinned memory
@@ -302,19 +302,10 @@ class TTSModel:
                 ctx = dict(st=batch, ms=ms, pipe=pipe, seeded=[False] * B, clamped=[False] * B)
             batch, ms, pipe = ctx["st"], ctx["ms"], ctx["pipe"]
             nb = pipe.nb
-            # group prefill: rows with the same voice and token count share one batched pass (lengths differ across groups)
-            groups: dict = {}
+            # group prefill: all rows, whatever their voices and token counts, share one ragged pass
+            tmp = [eng.prefill_group([voices[id(ms_)] for ms_ in model_states], toks)]
             for b in range(B):
-                groups.setdefault((id(model_states[b]), toks[b].shape[1]), []).append(b)
-            tmp = []
-            for (vid, Tt), rows in groups.items():
-                voice_st, t_voice = voices[vid]
-                grp = eng.new_lm_state(len(rows), t_voice + Tt)
-                tmp.append(grp)
-                grp.copy_from(voice_st)
-                eng.lm_prefill(grp, eng.embed_text(torch.cat([toks[b] for b in rows], dim=0)))
-                for i, b in enumerate(rows):
-                    batch.copy_row_from(b, grp, i)
+                batch.copy_row_from(b, tmp[0], b)
             for b in range(B):  # the rows' seeds, before their first step (single-chunk texts: chunk 0)
                 on = use_noise and seeds[b] is not None
                 if on:

@@ -6,6 +6,13 @@ N concurrent requests of the text bench.py's API leg uses, against `ContinuousBa
 
 Reports aggregate audio seconds per second for both, their ratio, and the p50 / p99 time from sending a request to
 its first audio byte (the chunk after the WAV header).  Fixed-length requests (EOS threshold +inf), as in bench.py.
+
+    python tools/serve_probe.py --traffic mixed [--voices 4] [...]
+
+Mixed traffic, the batcher only: the requests' texts have pairwise different token counts (8 .. 7 + requests) and are dealt
+over `--voices` voices of different lengths, all submitted before the first step.  Reports the admission time (submission
+to the end of the scheduler's first iteration: every request prefilled and in its slot, one step enqueued) and the
+aggregate audio seconds per second.
 """
 
 from __future__ import annotations
@@ -53,6 +60,61 @@ async def _post(app, body: bytes, ctype: str):
     return first, time.perf_counter() - t0, n
 
 
+def _mixed(args, eng, cfg, model, g):
+    """64 requests of pairwise different token counts over a few voices through the batcher"""
+    import numpy as np
+    import torch
+
+    from bench import FRAME_S
+    from pocket_tts_amd.batching import ContinuousBatcher
+    from pocket_tts_amd.tts_model import _export_lm_state
+
+    B = args.requests
+    voices = []
+    for v in range(args.voices):
+        n = args.voice_len - 7 * v  # voices of different lengths
+        vst = eng.new_lm_state(1, n)
+        eng.lm_prefill(vst, (torch.randn(1, n, eng.D, generator=g) * 0.1).to(eng.device))
+        voices.append(_export_lm_state(eng, vst, n))
+        vst.close()
+    words = "the quick brown fox jumps over the lazy dog and runs far away from here "
+    texts = [(words * 4)[:8 + i].replace(" ", "a") for i in range(B)]  # one token per character: 8 .. 7 + B tokens, no split
+    cb = ContinuousBatcher(model, slots=B, capacity=640)  # voice + 73 tokens + 330 frames
+    admit, wall, samples = [], [], set()
+    try:
+        seen = []
+        inner = cb._admit_group
+
+        def record(jobs, rows):
+            seen.extend(j.tokens.shape[1] for j in jobs)
+            return inner(jobs, rows)
+
+        cb._admit_group = record
+        for i in range(args.reps + 1):
+            eng.sync()
+            t0 = time.perf_counter()
+            reqs = [cb.submit(voices[k % len(voices)], t, max_tokens=10 ** 6) for k, t in enumerate(texts)]
+            cb.step()
+            t1 = time.perf_counter()
+            cb.run_until_idle()
+            n = sum(chunk.shape[0] for r in reqs for chunk in r)
+            dt = time.perf_counter() - t0
+            samples.add(n)
+            if i:
+                admit.append(t1 - t0)
+                wall.append(dt)
+        assert len(seen) == B * (args.reps + 1) and len(set(seen[:B])) == B, "the token counts are not pairwise different"
+        assert len(samples) == 1 and min(samples) > 0, samples
+    finally:
+        cb.close()
+    frames = samples.pop() // eng.frame_samples
+    audio = frames * FRAME_S
+    return dict(config=args.config, traffic="mixed", requests=B, voices=len(voices), tokens=[min(seen), max(seen)],
+                frames=frames, reps=args.reps, admission_ms=[round(a * 1e3, 2) for a in admit],
+                admission_ms_median=float(np.median(admit)) * 1e3, wall_ms=[round(w * 1e3, 1) for w in wall],
+                continuous_batcher_xrt=audio / float(np.median(wall)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="en100m", choices=["en100m", "24l", "tiny"])
@@ -60,6 +122,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--voice-len", type=int, default=126)
     ap.add_argument("--temp", type=float, default=0.7)
+    ap.add_argument("--traffic", default="uniform", choices=["uniform", "mixed"])
+    ap.add_argument("--voices", type=int, default=4, help="mixed traffic: number of voices")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -91,6 +155,15 @@ def main():
     eng.lm_prefill(vst, (torch.randn(1, args.voice_len, eng.D, generator=g) * 0.1).to(dev))
     voice_state = _export_lm_state(eng, vst, args.voice_len)
     vst.close()
+    if args.traffic == "mixed":
+        out = _mixed(args, eng, cfg, model, g)
+        eng.close()
+        line = json.dumps(out)
+        print(line)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(line + "\n")
+        return
     texts = [f"The quick brown fox jumps {i:04d}." for i in range(B)]  # 32 tokens each, as bench.py's API leg
     frames = estimate_max_gen_len(32, cfg.mimi.frame_rate)
     audio = B * frames * FRAME_S
