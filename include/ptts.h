@@ -37,6 +37,7 @@ typedef struct ptts_engine ptts_engine;         /* weights + kernels for one GPU
 typedef struct ptts_lm_state ptts_lm_state;     /* FlowLM KV caches of B sequences       */
 typedef struct ptts_mimi_state ptts_mimi_state; /* Mimi streaming state of B sequences   */
 typedef struct ptts_graph ptts_graph;           /* a captured hipGraph of one step       */
+typedef struct ptts_resampler ptts_resampler;   /* output sample rates of B sequences    */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
 typedef struct ptts_config {
@@ -238,6 +239,33 @@ int ptts_lm_state_set_row_active(ptts_lm_state *s, int32_t row, int32_t active, 
 /* 16-bit PCM straight from the codec's last kernel: (clamp(x, -1, 1) * 32767) truncated, the conversion of
  * StreamingWAVWriter.write_pcm_data (data/audio.py:79).  i16[B, frame_samples], device or pinned host. */
 int ptts_mimi_set_pcm_i16(ptts_mimi_state *s, int16_t *d_pcm_i16);
+/* ---- Output sample rates (no reference counterpart: the reference writes the codec's own rate, data/audio.py:69-72).
+ * A resampler holds, for B sequences, the polyphase tables of a list of rates, each row's rate and each row's history of
+ * PTTS_RS_HIST = 64 input samples; it turns one codec frame f32[B, frame_samples] into out[B, out_max] with row b's
+ * out_n(rate of b) = frame_samples * up / down samples at the front of its line (the rest of the line is not written).
+ * Rate i is the causal polyphase FIR y[N] = sum_k h[k] x_up[N down_i - k] (scipy.signal.upfirdn(h, x, up, down); input
+ * before the stream's start is zero) with h_poly[ph][j] = h[ph + j * up] given as h_up[i] * h_taps[i] floats; the tables
+ * follow each other in h_tables (n_table_floats in all).  up = down = 1 is an exact copy whatever its table holds.  A rate
+ * is refused (-1) unless frame_samples * up % down == 0 (whole outputs per frame, phase 0 at every frame start),
+ * taps - 1 <= 64 (the history covers the filter's reach) and out_n <= 4 * frame_samples: with these every index the kernel
+ * forms is in bounds by construction (csrc/ptts_resample.h).  Filter design: pocket_tts_amd/resample.py.  Every row starts
+ * at rate 0 with a zero history. */
+int ptts_resampler_create(ptts_engine *e, int32_t batch, const int32_t *h_up, const int32_t *h_down, const int32_t *h_taps,
+                          int32_t n_rates, const float *h_tables, int64_t n_table_floats, ptts_resampler **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_resampler(state, NULL, ..) on its states */
+void ptts_resampler_destroy(ptts_resampler *rs);
+/* a new utterance joins `row`: its rate from now on, and a zero history.  Stream-ordered on `stream`; captured graphs pick
+ * the rate up (the kernel reads it from device memory).  -1 for a row or a rate index out of range; nothing is enqueued. */
+int ptts_resampler_set_row(ptts_resampler *rs, int32_t row, int32_t rate_index, void *stream);
+/* One frame: d_pcm_in f32[B, frame_samples] (DEVICE memory) -> out [B, out_max], f32 or (is_i16) int16 converted as
+ * ptts_mimi_set_pcm_i16 converts, device or pinned host; then every row's history <- the frame's last 64 samples (a second
+ * launch: the blocks of a row read the history concurrently).  out_max = the largest out_n of the rates. */
+int ptts_resample_frame(ptts_resampler *rs, const float *d_pcm_in, void *out, int32_t is_i16, void *stream);
+/* While a resampler is set, ptts_mimi_decode and the graph captures append the two launches of ptts_resample_frame behind
+ * the codec's last kernel, reading d_pcm (which must then be device memory; NULL = the state's own buffer).  NULL switches
+ * it off: decodes and captures are then launch for launch those of a state that never had one.  -1 when the resampler's
+ * batch or frame length is not the state's. */
+int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, void *out, int32_t is_i16);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);

@@ -20,6 +20,10 @@ kernels read them per row.  A request without any of them runs exactly as the mo
 A request may also bring a `seed`: its slot's row then draws from the request's own stream (`LMState.set_row_seed`, one
 row seed per text chunk from `engine.chunk_seed`), so the noise of the request does not depend on the slot it was dealt,
 on the step at which it joined or on the other requests, and equals what `TTSModel.generate_audio(..., seed=)` draws.
+
+A batcher built with `sample_rates` lets a request choose its output `sample_rate`: the codec graphs end with the
+streaming polyphase resampler (`resample.py`, `engine.Resampler`), each slot's row runs at its request's rate, and a
+request's chunks hold `frame_samples * rate / native` samples each.  `Request.sample_rate` tells the consumer the rate.
 """
 
 from __future__ import annotations
@@ -74,8 +78,9 @@ def eos_bookkeeping_rows(local_step, max_gen_len, frames_after_eos, eos_step, n_
 class Request:
     """One submitted text.  Iterate to receive chunks; `result()` waits for the whole waveform."""
 
-    def __init__(self, rid: int):
+    def __init__(self, rid: int, sample_rate: int | None = None):
         self.id = rid
+        self.sample_rate = sample_rate  # rate of the chunks (the codec's own unless the request asked for another)
         self._q: queue.Queue = queue.Queue()
         self.frames = 0
         self.error: Exception | None = None
@@ -120,10 +125,11 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "rate")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, rate=0):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
+        self.rate = rate       # index of the request's sample rate in the pipeline's resampler (0: native)
         self.seed = seed       # the chunk's row seed (engine.chunk_seed of the request's seed), or None: the state's stream
         self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
         self.lsd = lsd         # the request's lsd_decode_steps, or None: the model's
@@ -132,8 +138,12 @@ class _Job:
 
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
-                 max_lsd_decode_steps: int | None = None):
+                 max_lsd_decode_steps: int | None = None, sample_rates=None):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
+
+        `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
+        output `sample_rate` among them and the native rate (`submit`).  None: every request gets the codec's rate, with
+        the same graphs and buffers as before.
 
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
@@ -165,8 +175,14 @@ class ContinuousBatcher:
                 raise ValueError(f"max_lsd_decode_steps must be an integer in [1, 64], got {max_lsd_decode_steps}")
             self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
         self.max_lsd = max_lsd_decode_steps
-        self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                 mode="events", pcm_i16=(pcm_format == "i16"))
+        self.native_rate = int(model.config.mimi.sample_rate)
+        if sample_rates is None:  # the call of before, argument for argument
+            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
+                                     mode="events", pcm_i16=(pcm_format == "i16"))
+        else:
+            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
+                                     mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=list(sample_rates))
+        self.rs = self.pipe.rs
         self.pipe.restart()
         self.slot: list = [None] * slots                 # running _Job per slot
         # per-slot bookkeeping of the job that owns the slot (arrays: one numpy pass per step instead of a Python loop)
@@ -198,7 +214,7 @@ class ContinuousBatcher:
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
-               seed: int | None = None) -> Request:
+               sample_rate: int | None = None, seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -207,7 +223,9 @@ class ContinuousBatcher:
         [1, max_lsd_decode_steps]) is the number of Euler steps of this request's flow head; a batcher built without
         `max_lsd_decode_steps` accepts only the model's value.  `seed` (an int in [0, 2**63)) makes the request's noise
         reproducible: the same seed, text and settings draw the same noise in any slot, under any traffic, and in
-        `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream."""
+        `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.  `sample_rate`: the rate of
+        this request's audio, one of the batcher's `sample_rates` or the native rate (None: native); anything else raises
+        ValueError, as does any rate but the native one on a batcher built without `sample_rates`."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -234,6 +252,13 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
+        rate = 0
+        if sample_rate is not None:
+            if self.rs is not None:
+                rate = self.rs.index_of(sample_rate)
+            elif isinstance(sample_rate, bool) or sample_rate != self.native_rate:
+                raise ValueError(f"sample rate {sample_rate!r}: this batcher writes {self.native_rate} Hz only (build it "
+                                 "with sample_rates for per-request rates)")
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -253,7 +278,7 @@ class ContinuousBatcher:
         t_voice = _state_current_end(model_state)
         jobs = []
         with self._lock:
-            req = Request(self._next_id)
+            req = Request(self._next_id, self.rs.rates[rate] if self.rs is not None else self.native_rate)
             self._next_id += 1
         for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
@@ -265,7 +290,7 @@ class ContinuousBatcher:
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp, lsd, None if seed is None else chunk_seed(seed, i)))
+                             samp, lsd, None if seed is None else chunk_seed(seed, i), rate))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -360,6 +385,8 @@ class ContinuousBatcher:
         for job, b in zip(jobs, rows):
             # the slot's codec carries: zero on the codec stream, behind the frames already queued there
             self.ms.reset_row(b, self.pipe.s2)
+            if self.rs is not None:  # the row's output rate and a zero filter history, on the same stream
+                self.rs.set_row(b, job.rate, self.pipe.s2)
             job.start = self.g
             self.slot[b] = job
             self.a_start[b], self.a_gen[b], self.a_fae[b] = self.g, job.gen, job.fae
@@ -389,11 +416,15 @@ class ContinuousBatcher:
         eos_bookkeeping_rows(frame - self.a_start, self.a_gen, self.a_fae, self.a_eos, self.a_emit,
                              pipe.flag[q].numpy() != 0, rows)
         # one copy of the frame out of the pinned ring (numpy memcpy: no intra-op thread team), rows are views of it
-        pcm = torch.from_numpy((pipe.pcm16_of(frame) if self.pcm_format == "i16" else pipe.pcm_of(frame)).numpy().copy())
+        if self.rs is not None:
+            ring = pipe.out_of(frame)
+        else:
+            ring = pipe.pcm16_of(frame) if self.pcm_format == "i16" else pipe.pcm_of(frame)
+        pcm = torch.from_numpy(ring.numpy().copy())
         for b in np.nonzero(rows)[0]:
             job = self.slot[b]
             if self.a_emit[b] < 0:
-                job.req._q.put(pcm[b])
+                job.req._q.put(pcm[b] if self.rs is None else pcm[b, :self.rs.out_n(job.rate)])
                 job.req.frames += 1
                 continue
             if self.a_eos[b] < 0:

@@ -2173,11 +2173,35 @@ static int mimi_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, cons
   return 0;
 }
 
+// Output sample rates: while a resampler is set, its two launches follow the codec's last kernel on the same stream and read
+// the frame's fp32 PCM from device memory (d_pcm, or the state's own buffer); out [B][out_max] is f32 or i16, device or pinned
+// host.  NULL switches it off: decodes and captures are then launch for launch what they were.
+extern "C" int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, void *out, int32_t is_i16) {
+  if (!s) return fail(-1, "null state");
+  if (rs && !out) return fail(-1, "set_resampler: null output");
+  if (rs && (resample_batch(rs) != s->B || resample_frame_samples(rs) != s->rows[3]))
+    return fail(-1, "set_resampler: the resampler's batch or frame length is not the state's");
+  s->rs = rs;
+  s->rs_out = rs ? out : nullptr;
+  s->rs_i16 = rs ? (is_i16 != 0) : 0;
+  return 0;
+}
+
+// the codec frame, then the resampler's launches if the state has one
+static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
+  CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
+  if (!s->rs) return 0;
+  SITE("resample");
+  const int r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, s->rs_out, s->rs_i16);
+  SITE("");
+  return r;
+}
+
 extern "C" int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream) {
   ENGINE_LOCK(e);
   HIPCHK(hipSetDevice(e->device));
   if (!d_latent) return fail(-1, "null latent");
-  CHK(mimi_enqueue(S(e, stream), e, s, d_latent, d_pcm));
+  CHK(mimi_frame_enqueue(S(e, stream), e, s, d_latent, d_pcm));
   s->h_frame += 1;
   LAUNCHCHK();
   return 0;
@@ -2437,7 +2461,7 @@ extern "C" int ptts_graph_capture_mimi(ptts_engine *e, ptts_mimi_state *s, const
   HIPCHK(hipSetDevice(e->device));
   ptts_graph *g = new ptts_graph();
   g->mimi = s;
-  const int rc = capture(e, g, [&](hipStream_t st) { return mimi_enqueue(st, e, s, d_latent, d_pcm); });
+  const int rc = capture(e, g, [&](hipStream_t st) { return mimi_frame_enqueue(st, e, s, d_latent, d_pcm); });
   if (rc < 0) { g->mimi = nullptr; ptts_graph_destroy(g); return rc; }
   *out = g;
   return 0;
@@ -2468,7 +2492,7 @@ extern "C" int ptts_graph_capture_pipelined(ptts_engine *e, ptts_lm_state *s, pt
     if (hipStreamWaitEvent(side, fork, 0) != hipSuccess) return fail(-2, "fork wait");
     int r = lm_step_enqueue(st, e, s, nullptr, d_noise, lsd_steps, eos_threshold, d_latent_out, d_eos_logit, d_is_eos);
     if (r < 0) return r;
-    r = mimi_enqueue(side, e, m, d_mimi_latent_in, d_pcm);
+    r = mimi_frame_enqueue(side, e, m, d_mimi_latent_in, d_pcm);
     if (r < 0) return r;
     if (hipEventRecord(join, side) != hipSuccess) return fail(-2, "join record");
     if (hipStreamWaitEvent(st, join, 0) != hipSuccess) return fail(-2, "join wait");

@@ -30,3 +30,11 @@ void launch_gemm_split(hipStream_t st, const GemmArgs &a, int pre, int cfg, unsi
 bool split_cfg(int cfg);
 // fp32 packed image [NT][KF][64][4] -> hi = bf16(w) and lo = bf16(w - hi) images, each [NT][KF/2][64][8]
 void pack_weight_split(hipStream_t st, const float *src, void *hi, void *lo, int NT, int KF);
+
+// ---- ptts_resample.hip: per-request output sample rates (streaming polyphase resampler behind the codec) ---------------
+// the frame's two launches on `st`: d_pcm f32[B][frame_samples] (device) -> out f32 / i16 [B][out_max] (device or pinned host),
+// then the rows' histories <- the frame's tail.  Returns 0 or a negative error code (message recorded).
+struct ptts_resampler;
+int resample_enqueue(hipStream_t st, ptts_resampler *rs, const float *d_pcm, void *out, int is_i16);
+int resample_frame_samples(const ptts_resampler *rs);
+int resample_batch(const ptts_resampler *rs);

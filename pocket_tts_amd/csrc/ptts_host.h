@@ -253,6 +253,10 @@ struct ptts_mimi_state {
   int rows[4];  // rows per sequence at each SEANet stage
   float *pcm_dbg;
   int16_t *pcm_i16 = nullptr;
+  // output sample rates (ptts_mimi_set_resampler): the two resampler launches follow the codec's last kernel
+  ptts_resampler *rs = nullptr;
+  void *rs_out = nullptr;
+  int rs_i16 = 0;
   // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
   float *pcm_part = nullptr, *pcm_carry = nullptr;
   long pcm_cstride = 0;

@@ -224,6 +224,97 @@ class MimiState:
         """int16 copy of the PCM written by the decodes / graph captures issued after this call (None: off)"""
         _lib.check(self.engine.lib.ptts_mimi_set_pcm_i16(self.handle, _ptr(buf) if buf is not None else None))
 
+    def set_resampler(self, rs: "Resampler | None", out: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `rs` behind the codec's last kernel: the frame's PCM
+        (which must then be a DEVICE tensor) is resampled into `out` [B, rs.out_max], float32 or int16, device or pinned
+        host (include/ptts.h: ptts_mimi_set_resampler).  None: off, the launches are those of before."""
+        if rs is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_resampler(self.handle, None, None, 0))
+            return
+        rs._check_out(out)
+        _lib.check(self.engine.lib.ptts_mimi_set_resampler(self.handle, rs.handle, _ptr(out), int(out.dtype == torch.int16)))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resampler:
+    """Output sample rates of `batch` sequences (include/ptts.h: ptts_resampler; filters and admission rules:
+    `resample.py`).  `rates[0]` is always the codec's native rate - what a row without a rate of its own runs at - followed
+    by `sample_rates`; a row is dealt a rate by its index (`index_of`).  `frame(pcm, out)` turns one codec frame into
+    `out[b, :out_n(rate of b)]`; each row carries 64 input samples from frame to frame, `set_row` zeroes them."""
+
+    def __init__(self, engine: "Engine", batch: int, sample_rates):
+        from . import resample
+
+        self.engine, self.batch = engine, batch
+        self.handle = None
+        self.plans = resample.plans(sample_rates, native=engine.sample_rate, frame_samples=engine.frame_samples)
+        self.rates = [p.rate for p in self.plans]
+        self.out_max = max(p.out_n for p in self.plans)
+        self.row_rate = [0] * batch  # host mirror of the rows' rate indices
+        n = len(self.plans)
+        ints = [(C.c_int32 * n)(*[getattr(p, k) for p in self.plans]) for k in ("up", "down", "taps")]
+        tables = np.concatenate([p.table.reshape(-1) for p in self.plans]).astype(np.float32)
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_resampler_create(engine.handle, batch, *ints, n,
+                                                    tables.ctypes.data_as(C.POINTER(C.c_float)), tables.size, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def index_of(self, rate) -> int:
+        """the rate's index (None: 0, the native rate); ValueError for a rate that is not configured"""
+        if rate is None:
+            return 0
+        if isinstance(rate, bool) or not isinstance(rate, numbers.Integral) or int(rate) not in self.rates:
+            raise ValueError(f"sample rate {rate!r} is not configured (this resampler has {self.rates})")
+        return self.rates.index(int(rate))
+
+    def out_n(self, rate_index: int) -> int:
+        """output samples per frame at `rates[rate_index]`"""
+        return self.plans[rate_index].out_n
+
+    def set_row(self, row: int, rate_index: int, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` at `rates[rate_index]` with a zero history; stream-ordered"""
+        sp = self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
+        _lib.check(self.engine.lib.ptts_resampler_set_row(self.handle, int(row), int(rate_index), sp))
+        self.row_rate[row] = int(rate_index)
+
+    def reset(self, stream: torch.cuda.Stream | None = None):
+        """every row's history back to zero (new utterances); the rows keep their rates"""
+        for b in range(self.batch):
+            self.set_row(b, self.row_rate[b], stream)
+
+    def _check_out(self, out):
+        if out is None or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (self.batch, self.out_max) \
+                or not out.is_contiguous():
+            raise ValueError(f"resampler output: expected a contiguous float32 or int16 [{self.batch}, {self.out_max}] tensor")
+
+    def frame(self, pcm: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """pcm f32[B, frame_samples] on the device -> out (float32 or int16 [B, out_max], device or pinned host)"""
+        e = self.engine
+        if pcm.device != e.device or pcm.dtype != torch.float32 or tuple(pcm.shape) != (self.batch, e.frame_samples) \
+                or not pcm.is_contiguous():
+            raise ValueError(f"resampler input: expected a contiguous float32 [{self.batch}, {e.frame_samples}] tensor on {e.device}")
+        self._check_out(out)
+        if stream is None:
+            e._pre()
+        sp = e._sp if stream is None else C.c_void_p(stream.cuda_stream)
+        _lib.check(e.lib.ptts_resample_frame(self.handle, _ptr(pcm), _ptr(out), int(out.dtype == torch.int16), sp))
+        if stream is None:
+            pcm.record_stream(e.stream)
+            if out.is_cuda:
+                out.record_stream(e.stream)
+            e._post()
+
+    def close(self):
+        if self.handle is not None:
+            self.engine.lib.ptts_resampler_destroy(self.handle)
+            self.handle = None
+
     def __del__(self):
         try:
             self.close()
@@ -299,6 +390,7 @@ class Engine:
         self.D, self.H, self.L = t.d_model, t.num_heads, t.num_layers
         self.ldim = cfg.mimi.quantizer.dimension
         self.frame_samples = cfg.frame_samples
+        self.sample_rate = int(cfg.mimi.sample_rate)
         # embedding table + voice-path parameters stay as torch tensors (gather / prefill inputs)
         self.embed = torch.as_tensor(weights["flow_lm.conditioner.embed.weight"]).to(self.device, torch.float32)
         self.bos_before_voice = None
@@ -458,6 +550,9 @@ class Engine:
 
     def new_mimi_state(self, batch: int) -> MimiState:
         return MimiState(self, batch)
+
+    def new_resampler(self, batch: int, sample_rates) -> Resampler:
+        return Resampler(self, batch, sample_rates)
 
     # ---- FlowLM
     def embed_text(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -830,16 +925,25 @@ class StepPipeline:
       second stream while step t is already running on the first.  No cross-stream event wait sits on the
       critical path (on this stack such waits around graph launches cost ~80 us per step, and the branches
       of a forked graph do not run concurrently).
+
+    `sample_rates` (a list of output rates, `resample.py`; not in "fork" mode): the codec graphs end with the resampler's
+    two launches.  `pcm[p]` are then DEVICE tensors (the resampler reads the frame from device memory) and the samples
+    reach the host through `out[p]`, a pinned [B, out_max] ring, int16 with `pcm_i16`, else float32: `out_of(frame)[b,
+    :rs.out_n(rate index of b)]` is row b's frame; `pcm_of` / `pcm16_of` raise.  Rows get their rates with
+    `rs.set_row(row, rs.index_of(rate), s2)` (codec stream).  With None nothing changes: same buffers, same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None):
+                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None):
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
+        if sample_rates is not None and self.mode == "fork":
+            raise ValueError("sample_rates: not available in the 'fork' mode")
+        self.rs = Resampler(eng, B, sample_rates) if sample_rates is not None else None
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -848,7 +952,13 @@ class StepPipeline:
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host
-        self.pcm = [torch.zeros(B, eng.frame_samples).pin_memory() for _ in range(nb)]
+        if self.rs is None:
+            self.pcm = [torch.zeros(B, eng.frame_samples).pin_memory() for _ in range(nb)]
+            self.out = None
+        else:
+            self.pcm = [torch.zeros(B, eng.frame_samples, device=dev) for _ in range(nb)]
+            self.out = [torch.zeros(B, self.rs.out_max, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
+                        for _ in range(nb)]
         self.ev = [torch.cuda.Event() for _ in range(nb)]    # codec frame (f % nb) complete -> pcm_of(f) valid
         self.ev_lm = [torch.cuda.Event() for _ in range(nb)]  # FlowLM step (t % nb) complete -> flag valid
         self.s1 = lm_stream or eng.stream  # FlowLM stream (several pipelines of one engine may use their own)
@@ -860,12 +970,18 @@ class StepPipeline:
         self.g_first = [eng.capture_lm_step(lm_state, noise, lsd_steps, eos_threshold, self.lat[p], self.logit[p],
                                             self.flag[p]) for p in range(nb)]
         # optional 16-bit PCM beside the fp32 one (the WAV sample format, data/audio.py:79), also pinned
-        self.pcm16 = [torch.zeros(B, eng.frame_samples, dtype=torch.int16).pin_memory() for _ in range(nb)] if pcm_i16 else None
+        self.pcm16 = [torch.zeros(B, eng.frame_samples, dtype=torch.int16).pin_memory() for _ in range(nb)] \
+            if pcm_i16 and self.rs is None else None
         self.g_last = []
         for p in range(nb):
-            mimi_state.set_pcm_i16(self.pcm16[p] if pcm_i16 else None)
+            if self.rs is not None:
+                mimi_state.set_resampler(self.rs, self.out[p])  # the 16-bit conversion happens behind the resampler
+            else:
+                mimi_state.set_pcm_i16(self.pcm16[p] if pcm_i16 else None)
             self.g_last.append(eng.capture_mimi(mimi_state, self.lat[p], self.pcm[p]))
         mimi_state.set_pcm_i16(None)
+        if self.rs is not None:
+            mimi_state.set_resampler(None)
         self.g_both = []
         if self.mode == "fork":
             for p in range(nb):
@@ -886,6 +1002,8 @@ class StepPipeline:
             # zero carries on the CODEC stream: ordered behind the frames already queued there and ahead of the next
             # utterance's first frame, off the FlowLM stream's critical path (clone + prefill + first step)
             self.ms.reset(self.s2)
+            if self.rs is not None:
+                self.rs.reset(self.s2)
         else:
             self.ms.reset()
         self.t = 0
@@ -969,13 +1087,23 @@ class StepPipeline:
 
     def pcm_of(self, frame: int) -> torch.Tensor:
         """host tensor [B, frame_samples] of `frame` (valid after `done_event(frame).synchronize()`)"""
+        if self.rs is not None:
+            raise RuntimeError("this pipeline resamples its output: read out_of(frame)")
         return self.pcm[frame % self.nb]
+
+    def out_of(self, frame: int) -> torch.Tensor:
+        """with `sample_rates`: host tensor [B, out_max] of `frame`, row b's samples in its first `rs.out_n(..)` entries"""
+        if self.rs is None:
+            raise RuntimeError("this pipeline has no sample_rates: read pcm_of(frame)")
+        return self.out[frame % self.nb]
 
     def done_event(self, frame: int):
         """event that fires when the codec decode of `frame` (PCM in `pcm_of(frame)`) is complete"""
         return self.ev[frame % self.nb]
 
     def pcm16_of(self, frame: int) -> torch.Tensor:
+        if self.rs is not None:
+            raise RuntimeError("this pipeline resamples its output: read out_of(frame)")
         return self.pcm16[frame % self.nb]
 
     def sync(self):
@@ -987,3 +1115,5 @@ class StepPipeline:
         self.sync()
         for g in self.g_first + self.g_last + self.g_both:
             self.eng.graph_destroy(g)
+        if self.rs is not None:
+            self.rs.close()

@@ -5,9 +5,11 @@
     python -m pocket_tts_amd serve --config cfg.yaml --voices-dir voices/ --default-voice alba
     python -m pocket_tts_amd export-voice prompt.wav voice.safetensors --config cfg.yaml
 
-`generate` writes 24 kHz mono 16-bit WAV followed by 200 ms of silence (reference data/audio.py:69-72,99-107).
+`generate` writes 24 kHz mono 16-bit WAV followed by 200 ms of silence (reference data/audio.py:69-72,99-107);
+`--sample-rate 8000|16000|44100|48000|...` resamples it on the GPU (resample.py).
 `serve` runs the HTTP server of `server.py` (`GET /health`, `POST /tts` streaming the same WAV bytes) on a continuous
-batcher, with per-request temperature, noise clamp, EOS threshold and seed.  `export-voice` encodes an audio prompt (first 30 s)
+batcher, with per-request temperature, noise clamp, EOS threshold and seed, and with `--sample-rates 8000,16000,48000` a
+per-request `sample_rate`.  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -66,6 +68,17 @@ def write_wav_stream(path, chunks, sample_rate: int) -> int:
     return n
 
 
+def parse_rate_list(text: str) -> list:
+    """"8000,16000,48000" -> [8000, 16000, 48000] (the `serve --sample-rates` value)"""
+    try:
+        rates = [int(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected integers separated by commas, got {text!r}") from None
+    if not rates:
+        raise argparse.ArgumentTypeError("expected at least one rate")
+    return rates
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="pocket-tts")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -82,6 +95,8 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--frames-after-eos", type=int, default=None)
     g.add_argument("--seed", type=int, default=None,
                    help="Seed of the noise in [0, 2**63): the same seed, text and settings give the same audio again")
+    g.add_argument("--sample-rate", type=int, default=None,
+                   help="Output sample rate (e.g. 8000, 16000, 22050, 44100, 48000; default: the codec's 24000), resampled on the GPU")
     g.add_argument("--output-path", default="./tts_output.wav")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
@@ -102,6 +117,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--max-lsd-decode-steps", type=int, default=None,
                    help="Largest lsd_decode_steps a request may ask for (default: --lsd-decode-steps).  A step takes as "
                         "long as its slowest rows: one request at a high count slows every request in the batch")
+    s.add_argument("--sample-rates", type=parse_rate_list, default=None, metavar="R1,R2,...",
+                   help="Output sample rates a request may choose with the form field sample_rate, e.g. 8000,16000,48000 "
+                        "(the codec's own rate is always available)")
     s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
     s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
     s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
@@ -133,7 +151,8 @@ def serve_app(args) -> int:
                                 device=args.device)
     # the model's noise clamp reaches every request as a per-request setting (server.py)
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
-                     default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps)
+                     default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
+                     sample_rates=args.sample_rates)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -167,11 +186,20 @@ def cli_app(argv=None) -> int:
                                 lsd_decode_steps=args.lsd_decode_steps, noise_clamp=args.noise_clamp,
                                 eos_threshold=args.eos_threshold, quantize=args.quantize, codec_bf16=args.codec_bf16,
                                 device=args.device)
+    if args.sample_rate is not None:
+        # generate_audio_stream is a generator and would refuse the rate only once write_wav_stream has opened the file
+        from . import resample
+
+        try:
+            resample.plan(args.sample_rate, int(model.sample_rate), model.engine.frame_samples)
+        except ValueError as e:
+            logger.error("--sample-rate: %s", e)
+            return 1
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
     chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                         seed=args.seed)
-    write_wav_stream(args.output_path, chunks, model.sample_rate)
+                                         seed=args.seed, sample_rate=args.sample_rate)
+    write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)
     return 0

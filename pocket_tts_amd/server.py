@@ -3,8 +3,8 @@ pocket_tts/main.py:121-214) with every request decoded in one shared batch.
 
 `POST /tts` takes the reference's form fields - `text`, `voice_url` (here: the name of a voice state in the voices
 directory) or the file `voice_wav` - plus this server's optional per-request settings `temperature`, `noise_clamp`,
-`eos_threshold`, `frames_after_eos`, `lsd_decode_steps` and `seed` (the same seed, text and settings give the same noise
-again).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+`eos_threshold`, `frames_after_eos`, `lsd_decode_steps`, `seed` (the same seed, text and settings give the same noise
+again) and `sample_rate` (one of the rates the server was started with, or the codec's own).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
@@ -39,6 +39,7 @@ INDEX_HTML = """<!doctype html>
 <p>Voice name <input name="voice_url"> or WAV prompt <input type="file" name="voice_wav" accept=".wav"></p>
 <p>LSD decode steps <input name="lsd_decode_steps" size="3"> (empty: the server's default)</p>
 <p>Seed <input name="seed" size="20"> (empty: a take that cannot be repeated)</p>
+<p>Sample rate <input name="sample_rate" size="6"> Hz (empty: the model's own rate)</p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -152,15 +153,39 @@ def parse_seed(fields: dict) -> int | None:
     return v
 
 
+def parse_sample_rate(fields: dict, native: int, sample_rates) -> int | None:
+    """the optional `sample_rate` field: the native rate or one of the configured `sample_rates` (absent or empty: None)"""
+    raw = fields.get("sample_rate")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        v = int(raw.strip(), 10)
+    except ValueError:
+        raise FormError(f"sample_rate must be an integer, got {raw!r}") from None
+    allowed = [int(native), *[int(r) for r in sample_rates or () if int(r) != int(native)]]
+    if v not in allowed:
+        raise FormError(f"sample_rate {v} is not configured (this server offers {allowed})")
+    return v
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
-               batcher_factory=None, max_lsd_decode_steps: int | None = None):
+               batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
     noise clamp.  A request's `lsd_decode_steps` may be 1 .. `max_lsd_decode_steps` (default: the model's
-    `lsd_decode_steps`; a larger maximum gives the batcher per-row LSD schedules).  `batcher_factory(model, slots,
+    `lsd_decode_steps`; a larger maximum gives the batcher per-row LSD schedules).  `sample_rates`: the output rates a
+    request may choose with `sample_rate` besides the model's own (None: only that one, and the batcher's graphs are those
+    of before); the WAV header and the trailing silence follow the request's rate.  `batcher_factory(model, slots,
     capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
+
+    if sample_rates is not None:
+        from . import resample
+
+        sample_rates = [int(r) for r in sample_rates]
+        for r in sample_rates:  # ValueError at start-up, not at the first request
+            resample.plan(r, int(model.sample_rate))
 
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
@@ -171,7 +196,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         reserve = max_lsd if max_lsd != own_lsd else None
 
         def batcher_factory(model, slots, capacity):
-            return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve)
+            if sample_rates is None:
+                return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve)
+            return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
+                                     sample_rates=sample_rates)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -260,6 +288,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             seed = parse_seed(fields)
             if seed is not None:
                 settings["seed"] = seed
+            rate = parse_sample_rate(fields, model.sample_rate, sample_rates)
+            if rate is not None and rate != int(model.sample_rate):
+                settings["sample_rate"] = rate
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:
@@ -287,7 +318,7 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             for chunks in req.iter_batches():
                 yield chunks[0] if len(chunks) == 1 else torch.cat(chunks)
 
-        return StreamingResponse(wav_stream_bytes(frames(), model.sample_rate), media_type="audio/wav",
+        return StreamingResponse(wav_stream_bytes(frames(), rate or model.sample_rate), media_type="audio/wav",
                                  headers={"Content-Disposition": "attachment; filename=generated_speech.wav"})
 
     return app

@@ -191,16 +191,22 @@ class TTSModel:
     # ---- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                       frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63), not in the reference): see `generate_audio_stream`."""
+                       frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
+                       seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63)) and `sample_rate` (not in the reference): see `generate_audio_stream`."""
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
-                                                 seed=seed))
+                                                 seed=seed, sample_rate=sample_rate))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                              frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None):
+                              frames_after_eos: int | None = None, copy_state: bool = True,
+                              sample_rate: int | None = None, seed: int | None = None):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
+
+        `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
+        resampled on the GPU behind the codec (streaming polyphase FIR, `resample.py`) and each chunk holds
+        `frame_samples * sample_rate / native` samples.  None or the native rate: the codec's own samples, as before.
 
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
@@ -209,6 +215,13 @@ class TTSModel:
         from torch's global CPU generator, as in the reference."""
         if seed is not None:
             seed = check_seed(seed)
+        if sample_rate is not None:
+            from . import resample
+
+            native = int(self.config.mimi.sample_rate)
+            sample_rate = resample.plan(sample_rate, native, self.engine.frame_samples).rate  # ValueError names the rule
+            if sample_rate == native:
+                sample_rate = None
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
@@ -218,7 +231,7 @@ class TTSModel:
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
-                                                              None if seed is None else chunk_seed(seed, i))
+                                                              None if seed is None else chunk_seed(seed, i), sample_rate)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -376,6 +389,18 @@ class TTSModel:
             c["st"].close()
             c["ms"].close()
 
+    RATE_CONTEXTS = 2  # cached contexts of `generate_audio(sample_rate=...)`: a caller that cycles through rates holds no more
+
+    def _drop_rate_contexts(self, keep: int = 0):
+        """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
+        recently used are released; a context in use is not in the cache"""
+        keys = [k for k in self._ctx_cache if len(k) >= 2 and k[-2] == "rate"]
+        for k in keys[: max(0, len(keys) - keep)]:
+            c = self._ctx_cache.pop(k)
+            c["pipe"].close()
+            c["st"].close()
+            c["ms"].close()
+
     class _Voice:
         """one device-resident voice: engine-layout KV of a voice-state dict + what identifies the dict's contents"""
 
@@ -444,7 +469,7 @@ class TTSModel:
             torch.nn.init.trunc_normal_(out, mean=0.0, std=std, a=-self.noise_clamp, b=self.noise_clamp)
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
-                                          row_seed: int | None = None):
+                                          row_seed: int | None = None, sample_rate: int | None = None):
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -458,6 +483,8 @@ class TTSModel:
         # states, scratch and captured graphs are reused across chunks and calls (capacity rounded up)
         cap = -(-(t_voice + Tt + max_gen_len) // 256) * 256
         key = (cap, self.lsd_decode_steps, float(self.eos_threshold), "seeded" if seeded else use_noise)
+        if sample_rate is not None:  # a context of its own: its codec graphs end with the resampler
+            key = (*key, "rate", sample_rate)
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -465,7 +492,13 @@ class TTSModel:
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
-            pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync")
+            if sample_rate is None:
+                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync")
+            else:
+                self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
+                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
+                                    sample_rates=[sample_rate])
+                pipe.rs.set_row(0, pipe.rs.index_of(sample_rate), pipe.s2)  # restart() below zeroes its history per chunk
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
         noise_host = ctx["noise_host"]
@@ -491,8 +524,12 @@ class TTSModel:
             emitted = 0    # frames handed to the codec
             yielded = 0    # frames handed to the caller
 
+            out_n = None if sample_rate is None else pipe.rs.out_n(pipe.rs.index_of(sample_rate))
+
             def pop(frame):
                 pipe.done_event(frame).synchronize()
+                if out_n is not None:
+                    return pipe.out_of(frame)[0, :out_n].clone()
                 return pipe.pcm_of(frame)[0].clone()
 
             for step in range(max_gen_len):
@@ -539,7 +576,7 @@ class TTSModel:
             self._ctx_cache[key] = ctx
         if st.error():  # a cooperative kernel gave up waiting for a peer (GPU oversubscribed beyond the library's contract)
             raise RuntimeError("libptts: a cooperative FlowLM kernel timed out; the audio of this chunk is invalid")
-        dur_ms = int(total * 1000 / self.config.mimi.sample_rate)
+        dur_ms = int(total * 1000 / (sample_rate or self.config.mimi.sample_rate))
         gen_ms = max(1, int((time.monotonic() - t_start) * 1000))
         logger.info("Generated: %d ms of audio in %d ms so %.2fx faster than real-time", dur_ms, gen_ms, dur_ms / gen_ms)
 
