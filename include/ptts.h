@@ -38,6 +38,7 @@ typedef struct ptts_lm_state ptts_lm_state;     /* FlowLM KV caches of B sequenc
 typedef struct ptts_mimi_state ptts_mimi_state; /* Mimi streaming state of B sequences   */
 typedef struct ptts_graph ptts_graph;           /* a captured hipGraph of one step       */
 typedef struct ptts_resampler ptts_resampler;   /* output sample rates of B sequences    */
+typedef struct ptts_stretcher ptts_stretcher;   /* speaking rates of B sequences         */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
 typedef struct ptts_config {
@@ -266,6 +267,42 @@ int ptts_resample_frame(ptts_resampler *rs, const float *d_pcm_in, void *out, in
  * it off: decodes and captures are then launch for launch those of a state that never had one.  -1 when the resampler's
  * batch or frame length is not the state's. */
 int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, void *out, int32_t is_i16);
+/* ---- Speaking rate (no reference counterpart).  A stretcher holds, for B sequences, a table of WSOLA plans, each row's
+ * plan and each row's streaming state; it turns one frame f32[B, in_max] of the previous output stage (the codec's PCM or the
+ * resampler's output; row b's n_in samples at the front of its line) into out[B, out_max] with row b's n_out samples at the
+ * front of its line (the rest of the line is not written).  Plan i is h_plans[5 i ..] = (n_in, Ha, Hs, D, L): window W = 2 Hs,
+ * K = n_in / Ha hops per frame, n_out = K Hs.  Hop k = 0, 1, .. of a row's input stream x (zero before its start and after
+ * the row is set to drain):
+ *   p_k = k Ha - L + delta_k; delta_0 = 0, else delta_k in [-D, D] maximises the fp32 dot product
+ *         sum_{i < Hs} x[p_{k-1} + Hs + i] x[k Ha - L + delta + i]  (equal maxima: the smallest |delta|, then the negative one)
+ *   y[k Hs + n] += w[n] x[p_k + n], n < W, with the plan's window w (its 2 Hs floats in h_windows, the plans' windows one
+ *         after the other, n_window_floats in all); y[k Hs .. (k + 1) Hs) is then final and emitted
+ * Ha == Hs is the identity plan: an exact copy of the first n_in samples, no lag, no state.  A plan is refused (-1) unless
+ * n_in % Ha == 0, 1/2 <= Ha / Hs <= 2, L % Ha == 0, L >= D + 3 Hs (no read past the frame's end), L + D + Ha <= 8192 (the
+ * samples a row carries), L + D + Ha + n_in <= 12288 (the window staged in LDS), Hs <= 2048 and 2 D + 1 <= 1024: with these
+ * every index the kernel forms is in bounds by construction (csrc/ptts_stretch.h).  Plan rule: pocket_tts_amd/stretch.py.
+ * in_max and out_max are the largest n_in and n_out of the plans, K_max the largest K of those that are not the identity
+ * (at least 1).  Every row starts on plan 0 with a zero state. */
+int ptts_stretcher_create(ptts_engine *e, int32_t batch, const int32_t *h_plans, int32_t n_plans, const float *h_windows,
+                          int64_t n_window_floats, ptts_stretcher **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_stretcher(state, NULL, ..) on its states */
+void ptts_stretcher_destroy(ptts_stretcher *ts);
+/* a new utterance joins `row`: its plan from now on; carried samples, carry, delta and the drain flag are zeroed.
+ * Stream-ordered on `stream`; captured graphs pick it up (the kernel reads all of it from device memory).  -1 for a row or
+ * a plan index out of range; nothing is enqueued. */
+int ptts_stretcher_set_row(ptts_stretcher *ts, int32_t row, int32_t plan_index, void *stream);
+/* from now on (stream-ordered) the row's incoming frames count as zeros (on != 0), until set_row or on == 0 */
+int ptts_stretcher_set_row_drain(ptts_stretcher *ts, int32_t row, int32_t on, void *stream);
+/* One frame, one launch: d_in f32[B, in_max] (DEVICE memory) -> out [B, out_max], f32 or (is_i16) int16 converted as
+ * ptts_mimi_set_pcm_i16 converts, device or pinned host; then the rows' states advance.  d_delta (i32 [B, K_max], device, or
+ * NULL) receives the delta_k of the frame's hops of every row that is not on an identity plan: the test tap. */
+int ptts_stretch_frame(ptts_stretcher *ts, const float *d_in, void *out, int32_t is_i16, int32_t *d_delta, void *stream);
+/* While a stretcher is set, ptts_mimi_decode and the graph captures append the launch of ptts_stretch_frame.  d_in == NULL:
+ * behind the codec's last kernel, reading d_pcm (which must then be device memory; NULL = the state's own buffer; in_max must
+ * be frame_samples).  Otherwise behind the resampler set on the state, which then writes f32 into the device buffer d_in
+ * [B, in_max] instead of its own output (in_max must be the resampler's out_max).  NULL stretcher: off, decodes and captures
+ * are launch for launch those of a state that never had one. */
+int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);

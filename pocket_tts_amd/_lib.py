@@ -123,6 +123,13 @@ PROTOTYPES = {
     "ptts_resampler_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ptts_resample_frame": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ptts_mimi_set_resampler": (C.c_int, [_P, _P, _P, C.c_int32]),
+    "ptts_stretcher_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_float), C.c_int64,
+                                        C.POINTER(_P)]),
+    "ptts_stretcher_destroy": (None, [_P]),
+    "ptts_stretcher_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_stretcher_set_row_drain": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_stretch_frame": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    "ptts_mimi_set_stretcher": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "ptts_tune": (C.c_int, [_P, C.c_int32, _P]),
     "ptts_tune_streams": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ptts_streams_overlap": (C.c_int, [_P, _P, _P]),
@@ -155,12 +162,16 @@ PROTOTYPES = {
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile csrc/*.hip for gfx950 in-tree (hipcc cross-compiles without a GPU).  Every .hip file is one translation
-    unit (ptts.hip = host side: engine, states, step orchestration, graphs, C ABI; ptts_dispatch.hip = the GEMM / attention
-    dispatchers and the tuner, the only unit that instantiates the round-1/2 kernel templates; newer kernel families live in
-    their own files behind plain C++ launcher functions declared in ptts_ext.h, ptts_resample.hip = the output-rate
-    resampler with its own part of the C ABI among them; ptts_debug.hip = the C ABI's test hooks;
-    these three see each other through ptts_host.h), compiled in parallel to csrc/.obj/*.o and linked into libptts.so; a
-    unit is recompiled when it or any header is newer than its object."""
+    unit:
+      * ptts.hip = host side: engine, states, step orchestration, graphs, C ABI;
+      * ptts_dispatch.hip = the GEMM / attention dispatchers and the tuner, the only unit that instantiates the round-1/2
+        kernel templates;
+      * ptts_debug.hip = the C ABI's test hooks;
+      * ptts_resample.hip = the output-rate resampler and ptts_stretch.hip = the speaking-rate time-stretch, each with its
+        own part of the C ABI;
+      * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
+    The first five see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
+    libptts.so; a unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = sorted(SRC.parent.glob("*.hip"))

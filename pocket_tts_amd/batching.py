@@ -24,6 +24,12 @@ on the step at which it joined or on the other requests, and equals what `TTSMod
 A batcher built with `sample_rates` lets a request choose its output `sample_rate`: the codec graphs end with the
 streaming polyphase resampler (`resample.py`, `engine.Resampler`), each slot's row runs at its request's rate, and a
 request's chunks hold `frame_samples * rate / native` samples each.  `Request.sample_rate` tells the consumer the rate.
+
+A batcher built with `speeds` lets a request choose its speaking rate `speed` among them: the codec graphs end with the
+streaming WSOLA time-stretch (`stretch.py`, `engine.Stretcher`), behind the resampler if there is one.  A stretched
+request of F frames delivers exactly F * n_out samples: the scheduler drops the row's pre-roll, sets the row to drain
+before the first codec frame past the request's last one is queued, and holds the slot for the plan's drain frames.  To
+know that frame in time it reads the EOS flags of a stretched row no later than `frames_after_eos` steps behind.
 """
 
 from __future__ import annotations
@@ -125,11 +131,12 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "rate")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "rate", "plan")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, rate=0):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, rate=0, plan=None):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
         self.rate = rate       # index of the request's sample rate in the pipeline's resampler (0: native)
+        self.plan = plan       # index of the request's (rate, speed) plan in the pipeline's stretcher (None: no stretcher)
         self.seed = seed       # the chunk's row seed (engine.chunk_seed of the request's seed), or None: the state's stream
         self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
         self.lsd = lsd         # the request's lsd_decode_steps, or None: the model's
@@ -138,12 +145,16 @@ class _Job:
 
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
-                 max_lsd_decode_steps: int | None = None, sample_rates=None):
+                 max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
         output `sample_rate` among them and the native rate (`submit`).  None: every request gets the codec's rate, with
         the same graphs and buffers as before.
+
+        `speeds` (a list of speaking rates `stretch.plan` admits at one of the batcher's rates at least, e.g. [0.8, 1.25,
+        1.5]) lets each request choose its `speed` among them and 1.0 (`submit`).  None: nobody is stretched, with the
+        same graphs and buffers as before.
 
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
@@ -163,6 +174,11 @@ class ContinuousBatcher:
         self.model, self.eng, self.B = model, model.engine, slots
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
+        if speeds is not None:  # a speed that no rate admits is refused before anything is allocated
+            from . import resample, stretch
+
+            stretch.table([(p.rate, p.out_n) for p in resample.plans(sample_rates or (), eng.sample_rate, eng.frame_samples)],
+                          stretch.normalise_speeds(speeds))
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -176,13 +192,18 @@ class ContinuousBatcher:
             self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
         self.max_lsd = max_lsd_decode_steps
         self.native_rate = int(model.config.mimi.sample_rate)
-        if sample_rates is None:  # the call of before, argument for argument
+        if sample_rates is None and speeds is None:  # the call of before, argument for argument
             self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                      mode="events", pcm_i16=(pcm_format == "i16"))
-        else:
+        elif speeds is None:
             self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                      mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=list(sample_rates))
+        else:
+            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
+                                     mode="events", pcm_i16=(pcm_format == "i16"),
+                                     sample_rates=None if sample_rates is None else list(sample_rates), speeds=list(speeds))
         self.rs = self.pipe.rs
+        self.ts = self.pipe.ts
         self.pipe.restart()
         self.slot: list = [None] * slots                 # running _Job per slot
         # per-slot bookkeeping of the job that owns the slot (arrays: one numpy pass per step instead of a Python loop)
@@ -194,6 +215,11 @@ class ContinuousBatcher:
         self.row_samp = [False] * slots                   # the slot's row carries a sampling override
         self.row_lsd = [False] * slots                    # ... an lsd_decode_steps override
         self.row_seed = [False] * slots                   # ... a seed
+        # stretched rows (`speeds`): output samples the slot's job has produced, whether its row has been set to drain,
+        # and the global frame after which a job that has ended leaves its slot (-1: not ended)
+        self.a_pos = np.zeros(slots, np.int64)
+        self.row_drain = [False] * slots
+        self.a_release = np.full(slots, -1, np.int64)
         # held by the background scheduler around each iteration: other users of the engine (e.g. a voice-prompt encode
         # on a request thread) take it to run between the scheduler's steps (`exclusive`)
         self.engine_lock = threading.RLock()
@@ -214,7 +240,7 @@ class ContinuousBatcher:
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
-               sample_rate: int | None = None, seed: int | None = None) -> Request:
+               sample_rate: int | None = None, speed: float | None = None, seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -225,7 +251,10 @@ class ContinuousBatcher:
         reproducible: the same seed, text and settings draw the same noise in any slot, under any traffic, and in
         `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.  `sample_rate`: the rate of
         this request's audio, one of the batcher's `sample_rates` or the native rate (None: native); anything else raises
-        ValueError, as does any rate but the native one on a batcher built without `sample_rates`."""
+        ValueError, as does any rate but the native one on a batcher built without `sample_rates`.  `speed`: the
+        request's speaking rate, one of the batcher's `speeds` or 1.0 (None: 1.0); a speed that is not configured, or
+        that the plan rule refuses at the request's rate, raises ValueError, as does any speed but 1.0 on a batcher built
+        without `speeds`.  A stretched request needs frames_after_eos >= 1."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -259,6 +288,12 @@ class ContinuousBatcher:
             elif isinstance(sample_rate, bool) or sample_rate != self.native_rate:
                 raise ValueError(f"sample rate {sample_rate!r}: this batcher writes {self.native_rate} Hz only (build it "
                                  "with sample_rates for per-request rates)")
+        plan = None
+        if self.ts is not None:
+            plan = self.pipe.speed_plan(rate, speed)
+        elif speed is not None and (isinstance(speed, bool) or not isinstance(speed, numbers.Real) or speed != 1.0):
+            raise ValueError(f"speed {speed!r}: this batcher speaks at 1.0 only (build it with speeds for per-request speeds)")
+        stretched = plan is not None and not self.ts.plans[plan].identity
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -284,13 +319,16 @@ class ContinuousBatcher:
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
             fae = frames_after_eos if frames_after_eos is not None else (
                 m.model_recommended_frames_after_eos if m.model_recommended_frames_after_eos is not None else guess + 2)
+            if stretched and fae < 1:
+                raise ValueError("a request with a speed needs frames_after_eos >= 1: the row is set to drain before the "
+                                 "frame that follows its last one is queued")
             ids = m.tokenizer.encode(chunk)
             gen = estimate_max_gen_len(len(ids), m.config.mimi.frame_rate)
             need = t_voice + len(ids) + gen + self.pipe.nb + 2  # a row runs up to nb steps past its end before it is parked
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp, lsd, None if seed is None else chunk_seed(seed, i), rate))
+                             samp, lsd, None if seed is None else chunk_seed(seed, i), rate, plan))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -387,6 +425,9 @@ class ContinuousBatcher:
             self.ms.reset_row(b, self.pipe.s2)
             if self.rs is not None:  # the row's output rate and a zero filter history, on the same stream
                 self.rs.set_row(b, job.rate, self.pipe.s2)
+            if self.ts is not None:  # the row's plan and a zero stretch state, not draining
+                self.ts.set_row(b, job.plan, self.pipe.s2)
+                self.a_pos[b], self.row_drain[b], self.a_release[b] = 0, False, -1
             job.start = self.g
             self.slot[b] = job
             self.a_start[b], self.a_gen[b], self.a_fae[b] = self.g, job.gen, job.fae
@@ -411,27 +452,88 @@ class ContinuousBatcher:
         pipe.done_event(frame).synchronize()  # codec frame done => the FlowLM step's flags are on the host too
         q = frame % pipe.nb
         rows = (self.a_emit < 0) & (self.a_start <= frame)
-        if not rows.any():
+        held = np.nonzero(self.a_release >= 0)[0] if self.ts is not None else ()
+        if not rows.any() and not len(held):
             return
         eos_bookkeeping_rows(frame - self.a_start, self.a_gen, self.a_fae, self.a_eos, self.a_emit,
                              pipe.flag[q].numpy() != 0, rows)
         # one copy of the frame out of the pinned ring (numpy memcpy: no intra-op thread team), rows are views of it
-        if self.rs is not None:
+        if pipe.out is not None:
             ring = pipe.out_of(frame)
         else:
             ring = pipe.pcm16_of(frame) if self.pcm_format == "i16" else pipe.pcm_of(frame)
         pcm = torch.from_numpy(ring.numpy().copy())
+        for b in held:  # jobs that have ended and flush their stretch tail: this is one of their drain frames
+            job = self.slot[b]
+            self._deliver_stretched(b, job, pcm[b])
+            if frame >= self.a_release[b]:
+                self.a_release[b] = -1
+                self.slot[b] = None
+                self._finish(job)
         for b in np.nonzero(rows)[0]:
             job = self.slot[b]
             if self.a_emit[b] < 0:
-                job.req._q.put(pcm[b] if self.rs is None else pcm[b, :self.rs.out_n(job.rate)])
+                if self.ts is not None:
+                    self._deliver_stretched(b, job, pcm[b])
+                else:
+                    job.req._q.put(pcm[b] if self.rs is None else pcm[b, :self.rs.out_n(job.rate)])
                 job.req.frames += 1
                 continue
             if self.a_eos[b] < 0:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
             self.st.set_row_active(int(b), False)
+            drain = self.ts.plans[job.plan].drain_frames if self.ts is not None else 0
+            if drain:
+                # `frame` is the first one past the job's end and, by _drain_due, the first one its row saw as zeros
+                if not self.row_drain[b]:
+                    raise RuntimeError("a stretched row ended before it was set to drain")
+                self._deliver_stretched(b, job, pcm[b])
+                if drain > 1:
+                    self.a_release[b] = frame + drain - 1
+                    continue
             self.slot[b] = None
             self._finish(job)
+
+    def _deliver_stretched(self, b, job, line):
+        """routes the part of a frame of slot `b` that belongs to its job: everything behind the plan's pre-roll, up to
+        frames * n_out samples in all once the job's frame count is known"""
+        p = self.ts.plans[job.plan]
+        pos = int(self.a_pos[b])
+        lo = max(p.preroll - pos, 0)
+        hi = p.n_out if self.a_emit[b] < 0 else min(p.n_out, p.preroll + int(self.a_emit[b]) * p.n_out - pos)
+        if hi > lo:
+            job.req._q.put(line[lo:hi])
+        self.a_pos[b] = pos + p.n_out
+
+    def _drain_due(self):
+        """Before codec frame g is queued: every stretched row whose job ends before that frame is set to drain on the
+        codec stream, so that the frames past the job's end count as zeros.  A job's end is known `frames_after_eos`
+        frames ahead once the EOS flags up to then have been read; where they have not, this reads them (it waits for
+        the frames concerned), which a row without a speed never needs."""
+        for b in range(self.B):
+            job = self.slot[b]
+            if job is None or self.row_drain[b] or self.ts.plans[job.plan].identity:
+                continue
+            start, gen, fae = int(self.a_start[b]), int(self.a_gen[b]), int(self.a_fae[b])
+            local = self.g - start
+            while True:
+                if self.a_emit[b] >= 0:
+                    end = int(self.a_emit[b])
+                elif self.a_eos[b] >= 0:
+                    end = min(int(self.a_eos[b]) + fae, gen)
+                elif local >= gen:
+                    end = gen
+                elif local < max(self.collected - start, 0) + fae:
+                    end = None  # no EOS in the frames read so far: frame `local` belongs to the job
+                else:
+                    # the flags of local frame `local - fae` decide; collected <= g - fae < g here
+                    self._process(self.collected)
+                    self.collected += 1
+                    continue
+                break
+            if end is not None and local >= end and self.slot[b] is job:
+                self.ts.set_row_drain(b, True, self.pipe.s2)
+                self.row_drain[b] = True
 
     def _finish(self, job):
         req = job.req
@@ -462,6 +564,11 @@ class ContinuousBatcher:
         if all(j is None for j in self.slot):
             self._drain()
             return bool(self.waiting)
+        if self.ts is not None:
+            self._drain_due()
+            if all(j is None for j in self.slot):
+                self._drain()
+                return bool(self.waiting)
         pipe.step()
         self.g += 1
         if self.g % 512 == 0:

@@ -2187,13 +2187,41 @@ extern "C" int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, v
   return 0;
 }
 
-// the codec frame, then the resampler's launches if the state has one
+// Speaking rate: while a stretcher is set, its launch follows the codec's last kernel (d_in == NULL: it reads the frame's fp32
+// PCM as the resampler would) or the resampler, which then writes f32 into the device buffer d_in instead of its own
+// output.  NULL switches it off: decodes and captures are then launch for launch what they were.
+extern "C" int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16) {
+  if (!s) return fail(-1, "null state");
+  if (ts && !out) return fail(-1, "set_stretcher: null output");
+  if (ts && stretch_batch(ts) != s->B) return fail(-1, "set_stretcher: the stretcher's batch is not the state's");
+  if (ts && !d_in && stretch_in_max(ts) != s->rows[3])
+    return fail(-1, "set_stretcher: the stretcher's frame length is not the state's");
+  if (ts && d_in && (!s->rs || resample_out_max(s->rs) != stretch_in_max(ts)))
+    return fail(-1, "set_stretcher: an input buffer needs a resampler on the state whose longest frame is the stretcher's");
+  s->ts = ts;
+  s->ts_in = ts ? d_in : nullptr;
+  s->ts_out = ts ? out : nullptr;
+  s->ts_i16 = ts ? (is_i16 != 0) : 0;
+  return 0;
+}
+
+// the codec frame, then the launches of the output stages the state has
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
-  if (!s->rs) return 0;
-  SITE("resample");
-  const int r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, s->rs_out, s->rs_i16);
-  SITE("");
+  if (!s->rs && !s->ts) return 0;
+  const bool chained = s->ts && s->ts_in;  // resampler -> ts_in -> stretcher
+  if (chained && !s->rs) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
+  int r = 0;
+  if (s->rs) {
+    SITE("resample");
+    r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, chained ? (void *)s->ts_in : s->rs_out, chained ? 0 : s->rs_i16);
+    SITE("");
+  }
+  if (r == 0 && s->ts) {
+    SITE("stretch");
+    r = stretch_enqueue(st, s->ts, chained ? s->ts_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ts_out, s->ts_i16, nullptr);
+    SITE("");
+  }
   return r;
 }
 

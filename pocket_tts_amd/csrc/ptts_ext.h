@@ -38,3 +38,12 @@ struct ptts_resampler;
 int resample_enqueue(hipStream_t st, ptts_resampler *rs, const float *d_pcm, void *out, int is_i16);
 int resample_frame_samples(const ptts_resampler *rs);
 int resample_batch(const ptts_resampler *rs);
+int resample_out_max(const ptts_resampler *rs);
+
+// ---- ptts_stretch.hip: per-request speaking rate (streaming WSOLA time-stretch behind the codec or the resampler) -------
+// the frame's launch on `st`: d_in f32[B][in_max] (device) -> out f32 / i16 [B][out_max] (device or pinned host); d_delta
+// (i32 [B][k_max], or null) receives the hops' deltas.  Returns 0 or a negative error code (message recorded).
+struct ptts_stretcher;
+int stretch_enqueue(hipStream_t st, ptts_stretcher *ts, const float *d_in, void *out, int is_i16, int *d_delta);
+int stretch_batch(const ptts_stretcher *ts);
+int stretch_in_max(const ptts_stretcher *ts);

@@ -257,6 +257,12 @@ struct ptts_mimi_state {
   ptts_resampler *rs = nullptr;
   void *rs_out = nullptr;
   int rs_i16 = 0;
+  // speaking rate (ptts_mimi_set_stretcher): the stretch launch follows the codec's last kernel (ts_in == nullptr) or the
+  // resampler, which then writes f32 into ts_in
+  ptts_stretcher *ts = nullptr;
+  float *ts_in = nullptr;
+  void *ts_out = nullptr;
+  int ts_i16 = 0;
   // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
   float *pcm_part = nullptr, *pcm_carry = nullptr;
   long pcm_cstride = 0;

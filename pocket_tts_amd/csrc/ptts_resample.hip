@@ -62,6 +62,7 @@ __global__ __launch_bounds__(PTTS_RS_HIST) void resample_set_row_kernel(int *row
 
 int resample_frame_samples(const ptts_resampler *rs) { return rs->fs; }
 int resample_batch(const ptts_resampler *rs) { return rs->B; }
+int resample_out_max(const ptts_resampler *rs) { return rs->out_max; }
 
 int resample_enqueue(hipStream_t st, ptts_resampler *rs, const float *d_pcm, void *out, int is_i16) {
   if (!rs || !d_pcm || !out) return fail(-1, "resample: null argument");

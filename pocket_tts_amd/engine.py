@@ -234,6 +234,107 @@ class MimiState:
         rs._check_out(out)
         _lib.check(self.engine.lib.ptts_mimi_set_resampler(self.handle, rs.handle, _ptr(out), int(out.dtype == torch.int16)))
 
+    def set_stretcher(self, ts: "Stretcher | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `ts` as the last output stage, writing `out`
+        [B, ts.out_max], float32 or int16, device or pinned host (include/ptts.h: ptts_mimi_set_stretcher).  `mid` None:
+        behind the codec's last kernel (the frame's PCM must then be a DEVICE tensor); otherwise behind the resampler set
+        on this state, which then writes float32 into the device tensor `mid` [B, ts.in_max].  None: off."""
+        if ts is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_stretcher(self.handle, None, None, None, 0))
+            return
+        ts._check_out(out)
+        if mid is not None:
+            ts._check_in(mid)
+        _lib.check(self.engine.lib.ptts_mimi_set_stretcher(self.handle, ts.handle, _ptr(mid) if mid is not None else None,
+                                                           _ptr(out), int(out.dtype == torch.int16)))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Stretcher:
+    """Speaking rates of `batch` sequences (include/ptts.h: ptts_stretcher; contract and plan rule: `stretch.py`).
+    `plans` is a list of `stretch.StretchPlan`; a row is dealt a plan by its index (`set_row`) and starts on plan 0.
+    `frame(x, out)` turns one frame x[b, :n_in(plan of b)] into out[b, :n_out(plan of b)]; `set_row_drain` makes a row's
+    incoming frames count as zeros, which flushes its tail."""
+
+    def __init__(self, engine: "Engine", batch: int, plans):
+        self.engine, self.batch = engine, batch
+        self.handle = None
+        self.plans = list(plans)
+        self.in_max = max(p.n_in for p in self.plans)
+        self.out_max = max(p.n_out for p in self.plans)
+        self.k_max = max([p.K for p in self.plans if not p.identity], default=1)
+        self.row_plan = [0] * batch  # host mirror of the rows' plan indices
+        n = len(self.plans)
+        ints = (C.c_int32 * (5 * n))(*[v for p in self.plans for v in p.ints()])
+        windows = np.concatenate([p.window.reshape(-1) for p in self.plans]).astype(np.float32)
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_stretcher_create(engine.handle, batch, ints, n,
+                                                    windows.ctypes.data_as(C.POINTER(C.c_float)), windows.size, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def n_out(self, plan_index: int) -> int:
+        """output samples per frame on `plans[plan_index]`"""
+        return self.plans[plan_index].n_out
+
+    def _sp(self, stream):
+        return self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
+
+    def set_row(self, row: int, plan_index: int, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` with a zero state, not draining; stream-ordered"""
+        _lib.check(self.engine.lib.ptts_stretcher_set_row(self.handle, int(row), int(plan_index), self._sp(stream)))
+        self.row_plan[row] = int(plan_index)
+
+    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
+        """from now on (stream-ordered) the row's incoming frames count as zeros"""
+        _lib.check(self.engine.lib.ptts_stretcher_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
+
+    def reset(self, stream: torch.cuda.Stream | None = None):
+        """every row's state back to zero (new utterances); the rows keep their plans"""
+        for b in range(self.batch):
+            self.set_row(b, self.row_plan[b], stream)
+
+    def _check_out(self, out):
+        if out is None or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (self.batch, self.out_max) \
+                or not out.is_contiguous():
+            raise ValueError(f"stretcher output: expected a contiguous float32 or int16 [{self.batch}, {self.out_max}] tensor")
+
+    def _check_in(self, x):
+        e = self.engine
+        if x is None or x.device != e.device or x.dtype != torch.float32 or tuple(x.shape) != (self.batch, self.in_max) \
+                or not x.is_contiguous():
+            raise ValueError(f"stretcher input: expected a contiguous float32 [{self.batch}, {self.in_max}] tensor on {e.device}")
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, delta: torch.Tensor | None = None,
+              stream: torch.cuda.Stream | None = None):
+        """x f32[B, in_max] on the device -> out (float32 or int16 [B, out_max], device or pinned host); `delta` (int32
+        [B, k_max] on the device) receives the hops' deltas of the rows that are not on an identity plan"""
+        e = self.engine
+        self._check_in(x)
+        self._check_out(out)
+        if delta is not None and (delta.device != e.device or delta.dtype != torch.int32 or not delta.is_contiguous()
+                                  or tuple(delta.shape) != (self.batch, self.k_max)):
+            raise ValueError(f"stretcher deltas: expected a contiguous int32 [{self.batch}, {self.k_max}] tensor on {e.device}")
+        if stream is None:
+            e._pre()
+        _lib.check(e.lib.ptts_stretch_frame(self.handle, _ptr(x), _ptr(out), int(out.dtype == torch.int16),
+                                            _ptr(delta) if delta is not None else None, self._sp(stream)))
+        if stream is None:
+            for t in (x, out, delta):
+                if t is not None and t.is_cuda:
+                    t.record_stream(e.stream)
+            e._post()
+
+    def close(self):
+        if self.handle is not None:
+            self.engine.lib.ptts_stretcher_destroy(self.handle)
+            self.handle = None
+
     def __del__(self):
         try:
             self.close()
@@ -553,6 +654,9 @@ class Engine:
 
     def new_resampler(self, batch: int, sample_rates) -> Resampler:
         return Resampler(self, batch, sample_rates)
+
+    def new_stretcher(self, batch: int, plans) -> Stretcher:
+        return Stretcher(self, batch, plans)
 
     # ---- FlowLM
     def embed_text(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -931,19 +1035,39 @@ class StepPipeline:
     reach the host through `out[p]`, a pinned [B, out_max] ring, int16 with `pcm_i16`, else float32: `out_of(frame)[b,
     :rs.out_n(rate index of b)]` is row b's frame; `pcm_of` / `pcm16_of` raise.  Rows get their rates with
     `rs.set_row(row, rs.index_of(rate), s2)` (codec stream).  With None nothing changes: same buffers, same graph nodes.
+
+    `speeds` (a list of speaking rates, `stretch.py`; not in "fork" mode): the codec graphs end with the time-stretch
+    launch, behind the resampler if there is one.  The pipeline holds the plan table of (each rate it serves) x (each
+    speed) in `ts` (`engine.Stretcher`); `speed_plan(rate index, speed)` is the plan index of a pair, ValueError for a
+    speed that is not configured or not admissible at that rate.  The samples reach the host through `out[p]` as above,
+    row b's in its first `ts.n_out(plan index of b)` entries; rows get their plans with `ts.set_row(row, plan, s2)`.  A
+    speed must be admissible at one of the rates at least.  With None nothing changes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None):
+                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None):
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
         if sample_rates is not None and self.mode == "fork":
             raise ValueError("sample_rates: not available in the 'fork' mode")
+        if speeds is not None and self.mode == "fork":
+            raise ValueError("speeds: not available in the 'fork' mode")
+        self.ts, self.speeds, self.ts_index, self.mid = None, None, None, None
+        if speeds is not None:  # the plan table first: a speed no rate admits is refused before anything is allocated
+            from . import resample, stretch
+
+            self.speeds = stretch.normalise_speeds(speeds)
+            rates = [(p.rate, p.out_n) for p in resample.plans(sample_rates, eng.sample_rate, eng.frame_samples)] \
+                if sample_rates is not None else [(eng.sample_rate, eng.frame_samples)]
+            self.ts_rates = [r for r, _ in rates]
+            ts_plans, self.ts_index = stretch.table(rates, self.speeds)
         self.rs = Resampler(eng, B, sample_rates) if sample_rates is not None else None
+        if speeds is not None:
+            self.ts = Stretcher(eng, B, ts_plans)
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -952,13 +1076,18 @@ class StepPipeline:
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host
-        if self.rs is None:
+        if self.rs is None and self.ts is None:
             self.pcm = [torch.zeros(B, eng.frame_samples).pin_memory() for _ in range(nb)]
             self.out = None
         else:
+            last = self.ts if self.ts is not None else self.rs  # the last output stage writes the pinned ring
             self.pcm = [torch.zeros(B, eng.frame_samples, device=dev) for _ in range(nb)]
-            self.out = [torch.zeros(B, self.rs.out_max, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
+            self.out = [torch.zeros(B, last.out_max, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
                         for _ in range(nb)]
+            if self.ts is not None and self.rs is not None:
+                # resampler -> stretcher: one device buffer serves every ring slot (the codec graphs run one after the
+                # other on the codec stream)
+                self.mid = torch.zeros(B, self.rs.out_max, device=dev)
         self.ev = [torch.cuda.Event() for _ in range(nb)]    # codec frame (f % nb) complete -> pcm_of(f) valid
         self.ev_lm = [torch.cuda.Event() for _ in range(nb)]  # FlowLM step (t % nb) complete -> flag valid
         self.s1 = lm_stream or eng.stream  # FlowLM stream (several pipelines of one engine may use their own)
@@ -971,15 +1100,20 @@ class StepPipeline:
                                             self.flag[p]) for p in range(nb)]
         # optional 16-bit PCM beside the fp32 one (the WAV sample format, data/audio.py:79), also pinned
         self.pcm16 = [torch.zeros(B, eng.frame_samples, dtype=torch.int16).pin_memory() for _ in range(nb)] \
-            if pcm_i16 and self.rs is None else None
+            if pcm_i16 and self.out is None else None
         self.g_last = []
         for p in range(nb):
-            if self.rs is not None:
-                mimi_state.set_resampler(self.rs, self.out[p])  # the 16-bit conversion happens behind the resampler
+            if self.out is not None:  # the 16-bit conversion happens behind the last output stage
+                if self.rs is not None:
+                    mimi_state.set_resampler(self.rs, self.out[p] if self.ts is None else self.mid)
+                if self.ts is not None:
+                    mimi_state.set_stretcher(self.ts, self.out[p], self.mid)
             else:
                 mimi_state.set_pcm_i16(self.pcm16[p] if pcm_i16 else None)
             self.g_last.append(eng.capture_mimi(mimi_state, self.lat[p], self.pcm[p]))
         mimi_state.set_pcm_i16(None)
+        if self.ts is not None:
+            mimi_state.set_stretcher(None)
         if self.rs is not None:
             mimi_state.set_resampler(None)
         self.g_both = []
@@ -1004,6 +1138,8 @@ class StepPipeline:
             self.ms.reset(self.s2)
             if self.rs is not None:
                 self.rs.reset(self.s2)
+            if self.ts is not None:
+                self.ts.reset(self.s2)
         else:
             self.ms.reset()
         self.t = 0
@@ -1087,23 +1223,38 @@ class StepPipeline:
 
     def pcm_of(self, frame: int) -> torch.Tensor:
         """host tensor [B, frame_samples] of `frame` (valid after `done_event(frame).synchronize()`)"""
-        if self.rs is not None:
-            raise RuntimeError("this pipeline resamples its output: read out_of(frame)")
+        if self.out is not None:
+            raise RuntimeError("this pipeline resamples or stretches its output: read out_of(frame)")
         return self.pcm[frame % self.nb]
 
     def out_of(self, frame: int) -> torch.Tensor:
-        """with `sample_rates`: host tensor [B, out_max] of `frame`, row b's samples in its first `rs.out_n(..)` entries"""
-        if self.rs is None:
+        """with `sample_rates` or `speeds`: host tensor [B, out_max] of `frame`, row b's samples in its first `rs.out_n(..)`
+        (with `speeds`: `ts.n_out(..)`) entries"""
+        if self.out is None:
             raise RuntimeError("this pipeline has no sample_rates: read pcm_of(frame)")
         return self.out[frame % self.nb]
+
+    def speed_plan(self, rate_index: int, speed) -> int:
+        """index in `ts.plans` of (the rate at `rate_index` of this pipeline, `speed`); None is speed 1.0.  ValueError for
+        a speed that is not configured, or that the plan rule refuses at that rate (the message lists those it admits)"""
+        from . import stretch
+
+        f = 1.0 if speed is None else float(stretch.fraction(speed))
+        if f not in self.speeds:
+            raise ValueError(f"speed {speed!r} is not configured (this pipeline has {self.speeds})")
+        i = self.ts_index[rate_index][self.speeds.index(f)]
+        if i is None:
+            ok = [s for j, s in enumerate(self.speeds) if self.ts_index[rate_index][j] is not None]
+            raise ValueError(f"speed {speed!r} is not admissible at {self.ts_rates[rate_index]} Hz (admissible there: {ok})")
+        return i
 
     def done_event(self, frame: int):
         """event that fires when the codec decode of `frame` (PCM in `pcm_of(frame)`) is complete"""
         return self.ev[frame % self.nb]
 
     def pcm16_of(self, frame: int) -> torch.Tensor:
-        if self.rs is not None:
-            raise RuntimeError("this pipeline resamples its output: read out_of(frame)")
+        if self.out is not None:
+            raise RuntimeError("this pipeline resamples or stretches its output: read out_of(frame)")
         return self.pcm16[frame % self.nb]
 
     def sync(self):
@@ -1115,5 +1266,7 @@ class StepPipeline:
         self.sync()
         for g in self.g_first + self.g_last + self.g_both:
             self.eng.graph_destroy(g)
+        if self.ts is not None:
+            self.ts.close()
         if self.rs is not None:
             self.rs.close()

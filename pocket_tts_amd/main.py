@@ -9,7 +9,8 @@
 `--sample-rate 8000|16000|44100|48000|...` resamples it on the GPU (resample.py).
 `serve` runs the HTTP server of `server.py` (`GET /health`, `POST /tts` streaming the same WAV bytes) on a continuous
 batcher, with per-request temperature, noise clamp, EOS threshold and seed, and with `--sample-rates 8000,16000,48000` a
-per-request `sample_rate`.  `export-voice` encodes an audio prompt (first 30 s)
+per-request `sample_rate`, and with `--speeds 0.8,1.25,1.5` a per-request `speed` (pitch-preserving time-stretch on the GPU,
+stretch.py; `generate --speed 1.25` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -79,6 +80,17 @@ def parse_rate_list(text: str) -> list:
     return rates
 
 
+def parse_speed_list(text: str) -> list:
+    """"0.8,1.25,1.5" -> [0.8, 1.25, 1.5] (the `serve --speeds` value)"""
+    try:
+        speeds = [float(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected numbers separated by commas, got {text!r}") from None
+    if not speeds:
+        raise argparse.ArgumentTypeError("expected at least one speed")
+    return speeds
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="pocket-tts")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -97,6 +109,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Seed of the noise in [0, 2**63): the same seed, text and settings give the same audio again")
     g.add_argument("--sample-rate", type=int, default=None,
                    help="Output sample rate (e.g. 8000, 16000, 22050, 44100, 48000; default: the codec's 24000), resampled on the GPU")
+    g.add_argument("--speed", type=float, default=None,
+                   help="Speaking rate in [0.5, 2] (e.g. 0.8, 1.25, 1.5; default 1.0): time-stretched on the GPU at constant pitch")
     g.add_argument("--output-path", default="./tts_output.wav")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
@@ -120,6 +134,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--sample-rates", type=parse_rate_list, default=None, metavar="R1,R2,...",
                    help="Output sample rates a request may choose with the form field sample_rate, e.g. 8000,16000,48000 "
                         "(the codec's own rate is always available)")
+    s.add_argument("--speeds", type=parse_speed_list, default=None, metavar="S1,S2,...",
+                   help="Speaking rates a request may choose with the form field speed, e.g. 0.8,1.25,1.5 (1.0 is always "
+                        "available); each must give whole hops per frame at one of the server's rates")
     s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
     s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
     s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
@@ -152,7 +169,7 @@ def serve_app(args) -> int:
     # the model's noise clamp reaches every request as a per-request setting (server.py)
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
-                     sample_rates=args.sample_rates)
+                     sample_rates=args.sample_rates, speeds=args.speeds)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -195,10 +212,26 @@ def cli_app(argv=None) -> int:
         except ValueError as e:
             logger.error("--sample-rate: %s", e)
             return 1
+    if args.speed is not None:
+        # likewise: refuse the speed before the output file is opened
+        from . import resample, stretch
+
+        try:
+            native, fs = int(model.sample_rate), model.engine.frame_samples
+            rate = args.sample_rate or native
+            if float(stretch.fraction(args.speed)) != 1.0:
+                stretch.plan(args.speed, rate, resample.plan(rate, native, fs).out_n)
+        except ValueError as e:
+            logger.error("--speed: %s", e)
+            return 1
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
-    chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                         seed=args.seed, sample_rate=args.sample_rate)
+    if args.speed is None:
+        chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
+                                             seed=args.seed, sample_rate=args.sample_rate)
+    else:
+        chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
+                                             seed=args.seed, sample_rate=args.sample_rate, speed=args.speed)
     write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)

@@ -4,7 +4,8 @@ pocket_tts/main.py:121-214) with every request decoded in one shared batch.
 `POST /tts` takes the reference's form fields - `text`, `voice_url` (here: the name of a voice state in the voices
 directory) or the file `voice_wav` - plus this server's optional per-request settings `temperature`, `noise_clamp`,
 `eos_threshold`, `frames_after_eos`, `lsd_decode_steps`, `seed` (the same seed, text and settings give the same noise
-again) and `sample_rate` (one of the rates the server was started with, or the codec's own).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+again), `sample_rate` (one of the rates the server was started with, or the codec's own) and `speed` (one of the speaking
+rates the server was started with that the plan rule of `stretch.py` admits at the request's rate, or 1.0).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
@@ -40,6 +41,7 @@ INDEX_HTML = """<!doctype html>
 <p>LSD decode steps <input name="lsd_decode_steps" size="3"> (empty: the server's default)</p>
 <p>Seed <input name="seed" size="20"> (empty: a take that cannot be repeated)</p>
 <p>Sample rate <input name="sample_rate" size="6"> Hz (empty: the model's own rate)</p>
+<p>Speed <input name="speed" size="5"> (empty: 1.0)</p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -168,16 +170,54 @@ def parse_sample_rate(fields: dict, native: int, sample_rates) -> int | None:
     return v
 
 
+def speed_table(speeds, native: int, sample_rates, frame_samples: int = 1920) -> dict:
+    """{rate: [speeds admissible at that rate, 1.0 first]} for the native rate and every configured rate; ValueError for a
+    speed that is no fraction in range, or that the plan rule admits at none of the rates"""
+    from . import resample, stretch
+
+    rates = [(p.rate, p.out_n) for p in resample.plans(sample_rates or (), int(native), frame_samples)]
+    speeds = stretch.normalise_speeds(speeds)
+    _, index = stretch.table(rates, speeds)
+    return {rate: [s for j, s in enumerate(speeds) if index[i][j] is not None] for i, (rate, _) in enumerate(rates)}
+
+
+def parse_speed(fields: dict, rate: int, table: dict | None) -> float | None:
+    """the optional `speed` field: 1.0 or one of the configured speeds admissible at the request's `rate` (absent or
+    empty: None).  `table`: what `speed_table` returns, or None on a server started without speeds"""
+    raw = fields.get("speed")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        v = float(raw.strip())
+    except ValueError:
+        raise FormError(f"speed must be a number, got {raw!r}") from None
+    if not math.isfinite(v):
+        raise FormError(f"speed must be a finite number, got {raw!r}")
+    if table is None:
+        if v != 1.0:
+            raise FormError(f"speed {v} is not configured (this server speaks at 1.0 only)")
+        return v
+    configured = sorted({s for row in table.values() for s in row})
+    near = [s for s in configured if abs(s - v) <= 1e-9]
+    if not near:
+        raise FormError(f"speed {v} is not configured (this server offers {configured})")
+    if near[0] not in table[int(rate)]:
+        raise FormError(f"speed {v} is not admissible at {int(rate)} Hz (admissible there: {table[int(rate)]})")
+    return near[0]
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
-               batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None):
+               batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
     noise clamp.  A request's `lsd_decode_steps` may be 1 .. `max_lsd_decode_steps` (default: the model's
     `lsd_decode_steps`; a larger maximum gives the batcher per-row LSD schedules).  `sample_rates`: the output rates a
     request may choose with `sample_rate` besides the model's own (None: only that one, and the batcher's graphs are those
-    of before); the WAV header and the trailing silence follow the request's rate.  `batcher_factory(model, slots,
-    capacity)` replaces the batcher (tests)."""
+    of before); the WAV header and the trailing silence follow the request's rate.  `speeds`: the speaking rates a request
+    may choose with `speed` besides 1.0 (None: only 1.0, and the batcher's graphs are those of before); each must be
+    admissible at one of the server's rates at least (ValueError here, not at the first request), and a request whose
+    speed its rate does not admit gets a 400.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
     if sample_rates is not None:
@@ -186,6 +226,11 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         sample_rates = [int(r) for r in sample_rates]
         for r in sample_rates:  # ValueError at start-up, not at the first request
             resample.plan(r, int(model.sample_rate))
+
+    speeds_of = None
+    if speeds is not None:
+        speeds = [float(v) for v in speeds]
+        speeds_of = speed_table(speeds, int(model.sample_rate), sample_rates, model.engine.frame_samples)
 
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
@@ -196,6 +241,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         reserve = max_lsd if max_lsd != own_lsd else None
 
         def batcher_factory(model, slots, capacity):
+            if speeds is not None:
+                return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
+                                         sample_rates=sample_rates, speeds=speeds)
             if sample_rates is None:
                 return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve)
             return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
@@ -291,6 +339,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             rate = parse_sample_rate(fields, model.sample_rate, sample_rates)
             if rate is not None and rate != int(model.sample_rate):
                 settings["sample_rate"] = rate
+            speed = parse_speed(fields, rate or int(model.sample_rate), speeds_of)
+            if speed is not None and speed != 1.0:
+                settings["speed"] = speed
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:

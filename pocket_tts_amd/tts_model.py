@@ -192,21 +192,26 @@ class TTSModel:
     @torch.no_grad()
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                        frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
-                       seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63)) and `sample_rate` (not in the reference): see `generate_audio_stream`."""
+                       speed: float | None = None, seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63)), `sample_rate` and `speed` (not in the reference): see `generate_audio_stream`."""
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
-                                                 seed=seed, sample_rate=sample_rate))
+                                                 seed=seed, sample_rate=sample_rate, speed=speed))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                               frames_after_eos: int | None = None, copy_state: bool = True,
-                              sample_rate: int | None = None, seed: int | None = None):
+                              sample_rate: int | None = None, speed: float | None = None, seed: int | None = None):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
 
         `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
         resampled on the GPU behind the codec (streaming polyphase FIR, `resample.py`) and each chunk holds
         `frame_samples * sample_rate / native` samples.  None or the native rate: the codec's own samples, as before.
+
+        `speed` (not in the reference; a speaking rate `stretch.plan` admits at the output rate, e.g. 0.8, 1.25, 1.5): the
+        audio is time-stretched on the GPU at constant pitch (streaming WSOLA, `stretch.py`) behind the codec, or behind
+        the resampler.  A text chunk of F frames yields exactly F * n_out samples, in chunks of up to n_out = frame samples
+        / speed.  None or 1.0: as before.
 
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
@@ -222,6 +227,17 @@ class TTSModel:
             sample_rate = resample.plan(sample_rate, native, self.engine.frame_samples).rate  # ValueError names the rule
             if sample_rate == native:
                 sample_rate = None
+        if speed is not None:
+            from . import resample, stretch
+
+            native = int(self.config.mimi.sample_rate)
+            n_in = self.engine.frame_samples if sample_rate is None else \
+                resample.plan(sample_rate, native, self.engine.frame_samples).out_n
+            speed = float(stretch.fraction(speed))
+            if speed == 1.0:
+                speed = None
+            else:
+                stretch.plan(speed, sample_rate or native, n_in)  # ValueError names the rule
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
@@ -231,7 +247,7 @@ class TTSModel:
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
-                                                              None if seed is None else chunk_seed(seed, i), sample_rate)
+                                                              None if seed is None else chunk_seed(seed, i), sample_rate, speed)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -394,7 +410,7 @@ class TTSModel:
     def _drop_rate_contexts(self, keep: int = 0):
         """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
         recently used are released; a context in use is not in the cache"""
-        keys = [k for k in self._ctx_cache if len(k) >= 2 and k[-2] == "rate"]
+        keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:]]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
             c["pipe"].close()
@@ -469,7 +485,8 @@ class TTSModel:
             torch.nn.init.trunc_normal_(out, mean=0.0, std=std, a=-self.noise_clamp, b=self.noise_clamp)
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
-                                          row_seed: int | None = None, sample_rate: int | None = None):
+                                          row_seed: int | None = None, sample_rate: int | None = None,
+                                          speed: float | None = None):
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -485,6 +502,8 @@ class TTSModel:
         key = (cap, self.lsd_decode_steps, float(self.eos_threshold), "seeded" if seeded else use_noise)
         if sample_rate is not None:  # a context of its own: its codec graphs end with the resampler
             key = (*key, "rate", sample_rate)
+        if speed is not None:  # likewise: its codec graphs end with the time-stretch
+            key = (*key, "speed", speed)
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -492,8 +511,17 @@ class TTSModel:
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
-            if sample_rate is None:
+            if sample_rate is None and speed is None:
                 pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync")
+            elif speed is not None:
+                self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
+                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
+                                    sample_rates=None if sample_rate is None else [sample_rate], speeds=[speed])
+                r = 0
+                if sample_rate is not None:
+                    r = pipe.rs.index_of(sample_rate)
+                    pipe.rs.set_row(0, r, pipe.s2)
+                pipe.ts.set_row(0, pipe.speed_plan(r, speed), pipe.s2)  # restart() below zeroes its state per chunk
             else:
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
                 pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
@@ -525,9 +553,20 @@ class TTSModel:
             yielded = 0    # frames handed to the caller
 
             out_n = None if sample_rate is None else pipe.rs.out_n(pipe.rs.index_of(sample_rate))
+            plan = None if speed is None else pipe.ts.plans[pipe.ts.row_plan[0]]
+            if plan is not None:
+                out_n = plan.n_out
+
+            pos, end = 0, None  # stretched: output samples read so far; pre-roll + frames * n_out once the frames are known
 
             def pop(frame):
+                nonlocal pos
                 pipe.done_event(frame).synchronize()
+                if plan is not None:  # frames are read in order: drop the pre-roll, stop at `end`
+                    lo = max(plan.preroll - pos, 0)
+                    hi = out_n if end is None else max(min(out_n, end - pos), lo)
+                    pos += out_n
+                    return pipe.out_of(frame)[0, lo:hi].clone()
                 if out_n is not None:
                     return pipe.out_of(frame)[0, :out_n].clone()
                 return pipe.pcm_of(frame)[0].clone()
@@ -539,7 +578,8 @@ class TTSModel:
                     chunk = pop(0)
                     yielded = 1
                     total += chunk.shape[0]
-                    yield chunk
+                    if chunk.shape[0]:  # empty only where a stretched row's pre-roll covers the frame
+                        yield chunk
                 if use_noise and not seeded:
                     self._draw_noise(noise_host)
                     with torch.cuda.stream(eng.stream):
@@ -550,7 +590,8 @@ class TTSModel:
                     chunk = pop(yielded)
                     yielded += 1
                     total += chunk.shape[0]
-                    yield chunk
+                    if chunk.shape[0]:
+                        yield chunk
                 # the EOS decision is a host decision, as in the reference (tts_model.py:761)
                 if bool(pipe.wait_flags(step)[0].item()) and eos_step is None:
                     eos_step = step
@@ -560,11 +601,26 @@ class TTSModel:
                 emitted += 1
             else:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
+            if plan is not None:
+                # stretched: `emitted` frames make emitted * n_out samples.  The row's tail comes out of `drain_frames`
+                # further codec frames, which it reads as zeros.
+                end = plan.preroll + emitted * plan.n_out
+                pipe.ts.set_row_drain(0, True, pipe.s2)
+                for f in range(emitted, emitted + plan.drain_frames):
+                    while yielded < f:  # every earlier frame is read before its ring slot is written again
+                        chunk = pop(yielded)
+                        yielded += 1
+                        total += chunk.shape[0]
+                        if chunk.shape[0]:
+                            yield chunk
+                    pipe.decode_async(f)
+                emitted += plan.drain_frames
             while yielded < emitted:
                 chunk = pop(yielded)
                 yielded += 1
                 total += chunk.shape[0]
-                yield chunk
+                if chunk.shape[0]:
+                    yield chunk
             if not copy_state:
                 # the reference mutates the caller's state in place (tts_model.py:637-638)
                 pipe.sync()
