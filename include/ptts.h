@@ -39,6 +39,7 @@ typedef struct ptts_mimi_state ptts_mimi_state; /* Mimi streaming state of B seq
 typedef struct ptts_graph ptts_graph;           /* a captured hipGraph of one step       */
 typedef struct ptts_resampler ptts_resampler;   /* output sample rates of B sequences    */
 typedef struct ptts_stretcher ptts_stretcher;   /* speaking rates of B sequences         */
+typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences          */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
 typedef struct ptts_config {
@@ -303,6 +304,36 @@ int ptts_stretch_frame(ptts_stretcher *ts, const float *d_in, void *out, int32_t
  * [B, in_max] instead of its own output (in_max must be the resampler's out_max).  NULL stretcher: off, decodes and captures
  * are launch for launch those of a state that never had one. */
 int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16);
+/* ---- Output level (no reference counterpart).  A leveler holds, for B sequences, a table of plans, each row's plan, gain G,
+ * ceiling C and streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front
+ * of its line) into out[B, width] with row b's n samples at the front of its line (the rest of the line is not written).
+ * Plan i is h_plans[4 i ..] = (n, LA, the bits of the float a, the bits of the float k): n samples per frame, look-ahead LA,
+ * release factor a per sample, k = 1 / LA.  With x the row's input stream (zero before its start and after the row is set
+ * to drain) and u = G x:
+ *   r[i] = |u[i]| > C ? C / |u[i]| : 1      m[i] = min r[i - LA .. i]         d[i] = max(1 - m[i], a d[i - 1]), d[-1] = 0
+ *   e[i] = 1 - d[i]                          g[i] = k sum e[i - LA + 1 .. i]   y[i] = g[i] u[i - LA]
+ * (r = e = 1 before the stream's start): |y| <= C up to fp32 rounding, the output lags by LA samples.  A plan is refused
+ * (-1) unless 1 <= LA <= 512, LA <= n <= 8192, 0 <= a < 1 and 0 < k <= 1: with these every index the kernel forms is in
+ * bounds by construction (csrc/ptts_level.h).  Plan rule: pocket_tts_amd/level.py.  width is the largest n of the plans.
+ * Every row starts on bypass: an exact copy of its whole line, no lag, no state. */
+int ptts_leveler_create(ptts_engine *e, int32_t batch, const int32_t *h_plans, int32_t n_plans, ptts_leveler **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_leveler(state, NULL, ..) on its states */
+void ptts_leveler_destroy(ptts_leveler *lv);
+/* a new utterance joins `row`: its plan (-1: bypass), gain G in (0, 16] and ceiling C in (0, 1] from now on; carried samples,
+ * d and the drain flag are zeroed.  Stream-ordered on `stream`; captured graphs pick it up (the kernel reads all of it from
+ * device memory).  -1 for a row, a plan index, a gain or a ceiling out of range; nothing is enqueued. */
+int ptts_leveler_set_row(ptts_leveler *lv, int32_t row, int32_t plan_index, float gain, float ceiling, void *stream);
+/* from now on (stream-ordered) the row's incoming frames count as zeros (on != 0), until set_row or on == 0 */
+int ptts_leveler_set_row_drain(ptts_leveler *lv, int32_t row, int32_t on, void *stream);
+/* One frame, one launch: d_in f32[B, width] (DEVICE memory) -> out [B, width], f32 or (is_i16) int16 converted as
+ * ptts_mimi_set_pcm_i16 converts, device or pinned host; then the rows' states advance. */
+int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_i16, void *stream);
+/* While a leveler is set, ptts_mimi_decode and the graph captures append the launch of ptts_level_frame as their LAST one.
+ * d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer; width must be
+ * frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given the preceding stage
+ * (resampler or stretcher) as its `out`.  NULL leveler: off, decodes and captures are launch for launch those of a state
+ * that never had one. */
+int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float *d_in, void *out, int32_t is_i16);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);

@@ -30,6 +30,12 @@ streaming WSOLA time-stretch (`stretch.py`, `engine.Stretcher`), behind the resa
 request of F frames delivers exactly F * n_out samples: the scheduler drops the row's pre-roll, sets the row to drain
 before the first codec frame past the request's last one is queued, and holds the slot for the plan's drain frames.  To
 know that frame in time it reads the EOS flags of a stretched row no later than `frames_after_eos` steps behind.
+
+A batcher built with `level=True` lets a request choose its output level (`gain_db`, `peak_dbfs`): the codec graphs end with
+the leveler (`level.py`, `engine.Leveler`), the last stage of the chain.  Its look-ahead makes a levelled row lag like a
+stretched one, so both are "rows whose output chain lags": the row's pre-roll is the stretcher's (0 without one) plus the
+look-ahead, it is held for ceil(pre-roll / n) drain frames and delivers the samples [pre-roll, pre-roll + F * n).  A
+levelled row without a stretch drains through the leveler's flag, one with a stretch through the stretcher's.
 """
 
 from __future__ import annotations
@@ -131,10 +137,15 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "rate", "plan")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "rate", "plan", "lvl", "n_out",
+                 "pre")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, rate=0, plan=None):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, rate=0, plan=None, lvl=None,
+                 n_out=0, pre=0):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
+        self.lvl = lvl         # (plan index in the pipeline's leveler, gain_db, peak_dbfs) of the request (None: bypass)
+        self.n_out = n_out     # samples per frame at the end of the row's output chain (pipelines with a lagging stage)
+        self.pre = pre         # pre-roll of the row's output chain: the stretcher's plus the leveler's look-ahead
         self.rate = rate       # index of the request's sample rate in the pipeline's resampler (0: native)
         self.plan = plan       # index of the request's (rate, speed) plan in the pipeline's stretcher (None: no stretcher)
         self.seed = seed       # the chunk's row seed (engine.chunk_seed of the request's seed), or None: the state's stream
@@ -145,7 +156,7 @@ class _Job:
 
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
-                 max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None):
+                 max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
@@ -155,6 +166,10 @@ class ContinuousBatcher:
         `speeds` (a list of speaking rates `stretch.plan` admits at one of the batcher's rates at least, e.g. [0.8, 1.25,
         1.5]) lets each request choose its `speed` among them and 1.0 (`submit`).  None: nobody is stretched, with the
         same graphs and buffers as before.
+
+        `level` = True lets each request choose its output level with `gain_db` and `peak_dbfs` (`submit`): gain plus a
+        look-ahead peak limiter as the last output stage.  False: nobody is levelled, with the same graphs and buffers as
+        before.
 
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
@@ -192,7 +207,12 @@ class ContinuousBatcher:
             self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
         self.max_lsd = max_lsd_decode_steps
         self.native_rate = int(model.config.mimi.sample_rate)
-        if sample_rates is None and speeds is None:  # the call of before, argument for argument
+        if level:
+            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
+                                     mode="events", pcm_i16=(pcm_format == "i16"),
+                                     sample_rates=None if sample_rates is None else list(sample_rates),
+                                     speeds=None if speeds is None else list(speeds), level=True)
+        elif sample_rates is None and speeds is None:  # the call of before, argument for argument
             self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                      mode="events", pcm_i16=(pcm_format == "i16"))
         elif speeds is None:
@@ -204,6 +224,8 @@ class ContinuousBatcher:
                                      sample_rates=None if sample_rates is None else list(sample_rates), speeds=list(speeds))
         self.rs = self.pipe.rs
         self.ts = self.pipe.ts
+        self.lv = self.pipe.lv
+        self.lagging = self.ts is not None or self.lv is not None  # the output chain has a stage that may lag
         self.pipe.restart()
         self.slot: list = [None] * slots                 # running _Job per slot
         # per-slot bookkeeping of the job that owns the slot (arrays: one numpy pass per step instead of a Python loop)
@@ -215,7 +237,8 @@ class ContinuousBatcher:
         self.row_samp = [False] * slots                   # the slot's row carries a sampling override
         self.row_lsd = [False] * slots                    # ... an lsd_decode_steps override
         self.row_seed = [False] * slots                   # ... a seed
-        # stretched rows (`speeds`): output samples the slot's job has produced, whether its row has been set to drain,
+        # rows whose output chain lags (`speeds`, `level`): output samples the slot's job has produced, whether its row has
+        # been set to drain,
         # and the global frame after which a job that has ended leaves its slot (-1: not ended)
         self.a_pos = np.zeros(slots, np.int64)
         self.row_drain = [False] * slots
@@ -240,7 +263,8 @@ class ContinuousBatcher:
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
-               sample_rate: int | None = None, speed: float | None = None, seed: int | None = None) -> Request:
+               sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
+               peak_dbfs: float | None = None, seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -254,7 +278,10 @@ class ContinuousBatcher:
         ValueError, as does any rate but the native one on a batcher built without `sample_rates`.  `speed`: the
         request's speaking rate, one of the batcher's `speeds` or 1.0 (None: 1.0); a speed that is not configured, or
         that the plan rule refuses at the request's rate, raises ValueError, as does any speed but 1.0 on a batcher built
-        without `speeds`.  A stretched request needs frames_after_eos >= 1."""
+        without `speeds`.  A stretched request needs frames_after_eos >= 1.  `gain_db` (in [-40, 24]) and `peak_dbfs` (in
+        [-20, 0], default -1, only together with `gain_db`): the request's output level, gain plus a peak limiter that
+        keeps |sample| <= 10^(peak_dbfs / 20) (`level.py`); None: the samples of before.  Either raises ValueError on a
+        batcher built without `level`; a levelled request needs frames_after_eos >= 1 too."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -294,6 +321,20 @@ class ContinuousBatcher:
         elif speed is not None and (isinstance(speed, bool) or not isinstance(speed, numbers.Real) or speed != 1.0):
             raise ValueError(f"speed {speed!r}: this batcher speaks at 1.0 only (build it with speeds for per-request speeds)")
         stretched = plan is not None and not self.ts.plans[plan].identity
+        lvl = None
+        if self.lv is not None:
+            from . import level
+
+            g_db, p_db = level.check(gain_db, peak_dbfs)
+            if g_db is not None:
+                lvl = (self.pipe.level_plan(rate, speed), g_db, p_db)
+        elif gain_db is not None or peak_dbfs is not None:
+            raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
+        n_out = pre = 0
+        if self.lagging:
+            n_out = self.ts.plans[plan].n_out if self.ts is not None else (
+                self.rs.out_n(rate) if self.rs is not None else self.eng.frame_samples)
+            pre = (self.ts.plans[plan].preroll if self.ts is not None else 0) + (self.lv.plans[lvl[0]].LA if lvl else 0)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -322,13 +363,16 @@ class ContinuousBatcher:
             if stretched and fae < 1:
                 raise ValueError("a request with a speed needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")
+            if lvl is not None and fae < 1:
+                raise ValueError("a request with a gain needs frames_after_eos >= 1: the row is set to drain before the "
+                                 "frame that follows its last one is queued")
             ids = m.tokenizer.encode(chunk)
             gen = estimate_max_gen_len(len(ids), m.config.mimi.frame_rate)
             need = t_voice + len(ids) + gen + self.pipe.nb + 2  # a row runs up to nb steps past its end before it is parked
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp, lsd, None if seed is None else chunk_seed(seed, i), rate, plan))
+                             samp, lsd, None if seed is None else chunk_seed(seed, i), rate, plan, lvl, n_out, pre))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -427,6 +471,9 @@ class ContinuousBatcher:
                 self.rs.set_row(b, job.rate, self.pipe.s2)
             if self.ts is not None:  # the row's plan and a zero stretch state, not draining
                 self.ts.set_row(b, job.plan, self.pipe.s2)
+            if self.lv is not None:  # the row's gain and ceiling (or bypass) and a zero limiter state, not draining
+                self.lv.set_row(b, *(job.lvl or (None, None, None)), self.pipe.s2)
+            if self.lagging:
                 self.a_pos[b], self.row_drain[b], self.a_release[b] = 0, False, -1
             job.start = self.g
             self.slot[b] = job
@@ -452,7 +499,7 @@ class ContinuousBatcher:
         pipe.done_event(frame).synchronize()  # codec frame done => the FlowLM step's flags are on the host too
         q = frame % pipe.nb
         rows = (self.a_emit < 0) & (self.a_start <= frame)
-        held = np.nonzero(self.a_release >= 0)[0] if self.ts is not None else ()
+        held = np.nonzero(self.a_release >= 0)[0] if self.lagging else ()
         if not rows.any() and not len(held):
             return
         eos_bookkeeping_rows(frame - self.a_start, self.a_gen, self.a_fae, self.a_eos, self.a_emit,
@@ -463,7 +510,7 @@ class ContinuousBatcher:
         else:
             ring = pipe.pcm16_of(frame) if self.pcm_format == "i16" else pipe.pcm_of(frame)
         pcm = torch.from_numpy(ring.numpy().copy())
-        for b in held:  # jobs that have ended and flush their stretch tail: this is one of their drain frames
+        for b in held:  # jobs that have ended and flush their chain's tail: this is one of their drain frames
             job = self.slot[b]
             self._deliver_stretched(b, job, pcm[b])
             if frame >= self.a_release[b]:
@@ -473,7 +520,7 @@ class ContinuousBatcher:
         for b in np.nonzero(rows)[0]:
             job = self.slot[b]
             if self.a_emit[b] < 0:
-                if self.ts is not None:
+                if self.lagging:
                     self._deliver_stretched(b, job, pcm[b])
                 else:
                     job.req._q.put(pcm[b] if self.rs is None else pcm[b, :self.rs.out_n(job.rate)])
@@ -482,11 +529,11 @@ class ContinuousBatcher:
             if self.a_eos[b] < 0:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
             self.st.set_row_active(int(b), False)
-            drain = self.ts.plans[job.plan].drain_frames if self.ts is not None else 0
+            drain = -(-job.pre // job.n_out) if self.lagging else 0
             if drain:
                 # `frame` is the first one past the job's end and, by _drain_due, the first one its row saw as zeros
                 if not self.row_drain[b]:
-                    raise RuntimeError("a stretched row ended before it was set to drain")
+                    raise RuntimeError("a row whose output chain lags ended before it was set to drain")
                 self._deliver_stretched(b, job, pcm[b])
                 if drain > 1:
                     self.a_release[b] = frame + drain - 1
@@ -495,24 +542,26 @@ class ContinuousBatcher:
             self._finish(job)
 
     def _deliver_stretched(self, b, job, line):
-        """routes the part of a frame of slot `b` that belongs to its job: everything behind the plan's pre-roll, up to
-        frames * n_out samples in all once the job's frame count is known"""
-        p = self.ts.plans[job.plan]
+        """routes the part of a frame of slot `b` that belongs to its job: everything behind the pre-roll of the row's
+        output chain, up to frames * n_out samples in all once the job's frame count is known"""
+        n_out, pre = job.n_out, job.pre
         pos = int(self.a_pos[b])
-        lo = max(p.preroll - pos, 0)
-        hi = p.n_out if self.a_emit[b] < 0 else min(p.n_out, p.preroll + int(self.a_emit[b]) * p.n_out - pos)
+        lo = max(pre - pos, 0)
+        hi = n_out if self.a_emit[b] < 0 else min(n_out, pre + int(self.a_emit[b]) * n_out - pos)
         if hi > lo:
             job.req._q.put(line[lo:hi])
-        self.a_pos[b] = pos + p.n_out
+        self.a_pos[b] = pos + n_out
 
     def _drain_due(self):
-        """Before codec frame g is queued: every stretched row whose job ends before that frame is set to drain on the
-        codec stream, so that the frames past the job's end count as zeros.  A job's end is known `frames_after_eos`
+        """Before codec frame g is queued: every row whose output chain lags (a stretch, a level, or both) and whose job
+        ends before that frame is set to drain on the codec stream, so that the frames past the job's end count as zeros:
+        through the stretcher's flag where the row is stretched (what the stretcher emits past its tail is zero, which is
+        what the leveler behind it then reads), else through the leveler's.  A job's end is known `frames_after_eos`
         frames ahead once the EOS flags up to then have been read; where they have not, this reads them (it waits for
         the frames concerned), which a row without a speed never needs."""
         for b in range(self.B):
             job = self.slot[b]
-            if job is None or self.row_drain[b] or self.ts.plans[job.plan].identity:
+            if job is None or self.row_drain[b] or job.pre == 0:
                 continue
             start, gen, fae = int(self.a_start[b]), int(self.a_gen[b]), int(self.a_fae[b])
             local = self.g - start
@@ -532,7 +581,10 @@ class ContinuousBatcher:
                     continue
                 break
             if end is not None and local >= end and self.slot[b] is job:
-                self.ts.set_row_drain(b, True, self.pipe.s2)
+                if self.ts is not None and not self.ts.plans[job.plan].identity:
+                    self.ts.set_row_drain(b, True, self.pipe.s2)
+                else:
+                    self.lv.set_row_drain(b, True, self.pipe.s2)
                 self.row_drain[b] = True
 
     def _finish(self, job):
@@ -564,7 +616,7 @@ class ContinuousBatcher:
         if all(j is None for j in self.slot):
             self._drain()
             return bool(self.waiting)
-        if self.ts is not None:
+        if self.lagging:
             self._drain_due()
             if all(j is None for j in self.slot):
                 self._drain()

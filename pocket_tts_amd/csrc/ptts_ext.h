@@ -47,3 +47,11 @@ struct ptts_stretcher;
 int stretch_enqueue(hipStream_t st, ptts_stretcher *ts, const float *d_in, void *out, int is_i16, int *d_delta);
 int stretch_batch(const ptts_stretcher *ts);
 int stretch_in_max(const ptts_stretcher *ts);
+
+// ---- ptts_level.hip: per-request output gain with a look-ahead peak limiter (the last output stage) ---------------------
+// the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host).  Returns 0 or
+// a negative error code (message recorded).
+struct ptts_leveler;
+int level_enqueue(hipStream_t st, ptts_leveler *lv, const float *d_in, void *out, int is_i16);
+int level_batch(const ptts_leveler *lv);
+int level_width(const ptts_leveler *lv);

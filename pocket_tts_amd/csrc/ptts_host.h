@@ -263,6 +263,12 @@ struct ptts_mimi_state {
   float *ts_in = nullptr;
   void *ts_out = nullptr;
   int ts_i16 = 0;
+  // output level (ptts_mimi_set_leveler): the level launch is the last one; it reads the frame's PCM (lv_in == nullptr) or
+  // lv_in, the buffer the stage before it writes
+  ptts_leveler *lv = nullptr;
+  float *lv_in = nullptr;
+  void *lv_out = nullptr;
+  int lv_i16 = 0;
   // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
   float *pcm_part = nullptr, *pcm_carry = nullptr;
   long pcm_cstride = 0;

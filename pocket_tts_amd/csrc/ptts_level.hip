@@ -1,0 +1,257 @@
+// Per-request output gain with a streaming look-ahead peak limiter: the last output stage, behind the codec's last kernel,
+// the resampler or the stretcher (include/ptts.h, "output level"; contract and plan rule: pocket_tts_amd/level.py; index
+// functions and their bounds: ptts_level.h).
+//
+// One launch per frame, one workgroup per row (a row's recurrence is serial across tiles, rows are independent).  A limiting
+// row walks its frame in tiles of at most PTTS_LV_TILE samples, two neighbouring samples per thread:
+//   stage    U = carried u || G x of the tile in LDS (zeros for the tile when the row drains: the input is then not read)
+//   r        R = |U| > C ? C / |U| : 1 over the whole line
+//   minimum  m[i] = min R[i .. i + LA]: exact, so the two samples of a thread share the entries both windows hold
+//   scan     d[i] = max(1 - m[i], a d[i - 1]) as an associative scan over pairs (A, c), f(d) = max(c, A d): the thread's two
+//            samples, an inclusive scan over the wave (shuffles), the 16 wave totals through LDS seeded with the d carried
+//            from the tile before.  The order of the combines is fixed by the sample's index in the frame.
+//   e        E = carried e || 1 - d of the tile, in the line R leaves
+//   box      g[i] = k (E[i + 1] + .. + E[i + LA]), added in ascending order of the index
+//   store    y[i] = g[i] U[i]
+// After the last tile the same workgroup writes the row's carried u, carried e and d back: no other block reads them, so there
+// is no second launch.  Bypass rows copy their line and exit.
+#include <cstring>
+
+#include "ptts_host.h"
+#include "ptts_level.h"
+
+struct ptts_leveler {
+  ptts_engine *e = nullptr;
+  int B = 0, n_plans = 0, width = 0;
+  LvPlan *plans = nullptr;   // [n_plans]
+  int *row_plan = nullptr;   // [B] index into plans, < 0: bypass
+  int *row_drain = nullptr;  // [B] != 0: the row's incoming frames count as zeros
+  float *row_gc = nullptr;   // [B][2]: G, C
+  float *cu = nullptr;       // [B][PTTS_LV_MAX_LA]: the row's last LA samples of u at the front of its line
+  float *ce = nullptr;       // [B][PTTS_LV_MAX_LA]: its last LA samples of e
+  float *row_d = nullptr;    // [B]: its last d
+};
+
+constexpr int kLvMaxPlans = 256;
+constexpr int kLvThreads = 1024;
+constexpr int kLvWaves = kLvThreads / 64;
+static_assert(2 * kLvThreads >= PTTS_LV_TILE, "two samples of a tile per thread");
+static_assert(PTTS_LV_MAX_LA <= kLvThreads, "one carried sample per thread");
+
+__device__ inline float lv_i16(float v) { return fminf(fmaxf(v, -1.0f), 1.0f) * 32767.0f; }
+
+__global__ __launch_bounds__(kLvThreads) void level_kernel(const float *__restrict__ in, int width,
+                                                           const LvPlan *__restrict__ plans, int n_plans,
+                                                           const int *__restrict__ row_plan, const int *__restrict__ row_drain,
+                                                           const float *__restrict__ row_gc, float *__restrict__ cu,
+                                                           float *__restrict__ ce, float *__restrict__ row_d,
+                                                           float *__restrict__ out_f, int16_t *__restrict__ out_i) {
+  __shared__ float U[PTTS_LV_LINE];  // carried u || u of the tile
+  __shared__ float E[PTTS_LV_LINE];  // r of the same samples, then carried e || e of the tile
+  __shared__ float wA[kLvWaves], wc[kLvWaves], wseed[kLvWaves];
+  __shared__ float dlast;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float *x = in + (size_t)row * width;  // n <= width (ptts_leveler_create)
+  const size_t o0 = (size_t)row * width;
+  const int pi = row_plan[row];
+  if (pi < 0) {  // bypass (uniform: the whole block leaves): a row without a plan has no n, its whole line is copied
+    for (int i = tid; i < width; i += kLvThreads) {
+      const float v = x[i];
+      if (out_i) out_i[o0 + i] = (int16_t)lv_i16(v);
+      else out_f[o0 + i] = v;
+    }
+    return;
+  }
+  const LvPlan P = plans[min(pi, n_plans - 1)];
+  const int n = P.n, LA = P.LA;  // 1 <= LA <= PTTS_LV_MAX_LA, LA <= n <= width (lv_plan_ok, ptts_leveler_create)
+  const float a = P.a, k = P.k, G = row_gc[2 * row], C = row_gc[2 * row + 1];
+  const bool drain = row_drain[row] != 0;
+  float *curow = cu + (size_t)row * PTTS_LV_MAX_LA;
+  float *cerow = ce + (size_t)row * PTTS_LV_MAX_LA;
+  float ucar = 0.f, ecar = 1.f;  // thread c < LA: entry c of the carried lines
+  if (tid < LA) { ucar = curow[tid]; ecar = cerow[tid]; U[tid] = ucar; }
+  float dcar = row_d[row];
+  const int tiles = lv_tiles(n);
+  for (int j = 0; j < tiles; ++j) {
+    const int T = lv_tile_len(j, n);
+    for (int i = tid; i < T; i += kLvThreads) U[lv_cur(i, LA)] = drain ? 0.f : G * x[lv_io(j, i)];
+    __syncthreads();
+    for (int i = tid; i < LA + T; i += kLvThreads) {
+      const float au = fabsf(U[i]);
+      E[i] = au > C ? C / au : 1.0f;  // a NaN compares false
+    }
+    __syncthreads();
+    const int i0 = 2 * tid, i1 = 2 * tid + 1;
+    const bool on0 = i0 < T, on1 = i1 < T;
+    float m0 = 1.f, m1 = 1.f;
+    if (on0) {
+      float common = 1.f;  // the entries both windows hold: [i0 + 1, i0 + LA]
+      for (int q = lv_min_lo(i0) + 1; q <= lv_min_hi(i0, LA); ++q) common = fminf(common, E[q]);
+      m0 = fminf(common, E[lv_min_lo(i0)]);
+      if (on1) m1 = fminf(common, E[lv_min_hi(i1, LA)]);
+    }
+    __syncthreads();  // every read of r is done: the line takes e below
+    // f_i(d) = max(c_i, A_i d); a sample past the tile's end is the identity (1, 0): d >= 0 throughout
+    const float A0 = on0 ? a : 1.f, c0 = on0 ? 1.0f - m0 : 0.f;
+    const float A1 = on1 ? a : 1.f, c1 = on1 ? 1.0f - m1 : 0.f;
+    float A = A1 * A0, c = fmaxf(c1, A1 * c0);
+    for (int off = 1; off < 64; off <<= 1) {
+      const float Ao = __shfl_up(A, off, 64), co = __shfl_up(c, off, 64);
+      if (lane >= off) { c = fmaxf(c, A * co); A = A * Ao; }
+    }
+    if (lane == 63) { wA[wave] = A; wc[wave] = c; }
+    __syncthreads();
+    if (tid == 0) {
+      float d = dcar;
+      for (int w = 0; w < kLvWaves; ++w) { wseed[w] = d; d = fmaxf(wc[w], wA[w] * d); }
+    }
+    __syncthreads();
+    const float Ae = __shfl_up(A, 1, 64), cex = __shfl_up(c, 1, 64), seed = wseed[wave];
+    const float dprev = lane == 0 ? seed : fmaxf(cex, Ae * seed);
+    const float d0 = fmaxf(c0, A0 * dprev), d1 = fmaxf(c1, A1 * d0);
+    if (on0 && i0 == T - 1) dlast = d0;
+    if (on1 && i1 == T - 1) dlast = d1;
+    if (tid < LA) E[tid] = ecar;
+    if (on0) E[lv_cur(i0, LA)] = 1.0f - d0;
+    if (on1) E[lv_cur(i1, LA)] = 1.0f - d1;
+    __syncthreads();
+    if (on0) {
+      float s = 0.f;  // the entries both sums hold: [i0 + 2, i0 + LA], ascending
+      for (int q = lv_box_lo(i0) + 1; q <= lv_box_hi(i0, LA); ++q) s += E[q];
+      const float y0 = (k * (E[lv_box_lo(i0)] + s)) * U[lv_delayed(i0)];
+      const size_t o = o0 + lv_io(j, i0);  // lv_io < n <= width
+      if (out_i) out_i[o] = (int16_t)lv_i16(y0);
+      else out_f[o] = y0;
+      if (on1) {
+        const float y1 = (k * (s + E[lv_box_hi(i1, LA)])) * U[lv_delayed(i1)];
+        if (out_i) out_i[o + 1] = (int16_t)lv_i16(y1);
+        else out_f[o + 1] = y1;
+      }
+    }
+    if (tid < LA) { ucar = U[lv_carry_src(tid, T)]; ecar = E[lv_carry_src(tid, T)]; }
+    dcar = dlast;
+    __syncthreads();  // every read of both lines is done
+    if (tid < LA) U[tid] = ucar;
+  }
+  if (tid < LA) { curow[tid] = ucar; cerow[tid] = ecar; }
+  if (tid == 0) row_d[row] = dcar;
+}
+
+__global__ __launch_bounds__(PTTS_LV_MAX_LA) void level_set_row_kernel(int *row_plan, int *row_drain, float *row_gc, float *cu,
+                                                                       float *ce, float *row_d, int row, int plan_index,
+                                                                       float G, float C) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    row_plan[row] = plan_index; row_drain[row] = 0; row_gc[2 * row] = G; row_gc[2 * row + 1] = C; row_d[row] = 0.f;
+  }
+  cu[(size_t)row * PTTS_LV_MAX_LA + tid] = 0.f;  // u = 0 and e = 1 before the stream's start
+  ce[(size_t)row * PTTS_LV_MAX_LA + tid] = 1.f;
+}
+
+__global__ void level_set_drain_kernel(int *row_drain, int row, int on) { row_drain[row] = on; }
+
+int level_batch(const ptts_leveler *lv) { return lv->B; }
+int level_width(const ptts_leveler *lv) { return lv->width; }
+
+int level_enqueue(hipStream_t st, ptts_leveler *lv, const float *d_in, void *out, int is_i16) {
+  if (!lv || !d_in || !out) return fail(-1, "level: null argument");
+  const int B = lv->B;
+  {
+    ProfScope ps(st, "level", 4.0 * B * (lv->width + 4.0 * PTTS_LV_MAX_LA) + (is_i16 ? 2.0 : 4.0) * B * lv->width, 0);
+    level_kernel<<<B, kLvThreads, 0, st>>>(d_in, lv->width, lv->plans, lv->n_plans, lv->row_plan, lv->row_drain, lv->row_gc,
+                                           lv->cu, lv->ce, lv->row_d, is_i16 ? nullptr : (float *)out,
+                                           is_i16 ? (int16_t *)out : nullptr);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ptts_leveler_create(ptts_engine *e, int32_t batch, const int32_t *h_plans, int32_t n_plans, ptts_leveler **out) {
+  if (!e || !out || !h_plans) return fail(-1, "leveler_create: null argument");
+  if (batch < 1 || n_plans < 1 || n_plans > kLvMaxPlans) return fail(-1, "leveler_create: batch or number of plans out of range");
+  std::vector<LvPlan> plans(n_plans);
+  int width = 0;
+  for (int i = 0; i < n_plans; ++i) {
+    const int32_t *p = h_plans + 4 * i;
+    LvPlan P;
+    P.n = p[0]; P.LA = p[1];
+    std::memcpy(&P.a, p + 2, sizeof(float));
+    std::memcpy(&P.k, p + 3, sizeof(float));
+    if (!lv_plan_ok(P.n, P.LA) || !(P.a >= 0.f && P.a < 1.f) || !(P.k > 0.f && P.k <= 1.f))
+      return fail(-1, "leveler_create: plan " + std::to_string(i) + " (n " + std::to_string(P.n) + ", LA " +
+                          std::to_string(P.LA) + ", a " + std::to_string(P.a) + ", k " + std::to_string(P.k) +
+                          ") is not admissible");
+    plans[i] = P;
+    width = std::max(width, (int)P.n);
+  }
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  ptts_leveler *lv = new ptts_leveler();
+  lv->e = e; lv->B = batch; lv->n_plans = n_plans; lv->width = width;
+  const size_t line = (size_t)batch * PTTS_LV_MAX_LA;
+  std::vector<float> ones(line, 1.0f);
+  std::vector<int> bypass(batch, -1);
+  hipError_t er = hipMalloc(&lv->plans, (size_t)n_plans * sizeof(LvPlan));
+  if (er == hipSuccess) er = hipMalloc(&lv->row_plan, (size_t)batch * sizeof(int));
+  if (er == hipSuccess) er = hipMalloc(&lv->row_drain, (size_t)batch * sizeof(int));
+  if (er == hipSuccess) er = hipMalloc(&lv->row_gc, (size_t)batch * 2 * sizeof(float));
+  if (er == hipSuccess) er = hipMalloc(&lv->cu, line * sizeof(float));
+  if (er == hipSuccess) er = hipMalloc(&lv->ce, line * sizeof(float));
+  if (er == hipSuccess) er = hipMalloc(&lv->row_d, (size_t)batch * sizeof(float));
+  if (er == hipSuccess) er = hipMemcpy(lv->plans, plans.data(), (size_t)n_plans * sizeof(LvPlan), hipMemcpyHostToDevice);
+  if (er == hipSuccess) er = hipMemcpy(lv->row_plan, bypass.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice);
+  if (er == hipSuccess) er = hipMemset(lv->row_drain, 0, (size_t)batch * sizeof(int));
+  if (er == hipSuccess) er = hipMemset(lv->row_gc, 0, (size_t)batch * 2 * sizeof(float));
+  if (er == hipSuccess) er = hipMemset(lv->cu, 0, line * sizeof(float));
+  if (er == hipSuccess) er = hipMemcpy(lv->ce, ones.data(), line * sizeof(float), hipMemcpyHostToDevice);
+  if (er == hipSuccess) er = hipMemset(lv->row_d, 0, (size_t)batch * sizeof(float));
+  if (er == hipSuccess) er = hipDeviceSynchronize();
+  if (er != hipSuccess) {
+    ptts_leveler_destroy(lv);
+    return fail(-2, std::string("leveler_create: ") + hipGetErrorString(er));
+  }
+  *out = lv;
+  return 0;
+}
+
+extern "C" void ptts_leveler_destroy(ptts_leveler *lv) {
+  if (!lv) return;
+  hipSetDevice(lv->e->device);
+  hipDeviceSynchronize();
+  hipFree(lv->plans); hipFree(lv->row_plan); hipFree(lv->row_drain); hipFree(lv->row_gc); hipFree(lv->cu); hipFree(lv->ce);
+  hipFree(lv->row_d);
+  delete lv;
+}
+
+extern "C" int ptts_leveler_set_row(ptts_leveler *lv, int32_t row, int32_t plan_index, float gain, float ceiling, void *stream) {
+  if (!lv) return fail(-1, "leveler_set_row: null leveler");
+  if (row < 0 || row >= lv->B) return fail(-1, "leveler_set_row: row out of range");
+  if (plan_index < -1 || plan_index >= lv->n_plans) return fail(-1, "leveler_set_row: plan index out of range");
+  if (plan_index >= 0 && !(gain > 0.f && gain <= 16.f && ceiling > 0.f && ceiling <= 1.f))
+    return fail(-1, "leveler_set_row: the gain must be in (0, 16] and the ceiling in (0, 1]");
+  ENGINE_LOCK(lv->e);
+  HIPCHK(hipSetDevice(lv->e->device));
+  level_set_row_kernel<<<1, PTTS_LV_MAX_LA, 0, S(lv->e, stream)>>>(lv->row_plan, lv->row_drain, lv->row_gc, lv->cu, lv->ce,
+                                                                  lv->row_d, row, plan_index, plan_index < 0 ? 1.f : gain,
+                                                                  plan_index < 0 ? 1.f : ceiling);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ptts_leveler_set_row_drain(ptts_leveler *lv, int32_t row, int32_t on, void *stream) {
+  if (!lv) return fail(-1, "leveler_set_row_drain: null leveler");
+  if (row < 0 || row >= lv->B) return fail(-1, "leveler_set_row_drain: row out of range");
+  ENGINE_LOCK(lv->e);
+  HIPCHK(hipSetDevice(lv->e->device));
+  level_set_drain_kernel<<<1, 1, 0, S(lv->e, stream)>>>(lv->row_drain, row, on != 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_i16, void *stream) {
+  if (!lv || !d_in || !out) return fail(-1, "level_frame: null argument");
+  ENGINE_LOCK(lv->e);
+  HIPCHK(hipSetDevice(lv->e->device));
+  bind_engine(lv->e);
+  return level_enqueue(S(lv->e, stream), lv, d_in, out, is_i16 != 0);
+}

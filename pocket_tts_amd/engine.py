@@ -248,6 +248,20 @@ class MimiState:
         _lib.check(self.engine.lib.ptts_mimi_set_stretcher(self.handle, ts.handle, _ptr(mid) if mid is not None else None,
                                                            _ptr(out), int(out.dtype == torch.int16)))
 
+    def set_leveler(self, lv: "Leveler | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `lv` as their last launch, writing `out` [B, lv.width],
+        float32 or int16, device or pinned host (include/ptts.h: ptts_mimi_set_leveler).  `mid` None: it reads the frame's
+        PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid` [B, lv.width], which the caller
+        has given the resampler or the stretcher set on this state as its output.  None: off."""
+        if lv is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, None, None, None, 0))
+            return
+        lv._check_out(out)
+        if mid is not None:
+            lv._check_in(mid)
+        _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, lv.handle, _ptr(mid) if mid is not None else None,
+                                                         _ptr(out), int(out.dtype == torch.int16)))
+
     def __del__(self):
         try:
             self.close()
@@ -333,6 +347,92 @@ class Stretcher:
     def close(self):
         if self.handle is not None:
             self.engine.lib.ptts_stretcher_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Leveler:
+    """Output levels of `batch` sequences (include/ptts.h: ptts_leveler; contract and plan rule: `level.py`).  `plans` is a
+    list of `level.LevelPlan`; a row is dealt a plan by its index together with its gain and ceiling in dB (`set_row`;
+    `gain_db` None: bypass) and starts on bypass.  `frame(x, out)` turns one frame x[b, :n(plan of b)] into
+    out[b, :n(plan of b)], LA samples late; `set_row_drain` makes a row's incoming frames count as zeros, which flushes its
+    tail.  A bypass row's whole line is copied."""
+
+    def __init__(self, engine: "Engine", batch: int, plans):
+        self.engine, self.batch = engine, batch
+        self.handle = None
+        self.plans = list(plans)
+        self.width = max(p.n for p in self.plans)
+        self.rows = [(-1, None, None)] * batch  # host mirror: (plan index, gain_db, peak_dbfs) of each row
+        n = len(self.plans)
+        ints = (C.c_int32 * (4 * n))(*[v for p in self.plans for v in p.ints()])
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_leveler_create(engine.handle, batch, ints, n, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _sp(self, stream):
+        return self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
+
+    def set_row(self, row: int, plan_index: int | None = None, gain_db=None, peak_dbfs=None,
+                stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` at `gain_db` under `peak_dbfs` (default -1) with a zero state,
+        not draining; `gain_db` None: the row bypasses the stage.  Stream-ordered"""
+        from . import level
+
+        g, c = level.check(gain_db, peak_dbfs)
+        if g is None:
+            idx, G, Cc = -1, 1.0, 1.0
+        else:
+            idx, G, Cc = int(plan_index), float(level.linear(g)), float(level.linear(c))
+            if not 0 <= idx < len(self.plans):
+                raise ValueError(f"leveler plan index {plan_index!r} out of range")
+        _lib.check(self.engine.lib.ptts_leveler_set_row(self.handle, int(row), idx, G, Cc, self._sp(stream)))
+        self.rows[row] = (idx, g, c)
+
+    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
+        """from now on (stream-ordered) the row's incoming frames count as zeros"""
+        _lib.check(self.engine.lib.ptts_leveler_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
+
+    def reset(self, stream: torch.cuda.Stream | None = None):
+        """every row's state back to zero (new utterances); the rows keep their plans, gains and ceilings"""
+        for b in range(self.batch):
+            idx, g, c = self.rows[b]
+            self.set_row(b, idx, g, c, stream)
+
+    def _check_out(self, out):
+        if out is None or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (self.batch, self.width) \
+                or not out.is_contiguous():
+            raise ValueError(f"leveler output: expected a contiguous float32 or int16 [{self.batch}, {self.width}] tensor")
+
+    def _check_in(self, x):
+        e = self.engine
+        if x is None or x.device != e.device or x.dtype != torch.float32 or tuple(x.shape) != (self.batch, self.width) \
+                or not x.is_contiguous():
+            raise ValueError(f"leveler input: expected a contiguous float32 [{self.batch}, {self.width}] tensor on {e.device}")
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] on the device -> out (float32 or int16 [B, width], device or pinned host)"""
+        e = self.engine
+        self._check_in(x)
+        self._check_out(out)
+        if stream is None:
+            e._pre()
+        _lib.check(e.lib.ptts_level_frame(self.handle, _ptr(x), _ptr(out), int(out.dtype == torch.int16), self._sp(stream)))
+        if stream is None:
+            for t in (x, out):
+                if t.is_cuda:
+                    t.record_stream(e.stream)
+            e._post()
+
+    def close(self):
+        if self.handle is not None:
+            self.engine.lib.ptts_leveler_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -657,6 +757,9 @@ class Engine:
 
     def new_stretcher(self, batch: int, plans) -> Stretcher:
         return Stretcher(self, batch, plans)
+
+    def new_leveler(self, batch: int, plans) -> Leveler:
+        return Leveler(self, batch, plans)
 
     # ---- FlowLM
     def embed_text(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -1042,13 +1145,19 @@ class StepPipeline:
     speed that is not configured or not admissible at that rate.  The samples reach the host through `out[p]` as above,
     row b's in its first `ts.n_out(plan index of b)` entries; rows get their plans with `ts.set_row(row, plan, s2)`.  A
     speed must be admissible at one of the rates at least.  With None nothing changes.
+
+    `level` (True; not in "fork" mode): the codec graphs end with the leveler's launch (`level.py`), the last stage of the
+    chain codec -> resampler -> stretcher -> level.  The pipeline holds one plan per distinct (rate, samples per frame) its
+    rates x speeds can produce in `lv` (`engine.Leveler`); `level_plan(rate index, speed)` is the plan index of a pair.  The
+    samples reach the host through `out[p]`; rows get their gains with `lv.set_row(row, plan, gain_db, peak_dbfs, s2)` and
+    start on bypass.  With False nothing changes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None):
+                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False):
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
@@ -1056,7 +1165,10 @@ class StepPipeline:
             raise ValueError("sample_rates: not available in the 'fork' mode")
         if speeds is not None and self.mode == "fork":
             raise ValueError("speeds: not available in the 'fork' mode")
+        if level and self.mode == "fork":
+            raise ValueError("level: not available in the 'fork' mode")
         self.ts, self.speeds, self.ts_index, self.mid = None, None, None, None
+        self.lv, self.lv_index, self.lv_mid = None, None, None
         if speeds is not None:  # the plan table first: a speed no rate admits is refused before anything is allocated
             from . import resample, stretch
 
@@ -1066,8 +1178,21 @@ class StepPipeline:
             self.ts_rates = [r for r, _ in rates]
             ts_plans, self.ts_index = stretch.table(rates, self.speeds)
         self.rs = Resampler(eng, B, sample_rates) if sample_rates is not None else None
+        if level:  # likewise: a (rate, samples per frame) the plan rule refuses is refused before anything is allocated
+            from . import level as level_rule
+            from . import resample
+
+            if speeds is not None:
+                pairs = [(rates[r][0], ts_plans[i].n_out) for r, row in enumerate(self.ts_index) for i in row if i is not None]
+            elif sample_rates is not None:
+                pairs = [(p.rate, p.out_n) for p in resample.plans(sample_rates, eng.sample_rate, eng.frame_samples)]
+            else:
+                pairs = [(eng.sample_rate, eng.frame_samples)]
+            lv_plans, self.lv_index = level_rule.table(pairs)
         if speeds is not None:
             self.ts = Stretcher(eng, B, ts_plans)
+        if level:
+            self.lv = Leveler(eng, B, lv_plans)
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -1076,14 +1201,20 @@ class StepPipeline:
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host
-        if self.rs is None and self.ts is None:
+        if self.rs is None and self.ts is None and self.lv is None:
             self.pcm = [torch.zeros(B, eng.frame_samples).pin_memory() for _ in range(nb)]
             self.out = None
         else:
             last = self.ts if self.ts is not None else self.rs  # the last output stage writes the pinned ring
+            width = self.lv.width if self.lv is not None else last.out_max
             self.pcm = [torch.zeros(B, eng.frame_samples, device=dev) for _ in range(nb)]
-            self.out = [torch.zeros(B, last.out_max, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
+            self.out = [torch.zeros(B, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
                         for _ in range(nb)]
+            if self.lv is not None and last is not None:
+                # resampler / stretcher -> leveler: likewise one device buffer for every ring slot
+                if last.out_max != width:
+                    raise ValueError("level: the leveler's line is not the line of the stage before it")
+                self.lv_mid = torch.zeros(B, width, device=dev)
             if self.ts is not None and self.rs is not None:
                 # resampler -> stretcher: one device buffer serves every ring slot (the codec graphs run one after the
                 # other on the codec stream)
@@ -1104,14 +1235,19 @@ class StepPipeline:
         self.g_last = []
         for p in range(nb):
             if self.out is not None:  # the 16-bit conversion happens behind the last output stage
+                end = self.out[p] if self.lv is None else self.lv_mid  # what the stage before the leveler writes
                 if self.rs is not None:
-                    mimi_state.set_resampler(self.rs, self.out[p] if self.ts is None else self.mid)
+                    mimi_state.set_resampler(self.rs, end if self.ts is None else self.mid)
                 if self.ts is not None:
-                    mimi_state.set_stretcher(self.ts, self.out[p], self.mid)
+                    mimi_state.set_stretcher(self.ts, end, self.mid)
+                if self.lv is not None:
+                    mimi_state.set_leveler(self.lv, self.out[p], self.lv_mid)
             else:
                 mimi_state.set_pcm_i16(self.pcm16[p] if pcm_i16 else None)
             self.g_last.append(eng.capture_mimi(mimi_state, self.lat[p], self.pcm[p]))
         mimi_state.set_pcm_i16(None)
+        if self.lv is not None:
+            mimi_state.set_leveler(None)
         if self.ts is not None:
             mimi_state.set_stretcher(None)
         if self.rs is not None:
@@ -1140,6 +1276,8 @@ class StepPipeline:
                 self.rs.reset(self.s2)
             if self.ts is not None:
                 self.ts.reset(self.s2)
+            if self.lv is not None:
+                self.lv.reset(self.s2)
         else:
             self.ms.reset()
         self.t = 0
@@ -1248,6 +1386,17 @@ class StepPipeline:
             raise ValueError(f"speed {speed!r} is not admissible at {self.ts_rates[rate_index]} Hz (admissible there: {ok})")
         return i
 
+    def level_plan(self, rate_index: int = 0, speed=None) -> int:
+        """index in `lv.plans` of the plan of a row at the rate at `rate_index` of this pipeline and at `speed` (None: 1.0);
+        ValueError as `speed_plan` raises it"""
+        if self.ts is not None:
+            rate, n = self.ts_rates[rate_index], self.ts.plans[self.speed_plan(rate_index, speed)].n_out
+        elif self.rs is not None:
+            rate, n = self.rs.rates[rate_index], self.rs.out_n(rate_index)
+        else:
+            rate, n = self.eng.sample_rate, self.eng.frame_samples
+        return self.lv_index[(int(rate), int(n))]
+
     def done_event(self, frame: int):
         """event that fires when the codec decode of `frame` (PCM in `pcm_of(frame)`) is complete"""
         return self.ev[frame % self.nb]
@@ -1266,6 +1415,8 @@ class StepPipeline:
         self.sync()
         for g in self.g_first + self.g_last + self.g_both:
             self.eng.graph_destroy(g)
+        if self.lv is not None:
+            self.lv.close()
         if self.ts is not None:
             self.ts.close()
         if self.rs is not None:

@@ -10,7 +10,8 @@
 `serve` runs the HTTP server of `server.py` (`GET /health`, `POST /tts` streaming the same WAV bytes) on a continuous
 batcher, with per-request temperature, noise clamp, EOS threshold and seed, and with `--sample-rates 8000,16000,48000` a
 per-request `sample_rate`, and with `--speeds 0.8,1.25,1.5` a per-request `speed` (pitch-preserving time-stretch on the GPU,
-stretch.py; `generate --speed 1.25` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
+stretch.py; `generate --speed 1.25` is the same for one text), and with `--level` a per-request `gain_db` / `peak_dbfs`
+(gain plus a look-ahead peak limiter on the GPU, level.py; `generate --gain-db 6 [--peak-dbfs -1]`).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -111,6 +112,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Output sample rate (e.g. 8000, 16000, 22050, 44100, 48000; default: the codec's 24000), resampled on the GPU")
     g.add_argument("--speed", type=float, default=None,
                    help="Speaking rate in [0.5, 2] (e.g. 0.8, 1.25, 1.5; default 1.0): time-stretched on the GPU at constant pitch")
+    g.add_argument("--gain-db", type=float, default=None,
+                   help="Output gain in dB, in [-40, 24], with a peak limiter that guarantees the ceiling (default: none)")
+    g.add_argument("--peak-dbfs", type=float, default=None,
+                   help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db")
     g.add_argument("--output-path", default="./tts_output.wav")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
@@ -137,6 +142,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--speeds", type=parse_speed_list, default=None, metavar="S1,S2,...",
                    help="Speaking rates a request may choose with the form field speed, e.g. 0.8,1.25,1.5 (1.0 is always "
                         "available); each must give whole hops per frame at one of the server's rates")
+    s.add_argument("--level", action="store_true",
+                   help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
+                        "limiter on the GPU)")
     s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
     s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
     s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
@@ -169,7 +177,7 @@ def serve_app(args) -> int:
     # the model's noise clamp reaches every request as a per-request setting (server.py)
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
-                     sample_rates=args.sample_rates, speeds=args.speeds)
+                     sample_rates=args.sample_rates, speeds=args.speeds, level=args.level)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -224,9 +232,28 @@ def cli_app(argv=None) -> int:
         except ValueError as e:
             logger.error("--speed: %s", e)
             return 1
+    if args.gain_db is not None or args.peak_dbfs is not None:
+        # likewise: refuse the level before the output file is opened
+        from . import level, resample, stretch
+
+        try:
+            level.check(args.gain_db, args.peak_dbfs)
+            native, fs = int(model.sample_rate), model.engine.frame_samples
+            rate = args.sample_rate or native
+            n = resample.plan(rate, native, fs).out_n
+            if args.speed is not None and float(stretch.fraction(args.speed)) != 1.0:
+                n = stretch.plan(args.speed, rate, n).n_out
+            level.plan(rate, n)
+        except ValueError as e:
+            logger.error("--gain-db / --peak-dbfs: %s", e)
+            return 1
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
-    if args.speed is None:
+    if args.gain_db is not None:
+        chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
+                                             seed=args.seed, sample_rate=args.sample_rate, speed=args.speed,
+                                             gain_db=args.gain_db, peak_dbfs=args.peak_dbfs)
+    elif args.speed is None:
         chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
                                              seed=args.seed, sample_rate=args.sample_rate)
     else:

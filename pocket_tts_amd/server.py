@@ -5,7 +5,8 @@ pocket_tts/main.py:121-214) with every request decoded in one shared batch.
 directory) or the file `voice_wav` - plus this server's optional per-request settings `temperature`, `noise_clamp`,
 `eos_threshold`, `frames_after_eos`, `lsd_decode_steps`, `seed` (the same seed, text and settings give the same noise
 again), `sample_rate` (one of the rates the server was started with, or the codec's own) and `speed` (one of the speaking
-rates the server was started with that the plan rule of `stretch.py` admits at the request's rate, or 1.0).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+rates the server was started with that the plan rule of `stretch.py` admits at the request's rate, or 1.0), and on a
+server started with `level` the output level `gain_db` with its ceiling `peak_dbfs` (`level.py`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
@@ -42,6 +43,7 @@ INDEX_HTML = """<!doctype html>
 <p>Seed <input name="seed" size="20"> (empty: a take that cannot be repeated)</p>
 <p>Sample rate <input name="sample_rate" size="6"> Hz (empty: the model's own rate)</p>
 <p>Speed <input name="speed" size="5"> (empty: 1.0)</p>
+<p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)</p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -206,8 +208,32 @@ def parse_speed(fields: dict, rate: int, table: dict | None) -> float | None:
     return near[0]
 
 
+def parse_level(fields: dict, enabled: bool):
+    """the optional `gain_db` and `peak_dbfs` fields as (gain_db, peak_dbfs), each None where absent or empty; FormError for
+    a value `level.check` refuses (its message names the rule) and for either field on a server started without level"""
+    from . import level
+
+    vals = {}
+    for name in ("gain_db", "peak_dbfs"):
+        raw = fields.get(name)
+        if raw is None or raw.strip() == "":
+            vals[name] = None
+            continue
+        if not enabled:
+            raise FormError(f"{name} is not available (this server was started without level)")
+        try:
+            vals[name] = float(raw.strip())
+        except ValueError:
+            raise FormError(f"{name} must be a number, got {raw!r}") from None
+    try:
+        return level.check(vals["gain_db"], vals["peak_dbfs"])
+    except ValueError as e:
+        raise FormError(str(e)) from None
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
-               batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None):
+               batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None,
+               level: bool = False):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
@@ -217,7 +243,8 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     of before); the WAV header and the trailing silence follow the request's rate.  `speeds`: the speaking rates a request
     may choose with `speed` besides 1.0 (None: only 1.0, and the batcher's graphs are those of before); each must be
     admissible at one of the server's rates at least (ValueError here, not at the first request), and a request whose
-    speed its rate does not admit gets a 400.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    speed its rate does not admit gets a 400.  `level`: requests may set their output level with `gain_db` and `peak_dbfs`
+    (False: a request that sends either gets a 400, and the batcher's graphs are those of before).  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
     if sample_rates is not None:
@@ -241,6 +268,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         reserve = max_lsd if max_lsd != own_lsd else None
 
         def batcher_factory(model, slots, capacity):
+            if level:
+                return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
+                                         sample_rates=sample_rates, speeds=speeds, level=True)
             if speeds is not None:
                 return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
                                          sample_rates=sample_rates, speeds=speeds)
@@ -342,6 +372,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             speed = parse_speed(fields, rate or int(model.sample_rate), speeds_of)
             if speed is not None and speed != 1.0:
                 settings["speed"] = speed
+            gain_db, peak_dbfs = parse_level(fields, level)
+            if gain_db is not None:
+                settings["gain_db"], settings["peak_dbfs"] = gain_db, peak_dbfs
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:

@@ -192,16 +192,24 @@ class TTSModel:
     @torch.no_grad()
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                        frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
-                       speed: float | None = None, seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63)), `sample_rate` and `speed` (not in the reference): see `generate_audio_stream`."""
+                       speed: float | None = None, gain_db: float | None = None, peak_dbfs: float | None = None,
+                       seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db` and `peak_dbfs` (not in the reference): see
+        `generate_audio_stream`."""
+        if gain_db is None and peak_dbfs is None:
+            chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
+                                                     seed=seed, sample_rate=sample_rate, speed=speed))
+            return torch.cat(chunks, dim=0)
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
-                                                 seed=seed, sample_rate=sample_rate, speed=speed))
+                                                 seed=seed, sample_rate=sample_rate, speed=speed, gain_db=gain_db,
+                                                 peak_dbfs=peak_dbfs))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                               frames_after_eos: int | None = None, copy_state: bool = True,
-                              sample_rate: int | None = None, speed: float | None = None, seed: int | None = None):
+                              sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
+                              peak_dbfs: float | None = None, seed: int | None = None):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
 
         `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
@@ -212,6 +220,12 @@ class TTSModel:
         audio is time-stretched on the GPU at constant pitch (streaming WSOLA, `stretch.py`) behind the codec, or behind
         the resampler.  A text chunk of F frames yields exactly F * n_out samples, in chunks of up to n_out = frame samples
         / speed.  None or 1.0: as before.
+
+        `gain_db` (not in the reference; in [-40, 24]) and `peak_dbfs` (in [-20, 0], default -1, only together with
+        `gain_db`): the audio is amplified by `gain_db` and peak-limited to 10^(peak_dbfs / 20) on the GPU (a streaming
+        look-ahead limiter, `level.py`), as the last output stage.  The samples yielded in all stay those of the same call
+        without a gain; the output lags by the look-ahead LA, so a text chunk's first tensor is LA samples short and a last
+        one of LA samples follows.  None: as before; 0 is not None, it limits at the ceiling.
 
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
@@ -238,6 +252,17 @@ class TTSModel:
                 speed = None
             else:
                 stretch.plan(speed, sample_rate or native, n_in)  # ValueError names the rule
+        lvl = None
+        if gain_db is not None or peak_dbfs is not None:
+            from . import level, resample, stretch
+
+            lvl = level.check(gain_db, peak_dbfs)  # ValueError names the rule
+            native = int(self.config.mimi.sample_rate)
+            n = self.engine.frame_samples if sample_rate is None else \
+                resample.plan(sample_rate, native, self.engine.frame_samples).out_n
+            if speed is not None:
+                n = stretch.plan(speed, sample_rate or native, n).n_out
+            level.plan(sample_rate or native, n)
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
@@ -247,7 +272,7 @@ class TTSModel:
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
-                                                              None if seed is None else chunk_seed(seed, i), sample_rate, speed)
+                                                              None if seed is None else chunk_seed(seed, i), sample_rate, speed, lvl)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -410,7 +435,7 @@ class TTSModel:
     def _drop_rate_contexts(self, keep: int = 0):
         """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
         recently used are released; a context in use is not in the cache"""
-        keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:]]
+        keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:] or "level" in k[4:]]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
             c["pipe"].close()
@@ -486,7 +511,7 @@ class TTSModel:
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
                                           row_seed: int | None = None, sample_rate: int | None = None,
-                                          speed: float | None = None):
+                                          speed: float | None = None, lvl=None):
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -504,6 +529,8 @@ class TTSModel:
             key = (*key, "rate", sample_rate)
         if speed is not None:  # likewise: its codec graphs end with the time-stretch
             key = (*key, "speed", speed)
+        if lvl is not None:  # likewise: its codec graphs end with the leveler (one context serves every gain and ceiling)
+            key = (*key, "level")
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -511,7 +538,18 @@ class TTSModel:
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
-            if sample_rate is None and speed is None:
+            if lvl is not None:
+                self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
+                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
+                                    sample_rates=None if sample_rate is None else [sample_rate],
+                                    speeds=None if speed is None else [speed], level=True)
+                r = 0
+                if sample_rate is not None:
+                    r = pipe.rs.index_of(sample_rate)
+                    pipe.rs.set_row(0, r, pipe.s2)
+                if speed is not None:
+                    pipe.ts.set_row(0, pipe.speed_plan(r, speed), pipe.s2)
+            elif sample_rate is None and speed is None:
                 pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync")
             elif speed is not None:
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
@@ -537,6 +575,9 @@ class TTSModel:
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         pipe.restart()
+        if lvl is not None:  # the row's gain and ceiling, with a zero limiter state, behind the restart on the codec stream
+            r = 0 if sample_rate is None else pipe.rs.index_of(sample_rate)
+            pipe.lv.set_row(0, pipe.level_plan(r, speed), lvl[0], lvl[1], pipe.s2)
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
             # state's own temperature is frozen into the captured step
@@ -556,14 +597,22 @@ class TTSModel:
             plan = None if speed is None else pipe.ts.plans[pipe.ts.row_plan[0]]
             if plan is not None:
                 out_n = plan.n_out
+            # a row whose output chain lags: its pre-roll is the stretcher's (0 without one) plus the leveler's look-ahead
+            preroll = plan.preroll if plan is not None else 0
+            if lvl is not None:
+                preroll += pipe.lv.plans[pipe.lv.rows[0][0]].LA
+            lagging = plan is not None or lvl is not None
+            if lagging and out_n is None:
+                out_n = eng.frame_samples
+            drain_frames = -(-preroll // out_n) if lagging else 0
 
-            pos, end = 0, None  # stretched: output samples read so far; pre-roll + frames * n_out once the frames are known
+            pos, end = 0, None  # lagging: output samples read so far; pre-roll + frames * n_out once the frames are known
 
             def pop(frame):
                 nonlocal pos
                 pipe.done_event(frame).synchronize()
-                if plan is not None:  # frames are read in order: drop the pre-roll, stop at `end`
-                    lo = max(plan.preroll - pos, 0)
+                if lagging:  # frames are read in order: drop the pre-roll, stop at `end`
+                    lo = max(preroll - pos, 0)
                     hi = out_n if end is None else max(min(out_n, end - pos), lo)
                     pos += out_n
                     return pipe.out_of(frame)[0, lo:hi].clone()
@@ -601,12 +650,16 @@ class TTSModel:
                 emitted += 1
             else:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
-            if plan is not None:
-                # stretched: `emitted` frames make emitted * n_out samples.  The row's tail comes out of `drain_frames`
-                # further codec frames, which it reads as zeros.
-                end = plan.preroll + emitted * plan.n_out
-                pipe.ts.set_row_drain(0, True, pipe.s2)
-                for f in range(emitted, emitted + plan.drain_frames):
+            if lagging:
+                # `emitted` frames make emitted * n_out samples.  The row's tail comes out of `drain_frames` further codec
+                # frames, which it reads as zeros: through the stretcher's flag where there is one (what it emits past its
+                # tail is zero), else through the leveler's.
+                end = preroll + emitted * out_n
+                if plan is not None:
+                    pipe.ts.set_row_drain(0, True, pipe.s2)
+                else:
+                    pipe.lv.set_row_drain(0, True, pipe.s2)
+                for f in range(emitted, emitted + drain_frames):
                     while yielded < f:  # every earlier frame is read before its ring slot is written again
                         chunk = pop(yielded)
                         yielded += 1
@@ -614,7 +667,7 @@ class TTSModel:
                         if chunk.shape[0]:
                             yield chunk
                     pipe.decode_async(f)
-                emitted += plan.drain_frames
+                emitted += drain_frames
             while yielded < emitted:
                 chunk = pop(yielded)
                 yielded += 1
