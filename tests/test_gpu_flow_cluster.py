@@ -1,5 +1,6 @@
 """The single-launch flow MLP (csrc/ptts_flow.h): parity with the one-launch-per-layer path, determinism of the
 in-launch hand-offs under load, and engine isolation (no process-global state in libptts).  `-m gpu`.
+Accuracy of both paths against fp64, with a derived bound: tests/test_gpu_flow_matrix.py; this file keeps determinism and isolation.
 
 The hand-off protocol (write-through stores + flag, polled by the consumers) must never deliver stale bytes.  A stale
 read would show as (a) a difference between two runs of the same trajectory, (b) a deviation from the multi-launch
