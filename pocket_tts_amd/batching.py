@@ -137,17 +137,11 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "rate", "plan", "lvl", "n_out",
-                 "pre")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "route")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, rate=0, plan=None, lvl=None,
-                 n_out=0, pre=0):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, route=None):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
-        self.lvl = lvl         # (plan index in the pipeline's leveler, gain_db, peak_dbfs) of the request (None: bypass)
-        self.n_out = n_out     # samples per frame at the end of the row's output chain (pipelines with a lagging stage)
-        self.pre = pre         # pre-roll of the row's output chain: the stretcher's plus the leveler's look-ahead
-        self.rate = rate       # index of the request's sample rate in the pipeline's resampler (0: native)
-        self.plan = plan       # index of the request's (rate, speed) plan in the pipeline's stretcher (None: no stretcher)
+        self.route = route     # the request's way through the pipeline's output chain (`output_chain.Route`)
         self.seed = seed       # the chunk's row seed (engine.chunk_seed of the request's seed), or None: the state's stream
         self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
         self.lsd = lsd         # the request's lsd_decode_steps, or None: the model's
@@ -183,17 +177,15 @@ class ContinuousBatcher:
         import numpy as np
 
         from .engine import StepPipeline
+        from .output_chain import ChainTable
 
         if pcm_format not in ("f32", "i16"):
             raise ValueError("pcm_format must be 'f32' or 'i16'")
         self.model, self.eng, self.B = model, model.engine, slots
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
-        if speeds is not None:  # a speed that no rate admits is refused before anything is allocated
-            from . import resample, stretch
-
-            stretch.table([(p.rate, p.out_n) for p in resample.plans(sample_rates or (), eng.sample_rate, eng.frame_samples)],
-                          stretch.normalise_speeds(speeds))
+        # what the chain's rules refuse is refused before anything is allocated
+        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level)
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -206,22 +198,10 @@ class ContinuousBatcher:
                 raise ValueError(f"max_lsd_decode_steps must be an integer in [1, 64], got {max_lsd_decode_steps}")
             self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
         self.max_lsd = max_lsd_decode_steps
-        self.native_rate = int(model.config.mimi.sample_rate)
-        if level:
-            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                     mode="events", pcm_i16=(pcm_format == "i16"),
-                                     sample_rates=None if sample_rates is None else list(sample_rates),
-                                     speeds=None if speeds is None else list(speeds), level=True)
-        elif sample_rates is None and speeds is None:  # the call of before, argument for argument
-            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                     mode="events", pcm_i16=(pcm_format == "i16"))
-        elif speeds is None:
-            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                     mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=list(sample_rates))
-        else:
-            self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                     mode="events", pcm_i16=(pcm_format == "i16"),
-                                     sample_rates=None if sample_rates is None else list(sample_rates), speeds=list(speeds))
+        self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
+                                 mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
+                                 level=level)
+        self.chain = self.pipe.chain
         self.rs = self.pipe.rs
         self.ts = self.pipe.ts
         self.lv = self.pipe.lv
@@ -308,33 +288,7 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
-        rate = 0
-        if sample_rate is not None:
-            if self.rs is not None:
-                rate = self.rs.index_of(sample_rate)
-            elif isinstance(sample_rate, bool) or sample_rate != self.native_rate:
-                raise ValueError(f"sample rate {sample_rate!r}: this batcher writes {self.native_rate} Hz only (build it "
-                                 "with sample_rates for per-request rates)")
-        plan = None
-        if self.ts is not None:
-            plan = self.pipe.speed_plan(rate, speed)
-        elif speed is not None and (isinstance(speed, bool) or not isinstance(speed, numbers.Real) or speed != 1.0):
-            raise ValueError(f"speed {speed!r}: this batcher speaks at 1.0 only (build it with speeds for per-request speeds)")
-        stretched = plan is not None and not self.ts.plans[plan].identity
-        lvl = None
-        if self.lv is not None:
-            from . import level
-
-            g_db, p_db = level.check(gain_db, peak_dbfs)
-            if g_db is not None:
-                lvl = (self.pipe.level_plan(rate, speed), g_db, p_db)
-        elif gain_db is not None or peak_dbfs is not None:
-            raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
-        n_out = pre = 0
-        if self.lagging:
-            n_out = self.ts.plans[plan].n_out if self.ts is not None else (
-                self.rs.out_n(rate) if self.rs is not None else self.eng.frame_samples)
-            pre = (self.ts.plans[plan].preroll if self.ts is not None else 0) + (self.lv.plans[lvl[0]].LA if lvl else 0)
+        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -354,16 +308,16 @@ class ContinuousBatcher:
         t_voice = _state_current_end(model_state)
         jobs = []
         with self._lock:
-            req = Request(self._next_id, self.rs.rates[rate] if self.rs is not None else self.native_rate)
+            req = Request(self._next_id, route.rate)
             self._next_id += 1
         for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
             fae = frames_after_eos if frames_after_eos is not None else (
                 m.model_recommended_frames_after_eos if m.model_recommended_frames_after_eos is not None else guess + 2)
-            if stretched and fae < 1:
+            if route.stretched and fae < 1:
                 raise ValueError("a request with a speed needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")
-            if lvl is not None and fae < 1:
+            if route.level is not None and fae < 1:
                 raise ValueError("a request with a gain needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")
             ids = m.tokenizer.encode(chunk)
@@ -372,7 +326,7 @@ class ContinuousBatcher:
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp, lsd, None if seed is None else chunk_seed(seed, i), rate, plan, lvl, n_out, pre))
+                             samp, lsd, None if seed is None else chunk_seed(seed, i), route))
         req._pending_chunks = len(jobs)
         with self._wake:
             if self._failed is not None or self._closed:
@@ -467,12 +421,7 @@ class ContinuousBatcher:
         for job, b in zip(jobs, rows):
             # the slot's codec carries: zero on the codec stream, behind the frames already queued there
             self.ms.reset_row(b, self.pipe.s2)
-            if self.rs is not None:  # the row's output rate and a zero filter history, on the same stream
-                self.rs.set_row(b, job.rate, self.pipe.s2)
-            if self.ts is not None:  # the row's plan and a zero stretch state, not draining
-                self.ts.set_row(b, job.plan, self.pipe.s2)
-            if self.lv is not None:  # the row's gain and ceiling (or bypass) and a zero limiter state, not draining
-                self.lv.set_row(b, *(job.lvl or (None, None, None)), self.pipe.s2)
+            self.chain.set_row(b, job.route, self.pipe.s2)  # the row's route and a zero state in every stage, same stream
             if self.lagging:
                 self.a_pos[b], self.row_drain[b], self.a_release[b] = 0, False, -1
             job.start = self.g
@@ -512,7 +461,7 @@ class ContinuousBatcher:
         pcm = torch.from_numpy(ring.numpy().copy())
         for b in held:  # jobs that have ended and flush their chain's tail: this is one of their drain frames
             job = self.slot[b]
-            self._deliver_stretched(b, job, pcm[b])
+            self._deliver(b, job, pcm[b])
             if frame >= self.a_release[b]:
                 self.a_release[b] = -1
                 self.slot[b] = None
@@ -521,36 +470,33 @@ class ContinuousBatcher:
             job = self.slot[b]
             if self.a_emit[b] < 0:
                 if self.lagging:
-                    self._deliver_stretched(b, job, pcm[b])
+                    self._deliver(b, job, pcm[b])
                 else:
-                    job.req._q.put(pcm[b] if self.rs is None else pcm[b, :self.rs.out_n(job.rate)])
+                    job.req._q.put(pcm[b] if self.rs is None else pcm[b, :job.route.n_out])
                 job.req.frames += 1
                 continue
             if self.a_eos[b] < 0:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
             self.st.set_row_active(int(b), False)
-            drain = -(-job.pre // job.n_out) if self.lagging else 0
+            drain = job.route.drain_frames
             if drain:
                 # `frame` is the first one past the job's end and, by _drain_due, the first one its row saw as zeros
                 if not self.row_drain[b]:
                     raise RuntimeError("a row whose output chain lags ended before it was set to drain")
-                self._deliver_stretched(b, job, pcm[b])
+                self._deliver(b, job, pcm[b])
                 if drain > 1:
                     self.a_release[b] = frame + drain - 1
                     continue
             self.slot[b] = None
             self._finish(job)
 
-    def _deliver_stretched(self, b, job, line):
-        """routes the part of a frame of slot `b` that belongs to its job: everything behind the pre-roll of the row's
-        output chain, up to frames * n_out samples in all once the job's frame count is known"""
-        n_out, pre = job.n_out, job.pre
+    def _deliver(self, b, job, line):
+        """routes the part of a frame of slot `b` that belongs to its job (`Route.take`)"""
         pos = int(self.a_pos[b])
-        lo = max(pre - pos, 0)
-        hi = n_out if self.a_emit[b] < 0 else min(n_out, pre + int(self.a_emit[b]) * n_out - pos)
+        lo, hi = job.route.take(pos, None if self.a_emit[b] < 0 else int(self.a_emit[b]))
         if hi > lo:
             job.req._q.put(line[lo:hi])
-        self.a_pos[b] = pos + n_out
+        self.a_pos[b] = pos + job.route.n_out
 
     def _drain_due(self):
         """Before codec frame g is queued: every row whose output chain lags (a stretch, a level, or both) and whose job
@@ -561,7 +507,7 @@ class ContinuousBatcher:
         the frames concerned), which a row without a speed never needs."""
         for b in range(self.B):
             job = self.slot[b]
-            if job is None or self.row_drain[b] or job.pre == 0:
+            if job is None or self.row_drain[b] or job.route.preroll == 0:
                 continue
             start, gen, fae = int(self.a_start[b]), int(self.a_gen[b]), int(self.a_fae[b])
             local = self.g - start
@@ -581,10 +527,7 @@ class ContinuousBatcher:
                     continue
                 break
             if end is not None and local >= end and self.slot[b] is job:
-                if self.ts is not None and not self.ts.plans[job.plan].identity:
-                    self.ts.set_row_drain(b, True, self.pipe.s2)
-                else:
-                    self.lv.set_row_drain(b, True, self.pipe.s2)
+                self.chain.drain_row(b, job.route, self.pipe.s2)
                 self.row_drain[b] = True
 
     def _finish(self, job):

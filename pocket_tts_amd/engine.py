@@ -269,18 +269,73 @@ class MimiState:
             pass
 
 
-class Stretcher:
+class _Stage:
+    """What the output stages share.  A subclass names itself (`_name`, in error texts) and its C ABI destroy function
+    (`_destroy`), gives the widths of its lines (`_in_width`, `_out_width`) and, in `_row_args(row)`, what `set_row` last
+    dealt the row according to its host mirror."""
+
+    _name = _destroy = None
+
+    def __init__(self, engine: "Engine", batch: int):
+        self.engine, self.batch = engine, batch
+        self.handle = None
+
+    def _sp(self, stream):
+        return self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
+
+    def reset(self, stream: torch.cuda.Stream | None = None):
+        """every row's state back to zero (new utterances); the rows keep what `set_row` dealt them"""
+        for b in range(self.batch):
+            self.set_row(b, *self._row_args(b), stream)
+
+    def _check_out(self, out):
+        shape = [self.batch, self._out_width]
+        if out is None or out.dtype not in (torch.float32, torch.int16) or list(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"{self._name} output: expected a contiguous float32 or int16 {shape} tensor")
+
+    def _check_in(self, x):
+        dev, shape = self.engine.device, [self.batch, self._in_width]
+        if x is None or x.device != dev or x.dtype != torch.float32 or list(x.shape) != shape or not x.is_contiguous():
+            raise ValueError(f"{self._name} input: expected a contiguous float32 {shape} tensor on {dev}")
+
+    def _frame(self, fn, x, out, stream, *extra):
+        """`fn(handle, x, out, is_i16, *extra, stream)` on `stream`, or on the engine's stream ordered against torch's
+        current one"""
+        e = self.engine
+        if stream is None:
+            e._pre()
+        _lib.check(fn(self.handle, _ptr(x), _ptr(out), int(out.dtype == torch.int16), *map(_ptr, extra), self._sp(stream)))
+        if stream is None:
+            for t in (x, out, *extra):
+                if t is not None and t.is_cuda:
+                    t.record_stream(e.stream)
+            e._post()
+
+    def close(self):
+        if self.handle is not None:
+            getattr(self.engine.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Stretcher(_Stage):
     """Speaking rates of `batch` sequences (include/ptts.h: ptts_stretcher; contract and plan rule: `stretch.py`).
     `plans` is a list of `stretch.StretchPlan`; a row is dealt a plan by its index (`set_row`) and starts on plan 0.
     `frame(x, out)` turns one frame x[b, :n_in(plan of b)] into out[b, :n_out(plan of b)]; `set_row_drain` makes a row's
     incoming frames count as zeros, which flushes its tail."""
 
+    _name, _destroy = "stretcher", "ptts_stretcher_destroy"
+
     def __init__(self, engine: "Engine", batch: int, plans):
-        self.engine, self.batch = engine, batch
-        self.handle = None
+        super().__init__(engine, batch)
         self.plans = list(plans)
-        self.in_max = max(p.n_in for p in self.plans)
-        self.out_max = max(p.n_out for p in self.plans)
+        self.in_max = self._in_width = max(p.n_in for p in self.plans)
+        self.out_max = self._out_width = max(p.n_out for p in self.plans)
         self.k_max = max([p.K for p in self.plans if not p.identity], default=1)
         self.row_plan = [0] * batch  # host mirror of the rows' plan indices
         n = len(self.plans)
@@ -296,8 +351,8 @@ class Stretcher:
         """output samples per frame on `plans[plan_index]`"""
         return self.plans[plan_index].n_out
 
-    def _sp(self, stream):
-        return self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
+    def _row_args(self, row):
+        return (self.row_plan[row],)
 
     def set_row(self, row: int, plan_index: int, stream: torch.cuda.Stream | None = None):
         """a new sequence joins `row` on `plans[plan_index]` with a zero state, not draining; stream-ordered"""
@@ -307,22 +362,6 @@ class Stretcher:
     def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
         """from now on (stream-ordered) the row's incoming frames count as zeros"""
         _lib.check(self.engine.lib.ptts_stretcher_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
-
-    def reset(self, stream: torch.cuda.Stream | None = None):
-        """every row's state back to zero (new utterances); the rows keep their plans"""
-        for b in range(self.batch):
-            self.set_row(b, self.row_plan[b], stream)
-
-    def _check_out(self, out):
-        if out is None or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (self.batch, self.out_max) \
-                or not out.is_contiguous():
-            raise ValueError(f"stretcher output: expected a contiguous float32 or int16 [{self.batch}, {self.out_max}] tensor")
-
-    def _check_in(self, x):
-        e = self.engine
-        if x is None or x.device != e.device or x.dtype != torch.float32 or tuple(x.shape) != (self.batch, self.in_max) \
-                or not x.is_contiguous():
-            raise ValueError(f"stretcher input: expected a contiguous float32 [{self.batch}, {self.in_max}] tensor on {e.device}")
 
     def frame(self, x: torch.Tensor, out: torch.Tensor, delta: torch.Tensor | None = None,
               stream: torch.cuda.Stream | None = None):
@@ -334,40 +373,22 @@ class Stretcher:
         if delta is not None and (delta.device != e.device or delta.dtype != torch.int32 or not delta.is_contiguous()
                                   or tuple(delta.shape) != (self.batch, self.k_max)):
             raise ValueError(f"stretcher deltas: expected a contiguous int32 [{self.batch}, {self.k_max}] tensor on {e.device}")
-        if stream is None:
-            e._pre()
-        _lib.check(e.lib.ptts_stretch_frame(self.handle, _ptr(x), _ptr(out), int(out.dtype == torch.int16),
-                                            _ptr(delta) if delta is not None else None, self._sp(stream)))
-        if stream is None:
-            for t in (x, out, delta):
-                if t is not None and t.is_cuda:
-                    t.record_stream(e.stream)
-            e._post()
-
-    def close(self):
-        if self.handle is not None:
-            self.engine.lib.ptts_stretcher_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._frame(e.lib.ptts_stretch_frame, x, out, stream, delta)
 
 
-class Leveler:
+class Leveler(_Stage):
     """Output levels of `batch` sequences (include/ptts.h: ptts_leveler; contract and plan rule: `level.py`).  `plans` is a
     list of `level.LevelPlan`; a row is dealt a plan by its index together with its gain and ceiling in dB (`set_row`;
     `gain_db` None: bypass) and starts on bypass.  `frame(x, out)` turns one frame x[b, :n(plan of b)] into
     out[b, :n(plan of b)], LA samples late; `set_row_drain` makes a row's incoming frames count as zeros, which flushes its
     tail.  A bypass row's whole line is copied."""
 
+    _name, _destroy = "leveler", "ptts_leveler_destroy"
+
     def __init__(self, engine: "Engine", batch: int, plans):
-        self.engine, self.batch = engine, batch
-        self.handle = None
+        super().__init__(engine, batch)
         self.plans = list(plans)
-        self.width = max(p.n for p in self.plans)
+        self.width = self._in_width = self._out_width = max(p.n for p in self.plans)
         self.rows = [(-1, None, None)] * batch  # host mirror: (plan index, gain_db, peak_dbfs) of each row
         n = len(self.plans)
         ints = (C.c_int32 * (4 * n))(*[v for p in self.plans for v in p.ints()])
@@ -376,8 +397,8 @@ class Leveler:
         self.handle = h
         engine._states.add(self)
 
-    def _sp(self, stream):
-        return self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
+    def _row_args(self, row):
+        return self.rows[row]
 
     def set_row(self, row: int, plan_index: int | None = None, gain_db=None, peak_dbfs=None,
                 stream: torch.cuda.Stream | None = None):
@@ -399,63 +420,30 @@ class Leveler:
         """from now on (stream-ordered) the row's incoming frames count as zeros"""
         _lib.check(self.engine.lib.ptts_leveler_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
 
-    def reset(self, stream: torch.cuda.Stream | None = None):
-        """every row's state back to zero (new utterances); the rows keep their plans, gains and ceilings"""
-        for b in range(self.batch):
-            idx, g, c = self.rows[b]
-            self.set_row(b, idx, g, c, stream)
-
-    def _check_out(self, out):
-        if out is None or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (self.batch, self.width) \
-                or not out.is_contiguous():
-            raise ValueError(f"leveler output: expected a contiguous float32 or int16 [{self.batch}, {self.width}] tensor")
-
-    def _check_in(self, x):
-        e = self.engine
-        if x is None or x.device != e.device or x.dtype != torch.float32 or tuple(x.shape) != (self.batch, self.width) \
-                or not x.is_contiguous():
-            raise ValueError(f"leveler input: expected a contiguous float32 [{self.batch}, {self.width}] tensor on {e.device}")
-
     def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """x f32[B, width] on the device -> out (float32 or int16 [B, width], device or pinned host)"""
-        e = self.engine
         self._check_in(x)
         self._check_out(out)
-        if stream is None:
-            e._pre()
-        _lib.check(e.lib.ptts_level_frame(self.handle, _ptr(x), _ptr(out), int(out.dtype == torch.int16), self._sp(stream)))
-        if stream is None:
-            for t in (x, out):
-                if t.is_cuda:
-                    t.record_stream(e.stream)
-            e._post()
-
-    def close(self):
-        if self.handle is not None:
-            self.engine.lib.ptts_leveler_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._frame(self.engine.lib.ptts_level_frame, x, out, stream)
 
 
-class Resampler:
+class Resampler(_Stage):
     """Output sample rates of `batch` sequences (include/ptts.h: ptts_resampler; filters and admission rules:
     `resample.py`).  `rates[0]` is always the codec's native rate - what a row without a rate of its own runs at - followed
     by `sample_rates`; a row is dealt a rate by its index (`index_of`).  `frame(pcm, out)` turns one codec frame into
-    `out[b, :out_n(rate of b)]`; each row carries 64 input samples from frame to frame, `set_row` zeroes them."""
+    `out[b, :out_n(rate of b)]`; each row carries 64 input samples from frame to frame, `set_row` zeroes them.  `plans`:
+    the `rate_plans` of an `output_chain.ChainTable` that has designed the rates' filters already."""
 
-    def __init__(self, engine: "Engine", batch: int, sample_rates):
-        from . import resample
+    _name, _destroy = "resampler", "ptts_resampler_destroy"
 
-        self.engine, self.batch = engine, batch
-        self.handle = None
-        self.plans = resample.plans(sample_rates, native=engine.sample_rate, frame_samples=engine.frame_samples)
+    def __init__(self, engine: "Engine", batch: int, sample_rates, plans=None):
+        from .output_chain import ChainTable
+
+        super().__init__(engine, batch)
+        self.plans = plans or ChainTable(engine.sample_rate, engine.frame_samples, sample_rates).rate_plans
         self.rates = [p.rate for p in self.plans]
-        self.out_max = max(p.out_n for p in self.plans)
+        self._in_width = engine.frame_samples
+        self.out_max = self._out_width = max(p.out_n for p in self.plans)
         self.row_rate = [0] * batch  # host mirror of the rows' rate indices
         n = len(self.plans)
         ints = [(C.c_int32 * n)(*[getattr(p, k) for p in self.plans]) for k in ("up", "down", "taps")]
@@ -468,59 +456,27 @@ class Resampler:
 
     def index_of(self, rate) -> int:
         """the rate's index (None: 0, the native rate); ValueError for a rate that is not configured"""
-        if rate is None:
-            return 0
-        if isinstance(rate, bool) or not isinstance(rate, numbers.Integral) or int(rate) not in self.rates:
-            raise ValueError(f"sample rate {rate!r} is not configured (this resampler has {self.rates})")
-        return self.rates.index(int(rate))
+        from .output_chain import rate_index
+
+        return rate_index(self.rates, rate)
 
     def out_n(self, rate_index: int) -> int:
         """output samples per frame at `rates[rate_index]`"""
         return self.plans[rate_index].out_n
 
+    def _row_args(self, row):
+        return (self.row_rate[row],)
+
     def set_row(self, row: int, rate_index: int, stream: torch.cuda.Stream | None = None):
         """a new sequence joins `row` at `rates[rate_index]` with a zero history; stream-ordered"""
-        sp = self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
-        _lib.check(self.engine.lib.ptts_resampler_set_row(self.handle, int(row), int(rate_index), sp))
+        _lib.check(self.engine.lib.ptts_resampler_set_row(self.handle, int(row), int(rate_index), self._sp(stream)))
         self.row_rate[row] = int(rate_index)
-
-    def reset(self, stream: torch.cuda.Stream | None = None):
-        """every row's history back to zero (new utterances); the rows keep their rates"""
-        for b in range(self.batch):
-            self.set_row(b, self.row_rate[b], stream)
-
-    def _check_out(self, out):
-        if out is None or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (self.batch, self.out_max) \
-                or not out.is_contiguous():
-            raise ValueError(f"resampler output: expected a contiguous float32 or int16 [{self.batch}, {self.out_max}] tensor")
 
     def frame(self, pcm: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """pcm f32[B, frame_samples] on the device -> out (float32 or int16 [B, out_max], device or pinned host)"""
-        e = self.engine
-        if pcm.device != e.device or pcm.dtype != torch.float32 or tuple(pcm.shape) != (self.batch, e.frame_samples) \
-                or not pcm.is_contiguous():
-            raise ValueError(f"resampler input: expected a contiguous float32 [{self.batch}, {e.frame_samples}] tensor on {e.device}")
+        self._check_in(pcm)
         self._check_out(out)
-        if stream is None:
-            e._pre()
-        sp = e._sp if stream is None else C.c_void_p(stream.cuda_stream)
-        _lib.check(e.lib.ptts_resample_frame(self.handle, _ptr(pcm), _ptr(out), int(out.dtype == torch.int16), sp))
-        if stream is None:
-            pcm.record_stream(e.stream)
-            if out.is_cuda:
-                out.record_stream(e.stream)
-            e._post()
-
-    def close(self):
-        if self.handle is not None:
-            self.engine.lib.ptts_resampler_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._frame(self.engine.lib.ptts_resample_frame, pcm, out, stream)
 
 
 class Engine:
@@ -1133,24 +1089,14 @@ class StepPipeline:
       critical path (on this stack such waits around graph launches cost ~80 us per step, and the branches
       of a forked graph do not run concurrently).
 
-    `sample_rates` (a list of output rates, `resample.py`; not in "fork" mode): the codec graphs end with the resampler's
-    two launches.  `pcm[p]` are then DEVICE tensors (the resampler reads the frame from device memory) and the samples
-    reach the host through `out[p]`, a pinned [B, out_max] ring, int16 with `pcm_i16`, else float32: `out_of(frame)[b,
-    :rs.out_n(rate index of b)]` is row b's frame; `pcm_of` / `pcm16_of` raise.  Rows get their rates with
-    `rs.set_row(row, rs.index_of(rate), s2)` (codec stream).  With None nothing changes: same buffers, same graph nodes.
-
-    `speeds` (a list of speaking rates, `stretch.py`; not in "fork" mode): the codec graphs end with the time-stretch
-    launch, behind the resampler if there is one.  The pipeline holds the plan table of (each rate it serves) x (each
-    speed) in `ts` (`engine.Stretcher`); `speed_plan(rate index, speed)` is the plan index of a pair, ValueError for a
-    speed that is not configured or not admissible at that rate.  The samples reach the host through `out[p]` as above,
-    row b's in its first `ts.n_out(plan index of b)` entries; rows get their plans with `ts.set_row(row, plan, s2)`.  A
-    speed must be admissible at one of the rates at least.  With None nothing changes.
-
-    `level` (True; not in "fork" mode): the codec graphs end with the leveler's launch (`level.py`), the last stage of the
-    chain codec -> resampler -> stretcher -> level.  The pipeline holds one plan per distinct (rate, samples per frame) its
-    rates x speeds can produce in `lv` (`engine.Leveler`); `level_plan(rate index, speed)` is the plan index of a pair.  The
-    samples reach the host through `out[p]`; rows get their gains with `lv.set_row(row, plan, gain_db, peak_dbfs, s2)` and
-    start on bypass.  With False nothing changes.
+    `sample_rates` (a list of output rates, `resample.py`), `speeds` (a list of speaking rates, `stretch.py`; each must be
+    admissible at one of the rates at least) and `level` (True: per-row gain and limiter, `level.py`) configure the output
+    chain codec -> resampler -> stretcher -> level (`output_chain.py`; not in "fork" mode): the codec graphs end with its
+    stages' launches.  `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts` and `lv`.
+    `pcm[p]` are then DEVICE tensors and the samples reach the host through `out[p]`, the chain's pinned ring, int16 with
+    `pcm_i16`, else float32: `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  A row gets
+    its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec stream); rows start on the
+    native rate, speed 1.0 and bypass.  With None / None / False nothing changes: same buffers, same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
@@ -1158,67 +1104,28 @@ class StepPipeline:
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
                  lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False):
+        from .output_chain import ChainTable, OutputChain
+
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
-        if sample_rates is not None and self.mode == "fork":
-            raise ValueError("sample_rates: not available in the 'fork' mode")
-        if speeds is not None and self.mode == "fork":
-            raise ValueError("speeds: not available in the 'fork' mode")
-        if level and self.mode == "fork":
-            raise ValueError("level: not available in the 'fork' mode")
-        self.ts, self.speeds, self.ts_index, self.mid = None, None, None, None
-        self.lv, self.lv_index, self.lv_mid = None, None, None
-        if speeds is not None:  # the plan table first: a speed no rate admits is refused before anything is allocated
-            from . import resample, stretch
-
-            self.speeds = stretch.normalise_speeds(speeds)
-            rates = [(p.rate, p.out_n) for p in resample.plans(sample_rates, eng.sample_rate, eng.frame_samples)] \
-                if sample_rates is not None else [(eng.sample_rate, eng.frame_samples)]
-            self.ts_rates = [r for r, _ in rates]
-            ts_plans, self.ts_index = stretch.table(rates, self.speeds)
-        self.rs = Resampler(eng, B, sample_rates) if sample_rates is not None else None
-        if level:  # likewise: a (rate, samples per frame) the plan rule refuses is refused before anything is allocated
-            from . import level as level_rule
-            from . import resample
-
-            if speeds is not None:
-                pairs = [(rates[r][0], ts_plans[i].n_out) for r, row in enumerate(self.ts_index) for i in row if i is not None]
-            elif sample_rates is not None:
-                pairs = [(p.rate, p.out_n) for p in resample.plans(sample_rates, eng.sample_rate, eng.frame_samples)]
-            else:
-                pairs = [(eng.sample_rate, eng.frame_samples)]
-            lv_plans, self.lv_index = level_rule.table(pairs)
-        if speeds is not None:
-            self.ts = Stretcher(eng, B, ts_plans)
-        if level:
-            self.lv = Leveler(eng, B, lv_plans)
+        # the plan table first: what the rules refuse is refused before anything is allocated
+        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level)
+        if not table.empty and self.mode == "fork":
+            raise ValueError("sample_rates / speeds / level: not available in the 'fork' mode")
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
         # read flag[t % nb] / pcm[t % nb] of step t - nb before it calls step() for step t.
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
+        self.chain = OutputChain(eng, B, table, nb, pcm_i16)
+        self.rs, self.ts, self.lv, self.out = self.chain.rs, self.chain.ts, self.chain.lv, self.chain.out
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host
-        if self.rs is None and self.ts is None and self.lv is None:
-            self.pcm = [torch.zeros(B, eng.frame_samples).pin_memory() for _ in range(nb)]
-            self.out = None
-        else:
-            last = self.ts if self.ts is not None else self.rs  # the last output stage writes the pinned ring
-            width = self.lv.width if self.lv is not None else last.out_max
-            self.pcm = [torch.zeros(B, eng.frame_samples, device=dev) for _ in range(nb)]
-            self.out = [torch.zeros(B, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
-                        for _ in range(nb)]
-            if self.lv is not None and last is not None:
-                # resampler / stretcher -> leveler: likewise one device buffer for every ring slot
-                if last.out_max != width:
-                    raise ValueError("level: the leveler's line is not the line of the stage before it")
-                self.lv_mid = torch.zeros(B, width, device=dev)
-            if self.ts is not None and self.rs is not None:
-                # resampler -> stretcher: one device buffer serves every ring slot (the codec graphs run one after the
-                # other on the codec stream)
-                self.mid = torch.zeros(B, self.rs.out_max, device=dev)
+        # without a chain the codec's last kernel writes pinned memory; with one, device memory the first stage reads
+        self.pcm = [torch.zeros(B, eng.frame_samples, device=dev) if self.out is not None else
+                    torch.zeros(B, eng.frame_samples).pin_memory() for _ in range(nb)]
         self.ev = [torch.cuda.Event() for _ in range(nb)]    # codec frame (f % nb) complete -> pcm_of(f) valid
         self.ev_lm = [torch.cuda.Event() for _ in range(nb)]  # FlowLM step (t % nb) complete -> flag valid
         self.s1 = lm_stream or eng.stream  # FlowLM stream (several pipelines of one engine may use their own)
@@ -1235,23 +1142,12 @@ class StepPipeline:
         self.g_last = []
         for p in range(nb):
             if self.out is not None:  # the 16-bit conversion happens behind the last output stage
-                end = self.out[p] if self.lv is None else self.lv_mid  # what the stage before the leveler writes
-                if self.rs is not None:
-                    mimi_state.set_resampler(self.rs, end if self.ts is None else self.mid)
-                if self.ts is not None:
-                    mimi_state.set_stretcher(self.ts, end, self.mid)
-                if self.lv is not None:
-                    mimi_state.set_leveler(self.lv, self.out[p], self.lv_mid)
+                self.chain.attach(mimi_state, p)
             else:
                 mimi_state.set_pcm_i16(self.pcm16[p] if pcm_i16 else None)
             self.g_last.append(eng.capture_mimi(mimi_state, self.lat[p], self.pcm[p]))
         mimi_state.set_pcm_i16(None)
-        if self.lv is not None:
-            mimi_state.set_leveler(None)
-        if self.ts is not None:
-            mimi_state.set_stretcher(None)
-        if self.rs is not None:
-            mimi_state.set_resampler(None)
+        self.chain.detach(mimi_state)
         self.g_both = []
         if self.mode == "fork":
             for p in range(nb):
@@ -1265,19 +1161,18 @@ class StepPipeline:
         self.t = 0          # FlowLM steps launched for the current utterances
         self.decoded = 0    # codec frames launched
 
-    def restart(self):
-        """new utterances: flush the pending frame, codec state back to zero carries"""
+    def restart(self, routes=None):
+        """new utterances: flush the pending frame, codec state back to zero carries.  `routes` (one `output_chain.Route`
+        per row): the rows join the output chain on these; None: they keep theirs"""
         self.flush()
         if self.mode != "fork":
             # zero carries on the CODEC stream: ordered behind the frames already queued there and ahead of the next
             # utterance's first frame, off the FlowLM stream's critical path (clone + prefill + first step)
             self.ms.reset(self.s2)
-            if self.rs is not None:
-                self.rs.reset(self.s2)
-            if self.ts is not None:
-                self.ts.reset(self.s2)
-            if self.lv is not None:
-                self.lv.reset(self.s2)
+            if routes is None:
+                self.chain.reset(self.s2)
+            for b, route in enumerate(routes or ()):
+                self.chain.set_row(b, route, self.s2)
         else:
             self.ms.reset()
         self.t = 0
@@ -1366,36 +1261,10 @@ class StepPipeline:
         return self.pcm[frame % self.nb]
 
     def out_of(self, frame: int) -> torch.Tensor:
-        """with `sample_rates` or `speeds`: host tensor [B, out_max] of `frame`, row b's samples in its first `rs.out_n(..)`
-        (with `speeds`: `ts.n_out(..)`) entries"""
+        """with an output chain: host tensor [B, widest line] of `frame`, row b's samples in its first `route.n_out` entries"""
         if self.out is None:
             raise RuntimeError("this pipeline has no sample_rates: read pcm_of(frame)")
         return self.out[frame % self.nb]
-
-    def speed_plan(self, rate_index: int, speed) -> int:
-        """index in `ts.plans` of (the rate at `rate_index` of this pipeline, `speed`); None is speed 1.0.  ValueError for
-        a speed that is not configured, or that the plan rule refuses at that rate (the message lists those it admits)"""
-        from . import stretch
-
-        f = 1.0 if speed is None else float(stretch.fraction(speed))
-        if f not in self.speeds:
-            raise ValueError(f"speed {speed!r} is not configured (this pipeline has {self.speeds})")
-        i = self.ts_index[rate_index][self.speeds.index(f)]
-        if i is None:
-            ok = [s for j, s in enumerate(self.speeds) if self.ts_index[rate_index][j] is not None]
-            raise ValueError(f"speed {speed!r} is not admissible at {self.ts_rates[rate_index]} Hz (admissible there: {ok})")
-        return i
-
-    def level_plan(self, rate_index: int = 0, speed=None) -> int:
-        """index in `lv.plans` of the plan of a row at the rate at `rate_index` of this pipeline and at `speed` (None: 1.0);
-        ValueError as `speed_plan` raises it"""
-        if self.ts is not None:
-            rate, n = self.ts_rates[rate_index], self.ts.plans[self.speed_plan(rate_index, speed)].n_out
-        elif self.rs is not None:
-            rate, n = self.rs.rates[rate_index], self.rs.out_n(rate_index)
-        else:
-            rate, n = self.eng.sample_rate, self.eng.frame_samples
-        return self.lv_index[(int(rate), int(n))]
 
     def done_event(self, frame: int):
         """event that fires when the codec decode of `frame` (PCM in `pcm_of(frame)`) is complete"""
@@ -1415,9 +1284,4 @@ class StepPipeline:
         self.sync()
         for g in self.g_first + self.g_last + self.g_both:
             self.eng.graph_destroy(g)
-        if self.lv is not None:
-            self.lv.close()
-        if self.ts is not None:
-            self.ts.close()
-        if self.rs is not None:
-            self.rs.close()
+        self.chain.close()

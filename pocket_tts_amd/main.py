@@ -211,54 +211,23 @@ def cli_app(argv=None) -> int:
                                 lsd_decode_steps=args.lsd_decode_steps, noise_clamp=args.noise_clamp,
                                 eos_threshold=args.eos_threshold, quantize=args.quantize, codec_bf16=args.codec_bf16,
                                 device=args.device)
-    if args.sample_rate is not None:
-        # generate_audio_stream is a generator and would refuse the rate only once write_wav_stream has opened the file
-        from . import resample
+    # generate_audio_stream is a generator and would refuse its arguments only once write_wav_stream has opened the file:
+    # check the rate, then the speed at that rate, then the level behind both, so the message names the flag at fault
+    from .output_chain import ChainTable
 
+    request = {}
+    for flag, names in (("--sample-rate", ("sample_rate",)), ("--speed", ("speed",)),
+                        ("--gain-db / --peak-dbfs", ("gain_db", "peak_dbfs"))):
+        request.update({k: getattr(args, k) for k in names})
         try:
-            resample.plan(args.sample_rate, int(model.sample_rate), model.engine.frame_samples)
+            ChainTable.single(int(model.sample_rate), model.engine.frame_samples, **request)
         except ValueError as e:
-            logger.error("--sample-rate: %s", e)
-            return 1
-    if args.speed is not None:
-        # likewise: refuse the speed before the output file is opened
-        from . import resample, stretch
-
-        try:
-            native, fs = int(model.sample_rate), model.engine.frame_samples
-            rate = args.sample_rate or native
-            if float(stretch.fraction(args.speed)) != 1.0:
-                stretch.plan(args.speed, rate, resample.plan(rate, native, fs).out_n)
-        except ValueError as e:
-            logger.error("--speed: %s", e)
-            return 1
-    if args.gain_db is not None or args.peak_dbfs is not None:
-        # likewise: refuse the level before the output file is opened
-        from . import level, resample, stretch
-
-        try:
-            level.check(args.gain_db, args.peak_dbfs)
-            native, fs = int(model.sample_rate), model.engine.frame_samples
-            rate = args.sample_rate or native
-            n = resample.plan(rate, native, fs).out_n
-            if args.speed is not None and float(stretch.fraction(args.speed)) != 1.0:
-                n = stretch.plan(args.speed, rate, n).n_out
-            level.plan(rate, n)
-        except ValueError as e:
-            logger.error("--gain-db / --peak-dbfs: %s", e)
+            logger.error("%s: %s", flag, e)
             return 1
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
-    if args.gain_db is not None:
-        chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                             seed=args.seed, sample_rate=args.sample_rate, speed=args.speed,
-                                             gain_db=args.gain_db, peak_dbfs=args.peak_dbfs)
-    elif args.speed is None:
-        chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                             seed=args.seed, sample_rate=args.sample_rate)
-    else:
-        chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                             seed=args.seed, sample_rate=args.sample_rate, speed=args.speed)
+    chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
+                                         seed=args.seed, **request)
     write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)

@@ -1,0 +1,222 @@
+"""The output chain codec -> resampler -> stretcher -> level as one object: what a pipeline's stages are (`ChainTable`), what
+a request's row does in them (`Route`), and the stage objects and buffers on the device (`OutputChain`).
+
+The first half is pure Python over the rule modules `resample.py`, `stretch.py` and `level.py`: it needs no library, no
+GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
+yields, how many leading samples to drop, how many drain frames flush its tail and which stage's drain flag to raise - is a
+`Route`; nothing outside this module composes the three plan rules.
+
+The drain rule: a row's pre-roll is the SUM of its stages' pre-rolls (the stretcher's, 0 on an identity plan, plus the
+leveler's look-ahead, 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
+ceil(preroll / n_out) further frames, which it reads as zeros, to get there - a count of the sum, not of any one stage.  The
+zeros enter at the first lagging stage: through the stretcher's flag where the row is stretched (what the stretcher emits
+past its tail is zero, which is what the leveler behind it then reads), else through the leveler's.
+"""
+
+from __future__ import annotations
+
+import numbers
+from dataclasses import dataclass
+
+from . import level as level_rule
+from . import resample, stretch
+
+
+def rate_index(rates, rate) -> int:
+    """index of `rate` in `rates` (None: 0, the native rate); ValueError for a rate that is not configured"""
+    if rate is None:
+        return 0
+    if isinstance(rate, bool) or not isinstance(rate, numbers.Integral) or int(rate) not in rates:
+        raise ValueError(f"sample rate {rate!r} is not configured (this resampler has {rates})")
+    return rates.index(int(rate))
+
+
+@dataclass(frozen=True)
+class Route:
+    """One row's way through the chain.  `rate_index`, `rate`: the row's output rate; `stretch_plan`: its plan index in
+    the stretcher (None without one), `stretched`: that plan is no identity plan; `level`: (plan index in the leveler,
+    gain_db, peak_dbfs), None for bypass; `n_out`: samples its frame yields at the end of the chain; `preroll`, `drain_frames`,
+    `drain_stage` ("stretch", "level" or None): the drain rule of the module's docstring."""
+
+    rate_index: int
+    rate: int
+    stretch_plan: int | None
+    stretched: bool
+    level: tuple | None
+    n_out: int
+    preroll: int
+    drain_frames: int
+    drain_stage: str | None
+
+    def take(self, pos: int, frames: int | None):
+        """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
+        read in order, `n_out` each) and consists of `frames` frames (None: not known yet) - everything behind the
+        pre-roll, up to frames * n_out samples in all"""
+        lo = min(max(self.preroll - pos, 0), self.n_out)
+        hi = self.n_out if frames is None else min(self.n_out, self.preroll + frames * self.n_out - pos)
+        return lo, max(hi, lo)
+
+
+class ChainTable:
+    """The plans of a pipeline's stages, built once: `rate_plans` (`resample.plans`: the native rate first), and with
+    `speeds` the stretcher's `stretch_plans` / `stretch_index[rate index][speed index]` (`stretch.table`), with `level`
+    the leveler's `level_plans` / `level_index[(rate, n)]` (`level.table` over every (rate, samples per frame) the rates x
+    speeds can produce).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
+    speed or line the rules refuse raises their ValueError here, before anything is allocated.  `sample_rates` / `speeds`
+    None and `level` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none)."""
+
+    def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False):
+        self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
+        self.has_rates = sample_rates is not None
+        self.sample_rates = list(sample_rates) if self.has_rates else None
+        self.speeds = None if speeds is None else stretch.normalise_speeds(speeds)
+        self.rate_plans = resample.plans(self.sample_rates or (), self.native_rate, self.frame_samples)
+        self.rates = [p.rate for p in self.rate_plans]
+        lines = [(p.rate, p.out_n) for p in self.rate_plans]
+        self.stretch_plans = self.stretch_index = self.level_plans = self.level_index = None
+        if self.speeds is not None:
+            self.stretch_plans, self.stretch_index = stretch.table(lines, self.speeds)
+            lines = [(self.rates[r], self.stretch_plans[i].n_out) for r, row in enumerate(self.stretch_index)
+                     for i in row if i is not None]
+        if level:
+            self.level_plans, self.level_index = level_rule.table(lines)
+
+    @property
+    def empty(self) -> bool:
+        return not self.has_rates and self.speeds is None and self.level_plans is None
+
+    def speeds_of(self) -> dict:
+        """{rate: [the configured speeds admissible at that rate, 1.0 first]}"""
+        return {rate: [s for j, s in enumerate(self.speeds) if self.stretch_index[r][j] is not None]
+                for r, rate in enumerate(self.rates)}
+
+    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None) -> Route:
+        """The `Route` of a request; None is the native rate, speed 1.0, no gain.  ValueError for a rate or speed that is
+        not configured, a speed the plan rule refuses at the request's rate (the message lists those it admits), a level
+        `level.check` refuses, and for any of them on a table without that stage."""
+        r = 0
+        if self.has_rates:
+            r = rate_index(self.rates, sample_rate)
+        elif sample_rate is not None and (isinstance(sample_rate, bool) or sample_rate != self.native_rate):
+            raise ValueError(f"sample rate {sample_rate!r}: this batcher writes {self.native_rate} Hz only (build it "
+                             "with sample_rates for per-request rates)")
+        rate, n_out, plan, preroll = self.rates[r], self.rate_plans[r].out_n, None, 0
+        if self.speeds is not None:
+            f = 1.0 if speed is None else float(stretch.fraction(speed))
+            if f not in self.speeds:
+                raise ValueError(f"speed {speed!r} is not configured (this pipeline has {self.speeds})")
+            plan = self.stretch_index[r][self.speeds.index(f)]
+            if plan is None:
+                raise ValueError(f"speed {speed!r} is not admissible at {rate} Hz (admissible there: {self.speeds_of()[rate]})")
+            n_out, preroll = self.stretch_plans[plan].n_out, self.stretch_plans[plan].preroll
+        elif speed is not None and (isinstance(speed, bool) or not isinstance(speed, numbers.Real) or speed != 1.0):
+            raise ValueError(f"speed {speed!r}: this batcher speaks at 1.0 only (build it with speeds for per-request speeds)")
+        stretched = plan is not None and not self.stretch_plans[plan].identity
+        lvl = None
+        if self.level_plans is not None:
+            g_db, p_db = level_rule.check(gain_db, peak_dbfs)
+            if g_db is not None:
+                lvl = (self.level_index[(rate, n_out)], g_db, p_db)
+                preroll += self.level_plans[lvl[0]].LA
+        elif gain_db is not None or peak_dbfs is not None:
+            raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
+        return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
+                     "stretch" if stretched else "level" if lvl is not None else None)
+
+    @staticmethod
+    def single(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None):
+        """One request that gets a chain of its own: (sample_rate, speed, gain_db, peak_dbfs) with the native rate, speed
+        1.0 and no gain as None, the speed as the float of its fraction and peak_dbfs defaulted - what a `ChainTable` of
+        exactly these stages is built from and routes.  ValueError with the message of the rule that refuses."""
+        native = int(native_rate)
+        n = int(frame_samples)
+        if sample_rate is not None:
+            p = resample.plan(sample_rate, native, frame_samples)
+            sample_rate, n = (None if p.rate == native else p.rate), p.out_n
+        if speed is not None:
+            speed = float(stretch.fraction(speed))
+            if speed == 1.0:
+                speed = None
+            else:
+                n = stretch.plan(speed, sample_rate or native, n).n_out
+        gain_db, peak_dbfs = level_rule.check(gain_db, peak_dbfs)
+        if gain_db is not None:
+            level_rule.plan(sample_rate or native, n)
+        return sample_rate, speed, gain_db, peak_dbfs
+
+
+class OutputChain:
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `lv` (`engine.Resampler`, `Stretcher`,
+    `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
+    [batch, widest line] tensors, int16 with `pcm_i16`, else float32, which the last stage writes.  An empty table creates
+    nothing: `out` is None and the codec writes its PCM as without a chain."""
+
+    def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
+        import torch
+
+        from .engine import Leveler, Resampler, Stretcher
+
+        self.table = table
+        self.rs = Resampler(engine, batch, table.sample_rates, table.rate_plans) if table.has_rates else None
+        self.ts = Stretcher(engine, batch, table.stretch_plans) if table.speeds is not None else None
+        self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
+        self.out = self.rs_out = self.lv_in = None
+        if table.empty:
+            return
+        last = self.ts if self.ts is not None else self.rs  # the stage before the leveler, if any
+        width = self.lv.width if self.lv is not None else last.out_max
+        self.out = [torch.zeros(batch, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory() for _ in range(nb)]
+        # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
+        if self.lv is not None and last is not None:
+            if last.out_max != width:
+                raise ValueError("level: the leveler's line is not the line of the stage before it")
+            self.lv_in = torch.zeros(batch, width, device=engine.device)
+        if self.ts is not None and self.rs is not None:
+            self.rs_out = torch.zeros(batch, self.rs.out_max, device=engine.device)
+
+    def stages(self):
+        return [s for s in (self.rs, self.ts, self.lv) if s is not None]
+
+    def attach(self, mimi_state, p: int):
+        """the decodes / graph captures of `mimi_state` issued after this call end with the chain's launches and write
+        ring slot `p` (the frame's PCM must then be a device tensor)"""
+        end = self.out[p] if self.lv is None else self.lv_in  # what the stage before the leveler writes
+        if self.rs is not None:
+            mimi_state.set_resampler(self.rs, end if self.ts is None else self.rs_out)
+        if self.ts is not None:
+            mimi_state.set_stretcher(self.ts, end, self.rs_out)
+        if self.lv is not None:
+            mimi_state.set_leveler(self.lv, self.out[p], self.lv_in)
+
+    def detach(self, mimi_state):
+        if self.lv is not None:
+            mimi_state.set_leveler(None)
+        if self.ts is not None:
+            mimi_state.set_stretcher(None)
+        if self.rs is not None:
+            mimi_state.set_resampler(None)
+
+    def reset(self, stream=None):
+        """every row's state back to zero in every stage (new utterances); the rows keep their routes"""
+        for s in self.stages():
+            s.reset(stream)
+
+    def set_row(self, row: int, route: Route, stream=None):
+        """a new sequence joins `row` on `route` with a zero state in every stage, not draining; a stage the route does not
+        use runs its identity plan or bypass.  Stream-ordered"""
+        if self.rs is not None:
+            self.rs.set_row(row, route.rate_index, stream)
+        if self.ts is not None:
+            self.ts.set_row(row, route.stretch_plan, stream)
+        if self.lv is not None:
+            self.lv.set_row(row, *(route.level or (None, None, None)), stream)
+
+    def drain_row(self, row: int, route: Route, stream=None):
+        """from now on (stream-ordered) the row's incoming frames count as zeros at the stage `route.drain_stage` names"""
+        stage = {"stretch": self.ts, "level": self.lv, None: None}[route.drain_stage]
+        if stage is not None:
+            stage.set_row_drain(row, True, stream)
+
+    def close(self):
+        for s in reversed(self.stages()):
+            s.close()

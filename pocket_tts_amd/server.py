@@ -175,12 +175,9 @@ def parse_sample_rate(fields: dict, native: int, sample_rates) -> int | None:
 def speed_table(speeds, native: int, sample_rates, frame_samples: int = 1920) -> dict:
     """{rate: [speeds admissible at that rate, 1.0 first]} for the native rate and every configured rate; ValueError for a
     speed that is no fraction in range, or that the plan rule admits at none of the rates"""
-    from . import resample, stretch
+    from .output_chain import ChainTable
 
-    rates = [(p.rate, p.out_n) for p in resample.plans(sample_rates or (), int(native), frame_samples)]
-    speeds = stretch.normalise_speeds(speeds)
-    _, index = stretch.table(rates, speeds)
-    return {rate: [s for j, s in enumerate(speeds) if index[i][j] is not None] for i, (rate, _) in enumerate(rates)}
+    return ChainTable(native, frame_samples, sample_rates, speeds).speeds_of()
 
 
 def parse_speed(fields: dict, rate: int, table: dict | None) -> float | None:
@@ -247,17 +244,16 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     (False: a request that sends either gets a 400, and the batcher's graphs are those of before).  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
-    if sample_rates is not None:
-        from . import resample
-
-        sample_rates = [int(r) for r in sample_rates]
-        for r in sample_rates:  # ValueError at start-up, not at the first request
-            resample.plan(r, int(model.sample_rate))
+    from .output_chain import ChainTable
 
     speeds_of = None
+    if sample_rates is not None:
+        sample_rates = [int(r) for r in sample_rates]
+        ChainTable(model.sample_rate, 1920, sample_rates)  # ValueError at start-up, not at the first request (1920: the
+        # codec's frame, as `resample.plan` assumes it by default)
     if speeds is not None:
         speeds = [float(v) for v in speeds]
-        speeds_of = speed_table(speeds, int(model.sample_rate), sample_rates, model.engine.frame_samples)
+        speeds_of = speed_table(speeds, model.sample_rate, sample_rates, model.engine.frame_samples)
 
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
@@ -268,16 +264,8 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         reserve = max_lsd if max_lsd != own_lsd else None
 
         def batcher_factory(model, slots, capacity):
-            if level:
-                return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
-                                         sample_rates=sample_rates, speeds=speeds, level=True)
-            if speeds is not None:
-                return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
-                                         sample_rates=sample_rates, speeds=speeds)
-            if sample_rates is None:
-                return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve)
             return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
-                                     sample_rates=sample_rates)
+                                     sample_rates=sample_rates, speeds=speeds, level=level)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits

@@ -196,10 +196,6 @@ class TTSModel:
                        seed: int | None = None) -> torch.Tensor:
         """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db` and `peak_dbfs` (not in the reference): see
         `generate_audio_stream`."""
-        if gain_db is None and peak_dbfs is None:
-            chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
-                                                     seed=seed, sample_rate=sample_rate, speed=speed))
-            return torch.cat(chunks, dim=0)
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
                                                  seed=seed, sample_rate=sample_rate, speed=speed, gain_db=gain_db,
                                                  peak_dbfs=peak_dbfs))
@@ -234,35 +230,11 @@ class TTSModel:
         from torch's global CPU generator, as in the reference."""
         if seed is not None:
             seed = check_seed(seed)
-        if sample_rate is not None:
-            from . import resample
+        from .output_chain import ChainTable
 
-            native = int(self.config.mimi.sample_rate)
-            sample_rate = resample.plan(sample_rate, native, self.engine.frame_samples).rate  # ValueError names the rule
-            if sample_rate == native:
-                sample_rate = None
-        if speed is not None:
-            from . import resample, stretch
-
-            native = int(self.config.mimi.sample_rate)
-            n_in = self.engine.frame_samples if sample_rate is None else \
-                resample.plan(sample_rate, native, self.engine.frame_samples).out_n
-            speed = float(stretch.fraction(speed))
-            if speed == 1.0:
-                speed = None
-            else:
-                stretch.plan(speed, sample_rate or native, n_in)  # ValueError names the rule
-        lvl = None
-        if gain_db is not None or peak_dbfs is not None:
-            from . import level, resample, stretch
-
-            lvl = level.check(gain_db, peak_dbfs)  # ValueError names the rule
-            native = int(self.config.mimi.sample_rate)
-            n = self.engine.frame_samples if sample_rate is None else \
-                resample.plan(sample_rate, native, self.engine.frame_samples).out_n
-            if speed is not None:
-                n = stretch.plan(speed, sample_rate or native, n).n_out
-            level.plan(sample_rate or native, n)
+        # the native rate, speed 1.0 and no gain become None: the call of before.  ValueError names the rule
+        request = ChainTable.single(int(self.config.mimi.sample_rate), self.engine.frame_samples, sample_rate, speed, gain_db,
+                                    peak_dbfs)
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
@@ -272,7 +244,7 @@ class TTSModel:
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
-                                                              None if seed is None else chunk_seed(seed, i), sample_rate, speed, lvl)
+                                                              None if seed is None else chunk_seed(seed, i), *request)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -511,7 +483,7 @@ class TTSModel:
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
                                           row_seed: int | None = None, sample_rate: int | None = None,
-                                          speed: float | None = None, lvl=None):
+                                          speed: float | None = None, gain_db=None, peak_dbfs=None):
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -529,7 +501,7 @@ class TTSModel:
             key = (*key, "rate", sample_rate)
         if speed is not None:  # likewise: its codec graphs end with the time-stretch
             key = (*key, "speed", speed)
-        if lvl is not None:  # likewise: its codec graphs end with the leveler (one context serves every gain and ceiling)
+        if gain_db is not None:  # likewise: its codec graphs end with the leveler (one context serves every gain and ceiling)
             key = (*key, "level")
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
@@ -538,33 +510,11 @@ class TTSModel:
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
-            if lvl is not None:
+            if sample_rate is not None or speed is not None or gain_db is not None:  # a context with an output chain
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
-                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
-                                    sample_rates=None if sample_rate is None else [sample_rate],
-                                    speeds=None if speed is None else [speed], level=True)
-                r = 0
-                if sample_rate is not None:
-                    r = pipe.rs.index_of(sample_rate)
-                    pipe.rs.set_row(0, r, pipe.s2)
-                if speed is not None:
-                    pipe.ts.set_row(0, pipe.speed_plan(r, speed), pipe.s2)
-            elif sample_rate is None and speed is None:
-                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync")
-            elif speed is not None:
-                self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
-                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
-                                    sample_rates=None if sample_rate is None else [sample_rate], speeds=[speed])
-                r = 0
-                if sample_rate is not None:
-                    r = pipe.rs.index_of(sample_rate)
-                    pipe.rs.set_row(0, r, pipe.s2)
-                pipe.ts.set_row(0, pipe.speed_plan(r, speed), pipe.s2)  # restart() below zeroes its state per chunk
-            else:
-                self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
-                pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
-                                    sample_rates=[sample_rate])
-                pipe.rs.set_row(0, pipe.rs.index_of(sample_rate), pipe.s2)  # restart() below zeroes its history per chunk
+            pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
+                                sample_rates=None if sample_rate is None else [sample_rate],
+                                speeds=None if speed is None else [speed], level=gain_db is not None)
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
         noise_host = ctx["noise_host"]
@@ -574,10 +524,9 @@ class TTSModel:
         pipe.flush()
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
-        pipe.restart()
-        if lvl is not None:  # the row's gain and ceiling, with a zero limiter state, behind the restart on the codec stream
-            r = 0 if sample_rate is None else pipe.rs.index_of(sample_rate)
-            pipe.lv.set_row(0, pipe.level_plan(r, speed), lvl[0], lvl[1], pipe.s2)
+        # the codec's carries and the row's rate, plan, gain and ceiling with a zero state in every stage, on the codec stream
+        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs)
+        pipe.restart([route])
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
             # state's own temperature is frozen into the captured step
@@ -593,32 +542,16 @@ class TTSModel:
             emitted = 0    # frames handed to the codec
             yielded = 0    # frames handed to the caller
 
-            out_n = None if sample_rate is None else pipe.rs.out_n(pipe.rs.index_of(sample_rate))
-            plan = None if speed is None else pipe.ts.plans[pipe.ts.row_plan[0]]
-            if plan is not None:
-                out_n = plan.n_out
-            # a row whose output chain lags: its pre-roll is the stretcher's (0 without one) plus the leveler's look-ahead
-            preroll = plan.preroll if plan is not None else 0
-            if lvl is not None:
-                preroll += pipe.lv.plans[pipe.lv.rows[0][0]].LA
-            lagging = plan is not None or lvl is not None
-            if lagging and out_n is None:
-                out_n = eng.frame_samples
-            drain_frames = -(-preroll // out_n) if lagging else 0
-
-            pos, end = 0, None  # lagging: output samples read so far; pre-roll + frames * n_out once the frames are known
+            pos, frames = 0, None  # output samples read so far; the chunk's frame count once it is known
 
             def pop(frame):
                 nonlocal pos
                 pipe.done_event(frame).synchronize()
-                if lagging:  # frames are read in order: drop the pre-roll, stop at `end`
-                    lo = max(preroll - pos, 0)
-                    hi = out_n if end is None else max(min(out_n, end - pos), lo)
-                    pos += out_n
-                    return pipe.out_of(frame)[0, lo:hi].clone()
-                if out_n is not None:
-                    return pipe.out_of(frame)[0, :out_n].clone()
-                return pipe.pcm_of(frame)[0].clone()
+                if pipe.out is None:
+                    return pipe.pcm_of(frame)[0].clone()
+                lo, hi = route.take(pos, frames)  # frames are read in order: drop the pre-roll, stop at the chunk's end
+                pos += route.n_out
+                return pipe.out_of(frame)[0, lo:hi].clone()
 
             for step in range(max_gen_len):
                 if yielded == 0 and emitted == 1:
@@ -650,16 +583,12 @@ class TTSModel:
                 emitted += 1
             else:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
-            if lagging:
+            if route.drain_frames:
                 # `emitted` frames make emitted * n_out samples.  The row's tail comes out of `drain_frames` further codec
-                # frames, which it reads as zeros: through the stretcher's flag where there is one (what it emits past its
-                # tail is zero), else through the leveler's.
-                end = preroll + emitted * out_n
-                if plan is not None:
-                    pipe.ts.set_row_drain(0, True, pipe.s2)
-                else:
-                    pipe.lv.set_row_drain(0, True, pipe.s2)
-                for f in range(emitted, emitted + drain_frames):
+                # frames, which it reads as zeros (the drain rule: output_chain.py)
+                frames = emitted
+                pipe.chain.drain_row(0, route, pipe.s2)
+                for f in range(emitted, emitted + route.drain_frames):
                     while yielded < f:  # every earlier frame is read before its ring slot is written again
                         chunk = pop(yielded)
                         yielded += 1
@@ -667,7 +596,7 @@ class TTSModel:
                         if chunk.shape[0]:
                             yield chunk
                     pipe.decode_async(f)
-                emitted += drain_frames
+                emitted += route.drain_frames
             while yielded < emitted:
                 chunk = pop(yielded)
                 yielded += 1

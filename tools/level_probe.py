@@ -48,7 +48,7 @@ def main():
         pipe = StepPipeline(eng, st, ms, None, 1, float("inf"), mode="events", pcm_i16=True, **kw)
         if name == "limit":
             for b in range(B):
-                pipe.lv.set_row(b, pipe.level_plan(0), a.gain_db, None, pipe.s2)
+                pipe.chain.set_row(b, pipe.chain.table.route(gain_db=a.gain_db), pipe.s2)
         legs[name] = (st, ms, pipe)
     rows = []
     for rep in range(a.reps):

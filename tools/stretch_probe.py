@@ -48,7 +48,7 @@ def main():
         pipe = StepPipeline(eng, st, ms, None, 1, float("inf"), mode="events", pcm_i16=True, **kw)
         if name == "stretch":
             for b in range(B):
-                pipe.ts.set_row(b, pipe.speed_plan(0, a.speed), pipe.s2)
+                pipe.chain.set_row(b, pipe.chain.table.route(speed=a.speed), pipe.s2)
         legs[name] = (st, ms, pipe)
     rows = []
     for rep in range(a.reps):
