@@ -681,6 +681,16 @@ class Engine:
         _lib.check(int(n))
         return [ln for ln in buf.value.decode().splitlines() if ln.strip()]
 
+    def tune_import(self, text: str) -> int:
+        """Set tile choices from table lines in `_tune_table`'s format (13 key integers, then the configuration); later
+        launches of those shapes use them where the configuration is admitted for the shape.  Returns the lines taken."""
+        return int(_lib.check(self.lib.ptts_tune_import(self.handle, text.encode())))
+
+    def tune_clear(self):
+        """Forget every tile choice, measured or imported: launches are back on the static heuristic until `tune` runs"""
+        self.lib.ptts_tune_clear(self.handle)
+        self._tuned.clear()
+
     def profile_start(self):
         _lib.check(self.lib.ptts_profile_start(self.handle))
 

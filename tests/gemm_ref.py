@@ -19,6 +19,15 @@ PRE_NONE, PRE_ELU, PRE_ADDSILU, PRE_LNFOLD, PRE_LNMOD = range(5)
 EPI_STORE, EPI_RES, EPI_GATE = range(3)
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_ELU = range(4)
 
+# mirror of kCfgName / kCfgShape in ptts_dispatch.hip: {TN, TM, WK, WN, WM} of the register-staged configurations,
+# {BNT, BMT, 0, 0, 0} of the LDS-staged ones
+CFG_NAME = ["gemm<1,1,8,1,1>", "gemm<1,2,4,1,1>", "gemm<1,4,4,1,1>", "gemm<2,4,1,2,2>", "gemm<2,4,1,1,4>", "gemm<1,4,1,1,4>",
+            "gemm<1,1,1,1,4>", "gemm<2,4,4,1,1>", "gemm_lds<4,8,2>", "gemm_lds<4,4,2>", "gemm<2,2,4,1,1>", "gemm<1,1,4,1,1>",
+            "gemm_lds<4,2,2>", "gemm<1,2,1,2,2>", "gemm<2,4,2,2,1>", "gemm_lds<8,8,2>", "gemm_lds<8,4,2>", "gemm_lds<8,2,2>"]
+CFG_SHAPE = [(1, 1, 8, 1, 1), (1, 2, 4, 1, 1), (1, 4, 4, 1, 1), (2, 4, 1, 2, 2), (2, 4, 1, 1, 4), (1, 4, 1, 1, 4),
+             (1, 1, 1, 1, 4), (2, 4, 4, 1, 1), (8, 4, 0, 0, 0), (4, 4, 0, 0, 0), (2, 2, 4, 1, 1), (1, 1, 4, 1, 1),
+             (2, 4, 0, 0, 0), (1, 2, 1, 2, 2), (2, 4, 2, 2, 1), (8, 8, 0, 0, 0), (4, 8, 0, 0, 0), (2, 8, 0, 0, 0)]
+
 F64 = torch.float64
 
 

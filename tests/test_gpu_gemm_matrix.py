@@ -10,8 +10,8 @@ from pathlib import Path
 import pytest
 import torch
 
-from gemm_ref import (ACT_ELU, ACT_GELU, ACT_NONE, ACT_SILU, EPI_GATE, EPI_RES, EPI_STORE, PRE_ADDSILU, PRE_ELU,
-                      PRE_LNFOLD, PRE_LNMOD, PRE_NONE, gemm_ref)
+from gemm_ref import (ACT_ELU, ACT_GELU, ACT_NONE, ACT_SILU, CFG_NAME, CFG_SHAPE, EPI_GATE, EPI_RES, EPI_STORE, PRE_ADDSILU,
+                      PRE_ELU, PRE_LNFOLD, PRE_LNMOD, PRE_NONE, gemm_ref)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +19,6 @@ REPO = Path(__file__).resolve().parents[1]
 TOL = 2.0 ** -18
 REF_MACS = 2 ** 28  # above this many multiply-adds the reference covers a fixed subset of row tiles
 
-# mirror of kCfgName / kCfgShape in ptts_dispatch.hip: {TN, TM, WK, WN, WM} of the register-staged configurations,
-# {BNT, BMT, 0, 0, 0} of the LDS-staged ones
-CFG_NAME = ["gemm<1,1,8,1,1>", "gemm<1,2,4,1,1>", "gemm<1,4,4,1,1>", "gemm<2,4,1,2,2>", "gemm<2,4,1,1,4>", "gemm<1,4,1,1,4>",
-            "gemm<1,1,1,1,4>", "gemm<2,4,4,1,1>", "gemm_lds<4,8,2>", "gemm_lds<4,4,2>", "gemm<2,2,4,1,1>", "gemm<1,1,4,1,1>",
-            "gemm_lds<4,2,2>", "gemm<1,2,1,2,2>", "gemm<2,4,2,2,1>", "gemm_lds<8,8,2>", "gemm_lds<8,4,2>", "gemm_lds<8,2,2>"]
-CFG_SHAPE = [(1, 1, 8, 1, 1), (1, 2, 4, 1, 1), (1, 4, 4, 1, 1), (2, 4, 1, 2, 2), (2, 4, 1, 1, 4), (1, 4, 1, 1, 4),
-             (1, 1, 1, 1, 4), (2, 4, 4, 1, 1), (8, 4, 0, 0, 0), (4, 4, 0, 0, 0), (2, 2, 4, 1, 1), (1, 1, 4, 1, 1),
-             (2, 4, 0, 0, 0), (1, 2, 1, 2, 2), (2, 4, 2, 2, 1), (8, 8, 0, 0, 0), (4, 8, 0, 0, 0), (2, 8, 0, 0, 0)]
 NCFG = len(CFG_NAME)
 # the configurations the library admits per weight format (fp32, int8, bf16, split bf16) on a shape every one of them fits
 ADMITTED = {
