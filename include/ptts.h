@@ -39,6 +39,7 @@ typedef struct ptts_mimi_state ptts_mimi_state; /* Mimi streaming state of B seq
 typedef struct ptts_graph ptts_graph;           /* a captured hipGraph of one step       */
 typedef struct ptts_resampler ptts_resampler;   /* output sample rates of B sequences    */
 typedef struct ptts_stretcher ptts_stretcher;   /* speaking rates of B sequences         */
+typedef struct ptts_pitcher ptts_pitcher;       /* pitches of B sequences                */
 typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences          */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
@@ -304,6 +305,45 @@ int ptts_stretch_frame(ptts_stretcher *ts, const float *d_in, void *out, int32_t
  * [B, in_max] instead of its own output (in_max must be the resampler's out_max).  NULL stretcher: off, decodes and captures
  * are launch for launch those of a state that never had one. */
 int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16);
+/* ---- Pitch (no reference counterpart).  A pitcher holds, for B sequences, a table of plans, each row's plan and each row's
+ * streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of its line)
+ * into out[B, width] with row b's n samples at the front of its line (the rest of the line is not written), every frequency
+ * moved by r = P / Q.  Plan i is h_plans[8 i ..] = (n, Ha, Hs, D, L, P, Q, T):
+ *   WSOLA part  (n, Ha, Hs, D, L) is a stretcher plan with Ha = Q u, Hs = P u, under the stretcher's contract word for word
+ *               (positions, score, tie-break, the plan's window of 2 Hs floats in h_windows, zero before the stream's start
+ *               and after the row is set to drain); a frame's K = n / Ha hops emit n_mid = n P / Q "mid" samples
+ *   FIR part    y[N] = sum_{j < T} table[(N P) % Q][j] mid[(N P) / Q - j], N < n, the taps in index order; the plan's table is
+ *               its Q T floats in h_tables (the plans' tables one after the other), mid = 0 before the stream's start
+ * The output lags by L samples (the WSOLA part's (L / Ha) Hs mid samples, times Q / P) plus the FIR's group delay of
+ * 10 max(P, Q) / P samples, which is not compensated.  Ha == Hs is the identity plan (P = Q = T = 1): an exact copy of the
+ * first n samples, no lag, no state.  A plan is refused (-1) unless the stretcher admits (n, Ha, Hs, D, L), P and Q are
+ * coprime and at most 20, Ha / Q == Hs / P, T == ceil((20 max(P, Q) + 1) / Q) <= 41 and n_mid <= 16384: with these every
+ * index the kernel forms is in bounds by construction (csrc/ptts_pitch.h, csrc/ptts_stretch.h).  Plan rule:
+ * pocket_tts_amd/pitch.py.  width is the largest n of the plans, mid_max the largest n_mid and K_max the largest K of those
+ * that are not the identity (at least 1).  The mid samples of a frame live in a row-private device buffer the pitcher owns.
+ * Every row starts on plan 0 with a zero state. */
+int ptts_pitcher_create(ptts_engine *e, int32_t batch, const int32_t *h_plans, int32_t n_plans, const float *h_windows,
+                        int64_t n_window_floats, const float *h_tables, int64_t n_table_floats, ptts_pitcher **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_pitcher(state, NULL, ..) on its states */
+void ptts_pitcher_destroy(ptts_pitcher *ps);
+/* a new utterance joins `row`: its plan from now on; carried samples, carry, delta, mid history and the drain flag are zeroed.
+ * Stream-ordered on `stream`; captured graphs pick it up (the kernel reads all of it from device memory).  -1 for a row or
+ * a plan index out of range; nothing is enqueued. */
+int ptts_pitcher_set_row(ptts_pitcher *ps, int32_t row, int32_t plan_index, void *stream);
+/* from now on (stream-ordered) the row's incoming frames count as zeros (on != 0), until set_row or on == 0 */
+int ptts_pitcher_set_row_drain(ptts_pitcher *ps, int32_t row, int32_t on, void *stream);
+/* One frame, one launch: d_in f32[B, width] (DEVICE memory) -> out [B, width], f32 or (is_i16) int16 converted as
+ * ptts_mimi_set_pcm_i16 converts, device or pinned host; then the rows' states advance.  The test taps, device or NULL:
+ * d_delta (i32 [B, K_max]) receives the delta_k of the frame's hops and d_mid (f32 [B, mid_max]) the frame's n_mid mid samples
+ * of every row that is not on an identity plan; nothing else of them is written. */
+int ptts_pitch_frame(ptts_pitcher *ps, const float *d_in, void *out, int32_t is_i16, int32_t *d_delta, float *d_mid,
+                     void *stream);
+/* While a pitcher is set, ptts_mimi_decode and the graph captures append the launch of ptts_pitch_frame after the stretcher's
+ * and before the leveler's.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer;
+ * width must be frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given the
+ * preceding stage (resampler or stretcher) as its `out`.  NULL pitcher: off, decodes and captures are launch for launch
+ * those of a state that never had one. */
+int ptts_mimi_set_pitcher(ptts_mimi_state *s, ptts_pitcher *ps, float *d_in, void *out, int32_t is_i16);
 /* ---- Output level (no reference counterpart).  A leveler holds, for B sequences, a table of plans, each row's plan, gain G,
  * ceiling C and streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front
  * of its line) into out[B, width] with row b's n samples at the front of its line (the rest of the line is not written).
@@ -331,7 +371,7 @@ int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_
 /* While a leveler is set, ptts_mimi_decode and the graph captures append the launch of ptts_level_frame as their LAST one.
  * d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer; width must be
  * frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given the preceding stage
- * (resampler or stretcher) as its `out`.  NULL leveler: off, decodes and captures are launch for launch those of a state
+ * (resampler, stretcher or pitcher) as its `out`.  NULL leveler: off, decodes and captures are launch for launch those of a state
  * that never had one. */
 int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float *d_in, void *out, int32_t is_i16);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the

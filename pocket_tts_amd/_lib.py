@@ -130,6 +130,13 @@ PROTOTYPES = {
     "ptts_stretcher_set_row_drain": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ptts_stretch_frame": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     "ptts_mimi_set_stretcher": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    "ptts_pitcher_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_float), C.c_int64,
+                                      C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "ptts_pitcher_destroy": (None, [_P]),
+    "ptts_pitcher_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_pitcher_set_row_drain": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_pitch_frame": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
+    "ptts_mimi_set_pitcher": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "ptts_leveler_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_P)]),
     "ptts_leveler_destroy": (None, [_P]),
     "ptts_leveler_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
@@ -173,10 +180,11 @@ def build(force: bool = False, verbose: bool = False) -> Path:
       * ptts_dispatch.hip = the GEMM / attention dispatchers and the tuner, the only unit that instantiates the round-1/2
         kernel templates;
       * ptts_debug.hip = the C ABI's test hooks;
-      * ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch and
-        ptts_level.hip = the output gain with its peak limiter, each with its own part of the C ABI;
+      * ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch,
+        ptts_pitch.hip = the pitch shifter and ptts_level.hip = the output gain with its peak limiter, each with its own
+        part of the C ABI;
       * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
-    The first six see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
+    The first seven see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
     libptts.so; a unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 

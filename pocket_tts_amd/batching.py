@@ -36,6 +36,11 @@ the leveler (`level.py`, `engine.Leveler`), the last stage of the chain.  Its lo
 stretched one, so both are "rows whose output chain lags": the row's pre-roll is the stretcher's (0 without one) plus the
 look-ahead, it is held for ceil(pre-roll / n) drain frames and delivers the samples [pre-roll, pre-roll + F * n).  A
 levelled row without a stretch drains through the leveler's flag, one with a stretch through the stretcher's.
+
+A batcher built with `pitches` lets a request choose its `pitch` among them: the codec graphs run the pitch shifter
+(`pitch.py`, `engine.Pitcher`) behind the stretcher and before the leveler.  The pitcher keeps a frame's length and lags by
+its plan's L samples, so a pitched row is one more row whose output chain lags: its pre-roll joins the sum, it drains through
+the pitcher's flag unless it is stretched as well, and a pitched request of F frames delivers exactly F * n_out samples.
 """
 
 from __future__ import annotations
@@ -150,7 +155,8 @@ class _Job:
 
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
-                 max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False):
+                 max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False,
+                 pitches=None):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
@@ -164,6 +170,10 @@ class ContinuousBatcher:
         `level` = True lets each request choose its output level with `gain_db` and `peak_dbfs` (`submit`): gain plus a
         look-ahead peak limiter as the last output stage.  False: nobody is levelled, with the same graphs and buffers as
         before.
+
+        `pitches` (a list of frequency ratios `pitch.plan` admits on one of the batcher's lines at least, numbers or "P/Q"
+        strings, e.g. ["17/16", "5/4", "4/5"]) lets each request choose its `pitch` among them and 1.0 (`submit`).  None:
+        nobody is pitched, with the same graphs and buffers as before.
 
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
@@ -185,7 +195,7 @@ class ContinuousBatcher:
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
         # what the chain's rules refuse is refused before anything is allocated
-        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level)
+        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches)
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -200,12 +210,14 @@ class ContinuousBatcher:
         self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                  mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
-                                 level=level)
+                                 level=level, pitches=pitches)
         self.chain = self.pipe.chain
         self.rs = self.pipe.rs
         self.ts = self.pipe.ts
         self.lv = self.pipe.lv
-        self.lagging = self.ts is not None or self.lv is not None  # the output chain has a stage that may lag
+        self.ps = self.pipe.ps
+        # the output chain has a stage that may lag
+        self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
         self.pipe.restart()
         self.slot: list = [None] * slots                 # running _Job per slot
         # per-slot bookkeeping of the job that owns the slot (arrays: one numpy pass per step instead of a Python loop)
@@ -244,7 +256,7 @@ class ContinuousBatcher:
                temperature: float | None = None, noise_clamp: float | None = None,
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
                sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
-               peak_dbfs: float | None = None, seed: int | None = None) -> Request:
+               peak_dbfs: float | None = None, pitch=None, seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -261,7 +273,10 @@ class ContinuousBatcher:
         without `speeds`.  A stretched request needs frames_after_eos >= 1.  `gain_db` (in [-40, 24]) and `peak_dbfs` (in
         [-20, 0], default -1, only together with `gain_db`): the request's output level, gain plus a peak limiter that
         keeps |sample| <= 10^(peak_dbfs / 20) (`level.py`); None: the samples of before.  Either raises ValueError on a
-        batcher built without `level`; a levelled request needs frames_after_eos >= 1 too."""
+        batcher built without `level`; a levelled request needs frames_after_eos >= 1 too.  `pitch`: the request's
+        frequency ratio, a number or a "P/Q" string, one of the batcher's `pitches` or 1.0 (None: 1.0); a pitch that is not
+        configured, or that the plan rule refuses on the request's line, raises ValueError, as does any pitch but 1.0 on a
+        batcher built without `pitches`.  A pitched request needs frames_after_eos >= 1 as well."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -288,7 +303,7 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
-        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs)
+        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -316,6 +331,9 @@ class ContinuousBatcher:
                 m.model_recommended_frames_after_eos if m.model_recommended_frames_after_eos is not None else guess + 2)
             if route.stretched and fae < 1:
                 raise ValueError("a request with a speed needs frames_after_eos >= 1: the row is set to drain before the "
+                                 "frame that follows its last one is queued")
+            if route.pitched and fae < 1:
+                raise ValueError("a request with a pitch needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")
             if route.level is not None and fae < 1:
                 raise ValueError("a request with a gain needs frames_after_eos >= 1: the row is set to drain before the "
@@ -499,10 +517,10 @@ class ContinuousBatcher:
         self.a_pos[b] = pos + job.route.n_out
 
     def _drain_due(self):
-        """Before codec frame g is queued: every row whose output chain lags (a stretch, a level, or both) and whose job
+        """Before codec frame g is queued: every row whose output chain lags (a stretch, a pitch, a level) and whose job
         ends before that frame is set to drain on the codec stream, so that the frames past the job's end count as zeros:
         through the stretcher's flag where the row is stretched (what the stretcher emits past its tail is zero, which is
-        what the leveler behind it then reads), else through the leveler's.  A job's end is known `frames_after_eos`
+        what the stages behind it then read), else through the pitcher's, else through the leveler's.  A job's end is known `frames_after_eos`
         frames ahead once the EOS flags up to then have been read; where they have not, this reads them (it waits for
         the frames concerned), which a row without a speed never needs."""
         for b in range(self.B):

@@ -2205,6 +2205,22 @@ extern "C" int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, f
   return 0;
 }
 
+// Pitch: while a pitcher is set, its launch follows the stretch launch and precedes the level launch.  d_in == NULL: it reads
+// the frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  NULL switches
+// it off: decodes and captures are then launch for launch what they were.
+extern "C" int ptts_mimi_set_pitcher(ptts_mimi_state *s, ptts_pitcher *ps, float *d_in, void *out, int32_t is_i16) {
+  if (!s) return fail(-1, "null state");
+  if (ps && !out) return fail(-1, "set_pitcher: null output");
+  if (ps && pitch_batch(ps) != s->B) return fail(-1, "set_pitcher: the pitcher's batch is not the state's");
+  if (ps && !d_in && pitch_width(ps) != s->rows[3]) return fail(-1, "set_pitcher: the pitcher's frame length is not the state's");
+  if (ps && d_in && !s->rs && !s->ts) return fail(-1, "set_pitcher: an input buffer needs a resampler or a stretcher on the state");
+  s->ps = ps;
+  s->ps_in = ps ? d_in : nullptr;
+  s->ps_out = ps ? out : nullptr;
+  s->ps_i16 = ps ? (is_i16 != 0) : 0;
+  return 0;
+}
+
 // Output level: while a leveler is set, its launch is the last one of a frame.  d_in == NULL: it reads the frame's fp32 PCM;
 // otherwise the buffer d_in, which the caller has given the stage before it as its output.  NULL switches it off: decodes and
 // captures are then launch for launch what they were.
@@ -2213,7 +2229,8 @@ extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float
   if (lv && !out) return fail(-1, "set_leveler: null output");
   if (lv && level_batch(lv) != s->B) return fail(-1, "set_leveler: the leveler's batch is not the state's");
   if (lv && !d_in && level_width(lv) != s->rows[3]) return fail(-1, "set_leveler: the leveler's frame length is not the state's");
-  if (lv && d_in && !s->rs && !s->ts) return fail(-1, "set_leveler: an input buffer needs a resampler or a stretcher on the state");
+  if (lv && d_in && !s->rs && !s->ts && !s->ps)
+    return fail(-1, "set_leveler: an input buffer needs a resampler, a stretcher or a pitcher on the state");
   s->lv = lv;
   s->lv_in = lv ? d_in : nullptr;
   s->lv_out = lv ? out : nullptr;
@@ -2224,7 +2241,7 @@ extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float
 // the codec frame, then the launches of the output stages the state has
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
-  if (!s->rs && !s->ts && !s->lv) return 0;
+  if (!s->rs && !s->ts && !s->ps && !s->lv) return 0;
   const bool chained = s->ts && s->ts_in;  // resampler -> ts_in -> stretcher
   if (chained && !s->rs) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
   int r = 0;
@@ -2236,6 +2253,11 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
   if (r == 0 && s->ts) {
     SITE("stretch");
     r = stretch_enqueue(st, s->ts, chained ? s->ts_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ts_out, s->ts_i16, nullptr);
+    SITE("");
+  }
+  if (r == 0 && s->ps) {
+    SITE("pitch");
+    r = pitch_enqueue(st, s->ps, s->ps_in ? s->ps_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ps_out, s->ps_i16, nullptr, nullptr);
     SITE("");
   }
   if (r == 0 && s->lv) {

@@ -55,3 +55,12 @@ struct ptts_leveler;
 int level_enqueue(hipStream_t st, ptts_leveler *lv, const float *d_in, void *out, int is_i16);
 int level_batch(const ptts_leveler *lv);
 int level_width(const ptts_leveler *lv);
+
+// ---- ptts_pitch.hip: per-request pitch (streaming WSOLA + polyphase FIR, between the stretcher and the leveler) ---------
+// the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host); d_delta
+// (i32 [B][k_max], or null) and d_mid (f32 [B][mid_max], or null) receive the hops' deltas and the frame's mid samples.
+// Returns 0 or a negative error code (message recorded).
+struct ptts_pitcher;
+int pitch_enqueue(hipStream_t st, ptts_pitcher *ps, const float *d_in, void *out, int is_i16, int *d_delta, float *d_mid);
+int pitch_batch(const ptts_pitcher *ps);
+int pitch_width(const ptts_pitcher *ps);

@@ -263,6 +263,12 @@ struct ptts_mimi_state {
   float *ts_in = nullptr;
   void *ts_out = nullptr;
   int ts_i16 = 0;
+  // pitch (ptts_mimi_set_pitcher): the pitch launch follows the stretch launch and precedes the level launch; it reads the
+  // frame's PCM (ps_in == nullptr) or ps_in, the buffer the stage before it writes
+  ptts_pitcher *ps = nullptr;
+  float *ps_in = nullptr;
+  void *ps_out = nullptr;
+  int ps_i16 = 0;
   // output level (ptts_mimi_set_leveler): the level launch is the last one; it reads the frame's PCM (lv_in == nullptr) or
   // lv_in, the buffer the stage before it writes
   ptts_leveler *lv = nullptr;

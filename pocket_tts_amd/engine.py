@@ -248,11 +248,26 @@ class MimiState:
         _lib.check(self.engine.lib.ptts_mimi_set_stretcher(self.handle, ts.handle, _ptr(mid) if mid is not None else None,
                                                            _ptr(out), int(out.dtype == torch.int16)))
 
+    def set_pitcher(self, ps: "Pitcher | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `ps` behind the stretcher's launch (if any) and before
+        the leveler's, writing `out` [B, ps.width], float32 or int16, device or pinned host (include/ptts.h:
+        ptts_mimi_set_pitcher).  `mid` None: it reads the frame's PCM (which must then be a DEVICE tensor); otherwise the
+        float32 device tensor `mid` [B, ps.width], which the caller has given the resampler or the stretcher set on this
+        state as its output.  None: off."""
+        if ps is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_pitcher(self.handle, None, None, None, 0))
+            return
+        ps._check_out(out)
+        if mid is not None:
+            ps._check_in(mid)
+        _lib.check(self.engine.lib.ptts_mimi_set_pitcher(self.handle, ps.handle, _ptr(mid) if mid is not None else None,
+                                                         _ptr(out), int(out.dtype == torch.int16)))
+
     def set_leveler(self, lv: "Leveler | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
         """The decodes / graph captures issued after this call run `lv` as their last launch, writing `out` [B, lv.width],
         float32 or int16, device or pinned host (include/ptts.h: ptts_mimi_set_leveler).  `mid` None: it reads the frame's
         PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid` [B, lv.width], which the caller
-        has given the resampler or the stretcher set on this state as its output.  None: off."""
+        has given the resampler, the stretcher or the pitcher set on this state as its output.  None: off."""
         if lv is None:
             _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, None, None, None, 0))
             return
@@ -374,6 +389,59 @@ class Stretcher(_Stage):
                                   or tuple(delta.shape) != (self.batch, self.k_max)):
             raise ValueError(f"stretcher deltas: expected a contiguous int32 [{self.batch}, {self.k_max}] tensor on {e.device}")
         self._frame(e.lib.ptts_stretch_frame, x, out, stream, delta)
+
+
+class Pitcher(_Stage):
+    """Pitches of `batch` sequences (include/ptts.h: ptts_pitcher; contract and plan rule: `pitch.py`).  `plans` is a list
+    of `pitch.PitchPlan`; a row is dealt a plan by its index (`set_row`) and starts on plan 0.  `frame(x, out)` turns one
+    frame x[b, :n(plan of b)] into out[b, :n(plan of b)], every frequency moved by the plan's ratio, `preroll` samples late;
+    `set_row_drain` makes a row's incoming frames count as zeros, which flushes its tail."""
+
+    _name, _destroy = "pitcher", "ptts_pitcher_destroy"
+
+    def __init__(self, engine: "Engine", batch: int, plans):
+        super().__init__(engine, batch)
+        self.plans = list(plans)
+        self.width = self.in_max = self.out_max = self._in_width = self._out_width = max(p.n for p in self.plans)
+        self.k_max = max([p.K for p in self.plans if not p.identity], default=1)
+        self.mid_max = max([p.n_mid for p in self.plans if not p.identity], default=1)
+        self.row_plan = [0] * batch  # host mirror of the rows' plan indices
+        n = len(self.plans)
+        ints = (C.c_int32 * (8 * n))(*[v for p in self.plans for v in p.ints()])
+        windows = np.concatenate([p.sp.window.reshape(-1) for p in self.plans]).astype(np.float32)
+        tables = np.concatenate([p.table.reshape(-1) for p in self.plans]).astype(np.float32)
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_pitcher_create(engine.handle, batch, ints, n,
+                                                  windows.ctypes.data_as(C.POINTER(C.c_float)), windows.size,
+                                                  tables.ctypes.data_as(C.POINTER(C.c_float)), tables.size, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _row_args(self, row):
+        return (self.row_plan[row],)
+
+    def set_row(self, row: int, plan_index: int, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` with a zero state, not draining; stream-ordered"""
+        _lib.check(self.engine.lib.ptts_pitcher_set_row(self.handle, int(row), int(plan_index), self._sp(stream)))
+        self.row_plan[row] = int(plan_index)
+
+    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
+        """from now on (stream-ordered) the row's incoming frames count as zeros"""
+        _lib.check(self.engine.lib.ptts_pitcher_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, delta: torch.Tensor | None = None, mid: torch.Tensor | None = None,
+              stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] on the device -> out (float32 or int16 [B, width], device or pinned host); the test taps `delta`
+        (int32 [B, k_max]) and `mid` (float32 [B, mid_max]), both on the device, receive the hops' deltas and the frame's
+        mid samples of the rows that are not on an identity plan"""
+        e = self.engine
+        self._check_in(x)
+        self._check_out(out)
+        for t, dtype, w, what in ((delta, torch.int32, self.k_max, "deltas"), (mid, torch.float32, self.mid_max, "mid samples")):
+            if t is not None and (t.device != e.device or t.dtype != dtype or not t.is_contiguous()
+                                  or tuple(t.shape) != (self.batch, w)):
+                raise ValueError(f"pitcher {what}: expected a contiguous {dtype} [{self.batch}, {w}] tensor on {e.device}")
+        self._frame(e.lib.ptts_pitch_frame, x, out, stream, delta, mid)
 
 
 class Leveler(_Stage):
@@ -723,6 +791,9 @@ class Engine:
 
     def new_stretcher(self, batch: int, plans) -> Stretcher:
         return Stretcher(self, batch, plans)
+
+    def new_pitcher(self, batch: int, plans) -> Pitcher:
+        return Pitcher(self, batch, plans)
 
     def new_leveler(self, batch: int, plans) -> Leveler:
         return Leveler(self, batch, plans)
@@ -1100,29 +1171,31 @@ class StepPipeline:
       of a forked graph do not run concurrently).
 
     `sample_rates` (a list of output rates, `resample.py`), `speeds` (a list of speaking rates, `stretch.py`; each must be
-    admissible at one of the rates at least) and `level` (True: per-row gain and limiter, `level.py`) configure the output
-    chain codec -> resampler -> stretcher -> level (`output_chain.py`; not in "fork" mode): the codec graphs end with its
-    stages' launches.  `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts` and `lv`.
+    admissible at one of the rates at least), `pitches` (a list of frequency ratios, `pitch.py`; each admissible on one of
+    the lines at least) and `level` (True: per-row gain and limiter, `level.py`) configure the output chain codec ->
+    resampler -> stretcher -> pitcher -> level (`output_chain.py`; not in "fork" mode): the codec graphs end with its stages'
+    launches.  `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts`, `ps` and `lv`.
     `pcm[p]` are then DEVICE tensors and the samples reach the host through `out[p]`, the chain's pinned ring, int16 with
     `pcm_i16`, else float32: `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  A row gets
     its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec stream); rows start on the
-    native rate, speed 1.0 and bypass.  With None / None / False nothing changes: same buffers, same graph nodes.
+    native rate, speed 1.0, pitch 1.0 and bypass.  With None / None / None / False nothing changes: same buffers, same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False):
+                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False,
+                 pitches=None):
         from .output_chain import ChainTable, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
         # the plan table first: what the rules refuse is refused before anything is allocated
-        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level)
+        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches)
         if not table.empty and self.mode == "fork":
-            raise ValueError("sample_rates / speeds / level: not available in the 'fork' mode")
+            raise ValueError("sample_rates / speeds / pitches / level: not available in the 'fork' mode")
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -1130,6 +1203,7 @@ class StepPipeline:
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
         self.rs, self.ts, self.lv, self.out = self.chain.rs, self.chain.ts, self.chain.lv, self.chain.out
+        self.ps = self.chain.ps
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host

@@ -11,7 +11,9 @@
 batcher, with per-request temperature, noise clamp, EOS threshold and seed, and with `--sample-rates 8000,16000,48000` a
 per-request `sample_rate`, and with `--speeds 0.8,1.25,1.5` a per-request `speed` (pitch-preserving time-stretch on the GPU,
 stretch.py; `generate --speed 1.25` is the same for one text), and with `--level` a per-request `gain_db` / `peak_dbfs`
-(gain plus a look-ahead peak limiter on the GPU, level.py; `generate --gain-db 6 [--peak-dbfs -1]`).  `export-voice` encodes an audio prompt (first 30 s)
+(gain plus a look-ahead peak limiter on the GPU, level.py; `generate --gain-db 6 [--peak-dbfs -1]`), and with
+`--pitches 17/16,5/4,4/5` a per-request `pitch` (a frequency ratio; pitch shift on the GPU, pitch.py; `generate --pitch 17/16`
+or `generate --pitch-semitones 1` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -92,6 +94,19 @@ def parse_speed_list(text: str) -> list:
     return speeds
 
 
+def parse_pitch_list(text: str) -> list:
+    """"17/16,5/4,0.8" -> [1.0625, 1.25, 0.8] (the `serve --pitches` value): ratios as numbers or "P/Q"""
+    from .pitch import fraction
+
+    try:
+        pitches = [float(fraction(t)) for t in text.split(",") if t.strip()]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    if not pitches:
+        raise argparse.ArgumentTypeError("expected at least one pitch")
+    return pitches
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="pocket-tts")
     sub = ap.add_subparsers(dest="command", required=True)
@@ -112,6 +127,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Output sample rate (e.g. 8000, 16000, 22050, 44100, 48000; default: the codec's 24000), resampled on the GPU")
     g.add_argument("--speed", type=float, default=None,
                    help="Speaking rate in [0.5, 2] (e.g. 0.8, 1.25, 1.5; default 1.0): time-stretched on the GPU at constant pitch")
+    g.add_argument("--pitch", default=None, metavar="P/Q",
+                   help="Pitch as a frequency ratio in [0.5, 2], a fraction P/Q with P, Q <= 20 or a number (e.g. 17/16, 5/4, "
+                        "0.8; default 1): shifted on the GPU, the formants move with it")
+    g.add_argument("--pitch-semitones", type=float, default=None, metavar="ST",
+                   help="Pitch in semitones, in [-12, 12]: the admissible ratio nearest to 2^(ST/12) is used")
     g.add_argument("--gain-db", type=float, default=None,
                    help="Output gain in dB, in [-40, 24], with a peak limiter that guarantees the ceiling (default: none)")
     g.add_argument("--peak-dbfs", type=float, default=None,
@@ -142,6 +162,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--speeds", type=parse_speed_list, default=None, metavar="S1,S2,...",
                    help="Speaking rates a request may choose with the form field speed, e.g. 0.8,1.25,1.5 (1.0 is always "
                         "available); each must give whole hops per frame at one of the server's rates")
+    s.add_argument("--pitches", type=parse_pitch_list, default=None, metavar="P1/Q1,P2/Q2,...",
+                   help="Pitch ratios a request may choose with the form field pitch, e.g. 17/16,5/4,4/5 (1 is always "
+                        "available); each must give whole hops per frame on one of the server's lines")
     s.add_argument("--level", action="store_true",
                    help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
                         "limiter on the GPU)")
@@ -177,7 +200,7 @@ def serve_app(args) -> int:
     # the model's noise clamp reaches every request as a per-request setting (server.py)
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
-                     sample_rates=args.sample_rates, speeds=args.speeds, level=args.level)
+                     sample_rates=args.sample_rates, speeds=args.speeds, level=args.level, pitches=args.pitches)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -224,6 +247,21 @@ def cli_app(argv=None) -> int:
         except ValueError as e:
             logger.error("%s: %s", flag, e)
             return 1
+    # the pitch behind the rate and the speed; semitones become the nearest ratio the rule admits on that line
+    try:
+        if args.pitch is not None and args.pitch_semitones is not None:
+            raise ValueError("give one of --pitch and --pitch-semitones")
+        native, fs = int(model.sample_rate), model.engine.frame_samples
+        pitch = args.pitch
+        if args.pitch_semitones is not None:
+            from .pitch import nearest
+
+            pitch, cents = nearest(args.pitch_semitones, *ChainTable.single_line(native, fs, args.sample_rate, args.speed))
+            logger.info("--pitch-semitones %g: pitch %s, %+.1f cents from the request", args.pitch_semitones, pitch, cents)
+        request["pitch"] = ChainTable.single_pitch(native, fs, args.sample_rate, args.speed, pitch)
+    except ValueError as e:
+        logger.error("--pitch / --pitch-semitones: %s", e)
+        return 1
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
     chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,

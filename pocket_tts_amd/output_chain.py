@@ -1,16 +1,17 @@
-"""The output chain codec -> resampler -> stretcher -> level as one object: what a pipeline's stages are (`ChainTable`), what
+"""The output chain codec -> resampler -> stretcher -> pitcher -> level as one object: what a pipeline's stages are (`ChainTable`), what
 a request's row does in them (`Route`), and the stage objects and buffers on the device (`OutputChain`).
 
-The first half is pure Python over the rule modules `resample.py`, `stretch.py` and `level.py`: it needs no library, no
+The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py` and `level.py`: it needs no library, no
 GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
 yields, how many leading samples to drop, how many drain frames flush its tail and which stage's drain flag to raise - is a
-`Route`; nothing outside this module composes the three plan rules.
+`Route`; nothing outside this module composes the four plan rules.
 
-The drain rule: a row's pre-roll is the SUM of its stages' pre-rolls (the stretcher's, 0 on an identity plan, plus the
-leveler's look-ahead, 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
+The drain rule: a row's pre-roll is the SUM of its stages' pre-rolls (the stretcher's and the pitcher's, 0 on an identity plan,
+plus the leveler's look-ahead, 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
 ceil(preroll / n_out) further frames, which it reads as zeros, to get there - a count of the sum, not of any one stage.  The
 zeros enter at the first lagging stage: through the stretcher's flag where the row is stretched (what the stretcher emits
-past its tail is zero, which is what the leveler behind it then reads), else through the leveler's.
+past its tail is zero, which is what the stages behind it then read), else through the pitcher's where the row is pitched,
+else through the leveler's.
 """
 
 from __future__ import annotations
@@ -19,6 +20,7 @@ import numbers
 from dataclasses import dataclass
 
 from . import level as level_rule
+from . import pitch as pitch_rule
 from . import resample, stretch
 
 
@@ -36,7 +38,8 @@ class Route:
     """One row's way through the chain.  `rate_index`, `rate`: the row's output rate; `stretch_plan`: its plan index in
     the stretcher (None without one), `stretched`: that plan is no identity plan; `level`: (plan index in the leveler,
     gain_db, peak_dbfs), None for bypass; `n_out`: samples its frame yields at the end of the chain; `preroll`, `drain_frames`,
-    `drain_stage` ("stretch", "level" or None): the drain rule of the module's docstring."""
+    `drain_stage` ("stretch", "pitch", "level" or None): the drain rule of the module's docstring; `pitch_plan`: its plan
+    index in the pitcher (None without one), `pitched`: that plan is no identity plan."""
 
     rate_index: int
     rate: int
@@ -47,6 +50,8 @@ class Route:
     preroll: int
     drain_frames: int
     drain_stage: str | None
+    pitch_plan: int | None = None
+    pitched: bool = False
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -61,39 +66,49 @@ class ChainTable:
     """The plans of a pipeline's stages, built once: `rate_plans` (`resample.plans`: the native rate first), and with
     `speeds` the stretcher's `stretch_plans` / `stretch_index[rate index][speed index]` (`stretch.table`), with `level`
     the leveler's `level_plans` / `level_index[(rate, n)]` (`level.table` over every (rate, samples per frame) the rates x
-    speeds can produce).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
-    speed or line the rules refuse raises their ValueError here, before anything is allocated.  `sample_rates` / `speeds`
-    None and `level` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none)."""
+    speeds can produce), with `pitches` the pitcher's `pitch_plans` / `pitch_index[(rate, n)][pitch index]` (`pitch.table`
+    over the same lines; the pitcher keeps a line's length, so the leveler's lines are unchanged).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
+    speed, pitch or line the rules refuse raises their ValueError here, before anything is allocated.  `sample_rates` /
+    `speeds` / `pitches` None and `level` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none)."""
 
-    def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False):
+    def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
+                 pitches=None):
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
         self.speeds = None if speeds is None else stretch.normalise_speeds(speeds)
+        self.pitches = None if pitches is None else pitch_rule.normalise_pitches(pitches)
         self.rate_plans = resample.plans(self.sample_rates or (), self.native_rate, self.frame_samples)
         self.rates = [p.rate for p in self.rate_plans]
         lines = [(p.rate, p.out_n) for p in self.rate_plans]
         self.stretch_plans = self.stretch_index = self.level_plans = self.level_index = None
+        self.pitch_plans = self.pitch_index = None
         if self.speeds is not None:
             self.stretch_plans, self.stretch_index = stretch.table(lines, self.speeds)
             lines = [(self.rates[r], self.stretch_plans[i].n_out) for r, row in enumerate(self.stretch_index)
                      for i in row if i is not None]
+        if self.pitches is not None:
+            self.pitch_plans, self.pitch_index = pitch_rule.table(lines, self.pitches)
         if level:
             self.level_plans, self.level_index = level_rule.table(lines)
 
     @property
     def empty(self) -> bool:
-        return not self.has_rates and self.speeds is None and self.level_plans is None
+        return not self.has_rates and self.speeds is None and self.pitches is None and self.level_plans is None
 
     def speeds_of(self) -> dict:
         """{rate: [the configured speeds admissible at that rate, 1.0 first]}"""
         return {rate: [s for j, s in enumerate(self.speeds) if self.stretch_index[r][j] is not None]
                 for r, rate in enumerate(self.rates)}
 
-    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None) -> Route:
-        """The `Route` of a request; None is the native rate, speed 1.0, no gain.  ValueError for a rate or speed that is
-        not configured, a speed the plan rule refuses at the request's rate (the message lists those it admits), a level
-        `level.check` refuses, and for any of them on a table without that stage."""
+    def pitches_of(self, rate: int, n: int) -> list:
+        """the configured pitches admissible on frames of `n` samples at `rate` Hz, 1.0 first"""
+        return [p for j, p in enumerate(self.pitches) if self.pitch_index[(rate, n)][j] is not None]
+
+    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None) -> Route:
+        """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0.  ValueError for a rate, speed
+        or pitch that is not configured, a speed or pitch the plan rule refuses on the request's line (the message lists
+        those it admits), a level `level.check` refuses, and for any of them on a table without that stage."""
         r = 0
         if self.has_rates:
             r = rate_index(self.rates, sample_rate)
@@ -112,6 +127,20 @@ class ChainTable:
         elif speed is not None and (isinstance(speed, bool) or not isinstance(speed, numbers.Real) or speed != 1.0):
             raise ValueError(f"speed {speed!r}: this batcher speaks at 1.0 only (build it with speeds for per-request speeds)")
         stretched = plan is not None and not self.stretch_plans[plan].identity
+        pplan, pitched = None, False
+        if self.pitches is not None:
+            f = 1.0 if pitch is None else float(pitch_rule.fraction(pitch))
+            if f not in self.pitches:
+                raise ValueError(f"pitch {pitch!r} is not configured (this pipeline has {self.pitches})")
+            pplan = self.pitch_index[(rate, n_out)][self.pitches.index(f)]
+            if pplan is None:
+                raise ValueError(f"pitch {pitch!r} is not admissible on frames of {n_out} samples at {rate} Hz (admissible "
+                                 f"there: {self.pitches_of(rate, n_out)})")
+            pitched = not self.pitch_plans[pplan].identity
+            preroll += self.pitch_plans[pplan].preroll
+        elif pitch is not None and float(pitch_rule.fraction(pitch)) != 1.0:
+            raise ValueError(f"pitch {pitch!r}: this batcher speaks at pitch 1.0 only (build it with pitches for per-request "
+                             "pitches)")
         lvl = None
         if self.level_plans is not None:
             g_db, p_db = level_rule.check(gain_db, peak_dbfs)
@@ -121,7 +150,7 @@ class ChainTable:
         elif gain_db is not None or peak_dbfs is not None:
             raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
-                     "stretch" if stretched else "level" if lvl is not None else None)
+                     "stretch" if stretched else "pitch" if pitched else "level" if lvl is not None else None, pplan, pitched)
 
     @staticmethod
     def single(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None):
@@ -144,26 +173,50 @@ class ChainTable:
             level_rule.plan(sample_rate or native, n)
         return sample_rate, speed, gain_db, peak_dbfs
 
+    @staticmethod
+    def single_line(native_rate: int, frame_samples: int, sample_rate=None, speed=None):
+        """(rate, n): the line that leaves the stretcher of one request's own chain - what its pitcher reads"""
+        sample_rate, speed, _, _ = ChainTable.single(native_rate, frame_samples, sample_rate, speed)
+        rate, n = sample_rate or int(native_rate), int(frame_samples)
+        if sample_rate is not None:
+            n = resample.plan(sample_rate, int(native_rate), frame_samples).out_n
+        if speed is not None:
+            n = stretch.plan(speed, rate, n).n_out
+        return rate, n
+
+    @staticmethod
+    def single_pitch(native_rate: int, frame_samples: int, sample_rate=None, speed=None, pitch=None):
+        """The pitch of one request that gets a chain of its own, behind that request's rate and speed: the float of its
+        fraction, None for 1.0.  ValueError with the message of the rule that refuses."""
+        if pitch is None:
+            return None
+        f = pitch_rule.fraction(pitch)
+        if f == 1:
+            return None
+        return pitch_rule.plan(f, *ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)).pitch
+
 
 class OutputChain:
-    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `lv` (`engine.Resampler`, `Stretcher`,
-    `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `lv` (`engine.Resampler`, `Stretcher`,
+    `Pitcher`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
     [batch, widest line] tensors, int16 with `pcm_i16`, else float32, which the last stage writes.  An empty table creates
     nothing: `out` is None and the codec writes its PCM as without a chain."""
 
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
 
-        from .engine import Leveler, Resampler, Stretcher
+        from .engine import Leveler, Pitcher, Resampler, Stretcher
 
         self.table = table
         self.rs = Resampler(engine, batch, table.sample_rates, table.rate_plans) if table.has_rates else None
         self.ts = Stretcher(engine, batch, table.stretch_plans) if table.speeds is not None else None
+        self.ps = Pitcher(engine, batch, table.pitch_plans) if table.pitches is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
-        self.out = self.rs_out = self.lv_in = None
+        self.out = self.rs_out = self.ps_in = self.lv_in = None
         if table.empty:
             return
-        last = self.ts if self.ts is not None else self.rs  # the stage before the leveler, if any
+        before_ps = self.ts if self.ts is not None else self.rs  # the stage before the pitcher, if any
+        last = self.ps if self.ps is not None else before_ps     # the stage before the leveler, if any
         width = self.lv.width if self.lv is not None else last.out_max
         self.out = [torch.zeros(batch, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory() for _ in range(nb)]
         # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
@@ -171,26 +224,35 @@ class OutputChain:
             if last.out_max != width:
                 raise ValueError("level: the leveler's line is not the line of the stage before it")
             self.lv_in = torch.zeros(batch, width, device=engine.device)
+        if self.ps is not None and before_ps is not None:
+            if before_ps.out_max != self.ps.width:
+                raise ValueError("pitch: the pitcher's line is not the line of the stage before it")
+            self.ps_in = torch.zeros(batch, self.ps.width, device=engine.device)
         if self.ts is not None and self.rs is not None:
             self.rs_out = torch.zeros(batch, self.rs.out_max, device=engine.device)
 
     def stages(self):
-        return [s for s in (self.rs, self.ts, self.lv) if s is not None]
+        return [s for s in (self.rs, self.ts, self.ps, self.lv) if s is not None]
 
     def attach(self, mimi_state, p: int):
         """the decodes / graph captures of `mimi_state` issued after this call end with the chain's launches and write
         ring slot `p` (the frame's PCM must then be a device tensor)"""
         end = self.out[p] if self.lv is None else self.lv_in  # what the stage before the leveler writes
+        mid = end if self.ps is None else self.ps_in          # what the stage before the pitcher writes
         if self.rs is not None:
-            mimi_state.set_resampler(self.rs, end if self.ts is None else self.rs_out)
+            mimi_state.set_resampler(self.rs, mid if self.ts is None else self.rs_out)
         if self.ts is not None:
-            mimi_state.set_stretcher(self.ts, end, self.rs_out)
+            mimi_state.set_stretcher(self.ts, mid, self.rs_out)
+        if self.ps is not None:
+            mimi_state.set_pitcher(self.ps, end, self.ps_in)
         if self.lv is not None:
             mimi_state.set_leveler(self.lv, self.out[p], self.lv_in)
 
     def detach(self, mimi_state):
         if self.lv is not None:
             mimi_state.set_leveler(None)
+        if self.ps is not None:
+            mimi_state.set_pitcher(None)
         if self.ts is not None:
             mimi_state.set_stretcher(None)
         if self.rs is not None:
@@ -208,12 +270,14 @@ class OutputChain:
             self.rs.set_row(row, route.rate_index, stream)
         if self.ts is not None:
             self.ts.set_row(row, route.stretch_plan, stream)
+        if self.ps is not None:
+            self.ps.set_row(row, route.pitch_plan, stream)
         if self.lv is not None:
             self.lv.set_row(row, *(route.level or (None, None, None)), stream)
 
     def drain_row(self, row: int, route: Route, stream=None):
         """from now on (stream-ordered) the row's incoming frames count as zeros at the stage `route.drain_stage` names"""
-        stage = {"stretch": self.ts, "level": self.lv, None: None}[route.drain_stage]
+        stage = {"stretch": self.ts, "pitch": self.ps, "level": self.lv, None: None}[route.drain_stage]
         if stage is not None:
             stage.set_row_drain(row, True, stream)
 

@@ -5,7 +5,9 @@ pocket_tts/main.py:121-214) with every request decoded in one shared batch.
 directory) or the file `voice_wav` - plus this server's optional per-request settings `temperature`, `noise_clamp`,
 `eos_threshold`, `frames_after_eos`, `lsd_decode_steps`, `seed` (the same seed, text and settings give the same noise
 again), `sample_rate` (one of the rates the server was started with, or the codec's own) and `speed` (one of the speaking
-rates the server was started with that the plan rule of `stretch.py` admits at the request's rate, or 1.0), and on a
+rates the server was started with that the plan rule of `stretch.py` admits at the request's rate, or 1.0), `pitch` (one
+of the frequency ratios the server was started with that the plan rule of `pitch.py` admits behind the request's rate and
+speed, a number or "P/Q", or 1), and on a
 server started with `level` the output level `gain_db` with its ceiling `peak_dbfs` (`level.py`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
 
@@ -43,6 +45,7 @@ INDEX_HTML = """<!doctype html>
 <p>Seed <input name="seed" size="20"> (empty: a take that cannot be repeated)</p>
 <p>Sample rate <input name="sample_rate" size="6"> Hz (empty: the model's own rate)</p>
 <p>Speed <input name="speed" size="5"> (empty: 1.0)</p>
+<p>Pitch <input name="pitch" size="6"> as a frequency ratio, e.g. 17/16 or 0.8 (empty: 1)</p>
 <p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)</p>
 <p><button type="submit">Speak</button></p>
 </form>
@@ -205,6 +208,24 @@ def parse_speed(fields: dict, rate: int, table: dict | None) -> float | None:
     return near[0]
 
 
+def parse_pitch(fields: dict, rate, speed, table) -> float | None:
+    """the optional `pitch` field, a number or "P/Q": 1 or one of the configured pitches admissible behind the request's
+    `rate` and `speed` (absent or empty: None).  `table`: the server's `ChainTable` (rates, speeds, pitches).  FormError
+    with the admissible list for a pitch that is not configured, that the plan rule refuses on the request's line, or that
+    is sent to a server started without pitches"""
+    from . import pitch as pitch_rule
+
+    raw = fields.get("pitch")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        v = float(pitch_rule.fraction(raw))
+        table.route(rate, speed, None, None, v)
+    except ValueError as e:
+        raise FormError(str(e)) from None
+    return v
+
+
 def parse_level(fields: dict, enabled: bool):
     """the optional `gain_db` and `peak_dbfs` fields as (gain_db, peak_dbfs), each None where absent or empty; FormError for
     a value `level.check` refuses (its message names the rule) and for either field on a server started without level"""
@@ -230,7 +251,7 @@ def parse_level(fields: dict, enabled: bool):
 
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
                batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None,
-               level: bool = False):
+               level: bool = False, pitches=None):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
@@ -241,7 +262,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     may choose with `speed` besides 1.0 (None: only 1.0, and the batcher's graphs are those of before); each must be
     admissible at one of the server's rates at least (ValueError here, not at the first request), and a request whose
     speed its rate does not admit gets a 400.  `level`: requests may set their output level with `gain_db` and `peak_dbfs`
-    (False: a request that sends either gets a 400, and the batcher's graphs are those of before).  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    (False: a request that sends either gets a 400, and the batcher's graphs are those of before).  `pitches`: the frequency ratios a
+    request may choose with `pitch` besides 1 (None: only 1, and the batcher's graphs are those of before); each must be
+    admissible on one of the server's lines at least (ValueError here), and a request whose pitch its line does not admit gets
+    a 400 with the admissible list.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
     from .output_chain import ChainTable
@@ -255,6 +279,14 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         speeds = [float(v) for v in speeds]
         speeds_of = speed_table(speeds, model.sample_rate, sample_rates, model.engine.frame_samples)
 
+    if pitches is not None:
+        from .pitch import normalise_pitches
+
+        pitches = normalise_pitches(pitches)[1:]
+    # what a request's pitch is checked against: the lines its rate and speed select (ValueError at start-up)
+    frame_samples = getattr(getattr(model, "engine", None), "frame_samples", 1920)
+    pitch_table = ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, pitches=pitches)
+
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
     if batcher_factory is None:
@@ -265,7 +297,7 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
 
         def batcher_factory(model, slots, capacity):
             return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
-                                     sample_rates=sample_rates, speeds=speeds, level=level)
+                                     sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -360,6 +392,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             speed = parse_speed(fields, rate or int(model.sample_rate), speeds_of)
             if speed is not None and speed != 1.0:
                 settings["speed"] = speed
+            pitch = parse_pitch(fields, settings.get("sample_rate"), settings.get("speed"), pitch_table)
+            if pitch is not None and pitch != 1.0:
+                settings["pitch"] = pitch
             gain_db, peak_dbfs = parse_level(fields, level)
             if gain_db is not None:
                 settings["gain_db"], settings["peak_dbfs"] = gain_db, peak_dbfs
