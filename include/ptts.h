@@ -41,6 +41,7 @@ typedef struct ptts_resampler ptts_resampler;   /* output sample rates of B sequ
 typedef struct ptts_stretcher ptts_stretcher;   /* speaking rates of B sequences         */
 typedef struct ptts_pitcher ptts_pitcher;       /* pitches of B sequences                */
 typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences          */
+typedef struct ptts_loudnorm ptts_loudnorm;     /* loudness targets of B sequences       */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
 typedef struct ptts_config {
@@ -371,9 +372,41 @@ int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_
 /* While a leveler is set, ptts_mimi_decode and the graph captures append the launch of ptts_level_frame as their LAST one.
  * d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer; width must be
  * frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given the preceding stage
- * (resampler, stretcher or pitcher) as its `out`.  NULL leveler: off, decodes and captures are launch for launch those of a state
+ * (resampler, stretcher, pitcher or normaliser) as its `out`.  NULL leveler: off, decodes and captures are launch for launch those of a state
  * that never had one. */
 int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float *d_in, void *out, int32_t is_i16);
+/* ---- Loudness (no reference counterpart).  A normaliser holds, for B sequences, a table of plans, each row's plan, target T
+ * in LUFS and streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of
+ * its line) into d_out f32[B, width] with row b's n samples at the front of its line (the rest of the line is neither read nor
+ * written).  It measures the running gated loudness of the row's own stream by ITU-R BS.1770-4 (K-weighting, 400 ms blocks
+ * every 100 ms, absolute and relative gate) and applies the gain, clamped to +-20 dB and ramped linearly over each 100 ms,
+ * that brings it to T; the output lags by D = 4 (rate / 10) samples (contract: pocket_tts_amd/loudness.py).  Plan i is
+ * h_plans[2 i ..] = (rate, n) and h_doubles[330 i ..] = the ten K-weighting coefficients (b0 b1 b2 a1 a2 of the shelf, then of
+ * the high-pass) followed by the ten matrices A^(chunk 2^t), chunk = ceil(n / 1024), of the recurrence the kernel scans, each
+ * as two row-major 4 x 4 matrices: the power rounded to double, then what the exact power leaves.  A plan is refused (-1) unless 8000 <= rate <= 48000, 1 <= n <= 8192 and every double is finite: with these
+ * every index the kernel forms is in bounds by construction (csrc/ptts_loud.h).  width is the largest n of the plans.  Every
+ * row starts on bypass: an exact copy of its whole line, no lag, no state. */
+int ptts_loudnorm_create(ptts_engine *e, int32_t batch, const int32_t *h_plans, int32_t n_plans, const double *h_doubles,
+                         int64_t n_doubles, ptts_loudnorm **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_loudnorm(state, NULL, ..) on its states */
+void ptts_loudnorm_destroy(ptts_loudnorm *ln);
+/* a new utterance joins `row`: its plan (-1: bypass) and target in [-40, -10] LUFS from now on; the filter state, the
+ * measurement, the delayed samples and the drain flag are zeroed.  Stream-ordered on `stream`; captured graphs pick it up.
+ * -1 for a row, a plan index or a target out of range; nothing is enqueued. */
+int ptts_loudnorm_set_row(ptts_loudnorm *ln, int32_t row, int32_t plan_index, double target_lufs, void *stream);
+/* from now on (stream-ordered) the row's incoming frames count as zeros (on != 0), until set_row or on == 0 */
+int ptts_loudnorm_set_row_drain(ptts_loudnorm *ln, int32_t row, int32_t on, void *stream);
+/* One frame, one launch: d_in f32[B, width] -> d_out f32[B, width], both DEVICE memory and distinct; then the rows' states
+ * advance.  The test tap d_tap, device or NULL: f64[B, 4] receives, for every row that is not on bypass, the sub-blocks it
+ * has completed, its last L (NaN while undefined), its last c and its last Z. */
+int ptts_loudnorm_frame(ptts_loudnorm *ln, const float *d_in, float *d_out, double *d_tap, void *stream);
+/* While a normaliser is set, ptts_mimi_decode and the graph captures append the launch of ptts_loudnorm_frame after the
+ * pitcher's and before the leveler's.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own
+ * buffer; width must be frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given
+ * the preceding stage (resampler, stretcher or pitcher) as its `out`.  It writes d_out, which the caller gives the leveler as
+ * its d_in: a frame enqueued with a normaliser but no leveler fails (-1).  NULL normaliser: off, decodes and captures are
+ * launch for launch those of a state that never had one. */
+int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);

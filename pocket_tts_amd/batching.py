@@ -41,6 +41,12 @@ A batcher built with `pitches` lets a request choose its `pitch` among them: the
 (`pitch.py`, `engine.Pitcher`) behind the stretcher and before the leveler.  The pitcher keeps a frame's length and lags by
 its plan's L samples, so a pitched row is one more row whose output chain lags: its pre-roll joins the sum, it drains through
 the pitcher's flag unless it is stretched as well, and a pitched request of F frames delivers exactly F * n_out samples.
+
+A batcher built with `loudness=True` lets a request choose a loudness target (`loudness_lufs`): the codec graphs run the
+BS.1770 normaliser (`loudness.py`, `engine.Normalizer`) behind the pitcher and the leveler behind it as its peak limiter.
+The normaliser lags by 400 ms, so such a row is one more row whose output chain lags: the delay joins the pre-roll, and the
+row drains through the normaliser's flag unless a stage before it lags as well.  The measurement restarts with every text
+chunk, so the chunks of a long request are normalised one by one.
 """
 
 from __future__ import annotations
@@ -156,7 +162,7 @@ class _Job:
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
                  max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None):
+                 pitches=None, loudness: bool = False):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
@@ -174,6 +180,10 @@ class ContinuousBatcher:
         `pitches` (a list of frequency ratios `pitch.plan` admits on one of the batcher's lines at least, numbers or "P/Q"
         strings, e.g. ["17/16", "5/4", "4/5"]) lets each request choose its `pitch` among them and 1.0 (`submit`).  None:
         nobody is pitched, with the same graphs and buffers as before.
+
+        `loudness` = True lets each request choose a loudness target with `loudness_lufs` (`submit`): the gain that brings
+        the running BS.1770 loudness of its own audio to the target, followed by the peak limiter.  False: nobody is
+        normalised, with the same graphs and buffers as before.
 
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
@@ -195,7 +205,7 @@ class ContinuousBatcher:
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
         # what the chain's rules refuse is refused before anything is allocated
-        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches)
+        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness)
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -210,12 +220,13 @@ class ContinuousBatcher:
         self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                  mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
-                                 level=level, pitches=pitches)
+                                 level=level, pitches=pitches, loudness=loudness)
         self.chain = self.pipe.chain
         self.rs = self.pipe.rs
         self.ts = self.pipe.ts
         self.lv = self.pipe.lv
         self.ps = self.pipe.ps
+        self.ln = self.pipe.ln
         # the output chain has a stage that may lag
         self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
         self.pipe.restart()
@@ -256,7 +267,8 @@ class ContinuousBatcher:
                temperature: float | None = None, noise_clamp: float | None = None,
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
                sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
-               peak_dbfs: float | None = None, pitch=None, seed: int | None = None) -> Request:
+               peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
+               seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -276,7 +288,10 @@ class ContinuousBatcher:
         batcher built without `level`; a levelled request needs frames_after_eos >= 1 too.  `pitch`: the request's
         frequency ratio, a number or a "P/Q" string, one of the batcher's `pitches` or 1.0 (None: 1.0); a pitch that is not
         configured, or that the plan rule refuses on the request's line, raises ValueError, as does any pitch but 1.0 on a
-        batcher built without `pitches`.  A pitched request needs frames_after_eos >= 1 as well."""
+        batcher built without `pitches`.  A pitched request needs frames_after_eos >= 1 as well.  `loudness_lufs` (in
+        [-40, -10]): the request's loudness target (`loudness.py`), limited to `peak_dbfs` (default -1) behind it; it
+        excludes `gain_db`, raises ValueError on a batcher built without `loudness` and needs frames_after_eos >= 1.  Each
+        text chunk of a long request is measured on its own, so the gain can differ between the chunks."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -303,7 +318,7 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
-        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch)
+        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -335,6 +350,9 @@ class ContinuousBatcher:
             if route.pitched and fae < 1:
                 raise ValueError("a request with a pitch needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")
+            if route.loud is not None and fae < 1:
+                raise ValueError("a request with a loudness target needs frames_after_eos >= 1: the row is set to drain "
+                                 "before the frame that follows its last one is queued")
             if route.level is not None and fae < 1:
                 raise ValueError("a request with a gain needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")

@@ -2221,6 +2221,24 @@ extern "C" int ptts_mimi_set_pitcher(ptts_mimi_state *s, ptts_pitcher *ps, float
   return 0;
 }
 
+// Loudness: while a normaliser is set, its launch follows the pitch launch and precedes the level launch.  d_in == NULL: it
+// reads the frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  It
+// always writes f32 into the device buffer d_out, which the leveler then reads: a frame enqueued with a normaliser but no
+// leveler fails.  NULL switches it off: decodes and captures are then launch for launch what they were.
+extern "C" int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out) {
+  if (!s) return fail(-1, "null state");
+  if (ln && !d_out) return fail(-1, "set_loudnorm: null output");
+  if (ln && d_in == d_out) return fail(-1, "set_loudnorm: the stage does not work in place");
+  if (ln && loud_batch(ln) != s->B) return fail(-1, "set_loudnorm: the normaliser's batch is not the state's");
+  if (ln && !d_in && loud_width(ln) != s->rows[3]) return fail(-1, "set_loudnorm: the normaliser's frame length is not the state's");
+  if (ln && d_in && !s->rs && !s->ts && !s->ps)
+    return fail(-1, "set_loudnorm: an input buffer needs a resampler, a stretcher or a pitcher on the state");
+  s->ln = ln;
+  s->ln_in = ln ? d_in : nullptr;
+  s->ln_out = ln ? d_out : nullptr;
+  return 0;
+}
+
 // Output level: while a leveler is set, its launch is the last one of a frame.  d_in == NULL: it reads the frame's fp32 PCM;
 // otherwise the buffer d_in, which the caller has given the stage before it as its output.  NULL switches it off: decodes and
 // captures are then launch for launch what they were.
@@ -2229,8 +2247,8 @@ extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float
   if (lv && !out) return fail(-1, "set_leveler: null output");
   if (lv && level_batch(lv) != s->B) return fail(-1, "set_leveler: the leveler's batch is not the state's");
   if (lv && !d_in && level_width(lv) != s->rows[3]) return fail(-1, "set_leveler: the leveler's frame length is not the state's");
-  if (lv && d_in && !s->rs && !s->ts && !s->ps)
-    return fail(-1, "set_leveler: an input buffer needs a resampler, a stretcher or a pitcher on the state");
+  if (lv && d_in && !s->rs && !s->ts && !s->ps && !s->ln)
+    return fail(-1, "set_leveler: an input buffer needs a resampler, a stretcher, a pitcher or a normaliser on the state");
   s->lv = lv;
   s->lv_in = lv ? d_in : nullptr;
   s->lv_out = lv ? out : nullptr;
@@ -2240,8 +2258,9 @@ extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float
 
 // the codec frame, then the launches of the output stages the state has
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
+  if (s->ln && !s->lv) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
-  if (!s->rs && !s->ts && !s->ps && !s->lv) return 0;
+  if (!s->rs && !s->ts && !s->ps && !s->ln && !s->lv) return 0;
   const bool chained = s->ts && s->ts_in;  // resampler -> ts_in -> stretcher
   if (chained && !s->rs) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
   int r = 0;
@@ -2258,6 +2277,11 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
   if (r == 0 && s->ps) {
     SITE("pitch");
     r = pitch_enqueue(st, s->ps, s->ps_in ? s->ps_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ps_out, s->ps_i16, nullptr, nullptr);
+    SITE("");
+  }
+  if (r == 0 && s->ln) {
+    SITE("loudnorm");
+    r = loud_enqueue(st, s->ln, s->ln_in ? s->ln_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ln_out, nullptr);
     SITE("");
   }
   if (r == 0 && s->lv) {

@@ -56,6 +56,14 @@ int level_enqueue(hipStream_t st, ptts_leveler *lv, const float *d_in, void *out
 int level_batch(const ptts_leveler *lv);
 int level_width(const ptts_leveler *lv);
 
+// ---- ptts_loud.hip: per-request loudness target (streaming BS.1770 normaliser, between the pitcher and the leveler) ------
+// the frame's launch on `st`: d_in f32[B][width] (device) -> d_out f32[B][width] (device, never d_in); d_tap (f64 [B][4], or
+// null) receives each normalising row's completed sub-blocks, last L, last c and last Z.  Returns 0 or a negative error code.
+struct ptts_loudnorm;
+int loud_enqueue(hipStream_t st, ptts_loudnorm *ln, const float *d_in, float *d_out, double *d_tap);
+int loud_batch(const ptts_loudnorm *ln);
+int loud_width(const ptts_loudnorm *ln);
+
 // ---- ptts_pitch.hip: per-request pitch (streaming WSOLA + polyphase FIR, between the stretcher and the leveler) ---------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host); d_delta
 // (i32 [B][k_max], or null) and d_mid (f32 [B][mid_max], or null) receive the hops' deltas and the frame's mid samples.

@@ -269,6 +269,11 @@ struct ptts_mimi_state {
   float *ps_in = nullptr;
   void *ps_out = nullptr;
   int ps_i16 = 0;
+  // loudness (ptts_mimi_set_loudnorm): the normaliser's launch follows the pitch launch and precedes the level launch; it
+  // reads the frame's PCM (ln_in == nullptr) or ln_in, the buffer the stage before it writes, and writes f32 into ln_out
+  ptts_loudnorm *ln = nullptr;
+  float *ln_in = nullptr;
+  float *ln_out = nullptr;
   // output level (ptts_mimi_set_leveler): the level launch is the last one; it reads the frame's PCM (lv_in == nullptr) or
   // lv_in, the buffer the stage before it writes
   ptts_leveler *lv = nullptr;

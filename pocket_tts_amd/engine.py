@@ -277,6 +277,21 @@ class MimiState:
         _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, lv.handle, _ptr(mid) if mid is not None else None,
                                                          _ptr(out), int(out.dtype == torch.int16)))
 
+    def set_loudnorm(self, ln: "Normalizer | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `ln` behind the pitcher's launch (if any) and before the
+        leveler's, writing float32 into the device tensor `out` [B, ln.width], which the caller gives the leveler as its
+        `mid` (include/ptts.h: ptts_mimi_set_loudnorm; a frame with a normaliser but no leveler fails).  `mid` None: it reads
+        the frame's PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid` [B, ln.width], which
+        the caller has given the resampler, the stretcher or the pitcher set on this state as its output.  None: off."""
+        if ln is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_loudnorm(self.handle, None, None, None))
+            return
+        ln._check_in(out)
+        if mid is not None:
+            ln._check_in(mid)
+        _lib.check(self.engine.lib.ptts_mimi_set_loudnorm(self.handle, ln.handle, _ptr(mid) if mid is not None else None,
+                                                          _ptr(out)))
+
     def __del__(self):
         try:
             self.close()
@@ -493,6 +508,72 @@ class Leveler(_Stage):
         self._check_in(x)
         self._check_out(out)
         self._frame(self.engine.lib.ptts_level_frame, x, out, stream)
+
+
+class Normalizer(_Stage):
+    """Loudness targets of `batch` sequences (include/ptts.h: ptts_loudnorm; contract and plan rule: `loudness.py`).
+    `plans` is a list of `loudness.LoudPlan`; a row is dealt a plan by its index together with its target in LUFS
+    (`set_row`; `loudness_lufs` None: bypass) and starts on bypass.  `frame(x, out)` turns one frame x[b, :n(plan of b)]
+    into out[b, :n(plan of b)], D = 400 ms late, under the gain that brings the row's running BS.1770 loudness to its
+    target; `set_row_drain` makes a row's incoming frames count as zeros, which flushes its tail.  A bypass row's whole line
+    is copied.  The output is always float32 on the device: the stage is never the last one."""
+
+    _name, _destroy = "normaliser", "ptts_loudnorm_destroy"
+
+    def __init__(self, engine: "Engine", batch: int, plans):
+        super().__init__(engine, batch)
+        self.plans = list(plans)
+        self.width = self.in_max = self.out_max = self._in_width = self._out_width = max(p.n for p in self.plans)
+        self.rows = [(-1, None)] * batch  # host mirror: (plan index, loudness_lufs) of each row
+        n = len(self.plans)
+        ints = (C.c_int32 * (2 * n))(*[v for p in self.plans for v in p.ints()])
+        doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_loudnorm_create(engine.handle, batch, ints, n,
+                                                   doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _row_args(self, row):
+        return self.rows[row]
+
+    def set_row(self, row: int, plan_index: int | None = None, loudness_lufs=None, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` with the target `loudness_lufs` and a zero state, not draining;
+        `loudness_lufs` None: the row bypasses the stage.  Stream-ordered"""
+        from . import loudness
+
+        t = loudness.check(loudness_lufs)
+        if t is None:
+            idx, t_arg = -1, 0.0
+        else:
+            idx, t_arg = int(plan_index), t
+            if not 0 <= idx < len(self.plans):
+                raise ValueError(f"normaliser plan index {plan_index!r} out of range")
+        _lib.check(self.engine.lib.ptts_loudnorm_set_row(self.handle, int(row), idx, t_arg, self._sp(stream)))
+        self.rows[row] = (idx, t)
+
+    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
+        """from now on (stream-ordered) the row's incoming frames count as zeros"""
+        _lib.check(self.engine.lib.ptts_loudnorm_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, tap: torch.Tensor | None = None,
+              stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] -> out f32[B, width], both on the device and distinct; the test tap `tap` (float64 [B, 4] on the
+        device) receives each normalising row's completed sub-blocks, last L (NaN while undefined), last c and last Z"""
+        e = self.engine
+        self._check_in(x)
+        self._check_in(out)
+        if tap is not None and (tap.device != e.device or tap.dtype != torch.float64 or not tap.is_contiguous()
+                                or tuple(tap.shape) != (self.batch, 4)):
+            raise ValueError(f"normaliser tap: expected a contiguous float64 [{self.batch}, 4] tensor on {e.device}")
+        if stream is None:
+            e._pre()
+        _lib.check(e.lib.ptts_loudnorm_frame(self.handle, _ptr(x), _ptr(out), _ptr(tap), self._sp(stream)))
+        if stream is None:
+            for t in (x, out, tap):
+                if t is not None:
+                    t.record_stream(e.stream)
+            e._post()
 
 
 class Resampler(_Stage):
@@ -797,6 +878,9 @@ class Engine:
 
     def new_leveler(self, batch: int, plans) -> Leveler:
         return Leveler(self, batch, plans)
+
+    def new_normalizer(self, batch: int, plans) -> Normalizer:
+        return Normalizer(self, batch, plans)
 
     # ---- FlowLM
     def embed_text(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -1172,13 +1256,15 @@ class StepPipeline:
 
     `sample_rates` (a list of output rates, `resample.py`), `speeds` (a list of speaking rates, `stretch.py`; each must be
     admissible at one of the rates at least), `pitches` (a list of frequency ratios, `pitch.py`; each admissible on one of
-    the lines at least) and `level` (True: per-row gain and limiter, `level.py`) configure the output chain codec ->
-    resampler -> stretcher -> pitcher -> level (`output_chain.py`; not in "fork" mode): the codec graphs end with its stages'
-    launches.  `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts`, `ps` and `lv`.
+    the lines at least), `loudness` (True: per-row loudness target, `loudness.py`; it brings the leveler with it) and
+    `level` (True: per-row gain and limiter, `level.py`) configure the output chain codec -> resampler -> stretcher ->
+    pitcher -> normaliser -> level (`output_chain.py`; not in "fork" mode): the codec graphs end with its stages' launches.
+    `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts`, `ps`, `ln` and `lv`.
     `pcm[p]` are then DEVICE tensors and the samples reach the host through `out[p]`, the chain's pinned ring, int16 with
     `pcm_i16`, else float32: `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  A row gets
     its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec stream); rows start on the
-    native rate, speed 1.0, pitch 1.0 and bypass.  With None / None / None / False nothing changes: same buffers, same graph nodes.
+    native rate, speed 1.0, pitch 1.0 and bypass.  With None / None / None / False / False nothing changes: same buffers,
+    same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
@@ -1186,16 +1272,16 @@ class StepPipeline:
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
                  lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None):
+                 pitches=None, loudness: bool = False):
         from .output_chain import ChainTable, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
         # the plan table first: what the rules refuse is refused before anything is allocated
-        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches)
+        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness)
         if not table.empty and self.mode == "fork":
-            raise ValueError("sample_rates / speeds / pitches / level: not available in the 'fork' mode")
+            raise ValueError("sample_rates / speeds / pitches / loudness / level: not available in the 'fork' mode")
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -1203,7 +1289,7 @@ class StepPipeline:
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
         self.rs, self.ts, self.lv, self.out = self.chain.rs, self.chain.ts, self.chain.lv, self.chain.out
-        self.ps = self.chain.ps
+        self.ps, self.ln = self.chain.ps, self.chain.ln
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host

@@ -13,7 +13,8 @@ per-request `sample_rate`, and with `--speeds 0.8,1.25,1.5` a per-request `speed
 stretch.py; `generate --speed 1.25` is the same for one text), and with `--level` a per-request `gain_db` / `peak_dbfs`
 (gain plus a look-ahead peak limiter on the GPU, level.py; `generate --gain-db 6 [--peak-dbfs -1]`), and with
 `--pitches 17/16,5/4,4/5` a per-request `pitch` (a frequency ratio; pitch shift on the GPU, pitch.py; `generate --pitch 17/16`
-or `generate --pitch-semitones 1` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
+or `generate --pitch-semitones 1` is the same for one text), and with `--loudness` a per-request `loudness_lufs` (a streaming
+BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--peak-dbfs -1]`).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -134,6 +135,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Pitch in semitones, in [-12, 12]: the admissible ratio nearest to 2^(ST/12) is used")
     g.add_argument("--gain-db", type=float, default=None,
                    help="Output gain in dB, in [-40, 24], with a peak limiter that guarantees the ceiling (default: none)")
+    g.add_argument("--loudness-lufs", type=float, default=None, metavar="LUFS",
+                   help="Loudness target in LUFS, in [-40, -10] (e.g. -16, -23): normalised on the GPU by ITU-R BS.1770-4, sentence "
+                        "by sentence, with the peak limiter behind it; excludes --gain-db (default: none)")
     g.add_argument("--peak-dbfs", type=float, default=None,
                    help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db")
     g.add_argument("--output-path", default="./tts_output.wav")
@@ -165,6 +169,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--pitches", type=parse_pitch_list, default=None, metavar="P1/Q1,P2/Q2,...",
                    help="Pitch ratios a request may choose with the form field pitch, e.g. 17/16,5/4,4/5 (1 is always "
                         "available); each must give whole hops per frame on one of the server's lines")
+    s.add_argument("--loudness", action="store_true",
+                   help="Requests may set a loudness target with the form field loudness_lufs (BS.1770 normaliser plus the "
+                        "peak limiter on the GPU)")
     s.add_argument("--level", action="store_true",
                    help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
                         "limiter on the GPU)")
@@ -200,7 +207,8 @@ def serve_app(args) -> int:
     # the model's noise clamp reaches every request as a per-request setting (server.py)
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
-                     sample_rates=args.sample_rates, speeds=args.speeds, level=args.level, pitches=args.pitches)
+                     sample_rates=args.sample_rates, speeds=args.speeds, level=args.level, pitches=args.pitches,
+                     loudness=args.loudness)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -239,14 +247,24 @@ def cli_app(argv=None) -> int:
     from .output_chain import ChainTable
 
     request = {}
-    for flag, names in (("--sample-rate", ("sample_rate",)), ("--speed", ("speed",)),
-                        ("--gain-db / --peak-dbfs", ("gain_db", "peak_dbfs"))):
+    checks = [("--sample-rate", ("sample_rate",)), ("--speed", ("speed",))]
+    if args.loudness_lufs is None:  # with a loudness target the ceiling belongs to it: both are checked below
+        checks.append(("--gain-db / --peak-dbfs", ("gain_db", "peak_dbfs")))
+    for flag, names in checks:
         request.update({k: getattr(args, k) for k in names})
         try:
             ChainTable.single(int(model.sample_rate), model.engine.frame_samples, **request)
         except ValueError as e:
             logger.error("%s: %s", flag, e)
             return 1
+    if args.loudness_lufs is not None:
+        try:
+            ChainTable.single_loudness(int(model.sample_rate), model.engine.frame_samples, args.sample_rate, args.speed,
+                                       args.gain_db, args.peak_dbfs, args.loudness_lufs)
+        except ValueError as e:
+            logger.error("--loudness-lufs / --peak-dbfs: %s", e)
+            return 1
+        request.update(gain_db=None, loudness_lufs=args.loudness_lufs, peak_dbfs=args.peak_dbfs)
     # the pitch behind the rate and the speed; semitones become the nearest ratio the rule admits on that line
     try:
         if args.pitch is not None and args.pitch_semitones is not None:

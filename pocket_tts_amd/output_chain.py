@@ -1,17 +1,17 @@
-"""The output chain codec -> resampler -> stretcher -> pitcher -> level as one object: what a pipeline's stages are (`ChainTable`), what
+"""The output chain codec -> resampler -> stretcher -> pitcher -> normaliser -> level as one object: what a pipeline's stages are (`ChainTable`), what
 a request's row does in them (`Route`), and the stage objects and buffers on the device (`OutputChain`).
 
-The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py` and `level.py`: it needs no library, no
+The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `loudness.py` and `level.py`: it needs no library, no
 GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
 yields, how many leading samples to drop, how many drain frames flush its tail and which stage's drain flag to raise - is a
-`Route`; nothing outside this module composes the four plan rules.
+`Route`; nothing outside this module composes the five plan rules.
 
 The drain rule: a row's pre-roll is the SUM of its stages' pre-rolls (the stretcher's and the pitcher's, 0 on an identity plan,
-plus the leveler's look-ahead, 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
+plus the normaliser's delay and the leveler's look-ahead, each 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
 ceil(preroll / n_out) further frames, which it reads as zeros, to get there - a count of the sum, not of any one stage.  The
 zeros enter at the first lagging stage: through the stretcher's flag where the row is stretched (what the stretcher emits
 past its tail is zero, which is what the stages behind it then read), else through the pitcher's where the row is pitched,
-else through the leveler's.
+else through the normaliser's where the row has a loudness target, else through the leveler's.
 """
 
 from __future__ import annotations
@@ -20,6 +20,7 @@ import numbers
 from dataclasses import dataclass
 
 from . import level as level_rule
+from . import loudness as loud_rule
 from . import pitch as pitch_rule
 from . import resample, stretch
 
@@ -38,8 +39,9 @@ class Route:
     """One row's way through the chain.  `rate_index`, `rate`: the row's output rate; `stretch_plan`: its plan index in
     the stretcher (None without one), `stretched`: that plan is no identity plan; `level`: (plan index in the leveler,
     gain_db, peak_dbfs), None for bypass; `n_out`: samples its frame yields at the end of the chain; `preroll`, `drain_frames`,
-    `drain_stage` ("stretch", "pitch", "level" or None): the drain rule of the module's docstring; `pitch_plan`: its plan
-    index in the pitcher (None without one), `pitched`: that plan is no identity plan."""
+    `drain_stage` ("stretch", "pitch", "loud", "level" or None): the drain rule of the module's docstring; `pitch_plan`: its
+    plan index in the pitcher (None without one), `pitched`: that plan is no identity plan; `loud`: (plan index in the
+    normaliser, loudness_lufs), None for bypass."""
 
     rate_index: int
     rate: int
@@ -52,6 +54,7 @@ class Route:
     drain_stage: str | None
     pitch_plan: int | None = None
     pitched: bool = False
+    loud: tuple | None = None
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -67,12 +70,14 @@ class ChainTable:
     `speeds` the stretcher's `stretch_plans` / `stretch_index[rate index][speed index]` (`stretch.table`), with `level`
     the leveler's `level_plans` / `level_index[(rate, n)]` (`level.table` over every (rate, samples per frame) the rates x
     speeds can produce), with `pitches` the pitcher's `pitch_plans` / `pitch_index[(rate, n)][pitch index]` (`pitch.table`
-    over the same lines; the pitcher keeps a line's length, so the leveler's lines are unchanged).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
+    over the same lines; the pitcher keeps a line's length, so the leveler's lines are unchanged), with `loudness` the
+    normaliser's `loud_plans` / `loud_index[(rate, n)]` (`loudness.table` over the lines the leveler gets; the leveler's
+    plans are then built whatever `level` says, because the normaliser is always followed by the limiter).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
     speed, pitch or line the rules refuse raises their ValueError here, before anything is allocated.  `sample_rates` /
-    `speeds` / `pitches` None and `level` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none)."""
+    `speeds` / `pitches` None and `level` / `loudness` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none)."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None):
+                 pitches=None, loudness: bool = False):
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
@@ -89,7 +94,10 @@ class ChainTable:
                      for i in row if i is not None]
         if self.pitches is not None:
             self.pitch_plans, self.pitch_index = pitch_rule.table(lines, self.pitches)
-        if level:
+        self.loud_plans = self.loud_index = None
+        if loudness:
+            self.loud_plans, self.loud_index = loud_rule.table(lines)
+        if level or loudness:
             self.level_plans, self.level_index = level_rule.table(lines)
 
     @property
@@ -105,10 +113,12 @@ class ChainTable:
         """the configured pitches admissible on frames of `n` samples at `rate` Hz, 1.0 first"""
         return [p for j, p in enumerate(self.pitches) if self.pitch_index[(rate, n)][j] is not None]
 
-    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None) -> Route:
-        """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0.  ValueError for a rate, speed
-        or pitch that is not configured, a speed or pitch the plan rule refuses on the request's line (the message lists
-        those it admits), a level `level.check` refuses, and for any of them on a table without that stage."""
+    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None) -> Route:
+        """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0, no loudness target.  A request
+        with a target gets the normaliser's plan and a leveler entry at gain 0 dB under its `peak_dbfs` (default -1).
+        ValueError for a rate, speed or pitch that is not configured, a speed or pitch the plan rule refuses on the
+        request's line (the message lists those it admits), a level `level.check` or a target `loudness.check` refuses,
+        `loudness_lufs` together with `gain_db`, and for any of them on a table without that stage."""
         r = 0
         if self.has_rates:
             r = rate_index(self.rates, sample_rate)
@@ -141,7 +151,15 @@ class ChainTable:
         elif pitch is not None and float(pitch_rule.fraction(pitch)) != 1.0:
             raise ValueError(f"pitch {pitch!r}: this batcher speaks at pitch 1.0 only (build it with pitches for per-request "
                              "pitches)")
-        lvl = None
+        lvl = loud = None
+        if self.loud_plans is not None:
+            target = loud_rule.check_with(loudness_lufs, gain_db)
+            if target is not None:
+                loud = (self.loud_index[(rate, n_out)], target)
+                preroll += self.loud_plans[loud[0]].D
+                gain_db = 0.0  # the limiter behind the normaliser
+        elif loudness_lufs is not None:
+            raise ValueError("loudness_lufs: this batcher has no loudness stage (build it with loudness=True)")
         if self.level_plans is not None:
             g_db, p_db = level_rule.check(gain_db, peak_dbfs)
             if g_db is not None:
@@ -150,7 +168,8 @@ class ChainTable:
         elif gain_db is not None or peak_dbfs is not None:
             raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
-                     "stretch" if stretched else "pitch" if pitched else "level" if lvl is not None else None, pplan, pitched)
+                     "stretch" if stretched else "pitch" if pitched else "loud" if loud is not None
+                     else "level" if lvl is not None else None, pplan, pitched, loud)
 
     @staticmethod
     def single(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None):
@@ -195,28 +214,44 @@ class ChainTable:
             return None
         return pitch_rule.plan(f, *ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)).pitch
 
+    @staticmethod
+    def single_loudness(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
+                        loudness_lufs=None):
+        """The loudness target of one request that gets a chain of its own, behind that request's rate and speed (the
+        pitcher keeps the line): (loudness_lufs as a float, peak_dbfs defaulted), (None, None) without a target.
+        ValueError with the message of the rule that refuses."""
+        target = loud_rule.check_with(loudness_lufs, gain_db)
+        if target is None:
+            return None, None
+        rate, n = ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)
+        loud_rule.plan(rate, n)
+        level_rule.plan(rate, n)
+        return target, level_rule.check(0.0, peak_dbfs)[1]
+
 
 class OutputChain:
-    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `lv` (`engine.Resampler`, `Stretcher`,
-    `Pitcher`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `ln` / `lv` (`engine.Resampler`,
+    `Stretcher`, `Pitcher`, `Normalizer`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
     [batch, widest line] tensors, int16 with `pcm_i16`, else float32, which the last stage writes.  An empty table creates
     nothing: `out` is None and the codec writes its PCM as without a chain."""
 
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
 
-        from .engine import Leveler, Pitcher, Resampler, Stretcher
+        from .engine import Leveler, Normalizer, Pitcher, Resampler, Stretcher
 
         self.table = table
         self.rs = Resampler(engine, batch, table.sample_rates, table.rate_plans) if table.has_rates else None
         self.ts = Stretcher(engine, batch, table.stretch_plans) if table.speeds is not None else None
         self.ps = Pitcher(engine, batch, table.pitch_plans) if table.pitches is not None else None
+        self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
-        self.out = self.rs_out = self.ps_in = self.lv_in = None
+        self.out = self.rs_out = self.ps_in = self.ln_in = self.lv_in = None
         if table.empty:
             return
         before_ps = self.ts if self.ts is not None else self.rs  # the stage before the pitcher, if any
-        last = self.ps if self.ps is not None else before_ps     # the stage before the leveler, if any
+        before_ln = self.ps if self.ps is not None else before_ps  # the stage before the normaliser, if any
+        last = self.ln if self.ln is not None else before_ln       # the stage before the leveler, if any
         width = self.lv.width if self.lv is not None else last.out_max
         self.out = [torch.zeros(batch, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory() for _ in range(nb)]
         # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
@@ -224,6 +259,10 @@ class OutputChain:
             if last.out_max != width:
                 raise ValueError("level: the leveler's line is not the line of the stage before it")
             self.lv_in = torch.zeros(batch, width, device=engine.device)
+        if self.ln is not None and before_ln is not None:
+            if before_ln.out_max != self.ln.width:
+                raise ValueError("loudness: the normaliser's line is not the line of the stage before it")
+            self.ln_in = torch.zeros(batch, self.ln.width, device=engine.device)
         if self.ps is not None and before_ps is not None:
             if before_ps.out_max != self.ps.width:
                 raise ValueError("pitch: the pitcher's line is not the line of the stage before it")
@@ -232,12 +271,14 @@ class OutputChain:
             self.rs_out = torch.zeros(batch, self.rs.out_max, device=engine.device)
 
     def stages(self):
-        return [s for s in (self.rs, self.ts, self.ps, self.lv) if s is not None]
+        return [s for s in (self.rs, self.ts, self.ps, self.ln, self.lv) if s is not None]
 
     def attach(self, mimi_state, p: int):
         """the decodes / graph captures of `mimi_state` issued after this call end with the chain's launches and write
         ring slot `p` (the frame's PCM must then be a device tensor)"""
         end = self.out[p] if self.lv is None else self.lv_in  # what the stage before the leveler writes
+        if self.ln is not None:
+            end = self.ln_in                                  # what the stage before the normaliser writes
         mid = end if self.ps is None else self.ps_in          # what the stage before the pitcher writes
         if self.rs is not None:
             mimi_state.set_resampler(self.rs, mid if self.ts is None else self.rs_out)
@@ -245,12 +286,16 @@ class OutputChain:
             mimi_state.set_stretcher(self.ts, mid, self.rs_out)
         if self.ps is not None:
             mimi_state.set_pitcher(self.ps, end, self.ps_in)
+        if self.ln is not None:
+            mimi_state.set_loudnorm(self.ln, self.lv_in, self.ln_in)
         if self.lv is not None:
             mimi_state.set_leveler(self.lv, self.out[p], self.lv_in)
 
     def detach(self, mimi_state):
         if self.lv is not None:
             mimi_state.set_leveler(None)
+        if self.ln is not None:
+            mimi_state.set_loudnorm(None)
         if self.ps is not None:
             mimi_state.set_pitcher(None)
         if self.ts is not None:
@@ -272,12 +317,14 @@ class OutputChain:
             self.ts.set_row(row, route.stretch_plan, stream)
         if self.ps is not None:
             self.ps.set_row(row, route.pitch_plan, stream)
+        if self.ln is not None:
+            self.ln.set_row(row, *(route.loud or (None, None)), stream)
         if self.lv is not None:
             self.lv.set_row(row, *(route.level or (None, None, None)), stream)
 
     def drain_row(self, row: int, route: Route, stream=None):
         """from now on (stream-ordered) the row's incoming frames count as zeros at the stage `route.drain_stage` names"""
-        stage = {"stretch": self.ts, "pitch": self.ps, "level": self.lv, None: None}[route.drain_stage]
+        stage = {"stretch": self.ts, "pitch": self.ps, "loud": self.ln, "level": self.lv, None: None}[route.drain_stage]
         if stage is not None:
             stage.set_row_drain(row, True, stream)
 

@@ -8,7 +8,8 @@ again), `sample_rate` (one of the rates the server was started with, or the code
 rates the server was started with that the plan rule of `stretch.py` admits at the request's rate, or 1.0), `pitch` (one
 of the frequency ratios the server was started with that the plan rule of `pitch.py` admits behind the request's rate and
 speed, a number or "P/Q", or 1), and on a
-server started with `level` the output level `gain_db` with its ceiling `peak_dbfs` (`level.py`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+server started with `level` the output level `gain_db` with its ceiling `peak_dbfs` (`level.py`), and on a server started
+with `loudness` the loudness target `loudness_lufs` (`loudness.py`; with `peak_dbfs` as its ceiling, without `gain_db`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
@@ -47,6 +48,7 @@ INDEX_HTML = """<!doctype html>
 <p>Speed <input name="speed" size="5"> (empty: 1.0)</p>
 <p>Pitch <input name="pitch" size="6"> as a frequency ratio, e.g. 17/16 or 0.8 (empty: 1)</p>
 <p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)</p>
+<p>Loudness <input name="loudness_lufs" size="5"> LUFS, e.g. -16 or -23, instead of a gain (empty: the model's own level)</p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -249,9 +251,33 @@ def parse_level(fields: dict, enabled: bool):
         raise FormError(str(e)) from None
 
 
+def parse_loudness(fields: dict, enabled: bool):
+    """the optional `loudness_lufs` field with its ceiling as (loudness_lufs, peak_dbfs), (None, None) where absent or empty;
+    FormError for a value `loudness.check` or `level.check` refuses (the message names the rule), for `gain_db` beside it and
+    for the field on a server started without loudness"""
+    from . import level, loudness
+
+    raw = fields.get("loudness_lufs")
+    if raw is None or raw.strip() == "":
+        return None, None
+    if not enabled:
+        raise FormError("loudness_lufs is not available (this server was started without loudness)")
+    vals = {}
+    for name in ("loudness_lufs", "peak_dbfs", "gain_db"):
+        text = (fields.get(name) or "").strip()
+        try:
+            vals[name] = float(text) if text else None
+        except ValueError:
+            raise FormError(f"{name} must be a number, got {text!r}") from None
+    try:
+        return loudness.check_with(vals["loudness_lufs"], vals["gain_db"]), level.check(0.0, vals["peak_dbfs"])[1]
+    except ValueError as e:
+        raise FormError(str(e)) from None
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
                batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None,
-               level: bool = False, pitches=None):
+               level: bool = False, pitches=None, loudness: bool = False):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
@@ -265,7 +291,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     (False: a request that sends either gets a 400, and the batcher's graphs are those of before).  `pitches`: the frequency ratios a
     request may choose with `pitch` besides 1 (None: only 1, and the batcher's graphs are those of before); each must be
     admissible on one of the server's lines at least (ValueError here), and a request whose pitch its line does not admit gets
-    a 400 with the admissible list.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    a 400 with the admissible list.  `loudness`: requests may set a loudness target with `loudness_lufs` (and its ceiling
+    with `peak_dbfs`; False: a request that sends it gets a 400, and the batcher's graphs are those of before).
+    `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
     from .output_chain import ChainTable
@@ -286,6 +314,8 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     # what a request's pitch is checked against: the lines its rate and speed select (ValueError at start-up)
     frame_samples = getattr(getattr(model, "engine", None), "frame_samples", 1920)
     pitch_table = ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, pitches=pitches)
+    if loudness:  # the normaliser's and the limiter's rules on every line (ValueError at start-up)
+        ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, loudness=True)
 
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
@@ -297,7 +327,8 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
 
         def batcher_factory(model, slots, capacity):
             return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
-                                     sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches)
+                                     sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
+                                     loudness=loudness)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -395,9 +426,13 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             pitch = parse_pitch(fields, settings.get("sample_rate"), settings.get("speed"), pitch_table)
             if pitch is not None and pitch != 1.0:
                 settings["pitch"] = pitch
-            gain_db, peak_dbfs = parse_level(fields, level)
-            if gain_db is not None:
-                settings["gain_db"], settings["peak_dbfs"] = gain_db, peak_dbfs
+            target, ceiling = parse_loudness(fields, loudness)
+            if target is not None:
+                settings["loudness_lufs"], settings["peak_dbfs"] = target, ceiling
+            else:
+                gain_db, peak_dbfs = parse_level(fields, level)
+                if gain_db is not None:
+                    settings["gain_db"], settings["peak_dbfs"] = gain_db, peak_dbfs
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:

@@ -193,19 +193,20 @@ class TTSModel:
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                        frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
                        speed: float | None = None, gain_db: float | None = None, peak_dbfs: float | None = None,
-                       pitch=None, seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs` and `pitch` (not in the reference):
-        see `generate_audio_stream`."""
+                       pitch=None, loudness_lufs: float | None = None, seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch` and `loudness_lufs` (not in
+        the reference): see `generate_audio_stream`."""
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
                                                  seed=seed, sample_rate=sample_rate, speed=speed, gain_db=gain_db,
-                                                 peak_dbfs=peak_dbfs, pitch=pitch))
+                                                 peak_dbfs=peak_dbfs, pitch=pitch, loudness_lufs=loudness_lufs))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                               frames_after_eos: int | None = None, copy_state: bool = True,
                               sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
-                              peak_dbfs: float | None = None, pitch=None, seed: int | None = None):
+                              peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
+                              seed: int | None = None):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
 
         `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
@@ -229,6 +230,12 @@ class TTSModel:
         leveler; the formants move with it.  The samples yielded in all stay those of the same call without a pitch; the
         output lags like a levelled one.  None or 1: as before.
 
+        `loudness_lufs` (not in the reference; in [-40, -10], e.g. -16 or -23): the audio is brought to that loudness on
+        the GPU by a streaming ITU-R BS.1770-4 normaliser (`loudness.py`) behind the pitcher, followed by the peak limiter
+        at `peak_dbfs` (default -1); it excludes `gain_db`.  The gain follows the running gated loudness of the text chunk
+        so far, clamped to +-20 dB, and the output lags by 400 ms like a levelled one.  The measurement restarts with every
+        text chunk of a long text, so the gain can differ between the chunks.  None: as before.
+
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
         per-step copy, nothing read from torch's global generator - and `generate_audio_batch(seeds=...)` and
@@ -239,8 +246,11 @@ class TTSModel:
         from .output_chain import ChainTable
 
         # the native rate, speed 1.0 and no gain become None: the call of before.  ValueError names the rule
-        request = ChainTable.single(int(self.config.mimi.sample_rate), self.engine.frame_samples, sample_rate, speed, gain_db,
-                                    peak_dbfs)
+        native, fs = int(self.config.mimi.sample_rate), self.engine.frame_samples
+        loud, loud_peak = ChainTable.single_loudness(native, fs, sample_rate, speed, gain_db, peak_dbfs, loudness_lufs)
+        request = ChainTable.single(native, fs, sample_rate, speed, gain_db, None if loud is not None else peak_dbfs)
+        if loud is not None:  # the limiter behind the normaliser: no gain of its own, the request's ceiling
+            request = (*request[:3], loud_peak)
         pitch = ChainTable.single_pitch(int(self.config.mimi.sample_rate), self.engine.frame_samples, sample_rate, speed, pitch)
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
@@ -252,7 +262,7 @@ class TTSModel:
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
                                                               None if seed is None else chunk_seed(seed, i), *request,
-                                                              pitch=pitch)
+                                                              pitch=pitch, loudness_lufs=loud)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -415,7 +425,8 @@ class TTSModel:
     def _drop_rate_contexts(self, keep: int = 0):
         """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
         recently used are released; a context in use is not in the cache"""
-        keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:] or "level" in k[4:] or "pitch" in k[4:]]
+        keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:] or "level" in k[4:] or "pitch" in k[4:]
+                or "loud" in k[4:]]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
             c["pipe"].close()
@@ -491,7 +502,8 @@ class TTSModel:
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
                                           row_seed: int | None = None, sample_rate: int | None = None,
-                                          speed: float | None = None, gain_db=None, peak_dbfs=None, pitch=None):
+                                          speed: float | None = None, gain_db=None, peak_dbfs=None, pitch=None,
+                                          loudness_lufs=None):
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -513,6 +525,8 @@ class TTSModel:
             key = (*key, "level")
         if pitch is not None:  # likewise: its codec graphs run the pitch shifter
             key = (*key, "pitch", pitch)
+        if loudness_lufs is not None:  # likewise: the normaliser and the leveler (one context serves every target)
+            key = (*key, "loud")
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -520,12 +534,13 @@ class TTSModel:
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
-            if sample_rate is not None or speed is not None or gain_db is not None or pitch is not None:  # with an output chain
+            if not (sample_rate is None and speed is None and gain_db is None and pitch is None
+                    and loudness_lufs is None):  # with an output chain
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
             pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
                                 sample_rates=None if sample_rate is None else [sample_rate],
                                 speeds=None if speed is None else [speed], level=gain_db is not None,
-                                pitches=None if pitch is None else [pitch])
+                                pitches=None if pitch is None else [pitch], loudness=loudness_lufs is not None)
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
         noise_host = ctx["noise_host"]
@@ -536,7 +551,7 @@ class TTSModel:
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         # the codec's carries and the row's rate, plan, gain and ceiling with a zero state in every stage, on the codec stream
-        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch)
+        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs)
         pipe.restart([route])
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
