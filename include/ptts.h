@@ -42,6 +42,7 @@ typedef struct ptts_stretcher ptts_stretcher;   /* speaking rates of B sequences
 typedef struct ptts_pitcher ptts_pitcher;       /* pitches of B sequences                */
 typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences          */
 typedef struct ptts_loudnorm ptts_loudnorm;     /* loudness targets of B sequences       */
+typedef struct ptts_encoder ptts_encoder;       /* output encodings of B sequences       */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
 typedef struct ptts_config {
@@ -407,6 +408,32 @@ int ptts_loudnorm_frame(ptts_loudnorm *ln, const float *d_in, float *d_out, doub
  * its d_in: a frame enqueued with a normaliser but no leveler fails (-1).  NULL normaliser: off, decodes and captures are
  * launch for launch those of a state that never had one. */
 int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out);
+/* ---- Output encoding (no reference counterpart).  An encoder holds, for B sequences, each row's number of samples n and
+ * encoding code: 0 pcm_s16le, 1 pcm_f32le, 2 mulaw, 3 alaw (contract: pocket_tts_amd/encoding.py).  It turns one frame
+ * f32[B, width] of the previous output stage (row b's n samples at the front of its line) into out_bytes u8[B, pitch],
+ * pitch = 4 width rounded up to 16: row b gets exactly n * bytes_per_sample(code) bytes (2, 4, 1, 1) at the start of its row
+ * and NOTHING behind them.  pcm_f32le: the sample's four bytes, bit for bit.  pcm_s16le: s = (int16)(clamp(x, -1, 1) * 32767.0f),
+ * truncated, as ptts_mimi_set_pcm_i16 converts (a NaN gives -32767).  mulaw / alaw: ITU-T G.711 of that s, mu-law from the
+ * 14-bit value s >> 2 with all bits inverted, A-law from the 13-bit value s >> 3 with the even bits inverted (0x55).  The
+ * stage has no state, no lag and no drain flag.  Every row starts as (width, pcm_s16le). */
+int ptts_encoder_create(ptts_engine *e, int32_t batch, int32_t width, ptts_encoder **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_encoder(state, NULL, ..) on its states */
+void ptts_encoder_destroy(ptts_encoder *en);
+/* `row` holds n samples (1 <= n <= width) in the encoding `code` (0 .. 3) from now on.  Stream-ordered on `stream`; captured
+ * graphs pick it up (the kernel reads both from device memory).  -1 for a row, an n or a code out of range; nothing is
+ * enqueued. */
+int ptts_encoder_set_row(ptts_encoder *en, int32_t row, int32_t n, int32_t code, void *stream);
+/* One frame, one launch: d_in f32[B, width] (DEVICE memory) -> out_bytes u8[B, pitch], device or pinned host, aligned to 16
+ * bytes (-1 otherwise). */
+int ptts_encode_frame(ptts_encoder *en, const float *d_in, void *out_bytes, void *stream);
+/* While an encoder is set, ptts_mimi_decode and the graph captures append the launch of ptts_encode_frame as their LAST one,
+ * writing out_bytes.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer; width
+ * must be frame_samples) and must be the only output stage.  Otherwise it reads the f32 device buffer d_in [B, width], and the
+ * last stage set on the state (leveler, else pitcher, else stretcher, else resampler; its widest line must be width) writes
+ * f32 into d_in instead of its own `out`.  -1 for a batch or width that does not match, a null output, or an input buffer on
+ * a state without such a stage.  NULL encoder: off, decodes and captures are launch for launch those of a state that never
+ * had one. */
+int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float *d_in, void *out_bytes);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);

@@ -47,6 +47,12 @@ BS.1770 normaliser (`loudness.py`, `engine.Normalizer`) behind the pitcher and t
 The normaliser lags by 400 ms, so such a row is one more row whose output chain lags: the delay joins the pre-roll, and the
 row drains through the normaliser's flag unless a stage before it lags as well.  The measurement restarts with every text
 chunk, so the chunks of a long request are normalised one by one.
+
+A batcher built with `encodings` lets a request choose its output `encoding` among them and `pcm_s16le`: the codec graphs
+end with the encoder (`encoding.py`, `engine.Encoder`), which writes each row's bytes in its own encoding into the pinned
+ring.  A request's chunks are then typed views of its bytes: int16 for `pcm_s16le`, float32 for `pcm_f32le`, uint8 for
+`mulaw` and `alaw` (ITU-T G.711).  The encoder does not lag: nothing of the above changes, and samples stay the unit of
+every count.
 """
 
 from __future__ import annotations
@@ -101,9 +107,10 @@ def eos_bookkeeping_rows(local_step, max_gen_len, frames_after_eos, eos_step, n_
 class Request:
     """One submitted text.  Iterate to receive chunks; `result()` waits for the whole waveform."""
 
-    def __init__(self, rid: int, sample_rate: int | None = None):
+    def __init__(self, rid: int, sample_rate: int | None = None, encoding: str | None = None):
         self.id = rid
         self.sample_rate = sample_rate  # rate of the chunks (the codec's own unless the request asked for another)
+        self.encoding = encoding        # encoding of the chunks (None: the batcher's one sample format)
         self._q: queue.Queue = queue.Queue()
         self.frames = 0
         self.error: Exception | None = None
@@ -162,7 +169,7 @@ class _Job:
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
                  max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False):
+                 pitches=None, loudness: bool = False, encodings=None):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
@@ -185,6 +192,11 @@ class ContinuousBatcher:
         the running BS.1770 loudness of its own audio to the target, followed by the peak limiter.  False: nobody is
         normalised, with the same graphs and buffers as before.
 
+        `encodings` (a list of names of `encoding.py`, e.g. ["mulaw", "alaw", "pcm_f32le"]) lets each request choose its
+        `encoding` among them and "pcm_s16le" (`submit`); its chunks are int16, float32 or uint8 tensors accordingly.  It
+        needs `pcm_format` left at its default (ValueError).  None: every request gets `pcm_format`, with the same graphs
+        and buffers as before.
+
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
         same graphs as before.
@@ -201,11 +213,14 @@ class ContinuousBatcher:
 
         if pcm_format not in ("f32", "i16"):
             raise ValueError("pcm_format must be 'f32' or 'i16'")
+        if encodings is not None and pcm_format != "f32":
+            raise ValueError("pcm_format and encodings exclude each other: with encodings a request asks for 'pcm_s16le' "
+                             "or 'pcm_f32le' itself")
         self.model, self.eng, self.B = model, model.engine, slots
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
         # what the chain's rules refuse is refused before anything is allocated
-        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness)
+        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings)
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -220,13 +235,14 @@ class ContinuousBatcher:
         self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                  mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
-                                 level=level, pitches=pitches, loudness=loudness)
+                                 level=level, pitches=pitches, loudness=loudness, encodings=encodings)
         self.chain = self.pipe.chain
         self.rs = self.pipe.rs
         self.ts = self.pipe.ts
         self.lv = self.pipe.lv
         self.ps = self.pipe.ps
         self.ln = self.pipe.ln
+        self.en = self.pipe.en
         # the output chain has a stage that may lag
         self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
         self.pipe.restart()
@@ -268,7 +284,7 @@ class ContinuousBatcher:
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
                sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
                peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
-               seed: int | None = None) -> Request:
+               encoding: str | None = None, seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -291,7 +307,9 @@ class ContinuousBatcher:
         batcher built without `pitches`.  A pitched request needs frames_after_eos >= 1 as well.  `loudness_lufs` (in
         [-40, -10]): the request's loudness target (`loudness.py`), limited to `peak_dbfs` (default -1) behind it; it
         excludes `gain_db`, raises ValueError on a batcher built without `loudness` and needs frames_after_eos >= 1.  Each
-        text chunk of a long request is measured on its own, so the gain can differ between the chunks."""
+        text chunk of a long request is measured on its own, so the gain can differ between the chunks.  `encoding`: the
+        name of the request's output encoding, one of the batcher's `encodings` or "pcm_s16le" (None: "pcm_s16le"); a name
+        that is not configured raises ValueError, as does any on a batcher built without `encodings`."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -318,7 +336,7 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
-        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs)
+        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -338,7 +356,7 @@ class ContinuousBatcher:
         t_voice = _state_current_end(model_state)
         jobs = []
         with self._lock:
-            req = Request(self._next_id, route.rate)
+            req = Request(self._next_id, route.rate, route.encoding)
             self._next_id += 1
         for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
@@ -505,7 +523,7 @@ class ContinuousBatcher:
         for b in np.nonzero(rows)[0]:
             job = self.slot[b]
             if self.a_emit[b] < 0:
-                if self.lagging:
+                if self.lagging or self.en is not None:
                     self._deliver(b, job, pcm[b])
                 else:
                     job.req._q.put(pcm[b] if self.rs is None else pcm[b, :job.route.n_out])
@@ -531,7 +549,13 @@ class ContinuousBatcher:
         pos = int(self.a_pos[b])
         lo, hi = job.route.take(pos, None if self.a_emit[b] < 0 else int(self.a_emit[b]))
         if hi > lo:
-            job.req._q.put(line[lo:hi])
+            bps = job.route.bytes_per_sample
+            if bps is None:
+                job.req._q.put(line[lo:hi])
+            else:  # the encoder's ring is in bytes: the job's samples as a typed view of them
+                from . import encoding
+
+                job.req._q.put(line[lo * bps:hi * bps].view(encoding.torch_dtype(job.route.encoding)))
         self.a_pos[b] = pos + job.route.n_out
 
     def _drain_due(self):

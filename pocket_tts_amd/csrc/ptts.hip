@@ -2256,27 +2256,57 @@ extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float
   return 0;
 }
 
+// Output encoding: while an encoder is set, its launch is the last one of a frame.  d_in == NULL: it reads the frame's fp32
+// PCM and is the only stage; otherwise the buffer d_in, into which the last stage before it (leveler, else pitcher, else
+// stretcher, else resampler) writes f32 instead of its own output.  NULL switches it off: decodes and captures are then launch
+// for launch what they were.
+extern "C" int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float *d_in, void *out_bytes) {
+  if (!s) return fail(-1, "null state");
+  if (en && !out_bytes) return fail(-1, "set_encoder: null output");
+  if (en && encode_batch(en) != s->B) return fail(-1, "set_encoder: the encoder's batch is not the state's");
+  const bool staged = s->rs || s->ts || s->ps || s->lv;
+  if (en && !d_in && staged) return fail(-1, "set_encoder: the state has output stages, the encoder needs an input buffer");
+  if (en && !d_in && encode_width(en) != s->rows[3]) return fail(-1, "set_encoder: the encoder's frame length is not the state's");
+  if (en && d_in && !staged)
+    return fail(-1, "set_encoder: an input buffer needs a resampler, a stretcher, a pitcher or a leveler on the state");
+  if (en && d_in) {
+    const int w = s->lv ? level_width(s->lv) : s->ps ? pitch_width(s->ps) : s->ts ? stretch_out_max(s->ts) : resample_out_max(s->rs);
+    if (w != encode_width(en)) return fail(-1, "set_encoder: the encoder's width is not the widest line of the stage before it");
+  }
+  s->en = en;
+  s->en_in = en ? d_in : nullptr;
+  s->en_out = en ? out_bytes : nullptr;
+  return 0;
+}
+
 // the codec frame, then the launches of the output stages the state has
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
   if (s->ln && !s->lv) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
+  // the stage the encoder follows: 4 leveler, 3 pitcher, 2 stretcher, 1 resampler, 0 none; -1 without an encoder
+  const int fed = !s->en ? -1 : s->lv ? 4 : s->ps ? 3 : s->ts ? 2 : s->rs ? 1 : 0;
+  if (s->en && (fed > 0) != (s->en_in != nullptr))
+    return fail(-1, "the encoder's input buffer and the state's output stages do not go together");
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
-  if (!s->rs && !s->ts && !s->ps && !s->ln && !s->lv) return 0;
+  if (!s->rs && !s->ts && !s->ps && !s->ln && !s->lv && !s->en) return 0;
   const bool chained = s->ts && s->ts_in;  // resampler -> ts_in -> stretcher
   if (chained && !s->rs) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
   int r = 0;
   if (s->rs) {
     SITE("resample");
-    r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, chained ? (void *)s->ts_in : s->rs_out, chained ? 0 : s->rs_i16);
+    if (fed == 1) r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, s->en_in, 0);
+    else r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, chained ? (void *)s->ts_in : s->rs_out, chained ? 0 : s->rs_i16);
     SITE("");
   }
   if (r == 0 && s->ts) {
     SITE("stretch");
-    r = stretch_enqueue(st, s->ts, chained ? s->ts_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ts_out, s->ts_i16, nullptr);
+    r = stretch_enqueue(st, s->ts, chained ? s->ts_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 2 ? (void *)s->en_in : s->ts_out,
+                        fed == 2 ? 0 : s->ts_i16, nullptr);
     SITE("");
   }
   if (r == 0 && s->ps) {
     SITE("pitch");
-    r = pitch_enqueue(st, s->ps, s->ps_in ? s->ps_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ps_out, s->ps_i16, nullptr, nullptr);
+    r = pitch_enqueue(st, s->ps, s->ps_in ? s->ps_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 3 ? (void *)s->en_in : s->ps_out,
+                      fed == 3 ? 0 : s->ps_i16, nullptr, nullptr);
     SITE("");
   }
   if (r == 0 && s->ln) {
@@ -2286,7 +2316,13 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
   }
   if (r == 0 && s->lv) {
     SITE("level");
-    r = level_enqueue(st, s->lv, s->lv_in ? s->lv_in : (d_pcm ? d_pcm : s->pcm_dbg), s->lv_out, s->lv_i16);
+    r = level_enqueue(st, s->lv, s->lv_in ? s->lv_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 4 ? (void *)s->en_in : s->lv_out,
+                      fed == 4 ? 0 : s->lv_i16);
+    SITE("");
+  }
+  if (r == 0 && s->en) {
+    SITE("encode");
+    r = encode_enqueue(st, s->en, s->en_in ? s->en_in : (d_pcm ? d_pcm : s->pcm_dbg), s->en_out);
     SITE("");
   }
   return r;

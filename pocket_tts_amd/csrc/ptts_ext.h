@@ -47,6 +47,7 @@ struct ptts_stretcher;
 int stretch_enqueue(hipStream_t st, ptts_stretcher *ts, const float *d_in, void *out, int is_i16, int *d_delta);
 int stretch_batch(const ptts_stretcher *ts);
 int stretch_in_max(const ptts_stretcher *ts);
+int stretch_out_max(const ptts_stretcher *ts);
 
 // ---- ptts_level.hip: per-request output gain with a look-ahead peak limiter (the last output stage) ---------------------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host).  Returns 0 or
@@ -72,3 +73,12 @@ struct ptts_pitcher;
 int pitch_enqueue(hipStream_t st, ptts_pitcher *ps, const float *d_in, void *out, int is_i16, int *d_delta, float *d_mid);
 int pitch_batch(const ptts_pitcher *ps);
 int pitch_width(const ptts_pitcher *ps);
+
+// ---- ptts_encode.hip: per-request output encoding (pcm_s16le, pcm_f32le, G.711 mu-law / A-law; the last output stage) -------
+// the frame's launch on `st`: d_in f32[B][width] (device) -> out_bytes u8[B][pitch] (device or pinned host, 16-byte aligned),
+// pitch = 4 width rounded up to 16; row b gets n_b * bytes_per_sample(code_b) bytes and nothing behind them.  Returns 0 or a
+// negative error code (message recorded).
+struct ptts_encoder;
+int encode_enqueue(hipStream_t st, ptts_encoder *en, const float *d_in, void *out_bytes);
+int encode_batch(const ptts_encoder *en);
+int encode_width(const ptts_encoder *en);

@@ -280,6 +280,11 @@ struct ptts_mimi_state {
   float *lv_in = nullptr;
   void *lv_out = nullptr;
   int lv_i16 = 0;
+  // output encoding (ptts_mimi_set_encoder): the encode launch is then the last one; it reads the frame's PCM (en_in ==
+  // nullptr) or en_in, into which the stage before it writes f32 instead of its own output
+  ptts_encoder *en = nullptr;
+  float *en_in = nullptr;
+  void *en_out = nullptr;
   // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
   float *pcm_part = nullptr, *pcm_carry = nullptr;
   long pcm_cstride = 0;

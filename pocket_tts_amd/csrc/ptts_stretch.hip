@@ -137,6 +137,7 @@ __global__ void stretch_set_drain_kernel(int *row_drain, int row, int on) { row_
 
 int stretch_batch(const ptts_stretcher *ts) { return ts->B; }
 int stretch_in_max(const ptts_stretcher *ts) { return ts->in_max; }
+int stretch_out_max(const ptts_stretcher *ts) { return ts->out_max; }
 
 int stretch_enqueue(hipStream_t st, ptts_stretcher *ts, const float *d_in, void *out, int is_i16, int *d_delta) {
   if (!ts || !d_in || !out) return fail(-1, "stretch: null argument");

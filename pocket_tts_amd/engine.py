@@ -292,6 +292,20 @@ class MimiState:
         _lib.check(self.engine.lib.ptts_mimi_set_loudnorm(self.handle, ln.handle, _ptr(mid) if mid is not None else None,
                                                           _ptr(out)))
 
+    def set_encoder(self, en: "Encoder | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `en` as their last launch, writing the uint8 tensor `out`
+        [B, en.pitch], device or pinned host (include/ptts.h: ptts_mimi_set_encoder).  `mid` None: it reads the frame's PCM
+        (which must then be a DEVICE tensor) and is the only output stage; otherwise the float32 device tensor `mid`
+        [B, en.width], into which the last stage set on this state writes float32 instead of its own output.  None: off."""
+        if en is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_encoder(self.handle, None, None, None))
+            return
+        en._check_bytes(out)
+        if mid is not None:
+            en._check_in(mid)
+        _lib.check(self.engine.lib.ptts_mimi_set_encoder(self.handle, en.handle, _ptr(mid) if mid is not None else None,
+                                                         _ptr(out)))
+
     def __del__(self):
         try:
             self.close()
@@ -572,6 +586,60 @@ class Normalizer(_Stage):
         if stream is None:
             for t in (x, out, tap):
                 if t is not None:
+                    t.record_stream(e.stream)
+            e._post()
+
+
+class Encoder(_Stage):
+    """Output encodings of `batch` sequences (include/ptts.h: ptts_encoder; contract: `encoding.py`).  A row is dealt its
+    number of samples `n` (1 <= n <= `width`) and the name of its encoding (`set_row`) and starts as (`width`,
+    "pcm_s16le").  `frame(x, out)` turns one frame x[b, :n] into the first n * bytes_per_sample bytes of out[b], a uint8
+    [batch, `pitch`] tensor with `pitch` = `encoding.pitch(width)`, and writes nothing behind them.  The stage has no state
+    and no drain flag."""
+
+    _name, _destroy = "encoder", "ptts_encoder_destroy"
+
+    def __init__(self, engine: "Engine", batch: int, width: int):
+        from . import encoding
+
+        super().__init__(engine, batch)
+        self.width = self.in_max = self._in_width = int(width)
+        self.pitch = encoding.pitch(self.width)
+        self.rows = [(self.width, encoding.DEFAULT)] * batch  # host mirror: (n, encoding) of each row
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_encoder_create(engine.handle, batch, self.width, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _row_args(self, row):
+        return self.rows[row]
+
+    def _check_bytes(self, out):
+        shape = [self.batch, self.pitch]
+        if out is None or out.dtype != torch.uint8 or list(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"{self._name} output: expected a contiguous uint8 {shape} tensor")
+        if not out.is_cuda and not out.is_pinned():
+            raise ValueError(f"{self._name} output: a host tensor must be pinned")
+
+    def set_row(self, row: int, n: int, encoding: str | None = None, stream: torch.cuda.Stream | None = None):
+        """`row` holds `n` samples in `encoding` (None: "pcm_s16le") from now on.  Stream-ordered"""
+        from . import encoding as rule
+
+        name = rule.check(encoding)
+        _lib.check(self.engine.lib.ptts_encoder_set_row(self.handle, int(row), int(n), rule.CODE[name], self._sp(stream)))
+        self.rows[row] = (int(n), name)
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] on the device -> out u8[B, pitch], device or pinned host"""
+        e = self.engine
+        self._check_in(x)
+        self._check_bytes(out)
+        if stream is None:
+            e._pre()
+        _lib.check(e.lib.ptts_encode_frame(self.handle, _ptr(x), _ptr(out), self._sp(stream)))
+        if stream is None:
+            for t in (x, out):
+                if t.is_cuda:
                     t.record_stream(e.stream)
             e._post()
 
@@ -881,6 +949,9 @@ class Engine:
 
     def new_normalizer(self, batch: int, plans) -> Normalizer:
         return Normalizer(self, batch, plans)
+
+    def new_encoder(self, batch: int, width: int) -> Encoder:
+        return Encoder(self, batch, width)
 
     # ---- FlowLM
     def embed_text(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -1265,6 +1336,11 @@ class StepPipeline:
     its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec stream); rows start on the
     native rate, speed 1.0, pitch 1.0 and bypass.  With None / None / None / False / False nothing changes: same buffers,
     same graph nodes.
+
+    `encodings` (a list of names of `encoding.py`, e.g. ["mulaw", "alaw", "pcm_f32le"]; not in "fork" mode, not with
+    `pcm_i16`) ends the chain with the encoder, also here as `en`: `out[p]` are then pinned uint8 tensors and
+    `out_of(frame)[b, : route.n_out * route.bytes_per_sample]` are row b's bytes in its route's encoding; rows start on
+    "pcm_s16le".  None: no such stage, same buffers, same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
@@ -1272,16 +1348,16 @@ class StepPipeline:
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
                  lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False):
+                 pitches=None, loudness: bool = False, encodings=None):
         from .output_chain import ChainTable, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
         # the plan table first: what the rules refuse is refused before anything is allocated
-        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness)
+        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings)
         if not table.empty and self.mode == "fork":
-            raise ValueError("sample_rates / speeds / pitches / loudness / level: not available in the 'fork' mode")
+            raise ValueError("sample_rates / speeds / pitches / loudness / level / encodings: not available in the 'fork' mode")
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -1289,7 +1365,7 @@ class StepPipeline:
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
         self.rs, self.ts, self.lv, self.out = self.chain.rs, self.chain.ts, self.chain.lv, self.chain.out
-        self.ps, self.ln = self.chain.ps, self.chain.ln
+        self.ps, self.ln, self.en = self.chain.ps, self.chain.ln, self.chain.en
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host

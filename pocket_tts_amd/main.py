@@ -14,7 +14,10 @@ stretch.py; `generate --speed 1.25` is the same for one text), and with `--level
 (gain plus a look-ahead peak limiter on the GPU, level.py; `generate --gain-db 6 [--peak-dbfs -1]`), and with
 `--pitches 17/16,5/4,4/5` a per-request `pitch` (a frequency ratio; pitch shift on the GPU, pitch.py; `generate --pitch 17/16`
 or `generate --pitch-semitones 1` is the same for one text), and with `--loudness` a per-request `loudness_lufs` (a streaming
-BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--peak-dbfs -1]`).  `export-voice` encodes an audio prompt (first 30 s)
+BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--peak-dbfs -1]`), and with
+`--encodings mulaw,alaw,pcm_f32le` a per-request `encoding` (G.711 or float samples, encoded on the GPU, encoding.py;
+`generate --sample-rate 8000 --encoding mulaw` is the same for one text) and `container=raw` for the bytes without a WAV
+header.  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -34,43 +37,89 @@ DEFAULT_TEXT = ("Hello world. I am Kyutai's Pocket TTS. I'm fast enough to run o
 _STREAM_FRAMES = 1_000_000_000  # streaming: the length is not known up front, the header announces this many samples
 
 
-def _wav_header(n_samples: int, sample_rate: int) -> bytes:
-    """44-byte RIFF header of mono 16-bit PCM (the one `wave` writes)"""
-    data = 2 * n_samples
-    return struct.pack("<4sL4s4sLHHLLHH4sL", b"RIFF", 36 + data, b"WAVE", b"fmt ", 16, 1, 1, sample_rate, 2 * sample_rate,
-                       2, 16, b"data", data)
+def _wav_header(n_samples: int, sample_rate: int, encoding: str = "pcm_s16le") -> bytes:
+    """RIFF header of a mono file in `encoding` (encoding.py).  `pcm_s16le`: the 44 bytes `wave` writes.  The others are
+    no PCM in the sense of the format and get what it asks of those: an 18-byte `fmt ` chunk (cbSize 0) with the encoding's
+    format tag, a `fact` chunk with the number of samples, then `data`: 58 bytes."""
+    from .encoding import BYTES_PER_SAMPLE, WAV_FORMAT_TAG
+
+    bps = BYTES_PER_SAMPLE[encoding]
+    data = bps * n_samples
+    if encoding == "pcm_s16le":
+        return struct.pack("<4sL4s4sLHHLLHH4sL", b"RIFF", 36 + data, b"WAVE", b"fmt ", 16, 1, 1, sample_rate, 2 * sample_rate,
+                           2, 16, b"data", data)
+    return struct.pack("<4sL4s4sLHHLLHHH4sLL4sL", b"RIFF", 50 + data, b"WAVE", b"fmt ", 18, WAV_FORMAT_TAG[encoding], 1,
+                       sample_rate, bps * sample_rate, bps, 8 * bps, 0, b"fact", 4, n_samples, b"data", data)
 
 
-def wav_stream_bytes(chunks, sample_rate: int):
-    """The bytes of a streamed WAV: the provisional header, each chunk's 16-bit frames as soon as it arrives, then 200 ms
-    of silence.  fp32 chunks are clamped and converted like data/audio.py:79; int16 chunks (the batcher's
-    `pcm_format="i16"`) are already converted."""
+def _wav_offsets(encoding: str):
+    """(header length, offsets of the RIFF length, the `fact` sample count (None without one) and the `data` length)"""
+    return (44, 4, None, 40) if encoding == "pcm_s16le" else (58, 4, 46, 54)
+
+
+def wav_stream_bytes(chunks, sample_rate: int, encoding: str | None = None, header: bool = True):
+    """The bytes of a streamed WAV: the provisional header, each chunk's frames as soon as it arrives, then 200 ms of
+    silence.  `encoding` None or "pcm_s16le": 16-bit frames; fp32 chunks are clamped and converted like data/audio.py:79,
+    int16 chunks (the batcher's `pcm_format="i16"`, or its "pcm_s16le") are already converted.  Another `encoding`
+    (encoding.py): the chunks are what the encoder wrote, float32 for "pcm_f32le", uint8 for "mulaw" and "alaw", and their
+    bytes are written as they come; the silence is the encoding's own (FF in mu-law, D5 in A-law: a zero byte there is a
+    full-scale sample).  `header` False: the same without the header (the server's `container=raw`)."""
     import torch
 
-    yield _wav_header(_STREAM_FRAMES, sample_rate)
+    from . import encoding as rule
+
+    enc = rule.check(encoding)
+    if header:
+        yield _wav_header(_STREAM_FRAMES, sample_rate, enc)
     for chunk in chunks:
-        if chunk.dtype != torch.int16:
-            chunk = (chunk.clamp(-1, 1) * 32767).short()
+        if enc == rule.PCM_S16LE:
+            if chunk.dtype != torch.int16:
+                chunk = (chunk.clamp(-1, 1) * 32767).short()
+        elif chunk.dtype != rule.torch_dtype(enc):
+            raise ValueError(f"encoding {enc!r}: expected {rule.torch_dtype(enc)} chunks, got {chunk.dtype}")
         yield chunk.cpu().numpy().tobytes()
-    yield bytes(2 * int(sample_rate * 0.2))
+    yield rule.silence(enc, int(sample_rate * 0.2))
 
 
-def write_wav_stream(path, chunks, sample_rate: int) -> int:
-    """fp32 chunks -> clamp, int16, raw frames; 200 ms of trailing silence.  Returns samples written.  A file gets the
-    real lengths patched into its header at the end; stdout keeps the provisional one."""
+def write_wav_stream(path, chunks, sample_rate: int, encoding: str | None = None) -> int:
+    """fp32 chunks -> clamp, int16, raw frames (or, with `encoding`, the encoder's chunks as `wav_stream_bytes` takes them);
+    200 ms of trailing silence.  Returns samples written.  A file gets the real lengths patched into its header at the end;
+    stdout keeps the provisional one."""
+    from . import encoding as rule
+
+    enc = rule.check(encoding)
+    head, at_riff, at_fact, at_data = _wav_offsets(enc)
+    bps = rule.BYTES_PER_SAMPLE[enc]
     out = sys.stdout.buffer if path == "-" else open(path, "wb")
     n = 0
     with out:
-        for b in wav_stream_bytes(chunks, sample_rate):
+        for b in wav_stream_bytes(chunks, sample_rate, encoding):
             out.write(b)
             n += len(b)
-        n = (n - 44) // 2
+        n = (n - head) // bps
         if path != "-":
-            out.seek(4)
-            out.write(struct.pack("<L", 36 + 2 * n))
-            out.seek(40)
-            out.write(struct.pack("<L", 2 * n))
+            out.seek(at_riff)
+            out.write(struct.pack("<L", head - 8 + bps * n))
+            if at_fact is not None:
+                out.seek(at_fact)
+                out.write(struct.pack("<L", n))
+            out.seek(at_data)
+            out.write(struct.pack("<L", bps * n))
     return n
+
+
+def parse_encoding_list(text: str) -> list:
+    """"mulaw,alaw,pcm_f32le" -> ["mulaw", "alaw", "pcm_f32le"] (the `serve --encodings` value)"""
+    from .encoding import normalise_encodings
+
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    if not names:
+        raise argparse.ArgumentTypeError("expected at least one encoding")
+    try:
+        normalise_encodings(names)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return names
 
 
 def parse_rate_list(text: str) -> list:
@@ -140,6 +189,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "by sentence, with the peak limiter behind it; excludes --gain-db (default: none)")
     g.add_argument("--peak-dbfs", type=float, default=None,
                    help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db")
+    g.add_argument("--encoding", default=None, choices=["pcm_s16le", "pcm_f32le", "mulaw", "alaw"],
+                   help="Sample encoding of the WAV, encoded on the GPU: 16-bit PCM, 32-bit float, or ITU-T G.711 mu-law / A-law "
+                        "(telephony; use it with --sample-rate 8000).  Default: 16-bit PCM, converted on the host")
     g.add_argument("--output-path", default="./tts_output.wav")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
@@ -172,6 +224,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--loudness", action="store_true",
                    help="Requests may set a loudness target with the form field loudness_lufs (BS.1770 normaliser plus the "
                         "peak limiter on the GPU)")
+    s.add_argument("--encodings", type=parse_encoding_list, default=None, metavar="E1,E2,...",
+                   help="Sample encodings a request may choose with the form field encoding, among mulaw, alaw and pcm_f32le "
+                        "(pcm_s16le is always available); encoded on the GPU")
     s.add_argument("--level", action="store_true",
                    help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
                         "limiter on the GPU)")
@@ -208,7 +263,7 @@ def serve_app(args) -> int:
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
                      sample_rates=args.sample_rates, speeds=args.speeds, level=args.level, pitches=args.pitches,
-                     loudness=args.loudness)
+                     loudness=args.loudness, encodings=args.encodings)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -283,8 +338,8 @@ def cli_app(argv=None) -> int:
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
     chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                         seed=args.seed, **request)
-    write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate)
+                                         seed=args.seed, encoding=args.encoding, **request)
+    write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate, args.encoding)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)
     return 0

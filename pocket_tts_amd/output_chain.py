@@ -1,4 +1,4 @@
-"""The output chain codec -> resampler -> stretcher -> pitcher -> normaliser -> level as one object: what a pipeline's stages are (`ChainTable`), what
+"""The output chain codec -> resampler -> stretcher -> pitcher -> normaliser -> level -> encoder as one object: what a pipeline's stages are (`ChainTable`), what
 a request's row does in them (`Route`), and the stage objects and buffers on the device (`OutputChain`).
 
 The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `loudness.py` and `level.py`: it needs no library, no
@@ -12,6 +12,10 @@ ceil(preroll / n_out) further frames, which it reads as zeros, to get there - a 
 zeros enter at the first lagging stage: through the stretcher's flag where the row is stretched (what the stretcher emits
 past its tail is zero, which is what the stages behind it then read), else through the pitcher's where the row is pitched,
 else through the normaliser's where the row has a loudness target, else through the leveler's.
+
+The encoder (`encoding.py`) is the last stage where a table has one.  It has no state and no lag: it adds nothing to a row's
+pre-roll, and the zeros of a draining row reach it like any other sample.  Everything above counts samples; only the ring the
+encoder writes is in bytes, `bytes_per_sample` of the row's encoding to a sample.
 """
 
 from __future__ import annotations
@@ -19,6 +23,7 @@ from __future__ import annotations
 import numbers
 from dataclasses import dataclass
 
+from . import encoding as encoding_rule
 from . import level as level_rule
 from . import loudness as loud_rule
 from . import pitch as pitch_rule
@@ -41,7 +46,9 @@ class Route:
     gain_db, peak_dbfs), None for bypass; `n_out`: samples its frame yields at the end of the chain; `preroll`, `drain_frames`,
     `drain_stage` ("stretch", "pitch", "loud", "level" or None): the drain rule of the module's docstring; `pitch_plan`: its
     plan index in the pitcher (None without one), `pitched`: that plan is no identity plan; `loud`: (plan index in the
-    normaliser, loudness_lufs), None for bypass."""
+    normaliser, loudness_lufs), None for bypass; `encoding`: the name of the row's output encoding, None on a table without
+    the encoder, and `bytes_per_sample`: what a sample of it takes in the encoder's ring (None likewise: the ring's dtype
+    says)."""
 
     rate_index: int
     rate: int
@@ -55,6 +62,8 @@ class Route:
     pitch_plan: int | None = None
     pitched: bool = False
     loud: tuple | None = None
+    encoding: str | None = None
+    bytes_per_sample: int | None = None
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -74,10 +83,13 @@ class ChainTable:
     normaliser's `loud_plans` / `loud_index[(rate, n)]` (`loudness.table` over the lines the leveler gets; the leveler's
     plans are then built whatever `level` says, because the normaliser is always followed by the limiter).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
     speed, pitch or line the rules refuse raises their ValueError here, before anything is allocated.  `sample_rates` /
-    `speeds` / `pitches` None and `level` / `loudness` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none)."""
+    `speeds` / `pitches` None and `level` / `loudness` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none).
+    With `encodings` (a list of names of `encoding.py`) the chain ends with the encoder and `encodings` is the configured
+    list, `pcm_s16le` first; None: that stage does not exist.  A list makes the table non-empty even when the encoder is the
+    only stage.  `width` is the widest line that leaves the last stage before the encoder."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False):
+                 pitches=None, loudness: bool = False, encodings=None):
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
@@ -99,10 +111,13 @@ class ChainTable:
             self.loud_plans, self.loud_index = loud_rule.table(lines)
         if level or loudness:
             self.level_plans, self.level_index = level_rule.table(lines)
+        self.encodings = None if encodings is None else encoding_rule.normalise_encodings(encodings)
+        self.width = max(n for _, n in lines)
 
     @property
     def empty(self) -> bool:
-        return not self.has_rates and self.speeds is None and self.pitches is None and self.level_plans is None
+        return (not self.has_rates and self.speeds is None and self.pitches is None and self.level_plans is None
+                and self.encodings is None)
 
     def speeds_of(self) -> dict:
         """{rate: [the configured speeds admissible at that rate, 1.0 first]}"""
@@ -113,8 +128,11 @@ class ChainTable:
         """the configured pitches admissible on frames of `n` samples at `rate` Hz, 1.0 first"""
         return [p for j, p in enumerate(self.pitches) if self.pitch_index[(rate, n)][j] is not None]
 
-    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None) -> Route:
-        """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0, no loudness target.  A request
+    def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None,
+              encoding=None) -> Route:
+        """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0, no loudness target and, on a
+        table with the encoder, `pcm_s16le` (an encoding that is not configured, or any on a table without the encoder,
+        raises ValueError).  A request
         with a target gets the normaliser's plan and a leveler entry at gain 0 dB under its `peak_dbfs` (default -1).
         ValueError for a rate, speed or pitch that is not configured, a speed or pitch the plan rule refuses on the
         request's line (the message lists those it admits), a level `level.check` or a target `loudness.check` refuses,
@@ -167,9 +185,16 @@ class ChainTable:
                 preroll += self.level_plans[lvl[0]].LA
         elif gain_db is not None or peak_dbfs is not None:
             raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
+        bps = None
+        if self.encodings is not None:
+            encoding = encoding_rule.check(encoding, self.encodings)
+            bps = encoding_rule.BYTES_PER_SAMPLE[encoding]
+        elif encoding is not None:
+            raise ValueError(f"encoding {encoding!r}: this batcher writes one sample format for all (build it with encodings "
+                             "for per-request encodings)")
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
                      "stretch" if stretched else "pitch" if pitched else "loud" if loud is not None
-                     else "level" if lvl is not None else None, pplan, pitched, loud)
+                     else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps)
 
     @staticmethod
     def single(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None):
@@ -233,27 +258,43 @@ class OutputChain:
     """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `ln` / `lv` (`engine.Resampler`,
     `Stretcher`, `Pitcher`, `Normalizer`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
     [batch, widest line] tensors, int16 with `pcm_i16`, else float32, which the last stage writes.  An empty table creates
-    nothing: `out` is None and the codec writes its PCM as without a chain."""
+    nothing: `out` is None and the codec writes its PCM as without a chain.  On a table with `encodings` the chain ends with
+    `en` (`engine.Encoder`): `out` is then a ring of pinned uint8 [batch, encoding.pitch(widest line)] tensors that the encoder
+    writes, row b's n_out * bytes_per_sample bytes at the start of its row, `en_in` is the one device buffer the stage
+    before the encoder writes (None where the encoder is the only stage and reads the frame's PCM), and `pcm_i16` must be
+    left False (ValueError)."""
 
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
 
-        from .engine import Leveler, Normalizer, Pitcher, Resampler, Stretcher
+        from .engine import Encoder, Leveler, Normalizer, Pitcher, Resampler, Stretcher
 
+        if table.encodings is not None and pcm_i16:
+            raise ValueError("pcm_i16 and encodings exclude each other: with encodings a row asks for pcm_s16le itself")
         self.table = table
         self.rs = Resampler(engine, batch, table.sample_rates, table.rate_plans) if table.has_rates else None
         self.ts = Stretcher(engine, batch, table.stretch_plans) if table.speeds is not None else None
         self.ps = Pitcher(engine, batch, table.pitch_plans) if table.pitches is not None else None
         self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
-        self.out = self.rs_out = self.ps_in = self.ln_in = self.lv_in = None
+        self.out = self.rs_out = self.ps_in = self.ln_in = self.lv_in = self.en = self.en_in = None
         if table.empty:
             return
+        if table.encodings is not None:
+            self.en = Encoder(engine, batch, table.width)
         before_ps = self.ts if self.ts is not None else self.rs  # the stage before the pitcher, if any
         before_ln = self.ps if self.ps is not None else before_ps  # the stage before the normaliser, if any
         last = self.ln if self.ln is not None else before_ln       # the stage before the leveler, if any
-        width = self.lv.width if self.lv is not None else last.out_max
-        self.out = [torch.zeros(batch, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory() for _ in range(nb)]
+        width = self.lv.width if self.lv is not None else last.out_max if last is not None else table.width
+        if self.en is not None:
+            if width != self.en.width:
+                raise ValueError("encoding: the encoder's line is not the line of the stage before it")
+            self.out = [torch.zeros(batch, self.en.pitch, dtype=torch.uint8).pin_memory() for _ in range(nb)]
+            if self.lv is not None or last is not None:
+                self.en_in = torch.zeros(batch, width, device=engine.device)
+        else:
+            self.out = [torch.zeros(batch, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
+                        for _ in range(nb)]
         # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
         if self.lv is not None and last is not None:
             if last.out_max != width:
@@ -271,12 +312,13 @@ class OutputChain:
             self.rs_out = torch.zeros(batch, self.rs.out_max, device=engine.device)
 
     def stages(self):
-        return [s for s in (self.rs, self.ts, self.ps, self.ln, self.lv) if s is not None]
+        return [s for s in (self.rs, self.ts, self.ps, self.ln, self.lv, self.en) if s is not None]
 
     def attach(self, mimi_state, p: int):
         """the decodes / graph captures of `mimi_state` issued after this call end with the chain's launches and write
         ring slot `p` (the frame's PCM must then be a device tensor)"""
-        end = self.out[p] if self.lv is None else self.lv_in  # what the stage before the leveler writes
+        final = self.out[p] if self.en is None else self.en_in  # what the last stage before the encoder, if any, writes
+        end = final if self.lv is None else self.lv_in         # what the stage before the leveler writes
         if self.ln is not None:
             end = self.ln_in                                  # what the stage before the normaliser writes
         mid = end if self.ps is None else self.ps_in          # what the stage before the pitcher writes
@@ -289,9 +331,13 @@ class OutputChain:
         if self.ln is not None:
             mimi_state.set_loudnorm(self.ln, self.lv_in, self.ln_in)
         if self.lv is not None:
-            mimi_state.set_leveler(self.lv, self.out[p], self.lv_in)
+            mimi_state.set_leveler(self.lv, final, self.lv_in)
+        if self.en is not None:
+            mimi_state.set_encoder(self.en, self.out[p], self.en_in)
 
     def detach(self, mimi_state):
+        if self.en is not None:
+            mimi_state.set_encoder(None)
         if self.lv is not None:
             mimi_state.set_leveler(None)
         if self.ln is not None:
@@ -321,6 +367,8 @@ class OutputChain:
             self.ln.set_row(row, *(route.loud or (None, None)), stream)
         if self.lv is not None:
             self.lv.set_row(row, *(route.level or (None, None, None)), stream)
+        if self.en is not None:
+            self.en.set_row(row, route.n_out, route.encoding, stream)
 
     def drain_row(self, row: int, route: Route, stream=None):
         """from now on (stream-ordered) the row's incoming frames count as zeros at the stage `route.drain_stage` names"""

@@ -10,7 +10,11 @@ of the frequency ratios the server was started with that the plan rule of `pitch
 speed, a number or "P/Q", or 1), and on a
 server started with `level` the output level `gain_db` with its ceiling `peak_dbfs` (`level.py`), and on a server started
 with `loudness` the loudness target `loudness_lufs` (`loudness.py`; with `peak_dbfs` as its ceiling, without `gain_db`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
-the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.
+the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.  On a server started with `encodings` the
+field `encoding` chooses the sample encoding among them and `pcm_s16le` (`encoding.py`: ITU-T G.711 `mulaw` / `alaw`, or
+`pcm_f32le`), encoded on the GPU; header and silence follow it.  `container=raw` (default `wav`) leaves the header out: the
+encoded samples and the trailing silence as `application/octet-stream`, with the response headers `X-Audio-Encoding` and
+`X-Sample-Rate` - what a media-stream gateway forwards.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
 `urllib.parse` and the standard library's `email` header parser.
@@ -49,6 +53,8 @@ INDEX_HTML = """<!doctype html>
 <p>Pitch <input name="pitch" size="6"> as a frequency ratio, e.g. 17/16 or 0.8 (empty: 1)</p>
 <p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)</p>
 <p>Loudness <input name="loudness_lufs" size="5"> LUFS, e.g. -16 or -23, instead of a gain (empty: the model's own level)</p>
+<p>Encoding <input name="encoding" size="10"> pcm_s16le, pcm_f32le, mulaw or alaw, as far as the server was started with
+them (empty: pcm_s16le), container <select name="container"><option>wav</option><option>raw</option></select></p>
 <p><button type="submit">Speak</button></p>
 </form>
 </body></html>
@@ -275,9 +281,36 @@ def parse_loudness(fields: dict, enabled: bool):
         raise FormError(str(e)) from None
 
 
+def parse_encoding(fields: dict, encodings):
+    """the optional `encoding` field: its name, None where absent or empty.  `encodings`: what the server was started with
+    (None: without the encoder; `pcm_s16le` is then the one name it takes).  FormError listing what is configured for any
+    other name"""
+    from .encoding import DEFAULT, normalise_encodings
+
+    raw = fields.get("encoding")
+    if raw is None or raw.strip() == "":
+        return None
+    name = raw.strip()
+    configured = [DEFAULT] if encodings is None else normalise_encodings(encodings)
+    if name not in configured:
+        hint = "" if encodings is not None else "; this server was started without encodings"
+        raise FormError(f"encoding {name!r} is not configured (this server has {configured}{hint})")
+    return name
+
+
+def parse_container(fields: dict) -> str:
+    """the optional `container` field: "wav" (absent or empty) or "raw"; FormError for anything else"""
+    raw = (fields.get("container") or "").strip()
+    if raw in ("", "wav"):
+        return "wav"
+    if raw == "raw":
+        return "raw"
+    raise FormError(f"container must be 'wav' or 'raw', got {raw!r}")
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
                batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None,
-               level: bool = False, pitches=None, loudness: bool = False):
+               level: bool = False, pitches=None, loudness: bool = False, encodings=None):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
@@ -293,7 +326,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     admissible on one of the server's lines at least (ValueError here), and a request whose pitch its line does not admit gets
     a 400 with the admissible list.  `loudness`: requests may set a loudness target with `loudness_lufs` (and its ceiling
     with `peak_dbfs`; False: a request that sends it gets a 400, and the batcher's graphs are those of before).
-    `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    `encodings`: the sample encodings a request may choose with `encoding` besides `pcm_s16le` (`encoding.py`; None: only
+    that one, a request that names another gets a 400 with the configured list, and the batcher's graphs are those of
+    before).  The batcher is then built with `encodings` and its default `pcm_format`: every request's samples leave the GPU
+    in its own encoding.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
     from .output_chain import ChainTable
@@ -317,6 +353,11 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     if loudness:  # the normaliser's and the limiter's rules on every line (ValueError at start-up)
         ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, loudness=True)
 
+    if encodings is not None:
+        from .encoding import normalise_encodings
+
+        encodings = normalise_encodings(encodings)  # ValueError at start-up
+
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
     if batcher_factory is None:
@@ -326,6 +367,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         reserve = max_lsd if max_lsd != own_lsd else None
 
         def batcher_factory(model, slots, capacity):
+            if encodings is not None:  # the encoder writes every request's format, pcm_s16le included
+                return ContinuousBatcher(model, slots=slots, capacity=capacity, max_lsd_decode_steps=reserve,
+                                         sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
+                                         loudness=loudness, encodings=encodings)
             return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
                                      sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
                                      loudness=loudness)
@@ -433,6 +478,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
                 gain_db, peak_dbfs = parse_level(fields, level)
                 if gain_db is not None:
                     settings["gain_db"], settings["peak_dbfs"] = gain_db, peak_dbfs
+            enc = parse_encoding(fields, encodings)
+            if enc is not None and encodings is not None:
+                settings["encoding"] = enc
+            container = parse_container(fields)
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:
@@ -460,7 +509,12 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             for chunks in req.iter_batches():
                 yield chunks[0] if len(chunks) == 1 else torch.cat(chunks)
 
-        return StreamingResponse(wav_stream_bytes(frames(), rate or model.sample_rate), media_type="audio/wav",
+        out_rate = rate or model.sample_rate
+        if container == "raw":
+            return StreamingResponse(wav_stream_bytes(frames(), out_rate, enc, header=False),
+                                     media_type="application/octet-stream",
+                                     headers={"X-Audio-Encoding": enc or "pcm_s16le", "X-Sample-Rate": str(int(out_rate))})
+        return StreamingResponse(wav_stream_bytes(frames(), out_rate, enc), media_type="audio/wav",
                                  headers={"Content-Disposition": "attachment; filename=generated_speech.wav"})
 
     return app

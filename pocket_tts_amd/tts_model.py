@@ -193,12 +193,14 @@ class TTSModel:
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
                        frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
                        speed: float | None = None, gain_db: float | None = None, peak_dbfs: float | None = None,
-                       pitch=None, loudness_lufs: float | None = None, seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch` and `loudness_lufs` (not in
-        the reference): see `generate_audio_stream`."""
+                       pitch=None, loudness_lufs: float | None = None, encoding: str | None = None,
+                       seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs` and
+        `encoding` (not in the reference): see `generate_audio_stream`."""
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
                                                  seed=seed, sample_rate=sample_rate, speed=speed, gain_db=gain_db,
-                                                 peak_dbfs=peak_dbfs, pitch=pitch, loudness_lufs=loudness_lufs))
+                                                 peak_dbfs=peak_dbfs, pitch=pitch, loudness_lufs=loudness_lufs,
+                                                 encoding=encoding))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
@@ -206,7 +208,7 @@ class TTSModel:
                               frames_after_eos: int | None = None, copy_state: bool = True,
                               sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
                               peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
-                              seed: int | None = None):
+                              encoding: str | None = None, seed: int | None = None):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
 
         `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
@@ -236,6 +238,11 @@ class TTSModel:
         so far, clamped to +-20 dB, and the output lags by 400 ms like a levelled one.  The measurement restarts with every
         text chunk of a long text, so the gain can differ between the chunks.  None: as before.
 
+        `encoding` (not in the reference; "pcm_s16le", "pcm_f32le", "mulaw" or "alaw", `encoding.py`): the samples are
+        encoded on the GPU by the last stage of the output chain and the chunks are int16, float32 or uint8 tensors
+        accordingly, one element per sample: the 16-bit samples a WAV file holds, the float samples as they are, or ITU-T
+        G.711 bytes of those 16-bit samples.  None: fp32 chunks, as before.
+
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
         per-step copy, nothing read from torch's global generator - and `generate_audio_batch(seeds=...)` and
@@ -243,8 +250,11 @@ class TTSModel:
         from torch's global CPU generator, as in the reference."""
         if seed is not None:
             seed = check_seed(seed)
+        from . import encoding as encoding_rule
         from .output_chain import ChainTable
 
+        if encoding is not None:
+            encoding_rule.check(encoding)
         # the native rate, speed 1.0 and no gain become None: the call of before.  ValueError names the rule
         native, fs = int(self.config.mimi.sample_rate), self.engine.frame_samples
         loud, loud_peak = ChainTable.single_loudness(native, fs, sample_rate, speed, gain_db, peak_dbfs, loudness_lufs)
@@ -262,7 +272,7 @@ class TTSModel:
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
                                                               None if seed is None else chunk_seed(seed, i), *request,
-                                                              pitch=pitch, loudness_lufs=loud)
+                                                              pitch=pitch, loudness_lufs=loud, encoding=encoding)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -426,7 +436,7 @@ class TTSModel:
         """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
         recently used are released; a context in use is not in the cache"""
         keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:] or "level" in k[4:] or "pitch" in k[4:]
-                or "loud" in k[4:]]
+                or "loud" in k[4:] or "enc" in k[4:]]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
             c["pipe"].close()
@@ -503,7 +513,9 @@ class TTSModel:
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
                                           row_seed: int | None = None, sample_rate: int | None = None,
                                           speed: float | None = None, gain_db=None, peak_dbfs=None, pitch=None,
-                                          loudness_lufs=None):
+                                          loudness_lufs=None, encoding=None):
+        from . import encoding as encoding_rule
+
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
         Tt = tokens.shape[1]
@@ -527,6 +539,8 @@ class TTSModel:
             key = (*key, "pitch", pitch)
         if loudness_lufs is not None:  # likewise: the normaliser and the leveler (one context serves every target)
             key = (*key, "loud")
+        if encoding is not None:  # likewise: its codec graphs end with the encoder (one context serves all four encodings)
+            key = (*key, "enc")
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -535,12 +549,13 @@ class TTSModel:
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
             if not (sample_rate is None and speed is None and gain_db is None and pitch is None
-                    and loudness_lufs is None):  # with an output chain
+                    and loudness_lufs is None and encoding is None):  # with an output chain
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
             pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
                                 sample_rates=None if sample_rate is None else [sample_rate],
                                 speeds=None if speed is None else [speed], level=gain_db is not None,
-                                pitches=None if pitch is None else [pitch], loudness=loudness_lufs is not None)
+                                pitches=None if pitch is None else [pitch], loudness=loudness_lufs is not None,
+                                encodings=None if encoding is None else list(encoding_rule.NAMES))
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
         noise_host = ctx["noise_host"]
@@ -551,7 +566,7 @@ class TTSModel:
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         # the codec's carries and the row's rate, plan, gain and ceiling with a zero state in every stage, on the codec stream
-        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs)
+        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding)
         pipe.restart([route])
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
@@ -577,7 +592,10 @@ class TTSModel:
                     return pipe.pcm_of(frame)[0].clone()
                 lo, hi = route.take(pos, frames)  # frames are read in order: drop the pre-roll, stop at the chunk's end
                 pos += route.n_out
-                return pipe.out_of(frame)[0, lo:hi].clone()
+                if route.bytes_per_sample is None:
+                    return pipe.out_of(frame)[0, lo:hi].clone()
+                bps = route.bytes_per_sample  # the encoder's ring is in bytes: the samples as a typed view of them
+                return pipe.out_of(frame)[0, lo * bps:hi * bps].clone().view(encoding_rule.torch_dtype(route.encoding))
 
             for step in range(max_gen_len):
                 if yielded == 0 and emitted == 1:
