@@ -42,6 +42,7 @@ typedef struct ptts_stretcher ptts_stretcher;   /* speaking rates of B sequences
 typedef struct ptts_pitcher ptts_pitcher;       /* pitches of B sequences                */
 typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences          */
 typedef struct ptts_loudnorm ptts_loudnorm;     /* loudness targets of B sequences       */
+typedef struct ptts_tone ptts_tone;             /* tones (equaliser) of B sequences      */
 typedef struct ptts_encoder ptts_encoder;       /* output encodings of B sequences       */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
@@ -408,6 +409,37 @@ int ptts_loudnorm_frame(ptts_loudnorm *ln, const float *d_in, float *d_out, doub
  * its d_in: a frame enqueued with a normaliser but no leveler fails (-1).  NULL normaliser: off, decodes and captures are
  * launch for launch those of a state that never had one. */
 int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out);
+/* ---- Tone (no reference counterpart).  A toner holds, for B sequences, a table of plans, each row's plan and streaming
+ * state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of its line) into d_out
+ * f32[B, width] with row b's n samples at the front of its line (the rest of the line is neither read nor written).  A plan
+ * is a cascade of K <= 8 biquad sections for frames of n samples: section k runs in transposed direct form II in float64 on
+ * the output of section k - 1 from a zero state, and y is rounded to f32 once, after the last one; no lag, no pre-roll, no
+ * drain flag (contract, grammar and presets: pocket_tts_amd/tone.py).  Plan i is h_plans[3 i ..] = (rate, n, K) and
+ * h_doubles[360 i ..] = 8 x (b0 b1 b2 a1 a2), a0 = 1, followed by 8 x 10 row-major 2 x 2 matrices A_k^(chunk 2^j), j = 0 .. 9,
+ * chunk = ceil(n / 1024), A_k = [[-a1, 1], [-a2, 0]]: the powers of section k's state transition that the kernel's scan
+ * uses; the sections behind the K-th are zero.  A plan is refused (-1) unless 8000 <= rate <= 48000, 1 <= n <= 8192,
+ * 1 <= K <= 8 and every double is finite: with these every index the kernel forms is in bounds by construction
+ * (csrc/ptts_tone.h).  The plans are copied to the device once; a row is dealt one by its index, so a captured graph follows
+ * ptts_tone_set_row without recapture.  width is `line`, which no plan's n may exceed (-1), or with line == 0 the largest n
+ * of the plans (a tone need not be admissible on the widest line of the chain it sits in).  Every row starts on bypass: an exact copy of
+ * its whole line, no state.  A row's output depends on its own stream alone, bit for bit: not on its slot, not on the batch. */
+int ptts_tone_create(ptts_engine *e, int32_t batch, int32_t line, const int32_t *h_plans, int32_t n_plans,
+                     const double *h_doubles, int64_t n_doubles, ptts_tone **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_tone(state, NULL, ..) on its states */
+void ptts_tone_destroy(ptts_tone *tn);
+/* a new utterance joins `row`: its plan (-1: bypass) from now on; the sections' states are zeroed.  Stream-ordered on
+ * `stream`; captured graphs pick it up.  -1 for a row or a plan index out of range; nothing is enqueued. */
+int ptts_tone_set_row(ptts_tone *tn, int32_t row, int32_t plan_index, void *stream);
+/* One frame, one launch: d_in f32[B, width] -> d_out f32[B, width], both DEVICE memory and distinct (-1 otherwise); then
+ * the rows' states advance. */
+int ptts_tone_frame(ptts_tone *tn, const float *d_in, float *d_out, void *stream);
+/* While a toner is set, ptts_mimi_decode and the graph captures append the launch of ptts_tone_frame after the pitcher's
+ * and before the normaliser's.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own
+ * buffer; width must be frame_samples, -1 otherwise).  Otherwise it reads the f32 device buffer d_in [B, width], which the
+ * caller has given the preceding stage (resampler, stretcher or pitcher) as its `out`.  It writes d_out, which the caller
+ * gives the normaliser or the leveler as its d_in: a frame enqueued with a toner but no leveler fails (-1).  NULL toner: off,
+ * decodes and captures are launch for launch those of a state that never had one. */
+int ptts_mimi_set_tone(ptts_mimi_state *s, ptts_tone *tn, float *d_in, float *d_out);
 /* ---- Output encoding (no reference counterpart).  An encoder holds, for B sequences, each row's number of samples n and
  * encoding code: 0 pcm_s16le, 1 pcm_f32le, 2 mulaw, 3 alaw (contract: pocket_tts_amd/encoding.py).  It turns one frame
  * f32[B, width] of the previous output stage (row b's n samples at the front of its line) into out_bytes u8[B, pitch],

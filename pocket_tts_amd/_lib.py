@@ -150,6 +150,12 @@ PROTOTYPES = {
     "ptts_loudnorm_set_row_drain": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ptts_loudnorm_frame": (C.c_int, [_P, _P, _P, _P, _P]),
     "ptts_mimi_set_loudnorm": (C.c_int, [_P, _P, _P, _P]),
+    "ptts_tone_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double),
+                                   C.c_int64, C.POINTER(_P)]),
+    "ptts_tone_destroy": (None, [_P]),
+    "ptts_tone_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_tone_frame": (C.c_int, [_P, _P, _P, _P]),
+    "ptts_mimi_set_tone": (C.c_int, [_P, _P, _P, _P]),
     "ptts_encoder_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "ptts_encoder_destroy": (None, [_P]),
     "ptts_encoder_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
@@ -193,11 +199,11 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         kernel templates;
       * ptts_debug.hip = the C ABI's test hooks;
       * ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch,
-        ptts_pitch.hip = the pitch shifter, ptts_loud.hip = the loudness normaliser, ptts_level.hip = the output gain with
+        ptts_pitch.hip = the pitch shifter, ptts_tone.hip = the equaliser, ptts_loud.hip = the loudness normaliser, ptts_level.hip = the output gain with
         its peak limiter and ptts_encode.hip = the output encoder (16-bit and float PCM, G.711), each with its own part of the
         C ABI;
       * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
-    The first nine see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
+    The first ten see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
     libptts.so; a unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 

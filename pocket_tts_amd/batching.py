@@ -53,6 +53,11 @@ end with the encoder (`encoding.py`, `engine.Encoder`), which writes each row's 
 ring.  A request's chunks are then typed views of its bytes: int16 for `pcm_s16le`, float32 for `pcm_f32le`, uint8 for
 `mulaw` and `alaw` (ITU-T G.711).  The encoder does not lag: nothing of the above changes, and samples stay the unit of
 every count.
+
+A batcher built with `tones` lets a request choose its `tone` among them: the codec graphs run the equaliser (`tone.py`,
+`engine.Toner`) behind the pitcher and before the normaliser, and the leveler behind it as peak limiter.  The toner has a
+state but no lag, so it adds nothing to a row's pre-roll and has no drain flag: the zeros of a draining row ring out through
+it.  A toned row lags by the limiter's look-ahead like a levelled one.
 """
 
 from __future__ import annotations
@@ -169,7 +174,7 @@ class _Job:
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
                  max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None):
+                 pitches=None, loudness: bool = False, encodings=None, tones=None):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
@@ -197,6 +202,10 @@ class ContinuousBatcher:
         needs `pcm_format` left at its default (ValueError).  None: every request gets `pcm_format`, with the same graphs
         and buffers as before.
 
+        `tones` (a list of tones of `tone.py`: preset names such as "telephone" or band lists such as
+        "hp:120;peak:3000:4") lets each request choose its `tone` among them (`submit`); a toned request runs the peak
+        limiter behind the equaliser.  None: nobody is toned, with the same graphs and buffers as before.
+
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
         same graphs as before.
@@ -220,7 +229,7 @@ class ContinuousBatcher:
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
         # what the chain's rules refuse is refused before anything is allocated
-        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings)
+        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings, tones)
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -235,7 +244,7 @@ class ContinuousBatcher:
         self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                  mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
-                                 level=level, pitches=pitches, loudness=loudness, encodings=encodings)
+                                 level=level, pitches=pitches, loudness=loudness, encodings=encodings, tones=tones)
         self.chain = self.pipe.chain
         self.rs = self.pipe.rs
         self.ts = self.pipe.ts
@@ -243,6 +252,7 @@ class ContinuousBatcher:
         self.ps = self.pipe.ps
         self.ln = self.pipe.ln
         self.en = self.pipe.en
+        self.tn = self.pipe.tn
         # the output chain has a stage that may lag
         self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
         self.pipe.restart()
@@ -284,7 +294,7 @@ class ContinuousBatcher:
                eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
                sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
                peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
-               encoding: str | None = None, seed: int | None = None) -> Request:
+               encoding: str | None = None, tone: str | None = None, seed: int | None = None) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -309,7 +319,11 @@ class ContinuousBatcher:
         excludes `gain_db`, raises ValueError on a batcher built without `loudness` and needs frames_after_eos >= 1.  Each
         text chunk of a long request is measured on its own, so the gain can differ between the chunks.  `encoding`: the
         name of the request's output encoding, one of the batcher's `encodings` or "pcm_s16le" (None: "pcm_s16le"); a name
-        that is not configured raises ValueError, as does any on a batcher built without `encodings`."""
+        that is not configured raises ValueError, as does any on a batcher built without `encodings`.  `tone`: the
+        request's tone, one of the batcher's `tones` (compared in the canonical form of `tone.normalise`; None, "" or "flat":
+        none); a tone that is not configured, or that the request's rate refuses, raises ValueError, as does any on a
+        batcher built without `tones`.  It combines freely with `gain_db` and `loudness_lufs`; alone it runs the limiter at
+        gain 0 dB under `peak_dbfs` (default -1), so a toned request needs frames_after_eos >= 1."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -336,7 +350,7 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
-        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding)
+        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding, tone)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -371,6 +385,9 @@ class ContinuousBatcher:
             if route.loud is not None and fae < 1:
                 raise ValueError("a request with a loudness target needs frames_after_eos >= 1: the row is set to drain "
                                  "before the frame that follows its last one is queued")
+            if route.toned and fae < 1:
+                raise ValueError("a request with a tone needs frames_after_eos >= 1: the row is set to drain before the "
+                                 "frame that follows its last one is queued")
             if route.level is not None and fae < 1:
                 raise ValueError("a request with a gain needs frames_after_eos >= 1: the row is set to drain before the "
                                  "frame that follows its last one is queued")

@@ -2221,6 +2221,24 @@ extern "C" int ptts_mimi_set_pitcher(ptts_mimi_state *s, ptts_pitcher *ps, float
   return 0;
 }
 
+// Tone: while a toner is set, its launch follows the pitch launch and precedes the normaliser's.  d_in == NULL: it reads the
+// frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  It always
+// writes f32 into the device buffer d_out, which the normaliser or the leveler then reads: a frame enqueued with a toner but
+// no leveler fails.  NULL switches it off: decodes and captures are then launch for launch what they were.
+extern "C" int ptts_mimi_set_tone(ptts_mimi_state *s, ptts_tone *tn, float *d_in, float *d_out) {
+  if (!s) return fail(-1, "null state");
+  if (tn && !d_out) return fail(-1, "set_tone: null output");
+  if (tn && d_in == d_out) return fail(-1, "set_tone: the stage does not work in place");
+  if (tn && tone_batch(tn) != s->B) return fail(-1, "set_tone: the toner's batch is not the state's");
+  if (tn && !d_in && tone_width(tn) != s->rows[3]) return fail(-1, "set_tone: the toner's frame length is not the state's");
+  if (tn && d_in && !s->rs && !s->ts && !s->ps)
+    return fail(-1, "set_tone: an input buffer needs a resampler, a stretcher or a pitcher on the state");
+  s->tn = tn;
+  s->tn_in = tn ? d_in : nullptr;
+  s->tn_out = tn ? d_out : nullptr;
+  return 0;
+}
+
 // Loudness: while a normaliser is set, its launch follows the pitch launch and precedes the level launch.  d_in == NULL: it
 // reads the frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  It
 // always writes f32 into the device buffer d_out, which the leveler then reads: a frame enqueued with a normaliser but no
@@ -2231,8 +2249,8 @@ extern "C" int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, flo
   if (ln && d_in == d_out) return fail(-1, "set_loudnorm: the stage does not work in place");
   if (ln && loud_batch(ln) != s->B) return fail(-1, "set_loudnorm: the normaliser's batch is not the state's");
   if (ln && !d_in && loud_width(ln) != s->rows[3]) return fail(-1, "set_loudnorm: the normaliser's frame length is not the state's");
-  if (ln && d_in && !s->rs && !s->ts && !s->ps)
-    return fail(-1, "set_loudnorm: an input buffer needs a resampler, a stretcher or a pitcher on the state");
+  if (ln && d_in && !s->rs && !s->ts && !s->ps && !s->tn)
+    return fail(-1, "set_loudnorm: an input buffer needs a resampler, a stretcher, a pitcher or a toner on the state");
   s->ln = ln;
   s->ln_in = ln ? d_in : nullptr;
   s->ln_out = ln ? d_out : nullptr;
@@ -2247,8 +2265,8 @@ extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float
   if (lv && !out) return fail(-1, "set_leveler: null output");
   if (lv && level_batch(lv) != s->B) return fail(-1, "set_leveler: the leveler's batch is not the state's");
   if (lv && !d_in && level_width(lv) != s->rows[3]) return fail(-1, "set_leveler: the leveler's frame length is not the state's");
-  if (lv && d_in && !s->rs && !s->ts && !s->ps && !s->ln)
-    return fail(-1, "set_leveler: an input buffer needs a resampler, a stretcher, a pitcher or a normaliser on the state");
+  if (lv && d_in && !s->rs && !s->ts && !s->ps && !s->tn && !s->ln)
+    return fail(-1, "set_leveler: an input buffer needs a resampler, a stretcher, a pitcher, a toner or a normaliser on the state");
   s->lv = lv;
   s->lv_in = lv ? d_in : nullptr;
   s->lv_out = lv ? out : nullptr;
@@ -2282,12 +2300,13 @@ extern "C" int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float
 // the codec frame, then the launches of the output stages the state has
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
   if (s->ln && !s->lv) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
+  if (s->tn && !s->lv) return fail(-1, "the toner must be followed by a leveler, but the state has none");
   // the stage the encoder follows: 4 leveler, 3 pitcher, 2 stretcher, 1 resampler, 0 none; -1 without an encoder
   const int fed = !s->en ? -1 : s->lv ? 4 : s->ps ? 3 : s->ts ? 2 : s->rs ? 1 : 0;
   if (s->en && (fed > 0) != (s->en_in != nullptr))
     return fail(-1, "the encoder's input buffer and the state's output stages do not go together");
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
-  if (!s->rs && !s->ts && !s->ps && !s->ln && !s->lv && !s->en) return 0;
+  if (!s->rs && !s->ts && !s->ps && !s->tn && !s->ln && !s->lv && !s->en) return 0;
   const bool chained = s->ts && s->ts_in;  // resampler -> ts_in -> stretcher
   if (chained && !s->rs) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
   int r = 0;
@@ -2307,6 +2326,11 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
     SITE("pitch");
     r = pitch_enqueue(st, s->ps, s->ps_in ? s->ps_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 3 ? (void *)s->en_in : s->ps_out,
                       fed == 3 ? 0 : s->ps_i16, nullptr, nullptr);
+    SITE("");
+  }
+  if (r == 0 && s->tn) {
+    SITE("tone");
+    r = tone_enqueue(st, s->tn, s->tn_in ? s->tn_in : (d_pcm ? d_pcm : s->pcm_dbg), s->tn_out);
     SITE("");
   }
   if (r == 0 && s->ln) {

@@ -65,6 +65,14 @@ int loud_enqueue(hipStream_t st, ptts_loudnorm *ln, const float *d_in, float *d_
 int loud_batch(const ptts_loudnorm *ln);
 int loud_width(const ptts_loudnorm *ln);
 
+// ---- ptts_tone.hip: per-request tone (a streaming cascade of biquad sections, between the pitcher and the normaliser) -----
+// the frame's launch on `st`: d_in f32[B][width] (device) -> d_out f32[B][width] (device, never d_in).  Returns 0 or a
+// negative error code (message recorded).
+struct ptts_tone;
+int tone_enqueue(hipStream_t st, ptts_tone *tn, const float *d_in, float *d_out);
+int tone_batch(const ptts_tone *tn);
+int tone_width(const ptts_tone *tn);
+
 // ---- ptts_pitch.hip: per-request pitch (streaming WSOLA + polyphase FIR, between the stretcher and the leveler) ---------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host); d_delta
 // (i32 [B][k_max], or null) and d_mid (f32 [B][mid_max], or null) receive the hops' deltas and the frame's mid samples.

@@ -269,6 +269,11 @@ struct ptts_mimi_state {
   float *ps_in = nullptr;
   void *ps_out = nullptr;
   int ps_i16 = 0;
+  // tone (ptts_mimi_set_tone): the toner's launch follows the pitch launch and precedes the normaliser's; it reads the
+  // frame's PCM (tn_in == nullptr) or tn_in, the buffer the stage before it writes, and writes f32 into tn_out
+  ptts_tone *tn = nullptr;
+  float *tn_in = nullptr;
+  float *tn_out = nullptr;
   // loudness (ptts_mimi_set_loudnorm): the normaliser's launch follows the pitch launch and precedes the level launch; it
   // reads the frame's PCM (ln_in == nullptr) or ln_in, the buffer the stage before it writes, and writes f32 into ln_out
   ptts_loudnorm *ln = nullptr;

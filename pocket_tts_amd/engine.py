@@ -277,6 +277,22 @@ class MimiState:
         _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, lv.handle, _ptr(mid) if mid is not None else None,
                                                          _ptr(out), int(out.dtype == torch.int16)))
 
+    def set_tone(self, tn: "Toner | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `tn` behind the pitcher's launch (if any) and before the
+        normaliser's, writing float32 into the device tensor `out` [B, tn.width], which the caller gives the normaliser or
+        the leveler as its `mid` (include/ptts.h: ptts_mimi_set_tone; a frame with a toner but no leveler fails).  `mid`
+        None: it reads the frame's PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid`
+        [B, tn.width], which the caller has given the resampler, the stretcher or the pitcher set on this state as its
+        output.  None: off."""
+        if tn is None:
+            _lib.check(self.engine.lib.ptts_mimi_set_tone(self.handle, None, None, None))
+            return
+        tn._check_in(out)
+        if mid is not None:
+            tn._check_in(mid)
+        _lib.check(self.engine.lib.ptts_mimi_set_tone(self.handle, tn.handle, _ptr(mid) if mid is not None else None,
+                                                      _ptr(out)))
+
     def set_loudnorm(self, ln: "Normalizer | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
         """The decodes / graph captures issued after this call run `ln` behind the pitcher's launch (if any) and before the
         leveler's, writing float32 into the device tensor `out` [B, ln.width], which the caller gives the leveler as its
@@ -644,6 +660,57 @@ class Encoder(_Stage):
             e._post()
 
 
+class Toner(_Stage):
+    """Tones of `batch` sequences (include/ptts.h: ptts_tone; contract, grammar and plan rule: `tone.py`).  `plans` is a list
+    of `tone.TonePlan`; a row is dealt a plan by its index (`set_row`; None: bypass) and starts on bypass.  `frame(x, out)`
+    turns one frame x[b, :n(plan of b)] into out[b, :n(plan of b)] through the plan's cascade of biquad sections, with no
+    lag; the sections' states are carried from frame to frame.  A bypass row's whole line is copied.  `width` is the line's
+    width, the largest n of the plans where it is left out.  The output is always float32 on the device: the stage is never
+    the last one."""
+
+    _name, _destroy = "toner", "ptts_tone_destroy"
+
+    def __init__(self, engine: "Engine", batch: int, plans, width: int | None = None):
+        super().__init__(engine, batch)
+        self.plans = list(plans)
+        self.width = max(p.n for p in self.plans) if width is None else int(width)
+        self.in_max = self.out_max = self._in_width = self._out_width = self.width
+        self.row_plan = [-1] * batch  # host mirror of the rows' plan indices
+        n = len(self.plans)
+        ints = (C.c_int32 * (3 * n))(*[v for p in self.plans for v in p.ints()])
+        doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_tone_create(engine.handle, batch, self.width, ints, n,
+                                               doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _row_args(self, row):
+        return (self.row_plan[row],)
+
+    def set_row(self, row: int, plan_index: int | None = None, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` with a zero state; None or -1: the row bypasses the stage.
+        Stream-ordered"""
+        idx = -1 if plan_index is None else int(plan_index)
+        if not -1 <= idx < len(self.plans):
+            raise ValueError(f"toner plan index {plan_index!r} out of range")
+        _lib.check(self.engine.lib.ptts_tone_set_row(self.handle, int(row), idx, self._sp(stream)))
+        self.row_plan[row] = idx
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] -> out f32[B, width], both on the device and distinct"""
+        e = self.engine
+        self._check_in(x)
+        self._check_in(out)
+        if stream is None:
+            e._pre()
+        _lib.check(e.lib.ptts_tone_frame(self.handle, _ptr(x), _ptr(out), self._sp(stream)))
+        if stream is None:
+            for t in (x, out):
+                t.record_stream(e.stream)
+            e._post()
+
+
 class Resampler(_Stage):
     """Output sample rates of `batch` sequences (include/ptts.h: ptts_resampler; filters and admission rules:
     `resample.py`).  `rates[0]` is always the codec's native rate - what a row without a rate of its own runs at - followed
@@ -949,6 +1016,9 @@ class Engine:
 
     def new_normalizer(self, batch: int, plans) -> Normalizer:
         return Normalizer(self, batch, plans)
+
+    def new_toner(self, batch: int, plans, width: int | None = None) -> Toner:
+        return Toner(self, batch, plans, width)
 
     def new_encoder(self, batch: int, width: int) -> Encoder:
         return Encoder(self, batch, width)
@@ -1341,6 +1411,10 @@ class StepPipeline:
     `pcm_i16`) ends the chain with the encoder, also here as `en`: `out[p]` are then pinned uint8 tensors and
     `out_of(frame)[b, : route.n_out * route.bytes_per_sample]` are row b's bytes in its route's encoding; rows start on
     "pcm_s16le".  None: no such stage, same buffers, same graph nodes.
+
+    `tones` (a list of tones of `tone.py`, preset names or band lists, e.g. ["telephone", "hp:120;peak:3000:4"]; not in
+    "fork" mode; it brings the leveler with it) puts the toner, also here as `tn`, between the pitcher and the normaliser;
+    rows start on bypass.  None: no such stage, same buffers, same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
@@ -1348,16 +1422,18 @@ class StepPipeline:
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
                  lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None):
+                 pitches=None, loudness: bool = False, encodings=None, tones=None):
         from .output_chain import ChainTable, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
         # the plan table first: what the rules refuse is refused before anything is allocated
-        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings)
+        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings,
+                           tones)
         if not table.empty and self.mode == "fork":
-            raise ValueError("sample_rates / speeds / pitches / loudness / level / encodings: not available in the 'fork' mode")
+            raise ValueError("sample_rates / speeds / pitches / tones / loudness / level / encodings: not available in the "
+                             "'fork' mode")
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
         # hiccup of one stalls the other); the latency modes need only 2.  A host loop over the "events" mode must have
@@ -1365,7 +1441,7 @@ class StepPipeline:
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
         self.rs, self.ts, self.lv, self.out = self.chain.rs, self.chain.ts, self.chain.lv, self.chain.out
-        self.ps, self.ln, self.en = self.chain.ps, self.chain.ln, self.chain.en
+        self.ps, self.ln, self.en, self.tn = self.chain.ps, self.chain.ln, self.chain.en, self.chain.tn
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host

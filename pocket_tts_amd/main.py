@@ -17,7 +17,8 @@ or `generate --pitch-semitones 1` is the same for one text), and with `--loudnes
 BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--peak-dbfs -1]`), and with
 `--encodings mulaw,alaw,pcm_f32le` a per-request `encoding` (G.711 or float samples, encoded on the GPU, encoding.py;
 `generate --sample-rate 8000 --encoding mulaw` is the same for one text) and `container=raw` for the bytes without a WAV
-header.  `export-voice` encodes an audio prompt (first 30 s)
+header, and with `--tones telephone,warm,"hp:120;peak:3000:4"` a per-request `tone` (a parametric equaliser on the GPU,
+tone.py; `generate --tone telephone` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -122,6 +123,20 @@ def parse_encoding_list(text: str) -> list:
     return names
 
 
+def parse_tone_list(text: str) -> list:
+    """"telephone,warm,hp:120;peak:3000:4" -> ["telephone", "warm", "hp:120;peak:3000:4"] (the `serve --tones` value): tones
+    are joined by commas, the bands of one tone by semicolons"""
+    from .tone import normalise_tones
+
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    try:
+        if not normalise_tones(names):
+            raise ValueError("expected at least one tone")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return names
+
+
 def parse_rate_list(text: str) -> list:
     """"8000,16000,48000" -> [8000, 16000, 48000] (the `serve --sample-rates` value)"""
     try:
@@ -187,8 +202,13 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--loudness-lufs", type=float, default=None, metavar="LUFS",
                    help="Loudness target in LUFS, in [-40, -10] (e.g. -16, -23): normalised on the GPU by ITU-R BS.1770-4, sentence "
                         "by sentence, with the peak limiter behind it; excludes --gain-db (default: none)")
+    g.add_argument("--tone", default=None, metavar="TONE",
+                   help="Tone: a preset (telephone, warm, bright, presence, small_speaker, deess) or a band list "
+                        "kind:f0[:gain_db[:q]];... with kinds hp, lp, peak, lowshelf, highshelf, e.g. \"hp:120;peak:3000:4\": "
+                        "equalised on the GPU, with the peak limiter behind it (default: none)")
     g.add_argument("--peak-dbfs", type=float, default=None,
-                   help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db")
+                   help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db, "
+                        "--loudness-lufs or --tone")
     g.add_argument("--encoding", default=None, choices=["pcm_s16le", "pcm_f32le", "mulaw", "alaw"],
                    help="Sample encoding of the WAV, encoded on the GPU: 16-bit PCM, 32-bit float, or ITU-T G.711 mu-law / A-law "
                         "(telephony; use it with --sample-rate 8000).  Default: 16-bit PCM, converted on the host")
@@ -227,6 +247,10 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--encodings", type=parse_encoding_list, default=None, metavar="E1,E2,...",
                    help="Sample encodings a request may choose with the form field encoding, among mulaw, alaw and pcm_f32le "
                         "(pcm_s16le is always available); encoded on the GPU")
+    s.add_argument("--tones", type=parse_tone_list, default=None, metavar="T1,T2,...",
+                   help="Tones a request may choose with the form field tone: presets or band lists, e.g. "
+                        "telephone,warm,hp:120;peak:3000:4 (bands are joined by ';', tones by ','); equalised on the GPU, with "
+                        "the peak limiter behind")
     s.add_argument("--level", action="store_true",
                    help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
                         "limiter on the GPU)")
@@ -263,7 +287,7 @@ def serve_app(args) -> int:
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
                      sample_rates=args.sample_rates, speeds=args.speeds, level=args.level, pitches=args.pitches,
-                     loudness=args.loudness, encodings=args.encodings)
+                     loudness=args.loudness, encodings=args.encodings, tones=args.tones)
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -302,16 +326,25 @@ def cli_app(argv=None) -> int:
     from .output_chain import ChainTable
 
     request = {}
-    checks = [("--sample-rate", ("sample_rate",)), ("--speed", ("speed",))]
+    checks = [("--sample-rate", ("sample_rate",)), ("--speed", ("speed",)), ("--tone", ())]
     if args.loudness_lufs is None:  # with a loudness target the ceiling belongs to it: both are checked below
         checks.append(("--gain-db / --peak-dbfs", ("gain_db", "peak_dbfs")))
+    tone = None
     for flag, names in checks:
         request.update({k: getattr(args, k) for k in names})
         try:
-            ChainTable.single(int(model.sample_rate), model.engine.frame_samples, **request)
+            if flag == "--tone":  # behind the rate and the speed, before the level: a tone alone brings the limiter
+                tone = ChainTable.single_tone(int(model.sample_rate), model.engine.frame_samples, args.sample_rate, args.speed,
+                                              args.tone)
+                continue
+            asked = dict(request)
+            if tone is not None and asked.get("gain_db") is None and "peak_dbfs" in asked:
+                asked["gain_db"] = 0.0
+            ChainTable.single(int(model.sample_rate), model.engine.frame_samples, **asked)
         except ValueError as e:
             logger.error("%s: %s", flag, e)
             return 1
+    request["tone"] = tone
     if args.loudness_lufs is not None:
         try:
             ChainTable.single_loudness(int(model.sample_rate), model.engine.frame_samples, args.sample_rate, args.speed,

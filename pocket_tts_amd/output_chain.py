@@ -1,10 +1,10 @@
-"""The output chain codec -> resampler -> stretcher -> pitcher -> normaliser -> level -> encoder as one object: what a pipeline's stages are (`ChainTable`), what
+"""The output chain codec -> resampler -> stretcher -> pitcher -> tone -> normaliser -> level -> encoder as one object: what a pipeline's stages are (`ChainTable`), what
 a request's row does in them (`Route`), and the stage objects and buffers on the device (`OutputChain`).
 
-The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `loudness.py` and `level.py`: it needs no library, no
+The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `tone.py`, `loudness.py` and `level.py`: it needs no library, no
 GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
 yields, how many leading samples to drop, how many drain frames flush its tail and which stage's drain flag to raise - is a
-`Route`; nothing outside this module composes the five plan rules.
+`Route`; nothing outside this module composes the six plan rules.
 
 The drain rule: a row's pre-roll is the SUM of its stages' pre-rolls (the stretcher's and the pitcher's, 0 on an identity plan,
 plus the normaliser's delay and the leveler's look-ahead, each 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
@@ -12,6 +12,10 @@ ceil(preroll / n_out) further frames, which it reads as zeros, to get there - a 
 zeros enter at the first lagging stage: through the stretcher's flag where the row is stretched (what the stretcher emits
 past its tail is zero, which is what the stages behind it then read), else through the pitcher's where the row is pitched,
 else through the normaliser's where the row has a loudness target, else through the leveler's.
+
+The toner (`tone.py`) sits between the pitcher and the normaliser.  It has state but no lag and no drain flag: it adds nothing
+to a row's pre-roll, the zeros of a draining row ring out through it, and `drain_stage` never names it.  A toned row always
+runs the limiter behind it, because a boost creates peaks; so its pre-roll is what the stages behind the tone add.
 
 The encoder (`encoding.py`) is the last stage where a table has one.  It has no state and no lag: it adds nothing to a row's
 pre-roll, and the zeros of a draining row reach it like any other sample.  Everything above counts samples; only the ring the
@@ -28,6 +32,7 @@ from . import level as level_rule
 from . import loudness as loud_rule
 from . import pitch as pitch_rule
 from . import resample, stretch
+from . import tone as tone_rule
 
 
 def rate_index(rates, rate) -> int:
@@ -48,7 +53,7 @@ class Route:
     plan index in the pitcher (None without one), `pitched`: that plan is no identity plan; `loud`: (plan index in the
     normaliser, loudness_lufs), None for bypass; `encoding`: the name of the row's output encoding, None on a table without
     the encoder, and `bytes_per_sample`: what a sample of it takes in the encoder's ring (None likewise: the ring's dtype
-    says)."""
+    says); `tone_plan`: its plan index in the toner (None: bypass, or no toner), `toned`: it has one."""
 
     rate_index: int
     rate: int
@@ -64,6 +69,8 @@ class Route:
     loud: tuple | None = None
     encoding: str | None = None
     bytes_per_sample: int | None = None
+    tone_plan: int | None = None
+    toned: bool = False
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -86,10 +93,13 @@ class ChainTable:
     `speeds` / `pitches` None and `level` / `loudness` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none).
     With `encodings` (a list of names of `encoding.py`) the chain ends with the encoder and `encodings` is the configured
     list, `pcm_s16le` first; None: that stage does not exist.  A list makes the table non-empty even when the encoder is the
-    only stage.  `width` is the widest line that leaves the last stage before the encoder."""
+    only stage.  `width` is the widest line that leaves the last stage before the encoder.  With `tones` (a list of tones of
+    `tone.py`) the toner's `tone_plans` / `tone_index[(rate, n)][tone index]` (`tone.table` over the lines the pitcher leaves,
+    None where the rate refuses a tone) and `tones`, the configured list in canonical form; the leveler's plans are then built
+    whatever `level` says, because a toned row is always followed by the limiter.  None: that stage does not exist."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None):
+                 pitches=None, loudness: bool = False, encodings=None, tones=None):
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
@@ -106,10 +116,16 @@ class ChainTable:
                      for i in row if i is not None]
         if self.pitches is not None:
             self.pitch_plans, self.pitch_index = pitch_rule.table(lines, self.pitches)
+        self.tones = None if tones is None else tone_rule.normalise_tones(tones)
+        self.tone_plans = self.tone_index = None
+        if self.tones is not None:
+            if not self.tones:
+                raise ValueError("tones: the list holds no tone but the bypass, which every request has anyway")
+            self.tone_plans, self.tone_index = tone_rule.table(lines, self.tones)
         self.loud_plans = self.loud_index = None
         if loudness:
             self.loud_plans, self.loud_index = loud_rule.table(lines)
-        if level or loudness:
+        if level or loudness or self.tones is not None:
             self.level_plans, self.level_index = level_rule.table(lines)
         self.encodings = None if encodings is None else encoding_rule.normalise_encodings(encodings)
         self.width = max(n for _, n in lines)
@@ -128,15 +144,22 @@ class ChainTable:
         """the configured pitches admissible on frames of `n` samples at `rate` Hz, 1.0 first"""
         return [p for j, p in enumerate(self.pitches) if self.pitch_index[(rate, n)][j] is not None]
 
+    def tones_of(self, rate: int, n: int) -> list:
+        """the configured tones admissible on frames of `n` samples at `rate` Hz"""
+        return [t for j, t in enumerate(self.tones) if self.tone_index[(rate, n)][j] is not None]
+
     def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None,
-              encoding=None) -> Route:
+              encoding=None, tone=None) -> Route:
         """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0, no loudness target and, on a
         table with the encoder, `pcm_s16le` (an encoding that is not configured, or any on a table without the encoder,
         raises ValueError).  A request
         with a target gets the normaliser's plan and a leveler entry at gain 0 dB under its `peak_dbfs` (default -1).
         ValueError for a rate, speed or pitch that is not configured, a speed or pitch the plan rule refuses on the
         request's line (the message lists those it admits), a level `level.check` or a target `loudness.check` refuses,
-        `loudness_lufs` together with `gain_db`, and for any of them on a table without that stage."""
+        `loudness_lufs` together with `gain_db`, and for any of them on a table without that stage.  `tone` (None, "" or
+        "flat": bypass) must be one of the configured tones (compared in canonical form) that the row's rate admits; a toned
+        request gets a leveler entry at gain 0 dB under its `peak_dbfs` (default -1) unless it has a gain or a loudness
+        target, with both of which it combines freely."""
         r = 0
         if self.has_rates:
             r = rate_index(self.rates, sample_rate)
@@ -169,6 +192,19 @@ class ChainTable:
         elif pitch is not None and float(pitch_rule.fraction(pitch)) != 1.0:
             raise ValueError(f"pitch {pitch!r}: this batcher speaks at pitch 1.0 only (build it with pitches for per-request "
                              "pitches)")
+        tplan, canon = None, tone_rule.normalise(tone)
+        if self.tones is not None:
+            if canon is not None:
+                if canon not in self.tones:
+                    raise ValueError(f"tone {tone!r} is not configured (this pipeline has {self.tones})")
+                tplan = self.tone_index[(rate, n_out)][self.tones.index(canon)]
+                if tplan is None:
+                    raise ValueError(f"tone {tone!r} is not admissible at {rate} Hz (admissible there: "
+                                     f"{self.tones_of(rate, n_out)})")
+                if gain_db is None and loudness_lufs is None:
+                    gain_db = 0.0  # the limiter behind the tone
+        elif canon is not None:
+            raise ValueError(f"tone {tone!r}: this batcher has no tone stage (build it with tones for per-request tones)")
         lvl = loud = None
         if self.loud_plans is not None:
             target = loud_rule.check_with(loudness_lufs, gain_db)
@@ -194,7 +230,7 @@ class ChainTable:
                              "for per-request encodings)")
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
                      "stretch" if stretched else "pitch" if pitched else "loud" if loud is not None
-                     else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps)
+                     else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps, tplan, tplan is not None)
 
     @staticmethod
     def single(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None):
@@ -240,6 +276,18 @@ class ChainTable:
         return pitch_rule.plan(f, *ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)).pitch
 
     @staticmethod
+    def single_tone(native_rate: int, frame_samples: int, sample_rate=None, speed=None, tone=None):
+        """The tone of one request that gets a chain of its own, behind that request's rate and speed (the pitcher keeps the
+        line): its canonical string, None for the bypass.  ValueError with the message of the rule that refuses."""
+        canon = tone_rule.normalise(tone)
+        if canon is None:
+            return None
+        rate, n = ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)
+        tone_rule.plan(rate, n, canon)
+        level_rule.plan(rate, n)
+        return canon
+
+    @staticmethod
     def single_loudness(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
                         loudness_lufs=None):
         """The loudness target of one request that gets a chain of its own, behind that request's rate and speed (the
@@ -255,8 +303,8 @@ class ChainTable:
 
 
 class OutputChain:
-    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `ln` / `lv` (`engine.Resampler`,
-    `Stretcher`, `Pitcher`, `Normalizer`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `ln` / `lv` (`engine.Resampler`,
+    `Stretcher`, `Pitcher`, `Toner`, `Normalizer`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
     [batch, widest line] tensors, int16 with `pcm_i16`, else float32, which the last stage writes.  An empty table creates
     nothing: `out` is None and the codec writes its PCM as without a chain.  On a table with `encodings` the chain ends with
     `en` (`engine.Encoder`): `out` is then a ring of pinned uint8 [batch, encoding.pitch(widest line)] tensors that the encoder
@@ -267,7 +315,7 @@ class OutputChain:
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
 
-        from .engine import Encoder, Leveler, Normalizer, Pitcher, Resampler, Stretcher
+        from .engine import Encoder, Leveler, Normalizer, Pitcher, Resampler, Stretcher, Toner
 
         if table.encodings is not None and pcm_i16:
             raise ValueError("pcm_i16 and encodings exclude each other: with encodings a row asks for pcm_s16le itself")
@@ -275,15 +323,17 @@ class OutputChain:
         self.rs = Resampler(engine, batch, table.sample_rates, table.rate_plans) if table.has_rates else None
         self.ts = Stretcher(engine, batch, table.stretch_plans) if table.speeds is not None else None
         self.ps = Pitcher(engine, batch, table.pitch_plans) if table.pitches is not None else None
+        self.tn = Toner(engine, batch, table.tone_plans, table.width) if table.tone_plans is not None else None
         self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
-        self.out = self.rs_out = self.ps_in = self.ln_in = self.lv_in = self.en = self.en_in = None
+        self.out = self.rs_out = self.ps_in = self.tn_in = self.ln_in = self.lv_in = self.en = self.en_in = None
         if table.empty:
             return
         if table.encodings is not None:
             self.en = Encoder(engine, batch, table.width)
         before_ps = self.ts if self.ts is not None else self.rs  # the stage before the pitcher, if any
-        before_ln = self.ps if self.ps is not None else before_ps  # the stage before the normaliser, if any
+        before_tn = self.ps if self.ps is not None else before_ps  # the stage before the toner, if any
+        before_ln = self.tn if self.tn is not None else before_tn  # the stage before the normaliser, if any
         last = self.ln if self.ln is not None else before_ln       # the stage before the leveler, if any
         width = self.lv.width if self.lv is not None else last.out_max if last is not None else table.width
         if self.en is not None:
@@ -304,6 +354,10 @@ class OutputChain:
             if before_ln.out_max != self.ln.width:
                 raise ValueError("loudness: the normaliser's line is not the line of the stage before it")
             self.ln_in = torch.zeros(batch, self.ln.width, device=engine.device)
+        if self.tn is not None and before_tn is not None:
+            if before_tn.out_max != self.tn.width:
+                raise ValueError("tone: the toner's line is not the line of the stage before it")
+            self.tn_in = torch.zeros(batch, self.tn.width, device=engine.device)
         if self.ps is not None and before_ps is not None:
             if before_ps.out_max != self.ps.width:
                 raise ValueError("pitch: the pitcher's line is not the line of the stage before it")
@@ -312,7 +366,7 @@ class OutputChain:
             self.rs_out = torch.zeros(batch, self.rs.out_max, device=engine.device)
 
     def stages(self):
-        return [s for s in (self.rs, self.ts, self.ps, self.ln, self.lv, self.en) if s is not None]
+        return [s for s in (self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en) if s is not None]
 
     def attach(self, mimi_state, p: int):
         """the decodes / graph captures of `mimi_state` issued after this call end with the chain's launches and write
@@ -321,6 +375,9 @@ class OutputChain:
         end = final if self.lv is None else self.lv_in         # what the stage before the leveler writes
         if self.ln is not None:
             end = self.ln_in                                  # what the stage before the normaliser writes
+        tn_out = end                                          # what the toner, if any, writes
+        if self.tn is not None:
+            end = self.tn_in                                  # what the stage before the toner writes
         mid = end if self.ps is None else self.ps_in          # what the stage before the pitcher writes
         if self.rs is not None:
             mimi_state.set_resampler(self.rs, mid if self.ts is None else self.rs_out)
@@ -328,6 +385,8 @@ class OutputChain:
             mimi_state.set_stretcher(self.ts, mid, self.rs_out)
         if self.ps is not None:
             mimi_state.set_pitcher(self.ps, end, self.ps_in)
+        if self.tn is not None:
+            mimi_state.set_tone(self.tn, tn_out, self.tn_in)
         if self.ln is not None:
             mimi_state.set_loudnorm(self.ln, self.lv_in, self.ln_in)
         if self.lv is not None:
@@ -342,6 +401,8 @@ class OutputChain:
             mimi_state.set_leveler(None)
         if self.ln is not None:
             mimi_state.set_loudnorm(None)
+        if self.tn is not None:
+            mimi_state.set_tone(None)
         if self.ps is not None:
             mimi_state.set_pitcher(None)
         if self.ts is not None:
@@ -363,6 +424,8 @@ class OutputChain:
             self.ts.set_row(row, route.stretch_plan, stream)
         if self.ps is not None:
             self.ps.set_row(row, route.pitch_plan, stream)
+        if self.tn is not None:
+            self.tn.set_row(row, route.tone_plan, stream)
         if self.ln is not None:
             self.ln.set_row(row, *(route.loud or (None, None)), stream)
         if self.lv is not None:

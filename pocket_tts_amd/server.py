@@ -14,7 +14,9 @@ the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.  
 field `encoding` chooses the sample encoding among them and `pcm_s16le` (`encoding.py`: ITU-T G.711 `mulaw` / `alaw`, or
 `pcm_f32le`), encoded on the GPU; header and silence follow it.  `container=raw` (default `wav`) leaves the header out: the
 encoded samples and the trailing silence as `application/octet-stream`, with the response headers `X-Audio-Encoding` and
-`X-Sample-Rate` - what a media-stream gateway forwards.
+`X-Sample-Rate` - what a media-stream gateway forwards.  On a server started with `tones` the field `tone` chooses one of
+them (`tone.py`: a preset such as `telephone`, or a band list), equalised on the GPU with the peak limiter behind it
+(`peak_dbfs` is then its ceiling); a tone the request's rate does not admit gets a 400 with those it admits.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
 `urllib.parse` and the standard library's `email` header parser.
@@ -53,6 +55,8 @@ INDEX_HTML = """<!doctype html>
 <p>Pitch <input name="pitch" size="6"> as a frequency ratio, e.g. 17/16 or 0.8 (empty: 1)</p>
 <p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)</p>
 <p>Loudness <input name="loudness_lufs" size="5"> LUFS, e.g. -16 or -23, instead of a gain (empty: the model's own level)</p>
+<p>Tone <input name="tone" size="20"> a preset or a band list such as hp:120;peak:3000:4, as far as the server was started
+with it (empty: none)</p>
 <p>Encoding <input name="encoding" size="10"> pcm_s16le, pcm_f32le, mulaw or alaw, as far as the server was started with
 them (empty: pcm_s16le), container <select name="container"><option>wav</option><option>raw</option></select></p>
 <p><button type="submit">Speak</button></p>
@@ -234,6 +238,46 @@ def parse_pitch(fields: dict, rate, speed, table) -> float | None:
     return v
 
 
+def parse_tone(fields: dict, rate, speed, table):
+    """the optional `tone` field: the canonical string of one of the configured tones admissible at the request's rate, None
+    where absent, empty or "flat".  `table`: the server's `ChainTable` with its tones, None on a server started without.
+    FormError with the configured list for a tone that is not configured, with the admissible list for one the request's
+    rate refuses, for what the grammar refuses, and for any tone on a server started without tones"""
+    from . import tone as tone_rule
+
+    raw = fields.get("tone")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        canon = tone_rule.normalise(raw)
+        if canon is None:
+            return None
+        if table is None:
+            raise FormError("tone is not available (this server was started without tones)")
+        table.route(rate, speed, tone=canon)
+    except ValueError as e:
+        raise FormError(str(e)) from None
+    return canon
+
+
+def parse_ceiling(fields: dict):
+    """the optional `peak_dbfs` field of a request with a tone and no gain: the limiter's ceiling, None where absent or empty;
+    FormError for a value `level.check` refuses"""
+    from . import level
+
+    raw = (fields.get("peak_dbfs") or "").strip()
+    if not raw:
+        return None
+    try:
+        peak = float(raw)
+    except ValueError:
+        raise FormError(f"peak_dbfs must be a number, got {raw!r}") from None
+    try:
+        return level.check(0.0, peak)[1]
+    except ValueError as e:
+        raise FormError(str(e)) from None
+
+
 def parse_level(fields: dict, enabled: bool):
     """the optional `gain_db` and `peak_dbfs` fields as (gain_db, peak_dbfs), each None where absent or empty; FormError for
     a value `level.check` refuses (its message names the rule) and for either field on a server started without level"""
@@ -310,7 +354,7 @@ def parse_container(fields: dict) -> str:
 
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
                batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None,
-               level: bool = False, pitches=None, loudness: bool = False, encodings=None):
+               level: bool = False, pitches=None, loudness: bool = False, encodings=None, tones=None):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
@@ -329,7 +373,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     `encodings`: the sample encodings a request may choose with `encoding` besides `pcm_s16le` (`encoding.py`; None: only
     that one, a request that names another gets a 400 with the configured list, and the batcher's graphs are those of
     before).  The batcher is then built with `encodings` and its default `pcm_format`: every request's samples leave the GPU
-    in its own encoding.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    in its own encoding.  `tones`: the tones a request may choose with `tone` (`tone.py`; None: a request that sends one
+    gets a 400, and the batcher's graphs are those of before); each must be admissible on one of the server's lines at least
+    (ValueError here), a request with another tone gets a 400 with the configured list, and one whose rate does not admit
+    its tone a 400 with the admissible list.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import wav_stream_bytes
 
     from .output_chain import ChainTable
@@ -353,6 +400,11 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     if loudness:  # the normaliser's and the limiter's rules on every line (ValueError at start-up)
         ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, loudness=True)
 
+    tone_table = None
+    if tones is not None:  # the toner's and the limiter's rules on every line (ValueError at start-up)
+        tone_table = ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, tones=tones)
+        tones = tone_table.tones
+
     if encodings is not None:
         from .encoding import normalise_encodings
 
@@ -370,10 +422,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             if encodings is not None:  # the encoder writes every request's format, pcm_s16le included
                 return ContinuousBatcher(model, slots=slots, capacity=capacity, max_lsd_decode_steps=reserve,
                                          sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
-                                         loudness=loudness, encodings=encodings)
+                                         loudness=loudness, encodings=encodings, tones=tones)
             return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
                                      sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
-                                     loudness=loudness)
+                                     loudness=loudness, tones=tones)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -471,9 +523,16 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             pitch = parse_pitch(fields, settings.get("sample_rate"), settings.get("speed"), pitch_table)
             if pitch is not None and pitch != 1.0:
                 settings["pitch"] = pitch
+            tone = parse_tone(fields, settings.get("sample_rate"), settings.get("speed"), tone_table)
+            if tone is not None:
+                settings["tone"] = tone
             target, ceiling = parse_loudness(fields, loudness)
             if target is not None:
                 settings["loudness_lufs"], settings["peak_dbfs"] = target, ceiling
+            elif tone is not None and not (fields.get("gain_db") or "").strip():
+                ceiling = parse_ceiling(fields)  # the limiter behind the tone: no gain of its own
+                if ceiling is not None:
+                    settings["peak_dbfs"] = ceiling
             else:
                 gain_db, peak_dbfs = parse_level(fields, level)
                 if gain_db is not None:

@@ -194,13 +194,13 @@ class TTSModel:
                        frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
                        speed: float | None = None, gain_db: float | None = None, peak_dbfs: float | None = None,
                        pitch=None, loudness_lufs: float | None = None, encoding: str | None = None,
-                       seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs` and
-        `encoding` (not in the reference): see `generate_audio_stream`."""
+                       tone: str | None = None, seed: int | None = None) -> torch.Tensor:
+        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
+        `encoding` and `tone` (not in the reference): see `generate_audio_stream`."""
         chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
                                                  seed=seed, sample_rate=sample_rate, speed=speed, gain_db=gain_db,
                                                  peak_dbfs=peak_dbfs, pitch=pitch, loudness_lufs=loudness_lufs,
-                                                 encoding=encoding))
+                                                 encoding=encoding, tone=tone))
         return torch.cat(chunks, dim=0)
 
     @torch.no_grad()
@@ -208,7 +208,7 @@ class TTSModel:
                               frames_after_eos: int | None = None, copy_state: bool = True,
                               sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
                               peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
-                              encoding: str | None = None, seed: int | None = None):
+                              encoding: str | None = None, tone: str | None = None, seed: int | None = None):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
 
         `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
@@ -243,6 +243,13 @@ class TTSModel:
         accordingly, one element per sample: the 16-bit samples a WAV file holds, the float samples as they are, or ITU-T
         G.711 bytes of those 16-bit samples.  None: fp32 chunks, as before.
 
+        `tone` (not in the reference; a preset such as "telephone", "warm", "bright", "presence", "small_speaker" or
+        "deess", or a band list such as "hp:120;peak:3000:4", `tone.py`): the audio runs through that cascade of at most
+        eight biquad sections on the GPU, in float64, behind the pitcher and before the normaliser, followed by the peak
+        limiter at `peak_dbfs` (default -1); it combines freely with `gain_db` and `loudness_lufs`.  The equaliser itself
+        does not lag; the output lags like a levelled one.  A band above 0.45 x the output rate is refused.  None, "" or
+        "flat": as before.
+
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
         per-step copy, nothing read from torch's global generator - and `generate_audio_batch(seeds=...)` and
@@ -257,6 +264,9 @@ class TTSModel:
             encoding_rule.check(encoding)
         # the native rate, speed 1.0 and no gain become None: the call of before.  ValueError names the rule
         native, fs = int(self.config.mimi.sample_rate), self.engine.frame_samples
+        tone = ChainTable.single_tone(native, fs, sample_rate, speed, tone)
+        if tone is not None and gain_db is None and loudness_lufs is None:
+            gain_db = 0.0  # the limiter behind the tone: no gain of its own, the request's ceiling
         loud, loud_peak = ChainTable.single_loudness(native, fs, sample_rate, speed, gain_db, peak_dbfs, loudness_lufs)
         request = ChainTable.single(native, fs, sample_rate, speed, gain_db, None if loud is not None else peak_dbfs)
         if loud is not None:  # the limiter behind the normaliser: no gain of its own, the request's ceiling
@@ -272,7 +282,7 @@ class TTSModel:
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
                                                               None if seed is None else chunk_seed(seed, i), *request,
-                                                              pitch=pitch, loudness_lufs=loud, encoding=encoding)
+                                                              pitch=pitch, loudness_lufs=loud, encoding=encoding, tone=tone)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -436,7 +446,7 @@ class TTSModel:
         """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
         recently used are released; a context in use is not in the cache"""
         keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:] or "level" in k[4:] or "pitch" in k[4:]
-                or "loud" in k[4:] or "enc" in k[4:]]
+                or "loud" in k[4:] or "enc" in k[4:] or "tone" in k[4:]]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
             c["pipe"].close()
@@ -513,7 +523,7 @@ class TTSModel:
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
                                           row_seed: int | None = None, sample_rate: int | None = None,
                                           speed: float | None = None, gain_db=None, peak_dbfs=None, pitch=None,
-                                          loudness_lufs=None, encoding=None):
+                                          loudness_lufs=None, encoding=None, tone=None):
         from . import encoding as encoding_rule
 
         eng = self.engine
@@ -541,6 +551,8 @@ class TTSModel:
             key = (*key, "loud")
         if encoding is not None:  # likewise: its codec graphs end with the encoder (one context serves all four encodings)
             key = (*key, "enc")
+        if tone is not None:  # likewise: its codec graphs run the toner, whose plans are those of this tone alone
+            key = (*key, "tone", tone)
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -549,13 +561,14 @@ class TTSModel:
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
             if not (sample_rate is None and speed is None and gain_db is None and pitch is None
-                    and loudness_lufs is None and encoding is None):  # with an output chain
+                    and loudness_lufs is None and encoding is None and tone is None):  # with an output chain
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
             pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
                                 sample_rates=None if sample_rate is None else [sample_rate],
                                 speeds=None if speed is None else [speed], level=gain_db is not None,
                                 pitches=None if pitch is None else [pitch], loudness=loudness_lufs is not None,
-                                encodings=None if encoding is None else list(encoding_rule.NAMES))
+                                encodings=None if encoding is None else list(encoding_rule.NAMES),
+                                tones=None if tone is None else [tone])
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
         noise_host = ctx["noise_host"]
@@ -566,7 +579,7 @@ class TTSModel:
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         # the codec's carries and the row's rate, plan, gain and ceiling with a zero state in every stage, on the codec stream
-        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding)
+        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding, tone)
         pipe.restart([route])
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
