@@ -267,10 +267,18 @@ int ptts_resampler_set_row(ptts_resampler *rs, int32_t row, int32_t rate_index, 
  * ptts_mimi_set_pcm_i16 converts, device or pinned host; then every row's history <- the frame's last 64 samples (a second
  * launch: the blocks of a row read the history concurrently).  out_max = the largest out_n of the rates. */
 int ptts_resample_frame(ptts_resampler *rs, const float *d_pcm_in, void *out, int32_t is_i16, void *stream);
-/* While a resampler is set, ptts_mimi_decode and the graph captures append the two launches of ptts_resample_frame behind
- * the codec's last kernel, reading d_pcm (which must then be device memory; NULL = the state's own buffer).  NULL switches
- * it off: decodes and captures are then launch for launch those of a state that never had one.  -1 when the resampler's
- * batch or frame length is not the state's. */
+/* ---- The output chain.  The seven ptts_mimi_set_* below follow one rule, stated here once.  While a stage is set on a
+ * state, ptts_mimi_decode and the graph captures append its ptts_*_frame launches behind the codec's last kernel, in the order
+ *   resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder
+ * whichever of them are set.  d_in == NULL: the stage reads d_pcm (which must then be device memory; NULL = the state's own
+ * buffer), and its input width must be frame_samples.  Otherwise it reads the f32 device buffer d_in [B, its input width],
+ * which the caller has given the stage before it as its `out`; some stage of an earlier kind must be set on the state at
+ * the time of the call, so the setters are called in chain order.  It writes `out` [B, its output width], f32 or (is_i16)
+ * int16 converted as ptts_mimi_set_pcm_i16 converts, device or pinned host.  -1 for a null state or output, for a batch that
+ * is not the state's, and for what the rule or the setter's own comment asks and does not get.  A NULL stage switches it off:
+ * decodes and captures are then launch for launch those of a state that never had one.  What follows each setter is only what
+ * is particular to it.
+ * The resampler is always first and has no d_in; its two launches are those of ptts_resample_frame. */
 int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, void *out, int32_t is_i16);
 /* ---- Speaking rate (no reference counterpart).  A stretcher holds, for B sequences, a table of WSOLA plans, each row's
  * plan and each row's streaming state; it turns one frame f32[B, in_max] of the previous output stage (the codec's PCM or the
@@ -302,11 +310,9 @@ int ptts_stretcher_set_row_drain(ptts_stretcher *ts, int32_t row, int32_t on, vo
  * ptts_mimi_set_pcm_i16 converts, device or pinned host; then the rows' states advance.  d_delta (i32 [B, K_max], device, or
  * NULL) receives the delta_k of the frame's hops of every row that is not on an identity plan: the test tap. */
 int ptts_stretch_frame(ptts_stretcher *ts, const float *d_in, void *out, int32_t is_i16, int32_t *d_delta, void *stream);
-/* While a stretcher is set, ptts_mimi_decode and the graph captures append the launch of ptts_stretch_frame.  d_in == NULL:
- * behind the codec's last kernel, reading d_pcm (which must then be device memory; NULL = the state's own buffer; in_max must
- * be frame_samples).  Otherwise behind the resampler set on the state, which then writes f32 into the device buffer d_in
- * [B, in_max] instead of its own output (in_max must be the resampler's out_max).  NULL stretcher: off, decodes and captures
- * are launch for launch those of a state that never had one. */
+/* The output chain's rule (ptts_mimi_set_resampler), with one difference: with d_in [B, in_max] the resampler set on the
+ * state writes f32 into d_in INSTEAD of its own output, so there must be one and in_max must be its out_max; a frame enqueued
+ * with d_in and no resampler fails (-1). */
 int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16);
 /* ---- Pitch (no reference counterpart).  A pitcher holds, for B sequences, a table of plans, each row's plan and each row's
  * streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of its line)
@@ -341,11 +347,7 @@ int ptts_pitcher_set_row_drain(ptts_pitcher *ps, int32_t row, int32_t on, void *
  * of every row that is not on an identity plan; nothing else of them is written. */
 int ptts_pitch_frame(ptts_pitcher *ps, const float *d_in, void *out, int32_t is_i16, int32_t *d_delta, float *d_mid,
                      void *stream);
-/* While a pitcher is set, ptts_mimi_decode and the graph captures append the launch of ptts_pitch_frame after the stretcher's
- * and before the leveler's.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer;
- * width must be frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given the
- * preceding stage (resampler or stretcher) as its `out`.  NULL pitcher: off, decodes and captures are launch for launch
- * those of a state that never had one. */
+/* The output chain's rule (ptts_mimi_set_resampler), nothing of its own. */
 int ptts_mimi_set_pitcher(ptts_mimi_state *s, ptts_pitcher *ps, float *d_in, void *out, int32_t is_i16);
 /* ---- Output level (no reference counterpart).  A leveler holds, for B sequences, a table of plans, each row's plan, gain G,
  * ceiling C and streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front
@@ -371,11 +373,7 @@ int ptts_leveler_set_row_drain(ptts_leveler *lv, int32_t row, int32_t on, void *
 /* One frame, one launch: d_in f32[B, width] (DEVICE memory) -> out [B, width], f32 or (is_i16) int16 converted as
  * ptts_mimi_set_pcm_i16 converts, device or pinned host; then the rows' states advance. */
 int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_i16, void *stream);
-/* While a leveler is set, ptts_mimi_decode and the graph captures append the launch of ptts_level_frame as their LAST one.
- * d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer; width must be
- * frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given the preceding stage
- * (resampler, stretcher, pitcher or normaliser) as its `out`.  NULL leveler: off, decodes and captures are launch for launch those of a state
- * that never had one. */
+/* The output chain's rule (ptts_mimi_set_resampler), nothing of its own. */
 int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float *d_in, void *out, int32_t is_i16);
 /* ---- Loudness (no reference counterpart).  A normaliser holds, for B sequences, a table of plans, each row's plan, target T
  * in LUFS and streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of
@@ -402,12 +400,8 @@ int ptts_loudnorm_set_row_drain(ptts_loudnorm *ln, int32_t row, int32_t on, void
  * advance.  The test tap d_tap, device or NULL: f64[B, 4] receives, for every row that is not on bypass, the sub-blocks it
  * has completed, its last L (NaN while undefined), its last c and its last Z. */
 int ptts_loudnorm_frame(ptts_loudnorm *ln, const float *d_in, float *d_out, double *d_tap, void *stream);
-/* While a normaliser is set, ptts_mimi_decode and the graph captures append the launch of ptts_loudnorm_frame after the
- * pitcher's and before the leveler's.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own
- * buffer; width must be frame_samples).  Otherwise it reads the f32 device buffer d_in [B, width], which the caller has given
- * the preceding stage (resampler, stretcher or pitcher) as its `out`.  It writes d_out, which the caller gives the leveler as
- * its d_in: a frame enqueued with a normaliser but no leveler fails (-1).  NULL normaliser: off, decodes and captures are
- * launch for launch those of a state that never had one. */
+/* The output chain's rule (ptts_mimi_set_resampler).  Its own: d_out is f32 device memory and not d_in (-1), and the caller
+ * gives it to the leveler as its d_in: a frame enqueued with a normaliser but no leveler fails (-1). */
 int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out);
 /* ---- Tone (no reference counterpart).  A toner holds, for B sequences, a table of plans, each row's plan and streaming
  * state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of its line) into d_out
@@ -433,12 +427,8 @@ int ptts_tone_set_row(ptts_tone *tn, int32_t row, int32_t plan_index, void *stre
 /* One frame, one launch: d_in f32[B, width] -> d_out f32[B, width], both DEVICE memory and distinct (-1 otherwise); then
  * the rows' states advance. */
 int ptts_tone_frame(ptts_tone *tn, const float *d_in, float *d_out, void *stream);
-/* While a toner is set, ptts_mimi_decode and the graph captures append the launch of ptts_tone_frame after the pitcher's
- * and before the normaliser's.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own
- * buffer; width must be frame_samples, -1 otherwise).  Otherwise it reads the f32 device buffer d_in [B, width], which the
- * caller has given the preceding stage (resampler, stretcher or pitcher) as its `out`.  It writes d_out, which the caller
- * gives the normaliser or the leveler as its d_in: a frame enqueued with a toner but no leveler fails (-1).  NULL toner: off,
- * decodes and captures are launch for launch those of a state that never had one. */
+/* The output chain's rule (ptts_mimi_set_resampler).  Its own: d_out is f32 device memory and not d_in (-1), and the caller
+ * gives it to the normaliser or the leveler as its d_in: a frame enqueued with a toner but no leveler fails (-1). */
 int ptts_mimi_set_tone(ptts_mimi_state *s, ptts_tone *tn, float *d_in, float *d_out);
 /* ---- Output encoding (no reference counterpart).  An encoder holds, for B sequences, each row's number of samples n and
  * encoding code: 0 pcm_s16le, 1 pcm_f32le, 2 mulaw, 3 alaw (contract: pocket_tts_amd/encoding.py).  It turns one frame
@@ -458,13 +448,10 @@ int ptts_encoder_set_row(ptts_encoder *en, int32_t row, int32_t n, int32_t code,
 /* One frame, one launch: d_in f32[B, width] (DEVICE memory) -> out_bytes u8[B, pitch], device or pinned host, aligned to 16
  * bytes (-1 otherwise). */
 int ptts_encode_frame(ptts_encoder *en, const float *d_in, void *out_bytes, void *stream);
-/* While an encoder is set, ptts_mimi_decode and the graph captures append the launch of ptts_encode_frame as their LAST one,
- * writing out_bytes.  d_in == NULL: it reads d_pcm (which must then be device memory; NULL = the state's own buffer; width
- * must be frame_samples) and must be the only output stage.  Otherwise it reads the f32 device buffer d_in [B, width], and the
- * last stage set on the state (leveler, else pitcher, else stretcher, else resampler; its widest line must be width) writes
- * f32 into d_in instead of its own `out`.  -1 for a batch or width that does not match, a null output, or an input buffer on
- * a state without such a stage.  NULL encoder: off, decodes and captures are launch for launch those of a state that never
- * had one. */
+/* The output chain's rule (ptts_mimi_set_resampler), writing out_bytes, with one difference: the last stage set on the state
+ * (leveler, else pitcher, else stretcher, else resampler; its widest line must be width) writes f32 into d_in INSTEAD of its
+ * own `out`.  So d_in must be NULL exactly when the state has none of these four, at the time of the call (-1) and when a
+ * frame is enqueued (-1). */
 int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float *d_in, void *out_bytes);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */

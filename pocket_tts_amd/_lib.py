@@ -198,10 +198,11 @@ def build(force: bool = False, verbose: bool = False) -> Path:
       * ptts_dispatch.hip = the GEMM / attention dispatchers and the tuner, the only unit that instantiates the round-1/2
         kernel templates;
       * ptts_debug.hip = the C ABI's test hooks;
-      * ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch,
-        ptts_pitch.hip = the pitch shifter, ptts_tone.hip = the equaliser, ptts_loud.hip = the loudness normaliser, ptts_level.hip = the output gain with
-        its peak limiter and ptts_encode.hip = the output encoder (16-bit and float PCM, G.711), each with its own part of the
-        C ABI;
+      * the seven stages of the output chain, in its order (`output_chain.py`), each with its own part of the C ABI:
+        ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch, ptts_pitch.hip =
+        the pitch shifter, ptts_tone.hip = the equaliser, ptts_loud.hip = the loudness normaliser, ptts_level.hip = the
+        output gain with its peak limiter and ptts_encode.hip = the output encoder (16-bit and float PCM, G.711); how they
+        are wired behind the codec is ptts.hip's (its section "the output chain");
       * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
     The first ten see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
     libptts.so; a unit is recompiled when it or any header is newer than its object."""

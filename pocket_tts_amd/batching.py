@@ -246,13 +246,7 @@ class ContinuousBatcher:
                                  mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
                                  level=level, pitches=pitches, loudness=loudness, encodings=encodings, tones=tones)
         self.chain = self.pipe.chain
-        self.rs = self.pipe.rs
-        self.ts = self.pipe.ts
-        self.lv = self.pipe.lv
-        self.ps = self.pipe.ps
-        self.ln = self.pipe.ln
-        self.en = self.pipe.en
-        self.tn = self.pipe.tn
+        self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
         # the output chain has a stage that may lag
         self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
         self.pipe.restart()

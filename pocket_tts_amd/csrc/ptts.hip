@@ -2173,183 +2173,158 @@ static int mimi_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, cons
   return 0;
 }
 
-// Output sample rates: while a resampler is set, its two launches follow the codec's last kernel on the same stream and read
-// the frame's fp32 PCM from device memory (d_pcm, or the state's own buffer); out [B][out_max] is f32 or i16, device or pinned
-// host.  NULL switches it off: decodes and captures are then launch for launch what they were.
+// ---- the output chain -------------------------------------------------------------------------------------------------
+// The stages behind the codec: one row per kind of ptts_mimi_state::chain, in launch order, with the words the kind's
+// messages use, its SITE and thin adapters over what ptts_ext.h declares (the test taps are not fed from here).  While a
+// link is set its stage's launch follows the codec's last kernel on the same stream.  It reads the link's `in`, which the
+// caller has given the stage before it as its output, or without one the frame's fp32 PCM (d_pcm, or the state's own
+// buffer), and writes the link's `out`.  A NULL stage clears the link: decodes and captures are then launch for launch what
+// they were.
+struct ChainKind {
+  const char *setter, *noun, *site;
+  bool f32_only;  // writes f32 into a device buffer that must not be its input
+  int (*batch)(const void *), (*in_width)(const void *), (*out_width)(const void *);
+  int (*enqueue)(hipStream_t st, void *stage, const float *in, void *out, int i16);
+};
+#define GET(T, f) [](const void *p) { return f((const T *)p); }
+#define ENQ(T, ...)                                                          \
+  [](hipStream_t st, void *p, const float *in, void *out, int i16) {         \
+    (void)i16;                                                               \
+    T *stage = (T *)p;                                                       \
+    return __VA_ARGS__;                                                      \
+  }
+static const ChainKind kChain[CH_N] = {
+    {"set_resampler", "resampler", "resample", false, GET(ptts_resampler, resample_batch),
+     GET(ptts_resampler, resample_frame_samples), GET(ptts_resampler, resample_out_max),
+     ENQ(ptts_resampler, resample_enqueue(st, stage, in, out, i16))},
+    {"set_stretcher", "stretcher", "stretch", false, GET(ptts_stretcher, stretch_batch), GET(ptts_stretcher, stretch_in_max),
+     GET(ptts_stretcher, stretch_out_max), ENQ(ptts_stretcher, stretch_enqueue(st, stage, in, out, i16, nullptr))},
+    {"set_pitcher", "pitcher", "pitch", false, GET(ptts_pitcher, pitch_batch), GET(ptts_pitcher, pitch_width),
+     GET(ptts_pitcher, pitch_width), ENQ(ptts_pitcher, pitch_enqueue(st, stage, in, out, i16, nullptr, nullptr))},
+    {"set_tone", "toner", "tone", true, GET(ptts_tone, tone_batch), GET(ptts_tone, tone_width), GET(ptts_tone, tone_width),
+     ENQ(ptts_tone, tone_enqueue(st, stage, in, (float *)out))},
+    {"set_loudnorm", "normaliser", "loudnorm", true, GET(ptts_loudnorm, loud_batch), GET(ptts_loudnorm, loud_width),
+     GET(ptts_loudnorm, loud_width), ENQ(ptts_loudnorm, loud_enqueue(st, stage, in, (float *)out, nullptr))},
+    {"set_leveler", "leveler", "level", false, GET(ptts_leveler, level_batch), GET(ptts_leveler, level_width),
+     GET(ptts_leveler, level_width), ENQ(ptts_leveler, level_enqueue(st, stage, in, out, i16))},
+    {"set_encoder", "encoder", "encode", false, GET(ptts_encoder, encode_batch), GET(ptts_encoder, encode_width),
+     GET(ptts_encoder, encode_width), ENQ(ptts_encoder, encode_enqueue(st, stage, in, out))},
+};
+#undef GET
+#undef ENQ
+
+// The stage that writes the encoder's input: the last one set of leveler, pitcher, stretcher, resampler; -1: none.  The
+// toner and the normaliser do not count, a leveler always follows them.
+static int before_encoder(const ptts_mimi_state *s) {
+  int last = -1;
+  for (int k : {CH_RS, CH_TS, CH_PS, CH_LV})
+    if (s->chain[k].stage) last = k;
+  return last;
+}
+
+// What the seven setters share, in this order: the state, the output, not in place (f32_only), the batch, then `own()`, the
+// calling setter's own refusals (a whole message, or nullptr), then the frame length of a stage that reads the frame's PCM,
+// and for an input buffer that some stage of a lower kind is set on the state NOW, which is why setters are called in
+// chain order.
+template <class Own>
+static int set_link(ptts_mimi_state *s, int kind, void *stage, float *in, void *out, int i16, Own own) {
+  if (!s) return fail(-1, "null state");
+  const ChainKind &k = kChain[kind];
+  const std::string set = std::string(k.setter) + ": ", its = set + "the " + k.noun + "'s ";
+  if (stage) {
+    if (!out) return fail(-1, set + "null output");
+    if (k.f32_only && in == out) return fail(-1, set + "the stage does not work in place");
+    if (k.batch(stage) != s->B) return fail(-1, its + "batch is not the state's");
+    if (const char *msg = own()) return fail(-1, msg);
+    if (!in && k.in_width(stage) != s->rows[3]) return fail(-1, its + "frame length is not the state's");
+    bool fed = false;
+    for (int i = 0; i < kind; i++) fed |= s->chain[i].stage != nullptr;
+    if (in && !fed) {
+      std::string kinds;  // "a resampler, a stretcher or a pitcher"
+      for (int i = 0; i < kind; i++) kinds += std::string(i == 0 ? "a " : i == kind - 1 ? " or a " : ", a ") + kChain[i].noun;
+      return fail(-1, set + "an input buffer needs " + kinds + " on the state");
+    }
+  }
+  s->chain[kind] = stage ? ChainLink{stage, in, out, i16 != 0} : ChainLink{};
+  return 0;
+}
+static int set_link(ptts_mimi_state *s, int kind, void *stage, float *in, void *out, int i16) {
+  return set_link(s, kind, stage, in, out, i16, [] { return (const char *)nullptr; });
+}
+
+// out [B][out_max] is f32 or i16, device or pinned host
 extern "C" int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, void *out, int32_t is_i16) {
-  if (!s) return fail(-1, "null state");
-  if (rs && !out) return fail(-1, "set_resampler: null output");
-  if (rs && (resample_batch(rs) != s->B || resample_frame_samples(rs) != s->rows[3]))
+  // its own: one message for the batch and the frame length, in place of the two of set_link
+  if (s && rs && out && (resample_batch(rs) != s->B || resample_frame_samples(rs) != s->rows[3]))
     return fail(-1, "set_resampler: the resampler's batch or frame length is not the state's");
-  s->rs = rs;
-  s->rs_out = rs ? out : nullptr;
-  s->rs_i16 = rs ? (is_i16 != 0) : 0;
-  return 0;
+  return set_link(s, CH_RS, rs, nullptr, out, is_i16);
 }
 
-// Speaking rate: while a stretcher is set, its launch follows the codec's last kernel (d_in == NULL: it reads the frame's fp32
-// PCM as the resampler would) or the resampler, which then writes f32 into the device buffer d_in instead of its own
-// output.  NULL switches it off: decodes and captures are then launch for launch what they were.
+// its own: with d_in the resampler writes f32 into d_in instead of its own output, so its longest frame must be the stretcher's
 extern "C" int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16) {
-  if (!s) return fail(-1, "null state");
-  if (ts && !out) return fail(-1, "set_stretcher: null output");
-  if (ts && stretch_batch(ts) != s->B) return fail(-1, "set_stretcher: the stretcher's batch is not the state's");
-  if (ts && !d_in && stretch_in_max(ts) != s->rows[3])
-    return fail(-1, "set_stretcher: the stretcher's frame length is not the state's");
-  if (ts && d_in && (!s->rs || resample_out_max(s->rs) != stretch_in_max(ts)))
-    return fail(-1, "set_stretcher: an input buffer needs a resampler on the state whose longest frame is the stretcher's");
-  s->ts = ts;
-  s->ts_in = ts ? d_in : nullptr;
-  s->ts_out = ts ? out : nullptr;
-  s->ts_i16 = ts ? (is_i16 != 0) : 0;
-  return 0;
+  return set_link(s, CH_TS, ts, d_in, out, is_i16, [&]() -> const char * {
+    const ptts_resampler *rs = (const ptts_resampler *)s->chain[CH_RS].stage;
+    if (d_in && (!rs || resample_out_max(rs) != stretch_in_max(ts)))
+      return "set_stretcher: an input buffer needs a resampler on the state whose longest frame is the stretcher's";
+    return nullptr;
+  });
 }
 
-// Pitch: while a pitcher is set, its launch follows the stretch launch and precedes the level launch.  d_in == NULL: it reads
-// the frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  NULL switches
-// it off: decodes and captures are then launch for launch what they were.
 extern "C" int ptts_mimi_set_pitcher(ptts_mimi_state *s, ptts_pitcher *ps, float *d_in, void *out, int32_t is_i16) {
-  if (!s) return fail(-1, "null state");
-  if (ps && !out) return fail(-1, "set_pitcher: null output");
-  if (ps && pitch_batch(ps) != s->B) return fail(-1, "set_pitcher: the pitcher's batch is not the state's");
-  if (ps && !d_in && pitch_width(ps) != s->rows[3]) return fail(-1, "set_pitcher: the pitcher's frame length is not the state's");
-  if (ps && d_in && !s->rs && !s->ts) return fail(-1, "set_pitcher: an input buffer needs a resampler or a stretcher on the state");
-  s->ps = ps;
-  s->ps_in = ps ? d_in : nullptr;
-  s->ps_out = ps ? out : nullptr;
-  s->ps_i16 = ps ? (is_i16 != 0) : 0;
-  return 0;
+  return set_link(s, CH_PS, ps, d_in, out, is_i16);
 }
 
-// Tone: while a toner is set, its launch follows the pitch launch and precedes the normaliser's.  d_in == NULL: it reads the
-// frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  It always
-// writes f32 into the device buffer d_out, which the normaliser or the leveler then reads: a frame enqueued with a toner but
-// no leveler fails.  NULL switches it off: decodes and captures are then launch for launch what they were.
+// a frame enqueued with a toner but no leveler fails
 extern "C" int ptts_mimi_set_tone(ptts_mimi_state *s, ptts_tone *tn, float *d_in, float *d_out) {
-  if (!s) return fail(-1, "null state");
-  if (tn && !d_out) return fail(-1, "set_tone: null output");
-  if (tn && d_in == d_out) return fail(-1, "set_tone: the stage does not work in place");
-  if (tn && tone_batch(tn) != s->B) return fail(-1, "set_tone: the toner's batch is not the state's");
-  if (tn && !d_in && tone_width(tn) != s->rows[3]) return fail(-1, "set_tone: the toner's frame length is not the state's");
-  if (tn && d_in && !s->rs && !s->ts && !s->ps)
-    return fail(-1, "set_tone: an input buffer needs a resampler, a stretcher or a pitcher on the state");
-  s->tn = tn;
-  s->tn_in = tn ? d_in : nullptr;
-  s->tn_out = tn ? d_out : nullptr;
-  return 0;
+  return set_link(s, CH_TN, tn, d_in, d_out, 0);
 }
 
-// Loudness: while a normaliser is set, its launch follows the pitch launch and precedes the level launch.  d_in == NULL: it
-// reads the frame's fp32 PCM; otherwise the buffer d_in, which the caller has given the stage before it as its output.  It
-// always writes f32 into the device buffer d_out, which the leveler then reads: a frame enqueued with a normaliser but no
-// leveler fails.  NULL switches it off: decodes and captures are then launch for launch what they were.
+// a frame enqueued with a normaliser but no leveler fails
 extern "C" int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out) {
-  if (!s) return fail(-1, "null state");
-  if (ln && !d_out) return fail(-1, "set_loudnorm: null output");
-  if (ln && d_in == d_out) return fail(-1, "set_loudnorm: the stage does not work in place");
-  if (ln && loud_batch(ln) != s->B) return fail(-1, "set_loudnorm: the normaliser's batch is not the state's");
-  if (ln && !d_in && loud_width(ln) != s->rows[3]) return fail(-1, "set_loudnorm: the normaliser's frame length is not the state's");
-  if (ln && d_in && !s->rs && !s->ts && !s->ps && !s->tn)
-    return fail(-1, "set_loudnorm: an input buffer needs a resampler, a stretcher, a pitcher or a toner on the state");
-  s->ln = ln;
-  s->ln_in = ln ? d_in : nullptr;
-  s->ln_out = ln ? d_out : nullptr;
-  return 0;
+  return set_link(s, CH_LN, ln, d_in, d_out, 0);
 }
 
-// Output level: while a leveler is set, its launch is the last one of a frame.  d_in == NULL: it reads the frame's fp32 PCM;
-// otherwise the buffer d_in, which the caller has given the stage before it as its output.  NULL switches it off: decodes and
-// captures are then launch for launch what they were.
 extern "C" int ptts_mimi_set_leveler(ptts_mimi_state *s, ptts_leveler *lv, float *d_in, void *out, int32_t is_i16) {
-  if (!s) return fail(-1, "null state");
-  if (lv && !out) return fail(-1, "set_leveler: null output");
-  if (lv && level_batch(lv) != s->B) return fail(-1, "set_leveler: the leveler's batch is not the state's");
-  if (lv && !d_in && level_width(lv) != s->rows[3]) return fail(-1, "set_leveler: the leveler's frame length is not the state's");
-  if (lv && d_in && !s->rs && !s->ts && !s->ps && !s->tn && !s->ln)
-    return fail(-1, "set_leveler: an input buffer needs a resampler, a stretcher, a pitcher, a toner or a normaliser on the state");
-  s->lv = lv;
-  s->lv_in = lv ? d_in : nullptr;
-  s->lv_out = lv ? out : nullptr;
-  s->lv_i16 = lv ? (is_i16 != 0) : 0;
-  return 0;
+  return set_link(s, CH_LV, lv, d_in, out, is_i16);
 }
 
-// Output encoding: while an encoder is set, its launch is the last one of a frame.  d_in == NULL: it reads the frame's fp32
-// PCM and is the only stage; otherwise the buffer d_in, into which the last stage before it (leveler, else pitcher, else
-// stretcher, else resampler) writes f32 instead of its own output.  NULL switches it off: decodes and captures are then launch
-// for launch what they were.
+// its own: the stage before_encoder() names writes f32 into d_in instead of its own output, so the encoder has an input
+// buffer exactly when there is such a stage, and is as wide as that stage's widest line
 extern "C" int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float *d_in, void *out_bytes) {
-  if (!s) return fail(-1, "null state");
-  if (en && !out_bytes) return fail(-1, "set_encoder: null output");
-  if (en && encode_batch(en) != s->B) return fail(-1, "set_encoder: the encoder's batch is not the state's");
-  const bool staged = s->rs || s->ts || s->ps || s->lv;
-  if (en && !d_in && staged) return fail(-1, "set_encoder: the state has output stages, the encoder needs an input buffer");
-  if (en && !d_in && encode_width(en) != s->rows[3]) return fail(-1, "set_encoder: the encoder's frame length is not the state's");
-  if (en && d_in && !staged)
-    return fail(-1, "set_encoder: an input buffer needs a resampler, a stretcher, a pitcher or a leveler on the state");
-  if (en && d_in) {
-    const int w = s->lv ? level_width(s->lv) : s->ps ? pitch_width(s->ps) : s->ts ? stretch_out_max(s->ts) : resample_out_max(s->rs);
-    if (w != encode_width(en)) return fail(-1, "set_encoder: the encoder's width is not the widest line of the stage before it");
-  }
-  s->en = en;
-  s->en_in = en ? d_in : nullptr;
-  s->en_out = en ? out_bytes : nullptr;
-  return 0;
+  return set_link(s, CH_EN, en, d_in, out_bytes, 0, [&]() -> const char * {
+    const int before = before_encoder(s);
+    if (!d_in && before >= 0) return "set_encoder: the state has output stages, the encoder needs an input buffer";
+    if (d_in && before < 0)
+      return "set_encoder: an input buffer needs a resampler, a stretcher, a pitcher or a leveler on the state";
+    if (d_in && kChain[before].out_width(s->chain[before].stage) != encode_width(en))
+      return "set_encoder: the encoder's width is not the widest line of the stage before it";
+    return nullptr;
+  });
 }
 
-// the codec frame, then the launches of the output stages the state has
+// the codec frame, then the launches of the links the state has; every refusal comes before the first launch
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
-  if (s->ln && !s->lv) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
-  if (s->tn && !s->lv) return fail(-1, "the toner must be followed by a leveler, but the state has none");
-  // the stage the encoder follows: 4 leveler, 3 pitcher, 2 stretcher, 1 resampler, 0 none; -1 without an encoder
-  const int fed = !s->en ? -1 : s->lv ? 4 : s->ps ? 3 : s->ts ? 2 : s->rs ? 1 : 0;
-  if (s->en && (fed > 0) != (s->en_in != nullptr))
+  const ChainLink *c = s->chain, &ts = c[CH_TS], &en = c[CH_EN];
+  if (c[CH_LN].stage && !c[CH_LV].stage) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
+  if (c[CH_TN].stage && !c[CH_LV].stage) return fail(-1, "the toner must be followed by a leveler, but the state has none");
+  const int before = en.stage ? before_encoder(s) : -1;
+  if (en.stage && (before >= 0) != (en.in != nullptr))
     return fail(-1, "the encoder's input buffer and the state's output stages do not go together");
+  const bool chained = ts.stage && ts.in;  // resampler -> ts.in -> stretcher
+  if (chained && !c[CH_RS].stage) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
-  if (!s->rs && !s->ts && !s->ps && !s->tn && !s->ln && !s->lv && !s->en) return 0;
-  const bool chained = s->ts && s->ts_in;  // resampler -> ts_in -> stretcher
-  if (chained && !s->rs) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
-  int r = 0;
-  if (s->rs) {
-    SITE("resample");
-    if (fed == 1) r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, s->en_in, 0);
-    else r = resample_enqueue(st, s->rs, d_pcm ? d_pcm : s->pcm_dbg, chained ? (void *)s->ts_in : s->rs_out, chained ? 0 : s->rs_i16);
+  for (int k = 0; k < CH_N; k++) {
+    if (!c[k].stage) continue;
+    // a stage writes its own output, but for two that write f32 into the next one's input buffer: the stage before the
+    // encoder, and the resampler before a stretcher that has one
+    float *next = k == before ? en.in : k == CH_RS && chained ? ts.in : nullptr;
+    const float *in = c[k].in ? c[k].in : (d_pcm ? d_pcm : s->pcm_dbg);
+    SITE(kChain[k].site);
+    const int r = kChain[k].enqueue(st, c[k].stage, in, next ? (void *)next : c[k].out, next ? 0 : c[k].i16);
     SITE("");
+    if (r != 0) return r;
   }
-  if (r == 0 && s->ts) {
-    SITE("stretch");
-    r = stretch_enqueue(st, s->ts, chained ? s->ts_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 2 ? (void *)s->en_in : s->ts_out,
-                        fed == 2 ? 0 : s->ts_i16, nullptr);
-    SITE("");
-  }
-  if (r == 0 && s->ps) {
-    SITE("pitch");
-    r = pitch_enqueue(st, s->ps, s->ps_in ? s->ps_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 3 ? (void *)s->en_in : s->ps_out,
-                      fed == 3 ? 0 : s->ps_i16, nullptr, nullptr);
-    SITE("");
-  }
-  if (r == 0 && s->tn) {
-    SITE("tone");
-    r = tone_enqueue(st, s->tn, s->tn_in ? s->tn_in : (d_pcm ? d_pcm : s->pcm_dbg), s->tn_out);
-    SITE("");
-  }
-  if (r == 0 && s->ln) {
-    SITE("loudnorm");
-    r = loud_enqueue(st, s->ln, s->ln_in ? s->ln_in : (d_pcm ? d_pcm : s->pcm_dbg), s->ln_out, nullptr);
-    SITE("");
-  }
-  if (r == 0 && s->lv) {
-    SITE("level");
-    r = level_enqueue(st, s->lv, s->lv_in ? s->lv_in : (d_pcm ? d_pcm : s->pcm_dbg), fed == 4 ? (void *)s->en_in : s->lv_out,
-                      fed == 4 ? 0 : s->lv_i16);
-    SITE("");
-  }
-  if (r == 0 && s->en) {
-    SITE("encode");
-    r = encode_enqueue(st, s->en, s->en_in ? s->en_in : (d_pcm ? d_pcm : s->pcm_dbg), s->en_out);
-    SITE("");
-  }
-  return r;
+  return 0;
 }
 
 extern "C" int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream) {

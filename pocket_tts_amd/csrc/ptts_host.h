@@ -237,6 +237,15 @@ struct ptts_lm_state {
   float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
 };
 
+// the kinds of output stage in launch order: resampler, stretcher, pitcher, toner, normaliser, leveler, encoder
+enum { CH_RS, CH_TS, CH_PS, CH_TN, CH_LN, CH_LV, CH_EN, CH_N };
+struct ChainLink {
+  void *stage = nullptr;
+  float *in = nullptr;
+  void *out = nullptr;
+  int i16 = 0;
+};
+
 struct ptts_mimi_state {
   ptts_engine *e;
   int B, MTb, MT16;
@@ -253,43 +262,11 @@ struct ptts_mimi_state {
   int rows[4];  // rows per sequence at each SEANet stage
   float *pcm_dbg;
   int16_t *pcm_i16 = nullptr;
-  // output sample rates (ptts_mimi_set_resampler): the two resampler launches follow the codec's last kernel
-  ptts_resampler *rs = nullptr;
-  void *rs_out = nullptr;
-  int rs_i16 = 0;
-  // speaking rate (ptts_mimi_set_stretcher): the stretch launch follows the codec's last kernel (ts_in == nullptr) or the
-  // resampler, which then writes f32 into ts_in
-  ptts_stretcher *ts = nullptr;
-  float *ts_in = nullptr;
-  void *ts_out = nullptr;
-  int ts_i16 = 0;
-  // pitch (ptts_mimi_set_pitcher): the pitch launch follows the stretch launch and precedes the level launch; it reads the
-  // frame's PCM (ps_in == nullptr) or ps_in, the buffer the stage before it writes
-  ptts_pitcher *ps = nullptr;
-  float *ps_in = nullptr;
-  void *ps_out = nullptr;
-  int ps_i16 = 0;
-  // tone (ptts_mimi_set_tone): the toner's launch follows the pitch launch and precedes the normaliser's; it reads the
-  // frame's PCM (tn_in == nullptr) or tn_in, the buffer the stage before it writes, and writes f32 into tn_out
-  ptts_tone *tn = nullptr;
-  float *tn_in = nullptr;
-  float *tn_out = nullptr;
-  // loudness (ptts_mimi_set_loudnorm): the normaliser's launch follows the pitch launch and precedes the level launch; it
-  // reads the frame's PCM (ln_in == nullptr) or ln_in, the buffer the stage before it writes, and writes f32 into ln_out
-  ptts_loudnorm *ln = nullptr;
-  float *ln_in = nullptr;
-  float *ln_out = nullptr;
-  // output level (ptts_mimi_set_leveler): the level launch is the last one; it reads the frame's PCM (lv_in == nullptr) or
-  // lv_in, the buffer the stage before it writes
-  ptts_leveler *lv = nullptr;
-  float *lv_in = nullptr;
-  void *lv_out = nullptr;
-  int lv_i16 = 0;
-  // output encoding (ptts_mimi_set_encoder): the encode launch is then the last one; it reads the frame's PCM (en_in ==
-  // nullptr) or en_in, into which the stage before it writes f32 instead of its own output
-  ptts_encoder *en = nullptr;
-  float *en_in = nullptr;
-  void *en_out = nullptr;
+  // the output stages behind the codec (ptts_mimi_set_*), one link per kind in launch order.  A link is empty (stage == nullptr)
+  // or holds the stage, the f32 device buffer it reads (`in`; nullptr: the frame's PCM) and what it writes (`out`, int16 with
+  // `i16`, else f32; the encoder's bytes).  mimi_frame_enqueue in ptts.hip states the two cases in which a stage writes
+  // another link's `in` instead
+  ChainLink chain[CH_N];
   // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
   float *pcm_part = nullptr, *pcm_carry = nullptr;
   long pcm_cstride = 0;

@@ -1,5 +1,5 @@
-"""Per-request output encoding: the last stage of the output chain codec -> resampler -> stretcher -> pitcher -> normaliser
--> level -> encoder (the kernel is csrc/ptts_encode.hip; pure Python, nothing here touches the GPU).
+"""Per-request output encoding: the last stage of the output chain, behind the leveler (`output_chain.py` gives its order;
+the kernel is csrc/ptts_encode.hip; pure Python, nothing here touches the GPU).
 
 A row's input `x` is whatever leaves the previous stage for that row, `n` fp32 samples per frame.  The stage writes
 n * bytes_per_sample bytes at the start of the row's line of the output and nothing behind them.  It has no state, no

@@ -224,103 +224,47 @@ class MimiState:
         """int16 copy of the PCM written by the decodes / graph captures issued after this call (None: off)"""
         _lib.check(self.engine.lib.ptts_mimi_set_pcm_i16(self.handle, _ptr(buf) if buf is not None else None))
 
+    def _set_stage(self, kind, stage, out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """The decodes / graph captures issued after this call run `stage`, an output stage of the class `kind`, behind the
+        codec's last kernel, at its place in the chain resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler ->
+        encoder (`output_chain.py`; the C side is `kind._attach` of include/ptts.h).  It writes `out`: [B, its output width],
+        float32 or int16, device or pinned host; float32 on the device for the toner and the normaliser, which a leveler
+        must follow; uint8 [B, en.pitch] for the encoder.  `mid` None: it reads the frame's PCM, which must then be a DEVICE
+        tensor.  Otherwise it reads the float32 device tensor `mid` [B, its input width], which the caller has given the
+        stage before it as its `out`; that stage must be set on this state already, so stages are set in chain order.  A
+        resampler is always first and has no `mid`.  `stage` None: off, the launches are those of before."""
+        args = [None, None, None]
+        if stage is not None:
+            stage._check_written(out)
+            if mid is not None:
+                stage._check_in(mid)
+            args = [stage.handle, _ptr(mid), _ptr(out)]
+        if kind is Resampler:
+            del args[1]
+        if kind._i16:
+            args.append(int(stage is not None and out.dtype == torch.int16))
+        _lib.check(getattr(self.engine.lib, kind._attach)(self.handle, *args))
+
     def set_resampler(self, rs: "Resampler | None", out: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `rs` behind the codec's last kernel: the frame's PCM
-        (which must then be a DEVICE tensor) is resampled into `out` [B, rs.out_max], float32 or int16, device or pinned
-        host (include/ptts.h: ptts_mimi_set_resampler).  None: off, the launches are those of before."""
-        if rs is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_resampler(self.handle, None, None, 0))
-            return
-        rs._check_out(out)
-        _lib.check(self.engine.lib.ptts_mimi_set_resampler(self.handle, rs.handle, _ptr(out), int(out.dtype == torch.int16)))
+        self._set_stage(Resampler, rs, out)
 
     def set_stretcher(self, ts: "Stretcher | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `ts` as the last output stage, writing `out`
-        [B, ts.out_max], float32 or int16, device or pinned host (include/ptts.h: ptts_mimi_set_stretcher).  `mid` None:
-        behind the codec's last kernel (the frame's PCM must then be a DEVICE tensor); otherwise behind the resampler set
-        on this state, which then writes float32 into the device tensor `mid` [B, ts.in_max].  None: off."""
-        if ts is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_stretcher(self.handle, None, None, None, 0))
-            return
-        ts._check_out(out)
-        if mid is not None:
-            ts._check_in(mid)
-        _lib.check(self.engine.lib.ptts_mimi_set_stretcher(self.handle, ts.handle, _ptr(mid) if mid is not None else None,
-                                                           _ptr(out), int(out.dtype == torch.int16)))
+        self._set_stage(Stretcher, ts, out, mid)
 
     def set_pitcher(self, ps: "Pitcher | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `ps` behind the stretcher's launch (if any) and before
-        the leveler's, writing `out` [B, ps.width], float32 or int16, device or pinned host (include/ptts.h:
-        ptts_mimi_set_pitcher).  `mid` None: it reads the frame's PCM (which must then be a DEVICE tensor); otherwise the
-        float32 device tensor `mid` [B, ps.width], which the caller has given the resampler or the stretcher set on this
-        state as its output.  None: off."""
-        if ps is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_pitcher(self.handle, None, None, None, 0))
-            return
-        ps._check_out(out)
-        if mid is not None:
-            ps._check_in(mid)
-        _lib.check(self.engine.lib.ptts_mimi_set_pitcher(self.handle, ps.handle, _ptr(mid) if mid is not None else None,
-                                                         _ptr(out), int(out.dtype == torch.int16)))
-
-    def set_leveler(self, lv: "Leveler | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `lv` as their last launch, writing `out` [B, lv.width],
-        float32 or int16, device or pinned host (include/ptts.h: ptts_mimi_set_leveler).  `mid` None: it reads the frame's
-        PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid` [B, lv.width], which the caller
-        has given the resampler, the stretcher or the pitcher set on this state as its output.  None: off."""
-        if lv is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, None, None, None, 0))
-            return
-        lv._check_out(out)
-        if mid is not None:
-            lv._check_in(mid)
-        _lib.check(self.engine.lib.ptts_mimi_set_leveler(self.handle, lv.handle, _ptr(mid) if mid is not None else None,
-                                                         _ptr(out), int(out.dtype == torch.int16)))
+        self._set_stage(Pitcher, ps, out, mid)
 
     def set_tone(self, tn: "Toner | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `tn` behind the pitcher's launch (if any) and before the
-        normaliser's, writing float32 into the device tensor `out` [B, tn.width], which the caller gives the normaliser or
-        the leveler as its `mid` (include/ptts.h: ptts_mimi_set_tone; a frame with a toner but no leveler fails).  `mid`
-        None: it reads the frame's PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid`
-        [B, tn.width], which the caller has given the resampler, the stretcher or the pitcher set on this state as its
-        output.  None: off."""
-        if tn is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_tone(self.handle, None, None, None))
-            return
-        tn._check_in(out)
-        if mid is not None:
-            tn._check_in(mid)
-        _lib.check(self.engine.lib.ptts_mimi_set_tone(self.handle, tn.handle, _ptr(mid) if mid is not None else None,
-                                                      _ptr(out)))
+        self._set_stage(Toner, tn, out, mid)
 
     def set_loudnorm(self, ln: "Normalizer | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `ln` behind the pitcher's launch (if any) and before the
-        leveler's, writing float32 into the device tensor `out` [B, ln.width], which the caller gives the leveler as its
-        `mid` (include/ptts.h: ptts_mimi_set_loudnorm; a frame with a normaliser but no leveler fails).  `mid` None: it reads
-        the frame's PCM (which must then be a DEVICE tensor); otherwise the float32 device tensor `mid` [B, ln.width], which
-        the caller has given the resampler, the stretcher or the pitcher set on this state as its output.  None: off."""
-        if ln is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_loudnorm(self.handle, None, None, None))
-            return
-        ln._check_in(out)
-        if mid is not None:
-            ln._check_in(mid)
-        _lib.check(self.engine.lib.ptts_mimi_set_loudnorm(self.handle, ln.handle, _ptr(mid) if mid is not None else None,
-                                                          _ptr(out)))
+        self._set_stage(Normalizer, ln, out, mid)
+
+    def set_leveler(self, lv: "Leveler | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        self._set_stage(Leveler, lv, out, mid)
 
     def set_encoder(self, en: "Encoder | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
-        """The decodes / graph captures issued after this call run `en` as their last launch, writing the uint8 tensor `out`
-        [B, en.pitch], device or pinned host (include/ptts.h: ptts_mimi_set_encoder).  `mid` None: it reads the frame's PCM
-        (which must then be a DEVICE tensor) and is the only output stage; otherwise the float32 device tensor `mid`
-        [B, en.width], into which the last stage set on this state writes float32 instead of its own output.  None: off."""
-        if en is None:
-            _lib.check(self.engine.lib.ptts_mimi_set_encoder(self.handle, None, None, None))
-            return
-        en._check_bytes(out)
-        if mid is not None:
-            en._check_in(mid)
-        _lib.check(self.engine.lib.ptts_mimi_set_encoder(self.handle, en.handle, _ptr(mid) if mid is not None else None,
-                                                         _ptr(out)))
+        self._set_stage(Encoder, en, out, mid)
 
     def __del__(self):
         try:
@@ -330,11 +274,15 @@ class MimiState:
 
 
 class _Stage:
-    """What the output stages share.  A subclass names itself (`_name`, in error texts) and its C ABI destroy function
-    (`_destroy`), gives the widths of its lines (`_in_width`, `_out_width`) and, in `_row_args(row)`, what `set_row` last
-    dealt the row according to its host mirror."""
+    """What the output stages share.  A subclass names itself (`_name`, in error texts; `_field`, the request field it
+    serves) and its C ABI functions: `_destroy`, `_attach` (its ptts_mimi_set_*, `MimiState._set_stage`) and `_drain` (its
+    set_row_drain, None for a stage without a drain flag, which `Route.drain_stage` calls `_drain_name`).  `_i16`: it
+    writes float32 or int16, so those functions take is_i16; otherwise `_check_written` says what it writes.  It gives the
+    widths of its lines (`_in_width`, `_out_width`), in `_row_args(row)` what `set_row` last dealt the row according to its
+    host mirror, and in `_route_args(route)` what `set_row` deals a row on that `output_chain.Route`."""
 
-    _name = _destroy = None
+    _name = _field = _destroy = _attach = _drain = _drain_name = None
+    _i16 = True
 
     def __init__(self, engine: "Engine", batch: int):
         self.engine, self.batch = engine, batch
@@ -358,13 +306,22 @@ class _Stage:
         if x is None or x.device != dev or x.dtype != torch.float32 or list(x.shape) != shape or not x.is_contiguous():
             raise ValueError(f"{self._name} input: expected a contiguous float32 {shape} tensor on {dev}")
 
+    _check_written = _check_out  # what checks the tensor the stage writes
+
+    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
+        """from now on (stream-ordered) the row's incoming frames count as zeros"""
+        if self._drain is None:
+            raise AttributeError(f"the {self._name} has no drain flag")
+        _lib.check(getattr(self.engine.lib, self._drain)(self.handle, int(row), int(bool(on)), self._sp(stream)))
+
     def _frame(self, fn, x, out, stream, *extra):
-        """`fn(handle, x, out, is_i16, *extra, stream)` on `stream`, or on the engine's stream ordered against torch's
+        """`fn(handle, x, out, [is_i16,] *extra, stream)` on `stream`, or on the engine's stream ordered against torch's
         current one"""
         e = self.engine
         if stream is None:
             e._pre()
-        _lib.check(fn(self.handle, _ptr(x), _ptr(out), int(out.dtype == torch.int16), *map(_ptr, extra), self._sp(stream)))
+        i16 = (int(out.dtype == torch.int16),) if self._i16 else ()
+        _lib.check(fn(self.handle, _ptr(x), _ptr(out), *i16, *map(_ptr, extra), self._sp(stream)))
         if stream is None:
             for t in (x, out, *extra):
                 if t is not None and t.is_cuda:
@@ -389,7 +346,9 @@ class Stretcher(_Stage):
     `frame(x, out)` turns one frame x[b, :n_in(plan of b)] into out[b, :n_out(plan of b)]; `set_row_drain` makes a row's
     incoming frames count as zeros, which flushes its tail."""
 
-    _name, _destroy = "stretcher", "ptts_stretcher_destroy"
+    _name, _field, _destroy, _attach = "stretcher", "speed", "ptts_stretcher_destroy", "ptts_mimi_set_stretcher"
+    _drain, _drain_name = "ptts_stretcher_set_row_drain", "stretch"
+    _route_args = staticmethod(lambda r: (r.stretch_plan,))
 
     def __init__(self, engine: "Engine", batch: int, plans):
         super().__init__(engine, batch)
@@ -419,10 +378,6 @@ class Stretcher(_Stage):
         _lib.check(self.engine.lib.ptts_stretcher_set_row(self.handle, int(row), int(plan_index), self._sp(stream)))
         self.row_plan[row] = int(plan_index)
 
-    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
-        """from now on (stream-ordered) the row's incoming frames count as zeros"""
-        _lib.check(self.engine.lib.ptts_stretcher_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
-
     def frame(self, x: torch.Tensor, out: torch.Tensor, delta: torch.Tensor | None = None,
               stream: torch.cuda.Stream | None = None):
         """x f32[B, in_max] on the device -> out (float32 or int16 [B, out_max], device or pinned host); `delta` (int32
@@ -442,7 +397,9 @@ class Pitcher(_Stage):
     frame x[b, :n(plan of b)] into out[b, :n(plan of b)], every frequency moved by the plan's ratio, `preroll` samples late;
     `set_row_drain` makes a row's incoming frames count as zeros, which flushes its tail."""
 
-    _name, _destroy = "pitcher", "ptts_pitcher_destroy"
+    _name, _field, _destroy, _attach = "pitcher", "pitch", "ptts_pitcher_destroy", "ptts_mimi_set_pitcher"
+    _drain, _drain_name = "ptts_pitcher_set_row_drain", "pitch"
+    _route_args = staticmethod(lambda r: (r.pitch_plan,))
 
     def __init__(self, engine: "Engine", batch: int, plans):
         super().__init__(engine, batch)
@@ -470,10 +427,6 @@ class Pitcher(_Stage):
         _lib.check(self.engine.lib.ptts_pitcher_set_row(self.handle, int(row), int(plan_index), self._sp(stream)))
         self.row_plan[row] = int(plan_index)
 
-    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
-        """from now on (stream-ordered) the row's incoming frames count as zeros"""
-        _lib.check(self.engine.lib.ptts_pitcher_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
-
     def frame(self, x: torch.Tensor, out: torch.Tensor, delta: torch.Tensor | None = None, mid: torch.Tensor | None = None,
               stream: torch.cuda.Stream | None = None):
         """x f32[B, width] on the device -> out (float32 or int16 [B, width], device or pinned host); the test taps `delta`
@@ -496,7 +449,9 @@ class Leveler(_Stage):
     out[b, :n(plan of b)], LA samples late; `set_row_drain` makes a row's incoming frames count as zeros, which flushes its
     tail.  A bypass row's whole line is copied."""
 
-    _name, _destroy = "leveler", "ptts_leveler_destroy"
+    _name, _field, _destroy, _attach = "leveler", "level", "ptts_leveler_destroy", "ptts_mimi_set_leveler"
+    _drain, _drain_name = "ptts_leveler_set_row_drain", "level"
+    _route_args = staticmethod(lambda r: r.level or (None, None, None))
 
     def __init__(self, engine: "Engine", batch: int, plans):
         super().__init__(engine, batch)
@@ -529,10 +484,6 @@ class Leveler(_Stage):
         _lib.check(self.engine.lib.ptts_leveler_set_row(self.handle, int(row), idx, G, Cc, self._sp(stream)))
         self.rows[row] = (idx, g, c)
 
-    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
-        """from now on (stream-ordered) the row's incoming frames count as zeros"""
-        _lib.check(self.engine.lib.ptts_leveler_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
-
     def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """x f32[B, width] on the device -> out (float32 or int16 [B, width], device or pinned host)"""
         self._check_in(x)
@@ -548,7 +499,10 @@ class Normalizer(_Stage):
     target; `set_row_drain` makes a row's incoming frames count as zeros, which flushes its tail.  A bypass row's whole line
     is copied.  The output is always float32 on the device: the stage is never the last one."""
 
-    _name, _destroy = "normaliser", "ptts_loudnorm_destroy"
+    _name, _field, _destroy, _attach = "normaliser", "loudness", "ptts_loudnorm_destroy", "ptts_mimi_set_loudnorm"
+    _drain, _drain_name = "ptts_loudnorm_set_row_drain", "loud"
+    _i16, _check_written = False, _Stage._check_in
+    _route_args = staticmethod(lambda r: r.loud or (None, None))
 
     def __init__(self, engine: "Engine", batch: int, plans):
         super().__init__(engine, batch)
@@ -582,10 +536,6 @@ class Normalizer(_Stage):
         _lib.check(self.engine.lib.ptts_loudnorm_set_row(self.handle, int(row), idx, t_arg, self._sp(stream)))
         self.rows[row] = (idx, t)
 
-    def set_row_drain(self, row: int, on: bool = True, stream: torch.cuda.Stream | None = None):
-        """from now on (stream-ordered) the row's incoming frames count as zeros"""
-        _lib.check(self.engine.lib.ptts_loudnorm_set_row_drain(self.handle, int(row), int(bool(on)), self._sp(stream)))
-
     def frame(self, x: torch.Tensor, out: torch.Tensor, tap: torch.Tensor | None = None,
               stream: torch.cuda.Stream | None = None):
         """x f32[B, width] -> out f32[B, width], both on the device and distinct; the test tap `tap` (float64 [B, 4] on the
@@ -596,14 +546,7 @@ class Normalizer(_Stage):
         if tap is not None and (tap.device != e.device or tap.dtype != torch.float64 or not tap.is_contiguous()
                                 or tuple(tap.shape) != (self.batch, 4)):
             raise ValueError(f"normaliser tap: expected a contiguous float64 [{self.batch}, 4] tensor on {e.device}")
-        if stream is None:
-            e._pre()
-        _lib.check(e.lib.ptts_loudnorm_frame(self.handle, _ptr(x), _ptr(out), _ptr(tap), self._sp(stream)))
-        if stream is None:
-            for t in (x, out, tap):
-                if t is not None:
-                    t.record_stream(e.stream)
-            e._post()
+        self._frame(e.lib.ptts_loudnorm_frame, x, out, stream, tap)
 
 
 class Encoder(_Stage):
@@ -613,7 +556,9 @@ class Encoder(_Stage):
     [batch, `pitch`] tensor with `pitch` = `encoding.pitch(width)`, and writes nothing behind them.  The stage has no state
     and no drain flag."""
 
-    _name, _destroy = "encoder", "ptts_encoder_destroy"
+    _name, _field, _destroy, _attach = "encoder", "encoding", "ptts_encoder_destroy", "ptts_mimi_set_encoder"
+    _i16 = False
+    _route_args = staticmethod(lambda r: (r.n_out, r.encoding))
 
     def __init__(self, engine: "Engine", batch: int, width: int):
         from . import encoding
@@ -637,6 +582,8 @@ class Encoder(_Stage):
         if not out.is_cuda and not out.is_pinned():
             raise ValueError(f"{self._name} output: a host tensor must be pinned")
 
+    _check_written = _check_bytes
+
     def set_row(self, row: int, n: int, encoding: str | None = None, stream: torch.cuda.Stream | None = None):
         """`row` holds `n` samples in `encoding` (None: "pcm_s16le") from now on.  Stream-ordered"""
         from . import encoding as rule
@@ -647,17 +594,9 @@ class Encoder(_Stage):
 
     def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """x f32[B, width] on the device -> out u8[B, pitch], device or pinned host"""
-        e = self.engine
         self._check_in(x)
         self._check_bytes(out)
-        if stream is None:
-            e._pre()
-        _lib.check(e.lib.ptts_encode_frame(self.handle, _ptr(x), _ptr(out), self._sp(stream)))
-        if stream is None:
-            for t in (x, out):
-                if t.is_cuda:
-                    t.record_stream(e.stream)
-            e._post()
+        self._frame(self.engine.lib.ptts_encode_frame, x, out, stream)
 
 
 class Toner(_Stage):
@@ -668,7 +607,9 @@ class Toner(_Stage):
     width, the largest n of the plans where it is left out.  The output is always float32 on the device: the stage is never
     the last one."""
 
-    _name, _destroy = "toner", "ptts_tone_destroy"
+    _name, _field, _destroy, _attach = "toner", "tone", "ptts_tone_destroy", "ptts_mimi_set_tone"
+    _i16, _check_written = False, _Stage._check_in
+    _route_args = staticmethod(lambda r: (r.tone_plan,))
 
     def __init__(self, engine: "Engine", batch: int, plans, width: int | None = None):
         super().__init__(engine, batch)
@@ -699,16 +640,9 @@ class Toner(_Stage):
 
     def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """x f32[B, width] -> out f32[B, width], both on the device and distinct"""
-        e = self.engine
         self._check_in(x)
         self._check_in(out)
-        if stream is None:
-            e._pre()
-        _lib.check(e.lib.ptts_tone_frame(self.handle, _ptr(x), _ptr(out), self._sp(stream)))
-        if stream is None:
-            for t in (x, out):
-                t.record_stream(e.stream)
-            e._post()
+        self._frame(self.engine.lib.ptts_tone_frame, x, out, stream)
 
 
 class Resampler(_Stage):
@@ -718,7 +652,8 @@ class Resampler(_Stage):
     `out[b, :out_n(rate of b)]`; each row carries 64 input samples from frame to frame, `set_row` zeroes them.  `plans`:
     the `rate_plans` of an `output_chain.ChainTable` that has designed the rates' filters already."""
 
-    _name, _destroy = "resampler", "ptts_resampler_destroy"
+    _name, _field, _destroy, _attach = "resampler", "sample_rate", "ptts_resampler_destroy", "ptts_mimi_set_resampler"
+    _route_args = staticmethod(lambda r: (r.rate_index,))
 
     def __init__(self, engine: "Engine", batch: int, sample_rates, plans=None):
         from .output_chain import ChainTable
@@ -1398,8 +1333,8 @@ class StepPipeline:
     `sample_rates` (a list of output rates, `resample.py`), `speeds` (a list of speaking rates, `stretch.py`; each must be
     admissible at one of the rates at least), `pitches` (a list of frequency ratios, `pitch.py`; each admissible on one of
     the lines at least), `loudness` (True: per-row loudness target, `loudness.py`; it brings the leveler with it) and
-    `level` (True: per-row gain and limiter, `level.py`) configure the output chain codec -> resampler -> stretcher ->
-    pitcher -> normaliser -> level (`output_chain.py`; not in "fork" mode): the codec graphs end with its stages' launches.
+    `level` (True: per-row gain and limiter, `level.py`) configure the output chain behind the codec (`output_chain.py`
+    gives its order; not in "fork" mode): the codec graphs end with its stages' launches.
     `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts`, `ps`, `ln` and `lv`.
     `pcm[p]` are then DEVICE tensors and the samples reach the host through `out[p]`, the chain's pinned ring, int16 with
     `pcm_i16`, else float32: `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  A row gets
@@ -1440,8 +1375,8 @@ class StepPipeline:
         # read flag[t % nb] / pcm[t % nb] of step t - nb before it calls step() for step t.
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
-        self.rs, self.ts, self.lv, self.out = self.chain.rs, self.chain.ts, self.chain.lv, self.chain.out
-        self.ps, self.ln, self.en, self.tn = self.chain.ps, self.chain.ln, self.chain.en, self.chain.tn
+        self.out = self.chain.out
+        self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host

@@ -1,5 +1,5 @@
 """Per-request loudness target: a streaming ITU-R BS.1770-4 normaliser, the stage of the output chain
-codec -> resampler -> stretcher -> pitcher -> normaliser -> level that sits before the peak limiter (the kernel is
+(`output_chain.py` gives its order) that sits behind the toner and before the peak limiter (the kernel is
 csrc/ptts_loud.hip; numpy only, nothing here touches the GPU).
 
 A row's input stream `x` is whatever leaves the previous stage for that row, `n` samples per frame; x[i] = 0 for i < 0 and

@@ -1,8 +1,16 @@
-"""The output chain codec -> resampler -> stretcher -> pitcher -> tone -> normaliser -> level -> encoder as one object: what a pipeline's stages are (`ChainTable`), what
-a request's row does in them (`Route`), and the stage objects and buffers on the device (`OutputChain`).
+"""The output chain as one object: what a pipeline's stages are (`ChainTable`), what a request's row does in them (`Route`),
+and the stage objects and buffers on the device (`OutputChain`).
 
-The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `tone.py`, `loudness.py` and `level.py`: it needs no library, no
-GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
+The order, which is also the launch order behind the codec's last kernel:
+
+    codec -> resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder
+
+A pipeline has any subset of the seven stages; the toner and the normaliser bring the leveler with them.  The buffer rule: the
+first stage present reads the frame's PCM; between two consecutive stages present there is one f32 device buffer [batch, input
+width of the later one], which must be the output width of the earlier one; the last stage writes the pinned ring.
+
+The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `tone.py`, `loudness.py` and
+`level.py`: it needs no library, no GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
 yields, how many leading samples to drop, how many drain frames flush its tail and which stage's drain flag to raise - is a
 `Route`; nothing outside this module composes the six plan rules.
 
@@ -303,14 +311,13 @@ class ChainTable:
 
 
 class OutputChain:
-    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `ln` / `lv` (`engine.Resampler`,
-    `Stretcher`, `Pitcher`, `Toner`, `Normalizer`, `Leveler`; None where the table has no such stage), the device buffers between them and the pinned ring `out` of `nb`
-    [batch, widest line] tensors, int16 with `pcm_i16`, else float32, which the last stage writes.  An empty table creates
-    nothing: `out` is None and the codec writes its PCM as without a chain.  On a table with `encodings` the chain ends with
-    `en` (`engine.Encoder`): `out` is then a ring of pinned uint8 [batch, encoding.pitch(widest line)] tensors that the encoder
-    writes, row b's n_out * bytes_per_sample bytes at the start of its row, `en_in` is the one device buffer the stage
-    before the encoder writes (None where the encoder is the only stage and reads the frame's PCM), and `pcm_i16` must be
-    left False (ValueError)."""
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `ln` / `lv` / `en`
+    (`engine.Resampler`, `Stretcher`, `Pitcher`, `Toner`, `Normalizer`, `Leveler`, `Encoder`; None where the table has no
+    such stage), the device buffers between them and the pinned ring `out` of `nb` tensors, which the last stage writes.
+    The buffer rule of the module's docstring gives them: without the encoder a ring slot is [batch, widest line], int16
+    with `pcm_i16`, else float32; on a table with `encodings` it is uint8 [batch, encoding.pitch(widest line)], row b's
+    n_out * bytes_per_sample bytes at the start of its row, and `pcm_i16` must be left False (ValueError).  An empty table
+    creates nothing: `out` is None and the codec writes its PCM as without a chain."""
 
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
@@ -326,119 +333,57 @@ class OutputChain:
         self.tn = Toner(engine, batch, table.tone_plans, table.width) if table.tone_plans is not None else None
         self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
-        self.out = self.rs_out = self.ps_in = self.tn_in = self.ln_in = self.lv_in = self.en = self.en_in = None
-        if table.empty:
+        self.en = Encoder(engine, batch, table.width) if table.encodings is not None else None
+        self._stages = [s for s in self.per_kind() if s is not None]
+        self._between = []  # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
+        self.out = None
+        if not self._stages:
             return
-        if table.encodings is not None:
-            self.en = Encoder(engine, batch, table.width)
-        before_ps = self.ts if self.ts is not None else self.rs  # the stage before the pitcher, if any
-        before_tn = self.ps if self.ps is not None else before_ps  # the stage before the toner, if any
-        before_ln = self.tn if self.tn is not None else before_tn  # the stage before the normaliser, if any
-        last = self.ln if self.ln is not None else before_ln       # the stage before the leveler, if any
-        width = self.lv.width if self.lv is not None else last.out_max if last is not None else table.width
+        for before, s in zip(self._stages, self._stages[1:]):
+            if before._out_width != s._in_width:
+                raise ValueError(f"{s._field}: the {s._name}'s line is not the line of the stage before it")
+            self._between.append(torch.zeros(batch, s._in_width, device=engine.device))
         if self.en is not None:
-            if width != self.en.width:
-                raise ValueError("encoding: the encoder's line is not the line of the stage before it")
-            self.out = [torch.zeros(batch, self.en.pitch, dtype=torch.uint8).pin_memory() for _ in range(nb)]
-            if self.lv is not None or last is not None:
-                self.en_in = torch.zeros(batch, width, device=engine.device)
+            shape, dtype = (batch, self.en.pitch), torch.uint8
         else:
-            self.out = [torch.zeros(batch, width, dtype=torch.int16 if pcm_i16 else torch.float32).pin_memory()
-                        for _ in range(nb)]
-        # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
-        if self.lv is not None and last is not None:
-            if last.out_max != width:
-                raise ValueError("level: the leveler's line is not the line of the stage before it")
-            self.lv_in = torch.zeros(batch, width, device=engine.device)
-        if self.ln is not None and before_ln is not None:
-            if before_ln.out_max != self.ln.width:
-                raise ValueError("loudness: the normaliser's line is not the line of the stage before it")
-            self.ln_in = torch.zeros(batch, self.ln.width, device=engine.device)
-        if self.tn is not None and before_tn is not None:
-            if before_tn.out_max != self.tn.width:
-                raise ValueError("tone: the toner's line is not the line of the stage before it")
-            self.tn_in = torch.zeros(batch, self.tn.width, device=engine.device)
-        if self.ps is not None and before_ps is not None:
-            if before_ps.out_max != self.ps.width:
-                raise ValueError("pitch: the pitcher's line is not the line of the stage before it")
-            self.ps_in = torch.zeros(batch, self.ps.width, device=engine.device)
-        if self.ts is not None and self.rs is not None:
-            self.rs_out = torch.zeros(batch, self.rs.out_max, device=engine.device)
+            shape, dtype = (batch, self._stages[-1]._out_width), torch.int16 if pcm_i16 else torch.float32
+        self.out = [torch.zeros(*shape, dtype=dtype).pin_memory() for _ in range(nb)]
+
+    def per_kind(self):
+        """(rs, ts, ps, tn, ln, lv, en) in chain order, None where the table has no such stage"""
+        return self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en
 
     def stages(self):
-        return [s for s in (self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en) if s is not None]
+        return list(self._stages)
 
     def attach(self, mimi_state, p: int):
         """the decodes / graph captures of `mimi_state` issued after this call end with the chain's launches and write
         ring slot `p` (the frame's PCM must then be a device tensor)"""
-        final = self.out[p] if self.en is None else self.en_in  # what the last stage before the encoder, if any, writes
-        end = final if self.lv is None else self.lv_in         # what the stage before the leveler writes
-        if self.ln is not None:
-            end = self.ln_in                                  # what the stage before the normaliser writes
-        tn_out = end                                          # what the toner, if any, writes
-        if self.tn is not None:
-            end = self.tn_in                                  # what the stage before the toner writes
-        mid = end if self.ps is None else self.ps_in          # what the stage before the pitcher writes
-        if self.rs is not None:
-            mimi_state.set_resampler(self.rs, mid if self.ts is None else self.rs_out)
-        if self.ts is not None:
-            mimi_state.set_stretcher(self.ts, mid, self.rs_out)
-        if self.ps is not None:
-            mimi_state.set_pitcher(self.ps, end, self.ps_in)
-        if self.tn is not None:
-            mimi_state.set_tone(self.tn, tn_out, self.tn_in)
-        if self.ln is not None:
-            mimi_state.set_loudnorm(self.ln, self.lv_in, self.ln_in)
-        if self.lv is not None:
-            mimi_state.set_leveler(self.lv, final, self.lv_in)
-        if self.en is not None:
-            mimi_state.set_encoder(self.en, self.out[p], self.en_in)
+        bufs = [None, *self._between, self.out[p]]  # stage i reads bufs[i] (None: the frame's PCM) and writes bufs[i + 1]
+        for i, s in enumerate(self._stages):
+            mimi_state._set_stage(type(s), s, bufs[i + 1], bufs[i])
 
     def detach(self, mimi_state):
-        if self.en is not None:
-            mimi_state.set_encoder(None)
-        if self.lv is not None:
-            mimi_state.set_leveler(None)
-        if self.ln is not None:
-            mimi_state.set_loudnorm(None)
-        if self.tn is not None:
-            mimi_state.set_tone(None)
-        if self.ps is not None:
-            mimi_state.set_pitcher(None)
-        if self.ts is not None:
-            mimi_state.set_stretcher(None)
-        if self.rs is not None:
-            mimi_state.set_resampler(None)
+        for s in reversed(self._stages):
+            mimi_state._set_stage(type(s), None)
 
     def reset(self, stream=None):
         """every row's state back to zero in every stage (new utterances); the rows keep their routes"""
-        for s in self.stages():
+        for s in self._stages:
             s.reset(stream)
 
     def set_row(self, row: int, route: Route, stream=None):
         """a new sequence joins `row` on `route` with a zero state in every stage, not draining; a stage the route does not
         use runs its identity plan or bypass.  Stream-ordered"""
-        if self.rs is not None:
-            self.rs.set_row(row, route.rate_index, stream)
-        if self.ts is not None:
-            self.ts.set_row(row, route.stretch_plan, stream)
-        if self.ps is not None:
-            self.ps.set_row(row, route.pitch_plan, stream)
-        if self.tn is not None:
-            self.tn.set_row(row, route.tone_plan, stream)
-        if self.ln is not None:
-            self.ln.set_row(row, *(route.loud or (None, None)), stream)
-        if self.lv is not None:
-            self.lv.set_row(row, *(route.level or (None, None, None)), stream)
-        if self.en is not None:
-            self.en.set_row(row, route.n_out, route.encoding, stream)
+        for s in self._stages:
+            s.set_row(row, *s._route_args(route), stream)
 
     def drain_row(self, row: int, route: Route, stream=None):
         """from now on (stream-ordered) the row's incoming frames count as zeros at the stage `route.drain_stage` names"""
-        stage = {"stretch": self.ts, "pitch": self.ps, "loud": self.ln, "level": self.lv, None: None}[route.drain_stage]
-        if stage is not None:
-            stage.set_row_drain(row, True, stream)
+        for s in self._stages:
+            if s._drain_name is not None and s._drain_name == route.drain_stage:
+                s.set_row_drain(row, True, stream)
 
     def close(self):
-        for s in reversed(self.stages()):
+        for s in reversed(self._stages):
             s.close()
