@@ -21,43 +21,20 @@ A request may also bring a `seed`: its slot's row then draws from the request's 
 row seed per text chunk from `engine.chunk_seed`), so the noise of the request does not depend on the slot it was dealt,
 on the step at which it joined or on the other requests, and equals what `TTSModel.generate_audio(..., seed=)` draws.
 
-A batcher built with `sample_rates` lets a request choose its output `sample_rate`: the codec graphs end with the
-streaming polyphase resampler (`resample.py`, `engine.Resampler`), each slot's row runs at its request's rate, and a
-request's chunks hold `frame_samples * rate / native` samples each.  `Request.sample_rate` tells the consumer the rate.
+A batcher built with options of `output_chain.ChainSpec` lets a request choose its way through the output chain with the
+fields of `ChainTable.route`: the codec graphs end with the chain's stages (`output_chain.py` gives their order and what each
+does), each slot's row runs on its request's `Route`, and `Request.sample_rate` / `Request.encoding` tell the consumer what
+the chunks are: `route.n_out` samples a frame, fp32, or with the encoder typed views of the row's bytes (int16, float32, or
+uint8 for G.711).  Samples stay the unit of every count.
 
-A batcher built with `speeds` lets a request choose its speaking rate `speed` among them: the codec graphs end with the
-streaming WSOLA time-stretch (`stretch.py`, `engine.Stretcher`), behind the resampler if there is one.  A stretched
-request of F frames delivers exactly F * n_out samples: the scheduler drops the row's pre-roll, sets the row to drain
-before the first codec frame past the request's last one is queued, and holds the slot for the plan's drain frames.  To
-know that frame in time it reads the EOS flags of a stretched row no later than `frames_after_eos` steps behind.
-
-A batcher built with `level=True` lets a request choose its output level (`gain_db`, `peak_dbfs`): the codec graphs end with
-the leveler (`level.py`, `engine.Leveler`), the last stage of the chain.  Its look-ahead makes a levelled row lag like a
-stretched one, so both are "rows whose output chain lags": the row's pre-roll is the stretcher's (0 without one) plus the
-look-ahead, it is held for ceil(pre-roll / n) drain frames and delivers the samples [pre-roll, pre-roll + F * n).  A
-levelled row without a stretch drains through the leveler's flag, one with a stretch through the stretcher's.
-
-A batcher built with `pitches` lets a request choose its `pitch` among them: the codec graphs run the pitch shifter
-(`pitch.py`, `engine.Pitcher`) behind the stretcher and before the leveler.  The pitcher keeps a frame's length and lags by
-its plan's L samples, so a pitched row is one more row whose output chain lags: its pre-roll joins the sum, it drains through
-the pitcher's flag unless it is stretched as well, and a pitched request of F frames delivers exactly F * n_out samples.
-
-A batcher built with `loudness=True` lets a request choose a loudness target (`loudness_lufs`): the codec graphs run the
-BS.1770 normaliser (`loudness.py`, `engine.Normalizer`) behind the pitcher and the leveler behind it as its peak limiter.
-The normaliser lags by 400 ms, so such a row is one more row whose output chain lags: the delay joins the pre-roll, and the
-row drains through the normaliser's flag unless a stage before it lags as well.  The measurement restarts with every text
-chunk, so the chunks of a long request are normalised one by one.
-
-A batcher built with `encodings` lets a request choose its output `encoding` among them and `pcm_s16le`: the codec graphs
-end with the encoder (`encoding.py`, `engine.Encoder`), which writes each row's bytes in its own encoding into the pinned
-ring.  A request's chunks are then typed views of its bytes: int16 for `pcm_s16le`, float32 for `pcm_f32le`, uint8 for
-`mulaw` and `alaw` (ITU-T G.711).  The encoder does not lag: nothing of the above changes, and samples stay the unit of
-every count.
-
-A batcher built with `tones` lets a request choose its `tone` among them: the codec graphs run the equaliser (`tone.py`,
-`engine.Toner`) behind the pitcher and before the normaliser, and the leveler behind it as peak limiter.  The toner has a
-state but no lag, so it adds nothing to a row's pre-roll and has no drain flag: the zeros of a draining row ring out through
-it.  A toned row lags by the limiter's look-ahead like a levelled one.
+The stretcher, the pitcher, the normaliser and the leveler lag, so their rows are "rows whose output chain lags" (the drain
+rule of `output_chain.py`): a request of F frames delivers exactly F * n_out samples, the scheduler drops the row's pre-roll,
+the sum of its stages' pre-rolls, sets the row to drain at its first lagging stage before the first codec frame past the
+request's last one is queued, and holds the slot for ceil(pre-roll / n_out) drain frames.  To know that frame in time it reads
+the EOS flags of such a row no later than `frames_after_eos` steps behind.  The resampler, the toner and the encoder do not
+lag: the toner has a state but no drain flag, the zeros of a draining row ring out through it, and a toned row lags by the
+limiter behind it like a levelled one.  The normaliser's measurement restarts with every text chunk, so the chunks of a long
+request are normalised one by one.
 """
 
 from __future__ import annotations
@@ -173,38 +150,13 @@ class _Job:
 
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
-                 max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None, tones=None):
+                 max_lsd_decode_steps: int | None = None, spec=None, **chain):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
-        `sample_rates` (a list of rates `resample.plan` admits, e.g. [8000, 16000, 48000]) lets each request choose its
-        output `sample_rate` among them and the native rate (`submit`).  None: every request gets the codec's rate, with
-        the same graphs and buffers as before.
-
-        `speeds` (a list of speaking rates `stretch.plan` admits at one of the batcher's rates at least, e.g. [0.8, 1.25,
-        1.5]) lets each request choose its `speed` among them and 1.0 (`submit`).  None: nobody is stretched, with the
-        same graphs and buffers as before.
-
-        `level` = True lets each request choose its output level with `gain_db` and `peak_dbfs` (`submit`): gain plus a
-        look-ahead peak limiter as the last output stage.  False: nobody is levelled, with the same graphs and buffers as
-        before.
-
-        `pitches` (a list of frequency ratios `pitch.plan` admits on one of the batcher's lines at least, numbers or "P/Q"
-        strings, e.g. ["17/16", "5/4", "4/5"]) lets each request choose its `pitch` among them and 1.0 (`submit`).  None:
-        nobody is pitched, with the same graphs and buffers as before.
-
-        `loudness` = True lets each request choose a loudness target with `loudness_lufs` (`submit`): the gain that brings
-        the running BS.1770 loudness of its own audio to the target, followed by the peak limiter.  False: nobody is
-        normalised, with the same graphs and buffers as before.
-
-        `encodings` (a list of names of `encoding.py`, e.g. ["mulaw", "alaw", "pcm_f32le"]) lets each request choose its
-        `encoding` among them and "pcm_s16le" (`submit`); its chunks are int16, float32 or uint8 tensors accordingly.  It
-        needs `pcm_format` left at its default (ValueError).  None: every request gets `pcm_format`, with the same graphs
-        and buffers as before.
-
-        `tones` (a list of tones of `tone.py`: preset names such as "telephone" or band lists such as
-        "hp:120;peak:3000:4") lets each request choose its `tone` among them (`submit`); a toned request runs the peak
-        limiter behind the equaliser.  None: nobody is toned, with the same graphs and buffers as before.
+        The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`,
+        `tones`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
+        `ChainTable.route` (`submit`).  `encodings` needs `pcm_format` left at its default (ValueError).  Without any of them
+        every request gets the codec's samples in `pcm_format`, with the same graphs and buffers as before.
 
         `max_lsd_decode_steps` = K lets each request choose its own `lsd_decode_steps` in [1, K] (`submit`).  A step then
         takes as long as its slowest group of 16 rows.  None: every request runs the model's `lsd_decode_steps`, with the
@@ -218,18 +170,19 @@ class ContinuousBatcher:
         import numpy as np
 
         from .engine import StepPipeline
-        from .output_chain import ChainTable
+        from .output_chain import ChainSpec
 
+        spec = ChainSpec.of(spec, **chain)
         if pcm_format not in ("f32", "i16"):
             raise ValueError("pcm_format must be 'f32' or 'i16'")
-        if encodings is not None and pcm_format != "f32":
+        if spec.encodings is not None and pcm_format != "f32":
             raise ValueError("pcm_format and encodings exclude each other: with encodings a request asks for 'pcm_s16le' "
                              "or 'pcm_f32le' itself")
         self.model, self.eng, self.B = model, model.engine, slots
         self.capacity, self.pcm_format = capacity, pcm_format
         eng = self.eng
         # what the chain's rules refuse is refused before anything is allocated
-        ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings, tones)
+        spec.table(eng.sample_rate, eng.frame_samples)
         self.st = eng.new_lm_state(slots, capacity)
         self.ms = eng.new_mimi_state(slots)
         # also at temp 0 (std 0: no draws): the seed is the one rows overridden to a temperature > 0 draw with
@@ -243,8 +196,7 @@ class ContinuousBatcher:
             self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
         self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                 mode="events", pcm_i16=(pcm_format == "i16"), sample_rates=sample_rates, speeds=speeds,
-                                 level=level, pitches=pitches, loudness=loudness, encodings=encodings, tones=tones)
+                                 mode="events", pcm_i16=(pcm_format == "i16"), spec=spec)
         self.chain = self.pipe.chain
         self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
         # the output chain has a stage that may lag
@@ -285,10 +237,8 @@ class ContinuousBatcher:
     # ---- submission (any thread) ---------------------------------------------------------------
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
-               eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
-               sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
-               peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
-               encoding: str | None = None, tone: str | None = None, seed: int | None = None) -> Request:
+               eos_threshold: float | None = None, lsd_decode_steps: int | None = None, seed: int | None = None,
+               **request) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
         chunks that run one after the other, each from the voice state.
 
@@ -297,27 +247,12 @@ class ContinuousBatcher:
         [1, max_lsd_decode_steps]) is the number of Euler steps of this request's flow head; a batcher built without
         `max_lsd_decode_steps` accepts only the model's value.  `seed` (an int in [0, 2**63)) makes the request's noise
         reproducible: the same seed, text and settings draw the same noise in any slot, under any traffic, and in
-        `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.  `sample_rate`: the rate of
-        this request's audio, one of the batcher's `sample_rates` or the native rate (None: native); anything else raises
-        ValueError, as does any rate but the native one on a batcher built without `sample_rates`.  `speed`: the
-        request's speaking rate, one of the batcher's `speeds` or 1.0 (None: 1.0); a speed that is not configured, or
-        that the plan rule refuses at the request's rate, raises ValueError, as does any speed but 1.0 on a batcher built
-        without `speeds`.  A stretched request needs frames_after_eos >= 1.  `gain_db` (in [-40, 24]) and `peak_dbfs` (in
-        [-20, 0], default -1, only together with `gain_db`): the request's output level, gain plus a peak limiter that
-        keeps |sample| <= 10^(peak_dbfs / 20) (`level.py`); None: the samples of before.  Either raises ValueError on a
-        batcher built without `level`; a levelled request needs frames_after_eos >= 1 too.  `pitch`: the request's
-        frequency ratio, a number or a "P/Q" string, one of the batcher's `pitches` or 1.0 (None: 1.0); a pitch that is not
-        configured, or that the plan rule refuses on the request's line, raises ValueError, as does any pitch but 1.0 on a
-        batcher built without `pitches`.  A pitched request needs frames_after_eos >= 1 as well.  `loudness_lufs` (in
-        [-40, -10]): the request's loudness target (`loudness.py`), limited to `peak_dbfs` (default -1) behind it; it
-        excludes `gain_db`, raises ValueError on a batcher built without `loudness` and needs frames_after_eos >= 1.  Each
-        text chunk of a long request is measured on its own, so the gain can differ between the chunks.  `encoding`: the
-        name of the request's output encoding, one of the batcher's `encodings` or "pcm_s16le" (None: "pcm_s16le"); a name
-        that is not configured raises ValueError, as does any on a batcher built without `encodings`.  `tone`: the
-        request's tone, one of the batcher's `tones` (compared in the canonical form of `tone.normalise`; None, "" or "flat":
-        none); a tone that is not configured, or that the request's rate refuses, raises ValueError, as does any on a
-        batcher built without `tones`.  It combines freely with `gain_db` and `loudness_lufs`; alone it runs the limiter at
-        gain 0 dB under `peak_dbfs` (default -1), so a toned request needs frames_after_eos >= 1."""
+        `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.
+
+        `**request`: the request's way through the output chain, the fields of `ChainTable.route` (`sample_rate`, `speed`,
+        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`), checked against the batcher's table: ValueError
+        for what it refuses, TypeError for another name.  A request whose row lags (a speed, a pitch, a loudness target, a
+        tone or a gain) needs frames_after_eos >= 1."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -344,7 +279,7 @@ class ContinuousBatcher:
             if samp is None and m.noise_clamp is not None:
                 # a seeded request draws as `generate_audio(seed=)` does: with the model's noise clamp
                 samp = (float(m.temp), float(m.noise_clamp), float(m.eos_threshold))
-        route = self.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding, tone)
+        route = self.chain.table.route(**request)
         lsd = None
         if lsd_decode_steps is not None:
             n = lsd_decode_steps
@@ -370,21 +305,12 @@ class ContinuousBatcher:
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
             fae = frames_after_eos if frames_after_eos is not None else (
                 m.model_recommended_frames_after_eos if m.model_recommended_frames_after_eos is not None else guess + 2)
-            if route.stretched and fae < 1:
-                raise ValueError("a request with a speed needs frames_after_eos >= 1: the row is set to drain before the "
-                                 "frame that follows its last one is queued")
-            if route.pitched and fae < 1:
-                raise ValueError("a request with a pitch needs frames_after_eos >= 1: the row is set to drain before the "
-                                 "frame that follows its last one is queued")
-            if route.loud is not None and fae < 1:
-                raise ValueError("a request with a loudness target needs frames_after_eos >= 1: the row is set to drain "
-                                 "before the frame that follows its last one is queued")
-            if route.toned and fae < 1:
-                raise ValueError("a request with a tone needs frames_after_eos >= 1: the row is set to drain before the "
-                                 "frame that follows its last one is queued")
-            if route.level is not None and fae < 1:
-                raise ValueError("a request with a gain needs frames_after_eos >= 1: the row is set to drain before the "
-                                 "frame that follows its last one is queued")
+            for lags, what in ((route.stretched, "a speed"), (route.pitched, "a pitch"),
+                               (route.loud is not None, "a loudness target"), (route.toned, "a tone"),
+                               (route.level is not None, "a gain")):
+                if lags and fae < 1:
+                    raise ValueError(f"a request with {what} needs frames_after_eos >= 1: the row is set to drain before the "
+                                     "frame that follows its last one is queued")
             ids = m.tokenizer.encode(chunk)
             gen = estimate_max_gen_len(len(ids), m.config.mimi.frame_rate)
             need = t_voice + len(ids) + gen + self.pipe.nb + 2  # a row runs up to nb steps past its end before it is parked

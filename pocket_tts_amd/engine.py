@@ -1330,42 +1330,30 @@ class StepPipeline:
       critical path (on this stack such waits around graph launches cost ~80 us per step, and the branches
       of a forked graph do not run concurrently).
 
-    `sample_rates` (a list of output rates, `resample.py`), `speeds` (a list of speaking rates, `stretch.py`; each must be
-    admissible at one of the rates at least), `pitches` (a list of frequency ratios, `pitch.py`; each admissible on one of
-    the lines at least), `loudness` (True: per-row loudness target, `loudness.py`; it brings the leveler with it) and
-    `level` (True: per-row gain and limiter, `level.py`) configure the output chain behind the codec (`output_chain.py`
-    gives its order; not in "fork" mode): the codec graphs end with its stages' launches.
-    `chain` holds the plan table (`chain.table`) and the stage objects, also here as `rs`, `ts`, `ps`, `ln` and `lv`.
-    `pcm[p]` are then DEVICE tensors and the samples reach the host through `out[p]`, the chain's pinned ring, int16 with
-    `pcm_i16`, else float32: `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  A row gets
-    its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec stream); rows start on the
-    native rate, speed 1.0, pitch 1.0 and bypass.  With None / None / None / False / False nothing changes: same buffers,
-    same graph nodes.
-
-    `encodings` (a list of names of `encoding.py`, e.g. ["mulaw", "alaw", "pcm_f32le"]; not in "fork" mode, not with
-    `pcm_i16`) ends the chain with the encoder, also here as `en`: `out[p]` are then pinned uint8 tensors and
-    `out_of(frame)[b, : route.n_out * route.bytes_per_sample]` are row b's bytes in its route's encoding; rows start on
-    "pcm_s16le".  None: no such stage, same buffers, same graph nodes.
-
-    `tones` (a list of tones of `tone.py`, preset names or band lists, e.g. ["telephone", "hp:120;peak:3000:4"]; not in
-    "fork" mode; it brings the leveler with it) puts the toner, also here as `tn`, between the pitcher and the normaliser;
-    rows start on bypass.  None: no such stage, same buffers, same graph nodes.
+    The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`, `tones`;
+    as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
+    "fork" mode): the codec graphs end with its stages' launches.  `chain` holds the plan table (`chain.table`) and the
+    stage objects, also here as `rs`, `ts`, `ps`, `tn`, `ln`, `lv` and `en`.  `pcm[p]` are then DEVICE tensors and the
+    samples reach the host through `out[p]`, the chain's pinned ring, int16 with `pcm_i16`, else float32:
+    `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  With the encoder (not with `pcm_i16`)
+    `out[p]` are pinned uint8 tensors and `out_of(frame)[b, : route.n_out * route.bytes_per_sample]` are row b's bytes in
+    its route's encoding.  A row gets its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec
+    stream); rows start on the native rate, speed 1.0, pitch 1.0, bypass and "pcm_s16le".  Without any option nothing
+    changes: same buffers, same graph nodes.
     """
 
     NB_EVENTS = int(os.environ.get("PTTS_PIPE_NB", "4"))  # output-buffer ring depth of the "events" mode
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None, tones=None):
-        from .output_chain import ChainTable, OutputChain
+                 lm_stream: torch.cuda.Stream | None = None, spec=None, **chain):
+        from .output_chain import ChainSpec, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
         # the plan table first: what the rules refuse is refused before anything is allocated
-        table = ChainTable(eng.sample_rate, eng.frame_samples, sample_rates, speeds, level, pitches, loudness, encodings,
-                           tones)
+        table = ChainSpec.of(spec, **chain).table(eng.sample_rate, eng.frame_samples)
         if not table.empty and self.mode == "fork":
             raise ValueError("sample_rates / speeds / pitches / tones / loudness / level / encodings: not available in the "
                              "'fork' mode")

@@ -35,6 +35,10 @@ DEFAULT_TEXT = ("Hello world. I am Kyutai's Pocket TTS. I'm fast enough to run o
                 "I hope you'll like me.")
 
 
+# the flags behind each request field of `ChainTable.for_request`, as `generate` names them when a rule refuses one
+FLAGS = dict(sample_rate="--sample-rate", speed="--speed", pitch="--pitch / --pitch-semitones", tone="--tone",
+             loudness_lufs="--loudness-lufs / --peak-dbfs", gain_db="--gain-db / --peak-dbfs", encoding="--encoding")
+
 _STREAM_FRAMES = 1_000_000_000  # streaming: the length is not known up front, the header announces this many samples
 
 
@@ -274,8 +278,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def serve_app(args) -> int:
+    import dataclasses
+
     import uvicorn
 
+    from .output_chain import ChainSpec
     from .server import create_app
     from .tts_model import TTSModel
 
@@ -283,11 +290,11 @@ def serve_app(args) -> int:
                                 lsd_decode_steps=args.lsd_decode_steps, noise_clamp=args.noise_clamp,
                                 eos_threshold=args.eos_threshold, quantize=args.quantize, codec_bf16=args.codec_bf16,
                                 device=args.device)
-    # the model's noise clamp reaches every request as a per-request setting (server.py)
+    # the model's noise clamp reaches every request as a per-request setting (server.py); the flags of the output chain
+    # carry the names of its options
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
-                     sample_rates=args.sample_rates, speeds=args.speeds, level=args.level, pitches=args.pitches,
-                     loudness=args.loudness, encodings=args.encodings, tones=args.tones)
+                     **{f.name: getattr(args, f.name) for f in dataclasses.fields(ChainSpec)})
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -322,56 +329,29 @@ def cli_app(argv=None) -> int:
                                 eos_threshold=args.eos_threshold, quantize=args.quantize, codec_bf16=args.codec_bf16,
                                 device=args.device)
     # generate_audio_stream is a generator and would refuse its arguments only once write_wav_stream has opened the file:
-    # check the rate, then the speed at that rate, then the level behind both, so the message names the flag at fault
+    # walk the request's chain here, so the message names the flag at fault (the first in chain order)
     from .output_chain import ChainTable
 
-    request = {}
-    checks = [("--sample-rate", ("sample_rate",)), ("--speed", ("speed",)), ("--tone", ())]
-    if args.loudness_lufs is None:  # with a loudness target the ceiling belongs to it: both are checked below
-        checks.append(("--gain-db / --peak-dbfs", ("gain_db", "peak_dbfs")))
-    tone = None
-    for flag, names in checks:
-        request.update({k: getattr(args, k) for k in names})
-        try:
-            if flag == "--tone":  # behind the rate and the speed, before the level: a tone alone brings the limiter
-                tone = ChainTable.single_tone(int(model.sample_rate), model.engine.frame_samples, args.sample_rate, args.speed,
-                                              args.tone)
-                continue
-            asked = dict(request)
-            if tone is not None and asked.get("gain_db") is None and "peak_dbfs" in asked:
-                asked["gain_db"] = 0.0
-            ChainTable.single(int(model.sample_rate), model.engine.frame_samples, **asked)
-        except ValueError as e:
-            logger.error("%s: %s", flag, e)
-            return 1
-    request["tone"] = tone
-    if args.loudness_lufs is not None:
-        try:
-            ChainTable.single_loudness(int(model.sample_rate), model.engine.frame_samples, args.sample_rate, args.speed,
-                                       args.gain_db, args.peak_dbfs, args.loudness_lufs)
-        except ValueError as e:
-            logger.error("--loudness-lufs / --peak-dbfs: %s", e)
-            return 1
-        request.update(gain_db=None, loudness_lufs=args.loudness_lufs, peak_dbfs=args.peak_dbfs)
-    # the pitch behind the rate and the speed; semitones become the nearest ratio the rule admits on that line
+    native, fs = int(model.sample_rate), model.engine.frame_samples
     try:
         if args.pitch is not None and args.pitch_semitones is not None:
             raise ValueError("give one of --pitch and --pitch-semitones")
-        native, fs = int(model.sample_rate), model.engine.frame_samples
         pitch = args.pitch
-        if args.pitch_semitones is not None:
+        if args.pitch_semitones is not None:  # semitones become the nearest ratio the rule admits behind the rate and the speed
             from .pitch import nearest
 
-            pitch, cents = nearest(args.pitch_semitones, *ChainTable.single_line(native, fs, args.sample_rate, args.speed))
+            pitch, cents = nearest(args.pitch_semitones, *ChainTable.line_of(native, fs, args.sample_rate, args.speed)[2])
             logger.info("--pitch-semitones %g: pitch %s, %+.1f cents from the request", args.pitch_semitones, pitch, cents)
-        request["pitch"] = ChainTable.single_pitch(native, fs, args.sample_rate, args.speed, pitch)
-    except ValueError as e:
-        logger.error("--pitch / --pitch-semitones: %s", e)
+        _, request = ChainTable.for_request(native, fs, args.sample_rate, args.speed, args.gain_db, args.peak_dbfs, pitch,
+                                            args.loudness_lufs, args.encoding, args.tone)
+    except ValueError as e:  # a `RequestError` names its field; the others are those of the two pitch flags above
+        logger.error("%s: %s", FLAGS[getattr(e, "field", "pitch")], e)
         return 1
     voice = args.voice if args.voice is not None else "alba"
     state = model.get_state_for_audio_prompt(voice)
+    request["gain_db"] = args.gain_db  # as it came: the limiter's 0 dB behind a tone alone is for the model to fill in
     chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                         seed=args.seed, encoding=args.encoding, **request)
+                                         seed=args.seed, **request)
     write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate, args.encoding)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)

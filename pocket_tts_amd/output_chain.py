@@ -1,5 +1,6 @@
-"""The output chain as one object: what a pipeline's stages are (`ChainTable`), what a request's row does in them (`Route`),
-and the stage objects and buffers on the device (`OutputChain`).
+"""The output chain as one object: the options a pipeline is built with (`ChainSpec`), what its stages are (`ChainTable`),
+what a request's row does in them (`Route`, and `ChainTable.for_request` for a request that gets a pipeline of its own), and
+the stage objects and buffers on the device (`OutputChain`).
 
 The order, which is also the launch order behind the codec's last kernel:
 
@@ -89,22 +90,101 @@ class Route:
         return lo, max(hi, lo)
 
 
+class RequestError(ValueError):
+    """A rule's refusal of one request field: `field` names it, the message is the rule's own."""
+
+    def __init__(self, field: str, message: str):
+        super().__init__(message)
+        self.field = field
+
+
+def _ask(field: str, rule, *args):
+    """rule(*args); its ValueError as the `RequestError` of `field`"""
+    try:
+        return rule(*args)
+    except ValueError as e:
+        raise RequestError(field, str(e)) from None
+
+
+@dataclass(frozen=True)
+class ChainSpec:
+    """What a pipeline's output chain is built with: the seven options that `StepPipeline`, `ContinuousBatcher` and
+    `server.create_app` take as keywords, one per stage but the leveler's, which three bring.  The default of each is "that
+    stage does not exist": with all seven nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
+    spec is hashable.
+
+    `sample_rates`: the output rates a row may choose besides the native one, each a rate `resample.plan` admits, e.g. [8000,
+    16000, 48000]; the streaming polyphase resampler (`resample.py`) is the first stage and a frame then holds
+    frame_samples * rate / native samples.
+    `speeds`: the speaking rates a row may choose besides 1.0, e.g. [0.8, 1.25, 1.5]; each must be one `stretch.plan` admits
+    at one of the rates at least.  The streaming WSOLA time-stretch (`stretch.py`) at constant pitch; a frame then holds
+    n_out = samples / speed samples.
+    `level`: True lets a row choose its output level, a gain and a look-ahead peak limiter (`level.py`).
+    `pitches`: the frequency ratios a row may choose besides 1, numbers or "P/Q" strings, e.g. ["17/16", "5/4", "4/5"]; each
+    must be one `pitch.plan` admits on one of the lines at least.  The pitch shifter (`pitch.py`) keeps a line's length.
+    `loudness`: True lets a row choose a loudness target, a streaming BS.1770 normaliser (`loudness.py`); it brings the
+    leveler with it as its peak limiter.
+    `encodings`: the sample encodings a row may choose besides "pcm_s16le", names of `encoding.py`, e.g. ["mulaw", "alaw",
+    "pcm_f32le"]; the encoder ends the chain and writes bytes.  Not together with a 16-bit ring (`pcm_i16`, `pcm_format`).
+    `tones`: the tones a row may choose, presets or band lists of `tone.py`, e.g. ["telephone", "hp:120;peak:3000:4"]; the
+    parametric equaliser, which brings the leveler with it as its peak limiter.
+
+    What the rules refuse raises their ValueError when the table is built (`table`), before anything is allocated."""
+
+    sample_rates: tuple | None = None
+    speeds: tuple | None = None
+    level: bool = False
+    pitches: tuple | None = None
+    loudness: bool = False
+    encodings: tuple | None = None
+    tones: tuple | None = None
+
+    TAGS = dict(sample_rates="rate", speeds="speed", level="level", pitches="pitch", loudness="loud", encodings="enc",
+                tones="tone")  # what `tags` calls each option
+
+    def __post_init__(self):
+        for name in ("sample_rates", "speeds", "pitches", "encodings", "tones"):
+            v = getattr(self, name)
+            if v is not None and not isinstance(v, (tuple, str)):  # a string is no list: the rules say so
+                object.__setattr__(self, name, tuple(v))
+
+    @classmethod
+    def of(cls, spec=None, **chain):
+        """`spec`, or the spec of the seven options given as keywords; TypeError for another keyword, or for both"""
+        if spec is None:
+            return cls(**chain)
+        if chain:
+            raise TypeError(f"a ChainSpec and the options {sorted(chain)} exclude each other")
+        return spec
+
+    def table(self, native_rate: int, frame_samples: int) -> "ChainTable":
+        return ChainTable(native_rate, frame_samples, **vars(self))
+
+    def tags(self) -> tuple:
+        """The stages of the spec as the words that tell cached contexts apart: each option that is set as its tag in
+        `TAGS`, a list other than the encoder's followed by its values.  ("rate", 8000, "level", "enc") is a resampler to 8
+        kHz, the leveler and the encoder: a context serves every gain, ceiling and target and all encodings, but one list
+        of rates, speeds, pitches and tones."""
+        out = []
+        for name, tag in self.TAGS.items():
+            v = getattr(self, name)
+            if v is not None and v is not False:
+                out += [tag, *(v if isinstance(v, tuple) and name != "encodings" else ())]
+        return tuple(out)
+
+
 class ChainTable:
-    """The plans of a pipeline's stages, built once: `rate_plans` (`resample.plans`: the native rate first), and with
-    `speeds` the stretcher's `stretch_plans` / `stretch_index[rate index][speed index]` (`stretch.table`), with `level`
-    the leveler's `level_plans` / `level_index[(rate, n)]` (`level.table` over every (rate, samples per frame) the rates x
-    speeds can produce), with `pitches` the pitcher's `pitch_plans` / `pitch_index[(rate, n)][pitch index]` (`pitch.table`
-    over the same lines; the pitcher keeps a line's length, so the leveler's lines are unchanged), with `loudness` the
-    normaliser's `loud_plans` / `loud_index[(rate, n)]` (`loudness.table` over the lines the leveler gets; the leveler's
-    plans are then built whatever `level` says, because the normaliser is always followed by the limiter).  The graphs bake plan indices into device tables, so the order is part of the contract.  A rate,
-    speed, pitch or line the rules refuse raises their ValueError here, before anything is allocated.  `sample_rates` /
-    `speeds` / `pitches` None and `level` / `loudness` False: that stage does not exist (`has_rates` tells a resampler of the native rate alone from none).
-    With `encodings` (a list of names of `encoding.py`) the chain ends with the encoder and `encodings` is the configured
-    list, `pcm_s16le` first; None: that stage does not exist.  A list makes the table non-empty even when the encoder is the
-    only stage.  `width` is the widest line that leaves the last stage before the encoder.  With `tones` (a list of tones of
-    `tone.py`) the toner's `tone_plans` / `tone_index[(rate, n)][tone index]` (`tone.table` over the lines the pitcher leaves,
-    None where the rate refuses a tone) and `tones`, the configured list in canonical form; the leveler's plans are then built
-    whatever `level` says, because a toned row is always followed by the limiter.  None: that stage does not exist."""
+    """The plans of a pipeline's stages, built once from the options of a `ChainSpec`: `rate_plans` (`resample.plans`: the
+    native rate first; `has_rates` tells a resampler of the native rate alone from none), and with `speeds` the stretcher's
+    `stretch_plans` / `stretch_index[rate index][speed index]` (`stretch.table`), with `pitches` the pitcher's `pitch_plans`
+    / `pitch_index[(rate, n)][pitch index]` (`pitch.table` over every (rate, samples per frame) the rates x speeds can
+    produce), with `tones` the toner's `tone_plans` / `tone_index[(rate, n)][tone index]` (`tone.table` over the same lines,
+    None where the rate refuses a tone) and `tones`, the configured list in canonical form, with `loudness` the normaliser's
+    `loud_plans` / `loud_index[(rate, n)]` (`loudness.table`), and with `level`, `loudness` or `tones` the leveler's
+    `level_plans` / `level_index[(rate, n)]` (`level.table`).  With `encodings` the chain ends with the encoder and
+    `encodings` is the configured list, `pcm_s16le` first; a list makes the table non-empty even when the encoder is the only
+    stage.  `width` is the widest line that leaves the last stage before the encoder.  The graphs bake plan indices into
+    device tables, so the order is part of the contract."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
                  pitches=None, loudness: bool = False, encodings=None, tones=None):
@@ -158,16 +238,32 @@ class ChainTable:
 
     def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None,
               encoding=None, tone=None) -> Route:
-        """The `Route` of a request; None is the native rate, speed 1.0, no gain, pitch 1.0, no loudness target and, on a
-        table with the encoder, `pcm_s16le` (an encoding that is not configured, or any on a table without the encoder,
-        raises ValueError).  A request
-        with a target gets the normaliser's plan and a leveler entry at gain 0 dB under its `peak_dbfs` (default -1).
-        ValueError for a rate, speed or pitch that is not configured, a speed or pitch the plan rule refuses on the
-        request's line (the message lists those it admits), a level `level.check` or a target `loudness.check` refuses,
-        `loudness_lufs` together with `gain_db`, and for any of them on a table without that stage.  `tone` (None, "" or
-        "flat": bypass) must be one of the configured tones (compared in canonical form) that the row's rate admits; a toned
-        request gets a leveler entry at gain 0 dB under its `peak_dbfs` (default -1) unless it has a gain or a loudness
-        target, with both of which it combines freely."""
+        """The `Route` of a request.  Its eight fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
+        `generate_audio_stream` take as keywords and hand on as they came; None is always "as without the stage":
+
+        `sample_rate`: the rate of the request's audio, the native one (None) or one of the configured; a frame then yields
+        frame_samples * rate / native samples.
+        `speed`: its speaking rate at constant pitch, 1.0 (None) or one of the configured that the plan rule admits at its
+        rate; a frame then yields n_out = samples / speed samples, and F frames exactly F * n_out.
+        `pitch`: a frequency ratio P / Q with P, Q <= 20 in [0.5, 2], a number or a "P/Q" string such as "17/16" for a
+        semitone up, 1 (None) or one of the configured that the plan rule admits on the line behind its rate and speed.
+        Every frequency moves by it, the formants too.
+        `tone`: a preset such as "telephone", "warm", "bright", "presence", "small_speaker" or "deess", or a band list such as
+        "hp:120;peak:3000:4" (at most eight biquad sections, none above 0.45 x the rate), compared in the canonical form of
+        `tone.normalise`; None, "" or "flat": bypass.  A toned request runs the limiter behind it, at gain 0 dB under its
+        `peak_dbfs` unless it has a gain or a target, with both of which it combines freely.
+        `loudness_lufs`: a loudness target in [-40, -10], e.g. -16 or -23.  The gain follows the running gated BS.1770
+        loudness of the text chunk so far, clamped to +-20 dB, 400 ms late, with the limiter at `peak_dbfs` behind it; it
+        excludes `gain_db`.  Each text chunk is measured on its own, so the gain can differ between the chunks of a long text.
+        `gain_db` (in [-40, 24]) and `peak_dbfs` (in [-20, 0], default -1, only together with a gain, a target or a tone):
+        the samples are amplified and peak-limited to 10^(peak_dbfs / 20).  0 is not None: it limits at the ceiling.
+        `encoding`: "pcm_s16le" (None on a table with the encoder), "pcm_f32le", "mulaw" or "alaw", among the configured:
+        the chunks are int16, float32 or uint8 (ITU-T G.711) tensors, one element per sample.
+
+        A stage that lags (all but the resampler, the toner and the encoder) delays the output, not the count: the samples
+        delivered in all stay those of the same request without it (the drain rule of the module's docstring).  ValueError for
+        a value that is not configured, that a rule refuses on the request's line (the message lists what it admits there),
+        and for any but None on a table without that stage (the message names the option to build it with)."""
         r = 0
         if self.has_rates:
             r = rate_index(self.rates, sample_rate)
@@ -241,73 +337,57 @@ class ChainTable:
                      else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps, tplan, tplan is not None)
 
     @staticmethod
-    def single(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None):
-        """One request that gets a chain of its own: (sample_rate, speed, gain_db, peak_dbfs) with the native rate, speed
-        1.0 and no gain as None, the speed as the float of its fraction and peak_dbfs defaulted - what a `ChainTable` of
-        exactly these stages is built from and routes.  ValueError with the message of the rule that refuses."""
-        native = int(native_rate)
-        n = int(frame_samples)
+    def line_of(native_rate: int, frame_samples: int, sample_rate=None, speed=None):
+        """(sample_rate, speed, (rate, n)) of one request that gets a chain of its own: its rate and speed in canonical form
+        (the native rate and speed 1.0 as None, the speed as the float of its fraction) and the line that leaves its
+        stretcher, which the pitcher keeps.  `RequestError` with the message of the rule that refuses."""
+        rate, n = int(native_rate), int(frame_samples)
         if sample_rate is not None:
-            p = resample.plan(sample_rate, native, frame_samples)
-            sample_rate, n = (None if p.rate == native else p.rate), p.out_n
+            p = _ask("sample_rate", resample.plan, sample_rate, rate, frame_samples)
+            sample_rate, rate, n = (None if p.rate == rate else p.rate), p.rate, p.out_n
         if speed is not None:
-            speed = float(stretch.fraction(speed))
+            speed = float(_ask("speed", stretch.fraction, speed))
             if speed == 1.0:
                 speed = None
             else:
-                n = stretch.plan(speed, sample_rate or native, n).n_out
-        gain_db, peak_dbfs = level_rule.check(gain_db, peak_dbfs)
-        if gain_db is not None:
-            level_rule.plan(sample_rate or native, n)
-        return sample_rate, speed, gain_db, peak_dbfs
+                n = _ask("speed", stretch.plan, speed, rate, n).n_out
+        return sample_rate, speed, (rate, n)
 
     @staticmethod
-    def single_line(native_rate: int, frame_samples: int, sample_rate=None, speed=None):
-        """(rate, n): the line that leaves the stretcher of one request's own chain - what its pitcher reads"""
-        sample_rate, speed, _, _ = ChainTable.single(native_rate, frame_samples, sample_rate, speed)
-        rate, n = sample_rate or int(native_rate), int(frame_samples)
-        if sample_rate is not None:
-            n = resample.plan(sample_rate, int(native_rate), frame_samples).out_n
-        if speed is not None:
-            n = stretch.plan(speed, rate, n).n_out
-        return rate, n
-
-    @staticmethod
-    def single_pitch(native_rate: int, frame_samples: int, sample_rate=None, speed=None, pitch=None):
-        """The pitch of one request that gets a chain of its own, behind that request's rate and speed: the float of its
-        fraction, None for 1.0.  ValueError with the message of the rule that refuses."""
-        if pitch is None:
-            return None
-        f = pitch_rule.fraction(pitch)
-        if f == 1:
-            return None
-        return pitch_rule.plan(f, *ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)).pitch
-
-    @staticmethod
-    def single_tone(native_rate: int, frame_samples: int, sample_rate=None, speed=None, tone=None):
-        """The tone of one request that gets a chain of its own, behind that request's rate and speed (the pitcher keeps the
-        line): its canonical string, None for the bypass.  ValueError with the message of the rule that refuses."""
-        canon = tone_rule.normalise(tone)
-        if canon is None:
-            return None
-        rate, n = ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)
-        tone_rule.plan(rate, n, canon)
-        level_rule.plan(rate, n)
-        return canon
-
-    @staticmethod
-    def single_loudness(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
-                        loudness_lufs=None):
-        """The loudness target of one request that gets a chain of its own, behind that request's rate and speed (the
-        pitcher keeps the line): (loudness_lufs as a float, peak_dbfs defaulted), (None, None) without a target.
-        ValueError with the message of the rule that refuses."""
-        target = loud_rule.check_with(loudness_lufs, gain_db)
-        if target is None:
-            return None, None
-        rate, n = ChainTable.single_line(native_rate, frame_samples, sample_rate, speed)
-        loud_rule.plan(rate, n)
-        level_rule.plan(rate, n)
-        return target, level_rule.check(0.0, peak_dbfs)[1]
+    def for_request(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
+                    pitch=None, loudness_lufs=None, encoding=None, tone=None):
+        """One request that gets a chain of its own (the fields of `route`): (spec, request), the `ChainSpec` of exactly the
+        stages it uses and the request in canonical form, the dict that `spec.table(native_rate, frame_samples).route`
+        takes - the native rate, speed 1.0 and pitch 1.0 as None, speed and pitch as the floats of their fractions, the tone
+        as its canonical string, `peak_dbfs` defaulted, and `gain_db` 0.0 behind a tone without a gain or a loudness target
+        of its own.  One walk in chain order over the request's own line, stage by stage through the plan rules themselves,
+        so a refusal is the rule's: a `RequestError` with its message, whose `field` names the request field at fault."""
+        sample_rate, speed, line = ChainTable.line_of(native_rate, frame_samples, sample_rate, speed)
+        if pitch is not None:
+            f = _ask("pitch", pitch_rule.fraction, pitch)
+            pitch = None if f == 1 else _ask("pitch", pitch_rule.plan, f, *line).pitch
+        tone = _ask("tone", tone_rule.normalise, tone)
+        if tone is not None:
+            _ask("tone", tone_rule.plan, *line, tone)
+            _ask("tone", level_rule.plan, *line)
+        loudness_lufs = _ask("loudness_lufs", loud_rule.check_with, loudness_lufs, gain_db)
+        if loudness_lufs is not None:  # the limiter behind the normaliser: no gain of its own, the request's ceiling
+            _ask("loudness_lufs", loud_rule.plan, *line)
+            _ask("loudness_lufs", level_rule.plan, *line)
+            peak_dbfs = _ask("loudness_lufs", level_rule.check, 0.0, peak_dbfs)[1]
+        else:
+            if tone is not None and gain_db is None:
+                gain_db = 0.0  # the limiter behind the tone: no gain of its own, the request's ceiling
+            gain_db, peak_dbfs = _ask("gain_db", level_rule.check, gain_db, peak_dbfs)
+            if gain_db is not None:
+                _ask("gain_db", level_rule.plan, *line)
+        if encoding is not None:
+            _ask("encoding", encoding_rule.check, encoding)
+        one = lambda v: None if v is None else (v,)  # noqa: E731
+        spec = ChainSpec(one(sample_rate), one(speed), gain_db is not None, one(pitch), loudness_lufs is not None,
+                         None if encoding is None else encoding_rule.NAMES, one(tone))
+        return spec, dict(sample_rate=sample_rate, speed=speed, gain_db=gain_db, peak_dbfs=peak_dbfs, pitch=pitch,
+                          loudness_lufs=loudness_lufs, encoding=encoding, tone=tone)
 
 
 class OutputChain:

@@ -240,7 +240,7 @@ def parse_pitch(fields: dict, rate, speed, table) -> float | None:
 
 def parse_tone(fields: dict, rate, speed, table):
     """the optional `tone` field: the canonical string of one of the configured tones admissible at the request's rate, None
-    where absent, empty or "flat".  `table`: the server's `ChainTable` with its tones, None on a server started without.
+    where absent, empty or "flat".  `table`: the server's `ChainTable`, without tones (or None) on a server started without.
     FormError with the configured list for a tone that is not configured, with the admissible list for one the request's
     rate refuses, for what the grammar refuses, and for any tone on a server started without tones"""
     from . import tone as tone_rule
@@ -252,7 +252,7 @@ def parse_tone(fields: dict, rate, speed, table):
         canon = tone_rule.normalise(raw)
         if canon is None:
             return None
-        if table is None:
+        if table is None or table.tones is None:
             raise FormError("tone is not available (this server was started without tones)")
         table.route(rate, speed, tone=canon)
     except ValueError as e:
@@ -353,62 +353,31 @@ def parse_container(fields: dict) -> str:
 
 
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
-               batcher_factory=None, max_lsd_decode_steps: int | None = None, sample_rates=None, speeds=None,
-               level: bool = False, pitches=None, loudness: bool = False, encodings=None, tones=None):
+               batcher_factory=None, max_lsd_decode_steps: int | None = None, **chain):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
     noise clamp.  A request's `lsd_decode_steps` may be 1 .. `max_lsd_decode_steps` (default: the model's
-    `lsd_decode_steps`; a larger maximum gives the batcher per-row LSD schedules).  `sample_rates`: the output rates a
-    request may choose with `sample_rate` besides the model's own (None: only that one, and the batcher's graphs are those
-    of before); the WAV header and the trailing silence follow the request's rate.  `speeds`: the speaking rates a request
-    may choose with `speed` besides 1.0 (None: only 1.0, and the batcher's graphs are those of before); each must be
-    admissible at one of the server's rates at least (ValueError here, not at the first request), and a request whose
-    speed its rate does not admit gets a 400.  `level`: requests may set their output level with `gain_db` and `peak_dbfs`
-    (False: a request that sends either gets a 400, and the batcher's graphs are those of before).  `pitches`: the frequency ratios a
-    request may choose with `pitch` besides 1 (None: only 1, and the batcher's graphs are those of before); each must be
-    admissible on one of the server's lines at least (ValueError here), and a request whose pitch its line does not admit gets
-    a 400 with the admissible list.  `loudness`: requests may set a loudness target with `loudness_lufs` (and its ceiling
-    with `peak_dbfs`; False: a request that sends it gets a 400, and the batcher's graphs are those of before).
-    `encodings`: the sample encodings a request may choose with `encoding` besides `pcm_s16le` (`encoding.py`; None: only
-    that one, a request that names another gets a 400 with the configured list, and the batcher's graphs are those of
-    before).  The batcher is then built with `encodings` and its default `pcm_format`: every request's samples leave the GPU
-    in its own encoding.  `tones`: the tones a request may choose with `tone` (`tone.py`; None: a request that sends one
-    gets a 400, and the batcher's graphs are those of before); each must be admissible on one of the server's lines at least
-    (ValueError here), a request with another tone gets a 400 with the configured list, and one whose rate does not admit
-    its tone a 400 with the admissible list.  `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
+    `lsd_decode_steps`; a larger maximum gives the batcher per-row LSD schedules).  `**chain`: the options of
+    `output_chain.ChainSpec`, what a request may choose with the form fields of the same names as `ChainTable.route`'s;
+    without one of them a request that sends its field gets a 400, and the batcher's graphs are those of before.  What the
+    rules refuse in a list is a ValueError here, not at the first request; a request with a value that is not configured, or
+    that its rate or line does not admit, gets a 400 with the list of what is.  The WAV header and the trailing silence
+    follow the request's rate and encoding.  With `encodings` the batcher is built with its default `pcm_format`: every
+    request's samples leave the GPU in its own encoding.  `batcher_factory(model, slots, capacity)` replaces the batcher
+    (tests)."""
     from .main import wav_stream_bytes
 
-    from .output_chain import ChainTable
+    from .output_chain import ChainSpec
 
-    speeds_of = None
-    if sample_rates is not None:
-        sample_rates = [int(r) for r in sample_rates]
-        ChainTable(model.sample_rate, 1920, sample_rates)  # ValueError at start-up, not at the first request (1920: the
-        # codec's frame, as `resample.plan` assumes it by default)
-    if speeds is not None:
-        speeds = [float(v) for v in speeds]
-        speeds_of = speed_table(speeds, model.sample_rate, sample_rates, model.engine.frame_samples)
-
-    if pitches is not None:
-        from .pitch import normalise_pitches
-
-        pitches = normalise_pitches(pitches)[1:]
-    # what a request's pitch is checked against: the lines its rate and speed select (ValueError at start-up)
-    frame_samples = getattr(getattr(model, "engine", None), "frame_samples", 1920)
-    pitch_table = ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, pitches=pitches)
-    if loudness:  # the normaliser's and the limiter's rules on every line (ValueError at start-up)
-        ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, loudness=True)
-
-    tone_table = None
-    if tones is not None:  # the toner's and the limiter's rules on every line (ValueError at start-up)
-        tone_table = ChainTable(model.sample_rate, frame_samples, sample_rates, speeds, tones=tones)
-        tones = tone_table.tones
-
-    if encodings is not None:
-        from .encoding import normalise_encodings
-
-        encodings = normalise_encodings(encodings)  # ValueError at start-up
+    for name, number in (("sample_rates", int), ("speeds", float)):
+        if chain.get(name) is not None:
+            chain[name] = [number(v) for v in chain[name]]
+    spec = ChainSpec(**chain)
+    # the one table every request is checked against: the rules of every stage on every line (ValueError at start-up)
+    table = spec.table(model.sample_rate, getattr(getattr(model, "engine", None), "frame_samples", 1920))
+    sample_rates, level, loudness, encodings = spec.sample_rates, spec.level, spec.loudness, table.encodings
+    speeds_of = None if spec.speeds is None else table.speeds_of()
 
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
@@ -418,14 +387,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
         # no per-row capacity when the maximum is the model's own count: the batcher's graphs are those of before
         reserve = max_lsd if max_lsd != own_lsd else None
 
-        def batcher_factory(model, slots, capacity):
-            if encodings is not None:  # the encoder writes every request's format, pcm_s16le included
-                return ContinuousBatcher(model, slots=slots, capacity=capacity, max_lsd_decode_steps=reserve,
-                                         sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
-                                         loudness=loudness, encodings=encodings, tones=tones)
-            return ContinuousBatcher(model, slots=slots, capacity=capacity, pcm_format="i16", max_lsd_decode_steps=reserve,
-                                     sample_rates=sample_rates, speeds=speeds, level=level, pitches=pitches,
-                                     loudness=loudness, tones=tones)
+        def batcher_factory(model, slots, capacity):  # the encoder writes every request's format, pcm_s16le included
+            return ContinuousBatcher(model, slots=slots, capacity=capacity, max_lsd_decode_steps=reserve, spec=spec,
+                                     pcm_format="f32" if encodings is not None else "i16")
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -520,10 +484,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             speed = parse_speed(fields, rate or int(model.sample_rate), speeds_of)
             if speed is not None and speed != 1.0:
                 settings["speed"] = speed
-            pitch = parse_pitch(fields, settings.get("sample_rate"), settings.get("speed"), pitch_table)
+            pitch = parse_pitch(fields, settings.get("sample_rate"), settings.get("speed"), table)
             if pitch is not None and pitch != 1.0:
                 settings["pitch"] = pitch
-            tone = parse_tone(fields, settings.get("sample_rate"), settings.get("speed"), tone_table)
+            tone = parse_tone(fields, settings.get("sample_rate"), settings.get("speed"), table)
             if tone is not None:
                 settings["tone"] = tone
             target, ceiling = parse_loudness(fields, loudness)

@@ -191,64 +191,23 @@ class TTSModel:
     # ---- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                       frames_after_eos: int | None = None, copy_state: bool = True, sample_rate: int | None = None,
-                       speed: float | None = None, gain_db: float | None = None, peak_dbfs: float | None = None,
-                       pitch=None, loudness_lufs: float | None = None, encoding: str | None = None,
-                       tone: str | None = None, seed: int | None = None) -> torch.Tensor:
-        """`seed` (an int in [0, 2**63)), `sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
-        `encoding` and `tone` (not in the reference): see `generate_audio_stream`."""
-        chunks = list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos, copy_state,
-                                                 seed=seed, sample_rate=sample_rate, speed=speed, gain_db=gain_db,
-                                                 peak_dbfs=peak_dbfs, pitch=pitch, loudness_lufs=loudness_lufs,
-                                                 encoding=encoding, tone=tone))
-        return torch.cat(chunks, dim=0)
+                       frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None,
+                       **request) -> torch.Tensor:
+        """`seed` and `**request` (not in the reference): see `generate_audio_stream`."""
+        return torch.cat(list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos,
+                                                         copy_state, seed=seed, **request)), dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                              frames_after_eos: int | None = None, copy_state: bool = True,
-                              sample_rate: int | None = None, speed: float | None = None, gain_db: float | None = None,
-                              peak_dbfs: float | None = None, pitch=None, loudness_lufs: float | None = None,
-                              encoding: str | None = None, tone: str | None = None, seed: int | None = None):
+                              frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None,
+                              **request):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
 
-        `sample_rate` (not in the reference; a rate `resample.plan` admits, e.g. 8000, 16000, 44100, 48000): the audio is
-        resampled on the GPU behind the codec (streaming polyphase FIR, `resample.py`) and each chunk holds
-        `frame_samples * sample_rate / native` samples.  None or the native rate: the codec's own samples, as before.
-
-        `speed` (not in the reference; a speaking rate `stretch.plan` admits at the output rate, e.g. 0.8, 1.25, 1.5): the
-        audio is time-stretched on the GPU at constant pitch (streaming WSOLA, `stretch.py`) behind the codec, or behind
-        the resampler.  A text chunk of F frames yields exactly F * n_out samples, in chunks of up to n_out = frame samples
-        / speed.  None or 1.0: as before.
-
-        `gain_db` (not in the reference; in [-40, 24]) and `peak_dbfs` (in [-20, 0], default -1, only together with
-        `gain_db`): the audio is amplified by `gain_db` and peak-limited to 10^(peak_dbfs / 20) on the GPU (a streaming
-        look-ahead limiter, `level.py`), as the last output stage.  The samples yielded in all stay those of the same call
-        without a gain; the output lags by the look-ahead LA, so a text chunk's first tensor is LA samples short and a last
-        one of LA samples follows.  None: as before; 0 is not None, it limits at the ceiling.
-
-        `pitch` (not in the reference; a frequency ratio P / Q with P, Q <= 20 in [0.5, 2] that `pitch.plan` admits behind the
-        request's rate and speed, a number or a "P/Q" string, e.g. "17/16" for a semitone up): every frequency is moved by
-        that ratio on the GPU (streaming WSOLA plus a polyphase FIR, `pitch.py`) behind the stretcher and before the
-        leveler; the formants move with it.  The samples yielded in all stay those of the same call without a pitch; the
-        output lags like a levelled one.  None or 1: as before.
-
-        `loudness_lufs` (not in the reference; in [-40, -10], e.g. -16 or -23): the audio is brought to that loudness on
-        the GPU by a streaming ITU-R BS.1770-4 normaliser (`loudness.py`) behind the pitcher, followed by the peak limiter
-        at `peak_dbfs` (default -1); it excludes `gain_db`.  The gain follows the running gated loudness of the text chunk
-        so far, clamped to +-20 dB, and the output lags by 400 ms like a levelled one.  The measurement restarts with every
-        text chunk of a long text, so the gain can differ between the chunks.  None: as before.
-
-        `encoding` (not in the reference; "pcm_s16le", "pcm_f32le", "mulaw" or "alaw", `encoding.py`): the samples are
-        encoded on the GPU by the last stage of the output chain and the chunks are int16, float32 or uint8 tensors
-        accordingly, one element per sample: the 16-bit samples a WAV file holds, the float samples as they are, or ITU-T
-        G.711 bytes of those 16-bit samples.  None: fp32 chunks, as before.
-
-        `tone` (not in the reference; a preset such as "telephone", "warm", "bright", "presence", "small_speaker" or
-        "deess", or a band list such as "hp:120;peak:3000:4", `tone.py`): the audio runs through that cascade of at most
-        eight biquad sections on the GPU, in float64, behind the pitcher and before the normaliser, followed by the peak
-        limiter at `peak_dbfs` (default -1); it combines freely with `gain_db` and `loudness_lufs`.  The equaliser itself
-        does not lag; the output lags like a levelled one.  A band above 0.45 x the output rate is refused.  None, "" or
-        "flat": as before.
+        `**request` (not in the reference): the request's way through the output chain on the GPU, the fields of
+        `output_chain.ChainTable.route` (`sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
+        `encoding`, `tone`), each checked by its rule on the request's own line (`ChainTable.for_request`): ValueError with
+        the rule's message, TypeError for another name.  The chunks then hold what a frame yields at the end of the chain,
+        as fp32, or typed as the `encoding`.  None of them: the codec's own samples, as before.
 
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
@@ -257,21 +216,10 @@ class TTSModel:
         from torch's global CPU generator, as in the reference."""
         if seed is not None:
             seed = check_seed(seed)
-        from . import encoding as encoding_rule
         from .output_chain import ChainTable
 
-        if encoding is not None:
-            encoding_rule.check(encoding)
         # the native rate, speed 1.0 and no gain become None: the call of before.  ValueError names the rule
-        native, fs = int(self.config.mimi.sample_rate), self.engine.frame_samples
-        tone = ChainTable.single_tone(native, fs, sample_rate, speed, tone)
-        if tone is not None and gain_db is None and loudness_lufs is None:
-            gain_db = 0.0  # the limiter behind the tone: no gain of its own, the request's ceiling
-        loud, loud_peak = ChainTable.single_loudness(native, fs, sample_rate, speed, gain_db, peak_dbfs, loudness_lufs)
-        request = ChainTable.single(native, fs, sample_rate, speed, gain_db, None if loud is not None else peak_dbfs)
-        if loud is not None:  # the limiter behind the normaliser: no gain of its own, the request's ceiling
-            request = (*request[:3], loud_peak)
-        pitch = ChainTable.single_pitch(int(self.config.mimi.sample_rate), self.engine.frame_samples, sample_rate, speed, pitch)
+        spec, request = ChainTable.for_request(int(self.config.mimi.sample_rate), self.engine.frame_samples, **request)
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
@@ -281,8 +229,7 @@ class TTSModel:
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
             yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
-                                                              None if seed is None else chunk_seed(seed, i), *request,
-                                                              pitch=pitch, loudness_lufs=loud, encoding=encoding, tone=tone)
+                                                              None if seed is None else chunk_seed(seed, i), spec, request)
 
     @torch.no_grad()
     def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
@@ -443,10 +390,10 @@ class TTSModel:
     RATE_CONTEXTS = 2  # cached contexts of `generate_audio(sample_rate=...)`: a caller that cycles through rates holds no more
 
     def _drop_rate_contexts(self, keep: int = 0):
-        """cached contexts with a resampler (state, resampler and graphs of one `sample_rate`) beyond the `keep` most
-        recently used are released; a context in use is not in the cache"""
-        keys = [k for k in self._ctx_cache if "rate" in k[4:] or "speed" in k[4:] or "level" in k[4:] or "pitch" in k[4:]
-                or "loud" in k[4:] or "enc" in k[4:] or "tone" in k[4:]]
+        """cached contexts with an output chain (state, stages and graphs of one `ChainSpec`: the keys that go on past their
+        four leading entries with its tags) beyond the `keep` most recently used are released; a context in use is not in
+        the cache"""
+        keys = [k for k in self._ctx_cache if len(k) > 4 and k[0] != "batch"]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
             c["pipe"].close()
@@ -521,9 +468,8 @@ class TTSModel:
             torch.nn.init.trunc_normal_(out, mean=0.0, std=std, a=-self.noise_clamp, b=self.noise_clamp)
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
-                                          row_seed: int | None = None, sample_rate: int | None = None,
-                                          speed: float | None = None, gain_db=None, peak_dbfs=None, pitch=None,
-                                          loudness_lufs=None, encoding=None, tone=None):
+                                          row_seed: int | None, spec, request: dict):
+        """one text chunk on a pipeline of `spec`, which routes `request`: the two that `ChainTable.for_request` returns"""
         from . import encoding as encoding_rule
 
         eng = self.engine
@@ -539,20 +485,8 @@ class TTSModel:
         # states, scratch and captured graphs are reused across chunks and calls (capacity rounded up)
         cap = -(-(t_voice + Tt + max_gen_len) // 256) * 256
         key = (cap, self.lsd_decode_steps, float(self.eos_threshold), "seeded" if seeded else use_noise)
-        if sample_rate is not None:  # a context of its own: its codec graphs end with the resampler
-            key = (*key, "rate", sample_rate)
-        if speed is not None:  # likewise: its codec graphs end with the time-stretch
-            key = (*key, "speed", speed)
-        if gain_db is not None:  # likewise: its codec graphs end with the leveler (one context serves every gain and ceiling)
-            key = (*key, "level")
-        if pitch is not None:  # likewise: its codec graphs run the pitch shifter
-            key = (*key, "pitch", pitch)
-        if loudness_lufs is not None:  # likewise: the normaliser and the leveler (one context serves every target)
-            key = (*key, "loud")
-        if encoding is not None:  # likewise: its codec graphs end with the encoder (one context serves all four encodings)
-            key = (*key, "enc")
-        if tone is not None:  # likewise: its codec graphs run the toner, whose plans are those of this tone alone
-            key = (*key, "tone", tone)
+        tags = spec.tags()  # a context of its own per chain: its codec graphs end with the chain's stages
+        key = (*key, *tags)
         ctx = self._ctx_cache.pop(key, None)
         if ctx is None:
             from .engine import StepPipeline
@@ -560,15 +494,10 @@ class TTSModel:
             st = eng.new_lm_state(1, cap)
             ms = eng.new_mimi_state(1)
             noise_dev = torch.zeros(1, eng.ldim, device=self.device) if use_noise and not seeded else None
-            if not (sample_rate is None and speed is None and gain_db is None and pitch is None
-                    and loudness_lufs is None and encoding is None and tone is None):  # with an output chain
+            if tags:  # with an output chain
                 self._drop_rate_contexts(keep=self.RATE_CONTEXTS - 1)
             pipe = StepPipeline(eng, st, ms, noise_dev, self.lsd_decode_steps, float(self.eos_threshold), mode="hostsync",
-                                sample_rates=None if sample_rate is None else [sample_rate],
-                                speeds=None if speed is None else [speed], level=gain_db is not None,
-                                pitches=None if pitch is None else [pitch], loudness=loudness_lufs is not None,
-                                encodings=None if encoding is None else list(encoding_rule.NAMES),
-                                tones=None if tone is None else [tone])
+                                spec=spec)
             ctx = dict(st=st, ms=ms, noise_dev=noise_dev, pipe=pipe, noise_host=torch.zeros(1, eng.ldim).pin_memory())
         st, ms, noise_dev, pipe = ctx["st"], ctx["ms"], ctx["noise_dev"], ctx["pipe"]
         noise_host = ctx["noise_host"]
@@ -579,7 +508,7 @@ class TTSModel:
         st.copy_from(voice_st)
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         # the codec's carries and the row's rate, plan, gain and ceiling with a zero state in every stage, on the codec stream
-        route = pipe.chain.table.route(sample_rate, speed, gain_db, peak_dbfs, pitch, loudness_lufs, encoding, tone)
+        route = pipe.chain.table.route(**request)
         pipe.restart([route])
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
@@ -671,7 +600,7 @@ class TTSModel:
             self._ctx_cache[key] = ctx
         if st.error():  # a cooperative kernel gave up waiting for a peer (GPU oversubscribed beyond the library's contract)
             raise RuntimeError("libptts: a cooperative FlowLM kernel timed out; the audio of this chunk is invalid")
-        dur_ms = int(total * 1000 / (sample_rate or self.config.mimi.sample_rate))
+        dur_ms = int(total * 1000 / route.rate)
         gen_ms = max(1, int((time.monotonic() - t_start) * 1000))
         logger.info("Generated: %d ms of audio in %d ms so %.2fx faster than real-time", dur_ms, gen_ms, dur_ms / gen_ms)
 

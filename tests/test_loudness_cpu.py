@@ -191,13 +191,17 @@ def test_route_with_every_mix_of_stages():
 def test_single_loudness():
     from pocket_tts_amd.output_chain import ChainTable
 
-    assert ChainTable.single_loudness(24000, 1920) == (None, None)
-    assert ChainTable.single_loudness(24000, 1920, None, None, None, None, -16) == (-16.0, -1.0)
-    assert ChainTable.single_loudness(24000, 1920, 8000, 1.25, None, -6, -23.0) == (-23.0, -6.0)
+    def one(rate=None, speed=None, gain_db=None, peak_dbfs=None, loudness_lufs=None):
+        got = ChainTable.for_request(24000, 1920, rate, speed, gain_db, peak_dbfs, loudness_lufs=loudness_lufs)[1]
+        return got["loudness_lufs"], got["peak_dbfs"]
+
+    assert one() == (None, None)
+    assert one(None, None, None, None, -16) == (-16.0, -1.0)
+    assert one(8000, 1.25, None, -6, -23.0) == (-23.0, -6.0)
     with pytest.raises(ValueError, match="exclude each other"):
-        ChainTable.single_loudness(24000, 1920, None, None, 3.0, None, -16)
+        one(None, None, 3.0, None, -16)
     with pytest.raises(ValueError, match=r"\[-20, 0\]"):
-        ChainTable.single_loudness(24000, 1920, None, None, None, 1.0, -16)
+        one(None, None, None, 1.0, -16)
 
 
 # ---- the index functions and the chunked recurrence under a host sanitizer --------------------------------------------------

@@ -1,4 +1,4 @@
-"""The planning half of the output chain (pocket_tts_amd/output_chain.py) against the three rule modules composed directly:
+"""The planning half of the output chain (pocket_tts_amd/output_chain.py) against the rule modules composed directly:
 no GPU, no library."""
 
 import itertools
@@ -6,8 +6,9 @@ import itertools
 import numpy as np
 import pytest
 
-from pocket_tts_amd import level, resample, stretch
-from pocket_tts_amd.output_chain import ChainTable, Route
+from pocket_tts_amd import encoding, level, loudness, pitch, resample, stretch
+from pocket_tts_amd import tone as tone_rule
+from pocket_tts_amd.output_chain import ChainSpec, ChainTable, RequestError, Route
 
 NATIVE, FS = 24000, 1920
 RATES = [None, 8000, 16000, 22050, 44100, 48000]
@@ -162,16 +163,102 @@ def test_messages_on_tables_without_the_stage():
 
 
 def test_single_request_validation_names_the_rule():
-    one = lambda *a: ChainTable.single(NATIVE, FS, *a)  # noqa: E731
+    def one(*a):
+        got = ChainTable.for_request(NATIVE, FS, *a)[1]
+        return got["sample_rate"], got["speed"], got["gain_db"], got["peak_dbfs"]
+
     assert one() == (None, None, None, None) and one(24000, 1.0) == (None, None, None, None)
     assert one(16000, 0.8, 6) == (16000, 0.8, 6.0, -1.0) and one(None, 1.25, -3, -6) == (None, 1.25, -3.0, -6.0)
+    assert one(48000, None, 0) == (48000, None, 0.0, -1.0)  # 0 is not None: it limits at the ceiling
     for args, msg in [((10560,), "whole number of output samples"), ((None, 0.9), "no multiple of 9"),
                       ((8000, 1.5), "no multiple of 3"), ((None, 0.77), "fraction"), ((None, None, 30), r"\[-40, 24\]"),
                       ((None, None, None, -3), "together with gain_db")]:
         with pytest.raises(ValueError, match=msg):
             one(*args)
-    # what it admits is what a table of exactly these stages routes
-    for rate, speed, gain in [(16000, 0.8, 6), (None, 1.25, None), (48000, None, 0), (None, None, None)]:
-        r, s, g, p = one(rate, speed, gain)
-        t = ChainTable(NATIVE, FS, None if r is None else [r], None if s is None else [s], g is not None)
-        assert t.route(r, s, g, p).n_out == _compose(rate, speed, gain)[1].n_out
+    with pytest.raises(TypeError):
+        ChainTable.for_request(NATIVE, FS, volume=3)
+
+
+def test_a_single_request_is_what_a_table_of_exactly_its_stages_routes():
+    """every point of the grid: `for_request` refuses it, or the table of its spec routes its canonical form to what the
+    rules composed directly give"""
+    levels = [{}, dict(gain_db=6), dict(gain_db=6, peak_dbfs=-3), dict(loudness_lufs=-16)]
+    grid = list(itertools.product([None, 8000, 16000, 48000], [None, 0.8, 1.25], [None, "5/4", "17/16"],
+                                  [None, "telephone", "hp:120"], levels, [None, "mulaw"]))
+    admitted = 0
+    for rate, speed, ratio, tone, lvl, enc in grid:
+        asked = dict(sample_rate=rate, speed=speed, pitch=ratio, tone=tone, encoding=enc, **lvl)
+        try:
+            spec, request = ChainTable.for_request(NATIVE, FS, **asked)
+        except ValueError:
+            continue
+        admitted += 1
+        assert list(request) == ["sample_rate", "speed", "gain_db", "peak_dbfs", "pitch", "loudness_lufs", "encoding", "tone"]
+        assert spec == ChainSpec(sample_rates=rate and (rate,), speeds=speed and (speed,), level="gain_db" in lvl or (
+            tone is not None and not lvl), pitches=ratio and (float(pitch.fraction(ratio)),), loudness="loudness_lufs" in lvl,
+            encodings=enc and encoding.NAMES, tones=tone and (tone_rule.normalise(tone),)), asked
+        r = spec.table(NATIVE, FS).route(**request)
+        rp, sp, _ = _compose(rate, speed, None)
+        pre = sp.preroll
+        if ratio is not None:
+            pre += pitch.plan(pitch.fraction(ratio), rp.rate, sp.n_out).preroll
+        if "loudness_lufs" in lvl:
+            pre += loudness.plan(rp.rate, sp.n_out).D
+        if lvl or tone is not None:
+            pre += level.plan(rp.rate, sp.n_out).LA
+        assert (r.rate, r.n_out, r.preroll) == (rp.rate, sp.n_out, pre), asked
+        assert (r.encoding, r.toned, r.loud is not None, r.level is not None) == (enc, tone is not None, "loudness_lufs" in lvl,
+                                                                                 bool(lvl) or tone is not None), asked
+    assert 2 * admitted >= len(grid)  # it cannot pass by refusing everything
+
+
+@pytest.mark.parametrize("field,asked,msg", [
+    ("sample_rate", dict(sample_rate=10560), "whole number of output samples"),
+    ("speed", dict(sample_rate=8000, speed=1.5), "no multiple of 3 divides 640"),
+    ("pitch", dict(sample_rate=8000, pitch="2/3"), "no multiple of 3"),
+    ("tone", dict(sample_rate=8000, tone="bright"), "not admissible at 8000 Hz"),
+    ("loudness_lufs", dict(loudness_lufs=-16, peak_dbfs=1.0), r"\[-20, 0\]"),
+    ("loudness_lufs", dict(loudness_lufs=-16, gain_db=3.0), "exclude each other"),
+    ("gain_db", dict(peak_dbfs=-3), "together with gain_db"),
+    ("gain_db", dict(tone="telephone", peak_dbfs=1.0), r"\[-20, 0\]"),
+    ("encoding", dict(encoding="mp3"), "not configured")])
+def test_a_refusal_names_the_request_field(field, asked, msg):
+    with pytest.raises(RequestError, match=msg) as e:
+        ChainTable.for_request(NATIVE, FS, **asked)
+    assert e.value.field == field and isinstance(e.value, ValueError)
+
+
+def test_the_first_field_in_chain_order_is_named_and_the_line_is_exposed():
+    with pytest.raises(RequestError) as e:
+        ChainTable.for_request(NATIVE, FS, speed=0.9, pitch="8/9", gain_db=30)
+    assert e.value.field == "speed"
+    assert ChainTable.line_of(NATIVE, FS, 8000, 1.25) == (8000, 1.25, (8000, 512))
+    assert ChainTable.line_of(NATIVE, FS, NATIVE, 1) == (None, None, (NATIVE, FS))
+
+
+@pytest.mark.parametrize("asked,tags", [
+    ({}, ()),
+    (dict(sample_rate=8000), ("rate", 8000)),
+    (dict(speed=1.25), ("speed", 1.25)),
+    (dict(gain_db=6), ("level",)),
+    (dict(gain_db=-3, peak_dbfs=-6), ("level",)),
+    (dict(pitch="5/4"), ("pitch", 1.25)),
+    (dict(loudness_lufs=-16), ("loud",)),
+    (dict(loudness_lufs=-23, peak_dbfs=-3), ("loud",)),
+    (dict(encoding="mulaw"), ("enc",)),
+    (dict(encoding="pcm_f32le"), ("enc",)),
+    (dict(tone="Telephone"), ("level", "tone", "telephone")),
+    (dict(tone="telephone", gain_db=6), ("level", "tone", "telephone")),
+    (dict(tone="telephone", loudness_lufs=-16), ("loud", "tone", "telephone")),
+    (dict(sample_rate=8000, speed=0.8, gain_db=6, pitch="17/16", encoding="alaw", tone="telephone"),
+     ("rate", 8000, "speed", 0.8, "level", "pitch", 1.0625, "enc", "tone", "telephone")),
+    (dict(sample_rate=8000, speed=0.8, pitch="17/16", loudness_lufs=-16, encoding="alaw", tone="telephone"),
+     ("rate", 8000, "speed", 0.8, "pitch", 1.0625, "loud", "enc", "tone", "telephone"))])
+def test_the_tags_of_a_spec_tell_cached_contexts_apart(asked, tags):
+    """what `TTSModel` appends to a context's four leading key entries: one context serves every gain, ceiling, target and
+    encoding; a toned request has "level" with or without a gain of its own, unless the normaliser brings the limiter"""
+    spec, _ = ChainTable.for_request(NATIVE, FS, **asked)
+    assert spec.tags() == tags and hash(spec) == hash(ChainTable.for_request(NATIVE, FS, **asked)[0])
+    assert ChainSpec(sample_rates=[8000, 16000], encodings=["mulaw"], loudness=True).tags() == ("rate", 8000, 16000, "loud", "enc")
+    with pytest.raises(TypeError):
+        ChainSpec(volume=True)

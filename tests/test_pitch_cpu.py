@@ -204,13 +204,15 @@ def test_chain_table_and_routes():
             pos += route.n_out
         assert got == list(range(route.preroll, route.preroll + F * route.n_out))
 
-    assert ChainTable.single(NATIVE, FS, 16000, 1.25, 6, None) == (16000, 1.25, 6.0, -1.0)  # as before
-    assert ChainTable.single_pitch(NATIVE, FS, 16000, 1.25, "5/4") == 1.25
-    assert ChainTable.single_pitch(NATIVE, FS, None, None, 1.0) is None and ChainTable.single_pitch(NATIVE, FS, None, None, None) is None
+    one = lambda *a, **kw: ChainTable.for_request(NATIVE, FS, *a, **kw)[1]  # noqa: E731
+    got = one(16000, 1.25, 6, None)
+    assert (got["sample_rate"], got["speed"], got["gain_db"], got["peak_dbfs"]) == (16000, 1.25, 6.0, -1.0)  # as before
+    assert one(16000, 1.25, pitch="5/4")["pitch"] == 1.25
+    assert one(pitch=1.0)["pitch"] is None and one(pitch=None)["pitch"] is None
     with pytest.raises(ValueError, match="no multiple of 9"):
-        ChainTable.single_pitch(NATIVE, FS, None, None, "8/9")
+        one(pitch="8/9")
     with pytest.raises(ValueError, match="no multiple of 3"):  # 2/3 behind 8 kHz: frames of 640 samples
-        ChainTable.single_pitch(NATIVE, FS, 8000, None, "2/3")
+        one(8000, pitch="2/3")
 
 
 # ---- the index functions under a host sanitizer --------------------------------------------------------------------------

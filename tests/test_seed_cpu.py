@@ -152,5 +152,6 @@ def test_entry_points_take_a_seed():
     for fn, name in ((TTSModel.generate_audio, "seed"), (TTSModel.generate_audio_stream, "seed"),
                      (TTSModel.generate_audio_batch, "seeds"), (ContinuousBatcher.submit, "seed")):
         p = inspect.signature(fn).parameters
-        assert name in p and p[name].default is None and list(p)[-1] == name, fn  # a new trailing keyword
+        named = [k for k, v in p.items() if v.kind is not v.VAR_KEYWORD]  # behind them only `**request`, the chain's fields
+        assert name in p and p[name].default is None and named[-1] == name, fn  # a new trailing keyword
     assert hasattr(LMState, "set_row_seed") and hasattr(LMState, "clear_row_seed")

@@ -296,12 +296,13 @@ def test_route_refusals():
 def test_single_tone():
     from pocket_tts_amd.output_chain import ChainTable
 
-    assert ChainTable.single_tone(24000, 1920, None, None, None) is None
-    assert ChainTable.single_tone(24000, 1920, None, None, "FLAT") is None
-    assert ChainTable.single_tone(24000, 1920, 8000, None, "Telephone") == "telephone"
-    assert ChainTable.single_tone(24000, 1920, None, 1.25, "hp:120") == f"hp:120.0:{math.sqrt(0.5)!r}"
+    one = lambda rate, speed, tone: ChainTable.for_request(24000, 1920, rate, speed, tone=tone)[1]["tone"]  # noqa: E731
+    assert one(None, None, None) is None
+    assert one(None, None, "FLAT") is None
+    assert one(8000, None, "Telephone") == "telephone"
+    assert one(None, 1.25, "hp:120") == f"hp:120.0:{math.sqrt(0.5)!r}"
     with pytest.raises(ValueError, match="not admissible at 8000 Hz"):
-        ChainTable.single_tone(24000, 1920, 8000, None, "bright")
+        one(8000, None, "bright")
 
 
 # ---- the server's field -------------------------------------------------------------------------------------------------------
