@@ -44,6 +44,7 @@ typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences 
 typedef struct ptts_loudnorm ptts_loudnorm;     /* loudness targets of B sequences       */
 typedef struct ptts_tone ptts_tone;             /* tones (equaliser) of B sequences      */
 typedef struct ptts_encoder ptts_encoder;       /* output encodings of B sequences       */
+typedef struct ptts_flac ptts_flac;             /* output compression of B sequences     */
 
 /* Model dimensions: pocket_tts/config/english.yaml:7-61 (schema utils/config.py:15-118). */
 typedef struct ptts_config {
@@ -267,9 +268,9 @@ int ptts_resampler_set_row(ptts_resampler *rs, int32_t row, int32_t rate_index, 
  * ptts_mimi_set_pcm_i16 converts, device or pinned host; then every row's history <- the frame's last 64 samples (a second
  * launch: the blocks of a row read the history concurrently).  out_max = the largest out_n of the rates. */
 int ptts_resample_frame(ptts_resampler *rs, const float *d_pcm_in, void *out, int32_t is_i16, void *stream);
-/* ---- The output chain.  The seven ptts_mimi_set_* below follow one rule, stated here once.  While a stage is set on a
+/* ---- The output chain.  The eight ptts_mimi_set_* below follow one rule, stated here once.  While a stage is set on a
  * state, ptts_mimi_decode and the graph captures append its ptts_*_frame launches behind the codec's last kernel, in the order
- *   resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder
+ *   resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder -> packer
  * whichever of them are set.  d_in == NULL: the stage reads d_pcm (which must then be device memory; NULL = the state's own
  * buffer), and its input width must be frame_samples.  Otherwise it reads the f32 device buffer d_in [B, its input width],
  * which the caller has given the stage before it as its `out`; some stage of an earlier kind must be set on the state at
@@ -453,6 +454,31 @@ int ptts_encode_frame(ptts_encoder *en, const float *d_in, void *out_bytes, void
  * own `out`.  So d_in must be NULL exactly when the state has none of these four, at the time of the call (-1) and when a
  * frame is enqueued (-1). */
 int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float *d_in, void *out_bytes);
+/* ---- Output compression (no reference counterpart): the packer, the eighth stage, behind the encoder.  A packer holds, for B
+ * sequences, each row's mode (0 pass-through, 1 flac), its data and the previous line of a flac row.  It reads the encoder's
+ * bytes, u8[B, 4 width rounded up to 16] in DEVICE memory, and writes ring lines u8[B, pitch], pitch = 16 + (max(4 width, 2 width
+ * + 18) rounded up to 16): the prefix {u32 nbytes, 0, 0, 0}, then nbytes bytes, and nothing behind 16 + nbytes rounded up to 16.
+ * A pass-through row's bytes are the encoder's n * bps.  A flac row's are one FLAC frame of n samples of the row's pcm_s16le
+ * line sequence (bitstream and choice rule: pocket_tts_amd/flac.py, csrc/ptts_flac.h), or none (nbytes 0) for the first
+ * ceil(preroll / n) lines after set_row: line f emits the n samples that begin preroll + (f - lead) n samples into the row's
+ * sequence, as frame first_block + f - lead, cut from the previous line and the current one.  Every row starts as
+ * pass-through (width, 2 bytes a sample). */
+int ptts_flac_create(ptts_engine *e, int32_t batch, int32_t width, ptts_flac **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_packer(state, NULL, ..) on its states */
+void ptts_flac_destroy(ptts_flac *pk);
+/* `row` is from now on pass-through (mode 0: n in [1, width] samples of bps = 1, 2 or 4 bytes; the other arguments are not
+ * read) or flac (mode 1: n in [16, min(width, 4608)], rate in [1, 65535] Hz, preroll >= 0 samples, first_block in [0, 2^30),
+ * bps is not read), with its line counter at 0.  Stream-ordered on `stream`; captured graphs pick it up (the kernel reads
+ * all of it from device memory).  -1 for a value out of range; nothing is enqueued. */
+int ptts_flac_set_row(ptts_flac *pk, int32_t row, int32_t mode, int32_t n, int32_t bps, int32_t rate, int32_t preroll,
+                      int32_t first_block, void *stream);
+/* One frame, one launch: d_in_bytes (DEVICE memory) -> out_bytes, device or pinned host, both aligned to 16 bytes (-1
+ * otherwise); the flac rows' line counters advance. */
+int ptts_flac_frame(ptts_flac *pk, const void *d_in_bytes, void *out_bytes, void *stream);
+/* The output chain's rule (ptts_mimi_set_resampler), with these differences: the packer needs an encoder of its width on the
+ * state, at the time of the call (-1) and when a frame is enqueued (-1); d_in_bytes is the device buffer the caller has given
+ * that encoder as its out_bytes, which is checked when a frame is enqueued (-1). */
+int ptts_mimi_set_packer(ptts_mimi_state *s, ptts_flac *pk, void *d_in_bytes, void *out_bytes);
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);

@@ -161,6 +161,11 @@ PROTOTYPES = {
     "ptts_encoder_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "ptts_encode_frame": (C.c_int, [_P, _P, _P, _P]),
     "ptts_mimi_set_encoder": (C.c_int, [_P, _P, _P, _P]),
+    "ptts_flac_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ptts_flac_destroy": (None, [_P]),
+    "ptts_flac_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "ptts_flac_frame": (C.c_int, [_P, _P, _P, _P]),
+    "ptts_mimi_set_packer": (C.c_int, [_P, _P, _P, _P]),
     "ptts_tune": (C.c_int, [_P, C.c_int32, _P]),
     "ptts_tune_streams": (C.c_int, [_P, C.c_int32, _P, _P]),
     "ptts_streams_overlap": (C.c_int, [_P, _P, _P]),
@@ -198,13 +203,14 @@ def build(force: bool = False, verbose: bool = False) -> Path:
       * ptts_dispatch.hip = the GEMM / attention dispatchers and the tuner, the only unit that instantiates the round-1/2
         kernel templates;
       * ptts_debug.hip = the C ABI's test hooks;
-      * the seven stages of the output chain, in its order (`output_chain.py`), each with its own part of the C ABI:
+      * the eight stages of the output chain, in its order (`output_chain.py`), each with its own part of the C ABI:
         ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch, ptts_pitch.hip =
         the pitch shifter, ptts_tone.hip = the equaliser, ptts_loud.hip = the loudness normaliser, ptts_level.hip = the
-        output gain with its peak limiter and ptts_encode.hip = the output encoder (16-bit and float PCM, G.711); how they
-        are wired behind the codec is ptts.hip's (its section "the output chain");
+        output gain with its peak limiter, ptts_encode.hip = the output encoder (16-bit and float PCM, G.711) and
+        ptts_flac.hip = the packer (FLAC frames); how they are wired behind the codec is ptts.hip's (its section "the output
+        chain");
       * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
-    The first ten see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
+    The first eleven see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
     libptts.so; a unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 

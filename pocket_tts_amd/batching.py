@@ -89,10 +89,13 @@ def eos_bookkeeping_rows(local_step, max_gen_len, frames_after_eos, eos_step, n_
 class Request:
     """One submitted text.  Iterate to receive chunks; `result()` waits for the whole waveform."""
 
-    def __init__(self, rid: int, sample_rate: int | None = None, encoding: str | None = None):
+    def __init__(self, rid: int, sample_rate: int | None = None, encoding: str | None = None,
+                 compression: str | None = None):
         self.id = rid
         self.sample_rate = sample_rate  # rate of the chunks (the codec's own unless the request asked for another)
         self.encoding = encoding        # encoding of the chunks (None: the batcher's one sample format)
+        self.compression = compression  # "flac": each chunk is one whole FLAC frame as a uint8 tensor (`flac.py`)
+        self.blocks = 0                 # FLAC frames delivered so far: the number of the next one
         self._q: queue.Queue = queue.Queue()
         self.frames = 0
         self.error: Exception | None = None
@@ -154,7 +157,7 @@ class ContinuousBatcher:
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`,
-        `tones`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
+        `tones`, `compressions`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
         `ChainTable.route` (`submit`).  `encodings` needs `pcm_format` left at its default (ValueError).  Without any of them
         every request gets the codec's samples in `pcm_format`, with the same graphs and buffers as before.
 
@@ -175,7 +178,7 @@ class ContinuousBatcher:
         spec = ChainSpec.of(spec, **chain)
         if pcm_format not in ("f32", "i16"):
             raise ValueError("pcm_format must be 'f32' or 'i16'")
-        if spec.encodings is not None and pcm_format != "f32":
+        if (spec.encodings is not None or spec.compressions is not None) and pcm_format != "f32":
             raise ValueError("pcm_format and encodings exclude each other: with encodings a request asks for 'pcm_s16le' "
                              "or 'pcm_f32le' itself")
         self.model, self.eng, self.B = model, model.engine, slots
@@ -199,6 +202,7 @@ class ContinuousBatcher:
                                  mode="events", pcm_i16=(pcm_format == "i16"), spec=spec)
         self.chain = self.pipe.chain
         self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
+        self.pk = self.chain.pk  # with the packer a ring line begins with a prefix that says how many bytes follow
         # the output chain has a stage that may lag
         self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
         self.pipe.restart()
@@ -218,6 +222,7 @@ class ContinuousBatcher:
         self.a_pos = np.zeros(slots, np.int64)
         self.row_drain = [False] * slots
         self.a_release = np.full(slots, -1, np.int64)
+        self.a_blocks = np.zeros(slots, np.int64)  # FLAC frames the slot's job has delivered
         # held by the background scheduler around each iteration: other users of the engine (e.g. a voice-prompt encode
         # on a request thread) take it to run between the scheduler's steps (`exclusive`)
         self.engine_lock = threading.RLock()
@@ -250,7 +255,7 @@ class ContinuousBatcher:
         `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.
 
         `**request`: the request's way through the output chain, the fields of `ChainTable.route` (`sample_rate`, `speed`,
-        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`), checked against the batcher's table: ValueError
+        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`, `compression`), checked against the batcher's table: ValueError
         for what it refuses, TypeError for another name.  A request whose row lags (a speed, a pitch, a loudness target, a
         tone or a gain) needs frames_after_eos >= 1."""
         from .engine import check_seed, chunk_seed
@@ -299,7 +304,7 @@ class ContinuousBatcher:
         t_voice = _state_current_end(model_state)
         jobs = []
         with self._lock:
-            req = Request(self._next_id, route.rate, route.encoding)
+            req = Request(self._next_id, route.rate, route.encoding, route.compression)
             self._next_id += 1
         for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
@@ -412,7 +417,10 @@ class ContinuousBatcher:
         for job, b in zip(jobs, rows):
             # the slot's codec carries: zero on the codec stream, behind the frames already queued there
             self.ms.reset_row(b, self.pipe.s2)
-            self.chain.set_row(b, job.route, self.pipe.s2)  # the row's route and a zero state in every stage, same stream
+            # the row's route and a zero state in every stage, same stream; a flac row numbers its frames on from what the
+            # request's earlier text chunks have delivered
+            self.chain.set_row(b, job.route, self.pipe.s2, first_block=job.req.blocks)
+            self.a_blocks[b] = 0
             if self.lagging:
                 self.a_pos[b], self.row_drain[b], self.a_release[b] = 0, False, -1
             job.start = self.g
@@ -483,6 +491,19 @@ class ContinuousBatcher:
 
     def _deliver(self, b, job, line):
         """routes the part of a frame of slot `b` that belongs to its job (`Route.take`)"""
+        if self.pk is not None:
+            from .flac import PREFIX
+
+            nbytes = int.from_bytes(line[:4].numpy().tobytes(), "little")
+            line = line[PREFIX:]
+            if job.route.compression is not None:
+                # the kernel has cut the pre-roll: a line holds one whole frame, or nothing while the row leads; a job of
+                # F frames delivers F of them
+                if nbytes and (self.a_emit[b] < 0 or self.a_blocks[b] < self.a_emit[b]):
+                    job.req._q.put(line[:nbytes])
+                    self.a_blocks[b] += 1
+                    job.req.blocks += 1
+                return
         pos = int(self.a_pos[b])
         lo, hi = job.route.take(pos, None if self.a_emit[b] < 0 else int(self.a_emit[b]))
         if hi > lo:

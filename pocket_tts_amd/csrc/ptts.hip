@@ -2209,6 +2209,8 @@ static const ChainKind kChain[CH_N] = {
      GET(ptts_leveler, level_width), ENQ(ptts_leveler, level_enqueue(st, stage, in, out, i16))},
     {"set_encoder", "encoder", "encode", false, GET(ptts_encoder, encode_batch), GET(ptts_encoder, encode_width),
      GET(ptts_encoder, encode_width), ENQ(ptts_encoder, encode_enqueue(st, stage, in, out))},
+    {"set_packer", "packer", "flac", false, GET(ptts_flac, flac_batch), GET(ptts_flac, flac_width), GET(ptts_flac, flac_width),
+     ENQ(ptts_flac, flac_enqueue(st, stage, (const void *)in, out))},
 };
 #undef GET
 #undef ENQ
@@ -2222,7 +2224,7 @@ static int before_encoder(const ptts_mimi_state *s) {
   return last;
 }
 
-// What the seven setters share, in this order: the state, the output, not in place (f32_only), the batch, then `own()`, the
+// What the eight setters share, in this order: the state, the output, not in place (f32_only), the batch, then `own()`, the
 // calling setter's own refusals (a whole message, or nullptr), then the frame length of a stage that reads the frame's PCM,
 // and for an input buffer that some stage of a lower kind is set on the state NOW, which is why setters are called in
 // chain order.
@@ -2302,6 +2304,18 @@ extern "C" int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float
   });
 }
 
+// its own: the packer reads the bytes of an encoder of its width, which must be on the state; ChainLink::in holds the byte
+// buffer's address
+extern "C" int ptts_mimi_set_packer(ptts_mimi_state *s, ptts_flac *pk, void *d_in_bytes, void *out_bytes) {
+  return set_link(s, CH_PK, pk, (float *)d_in_bytes, out_bytes, 0, [&]() -> const char * {
+    const ptts_encoder *en = (const ptts_encoder *)s->chain[CH_EN].stage;
+    if (!en) return "set_packer: a packer needs an encoder on the state";
+    if (!d_in_bytes) return "set_packer: null input";
+    if (encode_width(en) != flac_width(pk)) return "set_packer: the packer's width is not the encoder's";
+    return nullptr;
+  });
+}
+
 // the codec frame, then the launches of the links the state has; every refusal comes before the first launch
 static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
   const ChainLink *c = s->chain, &ts = c[CH_TS], &en = c[CH_EN];
@@ -2310,6 +2324,9 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
   const int before = en.stage ? before_encoder(s) : -1;
   if (en.stage && (before >= 0) != (en.in != nullptr))
     return fail(-1, "the encoder's input buffer and the state's output stages do not go together");
+  if (c[CH_PK].stage && !en.stage) return fail(-1, "the packer reads an encoder's bytes, but the state has no encoder");
+  if (c[CH_PK].stage && (void *)c[CH_PK].in != en.out)
+    return fail(-1, "the packer's input is not the buffer the encoder writes");
   const bool chained = ts.stage && ts.in;  // resampler -> ts.in -> stretcher
   if (chained && !c[CH_RS].stage) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
   CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));

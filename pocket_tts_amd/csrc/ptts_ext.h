@@ -90,3 +90,12 @@ struct ptts_encoder;
 int encode_enqueue(hipStream_t st, ptts_encoder *en, const float *d_in, void *out_bytes);
 int encode_batch(const ptts_encoder *en);
 int encode_width(const ptts_encoder *en);
+
+// ---- ptts_flac.hip: per-request output compression (FLAC frames; the packer behind the encoder) ----------------------------
+// the frame's launch on `st`: d_in_bytes u8[B][en_pitch(width)] (device, the encoder's output) -> out_bytes u8[B][fl_pitch(width)]
+// (device or pinned host, 16-byte aligned); row b gets the prefix {u32 nbytes, 0, 0, 0}, nbytes bytes and nothing behind 16 +
+// nbytes rounded up to 16.  Returns 0 or a negative error code (message recorded).
+struct ptts_flac;
+int flac_enqueue(hipStream_t st, ptts_flac *pk, const void *d_in_bytes, void *out_bytes);
+int flac_batch(const ptts_flac *pk);
+int flac_width(const ptts_flac *pk);

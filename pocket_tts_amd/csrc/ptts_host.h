@@ -237,8 +237,8 @@ struct ptts_lm_state {
   float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
 };
 
-// the kinds of output stage in launch order: resampler, stretcher, pitcher, toner, normaliser, leveler, encoder
-enum { CH_RS, CH_TS, CH_PS, CH_TN, CH_LN, CH_LV, CH_EN, CH_N };
+// the kinds of output stage in launch order: resampler, stretcher, pitcher, toner, normaliser, leveler, encoder, packer
+enum { CH_RS, CH_TS, CH_PS, CH_TN, CH_LN, CH_LV, CH_EN, CH_PK, CH_N };
 struct ChainLink {
   void *stage = nullptr;
   float *in = nullptr;
@@ -264,7 +264,7 @@ struct ptts_mimi_state {
   int16_t *pcm_i16 = nullptr;
   // the output stages behind the codec (ptts_mimi_set_*), one link per kind in launch order.  A link is empty (stage == nullptr)
   // or holds the stage, the f32 device buffer it reads (`in`; nullptr: the frame's PCM) and what it writes (`out`, int16 with
-  // `i16`, else f32; the encoder's bytes).  mimi_frame_enqueue in ptts.hip states the two cases in which a stage writes
+  // `i16`, else f32; the encoder's bytes; the packer reads the encoder's bytes through `in` and writes ring lines).  mimi_frame_enqueue in ptts.hip states the two cases in which a stage writes
   // another link's `in` instead
   ChainLink chain[CH_N];
   // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next

@@ -232,7 +232,8 @@ class MimiState:
         must follow; uint8 [B, en.pitch] for the encoder.  `mid` None: it reads the frame's PCM, which must then be a DEVICE
         tensor.  Otherwise it reads the float32 device tensor `mid` [B, its input width], which the caller has given the
         stage before it as its `out`; that stage must be set on this state already, so stages are set in chain order.  A
-        resampler is always first and has no `mid`.  `stage` None: off, the launches are those of before."""
+        resampler is always first and has no `mid`.  The packer, behind the encoder, reads the uint8 device tensor the
+        encoder writes and writes uint8 [B, pk.pitch].  `stage` None: off, the launches are those of before."""
         args = [None, None, None]
         if stage is not None:
             stage._check_written(out)
@@ -265,6 +266,10 @@ class MimiState:
 
     def set_encoder(self, en: "Encoder | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
         self._set_stage(Encoder, en, out, mid)
+
+    def set_packer(self, pk: "Packer | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        """`mid`: the uint8 device tensor [B, en.pitch] that the encoder on this state writes; `out`: uint8 [B, pk.pitch]"""
+        self._set_stage(Packer, pk, out, mid)
 
     def __del__(self):
         try:
@@ -565,7 +570,7 @@ class Encoder(_Stage):
 
         super().__init__(engine, batch)
         self.width = self.in_max = self._in_width = int(width)
-        self.pitch = encoding.pitch(self.width)
+        self.pitch = self._out_width = encoding.pitch(self.width)  # in bytes: what a packer behind it reads
         self.rows = [(self.width, encoding.DEFAULT)] * batch  # host mirror: (n, encoding) of each row
         h = C.c_void_p()
         _lib.check(engine.lib.ptts_encoder_create(engine.handle, batch, self.width, C.byref(h)))
@@ -597,6 +602,74 @@ class Encoder(_Stage):
         self._check_in(x)
         self._check_bytes(out)
         self._frame(self.engine.lib.ptts_encode_frame, x, out, stream)
+
+
+class Packer(_Stage):
+    """Output compression of `batch` sequences (include/ptts.h: ptts_flac; contract: `flac.py`), the stage behind the
+    encoder.  A row is dealt its number of samples `n`, its encoding and its compression (`set_row`) and starts as
+    pass-through (`width`, "pcm_s16le").  `frame(x, out)` turns the encoder's bytes x, uint8 [batch, `in_pitch`] on the
+    device, into ring lines out, uint8 [batch, `pitch`] with `pitch` = `flac.pitch(width)`: the prefix {u32 nbytes, 0, 0,
+    0}, then a pass-through row's n * bytes_per_sample bytes or a flac row's frame, and nothing behind 16 + nbytes rounded
+    up to 16.  A flac row keeps a line counter and its previous line on the device; it has no drain flag."""
+
+    _name, _field, _destroy, _attach = "packer", "compression", "ptts_flac_destroy", "ptts_mimi_set_packer"
+    _i16 = False
+    _route_args = staticmethod(lambda r: (r.n_out, r.encoding, r.compression, r.preroll, 0, r.rate))
+
+    def __init__(self, engine: "Engine", batch: int, width: int):
+        from . import encoding, flac
+
+        super().__init__(engine, batch)
+        self.width = int(width)
+        self.in_pitch = self._in_width = encoding.pitch(self.width)
+        self.pitch = self._out_width = flac.pitch(self.width)
+        self.rows = [(self.width, encoding.DEFAULT, None, 0, 0, None)] * batch  # host mirror: what set_row took
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_flac_create(engine.handle, batch, self.width, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _row_args(self, row):
+        return self.rows[row]
+
+    def _check_in(self, x):
+        dev, shape = self.engine.device, [self.batch, self.in_pitch]
+        if x is None or x.device != dev or x.dtype != torch.uint8 or list(x.shape) != shape or not x.is_contiguous():
+            raise ValueError(f"{self._name} input: expected a contiguous uint8 {shape} tensor on {dev}")
+
+    def _check_bytes(self, out):
+        shape = [self.batch, self.pitch]
+        if out is None or out.dtype != torch.uint8 or list(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"{self._name} output: expected a contiguous uint8 {shape} tensor")
+        if not out.is_cuda and not out.is_pinned():
+            raise ValueError(f"{self._name} output: a host tensor must be pinned")
+
+    _check_written = _check_bytes
+
+    def set_row(self, row: int, n: int, encoding: str | None = None, compression: str | None = None, preroll: int = 0,
+                first_block: int = 0, rate: int | None = None, stream: torch.cuda.Stream | None = None):
+        """`row` holds `n` samples in `encoding` (None: "pcm_s16le") from now on, its line counter at 0.  `compression`
+        None: its bytes pass through.  "flac": its lines leave as FLAC frames at `rate` Hz, numbered from `first_block`,
+        cut `preroll` samples into its sequence (`flac.py`, "the cut").  Stream-ordered"""
+        from . import encoding as rule
+        from . import flac
+
+        name = rule.check(encoding)
+        if flac.check(compression) is None:
+            args = (0, int(n), rule.BYTES_PER_SAMPLE[name], 0, 0, 0)
+        else:
+            if rate is None:
+                raise ValueError("packer: a flac row needs its rate")
+            flac.plan(rate, n, name)
+            args = (1, int(n), 2, int(rate), int(preroll), int(first_block))
+        _lib.check(self.engine.lib.ptts_flac_set_row(self.handle, int(row), *args, self._sp(stream)))
+        self.rows[row] = (int(n), name, compression, int(preroll), int(first_block), rate)
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """x u8[B, in_pitch] on the device (an encoder's output) -> out u8[B, pitch], device or pinned host"""
+        self._check_in(x)
+        self._check_bytes(out)
+        self._frame(self.engine.lib.ptts_flac_frame, x, out, stream)
 
 
 class Toner(_Stage):
@@ -957,6 +1030,9 @@ class Engine:
 
     def new_encoder(self, batch: int, width: int) -> Encoder:
         return Encoder(self, batch, width)
+
+    def new_packer(self, batch: int, width: int) -> Packer:
+        return Packer(self, batch, width)
 
     # ---- FlowLM
     def embed_text(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -1330,14 +1406,15 @@ class StepPipeline:
       critical path (on this stack such waits around graph launches cost ~80 us per step, and the branches
       of a forked graph do not run concurrently).
 
-    The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`, `tones`;
-    as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
+    The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`, `tones`,
+    `compressions`; as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
     "fork" mode): the codec graphs end with its stages' launches.  `chain` holds the plan table (`chain.table`) and the
     stage objects, also here as `rs`, `ts`, `ps`, `tn`, `ln`, `lv` and `en`.  `pcm[p]` are then DEVICE tensors and the
     samples reach the host through `out[p]`, the chain's pinned ring, int16 with `pcm_i16`, else float32:
     `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  With the encoder (not with `pcm_i16`)
     `out[p]` are pinned uint8 tensors and `out_of(frame)[b, : route.n_out * route.bytes_per_sample]` are row b's bytes in
-    its route's encoding.  A row gets its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec
+    its route's encoding; with the packer (`pk`, `compressions`) they are ring lines of `flac.pitch(width)` bytes, a 16-byte
+    prefix {u32 nbytes, 0, 0, 0} and then the row's bytes or its FLAC frame (`flac.py`).  A row gets its way through the chain with `chain.set_row(row, chain.table.route(...), s2)` (codec
     stream); rows start on the native rate, speed 1.0, pitch 1.0, bypass and "pcm_s16le".  Without any option nothing
     changes: same buffers, same graph nodes.
     """
@@ -1365,6 +1442,7 @@ class StepPipeline:
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
         self.out = self.chain.out
         self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
+        self.pk = self.chain.pk
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]
         self.flag = [torch.zeros(B, dtype=torch.uint8).pin_memory() for _ in range(nb)]  # EOS flags land on the host
@@ -1406,9 +1484,10 @@ class StepPipeline:
         self.t = 0          # FlowLM steps launched for the current utterances
         self.decoded = 0    # codec frames launched
 
-    def restart(self, routes=None):
+    def restart(self, routes=None, first_blocks=None):
         """new utterances: flush the pending frame, codec state back to zero carries.  `routes` (one `output_chain.Route`
-        per row): the rows join the output chain on these; None: they keep theirs"""
+        per row): the rows join the output chain on these; None: they keep theirs.  `first_blocks` (one int per row, with
+        `routes`): the number of each flac row's first frame; None: 0"""
         self.flush()
         if self.mode != "fork":
             # zero carries on the CODEC stream: ordered behind the frames already queued there and ahead of the next
@@ -1417,7 +1496,7 @@ class StepPipeline:
             if routes is None:
                 self.chain.reset(self.s2)
             for b, route in enumerate(routes or ()):
-                self.chain.set_row(b, route, self.s2)
+                self.chain.set_row(b, route, self.s2, first_block=first_blocks[b] if first_blocks else 0)
         else:
             self.ms.reset()
         self.t = 0

@@ -37,7 +37,8 @@ DEFAULT_TEXT = ("Hello world. I am Kyutai's Pocket TTS. I'm fast enough to run o
 
 # the flags behind each request field of `ChainTable.for_request`, as `generate` names them when a rule refuses one
 FLAGS = dict(sample_rate="--sample-rate", speed="--speed", pitch="--pitch / --pitch-semitones", tone="--tone",
-             loudness_lufs="--loudness-lufs / --peak-dbfs", gain_db="--gain-db / --peak-dbfs", encoding="--encoding")
+             loudness_lufs="--loudness-lufs / --peak-dbfs", gain_db="--gain-db / --peak-dbfs", encoding="--encoding",
+             compression="--compression")
 
 _STREAM_FRAMES = 1_000_000_000  # streaming: the length is not known up front, the header announces this many samples
 
@@ -111,6 +112,58 @@ def write_wav_stream(path, chunks, sample_rate: int, encoding: str | None = None
             out.seek(at_data)
             out.write(struct.pack("<L", bps * n))
     return n
+
+
+def flac_stream_bytes(chunks, sample_rate: int, n: int):
+    """The bytes of a streamed FLAC file: the stream header for blocks of `n` samples (total unknown), each chunk - one whole
+    frame, a uint8 tensor or array as a flac request delivers it - as soon as it arrives, then the 200 ms of silence every
+    container gets, as CONSTANT frames numbered on from the last one (`flac.py`).  An item of `chunks` may also be a list of
+    chunks (`Request.iter_batches`): its frames leave as one item."""
+    from . import flac
+
+    yield flac.stream_header(sample_rate, n)
+    count = 0
+    for item in chunks:
+        parts = []
+        for chunk in item if isinstance(item, (list, tuple)) else (item,):
+            data = chunk.cpu().numpy() if hasattr(chunk, "cpu") else chunk
+            if str(data.dtype) != "uint8":
+                raise ValueError(f"compression 'flac': expected uint8 chunks, one frame each, got {data.dtype}")
+            parts.append(data.tobytes())
+        yield b"".join(parts)
+        count += len(parts)
+    yield flac.silence(count, sample_rate, n)
+
+
+def write_flac_stream(path, chunks, sample_rate: int, n: int) -> int:
+    """`flac_stream_bytes` to a file or stdout ("-").  Returns samples written.  A file gets the total sample count patched
+    into its STREAMINFO at the end; stdout keeps 0, "unknown"."""
+    from . import flac
+
+    out = sys.stdout.buffer if path == "-" else open(path, "wb")
+    items = 0
+    with out:
+        for b in flac_stream_bytes(chunks, sample_rate, n):
+            out.write(b)
+            items += 1
+        total = (items - 2) * int(n) + int(sample_rate) // 5  # all but the header and the tail are one frame each
+        if path != "-":
+            out.seek(0)
+            out.write(flac.patch_total(flac.stream_header(sample_rate, n), total))
+    return total
+
+
+def parse_compression_list(text: str) -> list:
+    """"flac" -> ["flac"] (the `serve --compressions` value)"""
+    from .flac import normalise_compressions
+
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    if not names:
+        raise argparse.ArgumentTypeError("expected at least one compression")
+    try:
+        return normalise_compressions(names)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
 
 
 def parse_encoding_list(text: str) -> list:
@@ -216,7 +269,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--encoding", default=None, choices=["pcm_s16le", "pcm_f32le", "mulaw", "alaw"],
                    help="Sample encoding of the WAV, encoded on the GPU: 16-bit PCM, 32-bit float, or ITU-T G.711 mu-law / A-law "
                         "(telephony; use it with --sample-rate 8000).  Default: 16-bit PCM, converted on the host")
-    g.add_argument("--output-path", default="./tts_output.wav")
+    g.add_argument("--compression", default=None, choices=["flac"],
+                   help="Write a .flac file: lossless frames encoded on the GPU, which decode to the very samples of the 16-bit "
+                        "WAV; only with --encoding pcm_s16le or none (default: none, a WAV)")
+    g.add_argument("--output-path", default=None, help="Default: ./tts_output.wav, or ./tts_output.flac with --compression flac")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
     g.add_argument("--quantize", action="store_true")
@@ -251,6 +307,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--encodings", type=parse_encoding_list, default=None, metavar="E1,E2,...",
                    help="Sample encodings a request may choose with the form field encoding, among mulaw, alaw and pcm_f32le "
                         "(pcm_s16le is always available); encoded on the GPU")
+    s.add_argument("--compressions", type=parse_compression_list, default=None, metavar="C1,...",
+                   help="Compressions a request may choose with the form field container, i.e. flac: lossless frames encoded on "
+                        "the GPU, streamed as audio/flac")
     s.add_argument("--tones", type=parse_tone_list, default=None, metavar="T1,T2,...",
                    help="Tones a request may choose with the form field tone: presets or band lists, e.g. "
                         "telephone,warm,hp:120;peak:3000:4 (bands are joined by ';', tones by ','); equalised on the GPU, with "
@@ -343,7 +402,7 @@ def cli_app(argv=None) -> int:
             pitch, cents = nearest(args.pitch_semitones, *ChainTable.line_of(native, fs, args.sample_rate, args.speed)[2])
             logger.info("--pitch-semitones %g: pitch %s, %+.1f cents from the request", args.pitch_semitones, pitch, cents)
         _, request = ChainTable.for_request(native, fs, args.sample_rate, args.speed, args.gain_db, args.peak_dbfs, pitch,
-                                            args.loudness_lufs, args.encoding, args.tone)
+                                            args.loudness_lufs, args.encoding, args.tone, args.compression)
     except ValueError as e:  # a `RequestError` names its field; the others are those of the two pitch flags above
         logger.error("%s: %s", FLAGS[getattr(e, "field", "pitch")], e)
         return 1
@@ -352,7 +411,14 @@ def cli_app(argv=None) -> int:
     request["gain_db"] = args.gain_db  # as it came: the limiter's 0 dB behind a tone alone is for the model to fill in
     chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
                                          seed=args.seed, **request)
-    write_wav_stream(args.output_path, chunks, args.sample_rate or model.sample_rate, args.encoding)
+    rate = args.sample_rate or model.sample_rate
+    if args.output_path is None:
+        args.output_path = "./tts_output.flac" if args.compression else "./tts_output.wav"
+    if args.compression:
+        n = ChainTable.line_of(native, fs, args.sample_rate, args.speed)[2][1]  # the samples of a frame behind rate and speed
+        write_flac_stream(args.output_path, chunks, rate, n)
+    else:
+        write_wav_stream(args.output_path, chunks, rate, args.encoding)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)
     return 0

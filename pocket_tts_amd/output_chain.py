@@ -4,11 +4,12 @@ the stage objects and buffers on the device (`OutputChain`).
 
 The order, which is also the launch order behind the codec's last kernel:
 
-    codec -> resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder
+    codec -> resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder -> packer
 
-A pipeline has any subset of the seven stages; the toner and the normaliser bring the leveler with them.  The buffer rule: the
-first stage present reads the frame's PCM; between two consecutive stages present there is one f32 device buffer [batch, input
-width of the later one], which must be the output width of the earlier one; the last stage writes the pinned ring.
+A pipeline has any subset of the eight stages; the toner and the normaliser bring the leveler with them, the packer the
+encoder.  The buffer rule: the first stage present reads the frame's PCM; between two consecutive stages present there is one
+device buffer [batch, input width of the later one], which must be the output width of the earlier one, f32 but for the
+encoder's bytes before the packer, which are uint8 [batch, encoding.pitch(width)]; the last stage writes the pinned ring.
 
 The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `tone.py`, `loudness.py` and
 `level.py`: it needs no library, no GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
@@ -29,6 +30,11 @@ runs the limiter behind it, because a boost creates peaks; so its pre-roll is wh
 The encoder (`encoding.py`) is the last stage where a table has one.  It has no state and no lag: it adds nothing to a row's
 pre-roll, and the zeros of a draining row reach it like any other sample.  Everything above counts samples; only the ring the
 encoder writes is in bytes, `bytes_per_sample` of the row's encoding to a sample.
+
+The packer (`flac.py`) is the last stage where a table has one: it turns the encoder's bytes into ring lines with a 16-byte
+prefix that says how many bytes follow, a row's encoded bytes as they are or, for a row whose `compression` is "flac", one
+FLAC frame per line.  A compressed frame cannot be sliced on the host, so a flac row's pre-roll is cut on the device: its
+first `drain_frames` lines carry nothing and every later line carries one whole block of the samples behind the pre-roll.
 """
 
 from __future__ import annotations
@@ -37,6 +43,7 @@ import numbers
 from dataclasses import dataclass
 
 from . import encoding as encoding_rule
+from . import flac as flac_rule
 from . import level as level_rule
 from . import loudness as loud_rule
 from . import pitch as pitch_rule
@@ -62,7 +69,8 @@ class Route:
     plan index in the pitcher (None without one), `pitched`: that plan is no identity plan; `loud`: (plan index in the
     normaliser, loudness_lufs), None for bypass; `encoding`: the name of the row's output encoding, None on a table without
     the encoder, and `bytes_per_sample`: what a sample of it takes in the encoder's ring (None likewise: the ring's dtype
-    says); `tone_plan`: its plan index in the toner (None: bypass, or no toner), `toned`: it has one."""
+    says); `tone_plan`: its plan index in the toner (None: bypass, or no toner), `toned`: it has one;
+    `compression`: None or "flac", the row's lines leave the packer as FLAC frames."""
 
     rate_index: int
     rate: int
@@ -80,6 +88,7 @@ class Route:
     bytes_per_sample: int | None = None
     tone_plan: int | None = None
     toned: bool = False
+    compression: str | None = None
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -108,9 +117,9 @@ def _ask(field: str, rule, *args):
 
 @dataclass(frozen=True)
 class ChainSpec:
-    """What a pipeline's output chain is built with: the seven options that `StepPipeline`, `ContinuousBatcher` and
+    """What a pipeline's output chain is built with: the eight options that `StepPipeline`, `ContinuousBatcher` and
     `server.create_app` take as keywords, one per stage but the leveler's, which three bring.  The default of each is "that
-    stage does not exist": with all seven nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
+    stage does not exist": with all eight nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
     spec is hashable.
 
     `sample_rates`: the output rates a row may choose besides the native one, each a rate `resample.plan` admits, e.g. [8000,
@@ -128,6 +137,8 @@ class ChainSpec:
     "pcm_f32le"]; the encoder ends the chain and writes bytes.  Not together with a 16-bit ring (`pcm_i16`, `pcm_format`).
     `tones`: the tones a row may choose, presets or band lists of `tone.py`, e.g. ["telephone", "hp:120;peak:3000:4"]; the
     parametric equaliser, which brings the leveler with it as its peak limiter.
+    `compressions`: the compressions a row may choose, names of `flac.py`, i.e. ["flac"]; the packer ends the chain behind
+    the encoder, which it brings with it, and writes ring lines with a length prefix.
 
     What the rules refuse raises their ValueError when the table is built (`table`), before anything is allocated."""
 
@@ -138,19 +149,20 @@ class ChainSpec:
     loudness: bool = False
     encodings: tuple | None = None
     tones: tuple | None = None
+    compressions: tuple | None = None
 
     TAGS = dict(sample_rates="rate", speeds="speed", level="level", pitches="pitch", loudness="loud", encodings="enc",
-                tones="tone")  # what `tags` calls each option
+                tones="tone", compressions="comp")  # what `tags` calls each option
 
     def __post_init__(self):
-        for name in ("sample_rates", "speeds", "pitches", "encodings", "tones"):
+        for name in ("sample_rates", "speeds", "pitches", "encodings", "tones", "compressions"):
             v = getattr(self, name)
             if v is not None and not isinstance(v, (tuple, str)):  # a string is no list: the rules say so
                 object.__setattr__(self, name, tuple(v))
 
     @classmethod
     def of(cls, spec=None, **chain):
-        """`spec`, or the spec of the seven options given as keywords; TypeError for another keyword, or for both"""
+        """`spec`, or the spec of the eight options given as keywords; TypeError for another keyword, or for both"""
         if spec is None:
             return cls(**chain)
         if chain:
@@ -162,14 +174,14 @@ class ChainSpec:
 
     def tags(self) -> tuple:
         """The stages of the spec as the words that tell cached contexts apart: each option that is set as its tag in
-        `TAGS`, a list other than the encoder's followed by its values.  ("rate", 8000, "level", "enc") is a resampler to 8
+        `TAGS`, a list other than the encoder's and the packer's followed by its values.  ("rate", 8000, "level", "enc") is a resampler to 8
         kHz, the leveler and the encoder: a context serves every gain, ceiling and target and all encodings, but one list
         of rates, speeds, pitches and tones."""
         out = []
         for name, tag in self.TAGS.items():
             v = getattr(self, name)
             if v is not None and v is not False:
-                out += [tag, *(v if isinstance(v, tuple) and name != "encodings" else ())]
+                out += [tag, *(v if isinstance(v, tuple) and name not in ("encodings", "compressions") else ())]
         return tuple(out)
 
 
@@ -183,11 +195,13 @@ class ChainTable:
     `loud_plans` / `loud_index[(rate, n)]` (`loudness.table`), and with `level`, `loudness` or `tones` the leveler's
     `level_plans` / `level_index[(rate, n)]` (`level.table`).  With `encodings` the chain ends with the encoder and
     `encodings` is the configured list, `pcm_s16le` first; a list makes the table non-empty even when the encoder is the only
-    stage.  `width` is the widest line that leaves the last stage before the encoder.  The graphs bake plan indices into
+    stage.  With `compressions` it ends with the packer behind the encoder (which the option brings: `encodings` is then at
+    least ["pcm_s16le"]) and `compressions` is the configured list.  `width` is the widest line that leaves the last stage
+    before the encoder.  The graphs bake plan indices into
     device tables, so the order is part of the contract."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None, tones=None):
+                 pitches=None, loudness: bool = False, encodings=None, tones=None, compressions=None):
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
@@ -215,6 +229,12 @@ class ChainTable:
             self.loud_plans, self.loud_index = loud_rule.table(lines)
         if level or loudness or self.tones is not None:
             self.level_plans, self.level_index = level_rule.table(lines)
+        self.compressions = None if compressions is None else flac_rule.normalise_compressions(compressions)
+        if self.compressions is not None:
+            if not self.compressions:
+                raise ValueError("compressions: the list holds no compression")
+            if encodings is None:
+                encodings = ()  # the packer brings the encoder
         self.encodings = None if encodings is None else encoding_rule.normalise_encodings(encodings)
         self.width = max(n for _, n in lines)
 
@@ -237,8 +257,8 @@ class ChainTable:
         return [t for j, t in enumerate(self.tones) if self.tone_index[(rate, n)][j] is not None]
 
     def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None,
-              encoding=None, tone=None) -> Route:
-        """The `Route` of a request.  Its eight fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
+              encoding=None, tone=None, compression=None) -> Route:
+        """The `Route` of a request.  Its nine fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
         `generate_audio_stream` take as keywords and hand on as they came; None is always "as without the stage":
 
         `sample_rate`: the rate of the request's audio, the native one (None) or one of the configured; a frame then yields
@@ -259,6 +279,8 @@ class ChainTable:
         the samples are amplified and peak-limited to 10^(peak_dbfs / 20).  0 is not None: it limits at the ceiling.
         `encoding`: "pcm_s16le" (None on a table with the encoder), "pcm_f32le", "mulaw" or "alaw", among the configured:
         the chunks are int16, float32 or uint8 (ITU-T G.711) tensors, one element per sample.
+        `compression`: "flac" where configured, only with `encoding` None or "pcm_s16le" and on a line `flac.plan` admits:
+        the chunks are uint8 tensors, one whole FLAC frame each, which decode to the samples "pcm_s16le" would deliver.
 
         A stage that lags (all but the resampler, the toner and the encoder) delays the output, not the count: the samples
         delivered in all stay those of the same request without it (the drain rule of the module's docstring).  ValueError for
@@ -332,9 +354,16 @@ class ChainTable:
         elif encoding is not None:
             raise ValueError(f"encoding {encoding!r}: this batcher writes one sample format for all (build it with encodings "
                              "for per-request encodings)")
+        if self.compressions is not None:
+            if flac_rule.check(compression, self.compressions) is not None:
+                flac_rule.plan(rate, n_out, encoding)
+        elif compression is not None:
+            raise ValueError(f"compression {compression!r}: this batcher writes uncompressed samples only (build it with "
+                             "compressions for per-request compression)")
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
                      "stretch" if stretched else "pitch" if pitched else "loud" if loud is not None
-                     else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps, tplan, tplan is not None)
+                     else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps, tplan, tplan is not None,
+                     compression)
 
     @staticmethod
     def line_of(native_rate: int, frame_samples: int, sample_rate=None, speed=None):
@@ -355,7 +384,7 @@ class ChainTable:
 
     @staticmethod
     def for_request(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
-                    pitch=None, loudness_lufs=None, encoding=None, tone=None):
+                    pitch=None, loudness_lufs=None, encoding=None, tone=None, compression=None):
         """One request that gets a chain of its own (the fields of `route`): (spec, request), the `ChainSpec` of exactly the
         stages it uses and the request in canonical form, the dict that `spec.table(native_rate, frame_samples).route`
         takes - the native rate, speed 1.0 and pitch 1.0 as None, speed and pitch as the floats of their fractions, the tone
@@ -383,26 +412,33 @@ class ChainTable:
                 _ask("gain_db", level_rule.plan, *line)
         if encoding is not None:
             _ask("encoding", encoding_rule.check, encoding)
+        if compression is not None:
+            _ask("compression", flac_rule.check, compression)
+            _ask("compression", flac_rule.plan, *line, encoding)
         one = lambda v: None if v is None else (v,)  # noqa: E731
         spec = ChainSpec(one(sample_rate), one(speed), gain_db is not None, one(pitch), loudness_lufs is not None,
-                         None if encoding is None else encoding_rule.NAMES, one(tone))
-        return spec, dict(sample_rate=sample_rate, speed=speed, gain_db=gain_db, peak_dbfs=peak_dbfs, pitch=pitch,
-                          loudness_lufs=loudness_lufs, encoding=encoding, tone=tone)
+                         None if encoding is None else encoding_rule.NAMES, one(tone), one(compression))
+        req = dict(sample_rate=sample_rate, speed=speed, gain_db=gain_db, peak_dbfs=peak_dbfs, pitch=pitch,
+                   loudness_lufs=loudness_lufs, encoding=encoding, tone=tone)
+        if compression is not None:  # only then: a request without it is the dict it always was
+            req["compression"] = compression
+        return spec, req
 
 
 class OutputChain:
-    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `ln` / `lv` / `en`
-    (`engine.Resampler`, `Stretcher`, `Pitcher`, `Toner`, `Normalizer`, `Leveler`, `Encoder`; None where the table has no
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `ln` / `lv` / `en` / `pk`
+    (`engine.Resampler`, `Stretcher`, `Pitcher`, `Toner`, `Normalizer`, `Leveler`, `Encoder`, `Packer`; None where the table has no
     such stage), the device buffers between them and the pinned ring `out` of `nb` tensors, which the last stage writes.
     The buffer rule of the module's docstring gives them: without the encoder a ring slot is [batch, widest line], int16
     with `pcm_i16`, else float32; on a table with `encodings` it is uint8 [batch, encoding.pitch(widest line)], row b's
-    n_out * bytes_per_sample bytes at the start of its row, and `pcm_i16` must be left False (ValueError).  An empty table
+    n_out * bytes_per_sample bytes at the start of its row, and `pcm_i16` must be left False (ValueError); with `compressions`
+    it is uint8 [batch, flac.pitch(widest line)], a row's prefix and bytes (`flac.py`, "the ring").  An empty table
     creates nothing: `out` is None and the codec writes its PCM as without a chain."""
 
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
 
-        from .engine import Encoder, Leveler, Normalizer, Pitcher, Resampler, Stretcher, Toner
+        from .engine import Encoder, Leveler, Normalizer, Packer, Pitcher, Resampler, Stretcher, Toner
 
         if table.encodings is not None and pcm_i16:
             raise ValueError("pcm_i16 and encodings exclude each other: with encodings a row asks for pcm_s16le itself")
@@ -414,7 +450,8 @@ class OutputChain:
         self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
         self.en = Encoder(engine, batch, table.width) if table.encodings is not None else None
-        self._stages = [s for s in self.per_kind() if s is not None]
+        self.pk = Packer(engine, batch, table.width) if table.compressions is not None else None
+        self._stages = [s for s in (*self.per_kind(), self.pk) if s is not None]
         self._between = []  # one device buffer between two stages serves every ring slot: the codec graphs run one after the other
         self.out = None
         if not self._stages:
@@ -422,15 +459,18 @@ class OutputChain:
         for before, s in zip(self._stages, self._stages[1:]):
             if before._out_width != s._in_width:
                 raise ValueError(f"{s._field}: the {s._name}'s line is not the line of the stage before it")
-            self._between.append(torch.zeros(batch, s._in_width, device=engine.device))
-        if self.en is not None:
+            self._between.append(torch.zeros(batch, s._in_width, device=engine.device,
+                                             dtype=torch.uint8 if s is self.pk else torch.float32))
+        if self.pk is not None:
+            shape, dtype = (batch, self.pk.pitch), torch.uint8
+        elif self.en is not None:
             shape, dtype = (batch, self.en.pitch), torch.uint8
         else:
             shape, dtype = (batch, self._stages[-1]._out_width), torch.int16 if pcm_i16 else torch.float32
         self.out = [torch.zeros(*shape, dtype=dtype).pin_memory() for _ in range(nb)]
 
     def per_kind(self):
-        """(rs, ts, ps, tn, ln, lv, en) in chain order, None where the table has no such stage"""
+        """(rs, ts, ps, tn, ln, lv, en) in chain order, None where the table has no such stage; the packer is `pk`"""
         return self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en
 
     def stages(self):
@@ -452,11 +492,15 @@ class OutputChain:
         for s in self._stages:
             s.reset(stream)
 
-    def set_row(self, row: int, route: Route, stream=None):
+    def set_row(self, row: int, route: Route, stream=None, first_block: int = 0):
         """a new sequence joins `row` on `route` with a zero state in every stage, not draining; a stage the route does not
-        use runs its identity plan or bypass.  Stream-ordered"""
+        use runs its identity plan or bypass.  `first_block`: the number of a flac row's first frame, what its request has
+        delivered so far.  Stream-ordered"""
         for s in self._stages:
-            s.set_row(row, *s._route_args(route), stream)
+            if s is self.pk:
+                s.set_row(row, route.n_out, route.encoding, route.compression, route.preroll, first_block, route.rate, stream)
+            else:
+                s.set_row(row, *s._route_args(route), stream)
 
     def drain_row(self, row: int, route: Route, stream=None):
         """from now on (stream-ordered) the row's incoming frames count as zeros at the stage `route.drain_stage` names"""

@@ -12,7 +12,8 @@ server started with `level` the output level `gain_db` with its ceiling `peak_db
 with `loudness` the loudness target `loudness_lufs` (`loudness.py`; with `peak_dbfs` as its ceiling, without `gain_db`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.  On a server started with `encodings` the
 field `encoding` chooses the sample encoding among them and `pcm_s16le` (`encoding.py`: ITU-T G.711 `mulaw` / `alaw`, or
-`pcm_f32le`), encoded on the GPU; header and silence follow it.  `container=raw` (default `wav`) leaves the header out: the
+`pcm_f32le`), encoded on the GPU; header and silence follow it.  On a server started with `compressions` `container=flac`
+answers `audio/flac`, lossless frames encoded on the GPU (`flac.py`).  `container=raw` (default `wav`) leaves the header out: the
 encoded samples and the trailing silence as `application/octet-stream`, with the response headers `X-Audio-Encoding` and
 `X-Sample-Rate` - what a media-stream gateway forwards.  On a server started with `tones` the field `tone` chooses one of
 them (`tone.py`: a preset such as `telephone`, or a band list), equalised on the GPU with the peak limiter behind it
@@ -342,13 +343,18 @@ def parse_encoding(fields: dict, encodings):
     return name
 
 
-def parse_container(fields: dict) -> str:
-    """the optional `container` field: "wav" (absent or empty) or "raw"; FormError for anything else"""
+def parse_container(fields: dict, compressions=None) -> str:
+    """the optional `container` field: "wav" (absent or empty) or "raw", and on a server started with `compressions` one of
+    them ("flac"); FormError for anything else"""
     raw = (fields.get("container") or "").strip()
     if raw in ("", "wav"):
         return "wav"
     if raw == "raw":
         return "raw"
+    if compressions is not None:
+        if raw in compressions:
+            return raw
+        raise FormError(f"container must be 'wav', 'raw' or one of {list(compressions)}, got {raw!r}")
     raise FormError(f"container must be 'wav' or 'raw', got {raw!r}")
 
 
@@ -364,9 +370,12 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     rules refuse in a list is a ValueError here, not at the first request; a request with a value that is not configured, or
     that its rate or line does not admit, gets a 400 with the list of what is.  The WAV header and the trailing silence
     follow the request's rate and encoding.  With `encodings` the batcher is built with its default `pcm_format`: every
-    request's samples leave the GPU in its own encoding.  `batcher_factory(model, slots, capacity)` replaces the batcher
+    request's samples leave the GPU in its own encoding.  With `compressions` a request may send `container=flac`: the
+    answer is `audio/flac`, the stream header, one frame per codec frame as each is decoded and the silent tail
+    (`main.flac_stream_bytes`), which decodes to the samples of the `container=wav` answer; it takes `encoding` pcm_s16le or
+    none, and a line `flac.plan` admits (400 with the rule's message otherwise).  `batcher_factory(model, slots, capacity)` replaces the batcher
     (tests)."""
-    from .main import wav_stream_bytes
+    from .main import flac_stream_bytes, wav_stream_bytes
 
     from .output_chain import ChainSpec
 
@@ -377,6 +386,7 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     # the one table every request is checked against: the rules of every stage on every line (ValueError at start-up)
     table = spec.table(model.sample_rate, getattr(getattr(model, "engine", None), "frame_samples", 1920))
     sample_rates, level, loudness, encodings = spec.sample_rates, spec.level, spec.loudness, table.encodings
+    compressions = table.compressions
     speeds_of = None if spec.speeds is None else table.speeds_of()
 
     own_lsd = getattr(model, "lsd_decode_steps", 1)
@@ -504,7 +514,17 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             enc = parse_encoding(fields, encodings)
             if enc is not None and encodings is not None:
                 settings["encoding"] = enc
-            container = parse_container(fields)
+            container = parse_container(fields, compressions)
+            flac_n = None
+            if compressions is not None and container in compressions:
+                settings["compression"] = container
+                # the rule's refusals (an encoding that is not pcm_s16le, a line FLAC does not admit), and the block size
+                route_fields = ("sample_rate", "speed", "pitch", "tone", "loudness_lufs", "gain_db", "peak_dbfs", "encoding",
+                                "compression")
+                try:
+                    flac_n = table.route(**{k: settings[k] for k in route_fields if k in settings}).n_out
+                except ValueError as e:
+                    raise FormError(str(e)) from None
             voice_url = fields.get("voice_url") or None
             upload = files.get("voice_wav")
             if upload is not None and not upload[1]:
@@ -533,6 +553,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
                 yield chunks[0] if len(chunks) == 1 else torch.cat(chunks)
 
         out_rate = rate or model.sample_rate
+        if flac_n is not None:  # every frame that has arrived so far as one item: flac_stream_bytes counts them
+            return StreamingResponse(flac_stream_bytes(req.iter_batches(), out_rate, flac_n), media_type="audio/flac",
+                                     headers={"Content-Disposition": "attachment; filename=generated_speech.flac"})
         if container == "raw":
             return StreamingResponse(wav_stream_bytes(frames(), out_rate, enc, header=False),
                                      media_type="application/octet-stream",

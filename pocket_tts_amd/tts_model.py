@@ -205,9 +205,11 @@ class TTSModel:
 
         `**request` (not in the reference): the request's way through the output chain on the GPU, the fields of
         `output_chain.ChainTable.route` (`sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
-        `encoding`, `tone`), each checked by its rule on the request's own line (`ChainTable.for_request`): ValueError with
-        the rule's message, TypeError for another name.  The chunks then hold what a frame yields at the end of the chain,
-        as fp32, or typed as the `encoding`.  None of them: the codec's own samples, as before.
+        `encoding`, `tone`, `compression`), each checked by its rule on the request's own line (`ChainTable.for_request`):
+        ValueError with the rule's message, TypeError for another name.  The chunks then hold what a frame yields at the end
+        of the chain, as fp32, or typed as the `encoding`; with `compression="flac"` each chunk is one whole FLAC frame as a
+        uint8 tensor, numbered on across the text chunks (`flac.py`; `main.flac_stream_bytes` makes a file of them).  None of
+        them: the codec's own samples, as before.
 
         `seed` (an int in [0, 2**63), not in the reference) makes the noise of a temp > 0 generation reproducible: step j
         of text chunk i draws from the device generator keyed by (`chunk_seed(seed, i)`, j, column) - no host draw, no
@@ -224,15 +226,19 @@ class TTSModel:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
                                            self.pad_with_spaces_for_short_inputs, self.remove_semicolons)
+        blocks = 0  # FLAC frames yielded so far: a follow-up chunk numbers its frames on from here
         for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, self.pad_with_spaces_for_short_inputs, self.remove_semicolons)
             guess += 2
             effective = frames_after_eos if frames_after_eos is not None else guess
-            yield from self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
-                                                              None if seed is None else chunk_seed(seed, i), spec, request)
+            for audio in self._generate_audio_stream_short_text(model_state, chunk, effective, copy_state,
+                                                                None if seed is None else chunk_seed(seed, i), spec, request,
+                                                                first_block=blocks):
+                blocks += 1
+                yield audio
 
     @torch.no_grad()
-    def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None) -> list:
+    def generate_audio_batch(self, model_states, texts, frames_after_eos: int | None = None, seeds=None, **request) -> list:
         """Generate several utterances concurrently on one GPU (not in the reference, which is batch 1 and
         requires equal cache offsets across a batch: tts_model.py:491-492, transformer.py:12-13).
 
@@ -247,7 +253,11 @@ class TTSModel:
         single-utterance result; with temp > 0 rows draw independent noise (the reference's sequential use of the
         global generator cannot be reproduced across a batch).  `seeds`: one int in [0, 2**63) or None per text; a seeded
         text draws the noise `generate_audio(..., seed=)` draws for it, whatever its row and its neighbours, and a text
-        without a seed draws as without the argument.  Returns a list of fp32 CPU tensors."""
+        without a seed draws as without the argument.  Returns a list of fp32 CPU tensors.  `**request`: of the output chain's
+        fields this path takes `compression` alone (TypeError for another name), one value for all texts.  `compression="flac"`: every
+        utterance leaves the GPU as FLAC frames of its 16-bit samples (`flac.py`), and the list holds, per text, the list of
+        its frames, one uint8 CPU tensor each, numbered from 0 (`main.flac_stream_bytes` makes a file of them)."""
+        from . import flac as flac_rule
         from .batching import eos_bookkeeping_rows
         from .engine import StepPipeline
 
@@ -262,6 +272,12 @@ class TTSModel:
         if len(seeds) != B:
             raise ValueError("need one seed (or None) per text")
         seeds = [None if s is None else check_seed(s) for s in seeds]
+        if set(request) - {"compression"}:
+            raise TypeError(f"generate_audio_batch takes no {sorted(set(request) - {'compression'})} (of the chain's fields only "
+                            "compression)")
+        compression = request.get("compression")
+        if flac_rule.check(compression) is not None:
+            flac_rule.plan(int(self.config.mimi.sample_rate), eng.frame_samples)
         # rows of one voice next to each other: they share the voice's keys (KvPrefix), and the decode attention scores a
         # shared prefix once per 4 neighbouring rows (attn_cascade_kernel)
         first: dict = {}
@@ -270,7 +286,7 @@ class TTSModel:
         order = sorted(range(B), key=lambda i: first[id(model_states[i])])
         if order != list(range(B)):
             got = self.generate_audio_batch([model_states[i] for i in order], [texts[i] for i in order], frames_after_eos,
-                                            [seeds[i] for i in order])
+                                            [seeds[i] for i in order], **request)
             res = [None] * B
             for pos, i in enumerate(order):
                 res[i] = got[pos]
@@ -303,13 +319,16 @@ class TTSModel:
             need = max(t + tk.shape[1] for t, tk in zip(t0s, toks)) + steps_max + StepPipeline.NB_EVENTS + 2
             cap = -(-need // 256) * 256
             key = ("batch", B, cap, self.lsd_decode_steps, float(self.eos_threshold), use_noise)
+            if compression is not None:  # a context of its own: its codec graphs end with the encoder and the packer
+                key = (*key, "comp")
             ctx = self._ctx_cache.pop(key, None)
             if ctx is None:
                 self._drop_batch_contexts(keep=1)
                 batch, ms = eng.new_lm_state(B, cap), eng.new_mimi_state(B)
                 if use_noise:
                     batch.set_noise(self.temp, int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
-                pipe = StepPipeline(eng, batch, ms, None, self.lsd_decode_steps, float(self.eos_threshold), mode="events")
+                pipe = StepPipeline(eng, batch, ms, None, self.lsd_decode_steps, float(self.eos_threshold), mode="events",
+                                    compressions=None if compression is None else [compression])
                 ctx = dict(st=batch, ms=ms, pipe=pipe, seeded=[False] * B, clamped=[False] * B)
             batch, ms, pipe = ctx["st"], ctx["ms"], ctx["pipe"]
             nb = pipe.nb
@@ -331,19 +350,26 @@ class TTSModel:
                 elif ctx["clamped"][b]:
                     batch.clear_row_sampling(b)
                 ctx["clamped"][b] = clamp
-            pipe.restart()  # zero codec carries, on the codec stream
+            # zero codec carries, on the codec stream; compressed rows restart their frame numbers
+            pipe.restart(None if compression is None else [pipe.chain.table.route(compression=compression)] * B)
+            packed = [[] for _ in range(B)]  # compressed: each row's frames
             gens_a, faes_a = np.asarray(gens), np.asarray(faes)
             eos_step = np.full(B, -1, np.int64)
             n_emit = np.full(B, -1, np.int64)  # frames to keep for row b (decided when its loop would break)
             out = np.empty((B, steps_max, eng.frame_samples), np.float32)
             flags_np = [f_.numpy() for f_ in pipe.flag]   # views of the pinned buffers the kernels write
-            pcm_np = [p_.numpy() for p_ in pipe.pcm]
+            pcm_np = [p_.numpy() for p_ in pipe.pcm] if compression is None else None  # with a chain the PCM stays on the device
             t = collected = 0
 
             def collect(f):
                 pipe.done_event(f).synchronize()  # codec frame f done => FlowLM step f done too
                 eos_bookkeeping_rows(f, gens_a, faes_a, eos_step, n_emit, flags_np[f % nb] != 0)
-                if f < steps_max:
+                if f < steps_max and compression is not None:
+                    lines = pipe.out_of(f).numpy()
+                    for b in range(B):  # no pre-roll here: every line holds one frame behind its prefix
+                        nbytes = int.from_bytes(lines[b, :4].tobytes(), "little")
+                        packed[b].append(torch.from_numpy(lines[b, flac_rule.PREFIX:flac_rule.PREFIX + nbytes].copy()))
+                elif f < steps_max:
                     out[:, f] = pcm_np[f % nb]    # plain memcpy per row (numpy: no intra-op thread team)
 
             while True:
@@ -374,6 +400,9 @@ class TTSModel:
             n = int(n_emit[b]) if n_emit[b] >= 0 else gens[b]
             if eos_step[b] < 0:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
+            if compression is not None:
+                res.append(packed[b][:n])
+                continue
             # a view of this call's own frame buffer (allocated per call, so nothing rewrites it): no second copy of the audio
             res.append(torch.from_numpy(out[b, :n].reshape(-1)) if n > 0 else torch.zeros(0))
         return res
@@ -468,9 +497,11 @@ class TTSModel:
             torch.nn.init.trunc_normal_(out, mean=0.0, std=std, a=-self.noise_clamp, b=self.noise_clamp)
 
     def _generate_audio_stream_short_text(self, model_state: dict, text: str, frames_after_eos: int, copy_state: bool,
-                                          row_seed: int | None, spec, request: dict):
-        """one text chunk on a pipeline of `spec`, which routes `request`: the two that `ChainTable.for_request` returns"""
+                                          row_seed: int | None, spec, request: dict, first_block: int = 0):
+        """one text chunk on a pipeline of `spec`, which routes `request`: the two that `ChainTable.for_request` returns;
+        `first_block`: the number of the chunk's first FLAC frame where the request is compressed"""
         from . import encoding as encoding_rule
+        from .flac import PREFIX
 
         eng = self.engine
         tokens = torch.tensor(self.tokenizer.encode(text), dtype=torch.long)[None, :]
@@ -509,7 +540,7 @@ class TTSModel:
         eng.lm_prefill(st, eng.embed_text(tokens))            # text prefill (tts_model.py:722-725)
         # the codec's carries and the row's rate, plan, gain and ceiling with a zero state in every stage, on the codec stream
         route = pipe.chain.table.route(**request)
-        pipe.restart([route])
+        pipe.restart([route], [first_block])
         if seeded:
             # temperature and clamp through the row's sampling override: the kernels read it at run time, while the
             # state's own temperature is frozen into the captured step
@@ -526,18 +557,29 @@ class TTSModel:
             yielded = 0    # frames handed to the caller
 
             pos, frames = 0, None  # output samples read so far; the chunk's frame count once it is known
+            blocks = 0             # FLAC frames read so far
 
             def pop(frame):
-                nonlocal pos
+                nonlocal pos, blocks
                 pipe.done_event(frame).synchronize()
                 if pipe.out is None:
                     return pipe.pcm_of(frame)[0].clone()
+                if route.compression is not None:
+                    # the kernel has cut the pre-roll: a line holds one whole frame, or nothing while the row leads, and
+                    # `frames` frames make `frames` of them
+                    line = pipe.out_of(frame)[0]
+                    nbytes = int.from_bytes(line[:4].numpy().tobytes(), "little")
+                    if frames is not None and blocks >= frames:
+                        nbytes = 0
+                    blocks += nbytes > 0
+                    return line[PREFIX:PREFIX + nbytes].clone()
                 lo, hi = route.take(pos, frames)  # frames are read in order: drop the pre-roll, stop at the chunk's end
                 pos += route.n_out
                 if route.bytes_per_sample is None:
                     return pipe.out_of(frame)[0, lo:hi].clone()
                 bps = route.bytes_per_sample  # the encoder's ring is in bytes: the samples as a typed view of them
-                return pipe.out_of(frame)[0, lo * bps:hi * bps].clone().view(encoding_rule.torch_dtype(route.encoding))
+                at = PREFIX if pipe.chain.pk is not None else 0  # behind the packer's prefix
+                return pipe.out_of(frame)[0, at + lo * bps:at + hi * bps].clone().view(encoding_rule.torch_dtype(route.encoding))
 
             for step in range(max_gen_len):
                 if yielded == 0 and emitted == 1:
@@ -600,6 +642,8 @@ class TTSModel:
             self._ctx_cache[key] = ctx
         if st.error():  # a cooperative kernel gave up waiting for a peer (GPU oversubscribed beyond the library's contract)
             raise RuntimeError("libptts: a cooperative FlowLM kernel timed out; the audio of this chunk is invalid")
+        if route.compression is not None:
+            total = blocks * route.n_out  # `total` has counted bytes
         dur_ms = int(total * 1000 / route.rate)
         gen_ms = max(1, int((time.monotonic() - t_start) * 1000))
         logger.info("Generated: %d ms of audio in %d ms so %.2fx faster than real-time", dur_ms, gen_ms, dur_ms / gen_ms)
