@@ -7,7 +7,10 @@ with the activation rounded as the weight format rounds it (bf16 round-to-neares
 for wfmt 3, x * ln_g for int8 with a folded LayerNorm).  bf16 x bf16 and split products are exact in fp32, so the kernel
 and this reference then differ only by the order of the fp32 summation, in every format.
 
-Enumerations as in ptts_kernels.h / include/ptts.h.  Device-agnostic torch: the tensors' device is used throughout."""
+Enumerations as in ptts_kernels.h / include/ptts.h.  Device-agnostic torch: the tensors' device is used throughout.
+The epilogues behind EPI_GATE are tested where they run: EPI_QKV in test_gpu_lm_matrix.py (the fp32 FlowLM),
+test_gpu_mimi_matrix.py and test_gpu_codec_matrix.py (the codec), EPI_HEAD and EPI_LATENT in test_gpu_flow_matrix.py,
+EPI_CONVTR in test_gpu_mimi_matrix.py and test_gpu_codec_matrix.py, EPI_PCM in test_gpu_mimi_matrix.py."""
 
 from __future__ import annotations
 
