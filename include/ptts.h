@@ -43,6 +43,7 @@ typedef struct ptts_pitcher ptts_pitcher;       /* pitches of B sequences       
 typedef struct ptts_leveler ptts_leveler;       /* output levels of B sequences          */
 typedef struct ptts_loudnorm ptts_loudnorm;     /* loudness targets of B sequences       */
 typedef struct ptts_tone ptts_tone;             /* tones (equaliser) of B sequences      */
+typedef struct ptts_dynamics ptts_dynamics;     /* dynamics (compressor) of B sequences  */
 typedef struct ptts_encoder ptts_encoder;       /* output encodings of B sequences       */
 typedef struct ptts_flac ptts_flac;             /* output compression of B sequences     */
 
@@ -268,9 +269,9 @@ int ptts_resampler_set_row(ptts_resampler *rs, int32_t row, int32_t rate_index, 
  * ptts_mimi_set_pcm_i16 converts, device or pinned host; then every row's history <- the frame's last 64 samples (a second
  * launch: the blocks of a row read the history concurrently).  out_max = the largest out_n of the rates. */
 int ptts_resample_frame(ptts_resampler *rs, const float *d_pcm_in, void *out, int32_t is_i16, void *stream);
-/* ---- The output chain.  The eight ptts_mimi_set_* below follow one rule, stated here once.  While a stage is set on a
+/* ---- The output chain.  The nine ptts_mimi_set_* below follow one rule, stated here once.  While a stage is set on a
  * state, ptts_mimi_decode and the graph captures append its ptts_*_frame launches behind the codec's last kernel, in the order
- *   resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder -> packer
+ *   resampler -> stretcher -> pitcher -> toner -> compressor -> normaliser -> leveler -> encoder -> packer
  * whichever of them are set.  d_in == NULL: the stage reads d_pcm (which must then be device memory; NULL = the state's own
  * buffer), and its input width must be frame_samples.  Otherwise it reads the f32 device buffer d_in [B, its input width],
  * which the caller has given the stage before it as its `out`; some stage of an earlier kind must be set on the state at
@@ -431,6 +432,32 @@ int ptts_tone_frame(ptts_tone *tn, const float *d_in, float *d_out, void *stream
 /* The output chain's rule (ptts_mimi_set_resampler).  Its own: d_out is f32 device memory and not d_in (-1), and the caller
  * gives it to the normaliser or the leveler as its d_in: a frame enqueued with a toner but no leveler fails (-1). */
 int ptts_mimi_set_tone(ptts_mimi_state *s, ptts_tone *tn, float *d_in, float *d_out);
+/* ---- Dynamics (no reference counterpart).  A compressor holds, for B sequences, a table of plans, each row's plan and
+ * streaming state; it turns one frame f32[B, width] of the previous output stage (row b's n samples at the front of its
+ * line) into d_out f32[B, width] with row b's n samples at the front of its line (the rest of the line is neither read nor
+ * written).  A plan is a log-domain feed-forward compressor with a soft knee and a decoupled smooth peak detector, in float64,
+ * y rounded to f32 once; no look-ahead, no lag, no pre-roll, no drain flag (contract, grammar and presets:
+ * pocket_tts_amd/dynamics.py).  Plan i is h_plans[2 i ..] = (rate, n) and h_doubles[26 i ..] = T, k = 1 - 1 / ratio, W, M, aA,
+ * aR, followed by the ten powers aA^(chunk 2^j) and the ten powers aR^(chunk 2^j), j = 0 .. 9, chunk = ceil(n / 1024), that
+ * the kernel's two scans use.  A plan is refused (-1) unless 8000 <= rate <= 48000, 1 <= n <= 8192, every double is finite,
+ * T, W and M lie in the ranges of the grammar, 0 <= k < 1, 0 < aA, aR < 1 and every power is in [0, 1): with these every
+ * index the kernel forms is in bounds by construction (csrc/ptts_dyn.h).  The plans are copied to the device once; a row is
+ * dealt one by its index, so a captured graph follows ptts_dynamics_set_row without recapture.  width is `line`, which no
+ * plan's n may exceed (-1), or with line == 0 the largest n of the plans.  Every row starts on bypass: an exact copy of its
+ * whole line, no state.  A row's output depends on its own stream alone, bit for bit: not on its slot, not on the batch. */
+int ptts_dynamics_create(ptts_engine *e, int32_t batch, int32_t line, const int32_t *h_plans, int32_t n_plans,
+                         const double *h_doubles, int64_t n_doubles, ptts_dynamics **out);
+/* after every decode / graph that uses it has finished, and after ptts_mimi_set_dynamics(state, NULL, ..) on its states */
+void ptts_dynamics_destroy(ptts_dynamics *dy);
+/* a new utterance joins `row`: its plan (-1: bypass) from now on; p and s are zeroed.  Stream-ordered on `stream`; captured
+ * graphs pick it up.  -1 for a row or a plan index out of range; nothing is enqueued. */
+int ptts_dynamics_set_row(ptts_dynamics *dy, int32_t row, int32_t plan_index, void *stream);
+/* One frame, one launch: d_in f32[B, width] -> d_out f32[B, width], both DEVICE memory and distinct (-1 otherwise); then
+ * the rows' states advance. */
+int ptts_dynamics_frame(ptts_dynamics *dy, const float *d_in, float *d_out, void *stream);
+/* The output chain's rule (ptts_mimi_set_resampler).  Its own: d_out is f32 device memory and not d_in (-1), and the caller
+ * gives it to the normaliser or the leveler as its d_in: a frame enqueued with a compressor but no leveler fails (-1). */
+int ptts_mimi_set_dynamics(ptts_mimi_state *s, ptts_dynamics *dy, float *d_in, float *d_out);
 /* ---- Output encoding (no reference counterpart).  An encoder holds, for B sequences, each row's number of samples n and
  * encoding code: 0 pcm_s16le, 1 pcm_f32le, 2 mulaw, 3 alaw (contract: pocket_tts_amd/encoding.py).  It turns one frame
  * f32[B, width] of the previous output stage (row b's n samples at the front of its line) into out_bytes u8[B, pitch],

@@ -156,6 +156,12 @@ PROTOTYPES = {
     "ptts_tone_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ptts_tone_frame": (C.c_int, [_P, _P, _P, _P]),
     "ptts_mimi_set_tone": (C.c_int, [_P, _P, _P, _P]),
+    "ptts_dynamics_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double),
+                                       C.c_int64, C.POINTER(_P)]),
+    "ptts_dynamics_destroy": (None, [_P]),
+    "ptts_dynamics_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_dynamics_frame": (C.c_int, [_P, _P, _P, _P]),
+    "ptts_mimi_set_dynamics": (C.c_int, [_P, _P, _P, _P]),
     "ptts_encoder_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "ptts_encoder_destroy": (None, [_P]),
     "ptts_encoder_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
@@ -203,9 +209,10 @@ def build(force: bool = False, verbose: bool = False) -> Path:
       * ptts_dispatch.hip = the GEMM / attention dispatchers and the tuner, the only unit that instantiates the round-1/2
         kernel templates;
       * ptts_debug.hip = the C ABI's test hooks;
-      * the eight stages of the output chain, in its order (`output_chain.py`), each with its own part of the C ABI:
+      * the nine stages of the output chain, in its order (`output_chain.py`), each with its own part of the C ABI:
         ptts_resample.hip = the output-rate resampler, ptts_stretch.hip = the speaking-rate time-stretch, ptts_pitch.hip =
-        the pitch shifter, ptts_tone.hip = the equaliser, ptts_loud.hip = the loudness normaliser, ptts_level.hip = the
+        the pitch shifter, ptts_tone.hip = the equaliser, ptts_dyn.hip = the compressor, ptts_loud.hip = the loudness
+        normaliser, ptts_level.hip = the
         output gain with its peak limiter, ptts_encode.hip = the output encoder (16-bit and float PCM, G.711) and
         ptts_flac.hip = the packer (FLAC frames); how they are wired behind the codec is ptts.hip's (its section "the output
         chain");

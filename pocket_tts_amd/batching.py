@@ -31,9 +31,9 @@ The stretcher, the pitcher, the normaliser and the leveler lag, so their rows ar
 rule of `output_chain.py`): a request of F frames delivers exactly F * n_out samples, the scheduler drops the row's pre-roll,
 the sum of its stages' pre-rolls, sets the row to drain at its first lagging stage before the first codec frame past the
 request's last one is queued, and holds the slot for ceil(pre-roll / n_out) drain frames.  To know that frame in time it reads
-the EOS flags of such a row no later than `frames_after_eos` steps behind.  The resampler, the toner and the encoder do not
-lag: the toner has a state but no drain flag, the zeros of a draining row ring out through it, and a toned row lags by the
-limiter behind it like a levelled one.  The normaliser's measurement restarts with every text chunk, so the chunks of a long
+the EOS flags of such a row no later than `frames_after_eos` steps behind.  The resampler, the toner, the compressor and the
+encoder do not lag: the toner and the compressor have a state but no drain flag, the zeros of a draining row ring out through
+them, and a toned or compressed row lags by the limiter behind it like a levelled one.  The normaliser's measurement restarts with every text chunk, so the chunks of a long
 request are normalised one by one.
 """
 
@@ -157,7 +157,7 @@ class ContinuousBatcher:
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
 
         The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`,
-        `tones`, `compressions`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
+        `tones`, `compressions`, `dynamics`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
         `ChainTable.route` (`submit`).  `encodings` needs `pcm_format` left at its default (ValueError).  Without any of them
         every request gets the codec's samples in `pcm_format`, with the same graphs and buffers as before.
 
@@ -201,7 +201,7 @@ class ContinuousBatcher:
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
                                  mode="events", pcm_i16=(pcm_format == "i16"), spec=spec)
         self.chain = self.pipe.chain
-        self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
+        self.rs, self.ts, self.ps, self.tn, self.dy, self.ln, self.lv, self.en = self.chain.per_kind()
         self.pk = self.chain.pk  # with the packer a ring line begins with a prefix that says how many bytes follow
         # the output chain has a stage that may lag
         self.lagging = self.ts is not None or self.ps is not None or self.lv is not None
@@ -255,9 +255,9 @@ class ContinuousBatcher:
         `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.
 
         `**request`: the request's way through the output chain, the fields of `ChainTable.route` (`sample_rate`, `speed`,
-        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`, `compression`), checked against the batcher's table: ValueError
-        for what it refuses, TypeError for another name.  A request whose row lags (a speed, a pitch, a loudness target, a
-        tone or a gain) needs frames_after_eos >= 1."""
+        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`, `compression`, `dynamics`), checked against the batcher's table:
+        ValueError for what it refuses, TypeError for another name.  A request whose row lags (a speed, a pitch, a loudness
+        target, a tone, a compressor setting or a gain) needs frames_after_eos >= 1."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
@@ -312,7 +312,7 @@ class ContinuousBatcher:
                 m.model_recommended_frames_after_eos if m.model_recommended_frames_after_eos is not None else guess + 2)
             for lags, what in ((route.stretched, "a speed"), (route.pitched, "a pitch"),
                                (route.loud is not None, "a loudness target"), (route.toned, "a tone"),
-                               (route.level is not None, "a gain")):
+                               (route.dynamic, "a compressor setting"), (route.level is not None, "a gain")):
                 if lags and fae < 1:
                     raise ValueError(f"a request with {what} needs frames_after_eos >= 1: the row is set to drain before the "
                                      "frame that follows its last one is queued")

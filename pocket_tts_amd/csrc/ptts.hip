@@ -2203,6 +2203,8 @@ static const ChainKind kChain[CH_N] = {
      GET(ptts_pitcher, pitch_width), ENQ(ptts_pitcher, pitch_enqueue(st, stage, in, out, i16, nullptr, nullptr))},
     {"set_tone", "toner", "tone", true, GET(ptts_tone, tone_batch), GET(ptts_tone, tone_width), GET(ptts_tone, tone_width),
      ENQ(ptts_tone, tone_enqueue(st, stage, in, (float *)out))},
+    {"set_dynamics", "compressor", "dynamics", true, GET(ptts_dynamics, dyn_batch), GET(ptts_dynamics, dyn_width),
+     GET(ptts_dynamics, dyn_width), ENQ(ptts_dynamics, dyn_enqueue(st, stage, in, (float *)out))},
     {"set_loudnorm", "normaliser", "loudnorm", true, GET(ptts_loudnorm, loud_batch), GET(ptts_loudnorm, loud_width),
      GET(ptts_loudnorm, loud_width), ENQ(ptts_loudnorm, loud_enqueue(st, stage, in, (float *)out, nullptr))},
     {"set_leveler", "leveler", "level", false, GET(ptts_leveler, level_batch), GET(ptts_leveler, level_width),
@@ -2281,6 +2283,11 @@ extern "C" int ptts_mimi_set_tone(ptts_mimi_state *s, ptts_tone *tn, float *d_in
   return set_link(s, CH_TN, tn, d_in, d_out, 0);
 }
 
+// a frame enqueued with a compressor but no leveler fails
+extern "C" int ptts_mimi_set_dynamics(ptts_mimi_state *s, ptts_dynamics *dy, float *d_in, float *d_out) {
+  return set_link(s, CH_DY, dy, d_in, d_out, 0);
+}
+
 // a frame enqueued with a normaliser but no leveler fails
 extern "C" int ptts_mimi_set_loudnorm(ptts_mimi_state *s, ptts_loudnorm *ln, float *d_in, float *d_out) {
   return set_link(s, CH_LN, ln, d_in, d_out, 0);
@@ -2321,6 +2328,7 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
   const ChainLink *c = s->chain, &ts = c[CH_TS], &en = c[CH_EN];
   if (c[CH_LN].stage && !c[CH_LV].stage) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
   if (c[CH_TN].stage && !c[CH_LV].stage) return fail(-1, "the toner must be followed by a leveler, but the state has none");
+  if (c[CH_DY].stage && !c[CH_LV].stage) return fail(-1, "the compressor must be followed by a leveler, but the state has none");
   const int before = en.stage ? before_encoder(s) : -1;
   if (en.stage && (before >= 0) != (en.in != nullptr))
     return fail(-1, "the encoder's input buffer and the state's output stages do not go together");

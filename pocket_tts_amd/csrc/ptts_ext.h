@@ -73,6 +73,14 @@ int tone_enqueue(hipStream_t st, ptts_tone *tn, const float *d_in, float *d_out)
 int tone_batch(const ptts_tone *tn);
 int tone_width(const ptts_tone *tn);
 
+// ---- ptts_dyn.hip: per-request dynamics (a streaming feed-forward compressor, between the toner and the normaliser) ------
+// the frame's launch on `st`: d_in f32[B][width] (device) -> d_out f32[B][width] (device, never d_in).  Returns 0 or a
+// negative error code (message recorded).
+struct ptts_dynamics;
+int dyn_enqueue(hipStream_t st, ptts_dynamics *dy, const float *d_in, float *d_out);
+int dyn_batch(const ptts_dynamics *dy);
+int dyn_width(const ptts_dynamics *dy);
+
 // ---- ptts_pitch.hip: per-request pitch (streaming WSOLA + polyphase FIR, between the stretcher and the leveler) ---------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host); d_delta
 // (i32 [B][k_max], or null) and d_mid (f32 [B][mid_max], or null) receive the hops' deltas and the frame's mid samples.

@@ -237,8 +237,9 @@ struct ptts_lm_state {
   float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
 };
 
-// the kinds of output stage in launch order: resampler, stretcher, pitcher, toner, normaliser, leveler, encoder, packer
-enum { CH_RS, CH_TS, CH_PS, CH_TN, CH_LN, CH_LV, CH_EN, CH_PK, CH_N };
+// the kinds of output stage in launch order: resampler, stretcher, pitcher, toner, compressor, normaliser, leveler, encoder,
+// packer
+enum { CH_RS, CH_TS, CH_PS, CH_TN, CH_DY, CH_LN, CH_LV, CH_EN, CH_PK, CH_N };
 struct ChainLink {
   void *stage = nullptr;
   float *in = nullptr;

@@ -226,9 +226,9 @@ class MimiState:
 
     def _set_stage(self, kind, stage, out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
         """The decodes / graph captures issued after this call run `stage`, an output stage of the class `kind`, behind the
-        codec's last kernel, at its place in the chain resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler ->
-        encoder (`output_chain.py`; the C side is `kind._attach` of include/ptts.h).  It writes `out`: [B, its output width],
-        float32 or int16, device or pinned host; float32 on the device for the toner and the normaliser, which a leveler
+        codec's last kernel, at its place in the chain resampler -> stretcher -> pitcher -> toner -> compressor ->
+        normaliser -> leveler -> encoder (`output_chain.py`; the C side is `kind._attach` of include/ptts.h).  It writes `out`: [B, its output width],
+        float32 or int16, device or pinned host; float32 on the device for the toner, the compressor and the normaliser, which a leveler
         must follow; uint8 [B, en.pitch] for the encoder.  `mid` None: it reads the frame's PCM, which must then be a DEVICE
         tensor.  Otherwise it reads the float32 device tensor `mid` [B, its input width], which the caller has given the
         stage before it as its `out`; that stage must be set on this state already, so stages are set in chain order.  A
@@ -257,6 +257,9 @@ class MimiState:
 
     def set_tone(self, tn: "Toner | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
         self._set_stage(Toner, tn, out, mid)
+
+    def set_dynamics(self, dy: "Dynamics | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
+        self._set_stage(Dynamics, dy, out, mid)
 
     def set_loudnorm(self, ln: "Normalizer | None", out: torch.Tensor | None = None, mid: torch.Tensor | None = None):
         self._set_stage(Normalizer, ln, out, mid)
@@ -718,6 +721,52 @@ class Toner(_Stage):
         self._frame(self.engine.lib.ptts_tone_frame, x, out, stream)
 
 
+class Dynamics(_Stage):
+    """Dynamics of `batch` sequences (include/ptts.h: ptts_dynamics; contract, grammar and plan rule: `dynamics.py`).
+    `plans` is a list of `dynamics.DynPlan`; a row is dealt a plan by its index (`set_row`; None: bypass) and starts on
+    bypass.  `frame(x, out)` turns one frame x[b, :n(plan of b)] into out[b, :n(plan of b)] through the plan's compressor,
+    with no lag; the detector's two values are carried from frame to frame.  A bypass row's whole line is copied.  `width`
+    is the line's width, the largest n of the plans where it is left out.  The output is always float32 on the device: the
+    stage is never the last one."""
+
+    _name, _field, _destroy, _attach = "compressor", "dynamics", "ptts_dynamics_destroy", "ptts_mimi_set_dynamics"
+    _i16, _check_written = False, _Stage._check_in
+    _route_args = staticmethod(lambda r: (r.dyn_plan,))
+
+    def __init__(self, engine: "Engine", batch: int, plans, width: int | None = None):
+        super().__init__(engine, batch)
+        self.plans = list(plans)
+        self.width = max(p.n for p in self.plans) if width is None else int(width)
+        self.in_max = self.out_max = self._in_width = self._out_width = self.width
+        self.row_plan = [-1] * batch  # host mirror of the rows' plan indices
+        n = len(self.plans)
+        ints = (C.c_int32 * (2 * n))(*[v for p in self.plans for v in p.ints()])
+        doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
+        h = C.c_void_p()
+        _lib.check(engine.lib.ptts_dynamics_create(engine.handle, batch, self.width, ints, n,
+                                                   doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size, C.byref(h)))
+        self.handle = h
+        engine._states.add(self)
+
+    def _row_args(self, row):
+        return (self.row_plan[row],)
+
+    def set_row(self, row: int, plan_index: int | None = None, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` with a zero state; None or -1: the row bypasses the stage.
+        Stream-ordered"""
+        idx = -1 if plan_index is None else int(plan_index)
+        if not -1 <= idx < len(self.plans):
+            raise ValueError(f"compressor plan index {plan_index!r} out of range")
+        _lib.check(self.engine.lib.ptts_dynamics_set_row(self.handle, int(row), idx, self._sp(stream)))
+        self.row_plan[row] = idx
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] -> out f32[B, width], both on the device and distinct"""
+        self._check_in(x)
+        self._check_in(out)
+        self._frame(self.engine.lib.ptts_dynamics_frame, x, out, stream)
+
+
 class Resampler(_Stage):
     """Output sample rates of `batch` sequences (include/ptts.h: ptts_resampler; filters and admission rules:
     `resample.py`).  `rates[0]` is always the codec's native rate - what a row without a rate of its own runs at - followed
@@ -1027,6 +1076,9 @@ class Engine:
 
     def new_toner(self, batch: int, plans, width: int | None = None) -> Toner:
         return Toner(self, batch, plans, width)
+
+    def new_dynamics(self, batch: int, plans, width: int | None = None) -> Dynamics:
+        return Dynamics(self, batch, plans, width)
 
     def new_encoder(self, batch: int, width: int) -> Encoder:
         return Encoder(self, batch, width)
@@ -1407,9 +1459,9 @@ class StepPipeline:
       of a forked graph do not run concurrently).
 
     The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`, `tones`,
-    `compressions`; as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
+    `compressions`, `dynamics`; as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
     "fork" mode): the codec graphs end with its stages' launches.  `chain` holds the plan table (`chain.table`) and the
-    stage objects, also here as `rs`, `ts`, `ps`, `tn`, `ln`, `lv` and `en`.  `pcm[p]` are then DEVICE tensors and the
+    stage objects, also here as `rs`, `ts`, `ps`, `tn`, `dy`, `ln`, `lv` and `en`.  `pcm[p]` are then DEVICE tensors and the
     samples reach the host through `out[p]`, the chain's pinned ring, int16 with `pcm_i16`, else float32:
     `out_of(frame)[b, :route.n_out]` is row b's frame, `pcm_of` / `pcm16_of` raise.  With the encoder (not with `pcm_i16`)
     `out[p]` are pinned uint8 tensors and `out_of(frame)[b, : route.n_out * route.bytes_per_sample]` are row b's bytes in
@@ -1432,7 +1484,7 @@ class StepPipeline:
         # the plan table first: what the rules refuse is refused before anything is allocated
         table = ChainSpec.of(spec, **chain).table(eng.sample_rate, eng.frame_samples)
         if not table.empty and self.mode == "fork":
-            raise ValueError("sample_rates / speeds / pitches / tones / loudness / level / encodings: not available in the "
+            raise ValueError("sample_rates / speeds / pitches / tones / dynamics / loudness / level / encodings: not available in the "
                              "'fork' mode")
         # ring of output buffers (latent -> codec input, EOS flags, PCM).  Throughput mode keeps 4 so that the FlowLM
         # stream may run up to 3 steps ahead of the codec stream (with 2 the two streams move in lock-step and every
@@ -1441,7 +1493,7 @@ class StepPipeline:
         self.nb = nb = self.NB_EVENTS if self.mode == "events" else 2
         self.chain = OutputChain(eng, B, table, nb, pcm_i16)
         self.out = self.chain.out
-        self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en = self.chain.per_kind()
+        self.rs, self.ts, self.ps, self.tn, self.dy, self.ln, self.lv, self.en = self.chain.per_kind()
         self.pk = self.chain.pk
         self.lat = [torch.zeros(B, eng.ldim, device=dev) for _ in range(nb)]
         self.logit = [torch.empty(B, device=dev) for _ in range(nb)]

@@ -18,7 +18,8 @@ BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--pea
 `--encodings mulaw,alaw,pcm_f32le` a per-request `encoding` (G.711 or float samples, encoded on the GPU, encoding.py;
 `generate --sample-rate 8000 --encoding mulaw` is the same for one text) and `container=raw` for the bytes without a WAV
 header, and with `--tones telephone,warm,"hp:120;peak:3000:4"` a per-request `tone` (a parametric equaliser on the GPU,
-tone.py; `generate --tone telephone` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
+tone.py; `generate --tone telephone` is the same for one text), and with `--dynamics speech,"threshold=-24;ratio=4"` a
+per-request `dynamics` (a speech compressor on the GPU, dynamics.py; `generate --dynamics speech`).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -38,7 +39,7 @@ DEFAULT_TEXT = ("Hello world. I am Kyutai's Pocket TTS. I'm fast enough to run o
 # the flags behind each request field of `ChainTable.for_request`, as `generate` names them when a rule refuses one
 FLAGS = dict(sample_rate="--sample-rate", speed="--speed", pitch="--pitch / --pitch-semitones", tone="--tone",
              loudness_lufs="--loudness-lufs / --peak-dbfs", gain_db="--gain-db / --peak-dbfs", encoding="--encoding",
-             compression="--compression")
+             compression="--compression", dynamics="--dynamics")
 
 _STREAM_FRAMES = 1_000_000_000  # streaming: the length is not known up front, the header announces this many samples
 
@@ -194,6 +195,19 @@ def parse_tone_list(text: str) -> list:
     return names
 
 
+def parse_dynamics_list(text: str) -> list:
+    """"speech,threshold=-24;ratio=4" -> ["speech", "threshold=-24;ratio=4"] (the `serve --dynamics` value): settings are
+    joined by commas, the pairs of one setting by semicolons"""
+    from .dynamics import normalise_dynamics
+
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    try:
+        normalise_dynamics(names)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return names
+
+
 def parse_rate_list(text: str) -> list:
     """"8000,16000,48000" -> [8000, 16000, 48000] (the `serve --sample-rates` value)"""
     try:
@@ -265,7 +279,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "equalised on the GPU, with the peak limiter behind it (default: none)")
     g.add_argument("--peak-dbfs", type=float, default=None,
                    help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db, "
-                        "--loudness-lufs or --tone")
+                        "--loudness-lufs, --tone or --dynamics")
+    g.add_argument("--dynamics", default=None, metavar="SETTING",
+                   help="Dynamics: a compressor preset (speech, gentle, broadcast, telephone) or key=value pairs joined by ';' "
+                        "with the keys threshold, ratio, knee, attack, release, makeup, e.g. \"threshold=-24;ratio=4\": "
+                        "compressed on the GPU behind the tone and in front of the loudness measurement, with the peak "
+                        "limiter behind (default: none)")
     g.add_argument("--encoding", default=None, choices=["pcm_s16le", "pcm_f32le", "mulaw", "alaw"],
                    help="Sample encoding of the WAV, encoded on the GPU: 16-bit PCM, 32-bit float, or ITU-T G.711 mu-law / A-law "
                         "(telephony; use it with --sample-rate 8000).  Default: 16-bit PCM, converted on the host")
@@ -314,6 +333,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Tones a request may choose with the form field tone: presets or band lists, e.g. "
                         "telephone,warm,hp:120;peak:3000:4 (bands are joined by ';', tones by ','); equalised on the GPU, with "
                         "the peak limiter behind")
+    s.add_argument("--dynamics", type=parse_dynamics_list, default=None, metavar="S1,S2,...",
+                   help="Compressor settings a request may choose with the form field dynamics: presets or key=value lists, "
+                        "e.g. speech,threshold=-24;ratio=4 (pairs are joined by ';', settings by ','); compressed on the GPU, "
+                        "with the peak limiter behind")
     s.add_argument("--level", action="store_true",
                    help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
                         "limiter on the GPU)")
@@ -402,7 +425,7 @@ def cli_app(argv=None) -> int:
             pitch, cents = nearest(args.pitch_semitones, *ChainTable.line_of(native, fs, args.sample_rate, args.speed)[2])
             logger.info("--pitch-semitones %g: pitch %s, %+.1f cents from the request", args.pitch_semitones, pitch, cents)
         _, request = ChainTable.for_request(native, fs, args.sample_rate, args.speed, args.gain_db, args.peak_dbfs, pitch,
-                                            args.loudness_lufs, args.encoding, args.tone, args.compression)
+                                            args.loudness_lufs, args.encoding, args.tone, args.compression, args.dynamics)
     except ValueError as e:  # a `RequestError` names its field; the others are those of the two pitch flags above
         logger.error("%s: %s", FLAGS[getattr(e, "field", "pitch")], e)
         return 1

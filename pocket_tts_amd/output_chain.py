@@ -4,17 +4,17 @@ the stage objects and buffers on the device (`OutputChain`).
 
 The order, which is also the launch order behind the codec's last kernel:
 
-    codec -> resampler -> stretcher -> pitcher -> toner -> normaliser -> leveler -> encoder -> packer
+    codec -> resampler -> stretcher -> pitcher -> toner -> compressor -> normaliser -> leveler -> encoder -> packer
 
-A pipeline has any subset of the eight stages; the toner and the normaliser bring the leveler with them, the packer the
-encoder.  The buffer rule: the first stage present reads the frame's PCM; between two consecutive stages present there is one
+A pipeline has any subset of the nine stages; the toner, the compressor and the normaliser bring the leveler with them, the
+packer the encoder.  The buffer rule: the first stage present reads the frame's PCM; between two consecutive stages present there is one
 device buffer [batch, input width of the later one], which must be the output width of the earlier one, f32 but for the
 encoder's bytes before the packer, which are uint8 [batch, encoding.pitch(width)]; the last stage writes the pinned ring.
 
-The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `tone.py`, `loudness.py` and
-`level.py`: it needs no library, no GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
+The first half is pure Python over the rule modules `resample.py`, `stretch.py`, `pitch.py`, `tone.py`, `dynamics.py`,
+`loudness.py` and `level.py`: it needs no library, no GPU and no device memory.  Everything a caller has to know about a row - its plan indices, how many samples a frame
 yields, how many leading samples to drop, how many drain frames flush its tail and which stage's drain flag to raise - is a
-`Route`; nothing outside this module composes the six plan rules.
+`Route`; nothing outside this module composes the seven plan rules.
 
 The drain rule: a row's pre-roll is the SUM of its stages' pre-rolls (the stretcher's and the pitcher's, 0 on an identity plan,
 plus the normaliser's delay and the leveler's look-ahead, each 0 on bypass), it delivers the samples [preroll, preroll + frames * n_out) of its line and needs
@@ -26,6 +26,10 @@ else through the normaliser's where the row has a loudness target, else through 
 The toner (`tone.py`) sits between the pitcher and the normaliser.  It has state but no lag and no drain flag: it adds nothing
 to a row's pre-roll, the zeros of a draining row ring out through it, and `drain_stage` never names it.  A toned row always
 runs the limiter behind it, because a boost creates peaks; so its pre-roll is what the stages behind the tone add.
+
+The compressor (`dynamics.py`) sits between the toner and the normaliser, so that the loudness is measured on what the
+listener hears.  Like the toner it has state but no lag and no drain flag, adds nothing to a row's pre-roll, and a row with
+a setting always runs the limiter behind it, which catches what the make-up gain and the attack time let through.
 
 The encoder (`encoding.py`) is the last stage where a table has one.  It has no state and no lag: it adds nothing to a row's
 pre-roll, and the zeros of a draining row reach it like any other sample.  Everything above counts samples; only the ring the
@@ -44,6 +48,7 @@ from dataclasses import dataclass
 
 from . import encoding as encoding_rule
 from . import flac as flac_rule
+from . import dynamics as dyn_rule
 from . import level as level_rule
 from . import loudness as loud_rule
 from . import pitch as pitch_rule
@@ -70,7 +75,8 @@ class Route:
     normaliser, loudness_lufs), None for bypass; `encoding`: the name of the row's output encoding, None on a table without
     the encoder, and `bytes_per_sample`: what a sample of it takes in the encoder's ring (None likewise: the ring's dtype
     says); `tone_plan`: its plan index in the toner (None: bypass, or no toner), `toned`: it has one;
-    `compression`: None or "flac", the row's lines leave the packer as FLAC frames."""
+    `compression`: None or "flac", the row's lines leave the packer as FLAC frames; `dyn_plan`: its plan index in the
+    compressor (None: bypass, or no compressor), `dynamic`: it has one."""
 
     rate_index: int
     rate: int
@@ -89,6 +95,8 @@ class Route:
     tone_plan: int | None = None
     toned: bool = False
     compression: str | None = None
+    dyn_plan: int | None = None
+    dynamic: bool = False
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -117,9 +125,9 @@ def _ask(field: str, rule, *args):
 
 @dataclass(frozen=True)
 class ChainSpec:
-    """What a pipeline's output chain is built with: the eight options that `StepPipeline`, `ContinuousBatcher` and
-    `server.create_app` take as keywords, one per stage but the leveler's, which three bring.  The default of each is "that
-    stage does not exist": with all eight nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
+    """What a pipeline's output chain is built with: the nine options that `StepPipeline`, `ContinuousBatcher` and
+    `server.create_app` take as keywords, one per stage but the leveler's, which four bring.  The default of each is "that
+    stage does not exist": with all nine nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
     spec is hashable.
 
     `sample_rates`: the output rates a row may choose besides the native one, each a rate `resample.plan` admits, e.g. [8000,
@@ -139,6 +147,8 @@ class ChainSpec:
     parametric equaliser, which brings the leveler with it as its peak limiter.
     `compressions`: the compressions a row may choose, names of `flac.py`, i.e. ["flac"]; the packer ends the chain behind
     the encoder, which it brings with it, and writes ring lines with a length prefix.
+    `dynamics`: the compressor settings a row may choose, presets or key=value lists of `dynamics.py`, e.g. ["speech",
+    "threshold=-24;ratio=4"]; the speech compressor, which brings the leveler with it as its peak limiter.
 
     What the rules refuse raises their ValueError when the table is built (`table`), before anything is allocated."""
 
@@ -150,19 +160,20 @@ class ChainSpec:
     encodings: tuple | None = None
     tones: tuple | None = None
     compressions: tuple | None = None
+    dynamics: tuple | None = None
 
     TAGS = dict(sample_rates="rate", speeds="speed", level="level", pitches="pitch", loudness="loud", encodings="enc",
-                tones="tone", compressions="comp")  # what `tags` calls each option
+                tones="tone", dynamics="dyn", compressions="comp")  # what `tags` calls each option
 
     def __post_init__(self):
-        for name in ("sample_rates", "speeds", "pitches", "encodings", "tones", "compressions"):
+        for name in ("sample_rates", "speeds", "pitches", "encodings", "tones", "compressions", "dynamics"):
             v = getattr(self, name)
             if v is not None and not isinstance(v, (tuple, str)):  # a string is no list: the rules say so
                 object.__setattr__(self, name, tuple(v))
 
     @classmethod
     def of(cls, spec=None, **chain):
-        """`spec`, or the spec of the eight options given as keywords; TypeError for another keyword, or for both"""
+        """`spec`, or the spec of the nine options given as keywords; TypeError for another keyword, or for both"""
         if spec is None:
             return cls(**chain)
         if chain:
@@ -176,7 +187,7 @@ class ChainSpec:
         """The stages of the spec as the words that tell cached contexts apart: each option that is set as its tag in
         `TAGS`, a list other than the encoder's and the packer's followed by its values.  ("rate", 8000, "level", "enc") is a resampler to 8
         kHz, the leveler and the encoder: a context serves every gain, ceiling and target and all encodings, but one list
-        of rates, speeds, pitches and tones."""
+        of rates, speeds, pitches, tones and compressor settings."""
         out = []
         for name, tag in self.TAGS.items():
             v = getattr(self, name)
@@ -192,7 +203,9 @@ class ChainTable:
     / `pitch_index[(rate, n)][pitch index]` (`pitch.table` over every (rate, samples per frame) the rates x speeds can
     produce), with `tones` the toner's `tone_plans` / `tone_index[(rate, n)][tone index]` (`tone.table` over the same lines,
     None where the rate refuses a tone) and `tones`, the configured list in canonical form, with `loudness` the normaliser's
-    `loud_plans` / `loud_index[(rate, n)]` (`loudness.table`), and with `level`, `loudness` or `tones` the leveler's
+    `loud_plans` / `loud_index[(rate, n)]` (`loudness.table`), with `dynamics` the compressor's `dyn_plans` /
+    `dyn_index[(rate, n)][setting index]` (`dynamics.table` over the same lines) and `dynamics`, the configured list in
+    canonical form, and with `level`, `loudness`, `tones` or `dynamics` the leveler's
     `level_plans` / `level_index[(rate, n)]` (`level.table`).  With `encodings` the chain ends with the encoder and
     `encodings` is the configured list, `pcm_s16le` first; a list makes the table non-empty even when the encoder is the only
     stage.  With `compressions` it ends with the packer behind the encoder (which the option brings: `encodings` is then at
@@ -201,7 +214,7 @@ class ChainTable:
     device tables, so the order is part of the contract."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None, tones=None, compressions=None):
+                 pitches=None, loudness: bool = False, encodings=None, tones=None, compressions=None, dynamics=None):
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
@@ -224,10 +237,14 @@ class ChainTable:
             if not self.tones:
                 raise ValueError("tones: the list holds no tone but the bypass, which every request has anyway")
             self.tone_plans, self.tone_index = tone_rule.table(lines, self.tones)
+        self.dynamics = None if dynamics is None else dyn_rule.normalise_dynamics(dynamics)
+        self.dyn_plans = self.dyn_index = None
+        if self.dynamics is not None:
+            self.dyn_plans, self.dyn_index = dyn_rule.table(lines, self.dynamics)
         self.loud_plans = self.loud_index = None
         if loudness:
             self.loud_plans, self.loud_index = loud_rule.table(lines)
-        if level or loudness or self.tones is not None:
+        if level or loudness or self.tones is not None or self.dynamics is not None:
             self.level_plans, self.level_index = level_rule.table(lines)
         self.compressions = None if compressions is None else flac_rule.normalise_compressions(compressions)
         if self.compressions is not None:
@@ -256,9 +273,13 @@ class ChainTable:
         """the configured tones admissible on frames of `n` samples at `rate` Hz"""
         return [t for j, t in enumerate(self.tones) if self.tone_index[(rate, n)][j] is not None]
 
+    def dynamics_of(self, rate: int, n: int) -> list:
+        """the configured compressor settings admissible on frames of `n` samples at `rate` Hz"""
+        return [s for j, s in enumerate(self.dynamics) if self.dyn_index[(rate, n)][j] is not None]
+
     def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None,
-              encoding=None, tone=None, compression=None) -> Route:
-        """The `Route` of a request.  Its nine fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
+              encoding=None, tone=None, compression=None, dynamics=None) -> Route:
+        """The `Route` of a request.  Its ten fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
         `generate_audio_stream` take as keywords and hand on as they came; None is always "as without the stage":
 
         `sample_rate`: the rate of the request's audio, the native one (None) or one of the configured; a frame then yields
@@ -272,17 +293,22 @@ class ChainTable:
         "hp:120;peak:3000:4" (at most eight biquad sections, none above 0.45 x the rate), compared in the canonical form of
         `tone.normalise`; None, "" or "flat": bypass.  A toned request runs the limiter behind it, at gain 0 dB under its
         `peak_dbfs` unless it has a gain or a target, with both of which it combines freely.
+        `dynamics`: a compressor preset, "speech", "gentle", "broadcast" or "telephone", or a key=value list such as
+        "threshold=-24;ratio=4" (keys threshold, ratio, knee, attack, release, makeup; what is left out is that of `speech`),
+        compared in the canonical form of `dynamics.normalise`; None, "" or "off": bypass.  The compressor sits behind the
+        tone and in front of the loudness measurement; such a request runs the limiter behind it, like a toned one.
         `loudness_lufs`: a loudness target in [-40, -10], e.g. -16 or -23.  The gain follows the running gated BS.1770
         loudness of the text chunk so far, clamped to +-20 dB, 400 ms late, with the limiter at `peak_dbfs` behind it; it
         excludes `gain_db`.  Each text chunk is measured on its own, so the gain can differ between the chunks of a long text.
-        `gain_db` (in [-40, 24]) and `peak_dbfs` (in [-20, 0], default -1, only together with a gain, a target or a tone):
+        `gain_db` (in [-40, 24]) and `peak_dbfs` (in [-20, 0], default -1, only together with a gain, a target, a tone or a compressor
+        setting):
         the samples are amplified and peak-limited to 10^(peak_dbfs / 20).  0 is not None: it limits at the ceiling.
         `encoding`: "pcm_s16le" (None on a table with the encoder), "pcm_f32le", "mulaw" or "alaw", among the configured:
         the chunks are int16, float32 or uint8 (ITU-T G.711) tensors, one element per sample.
         `compression`: "flac" where configured, only with `encoding` None or "pcm_s16le" and on a line `flac.plan` admits:
         the chunks are uint8 tensors, one whole FLAC frame each, which decode to the samples "pcm_s16le" would deliver.
 
-        A stage that lags (all but the resampler, the toner and the encoder) delays the output, not the count: the samples
+        A stage that lags (all but the resampler, the toner, the compressor and the encoder) delays the output, not the count: the samples
         delivered in all stay those of the same request without it (the drain rule of the module's docstring).  ValueError for
         a value that is not configured, that a rule refuses on the request's line (the message lists what it admits there),
         and for any but None on a table without that stage (the message names the option to build it with)."""
@@ -331,6 +357,20 @@ class ChainTable:
                     gain_db = 0.0  # the limiter behind the tone
         elif canon is not None:
             raise ValueError(f"tone {tone!r}: this batcher has no tone stage (build it with tones for per-request tones)")
+        dplan, canon = None, dyn_rule.normalise(dynamics)
+        if self.dynamics is not None:
+            if canon is not None:
+                if canon not in self.dynamics:
+                    raise ValueError(f"dynamics {dynamics!r} is not configured (this pipeline has {self.dynamics})")
+                dplan = self.dyn_index[(rate, n_out)][self.dynamics.index(canon)]
+                if dplan is None:
+                    raise ValueError(f"dynamics {dynamics!r} is not admissible at {rate} Hz (admissible there: "
+                                     f"{self.dynamics_of(rate, n_out)})")
+                if gain_db is None and loudness_lufs is None:
+                    gain_db = 0.0  # the limiter behind the compressor
+        elif canon is not None:
+            raise ValueError(f"dynamics {dynamics!r}: this batcher has no dynamics stage (build it with dynamics for "
+                             "per-request dynamics)")
         lvl = loud = None
         if self.loud_plans is not None:
             target = loud_rule.check_with(loudness_lufs, gain_db)
@@ -363,7 +403,7 @@ class ChainTable:
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
                      "stretch" if stretched else "pitch" if pitched else "loud" if loud is not None
                      else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps, tplan, tplan is not None,
-                     compression)
+                     compression, dplan, dplan is not None)
 
     @staticmethod
     def line_of(native_rate: int, frame_samples: int, sample_rate=None, speed=None):
@@ -384,12 +424,12 @@ class ChainTable:
 
     @staticmethod
     def for_request(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
-                    pitch=None, loudness_lufs=None, encoding=None, tone=None, compression=None):
+                    pitch=None, loudness_lufs=None, encoding=None, tone=None, compression=None, dynamics=None):
         """One request that gets a chain of its own (the fields of `route`): (spec, request), the `ChainSpec` of exactly the
         stages it uses and the request in canonical form, the dict that `spec.table(native_rate, frame_samples).route`
         takes - the native rate, speed 1.0 and pitch 1.0 as None, speed and pitch as the floats of their fractions, the tone
-        as its canonical string, `peak_dbfs` defaulted, and `gain_db` 0.0 behind a tone without a gain or a loudness target
-        of its own.  One walk in chain order over the request's own line, stage by stage through the plan rules themselves,
+        and the compressor setting as their canonical strings, `peak_dbfs` defaulted, and `gain_db` 0.0 behind a tone or a
+        compressor without a gain or a loudness target of its own.  One walk in chain order over the request's own line, stage by stage through the plan rules themselves,
         so a refusal is the rule's: a `RequestError` with its message, whose `field` names the request field at fault."""
         sample_rate, speed, line = ChainTable.line_of(native_rate, frame_samples, sample_rate, speed)
         if pitch is not None:
@@ -399,14 +439,18 @@ class ChainTable:
         if tone is not None:
             _ask("tone", tone_rule.plan, *line, tone)
             _ask("tone", level_rule.plan, *line)
+        dynamics = _ask("dynamics", dyn_rule.normalise, dynamics)
+        if dynamics is not None:
+            _ask("dynamics", dyn_rule.plan, *line, dynamics)
+            _ask("dynamics", level_rule.plan, *line)
         loudness_lufs = _ask("loudness_lufs", loud_rule.check_with, loudness_lufs, gain_db)
         if loudness_lufs is not None:  # the limiter behind the normaliser: no gain of its own, the request's ceiling
             _ask("loudness_lufs", loud_rule.plan, *line)
             _ask("loudness_lufs", level_rule.plan, *line)
             peak_dbfs = _ask("loudness_lufs", level_rule.check, 0.0, peak_dbfs)[1]
         else:
-            if tone is not None and gain_db is None:
-                gain_db = 0.0  # the limiter behind the tone: no gain of its own, the request's ceiling
+            if (tone is not None or dynamics is not None) and gain_db is None:
+                gain_db = 0.0  # the limiter behind the tone or the compressor: no gain of its own, the request's ceiling
             gain_db, peak_dbfs = _ask("gain_db", level_rule.check, gain_db, peak_dbfs)
             if gain_db is not None:
                 _ask("gain_db", level_rule.plan, *line)
@@ -417,17 +461,19 @@ class ChainTable:
             _ask("compression", flac_rule.plan, *line, encoding)
         one = lambda v: None if v is None else (v,)  # noqa: E731
         spec = ChainSpec(one(sample_rate), one(speed), gain_db is not None, one(pitch), loudness_lufs is not None,
-                         None if encoding is None else encoding_rule.NAMES, one(tone), one(compression))
+                         None if encoding is None else encoding_rule.NAMES, one(tone), one(compression), one(dynamics))
         req = dict(sample_rate=sample_rate, speed=speed, gain_db=gain_db, peak_dbfs=peak_dbfs, pitch=pitch,
                    loudness_lufs=loudness_lufs, encoding=encoding, tone=tone)
         if compression is not None:  # only then: a request without it is the dict it always was
             req["compression"] = compression
+        if dynamics is not None:  # likewise
+            req["dynamics"] = dynamics
         return spec, req
 
 
 class OutputChain:
-    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `ln` / `lv` / `en` / `pk`
-    (`engine.Resampler`, `Stretcher`, `Pitcher`, `Toner`, `Normalizer`, `Leveler`, `Encoder`, `Packer`; None where the table has no
+    """The stages of `table` for `batch` rows on `engine`'s device: `rs` / `ts` / `ps` / `tn` / `dy` / `ln` / `lv` / `en` / `pk`
+    (`engine.Resampler`, `Stretcher`, `Pitcher`, `Toner`, `Dynamics`, `Normalizer`, `Leveler`, `Encoder`, `Packer`; None where the table has no
     such stage), the device buffers between them and the pinned ring `out` of `nb` tensors, which the last stage writes.
     The buffer rule of the module's docstring gives them: without the encoder a ring slot is [batch, widest line], int16
     with `pcm_i16`, else float32; on a table with `encodings` it is uint8 [batch, encoding.pitch(widest line)], row b's
@@ -438,7 +484,7 @@ class OutputChain:
     def __init__(self, engine, batch: int, table: ChainTable, nb: int, pcm_i16: bool = False):
         import torch
 
-        from .engine import Encoder, Leveler, Normalizer, Packer, Pitcher, Resampler, Stretcher, Toner
+        from .engine import Dynamics, Encoder, Leveler, Normalizer, Packer, Pitcher, Resampler, Stretcher, Toner
 
         if table.encodings is not None and pcm_i16:
             raise ValueError("pcm_i16 and encodings exclude each other: with encodings a row asks for pcm_s16le itself")
@@ -447,6 +493,7 @@ class OutputChain:
         self.ts = Stretcher(engine, batch, table.stretch_plans) if table.speeds is not None else None
         self.ps = Pitcher(engine, batch, table.pitch_plans) if table.pitches is not None else None
         self.tn = Toner(engine, batch, table.tone_plans, table.width) if table.tone_plans is not None else None
+        self.dy = Dynamics(engine, batch, table.dyn_plans, table.width) if table.dyn_plans is not None else None
         self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
         self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
         self.en = Encoder(engine, batch, table.width) if table.encodings is not None else None
@@ -470,8 +517,8 @@ class OutputChain:
         self.out = [torch.zeros(*shape, dtype=dtype).pin_memory() for _ in range(nb)]
 
     def per_kind(self):
-        """(rs, ts, ps, tn, ln, lv, en) in chain order, None where the table has no such stage; the packer is `pk`"""
-        return self.rs, self.ts, self.ps, self.tn, self.ln, self.lv, self.en
+        """(rs, ts, ps, tn, dy, ln, lv, en) in chain order, None where the table has no such stage; the packer is `pk`"""
+        return self.rs, self.ts, self.ps, self.tn, self.dy, self.ln, self.lv, self.en
 
     def stages(self):
         return list(self._stages)

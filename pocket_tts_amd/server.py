@@ -17,7 +17,10 @@ answers `audio/flac`, lossless frames encoded on the GPU (`flac.py`).  `containe
 encoded samples and the trailing silence as `application/octet-stream`, with the response headers `X-Audio-Encoding` and
 `X-Sample-Rate` - what a media-stream gateway forwards.  On a server started with `tones` the field `tone` chooses one of
 them (`tone.py`: a preset such as `telephone`, or a band list), equalised on the GPU with the peak limiter behind it
-(`peak_dbfs` is then its ceiling); a tone the request's rate does not admit gets a 400 with those it admits.
+(`peak_dbfs` is then its ceiling); a tone the request's rate does not admit gets a 400 with those it admits.  On a server
+started with `dynamics` the field `dynamics` chooses one of its compressor settings (`dynamics.py`: a preset such as
+`speech`, or key=value pairs), compressed on the GPU behind the tone with the peak limiter behind it; a setting that is not
+configured gets a 400 with the list of those that are.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
 `urllib.parse` and the standard library's `email` header parser.
@@ -58,6 +61,8 @@ INDEX_HTML = """<!doctype html>
 <p>Loudness <input name="loudness_lufs" size="5"> LUFS, e.g. -16 or -23, instead of a gain (empty: the model's own level)</p>
 <p>Tone <input name="tone" size="20"> a preset or a band list such as hp:120;peak:3000:4, as far as the server was started
 with it (empty: none)</p>
+<p>Dynamics <input name="dynamics" size="20"> a compressor preset such as speech or pairs such as threshold=-24;ratio=4, as
+far as the server was started with it (empty: none)</p>
 <p>Encoding <input name="encoding" size="10"> pcm_s16le, pcm_f32le, mulaw or alaw, as far as the server was started with
 them (empty: pcm_s16le), container <select name="container"><option>wav</option><option>raw</option></select></p>
 <p><button type="submit">Speak</button></p>
@@ -261,8 +266,30 @@ def parse_tone(fields: dict, rate, speed, table):
     return canon
 
 
+def parse_dynamics(fields: dict, rate, speed, table):
+    """the optional `dynamics` field: the canonical string of one of the configured compressor settings, None where absent,
+    empty or "off".  `table`: the server's `ChainTable`, without dynamics (or None) on a server started without.  FormError
+    with the configured list for a setting that is not configured, with the admissible list for one the request's line
+    refuses, for what the grammar refuses, and for any setting on a server started without dynamics"""
+    from . import dynamics as dyn_rule
+
+    raw = fields.get("dynamics")
+    if raw is None or raw.strip() == "":
+        return None
+    try:
+        canon = dyn_rule.normalise(raw)
+        if canon is None:
+            return None
+        if table is None or table.dynamics is None:
+            raise FormError("dynamics is not available (this server was started without dynamics)")
+        table.route(rate, speed, dynamics=canon)
+    except ValueError as e:
+        raise FormError(str(e)) from None
+    return canon
+
+
 def parse_ceiling(fields: dict):
-    """the optional `peak_dbfs` field of a request with a tone and no gain: the limiter's ceiling, None where absent or empty;
+    """the optional `peak_dbfs` field of a request with a tone or a compressor setting and no gain: the limiter's ceiling, None where absent or empty;
     FormError for a value `level.check` refuses"""
     from . import level
 
@@ -500,11 +527,14 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             tone = parse_tone(fields, settings.get("sample_rate"), settings.get("speed"), table)
             if tone is not None:
                 settings["tone"] = tone
+            dyn = parse_dynamics(fields, settings.get("sample_rate"), settings.get("speed"), table)
+            if dyn is not None:
+                settings["dynamics"] = dyn
             target, ceiling = parse_loudness(fields, loudness)
             if target is not None:
                 settings["loudness_lufs"], settings["peak_dbfs"] = target, ceiling
-            elif tone is not None and not (fields.get("gain_db") or "").strip():
-                ceiling = parse_ceiling(fields)  # the limiter behind the tone: no gain of its own
+            elif (tone is not None or dyn is not None) and not (fields.get("gain_db") or "").strip():
+                ceiling = parse_ceiling(fields)  # the limiter behind the tone or the compressor: no gain of its own
                 if ceiling is not None:
                     settings["peak_dbfs"] = ceiling
             else:
@@ -519,8 +549,8 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             if compressions is not None and container in compressions:
                 settings["compression"] = container
                 # the rule's refusals (an encoding that is not pcm_s16le, a line FLAC does not admit), and the block size
-                route_fields = ("sample_rate", "speed", "pitch", "tone", "loudness_lufs", "gain_db", "peak_dbfs", "encoding",
-                                "compression")
+                route_fields = ("sample_rate", "speed", "pitch", "tone", "dynamics", "loudness_lufs", "gain_db", "peak_dbfs",
+                                "encoding", "compression")
                 try:
                     flac_n = table.route(**{k: settings[k] for k in route_fields if k in settings}).n_out
                 except ValueError as e:

@@ -205,7 +205,7 @@ class TTSModel:
 
         `**request` (not in the reference): the request's way through the output chain on the GPU, the fields of
         `output_chain.ChainTable.route` (`sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
-        `encoding`, `tone`, `compression`), each checked by its rule on the request's own line (`ChainTable.for_request`):
+        `encoding`, `tone`, `compression`, `dynamics`), each checked by its rule on the request's own line (`ChainTable.for_request`):
         ValueError with the rule's message, TypeError for another name.  The chunks then hold what a frame yields at the end
         of the chain, as fp32, or typed as the `encoding`; with `compression="flac"` each chunk is one whole FLAC frame as a
         uint8 tensor, numbered on across the text chunks (`flac.py`; `main.flac_stream_bytes` makes a file of them).  None of
