@@ -35,6 +35,11 @@ the EOS flags of such a row no later than `frames_after_eos` steps behind.  The 
 encoder do not lag: the toner and the compressor have a state but no drain flag, the zeros of a draining row ring out through
 them, and a toned or compressed row lags by the limiter behind it like a levelled one.  The normaliser's measurement restarts with every text chunk, so the chunks of a long
 request are normalised one by one.
+
+The chunks of a long text are independent (each starts from the voice state), so with `parallel_chunks` = W a request runs up
+to W of them at a time in rows of their own (`submit`), and `chunk_order.ChunkOrder` hands their audio to the consumer in text
+order.  `submit_script` makes one request of segments with different voices, and `Request.cancel` takes a request out of
+`waiting` and out of its slots (`_purge`, which a failed request's siblings, `_fail` and `close` go through as well).
 """
 
 from __future__ import annotations
@@ -86,6 +91,19 @@ def eos_bookkeeping_rows(local_step, max_gen_len, frames_after_eos, eos_step, n_
     n_emit[done] = ls[done]
 
 
+def check_parallel_chunks(value, bound: int | None = None) -> int:
+    """`value` as the number of text chunks of one request that may wait or own slots at a time: an integer >= 1, and
+    <= `bound` where one is given; ValueError otherwise (bool and float are refused)"""
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or int(value) < 1:
+        raise ValueError(f"parallel_chunks must be an integer >= 1, got {value!r}")
+    if bound is not None and int(value) > bound:
+        raise ValueError(f"parallel_chunks must be in [1, {bound}] (the batcher's own), got {value!r}")
+    return int(value)
+
+
+_FRAME = object()  # through a request's chunk order: one codec frame of the chunk has been delivered (`Request.frames`)
+
+
 class Request:
     """One submitted text.  Iterate to receive chunks; `result()` waits for the whole waveform."""
 
@@ -100,6 +118,31 @@ class Request:
         self.frames = 0
         self.error: Exception | None = None
         self._pending_chunks = 0  # text chunks not yet finished
+        self._batcher = None      # the batcher that runs the request (`cancel`)
+        # a request with several chunks in flight: its `chunk_order.ChunkOrder`, which forwards to `_forward`.  None: one
+        # chunk at a time, whose items go to `_q` directly
+        self._order = None
+
+    def _forward(self, item):
+        """what the chunk order emits, in text order: a frame tick, an item for the consumer, or the final None.  `frames`
+        and `blocks` therefore count what has been forwarded, and a FLAC frame, numbered from 0 within its chunk by its
+        row, gets its number in the request's stream here (`flac.renumber`)"""
+        if item is _FRAME:
+            self.frames += 1
+            return
+        if item is not None and self.compression is not None:
+            from .flac import renumber
+
+            item = torch.frombuffer(bytearray(renumber(item.numpy().tobytes(), self.blocks)), dtype=torch.uint8)
+            self.blocks += 1
+        self._q.put(item)
+
+    def cancel(self):
+        """Ends the request: callable from any thread, takes effect at the scheduler's next iteration.  Its chunks leave
+        `waiting` and their slots, the consumer's iteration ends without an error behind what had been forwarded, and
+        `result()` returns that.  A second call, or a call after the request's end, does nothing."""
+        if self._batcher is not None:
+            self._batcher._cancel(self)
 
     def __iter__(self):
         while True:
@@ -140,10 +183,11 @@ class Request:
 class _Job:
     """one text chunk of a request while it owns a slot"""
 
-    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "route")
+    __slots__ = ("req", "tokens", "voice", "gen", "fae", "start", "last", "samp", "lsd", "seed", "route", "index")
 
-    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, route=None):
+    def __init__(self, req, tokens, voice, gen, fae, last, samp=None, lsd=None, seed=None, route=None, index=0):
         self.req, self.tokens, self.voice, self.gen, self.fae, self.last = req, tokens, voice, gen, fae, last
+        self.index = index     # which of the request's text chunks this is
         self.route = route     # the request's way through the pipeline's output chain (`output_chain.Route`)
         self.seed = seed       # the chunk's row seed (engine.chunk_seed of the request's seed), or None: the state's stream
         self.samp = samp       # (temperature, noise_clamp, eos_threshold) of the request, or None: the model's settings
@@ -153,8 +197,11 @@ class _Job:
 
 class ContinuousBatcher:
     def __init__(self, model, slots: int = 16, capacity: int = 1024, pcm_format: str = "f32", noise_seed: int = 0,
-                 max_lsd_decode_steps: int | None = None, spec=None, **chain):
+                 max_lsd_decode_steps: int | None = None, spec=None, parallel_chunks: int = 1, **chain):
         """`capacity`: KV positions per slot (voice + text + generated frames of one chunk must fit).
+
+        `parallel_chunks` = W: up to W text chunks of one request wait or own slots at a time (`submit`); it is the default
+        and the upper bound of a request's own value.  1: the chunks of a request run one after the other, as before.
 
         The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`,
         `tones`, `compressions`, `dynamics`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
@@ -175,6 +222,7 @@ class ContinuousBatcher:
         from .engine import StepPipeline
         from .output_chain import ChainSpec
 
+        self.parallel_chunks = check_parallel_chunks(parallel_chunks)  # before anything is allocated
         spec = ChainSpec.of(spec, **chain)
         if pcm_format not in ("f32", "i16"):
             raise ValueError("pcm_format must be 'f32' or 'i16'")
@@ -234,7 +282,8 @@ class ContinuousBatcher:
         self._wake = threading.Condition(self._lock)
         self._thread = None
         self._stop = False
-        self._chain: dict = {}  # request id -> deque of follow-up chunks (run one after the other)
+        self._chain: dict = {}  # request id -> deque of follow-up chunks (released as the request's earlier chunks leave)
+        self._cancels: list = []  # requests whose `cancel` waits for the scheduler's next iteration
         self._outstanding: dict = {}  # request id -> Request, from submit() until its final sentinel: what _fail / stop notify
         self._failed: Exception | None = None
         self._closed = False
@@ -242,10 +291,17 @@ class ContinuousBatcher:
     # ---- submission (any thread) ---------------------------------------------------------------
     def submit(self, model_state: dict, text: str, frames_after_eos: int | None = None, max_tokens: int = 50,
                temperature: float | None = None, noise_clamp: float | None = None,
-               eos_threshold: float | None = None, lsd_decode_steps: int | None = None, seed: int | None = None,
-               **request) -> Request:
+               eos_threshold: float | None = None, lsd_decode_steps: int | None = None,
+               parallel_chunks: int | None = None, seed: int | None = None, **request) -> Request:
         """Same text handling as `generate_audio_stream` (tts_model.py:618-631): long texts are split into
-        chunks that run one after the other, each from the voice state.
+        chunks, each of which runs from the voice state: one after the other, or with `parallel_chunks` = W > 1 (an int in
+        [1, the batcher's own]; None: the batcher's own) up to W of them at a time in rows of their own.  The first
+        min(W, n) chunks wait at once, and each chunk that leaves its slot releases the next, so the request never has
+        more than W chunks waiting or in slots and the other requests take the remaining slots in arrival order.  The
+        consumer receives what the serial run delivers, in text order (`chunk_order.ChunkOrder`): what a later chunk
+        produces early is held until the chunks before it have finished, and `Request.frames` / `Request.blocks` count
+        what has been forwarded.  A FLAC row of such a request numbers its frames from 0 and the host renumbers each
+        frame as it is forwarded (`flac.renumber`).  The one-segment case of `submit_script`.
 
         `temperature`, `noise_clamp` (<= 0: none) and `eos_threshold` apply to this request only; None means the model's
         value.  A request that gives none of them runs with the model's settings exactly.  `lsd_decode_steps` (an int in
@@ -258,14 +314,33 @@ class ContinuousBatcher:
         `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`, `compression`, `dynamics`), checked against the batcher's table:
         ValueError for what it refuses, TypeError for another name.  A request whose row lags (a speed, a pitch, a loudness
         target, a tone, a compressor setting or a gain) needs frames_after_eos >= 1."""
+        return self.submit_script([(model_state, text)], frames_after_eos, max_tokens, temperature=temperature,
+                                  noise_clamp=noise_clamp, eos_threshold=eos_threshold, lsd_decode_steps=lsd_decode_steps,
+                                  seed=seed, parallel_chunks=parallel_chunks, **request)
+
+    def submit_script(self, segments, frames_after_eos: int | None = None, max_tokens: int = 50,
+                      temperature: float | None = None, noise_clamp: float | None = None,
+                      eos_threshold: float | None = None, lsd_decode_steps: int | None = None, seed: int | None = None,
+                      parallel_chunks: int | None = None, **request) -> Request:
+        """One request made of `segments`, a non-empty list of `(model_state, text)` pairs: a dialogue script.  Each text is
+        split as `submit` splits it, the chunks of all segments form one list in order, each chunk runs on its segment's
+        voice, and chunk i of that list draws from `chunk_seed(seed, i)`.  One `Request`, one ordered stream and one route
+        for all segments; every other argument is `submit`'s and applies to the whole script.  An empty text in any
+        segment is the ValueError of `submit`."""
         from .engine import check_seed, chunk_seed
         from .tts_model import _state_current_end
 
         m = self.model
         if self._failed is not None:
             raise RuntimeError(f"the batcher has stopped after an error: {self._failed}")
-        if not text or not text.strip():
-            raise ValueError("Text to generate cannot be empty")
+        segments = list(segments)
+        if not segments:
+            raise ValueError("a script needs at least one segment")
+        for _, text in segments:
+            if not text or not text.strip():
+                raise ValueError("Text to generate cannot be empty")
+        window = self.parallel_chunks if parallel_chunks is None else check_parallel_chunks(parallel_chunks,
+                                                                                             self.parallel_chunks)
         samp = None
         if temperature is not None or noise_clamp is not None or eos_threshold is not None:
             t = float(m.temp if temperature is None else temperature)
@@ -299,14 +374,18 @@ class ContinuousBatcher:
                 raise ValueError(f"lsd_decode_steps must be in [1, {self.max_lsd}], got {n}")
             else:
                 lsd = n
-        chunks = split_into_best_sentences(m.tokenizer.encode, m.tokenizer.sp, text, max_tokens,
-                                           m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
-        t_voice = _state_current_end(model_state)
+        chunks = []  # (voice state, its KV positions, chunk text) of every chunk of every segment, in order
+        for model_state, text in segments:
+            t_voice = _state_current_end(model_state)
+            chunks += [(model_state, t_voice, c) for c in
+                       split_into_best_sentences(m.tokenizer.encode, m.tokenizer.sp, text, max_tokens,
+                                                 m.pad_with_spaces_for_short_inputs, m.remove_semicolons)]
         jobs = []
         with self._lock:
             req = Request(self._next_id, route.rate, route.encoding, route.compression)
             self._next_id += 1
-        for i, chunk in enumerate(chunks):
+        req._batcher = self
+        for i, (model_state, t_voice, chunk) in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, m.pad_with_spaces_for_short_inputs, m.remove_semicolons)
             fae = frames_after_eos if frames_after_eos is not None else (
                 m.model_recommended_frames_after_eos if m.model_recommended_frames_after_eos is not None else guess + 2)
@@ -322,18 +401,30 @@ class ContinuousBatcher:
             if need > self.capacity:
                 raise ValueError(f"request needs {need} KV positions; slot capacity is {self.capacity}")
             jobs.append(_Job(req, torch.tensor(ids, dtype=torch.long)[None, :], model_state, gen, fae, i == len(chunks) - 1,
-                             samp, lsd, None if seed is None else chunk_seed(seed, i), route))
+                             samp, lsd, None if seed is None else chunk_seed(seed, i), route, i))
         req._pending_chunks = len(jobs)
+        window = min(window, len(jobs))
+        if window > 1:  # several chunks in flight: their items reach the queue through the chunk order
+            from .chunk_order import ChunkOrder
+
+            req._order = ChunkOrder(len(jobs), req._forward)
         with self._wake:
             if self._failed is not None or self._closed:
                 raise RuntimeError("the batcher is closed" if self._failed is None else
                                    f"the batcher has stopped after an error: {self._failed}")
             self._outstanding[req.id] = req
-            self.waiting.append(jobs[0])
-            if len(jobs) > 1:
-                self._chain[req.id] = collections.deque(jobs[1:])
+            self.waiting.extend(jobs[:window])
+            if len(jobs) > window:
+                self._chain[req.id] = collections.deque(jobs[window:])
             self._wake.notify_all()
         return req
+
+    def _cancel(self, req):
+        """`Request.cancel`: noted here by any thread, carried out by the scheduler (`_cancel_due`)"""
+        with self._wake:
+            if req.id in self._outstanding and req not in self._cancels:
+                self._cancels.append(req)
+                self._wake.notify_all()
 
     # ---- scheduler (one thread) ----------------------------------------------------------------
     def _admit(self):
@@ -375,6 +466,8 @@ class ContinuousBatcher:
                 return
             for job in jobs:  # find the bad one(s): admit the group's members one by one
                 with self._lock:
+                    if job.req.id not in self._outstanding:
+                        continue  # a chunk of a request that another of its chunks has just failed
                     b = next(b for b in range(self.B) if self.slot[b] is None and self.a_emit[b] >= 0)
                 try:
                     self._admit_group([job], [b])
@@ -418,8 +511,9 @@ class ContinuousBatcher:
             # the slot's codec carries: zero on the codec stream, behind the frames already queued there
             self.ms.reset_row(b, self.pipe.s2)
             # the row's route and a zero state in every stage, same stream; a flac row numbers its frames on from what the
-            # request's earlier text chunks have delivered
-            self.chain.set_row(b, job.route, self.pipe.s2, first_block=job.req.blocks)
+            # request's earlier text chunks have delivered, which is not known while they still run: a row of a request with
+            # several chunks in flight numbers from 0, and the host renumbers each frame as it is forwarded
+            self.chain.set_row(b, job.route, self.pipe.s2, first_block=0 if job.req._order is not None else job.req.blocks)
             self.a_blocks[b] = 0
             if self.lagging:
                 self.a_pos[b], self.row_drain[b], self.a_release[b] = 0, False, -1
@@ -429,14 +523,47 @@ class ContinuousBatcher:
             self.a_eos[b], self.a_emit[b] = -1, -1
 
     def _end_request(self, req, error: Exception | None = None):
-        """final sentinel of a request (with `error`: the consumer's iteration raises it); drops its follow-up chunks"""
+        """final sentinel of a request (with `error`: the consumer's iteration raises it); removes every chunk it still has
+        anywhere (`_purge`).  Without an error this is a cancellation: the consumer's iteration ends behind what it has
+        been forwarded"""
         with self._wake:
             if self._outstanding.pop(req.id, None) is None:
                 return
-            self._chain.pop(req.id, None)
+        self._purge(req)
         if error is not None:
             req.error = error
-        req._q.put(None)
+        if req._order is not None:
+            req._order.cancel()  # nothing held is forwarded any more; emits the sentinel
+        else:
+            req._q.put(None)
+
+    def _purge(self, req):
+        """removes every job of `req` from `waiting`, from `_chain` and from the slots.  A slot is left as a job that ends
+        leaves it: the row parked, no job, nothing to emit, nothing to release or drain; the next admission resets the
+        row's codec and chain state, and `_process` drops the frames of the row that are still in flight, because their
+        slot is empty"""
+        with self._wake:
+            self._chain.pop(req.id, None)
+            if any(j.req is req for j in self.waiting):
+                self.waiting = collections.deque(j for j in self.waiting if j.req is not req)
+        for b in range(self.B):
+            job = self.slot[b]
+            if job is None or job.req is not req:
+                continue
+            try:
+                self.st.set_row_active(b, False)
+            except Exception:
+                if self._failed is None:  # after the scheduler's failure the row's state no longer matters
+                    raise
+            self.slot[b] = None
+            self.a_emit[b], self.a_release[b], self.row_drain[b] = 0, -1, False
+
+    def _cancel_due(self):
+        """carries out the cancellations noted since the last iteration"""
+        with self._wake:
+            reqs, self._cancels = self._cancels, []
+        for req in reqs:
+            self._end_request(req)
 
     def _process(self, frame: int):
         """EOS decisions of FlowLM step `frame` and the PCM of codec frame `frame`, for every slot whose job had started
@@ -468,11 +595,17 @@ class ContinuousBatcher:
         for b in np.nonzero(rows)[0]:
             job = self.slot[b]
             if self.a_emit[b] < 0:
+                order = job.req._order  # None: one chunk at a time, straight to the queue
                 if self.lagging or self.en is not None:
                     self._deliver(b, job, pcm[b])
-                else:
+                elif order is None:
                     job.req._q.put(pcm[b] if self.rs is None else pcm[b, :job.route.n_out])
-                job.req.frames += 1
+                else:
+                    order.push(job.index, pcm[b] if self.rs is None else pcm[b, :job.route.n_out])
+                if order is None:
+                    job.req.frames += 1
+                else:
+                    order.push(job.index, _FRAME)
                 continue
             if self.a_eos[b] < 0:
                 logger.warning("Maximum generation length reached without EOS, this very often indicates an error.")
@@ -490,7 +623,10 @@ class ContinuousBatcher:
             self._finish(job)
 
     def _deliver(self, b, job, line):
-        """routes the part of a frame of slot `b` that belongs to its job (`Route.take`)"""
+        """routes the part of a frame of slot `b` that belongs to its job (`Route.take`): to the request's queue, or
+        through its chunk order where it has several chunks in flight"""
+        order = job.req._order
+        put = job.req._q.put if order is None else (lambda item: order.push(job.index, item))
         if self.pk is not None:
             from .flac import PREFIX
 
@@ -500,20 +636,21 @@ class ContinuousBatcher:
                 # the kernel has cut the pre-roll: a line holds one whole frame, or nothing while the row leads; a job of
                 # F frames delivers F of them
                 if nbytes and (self.a_emit[b] < 0 or self.a_blocks[b] < self.a_emit[b]):
-                    job.req._q.put(line[:nbytes])
+                    put(line[:nbytes])
                     self.a_blocks[b] += 1
-                    job.req.blocks += 1
+                    if order is None:  # through the order the request counts, and numbers, what it forwards
+                        job.req.blocks += 1
                 return
         pos = int(self.a_pos[b])
         lo, hi = job.route.take(pos, None if self.a_emit[b] < 0 else int(self.a_emit[b]))
         if hi > lo:
             bps = job.route.bytes_per_sample
             if bps is None:
-                job.req._q.put(line[lo:hi])
+                put(line[lo:hi])
             else:  # the encoder's ring is in bytes: the job's samples as a typed view of them
                 from . import encoding
 
-                job.req._q.put(line[lo * bps:hi * bps].view(encoding.torch_dtype(job.route.encoding)))
+                put(line[lo * bps:hi * bps].view(encoding.torch_dtype(job.route.encoding)))
         self.a_pos[b] = pos + job.route.n_out
 
     def _drain_due(self):
@@ -553,13 +690,16 @@ class ContinuousBatcher:
         with self._wake:
             req._pending_chunks -= 1
             nxt = self._chain.get(req.id)
-            if nxt:
+            if nxt:  # the chunk that leaves releases the request's next one: its window stays full
                 self.waiting.appendleft(nxt.popleft())
                 if not nxt:
                     del self._chain[req.id]
             elif req._pending_chunks == 0:
                 self._outstanding.pop(req.id, None)
-                req._q.put(None)
+                if req._order is None:
+                    req._q.put(None)
+        if req._order is not None:
+            req._order.finish(job.index)  # flushes what the next chunks have produced; the sentinel behind the last chunk
 
     def _check_gpu_error(self):
         if self.st.error():  # synchronises the FlowLM stream: only called when idle / every 512 steps
@@ -568,6 +708,8 @@ class ContinuousBatcher:
     def step(self) -> bool:
         """One scheduler iteration: admit, read the steps whose frames are complete, queue FlowLM step g + codec frame g.
         Returns False when there is nothing to run."""
+        if self._cancels:
+            self._cancel_due()
         self._admit()
         pipe, nb = self.pipe, self.pipe.nb
         # mandatory for frame g - nb (its pinned buffers are about to be reused), opportunistic for the later ones
@@ -611,6 +753,9 @@ class ContinuousBatcher:
                     idle = not self.waiting and all(j is None for j in self.slot)
                 try:
                     if idle:
+                        if self._cancels:
+                            with self.engine_lock:
+                                self._cancel_due()
                         if self.collected < self.g:
                             with self.engine_lock:
                                 self._drain()  # the last frames of the rows that just left; may queue a follow-up chunk

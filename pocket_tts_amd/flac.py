@@ -155,6 +155,64 @@ def silent_frame(number: int, n: int, rate: int) -> bytes:
     return f + crc16(f).to_bytes(2, "big")
 
 
+def _mul16(a: int, b: int) -> int:
+    """the product of two remainders modulo the CRC-16 polynomial x^16 + x^15 + x^2 + 1 (bit i: the coefficient of x^i)"""
+    r = 0
+    while b:
+        if b & 1:
+            r ^= a
+        b >>= 1
+        a <<= 1
+        if a & 0x10000:
+            a ^= 0x18005
+    return r
+
+
+def _xpow16(n: int) -> int:
+    """x^n modulo the CRC-16 polynomial, by square-and-multiply"""
+    r, b = 1, 2
+    while n:
+        if n & 1:
+            r = _mul16(r, b)
+        b = _mul16(b, b)
+        n >>= 1
+    return r
+
+
+def header_length(frame: bytes) -> int:
+    """bytes of the header of `frame`, its CRC-8 included; ValueError where `frame` does not begin with a frame header of a
+    fixed-blocksize stream whose CRC-8 holds"""
+    if len(frame) < 6 or frame[0] != 0xFF or frame[1] != 0xF8:
+        raise ValueError("not a FLAC frame of a fixed-blocksize stream: no FF F8 sync")
+    b = frame[4]
+    digits = 1 if b < 0x80 else 8 - (b ^ 0xFF).bit_length()
+    if not 1 <= digits <= 6 or (b >= 0x80 and digits < 2):
+        raise ValueError("not a FLAC frame: malformed frame number")
+    size, rate = frame[2] >> 4, frame[2] & 15
+    n = 4 + digits + (1 if size == 6 else 2 if size == 7 else 0) + (1 if rate == 12 else 2 if rate in (13, 14) else 0) + 1
+    if len(frame) < n + 2 or crc8(frame[:n - 1]) != frame[n - 1]:
+        raise ValueError("not a FLAC frame: the header's CRC-8 does not hold")
+    return n
+
+
+def renumber(frame: bytes, number: int) -> bytes:
+    """`frame`, one whole frame, as frame `number` of its stream: the header with the new number (its length may change)
+    and CRC-8, the same subframe, the CRC-16 that belongs to them.
+
+    Both CRCs start at 0 and have no final xor, so they are linear: with header A, the rest B of the frame and the CRC-16
+    taken as the remainder of the message times x^16, crc16(A | B) = crc16(A) * x^(8 |B|) + crc16(B).  The new CRC-16 is the
+    old one plus (crc16(A_old) + crc16(A_new)) * x^(8 |B|), which costs the two headers and a square-and-multiply, not a
+    pass over the frame."""
+    frame = bytes(frame)
+    n = header_length(frame)
+    at = 4 + (1 if frame[4] < 0x80 else 8 - (frame[4] ^ 0xFF).bit_length())
+    head = frame[:4] + utf8_number(number) + frame[at:n - 1]
+    head += bytes([crc8(head)])
+    body = frame[n:-2]
+    crc = int.from_bytes(frame[-2:], "big") ^ _mul16(crc16(frame[:n]) ^ crc16(head), _xpow16(8 * len(body)))
+    return head + body + crc.to_bytes(2, "big")
+
+
 def silence(first_number: int, rate: int, n: int) -> bytes:
     """the frames of the 200 ms tail, numbered from `first_number`: rate // 5 samples as whole blocks of `n` and one
     shorter last block (the last block of a fixed-blocksize stream may be shorter)"""

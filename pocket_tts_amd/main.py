@@ -19,7 +19,9 @@ BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--pea
 `generate --sample-rate 8000 --encoding mulaw` is the same for one text) and `container=raw` for the bytes without a WAV
 header, and with `--tones telephone,warm,"hp:120;peak:3000:4"` a per-request `tone` (a parametric equaliser on the GPU,
 tone.py; `generate --tone telephone` is the same for one text), and with `--dynamics speech,"threshold=-24;ratio=4"` a
-per-request `dynamics` (a speech compressor on the GPU, dynamics.py; `generate --dynamics speech`).  `export-voice` encodes an audio prompt (first 30 s)
+per-request `dynamics` (a speech compressor on the GPU, dynamics.py; `generate --dynamics speech`), and with
+`--parallel-chunks W` up to W sentences of a request at a time as rows of the batch, delivered in text order (batching.py;
+`generate --parallel-chunks W` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
 """
 
@@ -294,6 +296,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--output-path", default=None, help="Default: ./tts_output.wav, or ./tts_output.flac with --compression flac")
     g.add_argument("--device", default="cuda:0")
     g.add_argument("--max-tokens", type=int, default=50)
+    g.add_argument("--parallel-chunks", type=int, default=1, metavar="W",
+                   help="Run up to W sentences of a long text at a time, as rows of one batch; the audio comes out in text "
+                        "order (default 1: one after the other)")
     g.add_argument("--quantize", action="store_true")
     g.add_argument("--codec-bf16", action="store_true",
                    help="bf16 weights + activations in the Mimi codec (fp32 accumulate; not in the reference, ~44 dB SNR)")
@@ -343,6 +348,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
     s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
     s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
+    s.add_argument("--parallel-chunks", type=int, default=1, metavar="W",
+                   help="Every request runs up to W sentences of its text at a time in slots of their own; a request never "
+                        "holds more than W slots (default 1: one after the other)")
     s.add_argument("--capacity", type=int, default=1024,
                    help="KV positions per slot: voice + text chunk + generated frames (a 30 s voice prompt is 376)")
     s.add_argument("--voices-dir", default=None, help="Directory of <name>.safetensors voice states for voice_url=<name>")
@@ -376,7 +384,7 @@ def serve_app(args) -> int:
     # carry the names of its options
     app = create_app(model, slots=args.slots, capacity=args.capacity, voices_dir=args.voices_dir,
                      default_voice=args.default_voice, max_lsd_decode_steps=args.max_lsd_decode_steps,
-                     **{f.name: getattr(args, f.name) for f in dataclasses.fields(ChainSpec)})
+                     parallel_chunks=args.parallel_chunks, **{f.name: getattr(args, f.name) for f in dataclasses.fields(ChainSpec)})
     uvicorn.run(app, host=args.host, port=args.port, log_level="error" if args.quiet else "info")
     return 0
 
@@ -403,6 +411,9 @@ def cli_app(argv=None) -> int:
         text = sys.stdin.read()
     if not text.strip():
         logger.error("No input received from stdin.")
+        return 1
+    if args.parallel_chunks < 1:
+        logger.error("--parallel-chunks: must be at least 1, got %d", args.parallel_chunks)
         return 1
     from .tts_model import TTSModel
 
@@ -433,7 +444,7 @@ def cli_app(argv=None) -> int:
     state = model.get_state_for_audio_prompt(voice)
     request["gain_db"] = args.gain_db  # as it came: the limiter's 0 dB behind a tone alone is for the model to fill in
     chunks = model.generate_audio_stream(state, text, frames_after_eos=args.frames_after_eos, max_tokens=args.max_tokens,
-                                         seed=args.seed, **request)
+                                         seed=args.seed, parallel_chunks=args.parallel_chunks, **request)
     rate = args.sample_rate or model.sample_rate
     if args.output_path is None:
         args.output_path = "./tts_output.flac" if args.compression else "./tts_output.wav"

@@ -20,7 +20,10 @@ them (`tone.py`: a preset such as `telephone`, or a band list), equalised on the
 (`peak_dbfs` is then its ceiling); a tone the request's rate does not admit gets a 400 with those it admits.  On a server
 started with `dynamics` the field `dynamics` chooses one of its compressor settings (`dynamics.py`: a preset such as
 `speech`, or key=value pairs), compressed on the GPU behind the tone with the peak limiter behind it; a setting that is not
-configured gets a 400 with the list of those that are.
+configured gets a 400 with the list of those that are.  Instead of `text` and a voice a request may send `script`, a JSON
+list of {"voice": <name>, "text": <text>} objects (at most 256): one request, one stream, each entry spoken in its voice of
+the voices directory, in order; a malformed value, an empty list, an entry without text or with an unknown voice gets a 400
+that names the entry.  On a server started with `parallel_chunks` W the sentences of a request run up to W at a time.
 
 FastAPI's `Form` / `File` need the `python-multipart` package; the two form encodings are parsed here instead, with
 `urllib.parse` and the standard library's `email` header parser.
@@ -52,6 +55,9 @@ INDEX_HTML = """<!doctype html>
 <form action="/tts" method="post" enctype="multipart/form-data">
 <p><textarea name="text" rows="4" cols="60">Hello world.</textarea></p>
 <p>Voice name <input name="voice_url"> or WAV prompt <input type="file" name="voice_wav" accept=".wav"></p>
+<p>Script <input name="script" size="60"> instead of text and voice: a JSON list such as
+[{"voice": "alba", "text": "Hello."}, {"voice": "marius", "text": "Hi."}] (clear the text and the voice above to use
+it; empty: the text above)</p>
 <p>LSD decode steps <input name="lsd_decode_steps" size="3"> (empty: the server's default)</p>
 <p>Seed <input name="seed" size="20"> (empty: a take that cannot be repeated)</p>
 <p>Sample rate <input name="sample_rate" size="6"> Hz (empty: the model's own rate)</p>
@@ -385,8 +391,50 @@ def parse_container(fields: dict, compressions=None) -> str:
     raise FormError(f"container must be 'wav' or 'raw', got {raw!r}")
 
 
+MAX_SCRIPT_ENTRIES = 256
+
+
+def parse_script(fields: dict, files: dict | None = None):
+    """the optional `script` field, a JSON list of {"voice": <name>, "text": <text>} objects, as [(voice name or None,
+    text)] (absent or empty field: None).  It excludes `text`, `voice_url` and `voice_wav`.  FormError, naming the entry
+    at fault, for a value that is no JSON, no list, an empty list, more than `MAX_SCRIPT_ENTRIES` entries, an entry that
+    is no object, has no text or whose voice is no string"""
+    import json
+
+    raw = fields.get("script")
+    if raw is None or raw.strip() == "":
+        return None
+    for name in ("text", "voice_url"):
+        if (fields.get(name) or "").strip():
+            raise FormError(f"script excludes {name}: the entries of the script carry their own")
+    upload = (files or {}).get("voice_wav")
+    if upload is not None and upload[1]:
+        raise FormError("script excludes voice_wav: the entries of the script name voices of the server")
+    try:
+        entries = json.loads(raw)
+    except ValueError as e:
+        raise FormError(f"script is not valid JSON: {e}") from None
+    if not isinstance(entries, list):
+        raise FormError("script must be a JSON list of {\"voice\": ..., \"text\": ...} objects")
+    if not entries:
+        raise FormError("script is an empty list")
+    if len(entries) > MAX_SCRIPT_ENTRIES:
+        raise FormError(f"script has {len(entries)} entries; at most {MAX_SCRIPT_ENTRIES} are accepted")
+    out = []
+    for i, entry in enumerate(entries):
+        if not isinstance(entry, dict):
+            raise FormError(f"script[{i}] is not an object with \"voice\" and \"text\"")
+        text, voice = entry.get("text"), entry.get("voice")
+        if not isinstance(text, str) or not text.strip():
+            raise FormError(f"script[{i}] has no text")
+        if voice is not None and (not isinstance(voice, str) or not voice.strip()):
+            raise FormError(f"script[{i}]: voice must be the name of a voice, got {voice!r}")
+        out.append((voice, text))
+    return out
+
+
 def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voice: str | None = None,
-               batcher_factory=None, max_lsd_decode_steps: int | None = None, **chain):
+               batcher_factory=None, max_lsd_decode_steps: int | None = None, parallel_chunks: int = 1, **chain):
     """FastAPI app serving `model` through one `ContinuousBatcher(pcm_format="i16")` of `slots` rows of `capacity` KV
     positions, started and closed by the app's lifespan.  `voice_url=<name>` reads `<voices_dir>/<name>.safetensors`
     once; requests without a voice use `default_voice`.  The model's `noise_clamp` (if any) is every request's default
@@ -400,8 +448,11 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     request's samples leave the GPU in its own encoding.  With `compressions` a request may send `container=flac`: the
     answer is `audio/flac`, the stream header, one frame per codec frame as each is decoded and the silent tail
     (`main.flac_stream_bytes`), which decodes to the samples of the `container=wav` answer; it takes `encoding` pcm_s16le or
-    none, and a line `flac.plan` admits (400 with the rule's message otherwise).  `batcher_factory(model, slots, capacity)` replaces the batcher
-    (tests)."""
+    none, and a line `flac.plan` admits (400 with the rule's message otherwise).  `parallel_chunks` = W: every request runs up to
+    W chunks of its text at a time in slots of their own (`ContinuousBatcher`; 1: one after the other).  The form field
+    `script`, a JSON list of {"voice": <name>, "text": <text>} objects, makes one request of several segments, each with a voice
+    of the voices directory (`parse_script`, `ContinuousBatcher.submit_script`); every other field applies to the whole script.
+    `batcher_factory(model, slots, capacity)` replaces the batcher (tests)."""
     from .main import flac_stream_bytes, wav_stream_bytes
 
     from .output_chain import ChainSpec
@@ -416,6 +467,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     compressions = table.compressions
     speeds_of = None if spec.speeds is None else table.speeds_of()
 
+    from .batching import check_parallel_chunks
+
+    parallel_chunks = check_parallel_chunks(parallel_chunks)  # ValueError at start-up
     own_lsd = getattr(model, "lsd_decode_steps", 1)
     max_lsd = own_lsd if max_lsd_decode_steps is None else int(max_lsd_decode_steps)
     if batcher_factory is None:
@@ -426,7 +480,7 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
 
         def batcher_factory(model, slots, capacity):  # the encoder writes every request's format, pcm_s16le included
             return ContinuousBatcher(model, slots=slots, capacity=capacity, max_lsd_decode_steps=reserve, spec=spec,
-                                     pcm_format="f32" if encodings is not None else "i16")
+                                     pcm_format="f32" if encodings is not None else "i16", parallel_chunks=parallel_chunks)
 
     voices_dir = Path(voices_dir) if voices_dir is not None else None
     voices: dict = {}  # name -> voice state dict: one object per voice, so the batcher's voice cache hits
@@ -505,8 +559,9 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             return JSONResponse({"detail": "the batcher is not running"}, status_code=503)
         try:
             fields, files = parse_form(request.headers.get("content-type"), await request.body())
+            script = parse_script(fields, files)
             text = fields.get("text", "")
-            if not text.strip():
+            if script is None and not text.strip():
                 raise FormError("Text cannot be empty")
             settings = parse_settings(fields)
             lsd = parse_lsd_steps(fields, max_lsd)
@@ -561,7 +616,17 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
                 upload = None  # an empty file input (a browser form sends one when no file is chosen)
             if voice_url is not None and upload is not None:
                 raise FormError("Cannot provide both voice_url and voice_wav")
-            if upload is not None:
+            segments = None
+            if script is not None:
+                segments = []
+                for i, (name, part) in enumerate(script):
+                    if name is None and default_voice is None:
+                        raise FormError(f"script[{i}] names no voice and the server has no default voice")
+                    try:
+                        segments.append((await run_in_threadpool(load_voice, name or default_voice), part))
+                    except FormError as e:
+                        raise FormError(f"script[{i}]: {e}") from None
+            elif upload is not None:
                 state = await run_in_threadpool(encode_upload, upload[0], upload[1], batcher)
             else:
                 if voice_url is None:
@@ -572,7 +637,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
             fae = settings.pop("frames_after_eos")
             if settings["noise_clamp"] is None and model.noise_clamp is not None:
                 settings["noise_clamp"] = model.noise_clamp
-            req = await run_in_threadpool(batcher.submit, state, text, fae, **settings)
+            if segments is not None:
+                req = await run_in_threadpool(batcher.submit_script, segments, fae, **settings)
+            else:
+                req = await run_in_threadpool(batcher.submit, state, text, fae, **settings)
         except ValueError as e:  # FormError, and submit's own (empty text, capacity)
             return bad(e)
 

@@ -95,6 +95,7 @@ class TTSModel:
         self.origin = origin
         self.has_voice_cloning = engine.has_voice_encoder
         self._ctx_cache: dict = {}
+        self._batchers: dict = {}  # the private batchers of `generate_audio(parallel_chunks=)` (`_batcher_for`)
         self._voice_cache: dict = {}  # id(model_state) -> (signature, LMState, tensors): device-resident voice states
         self._voice_lock = threading.Lock()  # the cache is shared with ContinuousBatcher's scheduler thread
         self.pad_with_spaces_for_short_inputs = config.pad_with_spaces_for_short_inputs
@@ -191,17 +192,25 @@ class TTSModel:
     # ---- generation ---------------------------------------------------------------------------
     @torch.no_grad()
     def generate_audio(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                       frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None,
-                       **request) -> torch.Tensor:
-        """`seed` and `**request` (not in the reference): see `generate_audio_stream`."""
+                       frames_after_eos: int | None = None, copy_state: bool = True, parallel_chunks: int = 1,
+                       seed: int | None = None, **request) -> torch.Tensor:
+        """`seed`, `parallel_chunks` and `**request` (not in the reference): see `generate_audio_stream`."""
         return torch.cat(list(self.generate_audio_stream(model_state, text_to_generate, max_tokens, frames_after_eos,
-                                                         copy_state, seed=seed, **request)), dim=0)
+                                                         copy_state, seed=seed, parallel_chunks=parallel_chunks,
+                                                         **request)), dim=0)
 
     @torch.no_grad()
     def generate_audio_stream(self, model_state: dict, text_to_generate: str, max_tokens: int = MAX_TOKEN_PER_CHUNK,
-                              frames_after_eos: int | None = None, copy_state: bool = True, seed: int | None = None,
-                              **request):
+                              frames_after_eos: int | None = None, copy_state: bool = True, parallel_chunks: int = 1,
+                              seed: int | None = None, **request):
         """Yields fp32 CPU tensors of `frame_samples` (1920) samples (reference tts_model.py:545-631).
+
+        `parallel_chunks` = W > 1 (not in the reference) runs up to W text chunks of a long text at a time, as rows of one
+        batch, and yields the same items in the same order (`ContinuousBatcher.submit(parallel_chunks=)`, on a private
+        batcher of W slots that the model builds on first use and keeps: `_batcher_for`).  A text of one chunk, or W = 1,
+        runs as before.  It needs `copy_state=True`.  An unseeded call at temp > 0 then draws from the batch state's stream
+        per row (seeded once from torch's generator when the batcher is built), not step by step from torch's global
+        generator; a seeded call draws what it draws at W = 1.
 
         `**request` (not in the reference): the request's way through the output chain on the GPU, the fields of
         `output_chain.ChainTable.route` (`sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
@@ -226,6 +235,17 @@ class TTSModel:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
                                            self.pad_with_spaces_for_short_inputs, self.remove_semicolons)
+        if type(parallel_chunks) is not int or parallel_chunks != 1:  # `True == 1`, and is refused
+            from .batching import check_parallel_chunks
+
+            window = check_parallel_chunks(parallel_chunks)
+            if window > 1 and not copy_state:
+                raise ValueError("parallel_chunks > 1 needs copy_state=True: the chunks run side by side, each from the "
+                                 "voice state")
+            if window > 1 and len(chunks) > 1:
+                yield from self._generate_parallel(model_state, text_to_generate, chunks, max_tokens, frames_after_eos,
+                                                   seed, window, spec, request)
+                return
         blocks = 0  # FLAC frames yielded so far: a follow-up chunk numbers its frames on from here
         for i, chunk in enumerate(chunks):
             _, guess = prepare_text_prompt(chunk, self.pad_with_spaces_for_short_inputs, self.remove_semicolons)
@@ -407,8 +427,78 @@ class TTSModel:
             res.append(torch.from_numpy(out[b, :n].reshape(-1)) if n > 0 else torch.zeros(0))
         return res
 
+    def _batcher_for(self, window: int, need: int, spec):
+        """The private `ContinuousBatcher` of `generate_audio(parallel_chunks=window)`: `window` slots, a capacity that fits
+        `need` KV positions (rounded up to 256, so that calls of about the same size share one), the output chain of
+        `spec`.  Built on first use and kept in `_batchers` under (window, capacity, lsd_decode_steps, *spec.tags());
+        its noise seed is drawn once, here, from torch's generator.  At most `RATE_CONTEXTS` are kept."""
+        from .batching import ContinuousBatcher
+
+        cap = -(-need // 256) * 256
+        key = (window, cap, self.lsd_decode_steps, *spec.tags())
+        cb = self._batchers.pop(key, None)
+        if cb is not None and cb.failed is not None:
+            cb.close()
+            cb = None
+        if cb is None:
+            self._drop_batchers(keep=self.RATE_CONTEXTS - 1)
+            cb = ContinuousBatcher(self, slots=window, capacity=cap, spec=spec, parallel_chunks=window,
+                                   noise_seed=int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        self._batchers[key] = cb  # the most recently used last
+        return cb
+
+    def _generate_parallel(self, model_state, text, chunks, max_tokens, frames_after_eos, seed, window, spec, request):
+        """the chunks of one text, up to `window` at a time, on the private batcher, driven from this thread: what the
+        request forwards after each scheduler iteration is yielded at once"""
+        import queue
+
+        from .engine import StepPipeline
+
+        tokens = max(max(len(self.tokenizer.encode(c)) for c in chunks), MAX_TOKEN_PER_CHUNK)
+        need = (_state_current_end(model_state) + tokens + estimate_max_gen_len(tokens, self.config.mimi.frame_rate)
+                + StepPipeline.NB_EVENTS + 2)
+        cb = self._batcher_for(window, need, spec)
+        # the model's settings of this call as the request's own: the rows read them at run time, whatever the model's were
+        # when the batcher's graphs were captured
+        req = cb.submit(model_state, text, frames_after_eos, max_tokens, temperature=self.temp,
+                        noise_clamp=self.noise_clamp, eos_threshold=self.eos_threshold, seed=seed, parallel_chunks=window,
+                        **request)
+        done = False
+        try:
+            while not done:
+                running = cb.step()
+                if not running:
+                    cb.run_until_idle()  # the frames still in flight, and the check of the device's error flag
+                while True:
+                    try:
+                        item = req._q.get_nowait()
+                    except queue.Empty:
+                        break
+                    if item is None:
+                        done = True
+                        break
+                    yield item
+                if not running and not done:
+                    raise RuntimeError("the batcher went idle before the request had finished")
+            if req.error is not None:
+                raise req.error
+        finally:
+            if not done:  # the consumer has stopped early, or an error: the request's rows leave their slots
+                req.cancel()
+                if cb.failed is None:
+                    cb.run_until_idle()
+
+    def _drop_batchers(self, keep: int = 0, chained: bool | None = None):
+        """the private batchers of `generate_audio(parallel_chunks=)` beyond the `keep` most recently used are closed;
+        `chained`: only those with (True) or without (False) an output chain"""
+        keys = [k for k in self._batchers if chained is None or (len(k) > 3) == chained]
+        for k in keys[: max(0, len(keys) - keep)]:
+            self._batchers.pop(k).close()
+
     def _drop_batch_contexts(self, keep: int = 0):
-        """cached batch contexts (state + graphs of `generate_audio_batch`) beyond the `keep` most recent are released"""
+        """cached batch contexts (state + graphs of `generate_audio_batch`) beyond the `keep` most recent are released, and
+        so are the private batchers without an output chain"""
+        self._drop_batchers(keep, chained=False)
         keys = [k for k in self._ctx_cache if k and k[0] == "batch"]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
@@ -421,7 +511,8 @@ class TTSModel:
     def _drop_rate_contexts(self, keep: int = 0):
         """cached contexts with an output chain (state, stages and graphs of one `ChainSpec`: the keys that go on past their
         four leading entries with its tags) beyond the `keep` most recently used are released; a context in use is not in
-        the cache"""
+        the cache.  The private batchers with an output chain go the same way"""
+        self._drop_batchers(keep, chained=True)
         keys = [k for k in self._ctx_cache if len(k) > 4 and k[0] != "batch"]
         for k in keys[: max(0, len(keys) - keep)]:
             c = self._ctx_cache.pop(k)
