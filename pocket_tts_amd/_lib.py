@@ -215,10 +215,12 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         normaliser, ptts_level.hip = the
         output gain with its peak limiter, ptts_encode.hip = the output encoder (16-bit and float PCM, G.711) and
         ptts_flac.hip = the packer (FLAC frames); how they are wired behind the codec is ptts.hip's (its section "the output
-        chain");
+        chain").  What their host sides share (the struct's head, owned device buffers, refusals, the drain flag) is
+        ptts_stage.h with ptts_stage.hip; the chunked scan of the equaliser, the compressor and the normaliser is
+        ptts_scan.h;
       * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
-    The first eleven see each other through ptts_host.h.  The units are compiled in parallel to csrc/.obj/*.o and linked into
-    libptts.so; a unit is recompiled when it or any header is newer than its object."""
+    ptts.hip, ptts_dispatch.hip, ptts_debug.hip and the stage units see each other through ptts_host.h.  The units are
+    compiled in parallel to csrc/.obj/*.o and linked into libptts.so; a unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = sorted(SRC.parent.glob("*.hip"))

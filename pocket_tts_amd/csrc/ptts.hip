@@ -1,6 +1,7 @@
 // Host side of libptts: engine construction (weight packing), FlowLM / Mimi step orchestration,
 // hipGraph capture and the C ABI declared in include/ptts.h.
 #include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_flow.h"
 #include "ptts_bf16.h"
 #include "ptts_lm.h"
@@ -2183,10 +2184,8 @@ static int mimi_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, cons
 struct ChainKind {
   const char *setter, *noun, *site;
   bool f32_only;  // writes f32 into a device buffer that must not be its input
-  int (*batch)(const void *), (*in_width)(const void *), (*out_width)(const void *);
   int (*enqueue)(hipStream_t st, void *stage, const float *in, void *out, int i16);
 };
-#define GET(T, f) [](const void *p) { return f((const T *)p); }
 #define ENQ(T, ...)                                                          \
   [](hipStream_t st, void *p, const float *in, void *out, int i16) {         \
     (void)i16;                                                               \
@@ -2194,28 +2193,19 @@ struct ChainKind {
     return __VA_ARGS__;                                                      \
   }
 static const ChainKind kChain[CH_N] = {
-    {"set_resampler", "resampler", "resample", false, GET(ptts_resampler, resample_batch),
-     GET(ptts_resampler, resample_frame_samples), GET(ptts_resampler, resample_out_max),
-     ENQ(ptts_resampler, resample_enqueue(st, stage, in, out, i16))},
-    {"set_stretcher", "stretcher", "stretch", false, GET(ptts_stretcher, stretch_batch), GET(ptts_stretcher, stretch_in_max),
-     GET(ptts_stretcher, stretch_out_max), ENQ(ptts_stretcher, stretch_enqueue(st, stage, in, out, i16, nullptr))},
-    {"set_pitcher", "pitcher", "pitch", false, GET(ptts_pitcher, pitch_batch), GET(ptts_pitcher, pitch_width),
-     GET(ptts_pitcher, pitch_width), ENQ(ptts_pitcher, pitch_enqueue(st, stage, in, out, i16, nullptr, nullptr))},
-    {"set_tone", "toner", "tone", true, GET(ptts_tone, tone_batch), GET(ptts_tone, tone_width), GET(ptts_tone, tone_width),
-     ENQ(ptts_tone, tone_enqueue(st, stage, in, (float *)out))},
-    {"set_dynamics", "compressor", "dynamics", true, GET(ptts_dynamics, dyn_batch), GET(ptts_dynamics, dyn_width),
-     GET(ptts_dynamics, dyn_width), ENQ(ptts_dynamics, dyn_enqueue(st, stage, in, (float *)out))},
-    {"set_loudnorm", "normaliser", "loudnorm", true, GET(ptts_loudnorm, loud_batch), GET(ptts_loudnorm, loud_width),
-     GET(ptts_loudnorm, loud_width), ENQ(ptts_loudnorm, loud_enqueue(st, stage, in, (float *)out, nullptr))},
-    {"set_leveler", "leveler", "level", false, GET(ptts_leveler, level_batch), GET(ptts_leveler, level_width),
-     GET(ptts_leveler, level_width), ENQ(ptts_leveler, level_enqueue(st, stage, in, out, i16))},
-    {"set_encoder", "encoder", "encode", false, GET(ptts_encoder, encode_batch), GET(ptts_encoder, encode_width),
-     GET(ptts_encoder, encode_width), ENQ(ptts_encoder, encode_enqueue(st, stage, in, out))},
-    {"set_packer", "packer", "flac", false, GET(ptts_flac, flac_batch), GET(ptts_flac, flac_width), GET(ptts_flac, flac_width),
-     ENQ(ptts_flac, flac_enqueue(st, stage, (const void *)in, out))},
+    {"set_resampler", "resampler", "resample", false, ENQ(ptts_resampler, resample_enqueue(st, stage, in, out, i16))},
+    {"set_stretcher", "stretcher", "stretch", false, ENQ(ptts_stretcher, stretch_enqueue(st, stage, in, out, i16, nullptr))},
+    {"set_pitcher", "pitcher", "pitch", false, ENQ(ptts_pitcher, pitch_enqueue(st, stage, in, out, i16, nullptr, nullptr))},
+    {"set_tone", "toner", "tone", true, ENQ(ptts_tone, tone_enqueue(st, stage, in, (float *)out))},
+    {"set_dynamics", "compressor", "dynamics", true, ENQ(ptts_dynamics, dyn_enqueue(st, stage, in, (float *)out))},
+    {"set_loudnorm", "normaliser", "loudnorm", true, ENQ(ptts_loudnorm, loud_enqueue(st, stage, in, (float *)out, nullptr))},
+    {"set_leveler", "leveler", "level", false, ENQ(ptts_leveler, level_enqueue(st, stage, in, out, i16))},
+    {"set_encoder", "encoder", "encode", false, ENQ(ptts_encoder, encode_enqueue(st, stage, in, out))},
+    {"set_packer", "packer", "flac", false, ENQ(ptts_flac, flac_enqueue(st, stage, (const void *)in, out))},
 };
-#undef GET
 #undef ENQ
+// what the chain reads of a stage: its batch and the widths of its lines (a stage's address is its StageBase's, ptts_stage.h)
+static const StageBase *base(const void *stage) { return (const StageBase *)stage; }
 
 // The stage that writes the encoder's input: the last one set of leveler, pitcher, stretcher, resampler; -1: none.  The
 // toner and the normaliser do not count, a leveler always follows them.
@@ -2238,9 +2228,9 @@ static int set_link(ptts_mimi_state *s, int kind, void *stage, float *in, void *
   if (stage) {
     if (!out) return fail(-1, set + "null output");
     if (k.f32_only && in == out) return fail(-1, set + "the stage does not work in place");
-    if (k.batch(stage) != s->B) return fail(-1, its + "batch is not the state's");
+    if (base(stage)->B != s->B) return fail(-1, its + "batch is not the state's");
     if (const char *msg = own()) return fail(-1, msg);
-    if (!in && k.in_width(stage) != s->rows[3]) return fail(-1, its + "frame length is not the state's");
+    if (!in && base(stage)->in_width != s->rows[3]) return fail(-1, its + "frame length is not the state's");
     bool fed = false;
     for (int i = 0; i < kind; i++) fed |= s->chain[i].stage != nullptr;
     if (in && !fed) {
@@ -2259,7 +2249,7 @@ static int set_link(ptts_mimi_state *s, int kind, void *stage, float *in, void *
 // out [B][out_max] is f32 or i16, device or pinned host
 extern "C" int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, void *out, int32_t is_i16) {
   // its own: one message for the batch and the frame length, in place of the two of set_link
-  if (s && rs && out && (resample_batch(rs) != s->B || resample_frame_samples(rs) != s->rows[3]))
+  if (s && rs && out && (base(rs)->B != s->B || base(rs)->in_width != s->rows[3]))
     return fail(-1, "set_resampler: the resampler's batch or frame length is not the state's");
   return set_link(s, CH_RS, rs, nullptr, out, is_i16);
 }
@@ -2267,8 +2257,8 @@ extern "C" int ptts_mimi_set_resampler(ptts_mimi_state *s, ptts_resampler *rs, v
 // its own: with d_in the resampler writes f32 into d_in instead of its own output, so its longest frame must be the stretcher's
 extern "C" int ptts_mimi_set_stretcher(ptts_mimi_state *s, ptts_stretcher *ts, float *d_in, void *out, int32_t is_i16) {
   return set_link(s, CH_TS, ts, d_in, out, is_i16, [&]() -> const char * {
-    const ptts_resampler *rs = (const ptts_resampler *)s->chain[CH_RS].stage;
-    if (d_in && (!rs || resample_out_max(rs) != stretch_in_max(ts)))
+    const StageBase *rs = base(s->chain[CH_RS].stage);
+    if (d_in && (!rs || rs->out_width != base(ts)->in_width))
       return "set_stretcher: an input buffer needs a resampler on the state whose longest frame is the stretcher's";
     return nullptr;
   });
@@ -2305,7 +2295,7 @@ extern "C" int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float
     if (!d_in && before >= 0) return "set_encoder: the state has output stages, the encoder needs an input buffer";
     if (d_in && before < 0)
       return "set_encoder: an input buffer needs a resampler, a stretcher, a pitcher or a leveler on the state";
-    if (d_in && kChain[before].out_width(s->chain[before].stage) != encode_width(en))
+    if (d_in && base(s->chain[before].stage)->out_width != base(en)->in_width)
       return "set_encoder: the encoder's width is not the widest line of the stage before it";
     return nullptr;
   });
@@ -2315,10 +2305,10 @@ extern "C" int ptts_mimi_set_encoder(ptts_mimi_state *s, ptts_encoder *en, float
 // buffer's address
 extern "C" int ptts_mimi_set_packer(ptts_mimi_state *s, ptts_flac *pk, void *d_in_bytes, void *out_bytes) {
   return set_link(s, CH_PK, pk, (float *)d_in_bytes, out_bytes, 0, [&]() -> const char * {
-    const ptts_encoder *en = (const ptts_encoder *)s->chain[CH_EN].stage;
+    const StageBase *en = base(s->chain[CH_EN].stage);
     if (!en) return "set_packer: a packer needs an encoder on the state";
     if (!d_in_bytes) return "set_packer: null input";
-    if (encode_width(en) != flac_width(pk)) return "set_packer: the packer's width is not the encoder's";
+    if (en->out_width != base(pk)->in_width) return "set_packer: the packer's width is not the encoder's";
     return nullptr;
   });
 }

@@ -9,6 +9,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "ptts_scan.h"
+
 #if defined(__HIPCC__)
 #define PTTS_DY_HD __host__ __device__
 #else
@@ -47,18 +49,12 @@ PTTS_DY_HD inline bool dyn_values_ok(double T, double k, double W, double M, dou
   return T >= -60.0 && T <= 0.0 && k >= 0.0 && k < 1.0 && W >= 0.0 && W <= 24.0 && M >= 0.0 && M <= 24.0 && aA > 0.0 &&
          aA < 1.0 && aR > 0.0 && aR < 1.0;
 }
-// Thread t of the first dy_threads(n) works on samples [t chunk, min((t + 1) chunk, n)): 1 <= chunk <= MAX_CHUNK,
-// (threads - 1) chunk < n <= threads chunk and threads <= PTTS_DY_THREADS.  A thread t >= threads has no sample.
-PTTS_DY_HD inline int dy_chunk(int n) { return (n + PTTS_DY_THREADS - 1) / PTTS_DY_THREADS; }
-PTTS_DY_HD inline int dy_threads(int n) { return (n + dy_chunk(n) - 1) / dy_chunk(n); }
-PTTS_DY_HD inline int dy_begin(int t, int chunk) { return t * chunk; }
-PTTS_DY_HD inline int dy_end(int t, int chunk, int n) { return (t + 1) * chunk < n ? (t + 1) * chunk : n; }
-// scan steps a frame of `threads` chunks needs: the smallest j with 2^j >= threads, <= PTTS_DY_SCAN
-PTTS_DY_HD inline int dy_steps(int threads) {
-  int j = 0;
-  while ((1 << j) < threads) ++j;
-  return j;
-}
+// The frame's partition over the threads (ptts_scan.h): chunk <= PTTS_DY_MAX_CHUNK, scan_steps <= PTTS_DY_SCAN
+PTTS_DY_HD inline int dy_chunk(int n) { return scan_chunk(n, PTTS_DY_THREADS); }
+PTTS_DY_HD inline int dy_threads(int n) { return scan_threads(n, PTTS_DY_THREADS); }
+PTTS_DY_HD inline int dy_begin(int t, int chunk) { return scan_begin(t, chunk); }
+PTTS_DY_HD inline int dy_end(int t, int chunk, int n) { return scan_end(t, chunk, n); }
+PTTS_DY_HD inline int dy_steps(int threads) { return scan_steps(threads); }
 
 // |x| in dBFS, clamped to [-120, 120]; a NaN compares false and is the floor
 PTTS_DY_HD inline double dy_level(double x) {
@@ -80,6 +76,21 @@ PTTS_DY_HD inline double dy_peak(double c, double aR, double p) {
   return c > q ? c : q;
 }
 PTTS_DY_HD inline double dy_smooth(double p, double aA, double s) { return aA * s + (1.0 - aA) * p; }
+// The two as the chunked scan's recurrences (ptts_scan.h): max-plus with pw = pwR, linear with pw = pwA
+struct DyPeak {
+  static constexpr int W = 1;
+  double aR;
+  const double *pw;  // [PTTS_DY_SCAN]
+  PTTS_DY_HD double step(double *s, double c) const { return s[0] = dy_peak(c, aR, s[0]); }
+  PTTS_DY_HD void join(int j, const double *e, double *s) const { s[0] = dy_peak(s[0], pw[j], e[0]); }
+};
+struct DySmooth {
+  static constexpr int W = 1;
+  double aA;
+  const double *pw;  // [PTTS_DY_SCAN]
+  PTTS_DY_HD double step(double *s, double p) const { return s[0] = dy_smooth(p, aA, s[0]); }
+  PTTS_DY_HD void join(int j, const double *e, double *s) const { s[0] += pw[j] * e[0]; }
+};
 // The gain of a sample whose smoothed reduction is s dB
 PTTS_DY_HD inline double dy_gain(double M, double s) { return exp((M - s) * PTTS_DY_K); }
 // One sample of the serial definition.  st = {p, s}; returns y.

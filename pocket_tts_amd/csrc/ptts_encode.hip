@@ -11,12 +11,10 @@
 //            memory, where a byte or short store costs many times the time per byte of a 16-byte one
 // Only the run that holds the row's end (n_b no multiple of 16) stores sample by sample, and a run past it stores nothing:
 // behind its n_b * bytes_per_sample bytes a row's line is not touched.
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_encode.h"
 
-struct ptts_encoder {
-  ptts_engine *e = nullptr;
-  int B = 0, width = 0;
+struct ptts_encoder : StageBase {  // no plans; in_width = out_width: the line's width in samples
   int *row_nc = nullptr;  // [B][2]: n, code
 };
 
@@ -83,18 +81,15 @@ __global__ void encode_set_row_kernel(int *row_nc, int row, int n, int code) {
   row_nc[2 * row + 1] = code;
 }
 
-int encode_batch(const ptts_encoder *en) { return en->B; }
-int encode_width(const ptts_encoder *en) { return en->width; }
-
 int encode_enqueue(hipStream_t st, ptts_encoder *en, const float *d_in, void *out_bytes) {
   if (!en || !d_in || !out_bytes) return fail(-1, "encode: null argument");
   if ((uintptr_t)out_bytes & 15) return fail(-1, "encode: the output is not aligned to 16 bytes");
   if ((uintptr_t)d_in & 3) return fail(-1, "encode: the input is not aligned to 4 bytes");
   const int B = en->B;
   {
-    ProfScope ps(st, "encode", 8.0 * B * en->width + 8.0 * B, 0);
-    encode_kernel<<<dim3(cdiv(en_runs(en->width), kEnThreads), B), kEnThreads, 0, st>>>(d_in, en->width, en->row_nc,
-                                                                                        (uint8_t *)out_bytes, en_pitch(en->width));
+    ProfScope ps(st, "encode", 8.0 * B * en->in_width + 8.0 * B, 0);
+    encode_kernel<<<dim3(cdiv(en_runs(en->in_width), kEnThreads), B), kEnThreads, 0, st>>>(d_in, en->in_width, en->row_nc,
+                                                                                        (uint8_t *)out_bytes, en_pitch(en->in_width));
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -103,48 +98,30 @@ int encode_enqueue(hipStream_t st, ptts_encoder *en, const float *d_in, void *ou
 extern "C" int ptts_encoder_create(ptts_engine *e, int32_t batch, int32_t width, ptts_encoder **out) {
   if (!e || !out) return fail(-1, "encoder_create: null argument");
   if (batch < 1 || batch > 65535 || width < 1 || width > (1 << 20)) return fail(-1, "encoder_create: batch or width out of range");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_encoder *en = new ptts_encoder();
-  en->e = e; en->B = batch; en->width = width;
+  StageLock lock;
+  ptts_encoder *en;
+  CHK(stage_new(e, batch, 0, width, width, lock, &en));
   std::vector<int> rows(2 * (size_t)batch);
   for (int b = 0; b < batch; ++b) { rows[2 * b] = width; rows[2 * b + 1] = 0; }  // (width, pcm_s16le)
-  hipError_t er = hipMalloc(&en->row_nc, rows.size() * sizeof(int));
-  if (er == hipSuccess) er = hipMemcpy(en->row_nc, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_encoder_destroy(en);
-    return fail(-2, std::string("encoder_create: ") + hipGetErrorString(er));
-  }
-  *out = en;
-  return 0;
+  stage_copy(*en, en->row_nc, rows.data(), rows.size());
+  return stage_finish(en, out, "encoder_create");
 }
 
-extern "C" void ptts_encoder_destroy(ptts_encoder *en) {
-  if (!en) return;
-  hipSetDevice(en->e->device);
-  hipDeviceSynchronize();
-  hipFree(en->row_nc);
-  delete en;
-}
+extern "C" void ptts_encoder_destroy(ptts_encoder *en) { stage_destroy(en); }
 
 extern "C" int ptts_encoder_set_row(ptts_encoder *en, int32_t row, int32_t n, int32_t code, void *stream) {
-  if (!en) return fail(-1, "encoder_set_row: null encoder");
-  if (row < 0 || row >= en->B) return fail(-1, "encoder_set_row: row out of range");
-  if (n < 1 || n > en->width)
-    return fail(-1, "encoder_set_row: n " + std::to_string(n) + " is not in [1, " + std::to_string(en->width) + "]");
+  CHK(stage_row_ok(en, "encoder_set_row", "encoder", row));
+  if (n < 1 || n > en->in_width)
+    return fail(-1, "encoder_set_row: n " + std::to_string(n) + " is not in [1, " + std::to_string(en->in_width) + "]");
   if (code < 0 || code >= PTTS_EN_CODES) return fail(-1, "encoder_set_row: code " + std::to_string(code) + " is not in [0, 3]");
-  ENGINE_LOCK(en->e);
-  HIPCHK(hipSetDevice(en->e->device));
+  StageLock lock;
+  CHK(stage_enter(en->e, lock));
   encode_set_row_kernel<<<1, 1, 0, S(en->e, stream)>>>(en->row_nc, row, n, code);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int ptts_encode_frame(ptts_encoder *en, const float *d_in, void *out_bytes, void *stream) {
-  if (!en || !d_in || !out_bytes) return fail(-1, "encode_frame: null argument");
-  ENGINE_LOCK(en->e);
-  HIPCHK(hipSetDevice(en->e->device));
-  bind_engine(en->e);
-  return encode_enqueue(S(en->e, stream), en, d_in, out_bytes);
+  return stage_frame(en, d_in && out_bytes, "encode_frame", stream,
+                     [&](hipStream_t st) { return encode_enqueue(st, en, d_in, out_bytes); });
 }

@@ -1,6 +1,8 @@
 // Launchers of the kernel families that live in their own translation units (compiled in parallel with ptts.hip, see
 // pocket_tts_amd/_lib.py::build).  Plain C++ functions: their callers (ptts.hip, ptts_dispatch.hip) never instantiate these
-// kernels themselves.
+// kernels themselves.  Of an output stage only its enqueue is declared here: what the stages' host sides share, and what
+// the output chain reads of a stage (batch, widths), is ptts_stage.h; the chunked scan of the toner's, the compressor's and
+// the normaliser's kernels is ptts_scan.h.
 #pragma once
 #include "ptts_kernels.h"
 
@@ -36,50 +38,36 @@ void pack_weight_split(hipStream_t st, const float *src, void *hi, void *lo, int
 // then the rows' histories <- the frame's tail.  Returns 0 or a negative error code (message recorded).
 struct ptts_resampler;
 int resample_enqueue(hipStream_t st, ptts_resampler *rs, const float *d_pcm, void *out, int is_i16);
-int resample_frame_samples(const ptts_resampler *rs);
-int resample_batch(const ptts_resampler *rs);
-int resample_out_max(const ptts_resampler *rs);
 
 // ---- ptts_stretch.hip: per-request speaking rate (streaming WSOLA time-stretch behind the codec or the resampler) -------
 // the frame's launch on `st`: d_in f32[B][in_max] (device) -> out f32 / i16 [B][out_max] (device or pinned host); d_delta
 // (i32 [B][k_max], or null) receives the hops' deltas.  Returns 0 or a negative error code (message recorded).
 struct ptts_stretcher;
 int stretch_enqueue(hipStream_t st, ptts_stretcher *ts, const float *d_in, void *out, int is_i16, int *d_delta);
-int stretch_batch(const ptts_stretcher *ts);
-int stretch_in_max(const ptts_stretcher *ts);
-int stretch_out_max(const ptts_stretcher *ts);
 
 // ---- ptts_level.hip: per-request output gain with a look-ahead peak limiter (the last output stage) ---------------------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host).  Returns 0 or
 // a negative error code (message recorded).
 struct ptts_leveler;
 int level_enqueue(hipStream_t st, ptts_leveler *lv, const float *d_in, void *out, int is_i16);
-int level_batch(const ptts_leveler *lv);
-int level_width(const ptts_leveler *lv);
 
 // ---- ptts_loud.hip: per-request loudness target (streaming BS.1770 normaliser, between the pitcher and the leveler) ------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> d_out f32[B][width] (device, never d_in); d_tap (f64 [B][4], or
 // null) receives each normalising row's completed sub-blocks, last L, last c and last Z.  Returns 0 or a negative error code.
 struct ptts_loudnorm;
 int loud_enqueue(hipStream_t st, ptts_loudnorm *ln, const float *d_in, float *d_out, double *d_tap);
-int loud_batch(const ptts_loudnorm *ln);
-int loud_width(const ptts_loudnorm *ln);
 
 // ---- ptts_tone.hip: per-request tone (a streaming cascade of biquad sections, between the pitcher and the normaliser) -----
 // the frame's launch on `st`: d_in f32[B][width] (device) -> d_out f32[B][width] (device, never d_in).  Returns 0 or a
 // negative error code (message recorded).
 struct ptts_tone;
 int tone_enqueue(hipStream_t st, ptts_tone *tn, const float *d_in, float *d_out);
-int tone_batch(const ptts_tone *tn);
-int tone_width(const ptts_tone *tn);
 
 // ---- ptts_dyn.hip: per-request dynamics (a streaming feed-forward compressor, between the toner and the normaliser) ------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> d_out f32[B][width] (device, never d_in).  Returns 0 or a
 // negative error code (message recorded).
 struct ptts_dynamics;
 int dyn_enqueue(hipStream_t st, ptts_dynamics *dy, const float *d_in, float *d_out);
-int dyn_batch(const ptts_dynamics *dy);
-int dyn_width(const ptts_dynamics *dy);
 
 // ---- ptts_pitch.hip: per-request pitch (streaming WSOLA + polyphase FIR, between the stretcher and the leveler) ---------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out f32 / i16 [B][width] (device or pinned host); d_delta
@@ -87,8 +75,6 @@ int dyn_width(const ptts_dynamics *dy);
 // Returns 0 or a negative error code (message recorded).
 struct ptts_pitcher;
 int pitch_enqueue(hipStream_t st, ptts_pitcher *ps, const float *d_in, void *out, int is_i16, int *d_delta, float *d_mid);
-int pitch_batch(const ptts_pitcher *ps);
-int pitch_width(const ptts_pitcher *ps);
 
 // ---- ptts_encode.hip: per-request output encoding (pcm_s16le, pcm_f32le, G.711 mu-law / A-law; the last output stage) -------
 // the frame's launch on `st`: d_in f32[B][width] (device) -> out_bytes u8[B][pitch] (device or pinned host, 16-byte aligned),
@@ -96,8 +82,6 @@ int pitch_width(const ptts_pitcher *ps);
 // negative error code (message recorded).
 struct ptts_encoder;
 int encode_enqueue(hipStream_t st, ptts_encoder *en, const float *d_in, void *out_bytes);
-int encode_batch(const ptts_encoder *en);
-int encode_width(const ptts_encoder *en);
 
 // ---- ptts_flac.hip: per-request output compression (FLAC frames; the packer behind the encoder) ----------------------------
 // the frame's launch on `st`: d_in_bytes u8[B][en_pitch(width)] (device, the encoder's output) -> out_bytes u8[B][fl_pitch(width)]
@@ -105,5 +89,3 @@ int encode_width(const ptts_encoder *en);
 // nbytes rounded up to 16.  Returns 0 or a negative error code (message recorded).
 struct ptts_flac;
 int flac_enqueue(hipStream_t st, ptts_flac *pk, const void *d_in_bytes, void *out_bytes);
-int flac_batch(const ptts_flac *pk);
-int flac_width(const ptts_flac *pk);

@@ -16,13 +16,11 @@
 // ORed in with LDS atomics (two lanes can share a word), the header by one lane, the CRC-16 as the XOR of each lane's table
 // CRC of its byte range times x^(8 * bytes behind it), and the stores.  Static LDS: 18.0 KB of samples, 9.1 KB of bit
 // buffer and 3 KB of tables and partial sums, whatever the row's n.
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_encode.h"
 #include "ptts_flac.h"
 
-struct ptts_flac {
-  ptts_engine *e = nullptr;
-  int B = 0, width = 0;
+struct ptts_flac : StageBase {  // no plans; in_width = out_width: the line's width in samples
   int *rows = nullptr;       // [B][kFlRow]
   int16_t *carry = nullptr;  // [B][width]: the previous line of a flac row
 };
@@ -223,16 +221,13 @@ __global__ void flac_set_row_kernel(int *rows, int row, int mode, int n, int bps
   rd[FL_COUNT] = 0; rd[FL_RATE] = rate;
 }
 
-int flac_batch(const ptts_flac *pk) { return pk->B; }
-int flac_width(const ptts_flac *pk) { return pk->width; }
-
 int flac_enqueue(hipStream_t st, ptts_flac *pk, const void *d_in_bytes, void *out_bytes) {
   if (!pk || !d_in_bytes || !out_bytes) return fail(-1, "flac: null argument");
   if (((uintptr_t)out_bytes | (uintptr_t)d_in_bytes) & 15) return fail(-1, "flac: the input or the output is not aligned to 16 bytes");
   {
-    ProfScope ps(st, "flac", 6.0 * pk->B * pk->width, 0);
-    flac_kernel<<<dim3(1, pk->B), kFlThreads, 0, st>>>((const uint8_t *)d_in_bytes, en_pitch(pk->width), pk->width, pk->rows,
-                                                       pk->carry, (uint8_t *)out_bytes, fl_pitch(pk->width));
+    ProfScope ps(st, "flac", 6.0 * pk->B * pk->in_width, 0);
+    flac_kernel<<<dim3(1, pk->B), kFlThreads, 0, st>>>((const uint8_t *)d_in_bytes, en_pitch(pk->in_width), pk->in_width, pk->rows,
+                                                       pk->carry, (uint8_t *)out_bytes, fl_pitch(pk->in_width));
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -241,47 +236,30 @@ int flac_enqueue(hipStream_t st, ptts_flac *pk, const void *d_in_bytes, void *ou
 extern "C" int ptts_flac_create(ptts_engine *e, int32_t batch, int32_t width, ptts_flac **out) {
   if (!e || !out) return fail(-1, "flac_create: null argument");
   if (batch < 1 || batch > 65535 || width < 1 || width > (1 << 20)) return fail(-1, "flac_create: batch or width out of range");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_flac *pk = new ptts_flac();
-  pk->e = e; pk->B = batch; pk->width = width;
+  StageLock lock;
+  ptts_flac *pk;
+  CHK(stage_new(e, batch, 0, width, width, lock, &pk));
   std::vector<int> rows(kFlRow * (size_t)batch, 0);
   for (int b = 0; b < batch; ++b) { rows[kFlRow * b + FL_N] = width; rows[kFlRow * b + FL_BPS] = 2; }  // pass-through, pcm_s16le
-  hipError_t er = hipMalloc(&pk->rows, rows.size() * sizeof(int));
-  if (er == hipSuccess) er = hipMemcpy(pk->rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMalloc(&pk->carry, (size_t)batch * width * sizeof(int16_t));
-  if (er == hipSuccess) er = hipMemset(pk->carry, 0, (size_t)batch * width * sizeof(int16_t));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_flac_destroy(pk);
-    return fail(-2, std::string("flac_create: ") + hipGetErrorString(er));
-  }
-  *out = pk;
-  return 0;
+  stage_copy(*pk, pk->rows, rows.data(), rows.size());
+  stage_zeros(*pk, pk->carry, (size_t)batch * width);
+  return stage_finish(pk, out, "flac_create");
 }
 
-extern "C" void ptts_flac_destroy(ptts_flac *pk) {
-  if (!pk) return;
-  hipSetDevice(pk->e->device);
-  hipDeviceSynchronize();
-  hipFree(pk->rows);
-  hipFree(pk->carry);
-  delete pk;
-}
+extern "C" void ptts_flac_destroy(ptts_flac *pk) { stage_destroy(pk); }
 
 extern "C" int ptts_flac_set_row(ptts_flac *pk, int32_t row, int32_t mode, int32_t n, int32_t bps, int32_t rate, int32_t preroll,
                                  int32_t first_block, void *stream) {
-  if (!pk) return fail(-1, "flac_set_row: null packer");
-  if (row < 0 || row >= pk->B) return fail(-1, "flac_set_row: row out of range");
+  CHK(stage_row_ok(pk, "flac_set_row", "packer", row));
   if (mode != 0 && mode != 1) return fail(-1, "flac_set_row: mode " + std::to_string(mode) + " is not 0 (pass-through) or 1 (flac)");
   int off = 0, lead = 0;
   if (mode == 0) {
-    if (n < 1 || n > pk->width)
-      return fail(-1, "flac_set_row: n " + std::to_string(n) + " is not in [1, " + std::to_string(pk->width) + "]");
+    if (n < 1 || n > pk->in_width)
+      return fail(-1, "flac_set_row: n " + std::to_string(n) + " is not in [1, " + std::to_string(pk->in_width) + "]");
     if (bps != 1 && bps != 2 && bps != 4) return fail(-1, "flac_set_row: bytes per sample " + std::to_string(bps) + " is not 1, 2 or 4");
     rate = preroll = first_block = 0;
   } else {
-    const int hi = pk->width < PTTS_FL_MAX_N ? pk->width : PTTS_FL_MAX_N;
+    const int hi = pk->in_width < PTTS_FL_MAX_N ? pk->in_width : PTTS_FL_MAX_N;
     if (n < PTTS_FL_MIN_N || n > hi)
       return fail(-1, "flac_set_row: n " + std::to_string(n) + " is not in [" + std::to_string(PTTS_FL_MIN_N) + ", " +
                           std::to_string(hi) + "]");
@@ -292,17 +270,14 @@ extern "C" int ptts_flac_set_row(ptts_flac *pk, int32_t row, int32_t mode, int32
     off = preroll % n;
     lead = (preroll + n - 1) / n;
   }
-  ENGINE_LOCK(pk->e);
-  HIPCHK(hipSetDevice(pk->e->device));
+  StageLock lock;
+  CHK(stage_enter(pk->e, lock));
   flac_set_row_kernel<<<1, 1, 0, S(pk->e, stream)>>>(pk->rows, row, mode, n, bps, off, lead, first_block, rate);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int ptts_flac_frame(ptts_flac *pk, const void *d_in_bytes, void *out_bytes, void *stream) {
-  if (!pk || !d_in_bytes || !out_bytes) return fail(-1, "flac_frame: null argument");
-  ENGINE_LOCK(pk->e);
-  HIPCHK(hipSetDevice(pk->e->device));
-  bind_engine(pk->e);
-  return flac_enqueue(S(pk->e, stream), pk, d_in_bytes, out_bytes);
+  return stage_frame(pk, d_in_bytes && out_bytes, "flac_frame", stream,
+                     [&](hipStream_t st) { return flac_enqueue(st, pk, d_in_bytes, out_bytes); });
 }

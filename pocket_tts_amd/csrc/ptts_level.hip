@@ -17,15 +17,11 @@
 // is no second launch.  Bypass rows copy their line and exit.
 #include <cstring>
 
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_level.h"
 
-struct ptts_leveler {
-  ptts_engine *e = nullptr;
-  int B = 0, n_plans = 0, width = 0;
+struct ptts_leveler : StageBase {  // row_plan < 0: bypass
   LvPlan *plans = nullptr;   // [n_plans]
-  int *row_plan = nullptr;   // [B] index into plans, < 0: bypass
-  int *row_drain = nullptr;  // [B] != 0: the row's incoming frames count as zeros
   float *row_gc = nullptr;   // [B][2]: G, C
   float *cu = nullptr;       // [B][PTTS_LV_MAX_LA]: the row's last LA samples of u at the front of its line
   float *ce = nullptr;       // [B][PTTS_LV_MAX_LA]: its last LA samples of e
@@ -148,17 +144,12 @@ __global__ __launch_bounds__(PTTS_LV_MAX_LA) void level_set_row_kernel(int *row_
   ce[(size_t)row * PTTS_LV_MAX_LA + tid] = 1.f;
 }
 
-__global__ void level_set_drain_kernel(int *row_drain, int row, int on) { row_drain[row] = on; }
-
-int level_batch(const ptts_leveler *lv) { return lv->B; }
-int level_width(const ptts_leveler *lv) { return lv->width; }
-
 int level_enqueue(hipStream_t st, ptts_leveler *lv, const float *d_in, void *out, int is_i16) {
   if (!lv || !d_in || !out) return fail(-1, "level: null argument");
   const int B = lv->B;
   {
-    ProfScope ps(st, "level", 4.0 * B * (lv->width + 4.0 * PTTS_LV_MAX_LA) + (is_i16 ? 2.0 : 4.0) * B * lv->width, 0);
-    level_kernel<<<B, kLvThreads, 0, st>>>(d_in, lv->width, lv->plans, lv->n_plans, lv->row_plan, lv->row_drain, lv->row_gc,
+    ProfScope ps(st, "level", 4.0 * B * (lv->in_width + 4.0 * PTTS_LV_MAX_LA) + (is_i16 ? 2.0 : 4.0) * B * lv->in_width, 0);
+    level_kernel<<<B, kLvThreads, 0, st>>>(d_in, lv->in_width, lv->plans, lv->n_plans, lv->row_plan, lv->row_drain, lv->row_gc,
                                            lv->cu, lv->ce, lv->row_d, is_i16 ? nullptr : (float *)out,
                                            is_i16 ? (int16_t *)out : nullptr);
   }
@@ -184,53 +175,28 @@ extern "C" int ptts_leveler_create(ptts_engine *e, int32_t batch, const int32_t 
     plans[i] = P;
     width = std::max(width, (int)P.n);
   }
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_leveler *lv = new ptts_leveler();
-  lv->e = e; lv->B = batch; lv->n_plans = n_plans; lv->width = width;
+  StageLock lock;
+  ptts_leveler *lv;
+  CHK(stage_new(e, batch, n_plans, width, width, lock, &lv));
   const size_t line = (size_t)batch * PTTS_LV_MAX_LA;
-  std::vector<float> ones(line, 1.0f);
-  std::vector<int> bypass(batch, -1);
-  hipError_t er = hipMalloc(&lv->plans, (size_t)n_plans * sizeof(LvPlan));
-  if (er == hipSuccess) er = hipMalloc(&lv->row_plan, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&lv->row_drain, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&lv->row_gc, (size_t)batch * 2 * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&lv->cu, line * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&lv->ce, line * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&lv->row_d, (size_t)batch * sizeof(float));
-  if (er == hipSuccess) er = hipMemcpy(lv->plans, plans.data(), (size_t)n_plans * sizeof(LvPlan), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(lv->row_plan, bypass.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(lv->row_drain, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(lv->row_gc, 0, (size_t)batch * 2 * sizeof(float));
-  if (er == hipSuccess) er = hipMemset(lv->cu, 0, line * sizeof(float));
-  if (er == hipSuccess) er = hipMemcpy(lv->ce, ones.data(), line * sizeof(float), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(lv->row_d, 0, (size_t)batch * sizeof(float));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_leveler_destroy(lv);
-    return fail(-2, std::string("leveler_create: ") + hipGetErrorString(er));
-  }
-  *out = lv;
-  return 0;
+  stage_copy(*lv, lv->plans, plans.data(), n_plans);
+  stage_fill(*lv, lv->row_plan, batch, -1);
+  stage_zeros(*lv, lv->row_drain, batch);
+  stage_zeros(*lv, lv->row_gc, (size_t)batch * 2);
+  stage_zeros(*lv, lv->cu, line);
+  stage_fill(*lv, lv->ce, line, 1.0f);
+  stage_zeros(*lv, lv->row_d, batch);
+  return stage_finish(lv, out, "leveler_create");
 }
 
-extern "C" void ptts_leveler_destroy(ptts_leveler *lv) {
-  if (!lv) return;
-  hipSetDevice(lv->e->device);
-  hipDeviceSynchronize();
-  hipFree(lv->plans); hipFree(lv->row_plan); hipFree(lv->row_drain); hipFree(lv->row_gc); hipFree(lv->cu); hipFree(lv->ce);
-  hipFree(lv->row_d);
-  delete lv;
-}
+extern "C" void ptts_leveler_destroy(ptts_leveler *lv) { stage_destroy(lv); }
 
 extern "C" int ptts_leveler_set_row(ptts_leveler *lv, int32_t row, int32_t plan_index, float gain, float ceiling, void *stream) {
-  if (!lv) return fail(-1, "leveler_set_row: null leveler");
-  if (row < 0 || row >= lv->B) return fail(-1, "leveler_set_row: row out of range");
-  if (plan_index < -1 || plan_index >= lv->n_plans) return fail(-1, "leveler_set_row: plan index out of range");
+  CHK(stage_row_ok(lv, "leveler_set_row", "leveler", row, "plan", plan_index, -1));
   if (plan_index >= 0 && !(gain > 0.f && gain <= 16.f && ceiling > 0.f && ceiling <= 1.f))
     return fail(-1, "leveler_set_row: the gain must be in (0, 16] and the ceiling in (0, 1]");
-  ENGINE_LOCK(lv->e);
-  HIPCHK(hipSetDevice(lv->e->device));
+  StageLock lock;
+  CHK(stage_enter(lv->e, lock));
   level_set_row_kernel<<<1, PTTS_LV_MAX_LA, 0, S(lv->e, stream)>>>(lv->row_plan, lv->row_drain, lv->row_gc, lv->cu, lv->ce,
                                                                   lv->row_d, row, plan_index, plan_index < 0 ? 1.f : gain,
                                                                   plan_index < 0 ? 1.f : ceiling);
@@ -239,19 +205,10 @@ extern "C" int ptts_leveler_set_row(ptts_leveler *lv, int32_t row, int32_t plan_
 }
 
 extern "C" int ptts_leveler_set_row_drain(ptts_leveler *lv, int32_t row, int32_t on, void *stream) {
-  if (!lv) return fail(-1, "leveler_set_row_drain: null leveler");
-  if (row < 0 || row >= lv->B) return fail(-1, "leveler_set_row_drain: row out of range");
-  ENGINE_LOCK(lv->e);
-  HIPCHK(hipSetDevice(lv->e->device));
-  level_set_drain_kernel<<<1, 1, 0, S(lv->e, stream)>>>(lv->row_drain, row, on != 0);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return stage_set_row_drain(lv, "leveler_set_row_drain", "leveler", row, on, stream);
 }
 
 extern "C" int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_i16, void *stream) {
-  if (!lv || !d_in || !out) return fail(-1, "level_frame: null argument");
-  ENGINE_LOCK(lv->e);
-  HIPCHK(hipSetDevice(lv->e->device));
-  bind_engine(lv->e);
-  return level_enqueue(S(lv->e, stream), lv, d_in, out, is_i16 != 0);
+  return stage_frame(lv, d_in && out, "level_frame", stream,
+                     [&](hipStream_t st) { return level_enqueue(st, lv, d_in, out, is_i16 != 0); });
 }

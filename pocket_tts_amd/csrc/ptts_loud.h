@@ -10,6 +10,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "ptts_scan.h"
+
 #if defined(__HIPCC__)
 #define PTTS_LD_HD __host__ __device__
 #else
@@ -45,12 +47,11 @@ PTTS_LD_HD inline bool ld_plan_ok(int rate, int n) {
 }
 PTTS_LD_HD inline int ld_sub(int rate) { return rate / 10; }                 // 800 <= S <= 4800
 PTTS_LD_HD inline int ld_delay(int rate) { return 4 * (rate / 10); }         // 3200 <= D <= PTTS_LD_MAX_D
-// Thread t of the first ld_threads(n) works on samples [t chunk, min((t + 1) chunk, n)): 1 <= chunk <= MAX_CHUNK,
-// (threads - 1) chunk < n <= threads chunk and threads <= PTTS_LD_THREADS.
-PTTS_LD_HD inline int ld_chunk(int n) { return (n + PTTS_LD_THREADS - 1) / PTTS_LD_THREADS; }
-PTTS_LD_HD inline int ld_threads(int n) { return (n + ld_chunk(n) - 1) / ld_chunk(n); }
-PTTS_LD_HD inline int ld_begin(int t, int chunk) { return t * chunk; }
-PTTS_LD_HD inline int ld_end(int t, int chunk, int n) { return (t + 1) * chunk < n ? (t + 1) * chunk : n; }
+// The frame's partition over the threads (ptts_scan.h): chunk <= PTTS_LD_MAX_CHUNK, scan_steps <= PTTS_LD_SCAN
+PTTS_LD_HD inline int ld_chunk(int n) { return scan_chunk(n, PTTS_LD_THREADS); }
+PTTS_LD_HD inline int ld_threads(int n) { return scan_threads(n, PTTS_LD_THREADS); }
+PTTS_LD_HD inline int ld_begin(int t, int chunk) { return scan_begin(t, chunk); }
+PTTS_LD_HD inline int ld_end(int t, int chunk, int n) { return scan_end(t, chunk, n); }
 
 // One sample of the 4-state recurrence: both biquads in transposed direct form II.  Returns w.
 PTTS_LD_HD inline double ld_step(const double *c, double *s, double x) {
@@ -72,6 +73,14 @@ PTTS_LD_HD inline void ld_mat_acc(const double *M, const double *v, double *acc)
     acc[r] += hi + lo;
   }
 }
+// The K-weighting as the chunked scan's recurrence (ptts_scan.h)
+struct LdWeighting {
+  static constexpr int W = 4;
+  double c[PTTS_LD_COEFS];
+  const double *pw;  // [PTTS_LD_SCAN][32]
+  PTTS_LD_HD double step(double *s, double x) const { return ld_step(c, s, x); }
+  PTTS_LD_HD void join(int j, const double *e, double *s) const { ld_mat_acc(pw + 32 * j, e, s); }
+};
 
 // Sample i of a frame (0 <= i < n) that begins at position pos of the open sub-block (0 <= pos < S) lies in the frame's
 // segment ld_seg: 0 <= seg <= (S - 1 + n - 1) / S <= PTTS_LD_MAX_DONE < PTTS_LD_SEGS.  A thread's chunk (<= 8 < S samples)

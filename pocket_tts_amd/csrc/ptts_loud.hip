@@ -18,7 +18,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_loud.h"
 
 constexpr int kLdDoubles = 12;  // per row: s[4], the open sub-block's partial sum, z[4], last L, last Z, the target T
@@ -28,12 +28,8 @@ static_assert((1 << PTTS_LD_SCAN) == PTTS_LD_THREADS, "the scan covers every thr
 static_assert(PTTS_LD_SEGS <= kLdWaves, "one wave per sub-block a frame touches");
 static_assert(PTTS_LD_HIST <= PTTS_LD_THREADS, "one history entry per thread");
 
-struct ptts_loudnorm {
-  ptts_engine *e = nullptr;
-  int B = 0, n_plans = 0, width = 0;
+struct ptts_loudnorm : StageBase {  // row_plan < 0: bypass
   LdPlan *plans = nullptr;    // [n_plans]
-  int *row_plan = nullptr;    // [B] index into plans, < 0: bypass
-  int *row_drain = nullptr;   // [B] != 0: the row's incoming frames count as zeros
   double *row_d = nullptr;    // [B][kLdDoubles]
   int *row_i = nullptr;       // [B][kLdInts]
   float *row_c = nullptr;     // [B][3]: the gains of the last three completed sub-blocks
@@ -58,7 +54,11 @@ __global__ __launch_bounds__(PTTS_LD_THREADS) void loud_kernel(const float *__re
                                                                int *__restrict__ row_i, float *__restrict__ row_c,
                                                                double *__restrict__ hist, float *__restrict__ ring,
                                                                double *__restrict__ tap) {
-  __shared__ double E[PTTS_LD_THREADS][4];  // chunk end states, scanned in place
+  // chunk end states (scan_block): two halves of 32 KB, one barrier per scan step where one half scanned in place took two.
+  // With P and the small arrays below the workgroup holds 82,552 B of LDS, more than the 64 KB of older parts and within the
+  // 160 KB of a gfx950 CU, which the kernel's 123 VGPRs limit to one such workgroup anyway
+  __shared__ double E[2 * PTTS_LD_THREADS * LdWeighting::W];
+  static_assert(sizeof(E) + sizeof(double) * 2 * PTTS_LD_THREADS <= 96 * 1024, "E and P leave room in a CU's 160 KB of LDS");
   __shared__ double P[PTTS_LD_THREADS][2];  // a thread's share of its first and its second sub-block
   __shared__ double segsum[kLdWaves];
   __shared__ double wsum[2][kLdWaves];
@@ -84,8 +84,9 @@ __global__ __launch_bounds__(PTTS_LD_THREADS) void loud_kernel(const float *__re
   float *rrow = ring + (size_t)row * PTTS_LD_MAX_D;
   const int pos = ri[0], cnt = ri[1], head = ri[2];
   const double part = rd[4], T = rd[11];
-  double coef[PTTS_LD_COEFS];
-  for (int q = 0; q < PTTS_LD_COEFS; ++q) coef[q] = Pl.coef[q];
+  LdWeighting kw;
+  for (int q = 0; q < PTTS_LD_COEFS; ++q) kw.c[q] = Pl.coef[q];
+  kw.pw = Pl.pw[0];
   if (tid == 0) {
     for (int q = 0; q < 4; ++q) zr[q] = rd[5 + q];
     shL = rd[9]; shLastZ = rd[10];
@@ -93,47 +94,18 @@ __global__ __launch_bounds__(PTTS_LD_THREADS) void loud_kernel(const float *__re
   }
   const int done = ld_done(pos, n, S);  // <= PTTS_LD_MAX_DONE
 
-  // chunk: the thread's samples, and their end state from a zero state (thread 0: from the carried one)
+  // chunk, scan, energy: the thread's samples; the re-run from the true state adds w^2 to the thread's two shares, and the
+  // last thread leaves the row's state after the frame in rd[0 .. 3]
   const int i0 = ld_begin(tid, chunk), i1 = tid < nT ? ld_end(tid, chunk, n) : i0;
   double xr[PTTS_LD_MAX_CHUNK];
 #pragma unroll
   for (int q = 0; q < PTTS_LD_MAX_CHUNK; ++q) xr[q] = (!drain && i0 + q < i1) ? (double)x[i0 + q] : 0.0;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (tid == 0) for (int q = 0; q < 4; ++q) s[q] = rd[q];
-  double s0[4] = {s[0], s[1], s[2], s[3]};
-  if (tid < nT) {
-#pragma unroll
-    for (int q = 0; q < PTTS_LD_MAX_CHUNK; ++q) if (i0 + q < i1) ld_step(coef, s, xr[q]);
-    for (int q = 0; q < 4; ++q) E[tid][q] = s[q];
-  }
-  __syncthreads();
-  // scan: E[t] = sum over j <= t of A^(chunk (t - j)) e_j
-  for (int k = 0; (1 << k) < nT; ++k) {
-    const int off = 1 << k;
-    const bool on = tid < nT && tid >= off;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    if (on) for (int q = 0; q < 4; ++q) v[q] = E[tid - off][q];
-    __syncthreads();
-    if (on) {
-      ld_mat_acc(Pl.pw[k], v, s);
-      for (int q = 0; q < 4; ++q) E[tid][q] = s[q];
-    }
-    __syncthreads();
-  }
-  // energy: re-run the chunk from its true state
-  if (tid > 0 && tid < nT) for (int q = 0; q < 4; ++q) s0[q] = E[tid - 1][q];
   const int seg0 = ld_seg(pos, i0, S);
   double pa = 0.0, pb = 0.0;
-  if (tid < nT) {
-#pragma unroll
-    for (int q = 0; q < PTTS_LD_MAX_CHUNK; ++q)
-      if (i0 + q < i1) {
-        const double w = ld_step(coef, s0, xr[q]);
-        if (ld_seg(pos, i0 + q, S) == seg0) pa += w * w;
-        else pb += w * w;
-      }
-    if (tid == nT - 1) for (int q = 0; q < 4; ++q) rd[q] = s0[q];  // the row's state after the frame
-  }
+  scan_block<PTTS_LD_MAX_CHUNK, PTTS_LD_THREADS>(kw, E, tid, nT, scan_steps(nT), rd, xr, i1 - i0, [&](int q, double w) {
+    if (ld_seg(pos, i0 + q, S) == seg0) pa += w * w;
+    else pb += w * w;
+  });
   P[tid][0] = pa; P[tid][1] = pb;
   __syncthreads();
   if (wave <= done) {  // wave g: the frame's g-th sub-block, threads in ascending order per lane, then across the lanes
@@ -247,18 +219,13 @@ __global__ __launch_bounds__(PTTS_LD_THREADS) void loud_set_row_kernel(int *row_
   for (int i = tid; i < PTTS_LD_MAX_D; i += PTTS_LD_THREADS) ring[(size_t)row * PTTS_LD_MAX_D + i] = 0.f;
 }
 
-__global__ void loud_set_drain_kernel(int *row_drain, int row, int on) { row_drain[row] = on; }
-
-int loud_batch(const ptts_loudnorm *ln) { return ln->B; }
-int loud_width(const ptts_loudnorm *ln) { return ln->width; }
-
 int loud_enqueue(hipStream_t st, ptts_loudnorm *ln, const float *d_in, float *d_out, double *d_tap) {
   if (!ln || !d_in || !d_out) return fail(-1, "loudnorm: null argument");
   if (d_in == d_out) return fail(-1, "loudnorm: the stage does not work in place");
   const int B = ln->B;
   {
-    ProfScope ps(st, "loudnorm", 4.0 * B * (3.0 * ln->width + 2.0 * PTTS_LD_MAX_D) + 8.0 * B * PTTS_LD_HIST, 0);
-    loud_kernel<<<B, PTTS_LD_THREADS, 0, st>>>(d_in, d_out, ln->width, ln->plans, ln->n_plans, ln->row_plan, ln->row_drain,
+    ProfScope ps(st, "loudnorm", 4.0 * B * (3.0 * ln->in_width + 2.0 * PTTS_LD_MAX_D) + 8.0 * B * PTTS_LD_HIST, 0);
+    loud_kernel<<<B, PTTS_LD_THREADS, 0, st>>>(d_in, d_out, ln->in_width, ln->plans, ln->n_plans, ln->row_plan, ln->row_drain,
                                                ln->row_d, ln->row_i, ln->row_c, ln->hist, ln->ring, d_tap);
   }
   HIPCHK(hipGetLastError());
@@ -287,53 +254,28 @@ extern "C" int ptts_loudnorm_create(ptts_engine *e, int32_t batch, const int32_t
     std::memcpy(P.pw, d + PTTS_LD_COEFS, sizeof(P.pw));
     width = std::max(width, (int)P.n);
   }
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_loudnorm *ln = new ptts_loudnorm();
-  ln->e = e; ln->B = batch; ln->n_plans = n_plans; ln->width = width;
-  std::vector<int> bypass(batch, -1);
-  hipError_t er = hipMalloc(&ln->plans, (size_t)n_plans * sizeof(LdPlan));
-  if (er == hipSuccess) er = hipMalloc(&ln->row_plan, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ln->row_drain, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ln->row_d, (size_t)batch * kLdDoubles * sizeof(double));
-  if (er == hipSuccess) er = hipMalloc(&ln->row_i, (size_t)batch * kLdInts * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ln->row_c, (size_t)batch * 3 * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ln->hist, (size_t)batch * PTTS_LD_HIST * sizeof(double));
-  if (er == hipSuccess) er = hipMalloc(&ln->ring, (size_t)batch * PTTS_LD_MAX_D * sizeof(float));
-  if (er == hipSuccess) er = hipMemcpy(ln->plans, plans.data(), (size_t)n_plans * sizeof(LdPlan), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(ln->row_plan, bypass.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(ln->row_drain, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ln->row_d, 0, (size_t)batch * kLdDoubles * sizeof(double));
-  if (er == hipSuccess) er = hipMemset(ln->row_i, 0, (size_t)batch * kLdInts * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ln->row_c, 0, (size_t)batch * 3 * sizeof(float));
-  if (er == hipSuccess) er = hipMemset(ln->hist, 0, (size_t)batch * PTTS_LD_HIST * sizeof(double));
-  if (er == hipSuccess) er = hipMemset(ln->ring, 0, (size_t)batch * PTTS_LD_MAX_D * sizeof(float));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_loudnorm_destroy(ln);
-    return fail(-2, std::string("loudnorm_create: ") + hipGetErrorString(er));
-  }
-  *out = ln;
-  return 0;
+  StageLock lock;
+  ptts_loudnorm *ln;
+  CHK(stage_new(e, batch, n_plans, width, width, lock, &ln));
+  stage_copy(*ln, ln->plans, plans.data(), n_plans);
+  stage_fill(*ln, ln->row_plan, batch, -1);
+  stage_zeros(*ln, ln->row_drain, batch);
+  stage_zeros(*ln, ln->row_d, (size_t)batch * kLdDoubles);
+  stage_zeros(*ln, ln->row_i, (size_t)batch * kLdInts);
+  stage_zeros(*ln, ln->row_c, (size_t)batch * 3);
+  stage_zeros(*ln, ln->hist, (size_t)batch * PTTS_LD_HIST);
+  stage_zeros(*ln, ln->ring, (size_t)batch * PTTS_LD_MAX_D);
+  return stage_finish(ln, out, "loudnorm_create");
 }
 
-extern "C" void ptts_loudnorm_destroy(ptts_loudnorm *ln) {
-  if (!ln) return;
-  hipSetDevice(ln->e->device);
-  hipDeviceSynchronize();
-  hipFree(ln->plans); hipFree(ln->row_plan); hipFree(ln->row_drain); hipFree(ln->row_d); hipFree(ln->row_i); hipFree(ln->row_c);
-  hipFree(ln->hist); hipFree(ln->ring);
-  delete ln;
-}
+extern "C" void ptts_loudnorm_destroy(ptts_loudnorm *ln) { stage_destroy(ln); }
 
 extern "C" int ptts_loudnorm_set_row(ptts_loudnorm *ln, int32_t row, int32_t plan_index, double target_lufs, void *stream) {
-  if (!ln) return fail(-1, "loudnorm_set_row: null normaliser");
-  if (row < 0 || row >= ln->B) return fail(-1, "loudnorm_set_row: row out of range");
-  if (plan_index < -1 || plan_index >= ln->n_plans) return fail(-1, "loudnorm_set_row: plan index out of range");
+  CHK(stage_row_ok(ln, "loudnorm_set_row", "normaliser", row, "plan", plan_index, -1));
   if (plan_index >= 0 && !(target_lufs >= -40.0 && target_lufs <= -10.0))
     return fail(-1, "loudnorm_set_row: the target must be in [-40, -10] LUFS");
-  ENGINE_LOCK(ln->e);
-  HIPCHK(hipSetDevice(ln->e->device));
+  StageLock lock;
+  CHK(stage_enter(ln->e, lock));
   loud_set_row_kernel<<<1, PTTS_LD_THREADS, 0, S(ln->e, stream)>>>(ln->row_plan, ln->row_drain, ln->row_d, ln->row_i, ln->row_c,
                                                                   ln->ring, row, plan_index, plan_index < 0 ? 0.0 : target_lufs);
   HIPCHK(hipGetLastError());
@@ -341,19 +283,10 @@ extern "C" int ptts_loudnorm_set_row(ptts_loudnorm *ln, int32_t row, int32_t pla
 }
 
 extern "C" int ptts_loudnorm_set_row_drain(ptts_loudnorm *ln, int32_t row, int32_t on, void *stream) {
-  if (!ln) return fail(-1, "loudnorm_set_row_drain: null normaliser");
-  if (row < 0 || row >= ln->B) return fail(-1, "loudnorm_set_row_drain: row out of range");
-  ENGINE_LOCK(ln->e);
-  HIPCHK(hipSetDevice(ln->e->device));
-  loud_set_drain_kernel<<<1, 1, 0, S(ln->e, stream)>>>(ln->row_drain, row, on != 0);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return stage_set_row_drain(ln, "loudnorm_set_row_drain", "normaliser", row, on, stream);
 }
 
 extern "C" int ptts_loudnorm_frame(ptts_loudnorm *ln, const float *d_in, float *d_out, double *d_tap, void *stream) {
-  if (!ln || !d_in || !d_out) return fail(-1, "loudnorm_frame: null argument");
-  ENGINE_LOCK(ln->e);
-  HIPCHK(hipSetDevice(ln->e->device));
-  bind_engine(ln->e);
-  return loud_enqueue(S(ln->e, stream), ln, d_in, d_out, d_tap);
+  return stage_frame(ln, d_in && d_out, "loudnorm_frame", stream,
+                     [&](hipStream_t st) { return loud_enqueue(st, ln, d_in, d_out, d_tap); });
 }

@@ -11,18 +11,14 @@
 //              line is row-private: the workgroup that wrote it reads it back, no other block touches it
 //   state      the same workgroup writes the row's carried samples, carry, delta and the line's new history
 // Rows on an identity plan copy their frame and exit.
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_pitch.h"
 
-struct ptts_pitcher {
-  ptts_engine *e = nullptr;
-  int B = 0, n_plans = 0, width = 0, mid_max = 0, k_max = 0, lds_floats = 0;
-  std::vector<PtPlan> h_plans;
+struct ptts_pitcher : StageBase {
+  int mid_max = 0, k_max = 0, lds_floats = 0;
   float *windows = nullptr;  // the plans' W = 2 Hs window floats, one after the other
   float *tables = nullptr;   // the plans' [Q][T] polyphase tables, one after the other
   PtPlan *plans = nullptr;   // [n_plans]
-  int *row_plan = nullptr;   // [B] index into plans
-  int *row_drain = nullptr;  // [B] != 0: the row's incoming frames count as zeros
   int *row_delta = nullptr;  // [B][2]: delta of the row's last hop, and whether the row has had a hop at all
   float *hist = nullptr;     // [B][PTTS_TS_HIST]: the row's last `reach` input samples at the front of its line
   float *carry = nullptr;    // [B][PTTS_TS_MAX_HS]: second half of the row's last segment
@@ -151,19 +147,14 @@ __global__ __launch_bounds__(kPtThreads) void pitch_set_row_kernel(int *row_plan
   for (int i = tid; i < PTTS_PT_HIST; i += kPtThreads) mid[(size_t)row * (PTTS_PT_HIST + mid_max) + i] = 0.f;
 }
 
-__global__ void pitch_set_drain_kernel(int *row_drain, int row, int on) { row_drain[row] = on; }
-
-int pitch_batch(const ptts_pitcher *ps) { return ps->B; }
-int pitch_width(const ptts_pitcher *ps) { return ps->width; }
-
 int pitch_enqueue(hipStream_t st, ptts_pitcher *ps, const float *d_in, void *out, int is_i16, int *d_delta, float *d_mid) {
   if (!ps || !d_in || !out) return fail(-1, "pitch: null argument");
   const int B = ps->B;
   {
-    ProfScope prof(st, "pitch", 4.0 * B * (ps->width + 2.0 * PTTS_TS_HIST + 2.0 * ps->mid_max) + (is_i16 ? 2.0 : 4.0) * B * ps->width,
+    ProfScope prof(st, "pitch", 4.0 * B * (ps->in_width + 2.0 * PTTS_TS_HIST + 2.0 * ps->mid_max) + (is_i16 ? 2.0 : 4.0) * B * ps->in_width,
                    0);
     pitch_kernel<<<B, kPtThreads, (size_t)ps->lds_floats * sizeof(float), st>>>(
-        d_in, ps->width, ps->plans, ps->n_plans, ps->windows, ps->tables, ps->row_plan, ps->row_drain, ps->row_delta, ps->hist,
+        d_in, ps->in_width, ps->plans, ps->n_plans, ps->windows, ps->tables, ps->row_plan, ps->row_drain, ps->row_delta, ps->hist,
         ps->carry, ps->mid, ps->mid_max, is_i16 ? nullptr : (float *)out, is_i16 ? (int16_t *)out : nullptr, d_delta, ps->k_max,
         d_mid);
   }
@@ -197,54 +188,28 @@ extern "C" int ptts_pitcher_create(ptts_engine *e, int32_t batch, const int32_t 
   }
   if (off != n_window_floats) return fail(-1, "pitcher_create: the windows do not hold sum(2 * Hs) floats");
   if (toff != n_table_floats) return fail(-1, "pitcher_create: the tables do not hold sum(Q * T) floats");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_pitcher *ps = new ptts_pitcher();
-  ps->e = e; ps->B = batch; ps->n_plans = n_plans; ps->width = width; ps->mid_max = mid_max; ps->k_max = k_max;
-  ps->lds_floats = lds; ps->h_plans = plans;
-  const size_t line = (size_t)PTTS_PT_HIST + mid_max;
-  hipError_t er = hipMalloc(&ps->windows, (size_t)off * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ps->tables, (size_t)toff * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ps->plans, (size_t)n_plans * sizeof(PtPlan));
-  if (er == hipSuccess) er = hipMalloc(&ps->row_plan, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ps->row_drain, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ps->row_delta, (size_t)batch * 2 * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ps->hist, (size_t)batch * PTTS_TS_HIST * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ps->carry, (size_t)batch * PTTS_TS_MAX_HS * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ps->mid, (size_t)batch * line * sizeof(float));
-  if (er == hipSuccess) er = hipMemcpy(ps->windows, h_windows, (size_t)off * sizeof(float), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(ps->tables, h_tables, (size_t)toff * sizeof(float), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(ps->plans, plans.data(), (size_t)n_plans * sizeof(PtPlan), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(ps->row_plan, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ps->row_drain, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ps->row_delta, 0, (size_t)batch * 2 * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ps->hist, 0, (size_t)batch * PTTS_TS_HIST * sizeof(float));
-  if (er == hipSuccess) er = hipMemset(ps->carry, 0, (size_t)batch * PTTS_TS_MAX_HS * sizeof(float));
-  if (er == hipSuccess) er = hipMemset(ps->mid, 0, (size_t)batch * line * sizeof(float));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_pitcher_destroy(ps);
-    return fail(-2, std::string("pitcher_create: ") + hipGetErrorString(er));
-  }
-  *out = ps;
-  return 0;
+  StageLock lock;
+  ptts_pitcher *ps;
+  CHK(stage_new(e, batch, n_plans, width, width, lock, &ps));
+  ps->mid_max = mid_max; ps->k_max = k_max; ps->lds_floats = lds;
+  stage_copy(*ps, ps->windows, h_windows, (size_t)off);
+  stage_copy(*ps, ps->tables, h_tables, (size_t)toff);
+  stage_copy(*ps, ps->plans, plans.data(), n_plans);
+  stage_zeros(*ps, ps->row_plan, batch);
+  stage_zeros(*ps, ps->row_drain, batch);
+  stage_zeros(*ps, ps->row_delta, (size_t)batch * 2);
+  stage_zeros(*ps, ps->hist, (size_t)batch * PTTS_TS_HIST);
+  stage_zeros(*ps, ps->carry, (size_t)batch * PTTS_TS_MAX_HS);
+  stage_zeros(*ps, ps->mid, (size_t)batch * (PTTS_PT_HIST + mid_max));
+  return stage_finish(ps, out, "pitcher_create");
 }
 
-extern "C" void ptts_pitcher_destroy(ptts_pitcher *ps) {
-  if (!ps) return;
-  hipSetDevice(ps->e->device);
-  hipDeviceSynchronize();
-  hipFree(ps->windows); hipFree(ps->tables); hipFree(ps->plans); hipFree(ps->row_plan); hipFree(ps->row_drain);
-  hipFree(ps->row_delta); hipFree(ps->hist); hipFree(ps->carry); hipFree(ps->mid);
-  delete ps;
-}
+extern "C" void ptts_pitcher_destroy(ptts_pitcher *ps) { stage_destroy(ps); }
 
 extern "C" int ptts_pitcher_set_row(ptts_pitcher *ps, int32_t row, int32_t plan_index, void *stream) {
-  if (!ps) return fail(-1, "pitcher_set_row: null pitcher");
-  if (row < 0 || row >= ps->B) return fail(-1, "pitcher_set_row: row out of range");
-  if (plan_index < 0 || plan_index >= ps->n_plans) return fail(-1, "pitcher_set_row: plan index out of range");
-  ENGINE_LOCK(ps->e);
-  HIPCHK(hipSetDevice(ps->e->device));
+  CHK(stage_row_ok(ps, "pitcher_set_row", "pitcher", row, "plan", plan_index, 0));
+  StageLock lock;
+  CHK(stage_enter(ps->e, lock));
   pitch_set_row_kernel<<<1, kPtThreads, 0, S(ps->e, stream)>>>(ps->row_plan, ps->row_drain, ps->row_delta, ps->hist, ps->carry,
                                                               ps->mid, ps->mid_max, row, plan_index);
   HIPCHK(hipGetLastError());
@@ -252,20 +217,11 @@ extern "C" int ptts_pitcher_set_row(ptts_pitcher *ps, int32_t row, int32_t plan_
 }
 
 extern "C" int ptts_pitcher_set_row_drain(ptts_pitcher *ps, int32_t row, int32_t on, void *stream) {
-  if (!ps) return fail(-1, "pitcher_set_row_drain: null pitcher");
-  if (row < 0 || row >= ps->B) return fail(-1, "pitcher_set_row_drain: row out of range");
-  ENGINE_LOCK(ps->e);
-  HIPCHK(hipSetDevice(ps->e->device));
-  pitch_set_drain_kernel<<<1, 1, 0, S(ps->e, stream)>>>(ps->row_drain, row, on != 0);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return stage_set_row_drain(ps, "pitcher_set_row_drain", "pitcher", row, on, stream);
 }
 
 extern "C" int ptts_pitch_frame(ptts_pitcher *ps, const float *d_in, void *out, int32_t is_i16, int32_t *d_delta, float *d_mid,
                                 void *stream) {
-  if (!ps || !d_in || !out) return fail(-1, "pitch_frame: null argument");
-  ENGINE_LOCK(ps->e);
-  HIPCHK(hipSetDevice(ps->e->device));
-  bind_engine(ps->e);
-  return pitch_enqueue(S(ps->e, stream), ps, d_in, out, is_i16 != 0, d_delta, d_mid);
+  return stage_frame(ps, d_in && out, "pitch_frame", stream,
+                     [&](hipStream_t st) { return pitch_enqueue(st, ps, d_in, out, is_i16 != 0, d_delta, d_mid); });
 }

@@ -7,16 +7,12 @@
 //                          row's rate
 //   resample_carry_kernel  hist[row] <- the frame's last PTTS_RS_HIST samples
 // The history is never written by the launch that reads it: the blocks of one row run concurrently.
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_resample.h"
 
-struct ptts_resampler {
-  ptts_engine *e = nullptr;
-  int B = 0, fs = 0, n_rates = 0, out_max = 0;
-  std::vector<RsRate> h_rates;
+struct ptts_resampler : StageBase {  // a plan is a rate; in_width: the codec's frame_samples, out_width: out_max
   float *tables = nullptr;  // the rates' [up][T] tables, one after the other
-  RsRate *rates = nullptr;  // [n_rates]
-  int *row_rate = nullptr;  // [B] index into rates
+  RsRate *rates = nullptr;  // [n_plans]
   float *hist = nullptr;    // [B][PTTS_RS_HIST]
 };
 
@@ -60,17 +56,13 @@ __global__ __launch_bounds__(PTTS_RS_HIST) void resample_set_row_kernel(int *row
   hist[(size_t)row * PTTS_RS_HIST + threadIdx.x] = 0.f;
 }
 
-int resample_frame_samples(const ptts_resampler *rs) { return rs->fs; }
-int resample_batch(const ptts_resampler *rs) { return rs->B; }
-int resample_out_max(const ptts_resampler *rs) { return rs->out_max; }
-
 int resample_enqueue(hipStream_t st, ptts_resampler *rs, const float *d_pcm, void *out, int is_i16) {
   if (!rs || !d_pcm || !out) return fail(-1, "resample: null argument");
-  const int B = rs->B, fs = rs->fs;
+  const int B = rs->B, fs = rs->in_width, out_max = rs->out_width;
   {
-    ProfScope ps(st, "resample", 4.0 * B * (fs + PTTS_RS_HIST) + (is_i16 ? 2.0 : 4.0) * B * rs->out_max, 0);
-    resample_kernel<<<dim3(cdiv(rs->out_max, 256), B), 256, (size_t)(PTTS_RS_HIST + fs) * sizeof(float), st>>>(
-        d_pcm, rs->hist, rs->tables, rs->rates, rs->row_rate, rs->n_rates, fs, rs->out_max, is_i16 ? nullptr : (float *)out,
+    ProfScope ps(st, "resample", 4.0 * B * (fs + PTTS_RS_HIST) + (is_i16 ? 2.0 : 4.0) * B * out_max, 0);
+    resample_kernel<<<dim3(cdiv(out_max, 256), B), 256, (size_t)(PTTS_RS_HIST + fs) * sizeof(float), st>>>(
+        d_pcm, rs->hist, rs->tables, rs->rates, rs->row_plan, rs->n_plans, fs, out_max, is_i16 ? nullptr : (float *)out,
         is_i16 ? (int16_t *)out : nullptr);
   }
   {
@@ -102,50 +94,28 @@ extern "C" int ptts_resampler_create(ptts_engine *e, int32_t batch, const int32_
     out_max = std::max(out_max, (int)rates[i].out_n);
   }
   if (off != n_table_floats) return fail(-1, "resampler_create: the tables do not hold sum(up * taps) floats");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_resampler *rs = new ptts_resampler();
-  rs->e = e; rs->B = batch; rs->fs = fs; rs->n_rates = n_rates; rs->out_max = out_max; rs->h_rates = rates;
-  hipError_t er = hipMalloc(&rs->tables, (size_t)off * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&rs->rates, (size_t)n_rates * sizeof(RsRate));
-  if (er == hipSuccess) er = hipMalloc(&rs->row_rate, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&rs->hist, (size_t)batch * PTTS_RS_HIST * sizeof(float));
-  if (er == hipSuccess) er = hipMemcpy(rs->tables, h_tables, (size_t)off * sizeof(float), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(rs->rates, rates.data(), (size_t)n_rates * sizeof(RsRate), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(rs->row_rate, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(rs->hist, 0, (size_t)batch * PTTS_RS_HIST * sizeof(float));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_resampler_destroy(rs);
-    return fail(-2, std::string("resampler_create: ") + hipGetErrorString(er));
-  }
-  *out = rs;
-  return 0;
+  StageLock lock;
+  ptts_resampler *rs;
+  CHK(stage_new(e, batch, n_rates, fs, out_max, lock, &rs));
+  stage_copy(*rs, rs->tables, h_tables, (size_t)off);
+  stage_copy(*rs, rs->rates, rates.data(), n_rates);
+  stage_zeros(*rs, rs->row_plan, batch);
+  stage_zeros(*rs, rs->hist, (size_t)batch * PTTS_RS_HIST);
+  return stage_finish(rs, out, "resampler_create");
 }
 
-extern "C" void ptts_resampler_destroy(ptts_resampler *rs) {
-  if (!rs) return;
-  hipSetDevice(rs->e->device);
-  hipDeviceSynchronize();
-  hipFree(rs->tables); hipFree(rs->rates); hipFree(rs->row_rate); hipFree(rs->hist);
-  delete rs;
-}
+extern "C" void ptts_resampler_destroy(ptts_resampler *rs) { stage_destroy(rs); }
 
 extern "C" int ptts_resampler_set_row(ptts_resampler *rs, int32_t row, int32_t rate_index, void *stream) {
-  if (!rs) return fail(-1, "resampler_set_row: null resampler");
-  if (row < 0 || row >= rs->B) return fail(-1, "resampler_set_row: row out of range");
-  if (rate_index < 0 || rate_index >= rs->n_rates) return fail(-1, "resampler_set_row: rate index out of range");
-  ENGINE_LOCK(rs->e);
-  HIPCHK(hipSetDevice(rs->e->device));
-  resample_set_row_kernel<<<1, PTTS_RS_HIST, 0, S(rs->e, stream)>>>(rs->row_rate, rs->hist, row, rate_index);
+  CHK(stage_row_ok(rs, "resampler_set_row", "resampler", row, "rate", rate_index, 0));
+  StageLock lock;
+  CHK(stage_enter(rs->e, lock));
+  resample_set_row_kernel<<<1, PTTS_RS_HIST, 0, S(rs->e, stream)>>>(rs->row_plan, rs->hist, row, rate_index);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int ptts_resample_frame(ptts_resampler *rs, const float *d_pcm_in, void *out, int32_t is_i16, void *stream) {
-  if (!rs || !d_pcm_in || !out) return fail(-1, "resample_frame: null argument");
-  ENGINE_LOCK(rs->e);
-  HIPCHK(hipSetDevice(rs->e->device));
-  bind_engine(rs->e);
-  return resample_enqueue(S(rs->e, stream), rs, d_pcm_in, out, is_i16 != 0);
+  return stage_frame(rs, d_pcm_in && out, "resample_frame", stream,
+                     [&](hipStream_t st) { return resample_enqueue(st, rs, d_pcm_in, out, is_i16 != 0); });
 }

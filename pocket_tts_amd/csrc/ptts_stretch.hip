@@ -8,17 +8,13 @@
 //   state      after the last read the same workgroup writes the row's carried samples, carry and delta: no other block
 //              reads them, so there is no second launch
 // Rows on an identity plan copy their frame and exit.
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_stretch.h"
 
-struct ptts_stretcher {
-  ptts_engine *e = nullptr;
-  int B = 0, n_plans = 0, in_max = 0, out_max = 0, k_max = 0, lds_floats = 0;
-  std::vector<TsPlan> h_plans;
+struct ptts_stretcher : StageBase {  // in_width: in_max, out_width: out_max
+  int k_max = 0, lds_floats = 0;
   float *windows = nullptr;  // the plans' W = 2 Hs window floats, one after the other
   TsPlan *plans = nullptr;   // [n_plans]
-  int *row_plan = nullptr;   // [B] index into plans
-  int *row_drain = nullptr;  // [B] != 0: the row's incoming frames count as zeros
   int *row_delta = nullptr;  // [B][2]: delta of the row's last hop, and whether the row has had a hop at all
   float *hist = nullptr;     // [B][PTTS_TS_HIST]: the row's last `reach` input samples at the front of its line
   float *carry = nullptr;    // [B][PTTS_TS_MAX_HS]: second half of the row's last segment
@@ -133,20 +129,14 @@ __global__ __launch_bounds__(kTsThreads) void stretch_set_row_kernel(int *row_pl
   for (int i = tid; i < PTTS_TS_MAX_HS; i += kTsThreads) carry[(size_t)row * PTTS_TS_MAX_HS + i] = 0.f;
 }
 
-__global__ void stretch_set_drain_kernel(int *row_drain, int row, int on) { row_drain[row] = on; }
-
-int stretch_batch(const ptts_stretcher *ts) { return ts->B; }
-int stretch_in_max(const ptts_stretcher *ts) { return ts->in_max; }
-int stretch_out_max(const ptts_stretcher *ts) { return ts->out_max; }
-
 int stretch_enqueue(hipStream_t st, ptts_stretcher *ts, const float *d_in, void *out, int is_i16, int *d_delta) {
   if (!ts || !d_in || !out) return fail(-1, "stretch: null argument");
   const int B = ts->B;
   {
-    ProfScope ps(st, "stretch", 4.0 * B * (ts->in_max + 2.0 * PTTS_TS_HIST) + (is_i16 ? 2.0 : 4.0) * B * ts->out_max, 0);
+    ProfScope ps(st, "stretch", 4.0 * B * (ts->in_width + 2.0 * PTTS_TS_HIST) + (is_i16 ? 2.0 : 4.0) * B * ts->out_width, 0);
     stretch_kernel<<<B, kTsThreads, (size_t)ts->lds_floats * sizeof(float), st>>>(
-        d_in, ts->in_max, ts->plans, ts->n_plans, ts->windows, ts->row_plan, ts->row_drain, ts->row_delta, ts->hist, ts->carry,
-        is_i16 ? nullptr : (float *)out, is_i16 ? (int16_t *)out : nullptr, ts->out_max, d_delta, ts->k_max);
+        d_in, ts->in_width, ts->plans, ts->n_plans, ts->windows, ts->row_plan, ts->row_drain, ts->row_delta, ts->hist, ts->carry,
+        is_i16 ? nullptr : (float *)out, is_i16 ? (int16_t *)out : nullptr, ts->out_width, d_delta, ts->k_max);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -175,49 +165,26 @@ extern "C" int ptts_stretcher_create(ptts_engine *e, int32_t batch, const int32_
     if (!id) lds = std::max(lds, plans[i].reach + n_in);  // <= PTTS_TS_WINDOW (ts_plan_ok)
   }
   if (off != n_window_floats) return fail(-1, "stretcher_create: the windows do not hold sum(2 * Hs) floats");
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_stretcher *ts = new ptts_stretcher();
-  ts->e = e; ts->B = batch; ts->n_plans = n_plans; ts->in_max = in_max; ts->out_max = out_max; ts->k_max = k_max;
-  ts->lds_floats = lds; ts->h_plans = plans;
-  hipError_t er = hipMalloc(&ts->windows, (size_t)off * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ts->plans, (size_t)n_plans * sizeof(TsPlan));
-  if (er == hipSuccess) er = hipMalloc(&ts->row_plan, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ts->row_drain, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ts->row_delta, (size_t)batch * 2 * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&ts->hist, (size_t)batch * PTTS_TS_HIST * sizeof(float));
-  if (er == hipSuccess) er = hipMalloc(&ts->carry, (size_t)batch * PTTS_TS_MAX_HS * sizeof(float));
-  if (er == hipSuccess) er = hipMemcpy(ts->windows, h_windows, (size_t)off * sizeof(float), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(ts->plans, plans.data(), (size_t)n_plans * sizeof(TsPlan), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(ts->row_plan, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ts->row_drain, 0, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ts->row_delta, 0, (size_t)batch * 2 * sizeof(int));
-  if (er == hipSuccess) er = hipMemset(ts->hist, 0, (size_t)batch * PTTS_TS_HIST * sizeof(float));
-  if (er == hipSuccess) er = hipMemset(ts->carry, 0, (size_t)batch * PTTS_TS_MAX_HS * sizeof(float));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_stretcher_destroy(ts);
-    return fail(-2, std::string("stretcher_create: ") + hipGetErrorString(er));
-  }
-  *out = ts;
-  return 0;
+  StageLock lock;
+  ptts_stretcher *ts;
+  CHK(stage_new(e, batch, n_plans, in_max, out_max, lock, &ts));
+  ts->k_max = k_max; ts->lds_floats = lds;
+  stage_copy(*ts, ts->windows, h_windows, (size_t)off);
+  stage_copy(*ts, ts->plans, plans.data(), n_plans);
+  stage_zeros(*ts, ts->row_plan, batch);
+  stage_zeros(*ts, ts->row_drain, batch);
+  stage_zeros(*ts, ts->row_delta, (size_t)batch * 2);
+  stage_zeros(*ts, ts->hist, (size_t)batch * PTTS_TS_HIST);
+  stage_zeros(*ts, ts->carry, (size_t)batch * PTTS_TS_MAX_HS);
+  return stage_finish(ts, out, "stretcher_create");
 }
 
-extern "C" void ptts_stretcher_destroy(ptts_stretcher *ts) {
-  if (!ts) return;
-  hipSetDevice(ts->e->device);
-  hipDeviceSynchronize();
-  hipFree(ts->windows); hipFree(ts->plans); hipFree(ts->row_plan); hipFree(ts->row_drain); hipFree(ts->row_delta);
-  hipFree(ts->hist); hipFree(ts->carry);
-  delete ts;
-}
+extern "C" void ptts_stretcher_destroy(ptts_stretcher *ts) { stage_destroy(ts); }
 
 extern "C" int ptts_stretcher_set_row(ptts_stretcher *ts, int32_t row, int32_t plan_index, void *stream) {
-  if (!ts) return fail(-1, "stretcher_set_row: null stretcher");
-  if (row < 0 || row >= ts->B) return fail(-1, "stretcher_set_row: row out of range");
-  if (plan_index < 0 || plan_index >= ts->n_plans) return fail(-1, "stretcher_set_row: plan index out of range");
-  ENGINE_LOCK(ts->e);
-  HIPCHK(hipSetDevice(ts->e->device));
+  CHK(stage_row_ok(ts, "stretcher_set_row", "stretcher", row, "plan", plan_index, 0));
+  StageLock lock;
+  CHK(stage_enter(ts->e, lock));
   stretch_set_row_kernel<<<1, kTsThreads, 0, S(ts->e, stream)>>>(ts->row_plan, ts->row_drain, ts->row_delta, ts->hist, ts->carry,
                                                                 row, plan_index);
   HIPCHK(hipGetLastError());
@@ -225,20 +192,11 @@ extern "C" int ptts_stretcher_set_row(ptts_stretcher *ts, int32_t row, int32_t p
 }
 
 extern "C" int ptts_stretcher_set_row_drain(ptts_stretcher *ts, int32_t row, int32_t on, void *stream) {
-  if (!ts) return fail(-1, "stretcher_set_row_drain: null stretcher");
-  if (row < 0 || row >= ts->B) return fail(-1, "stretcher_set_row_drain: row out of range");
-  ENGINE_LOCK(ts->e);
-  HIPCHK(hipSetDevice(ts->e->device));
-  stretch_set_drain_kernel<<<1, 1, 0, S(ts->e, stream)>>>(ts->row_drain, row, on != 0);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return stage_set_row_drain(ts, "stretcher_set_row_drain", "stretcher", row, on, stream);
 }
 
 extern "C" int ptts_stretch_frame(ptts_stretcher *ts, const float *d_in, void *out, int32_t is_i16, int32_t *d_delta,
                                   void *stream) {
-  if (!ts || !d_in || !out) return fail(-1, "stretch_frame: null argument");
-  ENGINE_LOCK(ts->e);
-  HIPCHK(hipSetDevice(ts->e->device));
-  bind_engine(ts->e);
-  return stretch_enqueue(S(ts->e, stream), ts, d_in, out, is_i16 != 0, d_delta);
+  return stage_frame(ts, d_in && out, "stretch_frame", stream,
+                     [&](hipStream_t st) { return stretch_enqueue(st, ts, d_in, out, is_i16 != 0, d_delta); });
 }

@@ -8,6 +8,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "ptts_scan.h"
+
 #if defined(__HIPCC__)
 #define PTTS_TN_HD __host__ __device__
 #else
@@ -38,18 +40,12 @@ PTTS_TN_HD inline bool tn_plan_ok(int rate, int n, int K) {
   if (rate < PTTS_TN_MIN_RATE || rate > PTTS_TN_MAX_RATE) return false;
   return n >= 1 && n <= PTTS_TN_MAX_N && K >= 1 && K <= PTTS_TN_MAX_SECTIONS;
 }
-// Thread t of the first tn_threads(n) works on samples [t chunk, min((t + 1) chunk, n)): 1 <= chunk <= MAX_CHUNK,
-// (threads - 1) chunk < n <= threads chunk and threads <= PTTS_TN_THREADS.  A thread t >= threads has no sample.
-PTTS_TN_HD inline int tn_chunk(int n) { return (n + PTTS_TN_THREADS - 1) / PTTS_TN_THREADS; }
-PTTS_TN_HD inline int tn_threads(int n) { return (n + tn_chunk(n) - 1) / tn_chunk(n); }
-PTTS_TN_HD inline int tn_begin(int t, int chunk) { return t * chunk; }
-PTTS_TN_HD inline int tn_end(int t, int chunk, int n) { return (t + 1) * chunk < n ? (t + 1) * chunk : n; }
-// scan steps a frame of `threads` chunks needs: the smallest j with 2^j >= threads, <= PTTS_TN_SCAN
-PTTS_TN_HD inline int tn_steps(int threads) {
-  int j = 0;
-  while ((1 << j) < threads) ++j;
-  return j;
-}
+// The frame's partition over the threads (ptts_scan.h): chunk <= PTTS_TN_MAX_CHUNK, scan_steps <= PTTS_TN_SCAN
+PTTS_TN_HD inline int tn_chunk(int n) { return scan_chunk(n, PTTS_TN_THREADS); }
+PTTS_TN_HD inline int tn_threads(int n) { return scan_threads(n, PTTS_TN_THREADS); }
+PTTS_TN_HD inline int tn_begin(int t, int chunk) { return scan_begin(t, chunk); }
+PTTS_TN_HD inline int tn_end(int t, int chunk, int n) { return scan_end(t, chunk, n); }
+PTTS_TN_HD inline int tn_steps(int threads) { return scan_steps(threads); }
 
 // One sample of one section in transposed direct form II.  Returns y.
 PTTS_TN_HD inline double tn_step(const double *c, double *s, double x) {
@@ -63,3 +59,11 @@ PTTS_TN_HD inline void tn_mat_acc(const double *M, const double *v, double *acc)
   acc[0] += M[0] * v[0] + M[1] * v[1];
   acc[1] += M[2] * v[0] + M[3] * v[1];
 }
+// Section k of a plan as the chunked scan's recurrence (ptts_scan.h): c = coef[k], pw = pw[k]
+struct TnSection {
+  static constexpr int W = 2;
+  double c[PTTS_TN_COEFS];
+  const double *pw;  // [PTTS_TN_SCAN][4]
+  PTTS_TN_HD double step(double *s, double x) const { return tn_step(c, s, x); }
+  PTTS_TN_HD void join(int j, const double *e, double *s) const { tn_mat_acc(pw + 4 * j, e, s); }
+};

@@ -22,24 +22,21 @@
 #include <cmath>
 #include <cstring>
 
-#include "ptts_host.h"
+#include "ptts_stage.h"
 #include "ptts_tone.h"
 
 static_assert((1 << PTTS_TN_SCAN) == PTTS_TN_THREADS, "the scan covers every thread");
 static_assert(PTTS_TN_MAX_CHUNK * PTTS_TN_THREADS == PTTS_TN_MAX_N, "a frame of the largest size is covered");
 
-struct ptts_tone {
-  ptts_engine *e = nullptr;
-  int B = 0, n_plans = 0, width = 0;
+struct ptts_tone : StageBase {  // row_plan < 0: bypass
   TnPlan *plans = nullptr;   // [n_plans]
-  int *row_plan = nullptr;   // [B] index into plans, < 0: bypass
   double *row_s = nullptr;   // [B][PTTS_TN_ROW_DOUBLES]: the sections' states
 };
 
 __global__ __launch_bounds__(PTTS_TN_THREADS) void tone_kernel(const float *__restrict__ in, float *__restrict__ out, int width,
                                                                const TnPlan *__restrict__ plans, int n_plans,
                                                                const int *__restrict__ row_plan, double *__restrict__ row_s) {
-  __shared__ double E[2][PTTS_TN_THREADS][2];  // chunk end states: a scan step reads one half and writes the other
+  __shared__ double E[2 * PTTS_TN_THREADS * TnSection::W];  // chunk end states (scan_block)
   const int row = blockIdx.x, tid = threadIdx.x;
   const float *x = in + (size_t)row * width;  // n <= width (ptts_tone_create)
   float *y = out + (size_t)row * width;
@@ -50,48 +47,20 @@ __global__ __launch_bounds__(PTTS_TN_THREADS) void tone_kernel(const float *__re
   }
   const TnPlan &Pl = plans[min(pi, n_plans - 1)];
   const int n = Pl.n, K = Pl.K, chunk = Pl.chunk, nT = Pl.threads;  // tn_plan_ok, ptts_tone_create
-  const int steps = tn_steps(nT);                                   // <= PTTS_TN_SCAN
+  const int steps = tn_steps(nT);                                 // <= PTTS_TN_SCAN
   double *rs = row_s + (size_t)row * PTTS_TN_ROW_DOUBLES;
-  const bool on = tid < nT;
-  const int i0 = tn_begin(tid, chunk), i1 = on ? tn_end(tid, chunk, n) : i0;  // i1 <= n
+  const int i0 = tn_begin(tid, chunk), i1 = tid < nT ? tn_end(tid, chunk, n) : i0;  // i1 <= n
   double xr[PTTS_TN_MAX_CHUNK];
 #pragma unroll
   for (int q = 0; q < PTTS_TN_MAX_CHUNK; ++q) xr[q] = i0 + q < i1 ? (double)x[i0 + q] : 0.0;
 
   for (int k = 0; k < K; ++k) {  // k < PTTS_TN_MAX_SECTIONS
-    double c[PTTS_TN_COEFS];
-    for (int q = 0; q < PTTS_TN_COEFS; ++q) c[q] = Pl.coef[k][q];
-    // chunk: the end state from a zero state (thread 0: from the carried one)
-    double s[2] = {0.0, 0.0};
-    if (tid == 0) { s[0] = rs[2 * k]; s[1] = rs[2 * k + 1]; }
-    double s0[2] = {s[0], s[1]};
-    if (on) {
-#pragma unroll
-      for (int q = 0; q < PTTS_TN_MAX_CHUNK; ++q) if (i0 + q < i1) tn_step(c, s, xr[q]);
-      E[0][tid][0] = s[0]; E[0][tid][1] = s[1];
-    }
-    __syncthreads();
-    // scan: E[t] = sum over u <= t of A^(chunk (t - u)) e_u
-    int cur = 0;
-    for (int j = 0; j < steps; ++j) {
-      const int off = 1 << j;
-      if (on) {
-        if (tid >= off) {
-          const double v[2] = {E[cur][tid - off][0], E[cur][tid - off][1]};
-          tn_mat_acc(Pl.pw[k][j], v, s);
-        }
-        E[cur ^ 1][tid][0] = s[0]; E[cur ^ 1][tid][1] = s[1];
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-    // re-run the chunk from its true state
-    if (on) {
-      if (tid > 0) { s0[0] = E[cur][tid - 1][0]; s0[1] = E[cur][tid - 1][1]; }
-#pragma unroll
-      for (int q = 0; q < PTTS_TN_MAX_CHUNK; ++q) if (i0 + q < i1) xr[q] = tn_step(c, s0, xr[q]);
-      if (tid == nT - 1) { rs[2 * k] = s0[0]; rs[2 * k + 1] = s0[1]; }  // the section's state after the frame
-    }
+    TnSection sec;
+    for (int q = 0; q < PTTS_TN_COEFS; ++q) sec.c[q] = Pl.coef[k][q];
+    sec.pw = Pl.pw[k][0];
+    // chunk, scan, re-run: y in place of x; the last thread leaves the section's state after the frame in rs
+    scan_block<PTTS_TN_MAX_CHUNK, PTTS_TN_THREADS>(sec, E, tid, nT, steps, rs + 2 * k, xr, i1 - i0,
+                                                   [&](int q, double y) { xr[q] = y; });
     __syncthreads();  // every read of E is done before the next section writes it
   }
 #pragma unroll
@@ -104,16 +73,13 @@ __global__ void tone_set_row_kernel(int *row_plan, double *row_s, int row, int p
   if (tid < PTTS_TN_ROW_DOUBLES) row_s[(size_t)row * PTTS_TN_ROW_DOUBLES + tid] = 0.0;
 }
 
-int tone_batch(const ptts_tone *tn) { return tn->B; }
-int tone_width(const ptts_tone *tn) { return tn->width; }
-
 int tone_enqueue(hipStream_t st, ptts_tone *tn, const float *d_in, float *d_out) {
   if (!tn || !d_in || !d_out) return fail(-1, "tone: null argument");
   if (d_in == d_out) return fail(-1, "tone: the stage does not work in place");
   const int B = tn->B;
   {
-    ProfScope ps(st, "tone", 4.0 * B * 2.0 * tn->width + 8.0 * B * 2.0 * PTTS_TN_ROW_DOUBLES, 0);
-    tone_kernel<<<B, PTTS_TN_THREADS, 0, st>>>(d_in, d_out, tn->width, tn->plans, tn->n_plans, tn->row_plan, tn->row_s);
+    ProfScope ps(st, "tone", 4.0 * B * 2.0 * tn->in_width + 8.0 * B * 2.0 * PTTS_TN_ROW_DOUBLES, 0);
+    tone_kernel<<<B, PTTS_TN_THREADS, 0, st>>>(d_in, d_out, tn->in_width, tn->plans, tn->n_plans, tn->row_plan, tn->row_s);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -146,49 +112,26 @@ extern "C" int ptts_tone_create(ptts_engine *e, int32_t batch, int32_t line, con
                           " samples, longer than the line of " + std::to_string(line));
     width = std::max(width, (int)P.n);
   }
-  ENGINE_LOCK(e);
-  HIPCHK(hipSetDevice(e->device));
-  ptts_tone *tn = new ptts_tone();
-  tn->e = e; tn->B = batch; tn->n_plans = n_plans; tn->width = width;
-  std::vector<int> bypass(batch, -1);
-  hipError_t er = hipMalloc(&tn->plans, (size_t)n_plans * sizeof(TnPlan));
-  if (er == hipSuccess) er = hipMalloc(&tn->row_plan, (size_t)batch * sizeof(int));
-  if (er == hipSuccess) er = hipMalloc(&tn->row_s, (size_t)batch * PTTS_TN_ROW_DOUBLES * sizeof(double));
-  if (er == hipSuccess) er = hipMemcpy(tn->plans, plans.data(), (size_t)n_plans * sizeof(TnPlan), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemcpy(tn->row_plan, bypass.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice);
-  if (er == hipSuccess) er = hipMemset(tn->row_s, 0, (size_t)batch * PTTS_TN_ROW_DOUBLES * sizeof(double));
-  if (er == hipSuccess) er = hipDeviceSynchronize();
-  if (er != hipSuccess) {
-    ptts_tone_destroy(tn);
-    return fail(-2, std::string("tone_create: ") + hipGetErrorString(er));
-  }
-  *out = tn;
-  return 0;
+  StageLock lock;
+  ptts_tone *tn;
+  CHK(stage_new(e, batch, n_plans, width, width, lock, &tn));
+  stage_copy(*tn, tn->plans, plans.data(), n_plans);
+  stage_fill(*tn, tn->row_plan, batch, -1);
+  stage_zeros(*tn, tn->row_s, (size_t)batch * PTTS_TN_ROW_DOUBLES);
+  return stage_finish(tn, out, "tone_create");
 }
 
-extern "C" void ptts_tone_destroy(ptts_tone *tn) {
-  if (!tn) return;
-  hipSetDevice(tn->e->device);
-  hipDeviceSynchronize();
-  hipFree(tn->plans); hipFree(tn->row_plan); hipFree(tn->row_s);
-  delete tn;
-}
+extern "C" void ptts_tone_destroy(ptts_tone *tn) { stage_destroy(tn); }
 
 extern "C" int ptts_tone_set_row(ptts_tone *tn, int32_t row, int32_t plan_index, void *stream) {
-  if (!tn) return fail(-1, "tone_set_row: null toner");
-  if (row < 0 || row >= tn->B) return fail(-1, "tone_set_row: row out of range");
-  if (plan_index < -1 || plan_index >= tn->n_plans) return fail(-1, "tone_set_row: plan index out of range");
-  ENGINE_LOCK(tn->e);
-  HIPCHK(hipSetDevice(tn->e->device));
+  CHK(stage_row_ok(tn, "tone_set_row", "toner", row, "plan", plan_index, -1));
+  StageLock lock;
+  CHK(stage_enter(tn->e, lock));
   tone_set_row_kernel<<<1, 64, 0, S(tn->e, stream)>>>(tn->row_plan, tn->row_s, row, plan_index);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 extern "C" int ptts_tone_frame(ptts_tone *tn, const float *d_in, float *d_out, void *stream) {
-  if (!tn || !d_in || !d_out) return fail(-1, "tone_frame: null argument");
-  ENGINE_LOCK(tn->e);
-  HIPCHK(hipSetDevice(tn->e->device));
-  bind_engine(tn->e);
-  return tone_enqueue(S(tn->e, stream), tn, d_in, d_out);
+  return stage_frame(tn, d_in && d_out, "tone_frame", stream, [&](hipStream_t st) { return tone_enqueue(st, tn, d_in, d_out); });
 }

@@ -296,6 +296,13 @@ class _Stage:
         self.engine, self.batch = engine, batch
         self.handle = None
 
+    def _create(self, create, *args):
+        """`create(engine, *args, &handle)`; the stage then counts among the engine's states"""
+        h = C.c_void_p()
+        _lib.check(create(self.engine.handle, *args, C.byref(h)))
+        self.handle = h
+        self.engine._states.add(self)
+
     def _sp(self, stream):
         return self.engine._sp if stream is None else C.c_void_p(stream.cuda_stream)
 
@@ -368,11 +375,8 @@ class Stretcher(_Stage):
         n = len(self.plans)
         ints = (C.c_int32 * (5 * n))(*[v for p in self.plans for v in p.ints()])
         windows = np.concatenate([p.window.reshape(-1) for p in self.plans]).astype(np.float32)
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_stretcher_create(engine.handle, batch, ints, n,
-                                                    windows.ctypes.data_as(C.POINTER(C.c_float)), windows.size, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_stretcher_create, batch, ints, n, windows.ctypes.data_as(C.POINTER(C.c_float)),
+                     windows.size)
 
     def n_out(self, plan_index: int) -> int:
         """output samples per frame on `plans[plan_index]`"""
@@ -420,12 +424,8 @@ class Pitcher(_Stage):
         ints = (C.c_int32 * (8 * n))(*[v for p in self.plans for v in p.ints()])
         windows = np.concatenate([p.sp.window.reshape(-1) for p in self.plans]).astype(np.float32)
         tables = np.concatenate([p.table.reshape(-1) for p in self.plans]).astype(np.float32)
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_pitcher_create(engine.handle, batch, ints, n,
-                                                  windows.ctypes.data_as(C.POINTER(C.c_float)), windows.size,
-                                                  tables.ctypes.data_as(C.POINTER(C.c_float)), tables.size, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_pitcher_create, batch, ints, n, windows.ctypes.data_as(C.POINTER(C.c_float)),
+                     windows.size, tables.ctypes.data_as(C.POINTER(C.c_float)), tables.size)
 
     def _row_args(self, row):
         return (self.row_plan[row],)
@@ -468,10 +468,7 @@ class Leveler(_Stage):
         self.rows = [(-1, None, None)] * batch  # host mirror: (plan index, gain_db, peak_dbfs) of each row
         n = len(self.plans)
         ints = (C.c_int32 * (4 * n))(*[v for p in self.plans for v in p.ints()])
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_leveler_create(engine.handle, batch, ints, n, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_leveler_create, batch, ints, n)
 
     def _row_args(self, row):
         return self.rows[row]
@@ -520,11 +517,8 @@ class Normalizer(_Stage):
         n = len(self.plans)
         ints = (C.c_int32 * (2 * n))(*[v for p in self.plans for v in p.ints()])
         doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_loudnorm_create(engine.handle, batch, ints, n,
-                                                   doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_loudnorm_create, batch, ints, n, doubles.ctypes.data_as(C.POINTER(C.c_double)),
+                     doubles.size)
 
     def _row_args(self, row):
         return self.rows[row]
@@ -575,10 +569,7 @@ class Encoder(_Stage):
         self.width = self.in_max = self._in_width = int(width)
         self.pitch = self._out_width = encoding.pitch(self.width)  # in bytes: what a packer behind it reads
         self.rows = [(self.width, encoding.DEFAULT)] * batch  # host mirror: (n, encoding) of each row
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_encoder_create(engine.handle, batch, self.width, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_encoder_create, batch, self.width)
 
     def _row_args(self, row):
         return self.rows[row]
@@ -627,10 +618,7 @@ class Packer(_Stage):
         self.in_pitch = self._in_width = encoding.pitch(self.width)
         self.pitch = self._out_width = flac.pitch(self.width)
         self.rows = [(self.width, encoding.DEFAULT, None, 0, 0, None)] * batch  # host mirror: what set_row took
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_flac_create(engine.handle, batch, self.width, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_flac_create, batch, self.width)
 
     def _row_args(self, row):
         return self.rows[row]
@@ -675,7 +663,46 @@ class Packer(_Stage):
         self._frame(self.engine.lib.ptts_flac_frame, x, out, stream)
 
 
-class Toner(_Stage):
+class _FilterStage(_Stage):
+    """What the toner and the compressor share: float32 lines of one width in and out on the device, plans of
+    `_plan_ints` ints and some doubles each, and rows that start on bypass.  A subclass names its `_create_fn`, `_set_row_fn`
+    and `_frame_fn` of the C ABI."""
+
+    _i16, _check_written = False, _Stage._check_in
+    _plan_ints = _create_fn = _set_row_fn = _frame_fn = None
+
+    def __init__(self, engine: "Engine", batch: int, plans, width: int | None = None):
+        super().__init__(engine, batch)
+        self.plans = list(plans)
+        self.width = max(p.n for p in self.plans) if width is None else int(width)
+        self.in_max = self.out_max = self._in_width = self._out_width = self.width
+        self.row_plan = [-1] * batch  # host mirror of the rows' plan indices
+        n = len(self.plans)
+        ints = (C.c_int32 * (self._plan_ints * n))(*[v for p in self.plans for v in p.ints()])
+        doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
+        self._create(getattr(engine.lib, self._create_fn), batch, self.width, ints, n,
+                     doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size)
+
+    def _row_args(self, row):
+        return (self.row_plan[row],)
+
+    def set_row(self, row: int, plan_index: int | None = None, stream: torch.cuda.Stream | None = None):
+        """a new sequence joins `row` on `plans[plan_index]` with a zero state; None or -1: the row bypasses the stage.
+        Stream-ordered"""
+        idx = -1 if plan_index is None else int(plan_index)
+        if not -1 <= idx < len(self.plans):
+            raise ValueError(f"{self._name} plan index {plan_index!r} out of range")
+        _lib.check(getattr(self.engine.lib, self._set_row_fn)(self.handle, int(row), idx, self._sp(stream)))
+        self.row_plan[row] = idx
+
+    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
+        """x f32[B, width] -> out f32[B, width], both on the device and distinct"""
+        self._check_in(x)
+        self._check_in(out)
+        self._frame(getattr(self.engine.lib, self._frame_fn), x, out, stream)
+
+
+class Toner(_FilterStage):
     """Tones of `batch` sequences (include/ptts.h: ptts_tone; contract, grammar and plan rule: `tone.py`).  `plans` is a list
     of `tone.TonePlan`; a row is dealt a plan by its index (`set_row`; None: bypass) and starts on bypass.  `frame(x, out)`
     turns one frame x[b, :n(plan of b)] into out[b, :n(plan of b)] through the plan's cascade of biquad sections, with no
@@ -684,44 +711,11 @@ class Toner(_Stage):
     the last one."""
 
     _name, _field, _destroy, _attach = "toner", "tone", "ptts_tone_destroy", "ptts_mimi_set_tone"
-    _i16, _check_written = False, _Stage._check_in
+    _plan_ints, _create_fn, _set_row_fn, _frame_fn = 3, "ptts_tone_create", "ptts_tone_set_row", "ptts_tone_frame"
     _route_args = staticmethod(lambda r: (r.tone_plan,))
 
-    def __init__(self, engine: "Engine", batch: int, plans, width: int | None = None):
-        super().__init__(engine, batch)
-        self.plans = list(plans)
-        self.width = max(p.n for p in self.plans) if width is None else int(width)
-        self.in_max = self.out_max = self._in_width = self._out_width = self.width
-        self.row_plan = [-1] * batch  # host mirror of the rows' plan indices
-        n = len(self.plans)
-        ints = (C.c_int32 * (3 * n))(*[v for p in self.plans for v in p.ints()])
-        doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_tone_create(engine.handle, batch, self.width, ints, n,
-                                               doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
 
-    def _row_args(self, row):
-        return (self.row_plan[row],)
-
-    def set_row(self, row: int, plan_index: int | None = None, stream: torch.cuda.Stream | None = None):
-        """a new sequence joins `row` on `plans[plan_index]` with a zero state; None or -1: the row bypasses the stage.
-        Stream-ordered"""
-        idx = -1 if plan_index is None else int(plan_index)
-        if not -1 <= idx < len(self.plans):
-            raise ValueError(f"toner plan index {plan_index!r} out of range")
-        _lib.check(self.engine.lib.ptts_tone_set_row(self.handle, int(row), idx, self._sp(stream)))
-        self.row_plan[row] = idx
-
-    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
-        """x f32[B, width] -> out f32[B, width], both on the device and distinct"""
-        self._check_in(x)
-        self._check_in(out)
-        self._frame(self.engine.lib.ptts_tone_frame, x, out, stream)
-
-
-class Dynamics(_Stage):
+class Dynamics(_FilterStage):
     """Dynamics of `batch` sequences (include/ptts.h: ptts_dynamics; contract, grammar and plan rule: `dynamics.py`).
     `plans` is a list of `dynamics.DynPlan`; a row is dealt a plan by its index (`set_row`; None: bypass) and starts on
     bypass.  `frame(x, out)` turns one frame x[b, :n(plan of b)] into out[b, :n(plan of b)] through the plan's compressor,
@@ -730,41 +724,8 @@ class Dynamics(_Stage):
     stage is never the last one."""
 
     _name, _field, _destroy, _attach = "compressor", "dynamics", "ptts_dynamics_destroy", "ptts_mimi_set_dynamics"
-    _i16, _check_written = False, _Stage._check_in
+    _plan_ints, _create_fn, _set_row_fn, _frame_fn = 2, "ptts_dynamics_create", "ptts_dynamics_set_row", "ptts_dynamics_frame"
     _route_args = staticmethod(lambda r: (r.dyn_plan,))
-
-    def __init__(self, engine: "Engine", batch: int, plans, width: int | None = None):
-        super().__init__(engine, batch)
-        self.plans = list(plans)
-        self.width = max(p.n for p in self.plans) if width is None else int(width)
-        self.in_max = self.out_max = self._in_width = self._out_width = self.width
-        self.row_plan = [-1] * batch  # host mirror of the rows' plan indices
-        n = len(self.plans)
-        ints = (C.c_int32 * (2 * n))(*[v for p in self.plans for v in p.ints()])
-        doubles = np.ascontiguousarray(np.concatenate([p.doubles() for p in self.plans]), dtype=np.float64)
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_dynamics_create(engine.handle, batch, self.width, ints, n,
-                                                   doubles.ctypes.data_as(C.POINTER(C.c_double)), doubles.size, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
-
-    def _row_args(self, row):
-        return (self.row_plan[row],)
-
-    def set_row(self, row: int, plan_index: int | None = None, stream: torch.cuda.Stream | None = None):
-        """a new sequence joins `row` on `plans[plan_index]` with a zero state; None or -1: the row bypasses the stage.
-        Stream-ordered"""
-        idx = -1 if plan_index is None else int(plan_index)
-        if not -1 <= idx < len(self.plans):
-            raise ValueError(f"compressor plan index {plan_index!r} out of range")
-        _lib.check(self.engine.lib.ptts_dynamics_set_row(self.handle, int(row), idx, self._sp(stream)))
-        self.row_plan[row] = idx
-
-    def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
-        """x f32[B, width] -> out f32[B, width], both on the device and distinct"""
-        self._check_in(x)
-        self._check_in(out)
-        self._frame(self.engine.lib.ptts_dynamics_frame, x, out, stream)
 
 
 class Resampler(_Stage):
@@ -789,11 +750,8 @@ class Resampler(_Stage):
         n = len(self.plans)
         ints = [(C.c_int32 * n)(*[getattr(p, k) for p in self.plans]) for k in ("up", "down", "taps")]
         tables = np.concatenate([p.table.reshape(-1) for p in self.plans]).astype(np.float32)
-        h = C.c_void_p()
-        _lib.check(engine.lib.ptts_resampler_create(engine.handle, batch, *ints, n,
-                                                    tables.ctypes.data_as(C.POINTER(C.c_float)), tables.size, C.byref(h)))
-        self.handle = h
-        engine._states.add(self)
+        self._create(engine.lib.ptts_resampler_create, batch, *ints, n, tables.ctypes.data_as(C.POINTER(C.c_float)),
+                     tables.size)
 
     def index_of(self, rate) -> int:
         """the rate's index (None: 0, the native rate); ValueError for a rate that is not configured"""

@@ -4,7 +4,8 @@
 //
 // The file: int32 count, then per plan int32 rate, int32 n and PTTS_DY_PLAN_DOUBLES doubles (T k W M aA aR, the powers of aA,
 // the powers of aR).  Every plan runs FRAMES frames of a deterministic signal the way the kernel walks them: the curve, then
-// for p and for s chunk, scan over two buffers, re-run, carried state.  The signal is noise-like, gated between two levels,
+// for p and for s chunk, scan over two buffers, re-run, carried state (scan_walk.h over DyPeak and DySmooth, the
+// kernel's two recurrences in the shared scheme's terms).  The signal is noise-like, gated between two levels,
 // with digital silence over frames 3 to 6 and one full-scale sample, so that the detector rises, decays and rings out on the
 // floor.  Every chunked s (float64, in dB) is compared with the serial one; the program prints the largest |chunked -
 // serial|, "e_db", and fails above 1e-9 dB: that is 1.2e-10 of the gain, three orders below the 6e-8 of the rounding to fp32.
@@ -14,6 +15,7 @@
 #include <cstring>
 
 #include "ptts_dyn.h"
+#include "scan_walk.h"
 
 #define CHECK(c, ...) do { if (!(c)) { std::printf(__VA_ARGS__); std::printf("\n"); return 1; } } while (0)
 
@@ -25,40 +27,6 @@ static float signal(long long i, int n) {
   if (i == 8LL * n + n / 2) return -1.0f;
   const float level = (i / 97) % 2 ? 0.004f : 1.0f;
   return level * (0.15f * (float)std::sin(0.05 * (double)i) + 0.1f * (float)((i * 7919) % 13 - 6) / 6.0f);
-}
-
-// one recurrence over the frame by the kernel's scheme; v: c in, the recurrence's values out.  peak: the p form, else the s form
-static int scan(bool peak, int n, const DyPlan &P, double *v, double *E, double *a_all, double *carry) {
-  const int chunk = P.chunk, nT = P.threads, steps = dy_steps(nT);
-  const double a1 = peak ? P.aR : P.aA;
-  const double *pw = peak ? P.pwR : P.pwA;
-  for (int t = 0; t < nT; ++t) {
-    double a = t == 0 ? *carry : 0.0;
-    const int i0 = dy_begin(t, chunk), i1 = dy_end(t, chunk, n);
-    CHECK(i0 >= 0 && i0 < i1 && i1 <= n && i1 - i0 <= PTTS_DY_MAX_CHUNK, "thread %d: [%d, %d)", t, i0, i1);
-    for (int i = i0; i < i1; ++i) a = peak ? dy_peak(v[i], a1, a) : dy_smooth(v[i], a1, a);
-    a_all[t] = E[t] = a;
-  }
-  int cur = 0;
-  for (int j = 0; j < steps; ++j) {  // a step reads one half of E and writes the other
-    const int off = 1 << j;
-    const double *src = E + (size_t)cur * nT;
-    double *dst = E + (size_t)(cur ^ 1) * nT;
-    for (int t = 0; t < nT; ++t) {
-      if (t >= off) a_all[t] = peak ? dy_peak(a_all[t], pw[j], src[t - off]) : a_all[t] + pw[j] * src[t - off];
-      dst[t] = a_all[t];
-    }
-    cur ^= 1;
-  }
-  const double *Ef = E + (size_t)cur * nT;
-  const double first = *carry;
-  for (int t = 0; t < nT; ++t) {
-    double a = t > 0 ? Ef[t - 1] : first;
-    const int i0 = dy_begin(t, chunk), i1 = dy_end(t, chunk, n);
-    for (int i = i0; i < i1; ++i) v[i] = a = peak ? dy_peak(v[i], a1, a) : dy_smooth(v[i], a1, a);
-    if (t == nT - 1) *carry = a;
-  }
-  return 0;
 }
 
 static int run_plan(int rate, int n, const double *d, double *e_db) {
@@ -74,7 +42,7 @@ static int run_plan(int rate, int n, const double *d, double *e_db) {
   CHECK((nT - 1) * chunk < n && n <= nT * chunk, "chunks do not cover the frame");
   CHECK(steps >= 0 && steps <= PTTS_DY_SCAN && (1 << steps) >= nT && (steps == 0 || (1 << (steps - 1)) < nT), "steps %d", steps);
   float *x = new float[n];
-  double *v = new double[n], *E = new double[2 * nT], *a_all = new double[nT];
+  double *v = new double[n];
   double carry[2] = {0.0, 0.0}, serial[2] = {0.0, 0.0}, worst = 0.0;
   for (int f = 0; f < FRAMES; ++f) {
     for (int i = 0; i < n; ++i) {
@@ -82,7 +50,10 @@ static int run_plan(int rate, int n, const double *d, double *e_db) {
       v[i] = dy_curve(dy_level((double)x[i]), P.T, P.k, P.W);
       CHECK(v[i] >= 0.0 && v[i] <= 180.0, "rate %d n %d frame %d sample %d: reduction %g", rate, n, f, i, v[i]);
     }
-    if (scan(true, n, P, v, E, a_all, carry) || scan(false, n, P, v, E, a_all, carry + 1)) return 1;
+    const auto keep = [&](int i, double a) { v[i] = a; };  // p in place of c, then s in place of p
+    int bad = scan_walk<PTTS_DY_MAX_CHUNK>(DyPeak{P.aR, P.pwR}, n, chunk, nT, carry, v, keep);
+    if (bad < 0) bad = scan_walk<PTTS_DY_MAX_CHUNK>(DySmooth{P.aA, P.pwA}, n, chunk, nT, carry + 1, v, keep);
+    CHECK(bad < 0, "thread %d: [%d, %d)", bad, dy_begin(bad, chunk), dy_end(bad, chunk, n));
     for (int i = 0; i < n; ++i) {
       const float y = dy_step(P, serial, x[i]);
       CHECK(std::isfinite(v[i]) && v[i] >= 0.0 && std::isfinite(y), "rate %d n %d frame %d sample %d is not finite", rate, n, f, i);
@@ -94,7 +65,7 @@ static int run_plan(int rate, int n, const double *d, double *e_db) {
   }
   CHECK(worst <= 1e-9, "rate %d n %d: chunked leaves serial by %.3g dB", rate, n, worst);
   *e_db = std::fmax(*e_db, worst);
-  delete[] x; delete[] v; delete[] E; delete[] a_all;
+  delete[] x; delete[] v;
   return 0;
 }
 

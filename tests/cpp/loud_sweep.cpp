@@ -4,7 +4,8 @@
 //
 // The file: int32 count, then per plan int32 rate, int32 n and PTTS_LD_PLAN_DOUBLES doubles (coefficients, matrix powers).
 // Every plan runs frames of a deterministic signal until the pre-roll and three further sub-blocks have passed, the way the
-// kernel walks them: chunk, scan, energy, segment sums, completions, output from the ring, ring update.  Every chunked sample
+// kernel walks them: chunk, scan, energy (scan_walk.h over the pieces the kernel runs), segment sums, completions, output
+// from the ring, ring update.  Every chunked sample
 // is compared with the serial one (1e-10 of 1 + |w|), and every sub-block's energy with the serial one's, 1e-9 relative: the
 // second check is the one that sees the silence.  Every scan level multiplies a state by a power whose product cancels by
 // about its span in samples (up to 4096), so a frame leaves some 1e-12 in a state and the frames of the silence add up; 1e-9
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "ptts_loud.h"
+#include "scan_walk.h"
 
 #define CHECK(c, ...) do { if (!(c)) { std::printf(__VA_ARGS__); std::printf("\n"); return 1; } } while (0)
 
@@ -33,10 +35,12 @@ static int run_plan(int rate, int n, const double *dbl, long long *frames_out) {
   CHECK(chunk >= 1 && chunk <= PTTS_LD_MAX_CHUNK && nT >= 1 && nT <= PTTS_LD_THREADS, "chunk %d threads %d", chunk, nT);
   CHECK((nT - 1) * chunk < n && n <= nT * chunk, "chunks do not cover the frame");
   CHECK(D >= 1 && D <= PTTS_LD_MAX_D, "delay %d", D);
-  const double *coef = dbl;
-  const double *pw = dbl + PTTS_LD_COEFS;
+  CHECK(scan_steps(nT) <= PTTS_LD_SCAN, "scan steps %d", scan_steps(nT));
+  LdWeighting kw;
+  for (int q = 0; q < PTTS_LD_COEFS; ++q) kw.c[q] = dbl[q];
+  kw.pw = dbl + PTTS_LD_COEFS;
   float *x = new float[n], *y = new float[n], *ring = new float[D];
-  double *hist = new double[PTTS_LD_HIST], *E = new double[4 * nT], *Eold = new double[4 * nT], *P = new double[2 * nT];
+  double *hist = new double[PTTS_LD_HIST], *P = new double[2 * nT], *xd = new double[n];
   std::memset(ring, 0, sizeof(float) * D);
   double s_carry[4] = {0, 0, 0, 0}, s_serial[4] = {0, 0, 0, 0}, part = 0.0;
   int pos = 0, cnt = 0, head = 0;
@@ -49,29 +53,16 @@ static int run_plan(int rate, int n, const double *dbl, long long *frames_out) {
     for (int i = 0; i < n; ++i) { x[i] = signal(start + i, S); all_x.push_back(x[i]); }
     const int done = ld_done(pos, n, S);
     CHECK(done >= 0 && done <= PTTS_LD_MAX_DONE, "done %d", done);
-    // chunk
-    for (int t = 0; t < nT; ++t) {
-      double s[4] = {0, 0, 0, 0};
-      if (t == 0) std::memcpy(s, s_carry, sizeof(s));
-      const int i0 = ld_begin(t, chunk), i1 = ld_end(t, chunk, n);
-      CHECK(i0 >= 0 && i0 < i1 && i1 <= n && i1 - i0 <= PTTS_LD_MAX_CHUNK, "thread %d: [%d, %d)", t, i0, i1);
-      for (int i = i0; i < i1; ++i) ld_step(coef, s, (double)x[i]);
-      std::memcpy(E + 4 * t, s, sizeof(s));
-    }
-    // scan
-    for (int k = 0; (1 << k) < nT; ++k) {
-      CHECK(k < PTTS_LD_SCAN, "scan step %d", k);
-      std::memcpy(Eold, E, sizeof(double) * 4 * nT);
-      for (int t = 1 << k; t < nT; ++t) ld_mat_acc(pw + 32 * k, Eold + 4 * (t - (1 << k)), E + 4 * t);
-    }
+    // chunk, scan, re-run: w in place of x
+    for (int i = 0; i < n; ++i) xd[i] = (double)x[i];
+    const int bad = scan_walk<PTTS_LD_MAX_CHUNK>(kw, n, chunk, nT, s_carry, xd, [&](int i, double w) { xd[i] = w; });
+    CHECK(bad < 0, "thread %d: [%d, %d)", bad, ld_begin(bad, chunk), ld_end(bad, chunk, n));
     // energy, against the serial recurrence
     for (int t = 0; t < nT; ++t) {
-      double s[4];
-      std::memcpy(s, t == 0 ? s_carry : E + 4 * (t - 1), sizeof(s));
       const int i0 = ld_begin(t, chunk), i1 = ld_end(t, chunk, n), seg0 = ld_seg(pos, i0, S);
       double pa = 0.0, pb = 0.0;
       for (int i = i0; i < i1; ++i) {
-        const double w = ld_step(coef, s, (double)x[i]), ws = ld_step(coef, s_serial, (double)x[i]);
+        const double w = xd[i], ws = ld_step(kw.c, s_serial, (double)x[i]);
         CHECK(std::fabs(w - ws) <= 1e-10 * (1.0 + std::fabs(ws)), "rate %d n %d sample %lld: chunked %.17g serial %.17g", rate, n,
               start + i, w, ws);
         const int sg = ld_seg(pos, i, S);
@@ -83,7 +74,6 @@ static int run_plan(int rate, int n, const double *dbl, long long *frames_out) {
         zc[blk] += w * w; zs[blk] += ws * ws;
       }
       P[2 * t] = pa; P[2 * t + 1] = pb;
-      if (t == nT - 1) std::memcpy(s_carry, s, sizeof(s));
     }
     double segsum[PTTS_LD_SEGS];
     for (int g = 0; g <= done; ++g) {
@@ -152,7 +142,7 @@ static int run_plan(int rate, int n, const double *dbl, long long *frames_out) {
     CHECK(std::fabs(zc[b] - zs[b]) <= 1e-9 * zs[b], "rate %d n %d sub-block %zu: energy chunked %.17g serial %.17g", rate, n, b,
           zc[b], zs[b]);
   CHECK(zs.size() > 3 && zs[2] > 0.0 && zs[2] < 1e-12 * zs[0], "the silence did not ring out: %g of %g", zs[2], zs[0]);
-  delete[] x; delete[] y; delete[] ring; delete[] hist; delete[] E; delete[] Eold; delete[] P;
+  delete[] x; delete[] y; delete[] ring; delete[] hist; delete[] P; delete[] xd;
   *frames_out += frames;
   return 0;
 }

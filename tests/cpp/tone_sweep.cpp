@@ -4,7 +4,7 @@
 //
 // The file: int32 count, then per plan int32 rate, int32 n, int32 K and PTTS_TN_PLAN_DOUBLES doubles (coefficients, matrix
 // powers).  Every plan runs FRAMES frames of a deterministic signal the way the kernel walks them, section by section: chunk,
-// scan over two buffers, re-run, carried state.  The signal is noise-like at 0.25 with digital silence over frames 3 to 6, so
+// scan over two buffers, re-run, carried state (scan_walk.h over the pieces the kernel runs).  The signal is noise-like at 0.25 with digital silence over frames 3 to 6, so
 // that the sections ring out and the scan's powers must carry a decaying state as the serial recurrence does.  Every chunked
 // output sample (float64, before the rounding to fp32) is compared with the serial one; the program prints the largest
 // |chunked - serial| / (running peak of |serial|), "e64", and fails where it exceeds 2^-25 = 3e-8: rounding to fp32 moves a
@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "ptts_tone.h"
+#include "scan_walk.h"
 
 #define CHECK(c, ...) do { if (!(c)) { std::printf(__VA_ARGS__); std::printf("\n"); return 1; } } while (0)
 
@@ -38,7 +39,6 @@ static int run_plan(int rate, int n, int K, const double *dbl, double *e64) {
   const double *coef = dbl;
   const double *pw = dbl + PTTS_TN_MAX_SECTIONS * PTTS_TN_COEFS;
   double *xc = new double[n], *xs = new double[n];                 // the frame through the sections: chunked, serial
-  double *E = new double[2 * 2 * nT], *s_all = new double[2 * nT];  // E[buf][t][2]; the threads' running states
   double *carry = new double[2 * K], *serial = new double[2 * K];
   std::memset(carry, 0, sizeof(double) * 2 * K);
   std::memset(serial, 0, sizeof(double) * 2 * K);
@@ -47,36 +47,12 @@ static int run_plan(int rate, int n, int K, const double *dbl, double *e64) {
     for (int i = 0; i < n; ++i) xc[i] = xs[i] = (double)signal((long long)f * n + i, n);
     for (int k = 0; k < K; ++k) {
       const double *c = coef + PTTS_TN_COEFS * k;
-      // chunk
-      for (int t = 0; t < nT; ++t) {
-        double s[2] = {0.0, 0.0};
-        if (t == 0) { s[0] = carry[2 * k]; s[1] = carry[2 * k + 1]; }
-        const int i0 = tn_begin(t, chunk), i1 = tn_end(t, chunk, n);
-        CHECK(i0 >= 0 && i0 < i1 && i1 <= n && i1 - i0 <= PTTS_TN_MAX_CHUNK, "thread %d: [%d, %d)", t, i0, i1);
-        for (int i = i0; i < i1; ++i) tn_step(c, s, xc[i]);
-        s_all[2 * t] = E[2 * t] = s[0]; s_all[2 * t + 1] = E[2 * t + 1] = s[1];
-      }
-      // scan: a step reads one half of E and writes the other
-      int cur = 0;
-      for (int j = 0; j < steps; ++j) {
-        const int off = 1 << j;
-        const double *src = E + (size_t)cur * 2 * nT;
-        double *dst = E + (size_t)(cur ^ 1) * 2 * nT;
-        for (int t = 0; t < nT; ++t) {
-          if (t >= off) tn_mat_acc(pw + ((size_t)k * PTTS_TN_SCAN + j) * 4, src + 2 * (t - off), s_all + 2 * t);
-          dst[2 * t] = s_all[2 * t]; dst[2 * t + 1] = s_all[2 * t + 1];
-        }
-        cur ^= 1;
-      }
-      // re-run, and the serial recurrence beside it
-      const double *Ef = E + (size_t)cur * 2 * nT;
-      for (int t = 0; t < nT; ++t) {
-        double s[2] = {carry[2 * k], carry[2 * k + 1]};
-        if (t > 0) { s[0] = Ef[2 * (t - 1)]; s[1] = Ef[2 * (t - 1) + 1]; }
-        const int i0 = tn_begin(t, chunk), i1 = tn_end(t, chunk, n);
-        for (int i = i0; i < i1; ++i) xc[i] = tn_step(c, s, xc[i]);
-        if (t == nT - 1) { carry[2 * k] = s[0]; carry[2 * k + 1] = s[1]; }
-      }
+      TnSection sec;
+      for (int q = 0; q < PTTS_TN_COEFS; ++q) sec.c[q] = c[q];
+      sec.pw = pw + (size_t)k * PTTS_TN_SCAN * 4;
+      const int bad = scan_walk<PTTS_TN_MAX_CHUNK>(sec, n, chunk, nT, carry + 2 * k, xc, [&](int i, double y) { xc[i] = y; });
+      CHECK(bad < 0, "thread %d: [%d, %d)", bad, tn_begin(bad, chunk), tn_end(bad, chunk, n));
+      // the serial recurrence beside it
       for (int i = 0; i < n; ++i) xs[i] = tn_step(c, serial + 2 * k, xs[i]);
     }
     for (int i = 0; i < n; ++i) {
@@ -89,7 +65,7 @@ static int run_plan(int rate, int n, int K, const double *dbl, double *e64) {
   }
   CHECK(worst <= 1.0 / 33554432.0, "rate %d n %d K %d: chunked leaves serial by %.3g of the running peak", rate, n, K, worst);
   *e64 = std::fmax(*e64, worst);
-  delete[] xc; delete[] xs; delete[] E; delete[] s_all; delete[] carry; delete[] serial;
+  delete[] xc; delete[] xs; delete[] carry; delete[] serial;
   return 0;
 }
 
