@@ -372,6 +372,20 @@ void ptts_leveler_destroy(ptts_leveler *lv);
 int ptts_leveler_set_row(ptts_leveler *lv, int32_t row, int32_t plan_index, float gain, float ceiling, void *stream);
 /* from now on (stream-ordered) the row's incoming frames count as zeros (on != 0), until set_row or on == 0 */
 int ptts_leveler_set_row_drain(ptts_leveler *lv, int32_t row, int32_t on, void *stream);
+/* True-peak mode (pocket_tts_amd/level.py, "True-peak mode").  taps63 is float[3][21], phases 1, 2, 3 of the 4x interpolator
+ * h_p[j] (level.TP_TAPS).  A row in this mode limits on P[i] = max(|u[i - 10]|, |v_1[i]|, |v_2[i]|, |v_3[i]|), v_p[i] =
+ * sum over j < 21 of h_p[j] u[i - j], in place of |u[i]|: r[i] = P[i] > C ? C / P[i] : 1, m, d, e, g as above and y[i] =
+ * g[i] u[i - 10 - LA]; the output lags by LA + 10 samples, and the row keeps a meter M = max(M, |y[i - 10]|, |w_p[i]|), w_p
+ * the same FIR over y.  enable allocates the mode's carries and meters, once per leveler and before its first frame or
+ * graph capture: from then on level_frame launches the kernel that knows the mode, in which a row that does not use it
+ * computes bit for bit what it computed before.  -1 for a null argument, a second call or a tap outside [-4, 4]. */
+int ptts_leveler_enable_true_peak(ptts_leveler *lv, const float *taps63);
+/* ptts_leveler_set_row for a row in true-peak mode, its meter at 0 (ptts_leveler_set_row puts a row in sample-peak mode).
+ * -1 additionally for a leveler without the mode, for plan_index -1 and for a plan with LA + 10 > n. */
+int ptts_leveler_set_row_tp(ptts_leveler *lv, int32_t row, int32_t plan_index, float gain, float ceiling, void *stream);
+/* the row's meter after everything enqueued on `stream` so far, into *host_out; waits for the stream, so not inside a
+ * capture.  0.0 for a row that is not in the mode.  -1 for a row out of range, a null argument, a leveler without the mode. */
+int ptts_leveler_row_true_peak(ptts_leveler *lv, int32_t row, float *host_out, void *stream);
 /* One frame, one launch: d_in f32[B, width] (DEVICE memory) -> out [B, width], f32 or (is_i16) int16 converted as
  * ptts_mimi_set_pcm_i16 converts, device or pinned host; then the rows' states advance. */
 int ptts_level_frame(ptts_leveler *lv, const float *d_in, void *out, int32_t is_i16, void *stream);

@@ -141,6 +141,9 @@ PROTOTYPES = {
     "ptts_leveler_destroy": (None, [_P]),
     "ptts_leveler_set_row": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
     "ptts_leveler_set_row_drain": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ptts_leveler_enable_true_peak": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ptts_leveler_set_row_tp": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
+    "ptts_leveler_row_true_peak": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), _P]),
     "ptts_level_frame": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ptts_mimi_set_leveler": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "ptts_loudnorm_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_int64,

@@ -114,6 +114,9 @@ class Request:
         self.encoding = encoding        # encoding of the chunks (None: the batcher's one sample format)
         self.compression = compression  # "flac": each chunk is one whole FLAC frame as a uint8 tensor (`flac.py`)
         self.blocks = 0                 # FLAC frames delivered so far: the number of the next one
+        # a request with `peak_dbtp`: the largest reading of its rows' true-peak meters over the text chunks that have
+        # finished, linear (`level.true_peak` of what they delivered); None for a request without the mode
+        self.true_peak: float | None = None
         self._q: queue.Queue = queue.Queue()
         self.frames = 0
         self.error: Exception | None = None
@@ -136,6 +139,13 @@ class Request:
             item = torch.frombuffer(bytearray(renumber(item.numpy().tobytes(), self.blocks)), dtype=torch.uint8)
             self.blocks += 1
         self._q.put(item)
+
+    @property
+    def true_peak_dbtp(self) -> float | None:
+        """`true_peak` in dBTP (-inf for digital silence); None for a request without `peak_dbtp`"""
+        if self.true_peak is None:
+            return None
+        return 20.0 * math.log10(self.true_peak) if self.true_peak > 0 else -math.inf
 
     def cancel(self):
         """Ends the request: callable from any thread, takes effect at the scheduler's next iteration.  Its chunks leave
@@ -204,7 +214,7 @@ class ContinuousBatcher:
         and the upper bound of a request's own value.  1: the chunks of a request run one after the other, as before.
 
         The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`,
-        `tones`, `compressions`, `dynamics`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
+        `tones`, `compressions`, `dynamics`, `true_peak`; as keywords, or as one `spec`) let each request choose its way through the output chain with the fields of
         `ChainTable.route` (`submit`).  `encodings` needs `pcm_format` left at its default (ValueError).  Without any of them
         every request gets the codec's samples in `pcm_format`, with the same graphs and buffers as before.
 
@@ -311,8 +321,9 @@ class ContinuousBatcher:
         `TTSModel.generate_audio(..., seed=)`; None draws from the batch state's own stream.
 
         `**request`: the request's way through the output chain, the fields of `ChainTable.route` (`sample_rate`, `speed`,
-        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`, `compression`, `dynamics`), checked against the batcher's table:
-        ValueError for what it refuses, TypeError for another name.  A request whose row lags (a speed, a pitch, a loudness
+        `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`, `encoding`, `tone`, `compression`, `dynamics`, `peak_dbtp`), checked against the batcher's table:
+        ValueError for what it refuses, TypeError for another name.  A request with `peak_dbtp` (the ceiling as a true peak)
+        has its row's meter read at the end of each text chunk: `Request.true_peak` / `true_peak_dbtp`.  A request whose row lags (a speed, a pitch, a loudness
         target, a tone, a compressor setting or a gain) needs frames_after_eos >= 1."""
         return self.submit_script([(model_state, text)], frames_after_eos, max_tokens, temperature=temperature,
                                   noise_clamp=noise_clamp, eos_threshold=eos_threshold, lsd_decode_steps=lsd_decode_steps,
@@ -590,6 +601,7 @@ class ContinuousBatcher:
             self._deliver(b, job, pcm[b])
             if frame >= self.a_release[b]:
                 self.a_release[b] = -1
+                self._read_meter(int(b), job)
                 self.slot[b] = None
                 self._finish(job)
         for b in np.nonzero(rows)[0]:
@@ -619,8 +631,18 @@ class ContinuousBatcher:
                 if drain > 1:
                     self.a_release[b] = frame + drain - 1
                     continue
+            self._read_meter(int(b), job)
             self.slot[b] = None
             self._finish(job)
+
+    def _read_meter(self, b, job):
+        """a text chunk in true-peak mode leaves slot `b`: its row's meter into the request's `true_peak`.  The frame that
+        flushed its tail is done, and the frames queued behind it are zeros to a draining row, which move no meter; the
+        read is ordered on the codec stream before the `set_row` of the slot's next job, and waits for that stream"""
+        if job.route.true_peak:
+            m = self.lv.row_true_peak(b, self.pipe.s2)
+            if m is not None:
+                job.req.true_peak = m if job.req.true_peak is None else max(job.req.true_peak, m)
 
     def _deliver(self, b, job, line):
         """routes the part of a frame of slot `b` that belongs to its job (`Route.take`): to the request's queue, or

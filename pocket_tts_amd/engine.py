@@ -455,39 +455,76 @@ class Leveler(_Stage):
     list of `level.LevelPlan`; a row is dealt a plan by its index together with its gain and ceiling in dB (`set_row`;
     `gain_db` None: bypass) and starts on bypass.  `frame(x, out)` turns one frame x[b, :n(plan of b)] into
     out[b, :n(plan of b)], LA samples late; `set_row_drain` makes a row's incoming frames count as zeros, which flushes its
-    tail.  A bypass row's whole line is copied."""
+    tail.  A bypass row's whole line is copied.  With `true_peak` the leveler has the true-peak mode of `level.py`: a row
+    dealt `true_peak=True` limits the 4x-oversampled peak, `LA + 10` samples late, and keeps a meter (`row_true_peak`); every
+    other row computes what it computes on a leveler without the mode, bit for bit."""
 
     _name, _field, _destroy, _attach = "leveler", "level", "ptts_leveler_destroy", "ptts_mimi_set_leveler"
     _drain, _drain_name = "ptts_leveler_set_row_drain", "level"
-    _route_args = staticmethod(lambda r: r.level or (None, None, None))
+    _route_args = staticmethod(lambda r: (*(r.level or (None, None, None)), r.true_peak))
 
-    def __init__(self, engine: "Engine", batch: int, plans):
+    def __init__(self, engine: "Engine", batch: int, plans, true_peak: bool = False):
         super().__init__(engine, batch)
         self.plans = list(plans)
         self.width = self._in_width = self._out_width = max(p.n for p in self.plans)
-        self.rows = [(-1, None, None)] * batch  # host mirror: (plan index, gain_db, peak_dbfs) of each row
+        self.rows = [(-1, None, None)] * batch  # host mirror: (plan index, gain_db, ceiling in dB) of each row
+        self.row_mode = [False] * batch         # and whether that ceiling is a true peak
+        self.true_peak = bool(true_peak)
         n = len(self.plans)
         ints = (C.c_int32 * (4 * n))(*[v for p in self.plans for v in p.ints()])
         self._create(engine.lib.ptts_leveler_create, batch, ints, n)
+        if self.true_peak:
+            from . import level
+
+            taps = np.ascontiguousarray(level.TP_TAPS, np.float32)
+            _lib.check(engine.lib.ptts_leveler_enable_true_peak(self.handle, taps.ctypes.data_as(C.POINTER(C.c_float))))
 
     def _row_args(self, row):
-        return self.rows[row]
+        return (*self.rows[row], self.row_mode[row])
 
-    def set_row(self, row: int, plan_index: int | None = None, gain_db=None, peak_dbfs=None,
+    def set_row(self, row: int, plan_index: int | None = None, gain_db=None, peak_dbfs=None, true_peak: bool = False,
                 stream: torch.cuda.Stream | None = None):
         """a new sequence joins `row` on `plans[plan_index]` at `gain_db` under `peak_dbfs` (default -1) with a zero state,
-        not draining; `gain_db` None: the row bypasses the stage.  Stream-ordered"""
+        not draining; `gain_db` None: the row bypasses the stage.  `true_peak`: the ceiling is a true peak (dBTP), the row
+        runs in true-peak mode with its meter at 0; ValueError on a leveler without the mode, on bypass and for a plan
+        with LA + 10 > n.  Stream-ordered"""
         from . import level
 
         g, c = level.check(gain_db, peak_dbfs)
         if g is None:
+            if true_peak:
+                raise ValueError("a true-peak ceiling is only meaningful together with gain_db")
             idx, G, Cc = -1, 1.0, 1.0
         else:
             idx, G, Cc = int(plan_index), float(level.linear(g)), float(level.linear(c))
             if not 0 <= idx < len(self.plans):
                 raise ValueError(f"leveler plan index {plan_index!r} out of range")
-        _lib.check(self.engine.lib.ptts_leveler_set_row(self.handle, int(row), idx, G, Cc, self._sp(stream)))
-        self.rows[row] = (idx, g, c)
+        if true_peak:
+            if not self.true_peak:
+                raise ValueError("this leveler has no true-peak mode (build it with true_peak=True)")
+            p = self.plans[idx]
+            level.plan(p.rate, p.n, True)  # the rule LA + 10 <= n, in its own words
+            fn = self.engine.lib.ptts_leveler_set_row_tp
+        else:
+            fn = self.engine.lib.ptts_leveler_set_row
+        _lib.check(fn(self.handle, int(row), idx, G, Cc, self._sp(stream)))
+        self.rows[row], self.row_mode[row] = (idx, g, c), bool(true_peak)
+
+    def row_true_peak(self, row: int, stream: torch.cuda.Stream | None = None):
+        """the meter of `row` after every frame enqueued so far (on `stream`, or on the engine's stream): the largest
+        magnitude of the 4x-oversampled output since `set_row`, linear, what `level.true_peak` reads on the samples the row
+        wrote.  None for a row that is not in true-peak mode.  Waits for the stream"""
+        if not self.true_peak:
+            raise ValueError("this leveler has no true-peak mode (build it with true_peak=True)")
+        if not 0 <= int(row) < self.batch:
+            raise ValueError(f"leveler row {row!r} out of range")
+        if not self.row_mode[row]:
+            return None
+        v = C.c_float()
+        if stream is None:
+            self.engine._pre()
+        _lib.check(self.engine.lib.ptts_leveler_row_true_peak(self.handle, int(row), C.byref(v), self._sp(stream)))
+        return float(v.value)
 
     def frame(self, x: torch.Tensor, out: torch.Tensor, stream: torch.cuda.Stream | None = None):
         """x f32[B, width] on the device -> out (float32 or int16 [B, width], device or pinned host)"""
@@ -1026,8 +1063,8 @@ class Engine:
     def new_pitcher(self, batch: int, plans) -> Pitcher:
         return Pitcher(self, batch, plans)
 
-    def new_leveler(self, batch: int, plans) -> Leveler:
-        return Leveler(self, batch, plans)
+    def new_leveler(self, batch: int, plans, true_peak: bool = False) -> Leveler:
+        return Leveler(self, batch, plans, true_peak)
 
     def new_normalizer(self, batch: int, plans) -> Normalizer:
         return Normalizer(self, batch, plans)
@@ -1417,7 +1454,7 @@ class StepPipeline:
       of a forked graph do not run concurrently).
 
     The options of `output_chain.ChainSpec` (`sample_rates`, `speeds`, `level`, `pitches`, `loudness`, `encodings`, `tones`,
-    `compressions`, `dynamics`; as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
+    `compressions`, `dynamics`, `true_peak`; as keywords, or as one `spec`) configure the output chain behind the codec (`output_chain.py` gives its order; not in
     "fork" mode): the codec graphs end with its stages' launches.  `chain` holds the plan table (`chain.table`) and the
     stage objects, also here as `rs`, `ts`, `ps`, `tn`, `dy`, `ln`, `lv` and `en`.  `pcm[p]` are then DEVICE tensors and the
     samples reach the host through `out[p]`, the chain's pinned ring, int16 with `pcm_i16`, else float32:

@@ -20,6 +20,8 @@ BS.1770 normaliser on the GPU, loudness.py; `generate --loudness-lufs -16 [--pea
 header, and with `--tones telephone,warm,"hp:120;peak:3000:4"` a per-request `tone` (a parametric equaliser on the GPU,
 tone.py; `generate --tone telephone` is the same for one text), and with `--dynamics speech,"threshold=-24;ratio=4"` a
 per-request `dynamics` (a speech compressor on the GPU, dynamics.py; `generate --dynamics speech`), and with
+`--true-peak` a per-request `peak_dbtp` in place of `peak_dbfs` (the ceiling as a BS.1770-4 true peak: a 4x oversampled
+limiter and meter on the GPU, level.py; `generate --loudness-lufs -16 --peak-dbtp -1` logs the measured true peak), and with
 `--parallel-chunks W` up to W sentences of a request at a time as rows of the batch, delivered in text order (batching.py;
 `generate --parallel-chunks W` is the same for one text).  `export-voice` encodes an audio prompt (first 30 s)
 into a voice-state file that `generate --voice` and the server's voices directory accept.
@@ -41,7 +43,7 @@ DEFAULT_TEXT = ("Hello world. I am Kyutai's Pocket TTS. I'm fast enough to run o
 # the flags behind each request field of `ChainTable.for_request`, as `generate` names them when a rule refuses one
 FLAGS = dict(sample_rate="--sample-rate", speed="--speed", pitch="--pitch / --pitch-semitones", tone="--tone",
              loudness_lufs="--loudness-lufs / --peak-dbfs", gain_db="--gain-db / --peak-dbfs", encoding="--encoding",
-             compression="--compression", dynamics="--dynamics")
+             compression="--compression", dynamics="--dynamics", peak_dbtp="--peak-dbtp")
 
 _STREAM_FRAMES = 1_000_000_000  # streaming: the length is not known up front, the header announces this many samples
 
@@ -282,6 +284,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--peak-dbfs", type=float, default=None,
                    help="Ceiling of the peak limiter in dBFS, in [-20, 0] (default -1); only together with --gain-db, "
                         "--loudness-lufs, --tone or --dynamics")
+    g.add_argument("--peak-dbtp", type=float, default=None,
+                   help="Ceiling of the limiter as a true peak in dBTP (ITU-R BS.1770-4: the peak of the 4x oversampled "
+                        "waveform), in [-20, 0], e.g. -1; in place of --peak-dbfs, which it excludes.  The measured true peak "
+                        "is logged when done")
     g.add_argument("--dynamics", default=None, metavar="SETTING",
                    help="Dynamics: a compressor preset (speech, gentle, broadcast, telephone) or key=value pairs joined by ';' "
                         "with the keys threshold, ratio, knee, attack, release, makeup, e.g. \"threshold=-24;ratio=4\": "
@@ -345,6 +351,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--level", action="store_true",
                    help="Requests may set their output level with the form fields gain_db and peak_dbfs (gain plus a peak "
                         "limiter on the GPU)")
+    s.add_argument("--true-peak", action="store_true",
+                   help="Requests may state their ceiling as a true peak with the form field peak_dbtp in place of peak_dbfs "
+                        "(a 4x oversampled limiter and meter on the GPU; brings the limiter with it, like --level)")
     s.add_argument("--noise-clamp", type=float, default=None, help="Default noise clamp of a request")
     s.add_argument("--eos-threshold", type=float, default=-4.0, help="Default EOS threshold of a request")
     s.add_argument("--slots", type=int, default=64, help="Utterances decoded together")
@@ -436,7 +445,8 @@ def cli_app(argv=None) -> int:
             pitch, cents = nearest(args.pitch_semitones, *ChainTable.line_of(native, fs, args.sample_rate, args.speed)[2])
             logger.info("--pitch-semitones %g: pitch %s, %+.1f cents from the request", args.pitch_semitones, pitch, cents)
         _, request = ChainTable.for_request(native, fs, args.sample_rate, args.speed, args.gain_db, args.peak_dbfs, pitch,
-                                            args.loudness_lufs, args.encoding, args.tone, args.compression, args.dynamics)
+                                            args.loudness_lufs, args.encoding, args.tone, args.compression, args.dynamics,
+                                            args.peak_dbtp)
     except ValueError as e:  # a `RequestError` names its field; the others are those of the two pitch flags above
         logger.error("%s: %s", FLAGS[getattr(e, "field", "pitch")], e)
         return 1
@@ -455,6 +465,11 @@ def cli_app(argv=None) -> int:
         write_wav_stream(args.output_path, chunks, rate, args.encoding)
     if args.output_path != "-":
         logger.info("Results written in %s", args.output_path)
+    if args.peak_dbtp is not None and model.last_true_peak is not None:
+        from .level import dbtp
+
+        # what `level.true_peak` reads on the samples before their encoding: the device meter's maximum over the sentences
+        logger.info("true peak %.2f dBTP", dbtp(model.last_true_peak))
     return 0
 
 

@@ -76,7 +76,8 @@ class Route:
     the encoder, and `bytes_per_sample`: what a sample of it takes in the encoder's ring (None likewise: the ring's dtype
     says); `tone_plan`: its plan index in the toner (None: bypass, or no toner), `toned`: it has one;
     `compression`: None or "flac", the row's lines leave the packer as FLAC frames; `dyn_plan`: its plan index in the
-    compressor (None: bypass, or no compressor), `dynamic`: it has one."""
+    compressor (None: bypass, or no compressor), `dynamic`: it has one; `true_peak`: the ceiling in `level` is a true peak
+    (dBTP), the leveler runs the row in true-peak mode, whose 10 samples of detector delay `preroll` includes."""
 
     rate_index: int
     rate: int
@@ -97,6 +98,7 @@ class Route:
     compression: str | None = None
     dyn_plan: int | None = None
     dynamic: bool = False
+    true_peak: bool = False
 
     def take(self, pos: int, frames: int | None):
         """(lo, hi): the part of the row's line that belongs to its job, which has produced `pos` samples so far (lines are
@@ -125,9 +127,9 @@ def _ask(field: str, rule, *args):
 
 @dataclass(frozen=True)
 class ChainSpec:
-    """What a pipeline's output chain is built with: the nine options that `StepPipeline`, `ContinuousBatcher` and
-    `server.create_app` take as keywords, one per stage but the leveler's, which four bring.  The default of each is "that
-    stage does not exist": with all nine nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
+    """What a pipeline's output chain is built with: the ten options that `StepPipeline`, `ContinuousBatcher` and
+    `server.create_app` take as keywords, one per stage but the leveler's, which five bring.  The default of each is "that
+    stage does not exist": with all ten nothing changes, same buffers, same graph nodes.  Lists are kept as tuples, so a
     spec is hashable.
 
     `sample_rates`: the output rates a row may choose besides the native one, each a rate `resample.plan` admits, e.g. [8000,
@@ -149,6 +151,9 @@ class ChainSpec:
     the encoder, which it brings with it, and writes ring lines with a length prefix.
     `dynamics`: the compressor settings a row may choose, presets or key=value lists of `dynamics.py`, e.g. ["speech",
     "threshold=-24;ratio=4"]; the speech compressor, which brings the leveler with it as its peak limiter.
+    `true_peak`: True lets a row state its ceiling as a true peak, `peak_dbtp` (`level.py`, "True-peak mode"); it brings the
+    leveler with it, like `level`, with the mode's carries and meters.  Rows that do not use it compute what they compute
+    without the option, bit for bit.
 
     What the rules refuse raises their ValueError when the table is built (`table`), before anything is allocated."""
 
@@ -161,9 +166,10 @@ class ChainSpec:
     tones: tuple | None = None
     compressions: tuple | None = None
     dynamics: tuple | None = None
+    true_peak: bool = False
 
-    TAGS = dict(sample_rates="rate", speeds="speed", level="level", pitches="pitch", loudness="loud", encodings="enc",
-                tones="tone", dynamics="dyn", compressions="comp")  # what `tags` calls each option
+    TAGS = dict(sample_rates="rate", speeds="speed", level="level", true_peak="tp", pitches="pitch", loudness="loud",
+                encodings="enc", tones="tone", dynamics="dyn", compressions="comp")  # what `tags` calls each option
 
     def __post_init__(self):
         for name in ("sample_rates", "speeds", "pitches", "encodings", "tones", "compressions", "dynamics"):
@@ -173,7 +179,7 @@ class ChainSpec:
 
     @classmethod
     def of(cls, spec=None, **chain):
-        """`spec`, or the spec of the nine options given as keywords; TypeError for another keyword, or for both"""
+        """`spec`, or the spec of the ten options given as keywords; TypeError for another keyword, or for both"""
         if spec is None:
             return cls(**chain)
         if chain:
@@ -205,8 +211,8 @@ class ChainTable:
     None where the rate refuses a tone) and `tones`, the configured list in canonical form, with `loudness` the normaliser's
     `loud_plans` / `loud_index[(rate, n)]` (`loudness.table`), with `dynamics` the compressor's `dyn_plans` /
     `dyn_index[(rate, n)][setting index]` (`dynamics.table` over the same lines) and `dynamics`, the configured list in
-    canonical form, and with `level`, `loudness`, `tones` or `dynamics` the leveler's
-    `level_plans` / `level_index[(rate, n)]` (`level.table`).  With `encodings` the chain ends with the encoder and
+    canonical form, and with `level`, `loudness`, `tones`, `dynamics` or `true_peak` the leveler's
+    `level_plans` / `level_index[(rate, n)]` (`level.table`); `true_peak` says whether it has the true-peak mode.  With `encodings` the chain ends with the encoder and
     `encodings` is the configured list, `pcm_s16le` first; a list makes the table non-empty even when the encoder is the only
     stage.  With `compressions` it ends with the packer behind the encoder (which the option brings: `encodings` is then at
     least ["pcm_s16le"]) and `compressions` is the configured list.  `width` is the widest line that leaves the last stage
@@ -214,7 +220,9 @@ class ChainTable:
     device tables, so the order is part of the contract."""
 
     def __init__(self, native_rate: int, frame_samples: int, sample_rates=None, speeds=None, level: bool = False,
-                 pitches=None, loudness: bool = False, encodings=None, tones=None, compressions=None, dynamics=None):
+                 pitches=None, loudness: bool = False, encodings=None, tones=None, compressions=None, dynamics=None,
+                 true_peak: bool = False):
+        self.true_peak = bool(true_peak)
         self.native_rate, self.frame_samples = int(native_rate), int(frame_samples)
         self.has_rates = sample_rates is not None
         self.sample_rates = list(sample_rates) if self.has_rates else None
@@ -244,7 +252,7 @@ class ChainTable:
         self.loud_plans = self.loud_index = None
         if loudness:
             self.loud_plans, self.loud_index = loud_rule.table(lines)
-        if level or loudness or self.tones is not None or self.dynamics is not None:
+        if level or loudness or self.tones is not None or self.dynamics is not None or self.true_peak:
             self.level_plans, self.level_index = level_rule.table(lines)
         self.compressions = None if compressions is None else flac_rule.normalise_compressions(compressions)
         if self.compressions is not None:
@@ -278,8 +286,8 @@ class ChainTable:
         return [s for j, s in enumerate(self.dynamics) if self.dyn_index[(rate, n)][j] is not None]
 
     def route(self, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None, pitch=None, loudness_lufs=None,
-              encoding=None, tone=None, compression=None, dynamics=None) -> Route:
-        """The `Route` of a request.  Its ten fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
+              encoding=None, tone=None, compression=None, dynamics=None, peak_dbtp=None) -> Route:
+        """The `Route` of a request.  Its eleven fields, which `ContinuousBatcher.submit`, `TTSModel.generate_audio` and
         `generate_audio_stream` take as keywords and hand on as they came; None is always "as without the stage":
 
         `sample_rate`: the rate of the request's audio, the native one (None) or one of the configured; a frame then yields
@@ -303,6 +311,9 @@ class ChainTable:
         `gain_db` (in [-40, 24]) and `peak_dbfs` (in [-20, 0], default -1, only together with a gain, a target, a tone or a compressor
         setting):
         the samples are amplified and peak-limited to 10^(peak_dbfs / 20).  0 is not None: it limits at the ceiling.
+        `peak_dbtp` (same range, same default, accepted wherever `peak_dbfs` is and excluding it): the ceiling as a true
+        peak, the peak of the reconstructed waveform as a BS.1770-4 meter reads it by 4x oversampling; the limiter then
+        runs in true-peak mode, 10 samples later still, on a line with LA + 10 <= n.
         `encoding`: "pcm_s16le" (None on a table with the encoder), "pcm_f32le", "mulaw" or "alaw", among the configured:
         the chunks are int16, float32 or uint8 (ITU-T G.711) tensors, one element per sample.
         `compression`: "flac" where configured, only with `encoding` None or "pcm_s16le" and on a line `flac.plan` admits:
@@ -372,6 +383,8 @@ class ChainTable:
             raise ValueError(f"dynamics {dynamics!r}: this batcher has no dynamics stage (build it with dynamics for "
                              "per-request dynamics)")
         lvl = loud = None
+        if peak_dbtp is not None and not self.true_peak:
+            raise ValueError("peak_dbtp: this batcher has no true-peak mode (build it with true_peak=True)")
         if self.loud_plans is not None:
             target = loud_rule.check_with(loudness_lufs, gain_db)
             if target is not None:
@@ -381,10 +394,10 @@ class ChainTable:
         elif loudness_lufs is not None:
             raise ValueError("loudness_lufs: this batcher has no loudness stage (build it with loudness=True)")
         if self.level_plans is not None:
-            g_db, p_db = level_rule.check(gain_db, peak_dbfs)
+            g_db, p_db = level_rule.check(gain_db, peak_dbfs, peak_dbtp)
             if g_db is not None:
                 lvl = (self.level_index[(rate, n_out)], g_db, p_db)
-                preroll += self.level_plans[lvl[0]].LA
+                preroll += level_rule.plan(rate, n_out, peak_dbtp is not None).preroll  # LA, and 10 more in true-peak mode
         elif gain_db is not None or peak_dbfs is not None:
             raise ValueError("gain_db / peak_dbfs: this batcher has no level stage (build it with level=True)")
         bps = None
@@ -403,7 +416,7 @@ class ChainTable:
         return Route(r, rate, plan, stretched, lvl, n_out, preroll, -(-preroll // n_out),
                      "stretch" if stretched else "pitch" if pitched else "loud" if loud is not None
                      else "level" if lvl is not None else None, pplan, pitched, loud, encoding, bps, tplan, tplan is not None,
-                     compression, dplan, dplan is not None)
+                     compression, dplan, dplan is not None, lvl is not None and peak_dbtp is not None)
 
     @staticmethod
     def line_of(native_rate: int, frame_samples: int, sample_rate=None, speed=None):
@@ -424,12 +437,14 @@ class ChainTable:
 
     @staticmethod
     def for_request(native_rate: int, frame_samples: int, sample_rate=None, speed=None, gain_db=None, peak_dbfs=None,
-                    pitch=None, loudness_lufs=None, encoding=None, tone=None, compression=None, dynamics=None):
+                    pitch=None, loudness_lufs=None, encoding=None, tone=None, compression=None, dynamics=None,
+                    peak_dbtp=None):
         """One request that gets a chain of its own (the fields of `route`): (spec, request), the `ChainSpec` of exactly the
         stages it uses and the request in canonical form, the dict that `spec.table(native_rate, frame_samples).route`
         takes - the native rate, speed 1.0 and pitch 1.0 as None, speed and pitch as the floats of their fractions, the tone
         and the compressor setting as their canonical strings, `peak_dbfs` defaulted, and `gain_db` 0.0 behind a tone or a
-        compressor without a gain or a loudness target of its own.  One walk in chain order over the request's own line, stage by stage through the plan rules themselves,
+        compressor without a gain or a loudness target of its own; a ceiling given as `peak_dbtp` stays under that name (the
+        dict then has `peak_dbfs` None, and the spec `true_peak`).  One walk in chain order over the request's own line, stage by stage through the plan rules themselves,
         so a refusal is the rule's: a `RequestError` with its message, whose `field` names the request field at fault."""
         sample_rate, speed, line = ChainTable.line_of(native_rate, frame_samples, sample_rate, speed)
         if pitch is not None:
@@ -443,17 +458,22 @@ class ChainTable:
         if dynamics is not None:
             _ask("dynamics", dyn_rule.plan, *line, dynamics)
             _ask("dynamics", level_rule.plan, *line)
+        tp = peak_dbtp is not None
+        ceiling = "peak_dbtp" if tp else "loudness_lufs"  # the field a refusal of the ceiling names
         loudness_lufs = _ask("loudness_lufs", loud_rule.check_with, loudness_lufs, gain_db)
         if loudness_lufs is not None:  # the limiter behind the normaliser: no gain of its own, the request's ceiling
             _ask("loudness_lufs", loud_rule.plan, *line)
             _ask("loudness_lufs", level_rule.plan, *line)
-            peak_dbfs = _ask("loudness_lufs", level_rule.check, 0.0, peak_dbfs)[1]
+            peak = _ask(ceiling, level_rule.check, 0.0, peak_dbfs, peak_dbtp)[1]
         else:
             if (tone is not None or dynamics is not None) and gain_db is None:
                 gain_db = 0.0  # the limiter behind the tone or the compressor: no gain of its own, the request's ceiling
-            gain_db, peak_dbfs = _ask("gain_db", level_rule.check, gain_db, peak_dbfs)
+            gain_db, peak = _ask("gain_db" if tp is False else ceiling, level_rule.check, gain_db, peak_dbfs, peak_dbtp)
             if gain_db is not None:
                 _ask("gain_db", level_rule.plan, *line)
+        if tp:
+            _ask("peak_dbtp", level_rule.plan, *line, True)
+        peak_dbfs, peak_dbtp = (None, peak) if tp else (peak, None)
         if encoding is not None:
             _ask("encoding", encoding_rule.check, encoding)
         if compression is not None:
@@ -461,13 +481,15 @@ class ChainTable:
             _ask("compression", flac_rule.plan, *line, encoding)
         one = lambda v: None if v is None else (v,)  # noqa: E731
         spec = ChainSpec(one(sample_rate), one(speed), gain_db is not None, one(pitch), loudness_lufs is not None,
-                         None if encoding is None else encoding_rule.NAMES, one(tone), one(compression), one(dynamics))
+                         None if encoding is None else encoding_rule.NAMES, one(tone), one(compression), one(dynamics), tp)
         req = dict(sample_rate=sample_rate, speed=speed, gain_db=gain_db, peak_dbfs=peak_dbfs, pitch=pitch,
                    loudness_lufs=loudness_lufs, encoding=encoding, tone=tone)
         if compression is not None:  # only then: a request without it is the dict it always was
             req["compression"] = compression
         if dynamics is not None:  # likewise
             req["dynamics"] = dynamics
+        if tp:  # likewise
+            req["peak_dbtp"] = peak_dbtp
         return spec, req
 
 
@@ -495,7 +517,7 @@ class OutputChain:
         self.tn = Toner(engine, batch, table.tone_plans, table.width) if table.tone_plans is not None else None
         self.dy = Dynamics(engine, batch, table.dyn_plans, table.width) if table.dyn_plans is not None else None
         self.ln = Normalizer(engine, batch, table.loud_plans) if table.loud_plans is not None else None
-        self.lv = Leveler(engine, batch, table.level_plans) if table.level_plans is not None else None
+        self.lv = Leveler(engine, batch, table.level_plans, table.true_peak) if table.level_plans is not None else None
         self.en = Encoder(engine, batch, table.width) if table.encodings is not None else None
         self.pk = Packer(engine, batch, table.width) if table.compressions is not None else None
         self._stages = [s for s in (*self.per_kind(), self.pk) if s is not None]

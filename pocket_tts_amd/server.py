@@ -9,7 +9,9 @@ rates the server was started with that the plan rule of `stretch.py` admits at t
 of the frequency ratios the server was started with that the plan rule of `pitch.py` admits behind the request's rate and
 speed, a number or "P/Q", or 1), and on a
 server started with `level` the output level `gain_db` with its ceiling `peak_dbfs` (`level.py`), and on a server started
-with `loudness` the loudness target `loudness_lufs` (`loudness.py`; with `peak_dbfs` as its ceiling, without `gain_db`).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
+with `loudness` the loudness target `loudness_lufs` (`loudness.py`; with `peak_dbfs` as its ceiling, without `gain_db`).
+On a server started with `true_peak` the field `peak_dbtp` states that ceiling as a true peak in place of `peak_dbfs`
+(`level.py`, "True-peak mode"; both together, or the field on a server started without, get a 400).  The body is the WAV the `generate` command writes (`main.wav_stream_bytes`):
 the streaming header, the 16-bit frames as each is decoded, 200 ms of silence.  On a server started with `encodings` the
 field `encoding` chooses the sample encoding among them and `pcm_s16le` (`encoding.py`: ITU-T G.711 `mulaw` / `alaw`, or
 `pcm_f32le`), encoded on the GPU; header and silence follow it.  On a server started with `compressions` `container=flac`
@@ -63,7 +65,9 @@ it; empty: the text above)</p>
 <p>Sample rate <input name="sample_rate" size="6"> Hz (empty: the model's own rate)</p>
 <p>Speed <input name="speed" size="5"> (empty: 1.0)</p>
 <p>Pitch <input name="pitch" size="6"> as a frequency ratio, e.g. 17/16 or 0.8 (empty: 1)</p>
-<p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)</p>
+<p>Gain <input name="gain_db" size="5"> dB, peak <input name="peak_dbfs" size="5"> dBFS (empty: the model's own level)
+or true peak <input name="peak_dbtp" size="5"> dBTP in its place (BS.1770-4, 4x oversampled; as far as the server was started
+with true_peak)</p>
 <p>Loudness <input name="loudness_lufs" size="5"> LUFS, e.g. -16 or -23, instead of a gain (empty: the model's own level)</p>
 <p>Tone <input name="tone" size="20"> a preset or a band list such as hp:120;peak:3000:4, as far as the server was started
 with it (empty: none)</p>
@@ -312,6 +316,33 @@ def parse_ceiling(fields: dict):
         raise FormError(str(e)) from None
 
 
+def parse_true_peak(fields: dict, enabled: bool, settings: dict, table):
+    """the optional `peak_dbtp` field, the request's ceiling as a true peak, None where absent or empty.  `settings`: what the
+    request's other fields came to; `table`: the server's `ChainTable`.  FormError for the field on a server started without
+    true_peak, beside `peak_dbfs`, for a value `level.check` refuses, on a request without a gain, a loudness target, a tone
+    or a compressor setting (it has no limiter), and on a line the mode's rule refuses"""
+    from . import level
+
+    raw = (fields.get("peak_dbtp") or "").strip()
+    if not raw:
+        return None
+    if not enabled:
+        raise FormError("peak_dbtp is not available (this server was started without true_peak)")
+    try:
+        peak = float(raw)
+    except ValueError:
+        raise FormError(f"peak_dbtp must be a number, got {raw!r}") from None
+    limited = any(settings.get(k) is not None for k in ("gain_db", "loudness_lufs", "tone", "dynamics"))
+    try:
+        peak_dbfs = (fields.get("peak_dbfs") or "").strip() or None
+        peak = level.check(0.0 if limited else None, None if peak_dbfs is None else 0.0, peak)[1]
+        keys = ("sample_rate", "speed", "pitch", "tone", "dynamics", "loudness_lufs", "gain_db")
+        table.route(**{k: settings[k] for k in keys if k in settings}, peak_dbtp=peak)
+    except ValueError as e:
+        raise FormError(str(e)) from None
+    return peak
+
+
 def parse_level(fields: dict, enabled: bool):
     """the optional `gain_db` and `peak_dbfs` fields as (gain_db, peak_dbfs), each None where absent or empty; FormError for
     a value `level.check` refuses (its message names the rule) and for either field on a server started without level"""
@@ -463,7 +494,8 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
     spec = ChainSpec(**chain)
     # the one table every request is checked against: the rules of every stage on every line (ValueError at start-up)
     table = spec.table(model.sample_rate, getattr(getattr(model, "engine", None), "frame_samples", 1920))
-    sample_rates, level, loudness, encodings = spec.sample_rates, spec.level, spec.loudness, table.encodings
+    # true_peak brings the leveler as level does: such a server takes gain_db too
+    sample_rates, level, loudness, encodings = spec.sample_rates, spec.level or spec.true_peak, spec.loudness, table.encodings
     compressions = table.compressions
     speeds_of = None if spec.speeds is None else table.speeds_of()
 
@@ -596,6 +628,10 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
                 gain_db, peak_dbfs = parse_level(fields, level)
                 if gain_db is not None:
                     settings["gain_db"], settings["peak_dbfs"] = gain_db, peak_dbfs
+            peak_dbtp = parse_true_peak(fields, spec.true_peak, settings, table)
+            if peak_dbtp is not None:
+                settings.pop("peak_dbfs", None)
+                settings["peak_dbtp"] = peak_dbtp
             enc = parse_encoding(fields, encodings)
             if enc is not None and encodings is not None:
                 settings["encoding"] = enc
@@ -605,7 +641,7 @@ def create_app(model, *, slots: int, capacity: int, voices_dir=None, default_voi
                 settings["compression"] = container
                 # the rule's refusals (an encoding that is not pcm_s16le, a line FLAC does not admit), and the block size
                 route_fields = ("sample_rate", "speed", "pitch", "tone", "dynamics", "loudness_lufs", "gain_db", "peak_dbfs",
-                                "encoding", "compression")
+                                "peak_dbtp", "encoding", "compression")
                 try:
                     flac_n = table.route(**{k: settings[k] for k in route_fields if k in settings}).n_out
                 except ValueError as e:

@@ -214,8 +214,10 @@ class TTSModel:
 
         `**request` (not in the reference): the request's way through the output chain on the GPU, the fields of
         `output_chain.ChainTable.route` (`sample_rate`, `speed`, `gain_db`, `peak_dbfs`, `pitch`, `loudness_lufs`,
-        `encoding`, `tone`, `compression`, `dynamics`), each checked by its rule on the request's own line (`ChainTable.for_request`):
-        ValueError with the rule's message, TypeError for another name.  The chunks then hold what a frame yields at the end
+        `encoding`, `tone`, `compression`, `dynamics`, `peak_dbtp`), each checked by its rule on the request's own line (`ChainTable.for_request`):
+        ValueError with the rule's message, TypeError for another name.  With `peak_dbtp`, the ceiling as a true peak, the
+        model's `last_true_peak` is afterwards what the leveler's meter read over the text chunks, linear (`level.true_peak`
+        of the samples yielded; `level.dbtp` makes dBTP of it); None after a call without it.  The chunks then hold what a frame yields at the end
         of the chain, as fp32, or typed as the `encoding`; with `compression="flac"` each chunk is one whole FLAC frame as a
         uint8 tensor, numbered on across the text chunks (`flac.py`; `main.flac_stream_bytes` makes a file of them).  None of
         them: the codec's own samples, as before.
@@ -231,6 +233,7 @@ class TTSModel:
 
         # the native rate, speed 1.0 and no gain become None: the call of before.  ValueError names the rule
         spec, request = ChainTable.for_request(int(self.config.mimi.sample_rate), self.engine.frame_samples, **request)
+        self.last_true_peak = None
         if frames_after_eos is None:
             frames_after_eos = self.model_recommended_frames_after_eos
         chunks = split_into_best_sentences(self.tokenizer.encode, self.tokenizer.sp, text_to_generate, max_tokens,
@@ -482,6 +485,7 @@ class TTSModel:
                     raise RuntimeError("the batcher went idle before the request had finished")
             if req.error is not None:
                 raise req.error
+            self.last_true_peak = req.true_peak
         finally:
             if not done:  # the consumer has stopped early, or an error: the request's rows leave their slots
                 req.cancel()
@@ -722,6 +726,9 @@ class TTSModel:
                 total += chunk.shape[0]
                 if chunk.shape[0]:
                     yield chunk
+            if route.true_peak:  # the chunk's last frame has been read: the row's meter holds all of it
+                m = pipe.chain.lv.row_true_peak(0, pipe.s2)
+                self.last_true_peak = m if self.last_true_peak is None else max(self.last_true_peak, m)
             if not copy_state:
                 # the reference mutates the caller's state in place (tts_model.py:637-638)
                 pipe.sync()
