@@ -643,6 +643,28 @@ int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
  * Returns rows*cols or <0. */
 int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi, const char *name, float *d_out,
                         int64_t capacity, int32_t *rows, int32_t *cols, void *stream);
+/* Test hook: the intermediates of the voice-prompt encoder.  A ptts_encode_voice that runs with the engine option
+ * "debug_taps" set keeps them in the engine until the next ptts_encode_voice or ptts_destroy (without the option it
+ * allocates, copies and launches nothing for them, and this function returns -1).  Same conversion and return value as
+ * ptts_debug_read.  With R = the padded sample count (a multiple of the frame size), r = 4, 5, 6 the strides of rounds
+ * i = 1, 2, 3 and dim = n_filters * 2^(i-1), each name holds what the NEXT kernel reads:
+ *   "audio"       [R, 16]            column 0 = the samples, zero from n_samples on; columns 1..15 zero
+ *   "conv0_raw"   [R, n_filters]     k7 conv, RAW (the first block's skip input)
+ *   "conv0"       [R, n_filters]     the same, ELU'd
+ *   "rb<i>"       [rows, dim / compress]  the block's hidden activation: k3 conv of the ELU'd input, ELU'd
+ *   "se<i>"       [rows, dim]        the block's output raw skip + 1x1 conv, ELU'd (nothing reads the raw sum)
+ *   "down<i>_raw" [rows / r, 2 dim]  the strided conv, RAW (the next block's skip input)
+ *   "down<i>"     [rows / r, 2 dim]  the same, ELU'd
+ *   "final"       [R / 120, m_dim]   the k3 conv, raw: the transformer's input (a copy; the transformer works in place)
+ *   "tr_qkv"      [R / 120, 3 m_dim] the LAST layer's queries and keys after RoPE and its values, [q | k | v] per position,
+ *                                    read from the query blocks and the key / value cache the attention kernel reads
+ *   "tr_attn", "tr_resid", "tr_ff"   the LAST layer's attention output before out_proj, stream after attention (a copy)
+ *                                    and GELU(linear1)
+ *   "enc_tr"      [R / 120, m_dim]   the transformer's output
+ *   "latent"      [frames, ldim]     the replicate-padded downsample
+ *   "cond"        [frames, d_model]  the speaker projection */
+int64_t ptts_debug_read_encoder(ptts_engine *e, const char *name, float *d_out, int64_t capacity, int32_t *rows,
+                                int32_t *cols, void *stream);
 /* Test hook: ONE GEMM of the hot path's kernel family (gemm_kernel / gemm_lds_kernel), packed by the engine's own
  * packers and launched through the production dispatcher, on plain row-major device buffers:
  *   y[m][n] = epilogue( sum_tap sum_c pre(x[row(m, tap)][c]) * w[n][c][tap] ),  row(b * T + t, tap) = b * T * xstride + t * xstride + tap - halo

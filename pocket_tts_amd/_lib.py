@@ -197,6 +197,7 @@ PROTOTYPES = {
     "ptts_timer_stop_ms": (C.c_int, [_P, _P, C.POINTER(C.c_float)]),
     "ptts_debug_read": (C.c_int64, [_P, _P, C.c_int32, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), _P]),
+    "ptts_debug_read_encoder": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "ptts_debug_gemm": (C.c_int, [_P, C.POINTER(PttsGemmCase), _P]),
     "ptts_debug_attn": (C.c_int, [_P, C.POINTER(PttsAttnCase), _P]),
     "ptts_debug_codec_gemm": (C.c_int, [_P, C.POINTER(PttsCodecGemmCase), _P]),

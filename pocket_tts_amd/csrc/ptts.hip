@@ -284,6 +284,7 @@ struct TrCtx {
   int cascade = 0;                // decode steps: attn_cascade_kernel tile shape (10 R + PW) or 0
   const int *qlen = nullptr;      // ragged prefill: real rows of each sequence (GemmArgs::qlen, AttnArgs::qlen) or null
   const float *rope;  // [M][32][2]
+  float *tap_x = nullptr;  // test hook: receives a copy of the stream after attention (x), which x_out may overwrite
   double kv_keys;  // sum over sequences of the keys attended (profiling only)
   const char *tag;
 };
@@ -315,6 +316,7 @@ static void run_tr_layer(hipStream_t st, const TrLayer &T, const TrCtx &c) {
   a = mk_gemm(T.out, c.ao, DF, c.MT, c.M);
   a.epi = EPI_RES; a.R = c.x_in; a.RF = DF; a.Y = c.x; a.YF = DF; a.ls = T.ls1;
   launch_gemm(st, a, PRE_NONE);
+  if (c.tap_x) (void)hipMemcpyAsync(c.tap_x, c.x, (size_t)c.M * c.D * 4, hipMemcpyDeviceToDevice, st);
   SITE(s6.c_str());
   a = mk_gemm(T.ff1, c.x, DF, c.MT, c.M);
   a.epi = EPI_STORE; a.act = ACT_GELU; a.Y = c.ff; a.YF = c.FF / 16;
@@ -766,6 +768,7 @@ extern "C" void ptts_destroy(ptts_engine *e) {
   hipSetDevice(e->device);
   hipDeviceSynchronize();
   for (void *p : e->allocs) hipFree(p);
+  for (void *p : e->enc_keep) hipFree(p);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
   if (e->stream) hipStreamDestroy(e->stream);
@@ -2443,10 +2446,20 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
   if (!e->has_encoder) return fail(-3, "the checkpoint passed to ptts_create has no Mimi encoder tensors");
   if (n_samples < 1) return fail(-1, "empty audio");
   HIPCHK(hipSetDevice(e->device));
+  for (void *p : e->enc_keep) hipFree(p);  // the taps of the call before this one ("debug_taps")
+  e->enc_keep.clear();
+  e->enc_taps.clear();
   const ptts_config &c = e->cfg;
   hipStream_t st = S(e, stream);
   bind_engine(e);
   AllocScope alloc_scope(st);
+  // "debug_taps": every intermediate is named here and outlives the call (ptts_debug_read_encoder); without it this
+  // function allocates, copies and launches nothing more than it needs
+  const bool keep = e->opt_debug_taps != 0;
+  std::vector<ptts_engine::EncTap> taps;
+  auto tap = [&](const std::string &name, const float *p, long n_rows, int cols) {
+    if (keep) taps.push_back({name, p, (int)n_rows, cols});
+  };
   const int hop = c.ratios[0] * c.ratios[1] * c.ratios[2];
   const long fs = (long)hop * c.upsample_stride;  // 1920
   const long R0 = (n_samples + fs - 1) / fs * fs;  // pad_for_conv1d(x, frame_size, frame_size)
@@ -2459,6 +2472,7 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
   CHK(talloc(&cur_r, (size_t)R0 * nf));
   CHK(talloc(&cur_e, (size_t)R0 * nf));
   audio_to_fm_kernel<<<cdiv(R0 / 16 * 64, 256), 256, 0, st>>>(d_audio, x0, (int)n_samples, (int)R0);
+  tap("audio", x0, R0, 16);  // column 0: the samples, zero from n_samples on; columns 1..15 zero
   long rows = R0;
   auto conv = [&](const Lin &L, const float *X, int XF, long out_rows, int xstride, int halo, int mode) {
     GemmArgs a = mk_gemm(L, X, XF, (int)cdiv(out_rows, 16), (int)out_rows);
@@ -2470,6 +2484,8 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
   GemmArgs a = conv(e->enc_conv0, x0, 1, rows, 1, c.kernel_size - 1, 1);
   a.Y = cur_e; a.YF = nf / 16; a.act = ACT_ELU; a.Yraw = cur_r;
   launch_gemm(st, a, PRE_NONE);
+  tap("conv0_raw", cur_r, rows, nf);
+  tap("conv0", cur_e, rows, nf);
   int dim = nf;
   for (int i = 0; i < 3; ++i) {
     const int r = c.ratios[2 - i], hid = dim / c.compress;
@@ -2491,6 +2507,11 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
     a = conv(e->enc_down[i], se, dim / 16, nrows, r, r, 1);  // kernel 2r, stride r: left context r
     a.Y = ne; a.YF = 2 * dim / 16; a.act = ACT_ELU; a.Yraw = nr;
     launch_gemm(st, a, PRE_NONE);
+    const std::string n = std::to_string(i + 1);
+    tap("rb" + n, rb, rows, hid);
+    tap("se" + n, se, rows, dim);
+    tap("down" + n + "_raw", nr, nrows, 2 * dim);
+    tap("down" + n, ne, nrows, 2 * dim);
     cur_r = nr; cur_e = ne; rows = nrows; dim *= 2;
   }
   // final conv -> encoder-transformer input (rows = R0 / hop, a multiple of 16)
@@ -2502,6 +2523,13 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
   a = conv(e->enc_final, cur_e, dim / 16, M2, 1, c.last_kernel_size - 1, 1);
   a.Y = tx; a.YF = C / 16;
   launch_gemm(st, a, PRE_NONE);
+  float *tx_in = nullptr, *resid = nullptr;  // the transformer works in place: its input and the last layer's inner stream are copied
+  if (keep) {
+    CHK(talloc(&tx_in, (size_t)M2 * C));
+    CHK(talloc(&resid, (size_t)M2 * C));
+    HIPCHK(hipMemcpyAsync(tx_in, tx, (size_t)M2 * C * 4, hipMemcpyDeviceToDevice, st));
+    tap("final", tx_in, M2, C);
+  }
   // encoder transformer, whole sequence, RoPE offset 0, window = context (transformer.py:63-75)
   {
     const int H = c.m_heads, QB = MT2, cap = MT2 * 16;
@@ -2525,8 +2553,14 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
       t.Kc = kv; t.Vc = kv + (size_t)H * cap * 64; t.offset = off; t.rope = rope;
       t.kv_keys = (double)M2 * std::min(M2, c.m_context) / 16.0;
       t.tag = "enc";
+      t.tap_x = l == c.m_layers - 1 ? resid : nullptr;
       run_tr_layer(st, e->enc_tr[l], t);
     }
+    if (keep) taps.push_back({"tr_qkv", q, M2, 3 * C, kv, kv + (size_t)H * cap * 64, off, H, QB, cap});
+    tap("tr_attn", ao, M2, C);
+    tap("tr_resid", resid, M2, C);
+    tap("tr_ff", ff, M2, c.m_ff);
+    tap("enc_tr", tx, M2, C);
   }
   // ConvDownsample1d: kernel 2s, stride s, replicate padding, no bias (resample.py:7-29)
   float *lat, *cond;
@@ -2546,6 +2580,12 @@ extern "C" int ptts_encode_voice(ptts_engine *e, const float *d_audio, int64_t n
   if (d_cond_out) from_fm_kernel<<<cdiv((long)Tf * c.d_model / 4, 256), 256, 0, st>>>(cond, d_cond_out, Tf, c.d_model, c.d_model / 16, 0);
   LAUNCHCHK();
   HIPCHK(hipStreamSynchronize(st));
+  if (keep) {
+    tap("latent", lat, Tf, c.ldim);
+    tap("cond", cond, Tf, c.d_model);
+    e->enc_keep.swap(tmp);
+    e->enc_taps.swap(taps);
+  }
   for (void *p : tmp) hipFree(p);
   if (h_frames) *h_frames = Tf;
   return 0;

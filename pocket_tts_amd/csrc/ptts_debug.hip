@@ -698,3 +698,28 @@ extern "C" int ptts_debug_codec_gemm(ptts_engine *e, ptts_codec_gemm_case *c, vo
   if (!e || !c) return fail(-1, "debug_codec_gemm: null argument");
   return run_case(e, stream, [&](hipStream_t st, ptts_engine &scr) { return debug_codec_gemm(e, c, st, scr); });
 }
+
+// ------------------------------------------------------------------------------------------------
+// ptts_debug_read_encoder (test hook, include/ptts.h): the intermediates of the last ptts_encode_voice that ran with
+// "debug_taps".  FM buffers, but for "tr_qkv": the last layer's query blocks and key / value caches
+extern "C" int64_t ptts_debug_read_encoder(ptts_engine *e, const char *name, float *d_out, int64_t capacity, int32_t *rows,
+                                           int32_t *cols, void *stream) {
+  if (!e || !name || !d_out || !rows || !cols) return fail(-1, "debug_read_encoder: null argument");
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  if (e->enc_taps.empty())
+    return fail(-1, "debug_read_encoder: nothing kept; set the engine option \"debug_taps\" before ptts_encode_voice");
+  hipStream_t st = S(e, stream);
+  for (const ptts_engine::EncTap &t : e->enc_taps) {
+    if (t.name != name) continue;
+    const long n = (long)t.rows * t.cols;
+    if (n > capacity) return fail(-1, "debug_read_encoder: capacity too small");
+    if (t.H) dbg_from_qkv_kernel<<<cdiv(n, 256), 256, 0, st>>>(t.p, t.kc, t.vc, t.offset, d_out, t.rows, t.H, t.rows, t.QB, t.cap, 0);
+    else from_fm_kernel<<<cdiv(n / 4, 256), 256, 0, st>>>(t.p, d_out, t.rows, t.cols, t.cols / 16, 0);
+    LAUNCHCHK();
+    *rows = t.rows;
+    *cols = t.cols;
+    return n;
+  }
+  return fail(-1, std::string("debug_read_encoder: unknown buffer ") + name);
+}

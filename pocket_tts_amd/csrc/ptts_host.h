@@ -148,6 +148,19 @@ struct ptts_engine {
   bool has_encoder = false;
   Lin enc_conv0, enc_res_a[3], enc_res_b[3], enc_down[3], enc_final, enc_downsample, speaker_proj;
   std::vector<TrLayer> enc_tr;
+  // test hook (ptts_debug_read_encoder): with "debug_taps" the intermediates of the last ptts_encode_voice stay allocated
+  // (enc_keep) until the next call or ptts_destroy; each tap is an FM buffer of `rows` rows and `cols` (% 16 == 0) columns,
+  // or (H > 0) the query blocks p, the key / value caches kc / vc of `cap` slots and their offset word: [rows][q | k | v]
+  struct EncTap {
+    std::string name;
+    const float *p;
+    int rows, cols;
+    const float *kc = nullptr, *vc = nullptr;
+    const int *offset = nullptr;
+    int H = 0, QB = 0, cap = 0;
+  };
+  std::vector<EncTap> enc_taps;
+  std::vector<void *> enc_keep;
   float *zeros = nullptr;
   int64_t lm_bytes = 0, mimi_bytes = 0;
   Tuner *tuner = nullptr;

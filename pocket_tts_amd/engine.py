@@ -1229,6 +1229,17 @@ class Engine:
         self.sync()
         return buf[: r.value * c.value].view(r.value, c.value).clone()
 
+    def debug_read_encoder(self, name: str, capacity: int = 1 << 23) -> torch.Tensor:
+        """Test hook: intermediate `name` (include/ptts.h: ptts_debug_read_encoder) of the last `encode_voice` that ran with
+        the engine option `debug_taps` set, as f32[rows, cols] of at most `capacity` floats"""
+        r, c = C.c_int32(), C.c_int32()
+        buf = torch.empty((capacity,), dtype=torch.float32, device=self.device)
+        self._pre()
+        n = self.lib.ptts_debug_read_encoder(self.handle, name.encode(), _ptr(buf), capacity, C.byref(r), C.byref(c), self._sp)
+        _lib.check(int(n))
+        self.sync()
+        return buf[: r.value * c.value].view(r.value, c.value).clone()
+
     _GEMM_INTS = ("T", "xstride", "halo", "halo_mode", "wfmt", "pre", "epi", "act", "cfg", "krot", "lds_target")
     _GEMM_INS = ("x_prev", "bias", "ln_w", "ln_b", "prevec", "mod_shift", "mod_scale", "r", "g", "ls")
 

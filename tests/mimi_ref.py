@@ -235,7 +235,10 @@ def _rope(x, pos, max_period, dtype):
     """interleaved-pair rotary embedding of x [B, T, H, D] at the integer positions pos [B, T]; float32 angle"""
     D = x.shape[-1]
     ds = np.arange(D // 2, dtype=F32)
-    freqs = np.exp(ds * F32(-math.log(max_period) * 2 / D)).astype(F32)
+    # the correctly rounded float32 exp of the float32 argument.  numpy's own float32 exp is one ulp off in 13 of the 32
+    # entries at max_period 10000 (torch's in one, glibc's expf in none), which moves an angle by 4e-6 at position 271: more
+    # than a stage's E32 once it multiplies a query (tests/test_gpu_voice_matrix.py, stage Q)
+    freqs = np.exp((ds * F32(-math.log(max_period) * 2 / D)).astype(F64)).astype(F32)
     ang = (freqs[None, None, :] * pos.astype(F32)[:, :, None]).astype(F32).astype(dtype)  # the float32 product
     c, s = np.cos(ang)[:, :, None, :], np.sin(ang)[:, :, None, :]
     xr, xi = x[..., 0::2], x[..., 1::2]
