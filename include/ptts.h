@@ -523,6 +523,15 @@ int ptts_mimi_set_packer(ptts_mimi_state *s, ptts_flac *pk, void *d_in_bytes, vo
 /* d_latent f32[B, ldim] (normalised FlowLM output) -> d_pcm f32[B, frame_samples]; includes the
  * emb_std/emb_mean de-normalisation, the quantizer 1x1 conv and increment_steps(mimi, 16). */
 int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, void *stream);
+/* The same frame in its two parts, for callers that schedule them apart.  ptts_mimi_decode_tr: the de-normalisation, the
+ * quantizer conv, the upsample and the decoder transformer of ONE frame (d_latent_b NULL) or of a PAIR of consecutive
+ * frames (d_latent, then d_latent_b; fp32 codec only, -1 otherwise): a pair runs the transformer once on twice the rows.
+ * ptts_mimi_decode_seanet: SEANet, the PCM and the state's output stages of the oldest frame the transformer has handed
+ * over and SEANet has not decoded.  The hand-over holds a pair beside the frame before it: -1 when the transformer would
+ * run further ahead than that, or when SEANet has no frame to decode; nothing is enqueued then.  Parts and whole frames
+ * mix freely on one state; results are those of ptts_mimi_decode called once per frame. */
+int ptts_mimi_decode_tr(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, const float *d_latent_b, void *stream);
+int ptts_mimi_decode_seanet(ptts_engine *e, ptts_mimi_state *s, float *d_pcm, void *stream);
 
 /* ---- Voice-prompt encode path (one-off per voice): MimiModel.encode_to_latent + F.linear(speaker_proj_weight)
  *      (mimi.py:96-119, tts_model.py:379-388).  d_audio f32[n_samples] mono at the model rate; the signal is
@@ -538,6 +547,13 @@ int ptts_graph_capture_lm_step(ptts_engine *e, ptts_lm_state *s, const float *d_
                                uint8_t *d_is_eos, ptts_graph **out);
 int ptts_graph_capture_mimi(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm,
                             ptts_graph **out);
+/* The parts of the codec frame as graphs of their own (ptts_mimi_decode_tr / ptts_mimi_decode_seanet; the same refusals, at
+ * ptts_graph_launch): the transformer of one frame, of a frame pair, and SEANet of one frame with the output stages the
+ * state has when it is captured. */
+int ptts_graph_capture_mimi_tr(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, ptts_graph **out);
+int ptts_graph_capture_mimi_tr_pair(ptts_engine *e, ptts_mimi_state *s, const float *d_latent_a, const float *d_latent_b,
+                                    ptts_graph **out);
+int ptts_graph_capture_mimi_seanet(ptts_engine *e, ptts_mimi_state *s, float *d_pcm, ptts_graph **out);
 /* One graph with two parallel branches: the FlowLM step (as ptts_graph_capture_lm_step) and the Mimi decode of
  * the PREVIOUS frame (reads d_mimi_latent_in, which must differ from d_latent_out).  Replaying such graphs
  * back to back on one stream overlaps step t+1 with frame t without cross-stream events (the reference

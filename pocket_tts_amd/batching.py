@@ -257,7 +257,8 @@ class ContinuousBatcher:
             self.st.reserve_row_lsd(k)  # before the pipeline captures its graphs
         self.max_lsd = max_lsd_decode_steps
         self.pipe = StepPipeline(eng, self.st, self.ms, None, model.lsd_decode_steps, float(model.eos_threshold),
-                                 mode="events", pcm_i16=(pcm_format == "i16"), spec=spec)
+                                 mode="events", pcm_i16=(pcm_format == "i16"), spec=spec,
+                                 codec_pair=False)  # rows are reset between any two frames: single frames
         self.chain = self.pipe.chain
         self.rs, self.ts, self.ps, self.tn, self.dy, self.ln, self.lv, self.en = self.chain.per_kind()
         self.pk = self.chain.pk  # with the packer a ring line begins with a prefix that says how many bytes follow

@@ -53,6 +53,7 @@ struct ptts_graph {
   hipGraphExec_t exec_c = nullptr;
   ptts_lm_state *lm = nullptr;
   ptts_mimi_state *mimi = nullptr;
+  int mimi_parts = 3, mimi_frames = 1;  // what of the codec frame the graph holds (PART_*), transformer frames per launch
   hipStream_t cap_stream = nullptr;
   int coop_wgs = 0;  // workgroups of the largest cooperative launch inside (0: none): the launch stream needs that many CUs
   hipStream_t cu_checked = nullptr;  // the last launch stream whose CU mask was found large enough (checked once per stream)
@@ -276,6 +277,7 @@ struct TrCtx {
   float *x_out;      // residual stream output of the layer (dbl-buffered if out_ds != 0)
   long out_ds;
   const int *par;
+  int out_ring = 0;  // x_out is the codec's hand-over ring (GemmArgs::yring): frames in the launch, 0: parity halves
   float *h, *ao, *ff, *q, *part;
   float *Kc, *Vc;
   const int *offset;
@@ -324,6 +326,7 @@ static void run_tr_layer(hipStream_t st, const TrLayer &T, const TrCtx &c) {
   SITE(s7.c_str());
   a = mk_gemm(T.ff2, c.ff, c.FF / 16, c.MT, c.M);
   a.epi = EPI_RES; a.R = c.x; a.RF = DF; a.Y = c.x_out; a.YF = DF; a.Ydstride = c.out_ds; a.par = c.par; a.ls = T.ls2;
+  a.yring = c.out_ring;
   launch_gemm(st, a, PRE_NONE);
   SITE("");
 }
@@ -479,7 +482,9 @@ static int build_engine(ptts_engine *e, const ptts_tensor *tensors, int32_t n) {
   e->mm.resize(c.m_layers);
   for (int l = 0; l < c.m_layers; ++l)
     CHK(pack_tr_layer(e, &e->mm[l], "mimi.decoder_transformer.transformer.layers." + std::to_string(l), C, c.m_ff, true));
-  e->ring = c.m_context > 0 ? (cdiv(c.m_context - 1, 16) + 1) * 16 : 0;
+  // the context in whole 16-row frames plus TWO frames being written: a frame pair's 32 queries per sequence need
+  // ring >= context + 31 (attn_valid).  The window mask decides what a query attends, not the ring's size
+  e->ring = c.m_context > 0 ? (cdiv(c.m_context - 1, 16) + 2) * 16 : 0;
   if (e->ring == 0) return fail(-4, "Mimi decoder transformer needs a finite context");
   int mult = 8, idx = 1;
   const int nf = c.n_filters;
@@ -583,7 +588,7 @@ __global__ void calib_latent_kernel(float *lat, int n, unsigned frame) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) lat[i] = counter_normal(0x5EEDull, frame, (unsigned)i);
 }
-static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm);
+static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, int parts = 3);
 static int build_fp8_codec(ptts_engine *e) {
   const ptts_config &c = e->cfg;
   const int nf = c.n_filters;
@@ -626,6 +631,7 @@ static int build_fp8_codec(ptts_engine *e) {
       calib_latent_kernel<<<cdiv(B * c.ldim, 256), 256, 0, st>>>(lat, B * c.ldim, (unsigned)f);
       rc = mimi_enqueue_h(st, e, ms, lat, nullptr);
       ms->h_frame += 1;
+      ms->h_tr += 1;
       // both parity halves hold bf16 data in their first half (see mimi_enqueue_h); scan them after every frame
       auto scan = [&](const float *buf, long stride, int slot) {
         for (int par = 0; par < 2; ++par) amax_bf16(st, (const char *)buf + (size_t)par * stride * 4, stride, amax + slot);
@@ -1812,24 +1818,30 @@ static int build_mimi_state(ptts_engine *e, ptts_mimi_state *s) {
   s->MTb = cdiv(B, 16);
   s->MT16 = B;  // one 16-row tile per sequence
   const int C = c.m_dim, CF = C / 16;
-  CHK(dallocT(nullptr, &s->frame, 1));
+  CHK(dallocT(nullptr, &s->frame, 4));  // frame, trf, trl
   CHK(dallocT(nullptr, &s->offset, B));
   CHK(dallocT(nullptr, &s->kv, (size_t)c.m_layers * 2 * s->kv_plane()));
   CHK(dallocT(nullptr, &s->zl, (size_t)s->MTb * 256 * (c.ldim / 16)));
   s->zq_stride = (long)s->MTb * 256 * CF;
   CHK(dallocT(nullptr, &s->zq, (size_t)2 * s->zq_stride));
   const size_t r16 = (size_t)s->MT16 * 256;
-  CHK(dallocT(nullptr, &s->u0, r16 * CF));
-  CHK(dallocT(nullptr, &s->u, r16 * CF));
-  CHK(dallocT(nullptr, &s->h, r16 * CF));
-  CHK(dallocT(nullptr, &s->ao, r16 * CF));
-  CHK(dallocT(nullptr, &s->ff, r16 * (c.m_ff / 16)));
-  CHK(dallocT(nullptr, &s->q, (size_t)B * c.m_heads * 4 * 256));
-  CHK(dallocT(nullptr, &s->rope, (size_t)B * 16 * 64));
-  s->splits = attn_splits(B * c.m_heads, e->ring / 16);
-  CHK(dallocT(nullptr, &s->part, (size_t)B * c.m_heads * s->splits * 16 * ATT_PSTRIDE));
+  // the transformer's buffers hold a frame pair (32 rows per sequence) on the fp32 codec, whose transformer takes pairs
+  const bool pairs = !e->codec_bf16;
+  const size_t r32 = pairs ? 2 * r16 : r16;
+  CHK(dallocT(nullptr, &s->u0, r32 * CF));
+  CHK(dallocT(nullptr, &s->u, r32 * CF));
+  CHK(dallocT(nullptr, &s->h, r32 * CF));
+  CHK(dallocT(nullptr, &s->ao, r32 * CF));
+  CHK(dallocT(nullptr, &s->ff, r32 * (c.m_ff / 16)));
+  CHK(dallocT(nullptr, &s->q, (size_t)B * c.m_heads * 4 * 256 * (pairs ? 2 : 1)));
+  CHK(dallocT(nullptr, &s->rope, (size_t)B * 16 * 64 * (pairs ? 2 : 1)));
+  // key tiles a 16-query block attends at most: the context in whole frames plus its own (the ring holds one frame more)
+  s->splits = attn_splits(B * c.m_heads, e->ring / 16 - 1);
+  s->splits2 = attn_splits(B * c.m_heads * 2, e->ring / 16 - 1);
+  CHK(dallocT(nullptr, &s->part, (size_t)B * c.m_heads * std::max(s->splits, pairs ? 2 * s->splits2 : 0) * 16 * ATT_PSTRIDE));
   s->tr_stride = (long)r16 * CF;
-  CHK(dallocT(nullptr, &s->tr_out, (size_t)2 * s->tr_stride));
+  s->tr_slots = pairs ? 4 : 2;
+  CHK(dallocT(nullptr, &s->tr_out, (size_t)s->tr_slots * s->tr_stride));
   int mult = 8, rows = 16;
   s->rows[0] = rows;
   s->a0_stride = (long)r16 * (mult * c.n_filters / 16);
@@ -1869,10 +1881,10 @@ extern "C" void ptts_mimi_state_destroy(ptts_mimi_state *s) {
 extern "C" int ptts_mimi_state_reset(ptts_mimi_state *s, void *stream) {
   hipStream_t st = S(s->e, stream);
   // zero-initialised carries == `previous` / `partial` zeros of init_state (conv.py:84-91,145-149)
-  HIPCHK(hipMemsetAsync(s->frame, 0, sizeof(int), st));
+  HIPCHK(hipMemsetAsync(s->frame, 0, 4 * sizeof(int), st));
   HIPCHK(hipMemsetAsync(s->offset, 0, s->B * sizeof(int), st));
   HIPCHK(hipMemsetAsync(s->zq, 0, (size_t)2 * s->zq_stride * 4, st));
-  HIPCHK(hipMemsetAsync(s->tr_out, 0, (size_t)2 * s->tr_stride * 4, st));
+  HIPCHK(hipMemsetAsync(s->tr_out, 0, (size_t)s->tr_slots * s->tr_stride * 4, st));
   HIPCHK(hipMemsetAsync(s->a0, 0, (size_t)2 * s->a0_stride * 4, st));
   for (int i = 0; i < 3; ++i) {
     HIPCHK(hipMemsetAsync(s->cbuf[i], 0, (size_t)2 * s->c_stride[i] * 4, st));
@@ -1880,7 +1892,7 @@ extern "C" int ptts_mimi_state_reset(ptts_mimi_state *s, void *stream) {
   }
   HIPCHK(hipMemsetAsync(s->kv, 0, (size_t)s->e->cfg.m_layers * 2 * s->kv_plane() * 4, st));
   if (s->pcm_carry) HIPCHK(hipMemsetAsync(s->pcm_carry, 0, (size_t)2 * s->pcm_cstride * 4, st));  // the fused last conv's tile carries
-  s->h_frame = 0;
+  s->h_frame = s->h_tr = 0;
   return 0;
 }
 
@@ -1903,6 +1915,7 @@ extern "C" int ptts_mimi_state_reset_row(ptts_mimi_state *s, int32_t row, void *
   for (int par = 0; par < 2; ++par) {
     zero_row_fm_kernel<<<cdiv(CF * 16, 256), 256, 0, st>>>(s->zq + par * s->zq_stride, CF, row);
     HIPCHK(zero_block(s->tr_out, s->tr_stride, par, e_tr));
+    if (s->tr_slots == 4) HIPCHK(zero_block(s->tr_out, s->tr_stride, par + 2, e_tr));
     HIPCHK(zero_block(s->a0, s->a0_stride, par, e_a0));
     for (int i = 0; i < 3; ++i) {
       HIPCHK(zero_block(s->cbuf[i], s->c_stride[i], par, e_a0));
@@ -1926,21 +1939,23 @@ extern "C" int ptts_mimi_set_pcm_i16(ptts_mimi_state *s, int16_t *d_pcm_i16) {
 
 // the codec frame with bf16 activations: same dataflow, buffers and carries as mimi_enqueue (the fp32 buffers are
 // reused, half filled); block counts are per 32 channels
-static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
+// parts: 1 = the transformer, 2 = SEANet, 3 = the whole frame (mimi_enqueue); single frames, tr_out's two parity halves
+static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm, int parts) {
   const ptts_config &c = e->cfg;
   bind_engine(e);
   KnobScope knobs(e->opt_codec_lds_target, e->opt_k_rotate);
   const int B = s->B, C = c.m_dim, CB = C / 32, st16 = c.upsample_stride;
+  const int M16 = B * st16, MT16 = s->MT16;
+  GemmArgs a;
+  if (parts & 1) {
   SITE("mimi.prologue");
   {
     ProfScope ps(st, "mimi_prologue", 4.0 * (B * c.ldim + (double)C * c.ldim) + B * C * (8.0 + 2.0 * st16), 2.0 * B * C * (c.ldim + 2.0 * st16));
     const int nb_main = cdiv((long)B * (C / 4) * st16, 256);
     mimi_prologue_kernel<<<nb_main + cdiv(B * st16 * 32, 256), 256, 0, st>>>(
-        d_latent, e->emb_std, e->emb_mean, e->quant_w, e->up_w, s->zq, s->zq_stride, s->frame, s->u0, B, c.ldim, C, st16,
-        nb_main, RopeArgs{s->offset, e->freq_mimi, s->rope, B * st16, st16}, 1);
+        d_latent, nullptr, e->emb_std, e->emb_mean, e->quant_w, e->up_w, s->zq, s->zq_stride, s->trl(), s->u0, B, c.ldim, C,
+        st16, nb_main, RopeArgs{s->offset, e->freq_mimi, s->rope, B * st16, st16}, 1);
   }
-  const int M16 = B * st16, MT16 = s->MT16;
-  GemmArgs a;
   for (int l = 0; l < c.m_layers; ++l) {
     const TrLayer &T = e->mm[l];
     float *x_in = l == 0 ? s->u0 : s->u;
@@ -1959,7 +1974,7 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     at.nseq = B;
     SITE("mimi.attn");
     {
-      const double keys = (double)B * std::min(e->ring, (s->h_frame + 1) * st16);
+      const double keys = (double)B * std::min(e->ring, (s->h_tr + 1) * st16);
       launch_attention(st, at, BH, 0, -1, keys * c.m_heads * 64 * 4 * 2 + 6.0 * M16 * C, 4.0 * keys * c.m_heads * 64 * 16);
     }
     SITE("mimi.out");
@@ -1973,9 +1988,16 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     SITE("mimi.ff2");
     a = mk_gemm(T.ff2, s->ff, c.m_ff / 32, MT16, M16);
     a.epi = EPI_RES; a.R = s->u; a.RF = CB; a.ls = T.ls2;
-    a.Y = last ? s->tr_out : s->u; a.YF = CB; a.Ydstride = last ? 2 * s->tr_stride : 0; a.par = last ? s->frame : nullptr;
+    a.Y = last ? s->tr_out : s->u; a.YF = CB; a.Ydstride = last ? 2 * s->tr_stride : 0; a.par = last ? s->trf() : nullptr;
     launch_gemm_h(st, a, PRE_NONE, T.ff2);
   }
+  if (parts == 1) {
+    SITE("mimi.tail");
+    ProfScope ps(st, "step_tail", 8.0 * B, 0);
+    mimi_tail_kernel<<<cdiv(B, 256), 256, 0, st>>>(s->offset, B, st16, s->frame, 1, 0);
+  }
+  }
+  if (!(parts & 2)) { SITE(""); return 0; }
   // strides of the frame-parity double buffers: the float buffers hold bf16 (or, for the inputs of the fp8 convolutions,
   // e4m3 bytes), so a parity step of `stride` floats is 2 * stride bf16 elements / 4 * stride bytes
   const bool f8 = e->codec_fp8;
@@ -2048,48 +2070,71 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
   SITE("mimi.tail");
   {
     ProfScope ps(st, "step_tail", 8.0 * B, 0);
-    step_tail_kernel<<<cdiv(B, 256), 256, 0, st>>>(s->offset, B, st16, s->frame, nullptr);
+    mimi_tail_kernel<<<cdiv(B, 256), 256, 0, st>>>(s->offset, B, st16, s->frame, parts == 3 ? 1 : 0, 1);
   }
   SITE("");
   return 0;
 }
 
-static int mimi_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
-  if (e->codec_bf16) return mimi_enqueue_h(st, e, s, d_latent, d_pcm);
+// The codec frame of the fp32 codec in two parts that meet in tr_out, a ring of 4 frame slots (frame f in slot f & 3):
+// the transformer part, for one frame or for a PAIR of consecutive frames in one launch sequence (rows b * 32 + t, the
+// T-general path of the prefills: twice the rows per GEMM, half the launches and weight reads per frame), and the SEANet
+// part, always one frame.  `tail`: the part ends with its own bookkeeping launch; the whole frame (mimi_enqueue) leaves
+// both parts' bookkeeping to ONE launch at its end, as before the split.
+static int mimi_tr_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, const float *d_latent2,
+                           bool tail) {
   const ptts_config &c = e->cfg;
   bind_engine(e);
   KnobScope knobs(e->opt_codec_lds_target, e->opt_k_rotate, e->codec_split);
-  const int B = s->B, C = c.m_dim, CF = C / 16, LF = c.ldim / 16, st16 = c.upsample_stride;
+  const int frames = d_latent2 ? 2 : 1;
+  const int B = s->B, C = c.m_dim, st16 = c.upsample_stride, Tq = st16 * frames;
   SITE("mimi.prologue");  // de-normalise + quantizer 1x1 conv + depthwise x16 upsample + RoPE table: one launch
   {
-    ProfScope ps(st, "mimi_prologue", 4.0 * (B * c.ldim + (double)C * c.ldim + B * C * (2.0 + st16)), 2.0 * B * C * (c.ldim + 2.0 * st16));
-    const int nb_main = cdiv((long)B * (C / 4) * st16, 256);
-    mimi_prologue_kernel<<<nb_main + cdiv(B * st16 * 32, 256), 256, 0, st>>>(
-        d_latent, e->emb_std, e->emb_mean, e->quant_w, e->up_w, s->zq, s->zq_stride, s->frame, s->u0, B, c.ldim, C, st16,
-        nb_main, RopeArgs{s->offset, e->freq_mimi, s->rope, B * st16, st16}, 0);
+    ProfScope ps(st, "mimi_prologue", 4.0 * (frames * B * c.ldim + (double)C * c.ldim + frames * B * C * (2.0 + st16)),
+                 2.0 * frames * B * C * (c.ldim + 2.0 * st16));
+    const int nb_main = cdiv((long)B * (C / 4) * Tq, 256);
+    mimi_prologue_kernel<<<nb_main + cdiv(B * Tq * 32, 256), 256, 0, st>>>(
+        d_latent, d_latent2, e->emb_std, e->emb_mean, e->quant_w, e->up_w, s->zq, s->zq_stride, s->trl(), s->u0, B, c.ldim, C,
+        st16, nb_main, RopeArgs{s->offset, e->freq_mimi, s->rope, B * Tq, Tq}, 0);
   }
-  GemmArgs a;
-  const int M16 = B * st16;
-
+  const int M = B * Tq;
   for (int l = 0; l < c.m_layers; ++l) {
     TrCtx t;
-    t.D = C; t.H = c.m_heads; t.FF = c.m_ff; t.MT = s->MT16; t.M = M16; t.Tq = st16; t.QB = 1;
-    t.cap = e->ring; t.ring = e->ring; t.ctx = c.m_context; t.splits = s->splits;
+    t.D = C; t.H = c.m_heads; t.FF = c.m_ff; t.MT = s->MT16 * frames; t.M = M; t.Tq = Tq; t.QB = frames;
+    t.cap = e->ring; t.ring = e->ring; t.ctx = c.m_context; t.splits = frames == 2 ? s->splits2 : s->splits;
     t.x_in = l == 0 ? s->u0 : s->u; t.x = s->u;
     const bool last = l == c.m_layers - 1;
-    t.x_out = last ? s->tr_out : s->u; t.out_ds = last ? s->tr_stride : 0; t.par = last ? s->frame : nullptr;
+    t.x_out = last ? s->tr_out : s->u; t.out_ds = last ? s->tr_stride : 0; t.par = last ? s->trf() : nullptr;
+    t.out_ring = last ? frames : 0;
     t.h = s->h; t.ao = s->ao; t.ff = s->ff; t.q = s->q; t.part = s->part;
     t.Kc = s->K(l); t.Vc = s->V(l); t.offset = s->offset; t.rope = s->rope;
-    t.kv_keys = (double)B * std::min(e->ring, (s->h_frame + 1) * st16);
+    t.kv_keys = (double)B * std::min(e->ring, (s->h_tr + frames) * st16);
     t.tag = "mimi";
     run_tr_layer(st, e->mm[l], t);
   }
+  if (tail) {
+    SITE("mimi.tail");
+    ProfScope ps(st, "step_tail", 8.0 * B, 0);
+    mimi_tail_kernel<<<cdiv(B, 256), 256, 0, st>>>(s->offset, B, Tq, s->frame, frames, 0);
+  }
+  SITE("");
+  return 0;
+}
+
+// `tail`: 1 = the part's own bookkeeping, 2 = a whole frame's (the transformer's single frame before it included)
+static int mimi_seanet_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, float *d_pcm, int tail) {
+  const ptts_config &c = e->cfg;
+  bind_engine(e);
+  KnobScope knobs(e->opt_codec_lds_target, e->opt_k_rotate, e->codec_split);
+  const int B = s->B, C = c.m_dim, CF = C / 16, st16 = c.upsample_stride;
+  GemmArgs a;
+  const int M16 = B * st16;
   // SEANet decoder (seanet.py:141-180) as implicit GEMMs over (sequence, time) rows
   int mult = 8;
   bool fused_pcm = false;
   SITE("seanet.conv0");
   a = mk_gemm(e->conv0, s->tr_out, CF, s->MT16, M16);
-  a.Xdstride = s->tr_stride; a.T = s->rows[0]; a.par = s->frame;
+  a.Xdstride = s->tr_stride; a.T = s->rows[0]; a.par = s->frame; a.xmask = 3;  // frame f and its halo f - 1 in the hand-over ring
   a.Y = s->a0; a.Ydstride = s->a0_stride; a.YF = mult * c.n_filters / 16;
   a.act = ACT_ELU;  // every SEANet conv input is ELU(previous output): apply it once, in the producer
   launch_gemm(st, a, PRE_NONE);
@@ -2171,10 +2216,38 @@ static int mimi_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, cons
   SITE("mimi.tail");
   {
     ProfScope ps(st, "step_tail", 8.0 * B, 0);
-    step_tail_kernel<<<cdiv(B, 256), 256, 0, st>>>(s->offset, B, st16, s->frame, nullptr);
+    mimi_tail_kernel<<<cdiv(B, 256), 256, 0, st>>>(s->offset, B, st16, s->frame, tail == 2 ? 1 : 0, 1);
   }
   SITE("");
   return 0;
+}
+
+// parts of a frame: PART_TR the transformer (one frame, or a pair with a second latent), PART_SEANET one SEANet frame
+// (with the PCM and the int16 copy); both = the whole frame.  The reduced-precision codecs take single frames only.
+enum { PART_TR = 1, PART_SEANET = 2, PART_ALL = 3 };
+static int mimi_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, const float *d_latent2,
+                        float *d_pcm, int parts) {
+  if (d_latent2 && (e->codec_bf16 || !(parts & PART_TR))) return fail(-1, "frame pairs: fp32 codec transformer only");
+  if (e->codec_bf16) return mimi_enqueue_h(st, e, s, d_latent, d_pcm, parts);
+  if (parts & PART_TR) CHK(mimi_tr_enqueue(st, e, s, d_latent, d_latent2, parts == PART_TR));
+  if (parts & PART_SEANET) CHK(mimi_seanet_enqueue(st, e, s, d_pcm, parts == PART_ALL ? 2 : 1));
+  return 0;
+}
+// host bookkeeping of an enqueued (or replayed) part, and what must hold before it: tr_out is a ring, a transformer launch
+// must not overwrite a slot that a waiting SEANet frame still reads (its own or its halo), SEANet needs a frame waiting
+static int mimi_parts_check(const ptts_mimi_state *s, int parts, int frames) {
+  int wait = s->h_tr - s->h_frame;  // frames in tr_out that SEANet has not read
+  if (parts & PART_TR) {
+    // writing frames n .. n + frames - 1 frees slots (n - 4 ..): the oldest waiting frame f reads f and f - 1
+    if (wait + frames + 1 > s->tr_slots) return fail(-1, "codec: the transformer is too far ahead of SEANet for the hand-over ring");
+    wait += frames;
+  }
+  if ((parts & PART_SEANET) && wait < 1) return fail(-1, "codec: SEANet has no transformer frame to decode");
+  return 0;
+}
+static void mimi_parts_done(ptts_mimi_state *s, int parts, int frames) {
+  if (parts & PART_TR) s->h_tr += frames;
+  if (parts & PART_SEANET) s->h_frame += 1;
 }
 
 // ---- the output chain -------------------------------------------------------------------------------------------------
@@ -2317,7 +2390,10 @@ extern "C" int ptts_mimi_set_packer(ptts_mimi_state *s, ptts_flac *pk, void *d_i
 }
 
 // the codec frame, then the launches of the links the state has; every refusal comes before the first launch
-static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm) {
+// (parts without PART_SEANET: the transformer alone, no stage launches)
+static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm,
+                              int parts = PART_ALL, const float *d_latent2 = nullptr) {
+  if (!(parts & PART_SEANET)) return mimi_enqueue(st, e, s, d_latent, d_latent2, nullptr, parts);
   const ChainLink *c = s->chain, &ts = c[CH_TS], &en = c[CH_EN];
   if (c[CH_LN].stage && !c[CH_LV].stage) return fail(-1, "the normaliser must be followed by a leveler, but the state has none");
   if (c[CH_TN].stage && !c[CH_LV].stage) return fail(-1, "the toner must be followed by a leveler, but the state has none");
@@ -2330,7 +2406,7 @@ static int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s
     return fail(-1, "the packer's input is not the buffer the encoder writes");
   const bool chained = ts.stage && ts.in;  // resampler -> ts.in -> stretcher
   if (chained && !c[CH_RS].stage) return fail(-1, "the stretcher reads a resampler's output, but the state has no resampler");
-  CHK(mimi_enqueue(st, e, s, d_latent, d_pcm));
+  CHK(mimi_enqueue(st, e, s, d_latent, d_latent2, d_pcm, parts));
   for (int k = 0; k < CH_N; k++) {
     if (!c[k].stage) continue;
     // a stage writes its own output, but for two that write f32 into the next one's input buffer: the stage before the
@@ -2349,8 +2425,32 @@ extern "C" int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float 
   ENGINE_LOCK(e);
   HIPCHK(hipSetDevice(e->device));
   if (!d_latent) return fail(-1, "null latent");
+  CHK(mimi_parts_check(s, PART_ALL, 1));
   CHK(mimi_frame_enqueue(S(e, stream), e, s, d_latent, d_pcm));
-  s->h_frame += 1;
+  mimi_parts_done(s, PART_ALL, 1);
+  LAUNCHCHK();
+  return 0;
+}
+
+// The codec frame in its two parts (see mimi_tr_enqueue), for callers that schedule them apart: the transformer of one
+// frame, or of a pair of consecutive frames (d_latent_b != NULL; fp32 codec), then one SEANet decode per frame, oldest first
+extern "C" int ptts_mimi_decode_tr(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, const float *d_latent_b, void *stream) {
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  if (!d_latent) return fail(-1, "null latent");
+  const int frames = d_latent_b ? 2 : 1;
+  CHK(mimi_parts_check(s, PART_TR, frames));
+  CHK(mimi_frame_enqueue(S(e, stream), e, s, d_latent, nullptr, PART_TR, d_latent_b));
+  mimi_parts_done(s, PART_TR, frames);
+  LAUNCHCHK();
+  return 0;
+}
+extern "C" int ptts_mimi_decode_seanet(ptts_engine *e, ptts_mimi_state *s, float *d_pcm, void *stream) {
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  CHK(mimi_parts_check(s, PART_SEANET, 0));
+  CHK(mimi_frame_enqueue(S(e, stream), e, s, nullptr, d_pcm, PART_SEANET));
+  mimi_parts_done(s, PART_SEANET, 0);
   LAUNCHCHK();
   return 0;
 }
@@ -2384,6 +2484,8 @@ extern "C" int ptts_tune_streams(ptts_engine *e, int32_t B, void *lm_stream, voi
     rc = ptts_lm_decode_step(e, ls, nullptr, nullptr, 1, 1e30f, nullptr, nullptr, nullptr, st);
     if (hipStreamSynchronize(st) != hipSuccess && rc == 0) rc = fail(-2, "tune: stream error");
     if (rc == 0) rc = ptts_mimi_decode(e, ms, ls->lat, nullptr, st2);
+    // the transformer's GEMMs at a frame pair's row count (the throughput pipeline decodes pairs)
+    if (rc == 0 && !e->codec_bf16) rc = ptts_mimi_decode_tr(e, ms, ls->lat, ls->lat, st2);
     t.active = false;
     e->prof.on = prof;
     if (hipStreamSynchronize(st2) != hipSuccess && rc == 0) rc = fail(-2, "tune: stream error");
@@ -2652,6 +2754,34 @@ extern "C" int ptts_graph_capture_mimi(ptts_engine *e, ptts_mimi_state *s, const
   return 0;
 }
 
+// The codec frame's parts as graphs of their own (ptts_mimi_decode_tr / _seanet): the transformer of one frame or, with
+// d_latent_b, of a frame pair; SEANet of one frame with the state's output stages behind it
+static int capture_mimi_parts(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, const float *d_latent_b, float *d_pcm,
+                              int parts, ptts_graph **out) {
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  ptts_graph *g = new ptts_graph();
+  g->mimi = s;
+  g->mimi_parts = parts;
+  g->mimi_frames = d_latent_b ? 2 : 1;
+  const int rc = capture(e, g, [&](hipStream_t st) { return mimi_frame_enqueue(st, e, s, d_latent, d_pcm, parts, d_latent_b); });
+  if (rc < 0) { g->mimi = nullptr; ptts_graph_destroy(g); return rc; }
+  *out = g;
+  return 0;
+}
+extern "C" int ptts_graph_capture_mimi_tr(ptts_engine *e, ptts_mimi_state *s, const float *d_latent, ptts_graph **out) {
+  if (!d_latent) return fail(-1, "null latent");
+  return capture_mimi_parts(e, s, d_latent, nullptr, nullptr, PART_TR, out);
+}
+extern "C" int ptts_graph_capture_mimi_tr_pair(ptts_engine *e, ptts_mimi_state *s, const float *d_latent_a,
+                                               const float *d_latent_b, ptts_graph **out) {
+  if (!d_latent_a || !d_latent_b) return fail(-1, "null latent");
+  return capture_mimi_parts(e, s, d_latent_a, d_latent_b, nullptr, PART_TR, out);
+}
+extern "C" int ptts_graph_capture_mimi_seanet(ptts_engine *e, ptts_mimi_state *s, float *d_pcm, ptts_graph **out) {
+  return capture_mimi_parts(e, s, nullptr, nullptr, d_pcm, PART_SEANET, out);
+}
+
 // One graph, two parallel branches: FlowLM step (writes d_latent_out) || Mimi decode of the PREVIOUS frame
 // (reads d_mimi_latent_in, a different buffer).  Fork/join inside the capture, so a replay needs no
 // cross-stream events: consecutive launches on one stream give step t+1 || frame t.
@@ -2701,6 +2831,7 @@ extern "C" int ptts_graph_launch(ptts_graph *g, void *stream) {
     for (int b = 0; b < g->lm->B; ++b)
       if (g->lm->h_off[b] + 1 > g->lm->cap) return fail(-5, "decode: KV cache capacity exceeded");
   }
+  if (g->mimi) CHK(mimi_parts_check(g->mimi, g->mimi_parts, g->mimi_frames));
   {
     if (g->coop_wgs > 0 && g->cu_checked != S(e, stream)) {
       if (g->coop_wgs > stream_cu_count(S(e, stream), e->n_cus))
@@ -2712,7 +2843,7 @@ extern "C" int ptts_graph_launch(ptts_graph *g, void *stream) {
     if (guard.finish() < 0) return fail(-2, "graph launch: could not chain the cooperative launch behind its predecessor");
   }
   if (g->lm) for (int b = 0; b < g->lm->B; ++b) g->lm->h_off[b] += g->lm->h_active[b];
-  if (g->mimi) g->mimi->h_frame += 1;
+  if (g->mimi) mimi_parts_done(g->mimi, g->mimi_parts, g->mimi_frames);
   return 0;
 }
 

@@ -90,7 +90,12 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
     const int par = (s->h_frame - 1) & 1;  // parity of the frame decoded last
     const int B = s->B;
     if (n == "upsample") { src = s->u0; M = B * 16; K = c.m_dim; }
-    else if (n == "dec_tr") { src = s->tr_out + par * s->tr_stride; M = B * 16; K = c.m_dim; }
+    else if (n == "dec_tr") { src = s->tr_out + ((s->h_frame - 1) & (s->tr_slots - 1)) * s->tr_stride; M = B * 16; K = c.m_dim; }
+    else if (n.compare(0, 11, "dec_tr_slot") == 0) {  // slot k of the hand-over ring (frame f lies in slot f & (slots - 1))
+      const int k = atoi(n.c_str() + 11);
+      if (n.size() != 12 || k < 0 || k >= s->tr_slots) return fail(-1, "unknown buffer " + n);
+      src = s->tr_out + k * s->tr_stride; M = B * 16; K = c.m_dim;
+    }
     else if (n == "seanet0") { src = s->a0 + par * s->a0_stride; M = B * 16; K = 8 * c.n_filters; }
     else if (n == "tr_attn") { src = s->ao; M = B * 16; K = c.m_dim; }       // last layer's attention output
     else if (n == "tr_resid") { src = s->u; M = B * 16; K = c.m_dim; }       // last layer's stream after attention

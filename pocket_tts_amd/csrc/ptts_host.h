@@ -263,8 +263,18 @@ struct ChainLink {
 struct ptts_mimi_state {
   ptts_engine *e;
   int B, MTb, MT16;
+  // device counters, three ints at `frame` (mimi_tail_kernel): frames through SEANet (frame parity of every conv carry),
+  // frames through the transformer (trf = frame + 1: the slot of the hand-over ring), transformer launches (trl = frame + 2:
+  // the parity of zq, which a frame pair writes once)
   int *frame = nullptr, *offset = nullptr;
-  int h_frame = 0;
+  int *trf() const { return frame + 1; }
+  int *trl() const { return frame + 2; }
+  int h_frame = 0;  // frames through SEANet, host copy
+  int h_tr = 0;     // frames through the transformer, host copy (h_tr - h_frame frames wait in tr_out)
+  // tr_out: the transformer's hand-over to SEANet's first conv, a ring of tr_slots frames of tr_stride floats (fp32 codec:
+  // 4, frame f in slot f & 3, so that a frame pair fits beside the frame before it; reduced-precision codecs: the two
+  // parity halves).  splits2: key splits of a frame pair's attention (32 queries per sequence)
+  int tr_slots = 2, splits2 = 1;
   float *kv = nullptr;  // [ML][2][B][H][ring][64]
   float *zl, *zq, *u0, *u, *h, *ao, *ff, *q, *part, *tr_out, *rope;
   long zq_stride, tr_stride;

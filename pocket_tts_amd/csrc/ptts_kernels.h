@@ -127,6 +127,11 @@ struct GemmArgs {
   int xstride, halo, halo_mode;
   const float *zeros;  // >= 16 B of zeros (halo_mode 1)
   const int *par;    // device frame counter (parity = *par & 1) or null
+  // frame rings in place of the two parity halves (the codec transformer's hand-over to SEANet, 4 slots of Xdstride /
+  // Ydstride floats).  xmask = 3: X's current frame is slot *par & 3, its previous frame the slot before it; 0: parity
+  // halves.  yring (EPI_RES): 1 = the launch's rows are frame *par and go to slot *par & 3; 2 = a frame pair in rows
+  // b * 32 + t: row tile mt belongs to frame *par + (mt & 1) and is that frame's tile mt >> 1; 0: parity halves
+  int xmask, yring;
   const float *prevec;  // PRE_ADDSILU: per-k vector
   // PRE_LNFOLD: LayerNorm folded into this GEMM.  W is packed with the LN gain multiplied in (W' = W diag(g)),
   // ln_s[n] = sum_k W'[n][k], ln_c[n] = sum_k W[n][k] beta[k] (+ bias); the kernel accumulates sum(x), sum(x^2)
@@ -283,7 +288,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &a, f32x4 acc, int 
       f32x4 rv = pf ? pf->r : *(const f32x4 *)(r + (((size_t)mt * a.RF + nt) * 64 + lane) * 4);
       if (a.ls) acc *= *(const f32x4 *)(a.ls + n0);
       float *y = a.Y + par * a.Ydstride;
-      *(f32x4 *)(y + (((size_t)mt * a.YF + nt) * 64 + lane) * 4) = act4(rv + acc, a.act);
+      size_t mty = mt;
+      if (a.yring) {  // uniform over the launch
+        const int pair = a.yring == 2;
+        y = a.Y + ((*a.par + (pair ? (mt & 1) : 0)) & 3) * a.Ydstride;
+        mty = pair ? mt >> 1 : mt;
+      }
+      *(f32x4 *)(y + ((mty * a.YF + nt) * 64 + lane) * 4) = act4(rv + acc, a.act);
     } break;
     case EPI_GATE: {
       f32x4 rv = pf ? pf->r : *(const f32x4 *)(a.R + (((size_t)mt * a.RF + nt) * 64 + lane) * 4);
@@ -407,9 +418,10 @@ __global__ __launch_bounds__(64 * WK * WN * WM) void gemm_kernel(GemmArgs a) {
   tile_of_block(a.swz, bx, by);
   const int nt0 = (bx * WN + wn) * TN;
   const int mt0 = (by * WM + wm) * TM;
-  const int par = a.par ? (*a.par & 1) : 0;
-  const float *Xc = a.X + par * a.Xdstride;
-  const float *Xp = a.X + (par ^ 1) * a.Xdstride;
+  const int praw = a.par ? *a.par : 0, par = praw & 1;
+  const int xm = a.xmask | 1, xpar = praw & xm;  // xmask 0: the two parity halves, (xpar - 1) & 1 == par ^ 1
+  const float *Xc = a.X + xpar * a.Xdstride;
+  const float *Xp = a.X + ((xpar - 1) & xm) * a.Xdstride;
   const int k0 = (a.KF * wk) / WK, k1 = (a.KF * (wk + 1)) / WK;
 
   float sx[TM], sxx[TM];  // PRE_LNFOLD row statistics (this lane's row of each m-tile, its k-groups only)
@@ -982,9 +994,10 @@ __global__ __launch_bounds__(256) void gemm_lds_kernel(GemmArgs a) {
   int bx, by;
   tile_of_block(a.swz, bx, by);
   const int mt0 = by * BMT, nt0 = bx * BNT;
-  const int par = a.par ? (*a.par & 1) : 0;
-  const float *Xc = a.X + par * a.Xdstride;
-  const float *Xp = a.X + (par ^ 1) * a.Xdstride;
+  const int praw = a.par ? *a.par : 0, par = praw & 1;
+  const int xm = a.xmask | 1, xpar = praw & xm;  // as in gemm_kernel
+  const float *Xc = a.X + xpar * a.Xdstride;
+  const float *Xp = a.X + ((xpar - 1) & xm) * a.Xdstride;
   const int halo = a.halo;
 
   // loader bookkeeping: this wave copies X fragments of m-tiles {wave, wave+4, ..} and W fragments f % 4 == wave
@@ -1578,42 +1591,49 @@ static __global__ __launch_bounds__(256) void prep_in_kernel(const float *lat_in
 //     out[b, t, c] = zq[b, c] w[c, t] + zq_prev[b, c] w[c, s + t]
 // zq is double-buffered by frame parity (FM layout, one row per sequence), so `partial` is never materialised.
 // The three tiny launches this replaces cost more in launch latency than in work.
-static __global__ void mimi_prologue_kernel(const float *lat, const float *std, const float *mean, const float *wq,
-                                     const float *wup, float *zq, long zdstride, const int *par_p, float *out, int B,
-                                     int ldim, int C, int s, int nb_main, RopeArgs rope, int h16) {
+static __global__ void mimi_prologue_kernel(const float *lat, const float *lat2, const float *std, const float *mean,
+                                     const float *wq, const float *wup, float *zq, long zdstride, const int *par_p,
+                                     float *out, int B, int ldim, int C, int s, int nb_main, RopeArgs rope, int h16) {
   if ((int)blockIdx.x >= nb_main) {
     rope_table_entry(rope, (blockIdx.x - nb_main) * blockDim.x + threadIdx.x);
     return;
   }
   // thread = (sequence b, 4 channels c, output step t), t fastest: the s threads of one (b, c) recompute the same
-  // 4 x ldim dot products from broadcast loads (cheaper than a second phase) and write s adjacent 16-byte outputs
-  const int C4 = C / 4, CF = C / 16;
+  // 4 x ldim dot products from broadcast loads (cheaper than a second phase) and write s adjacent 16-byte outputs.
+  // lat2 != null: a frame pair, rows b * 2s + t: steps t < s are frame A (lat), steps t >= s frame B (lat2), whose
+  // carry is A's quantised vector: B's threads recompute it instead of waiting for A's; only B's is stored
+  const int C4 = C / 4, CF = C / 16, S = lat2 ? 2 * s : s;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)B * C4 * s) return;
-  const int t = (int)(i % s);
-  const int c = (int)((i / s) % C4) * 4, b = (int)(i / ((long)s * C4));
+  if (i >= (long)B * C4 * S) return;
+  const int tp = (int)(i % S);
+  const int c = (int)((i / S) % C4) * 4, b = (int)(i / ((long)S * C4));
+  const bool second = tp >= s;
+  const int t = second ? tp - s : tp;
   const int par = *par_p & 1;
-  f32x4 zc = {0.f, 0.f, 0.f, 0.f};
-  const float *lr = lat + (size_t)b * ldim;
-  for (int k = 0; k < ldim; k += 4) {
-    const f32x4 z = *(const f32x4 *)(lr + k) * *(const f32x4 *)(std + k) + *(const f32x4 *)(mean + k);
-    const f32x4 w0 = *(const f32x4 *)(wq + (size_t)(c + 0) * ldim + k), w1 = *(const f32x4 *)(wq + (size_t)(c + 1) * ldim + k);
-    const f32x4 w2 = *(const f32x4 *)(wq + (size_t)(c + 2) * ldim + k), w3 = *(const f32x4 *)(wq + (size_t)(c + 3) * ldim + k);
-    zc.x += (z.x * w0.x + z.y * w0.y) + (z.z * w0.z + z.w * w0.w);
-    zc.y += (z.x * w1.x + z.y * w1.y) + (z.z * w1.z + z.w * w1.w);
-    zc.z += (z.x * w2.x + z.y * w2.y) + (z.z * w2.z + z.w * w2.w);
-    zc.w += (z.x * w3.x + z.y * w3.y) + (z.z * w3.z + z.w * w3.w);
-  }
+  auto quant = [&](const float *lr) {
+    f32x4 zc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < ldim; k += 4) {
+      const f32x4 z = *(const f32x4 *)(lr + k) * *(const f32x4 *)(std + k) + *(const f32x4 *)(mean + k);
+      const f32x4 w0 = *(const f32x4 *)(wq + (size_t)(c + 0) * ldim + k), w1 = *(const f32x4 *)(wq + (size_t)(c + 1) * ldim + k);
+      const f32x4 w2 = *(const f32x4 *)(wq + (size_t)(c + 2) * ldim + k), w3 = *(const f32x4 *)(wq + (size_t)(c + 3) * ldim + k);
+      zc.x += (z.x * w0.x + z.y * w0.y) + (z.z * w0.z + z.w * w0.w);
+      zc.y += (z.x * w1.x + z.y * w1.y) + (z.z * w1.z + z.w * w1.w);
+      zc.z += (z.x * w2.x + z.y * w2.y) + (z.z * w2.z + z.w * w2.w);
+      zc.w += (z.x * w3.x + z.y * w3.y) + (z.z * w3.z + z.w * w3.w);
+    }
+    return zc;
+  };
+  const f32x4 zc = quant((second ? lat2 : lat) + (size_t)b * ldim);
   const size_t zi = (((size_t)(b >> 4) * CF + (c >> 4)) * 64 + 16 * ((c & 15) >> 2) + (b & 15)) * 4;
-  const f32x4 zp = *(const f32x4 *)(zq + (par ^ 1) * zdstride + zi);
-  if (t == 0) *(f32x4 *)(zq + par * zdstride + zi) = zc;  // next frame's zq_prev
+  const f32x4 zp = second ? quant(lat + (size_t)b * ldim) : *(const f32x4 *)(zq + (par ^ 1) * zdstride + zi);
+  if (lat2 ? tp == s : tp == 0) *(f32x4 *)(zq + par * zdstride + zi) = zc;  // the next launch's zq_prev
   const int k2 = 2 * s;
   f32x4 o;
   o.x = zc.x * wup[(c + 0) * k2 + t] + zp.x * wup[(c + 0) * k2 + s + t];
   o.y = zc.y * wup[(c + 1) * k2 + t] + zp.y * wup[(c + 1) * k2 + s + t];
   o.z = zc.z * wup[(c + 2) * k2 + t] + zp.z * wup[(c + 2) * k2 + s + t];
   o.w = zc.w * wup[(c + 3) * k2 + t] + zp.w * wup[(c + 3) * k2 + s + t];
-  const long m = (long)b * s + t;
+  const long m = (long)b * S + tp;
   if (h16) *(bf16x4 *)((__bf16 *)out + fmh_off((size_t)m, c, C / 32)) = to_bf16x4(o);
   else *(f32x4 *)(out + (((size_t)(m >> 4) * CF + (c >> 4)) * 64 + 16 * ((c & 15) >> 2) + (m & 15)) * 4) = o;
 }
@@ -1654,6 +1674,16 @@ static __global__ void step_tail_kernel(int *offset, int n, int inc, int *counte
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && (!active || active[i])) offset[i] += inc;
   if (i == 0 && counter) *counter += 1;
+}
+// the codec's bookkeeping behind a launch, ctr = {frames through SEANet, frames through the transformer, transformer
+// launches}: a transformer launch of `tr` frames advances the positions by `inc` and ctr[1], ctr[2]; a SEANet frame ctr[0]
+static __global__ void mimi_tail_kernel(int *offset, int n, int inc, int *ctr, int tr, int seanet) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && tr) offset[i] += inc;
+  if (i == 0) {
+    if (seanet) ctr[0] += 1;
+    if (tr) { ctr[1] += tr; ctr[2] += 1; }
+  }
 }
 // zero row `row` of an FM buffer with F k-fragments per row tile (a joining utterance's codec carries)
 static __global__ void zero_row_fm_kernel(float *buf, int F, int row) {

@@ -1174,6 +1174,42 @@ class Engine:
         _lib.check(self.lib.ptts_graph_capture_mimi(self.handle, state.handle, lp, _ptr(pcm), C.byref(g)))
         return g
 
+    def capture_mimi_tr(self, state: MimiState, latent, latent_b=None):
+        """the codec transformer of one frame, or of the frame pair (latent, latent_b), as a graph of its own"""
+        g = C.c_void_p()
+        if latent_b is None:
+            _lib.check(self.lib.ptts_graph_capture_mimi_tr(self.handle, state.handle, _ptr(latent), C.byref(g)))
+        else:
+            _lib.check(self.lib.ptts_graph_capture_mimi_tr_pair(self.handle, state.handle, _ptr(latent), _ptr(latent_b),
+                                                                C.byref(g)))
+        return g
+
+    def capture_mimi_seanet(self, state: MimiState, pcm: torch.Tensor):
+        """SEANet of the oldest frame the transformer has handed over, with the state's output stages behind it"""
+        g = C.c_void_p()
+        _lib.check(self.lib.ptts_graph_capture_mimi_seanet(self.handle, state.handle, _ptr(pcm), C.byref(g)))
+        return g
+
+    def mimi_decode_tr(self, state: MimiState, latent: torch.Tensor, latent_b: torch.Tensor | None = None):
+        """eager `ptts_mimi_decode_tr`: the transformer part of one frame or of a frame pair"""
+        self._pre()
+        _lib.check(self.lib.ptts_mimi_decode_tr(self.handle, state.handle, _ptr(latent),
+                                                _ptr(latent_b) if latent_b is not None else None, self._sp))
+        for t in (latent, latent_b):
+            if t is not None:
+                t.record_stream(self.stream)
+        self._post()
+
+    def mimi_decode_seanet(self, state: MimiState, out_pcm=None) -> torch.Tensor:
+        """eager `ptts_mimi_decode_seanet`: pcm f32[B, frame_samples] of the oldest frame handed over"""
+        if out_pcm is None:
+            out_pcm = torch.empty((state.batch, self.frame_samples), dtype=torch.float32, device=self.device)
+        self._pre()
+        _lib.check(self.lib.ptts_mimi_decode_seanet(self.handle, state.handle, _ptr(out_pcm), self._sp))
+        out_pcm.record_stream(self.stream)
+        self._post()
+        return out_pcm
+
     def graph_launch(self, g, stream: torch.cuda.Stream | None = None):
         sp = self._sp if stream is None else C.c_void_p(stream.cuda_stream)
         _lib.check(self.lib.ptts_graph_launch(g, sp))
@@ -1481,12 +1517,19 @@ class StepPipeline:
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None, spec=None, **chain):
+                 lm_stream: torch.cuda.Stream | None = None, spec=None, codec_pair: bool | None = None, **chain):
         from .output_chain import ChainSpec, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
         B, dev = lm_state.batch, eng.device
         self.mode = mode or ("hostsync" if B <= 8 else "events")
+        # frame pairs through the codec transformer ("events" mode, fp32 codec): None = PTTS_CODEC_PAIR (default 1) for
+        # throughput batches (> 8 rows, where "events" is the default mode); smaller batches run for latency, and a frame
+        # that waits for its partner is 80 ms late
+        if codec_pair is None:
+            codec_pair = os.environ.get("PTTS_CODEC_PAIR", "1") != "0" and B > 8
+        self.codec_pair = bool(codec_pair) and self.mode == "events" and not (
+            {"codec_bf16", "codec_fp8"} & set(eng.quantize_groups))
         # the plan table first: what the rules refuse is refused before anything is allocated
         table = ChainSpec.of(spec, **chain).table(eng.sample_rate, eng.frame_samples)
         if not table.empty and self.mode == "fork":
@@ -1520,13 +1563,17 @@ class StepPipeline:
         # optional 16-bit PCM beside the fp32 one (the WAV sample format, data/audio.py:79), also pinned
         self.pcm16 = [torch.zeros(B, eng.frame_samples, dtype=torch.int16).pin_memory() for _ in range(nb)] \
             if pcm_i16 and self.out is None else None
-        self.g_last = []
+        self.g_last, self.g_sn, self.g_tr1, self.g_tr2 = [], [], [], []
         for p in range(nb):
             if self.out is not None:  # the 16-bit conversion happens behind the last output stage
                 self.chain.attach(mimi_state, p)
             else:
                 mimi_state.set_pcm_i16(self.pcm16[p] if pcm_i16 else None)
             self.g_last.append(eng.capture_mimi(mimi_state, self.lat[p], self.pcm[p]))
+            if self.codec_pair:  # the frame's parts: SEANet with the same stages behind it as the whole frame
+                self.g_sn.append(eng.capture_mimi_seanet(mimi_state, self.pcm[p]))
+                self.g_tr1.append(eng.capture_mimi_tr(mimi_state, self.lat[p]))
+                self.g_tr2.append(eng.capture_mimi_tr(mimi_state, self.lat[(p - 1) % nb], self.lat[p]))
         mimi_state.set_pcm_i16(None)
         self.chain.detach(mimi_state)
         self.g_both = []
@@ -1573,7 +1620,12 @@ class StepPipeline:
     def step(self):
         """Launch FlowLM step t and the decode of frame t-1.  Returns the index of the frame whose PCM is
         complete when `done_event(frame)` fires (None for the first step).  After the call,
-        `flag[(t-1) % nb]` (hostsync mode) holds the EOS flags of step t-1."""
+        `flag[(t-1) % nb]` (hostsync mode) holds the EOS flags of step t-1.
+
+        With `codec_pair` the codec runs behind every SECOND step: after an odd step t the transformer of the frame pair
+        (t-1, t) in one launch sequence, then SEANet of t-1 and of t, each with its `done_event`; the call returns t (frame
+        t-1 is complete before it).  An even step returns None and leaves its frame pending: the next step, `flush()` or
+        `restart()` decodes it, and until then `done_event` of that frame is the event of an EARLIER frame."""
         eng, p = self.eng, self.t % self.nb
         done = None
         if self.mode == "fork":
@@ -1588,11 +1640,24 @@ class StepPipeline:
             self.s1.wait_event(self.ev[p])             # codec frame t-nb done: lat[p] / pcm[p] are free
             eng.graph_launch(self.g_first[p], self.s1)  # FlowLM step t -> lat[p]
             self.ev_lm[p].record(self.s1)
-            self.s2.wait_event(self.ev_lm[p])
-            eng.graph_launch(self.g_last[p], self.s2)  # codec frame t -> pcm[p] (overlaps FlowLM step t+1)
-            self.ev[p].record(self.s2)
-            self.decoded += 1
-            done = self.t
+            if self.codec_pair and self.t % 2 == 0:
+                pass  # the frame waits for its partner
+            elif self.codec_pair:
+                q = (p - 1) % self.nb
+                self.s2.wait_event(self.ev_lm[p])           # step t done, and step t-1 before it on the same stream
+                eng.graph_launch(self.g_tr2[p], self.s2)    # transformer of frames t-1 and t
+                eng.graph_launch(self.g_sn[q], self.s2)     # SEANet frame t-1 -> pcm[q]
+                self.ev[q].record(self.s2)
+                eng.graph_launch(self.g_sn[p], self.s2)     # SEANet frame t -> pcm[p]
+                self.ev[p].record(self.s2)
+                self.decoded += 2
+                done = self.t
+            else:
+                self.s2.wait_event(self.ev_lm[p])
+                eng.graph_launch(self.g_last[p], self.s2)  # codec frame t -> pcm[p] (overlaps FlowLM step t+1)
+                self.ev[p].record(self.s2)
+                self.decoded += 1
+                done = self.t
         else:
             self.s1.wait_event(self.ev[p])  # frame t-2 decoded: lat[p] / pcm[p] may be reused (long done)
             eng.graph_launch(self.g_first[p], self.s1)
@@ -1631,6 +1696,13 @@ class StepPipeline:
         if self.mode == "hostsync":
             return self._decode_pending()
         p = (self.t - 1) % self.nb
+        if self.codec_pair:  # the frame an even step left pending, as a single frame in its two parts, on the codec stream
+            self.s2.wait_event(self.ev_lm[p])
+            self.eng.graph_launch(self.g_tr1[p], self.s2)
+            self.eng.graph_launch(self.g_sn[p], self.s2)
+            self.ev[p].record(self.s2)
+            self.decoded += 1
+            return self.decoded - 1
         self.eng.graph_launch(self.g_last[p])
         self.ev[p].record(self.eng.stream)
         self.decoded += 1
@@ -1664,6 +1736,6 @@ class StepPipeline:
 
     def close(self):
         self.sync()
-        for g in self.g_first + self.g_last + self.g_both:
+        for g in self.g_first + self.g_last + self.g_both + self.g_sn + self.g_tr1 + self.g_tr2:
             self.eng.graph_destroy(g)
         self.chain.close()

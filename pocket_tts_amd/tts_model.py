@@ -350,8 +350,9 @@ class TTSModel:
                 batch, ms = eng.new_lm_state(B, cap), eng.new_mimi_state(B)
                 if use_noise:
                     batch.set_noise(self.temp, int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+                # codec_pair off: the loop below collects every frame by its own done_event as soon as it fires
                 pipe = StepPipeline(eng, batch, ms, None, self.lsd_decode_steps, float(self.eos_threshold), mode="events",
-                                    compressions=None if compression is None else [compression])
+                                    codec_pair=False, compressions=None if compression is None else [compression])
                 ctx = dict(st=batch, ms=ms, pipe=pipe, seeded=[False] * B, clamped=[False] * B)
             batch, ms, pipe = ctx["st"], ctx["ms"], ctx["pipe"]
             nb = pipe.nb

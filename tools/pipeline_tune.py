@@ -27,7 +27,7 @@ def recapture():
     old = job.pipe
     job.pipe.flush(); job.sync(); torch.cuda.synchronize()
     job.pipe = StepPipeline(eng, job.st, job.ms, None, 1, float("inf"))
-    for g in old.g_first + old.g_last:
+    for g in old.g_first + old.g_last + old.g_sn + old.g_tr1 + old.g_tr2:
         eng.graph_destroy(g)
 
 
@@ -50,8 +50,11 @@ table = {}
 for ln in eng._tune_table():
     f = ln.split()
     table[tuple(int(x) for x in f[:13])] = int(f[13])
-# the shapes of THIS batch: FlowLM rows = ceil(B / 16) row tiles, codec rows = B * 16 * {1, 6, 30, 120} / 16
-mts = {(B + 15) // 16, B, 6 * B, 30 * B, 120 * B}
+# the shapes of THIS batch: FlowLM rows = ceil(B / 16) row tiles, codec rows = B * 16 * {1, 6, 30, 120} / 16, and the codec
+# transformer on a frame pair (2 B row tiles).  PTTS_PIPELINE_TUNE_MT="128,64": only these row-tile counts
+mts = {(B + 15) // 16, B, 2 * B, 6 * B, 30 * B, 120 * B}
+if os.environ.get("PTTS_PIPELINE_TUNE_MT"):
+    mts &= {int(v) for v in os.environ["PTTS_PIPELINE_TUNE_MT"].split(",")}
 keys = [k for k in table if k[4] in mts]
 print(f"batch {B}: {len(keys)} shapes, start {measure(3):.4f} ms/step", flush=True)
 
