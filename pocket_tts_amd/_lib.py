@@ -214,7 +214,8 @@ PROTOTYPES = {
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile csrc/*.hip for gfx950 in-tree (hipcc cross-compiles without a GPU).  Every .hip file is one translation
     unit:
-      * ptts.hip = host side: engine, states, step orchestration, graphs, C ABI;
+      * ptts.hip = host side: engine, FlowLM states and step, graphs, C ABI;
+      * ptts_codec.hip = the Mimi codec's host side: its state, frame walks, output chain, decode entry points, voice encoder;
       * ptts_dispatch.hip = the GEMM / attention dispatchers and the tuner, the only unit that instantiates the round-1/2
         kernel templates;
       * ptts_debug.hip = the C ABI's test hooks;
@@ -223,12 +224,12 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         the pitch shifter, ptts_tone.hip = the equaliser, ptts_dyn.hip = the compressor, ptts_loud.hip = the loudness
         normaliser, ptts_level.hip = the
         output gain with its peak limiter, ptts_encode.hip = the output encoder (16-bit and float PCM, G.711) and
-        ptts_flac.hip = the packer (FLAC frames); how they are wired behind the codec is ptts.hip's (its section "the output
+        ptts_flac.hip = the packer (FLAC frames); how they are wired behind the codec is ptts_codec.hip's (its section "the output
         chain").  What their host sides share (the struct's head, owned device buffers, refusals, the drain flag) is
         ptts_stage.h with ptts_stage.hip; the chunked scan of the equaliser, the compressor and the normaliser is
         ptts_scan.h;
       * newer kernel families live in their own files behind plain C++ launcher functions declared in ptts_ext.h.
-    ptts.hip, ptts_dispatch.hip, ptts_debug.hip and the stage units see each other through ptts_host.h.  The units are
+    ptts.hip, ptts_codec.hip, ptts_dispatch.hip, ptts_debug.hip and the stage units see each other through ptts_host.h.  The units are
     compiled in parallel to csrc/.obj/*.o and linked into libptts.so; a unit is recompiled when it or any header is newer than its object."""
     from concurrent.futures import ThreadPoolExecutor
 

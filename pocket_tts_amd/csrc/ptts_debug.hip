@@ -90,13 +90,13 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
     const int par = (s->h_frame - 1) & 1;  // parity of the frame decoded last
     const int B = s->B;
     if (n == "upsample") { src = s->u0; M = B * 16; K = c.m_dim; }
-    else if (n == "dec_tr") { src = s->tr_out + ((s->h_frame - 1) & (s->tr_slots - 1)) * s->tr_stride; M = B * 16; K = c.m_dim; }
+    else if (n == "dec_tr") { src = s->tr_out.slot((s->h_frame - 1) & (s->tr_out.slots - 1)); M = B * 16; K = c.m_dim; }
     else if (n.compare(0, 11, "dec_tr_slot") == 0) {  // slot k of the hand-over ring (frame f lies in slot f & (slots - 1))
       const int k = atoi(n.c_str() + 11);
-      if (n.size() != 12 || k < 0 || k >= s->tr_slots) return fail(-1, "unknown buffer " + n);
-      src = s->tr_out + k * s->tr_stride; M = B * 16; K = c.m_dim;
+      if (n.size() != 12 || k < 0 || k >= s->tr_out.slots) return fail(-1, "unknown buffer " + n);
+      src = s->tr_out.slot(k); M = B * 16; K = c.m_dim;
     }
-    else if (n == "seanet0") { src = s->a0 + par * s->a0_stride; M = B * 16; K = 8 * c.n_filters; }
+    else if (n == "seanet0") { src = s->a0.slot(par); M = B * 16; K = 8 * c.n_filters; }
     else if (n == "tr_attn") { src = s->ao; M = B * 16; K = c.m_dim; }       // last layer's attention output
     else if (n == "tr_resid") { src = s->u; M = B * 16; K = c.m_dim; }       // last layer's stream after attention
     else if (n == "tr_ff") { src = s->ff; M = B * 16; K = c.m_ff; }          // last layer's GELU(linear1)
@@ -115,11 +115,9 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
       int mult = 8 >> stage;
       K = mult * c.n_filters / 2;
       M = B * s->rows[stage + 1];
-      const ptts_engine *en = s->e;
-      if (is_res && stage == 2 && en->opt_fuse_pcm && !en->opt_debug_taps && !en->codec_split && en->res_a[2].NT == 2 && s->rows[3] % 64 == 0)
+      if (is_res && stage == 2 && seanet_fuses_pcm(s) && !s->e->opt_debug_taps)
         return fail(-1, "debug_read: " + n + " stays on chip with \"fuse_pcm\"; set the engine option \"debug_taps\" before decoding");
-      const bool single = en->opt_single_store && !en->codec_split && !en->res_a[stage].wq && !en->res_a[stage].wb16;
-      src = is_res ? s->sbuf[stage] + par * s->s_stride[stage] : single ? s->cbuf[stage] + par * s->c_stride[stage] : s->craw[stage];
+      src = is_res ? s->sbuf[stage].slot(par) : seanet_single_store(s->e, stage) ? s->cbuf[stage].slot(par) : s->craw[stage];
     }
     F = K / 16;
   }

@@ -1,7 +1,9 @@
-// The boundary between the three units that share the engine's structures.  Internal (never installed, not part of
+// The boundary between the four units that share the engine's structures.  Internal (never installed, not part of
 // include/ptts.h).
-//   ptts.hip           defines the error plumbing, the profiler, the entry-point frame, allocation and packing sections:
-//                      engine construction, the states, step orchestration, graph capture, the C ABI.
+//   ptts.hip           defines the error plumbing, the profiler, the entry-point frame, allocation and packing sections and
+//                      the transformer layer: engine construction, the FlowLM states and step, graph capture, the C ABI.
+//   ptts_codec.hip     defines the Mimi codec section: the codec state, the frame walks, the output chain behind them, the
+//                      decode entry points, the voice-prompt encoder and the fp8 calibration run.
 //   ptts_dispatch.hip  defines the dispatcher sections (GEMM, tuner table, attention, reduced-precision codec tiles).  It
 //                      alone instantiates gemm_kernel, gemm_lds_kernel, gemm_h_kernel and attn_*: every other unit launches
 //                      them through the functions declared here.
@@ -21,7 +23,7 @@
 
 #include "../../include/ptts.h"
 
-#pragma GCC visibility push(hidden)  // links the three units; libptts.so exports none of it
+#pragma GCC visibility push(hidden)  // links the four units; libptts.so exports none of it
 
 // ---- error plumbing ---------------------------------------------------------------------------------------------------
 int fail(int code, const std::string &msg);  // records the calling thread's ptts_last_error(), returns code
@@ -61,6 +63,7 @@ struct ProfScope {
   ~ProfScope();
 };
 const char *launch_site();  // the call site (SITE in ptts.hip) the calling thread is enqueueing for; "" outside one
+void set_launch_site(const char *site);  // SITE of ptts_codec.hip
 
 // ------------------------------------------------------------------------------------------------
 struct Lin {  // one packed weight matrix
@@ -260,6 +263,17 @@ struct ChainLink {
   int i16 = 0;
 };
 
+// One streaming buffer of the codec: a ring of `slots` frames.  A slot is `stride` floats of allocation and holds `stride`
+// elements of `esz` bytes (4 fp32, 2 bf16, 1 e4m3; build_mimi_state decides): a reduced-precision ring is partly filled
+struct Ring {
+  float *p = nullptr;
+  long stride = 0;
+  int slots = 0, esz = 4;
+  float *slot(int k) const { return p + (size_t)k * stride; }
+  long step() const { return stride * 4 / esz; }          // from one slot to the next, in elements (GemmArgs::Xdstride)
+  size_t bytes() const { return (size_t)stride * esz; }   // what a slot's elements fill
+};
+
 struct ptts_mimi_state {
   ptts_engine *e;
   int B, MTb, MT16;
@@ -271,33 +285,65 @@ struct ptts_mimi_state {
   int *trl() const { return frame + 2; }
   int h_frame = 0;  // frames through SEANet, host copy
   int h_tr = 0;     // frames through the transformer, host copy (h_tr - h_frame frames wait in tr_out)
-  // tr_out: the transformer's hand-over to SEANet's first conv, a ring of tr_slots frames of tr_stride floats (fp32 codec:
-  // 4, frame f in slot f & 3, so that a frame pair fits beside the frame before it; reduced-precision codecs: the two
-  // parity halves).  splits2: key splits of a frame pair's attention (32 queries per sequence)
-  int tr_slots = 2, splits2 = 1;
+  int splits, splits2 = 1;  // key splits of a frame's attention, and of a frame pair's (32 queries per sequence)
   float *kv = nullptr;  // [ML][2][B][H][ring][64]
-  float *zl, *zq, *u0, *u, *h, *ao, *ff, *q, *part, *tr_out, *rope;
-  long zq_stride, tr_stride;
-  int splits;
-  float *a0;
-  long a0_stride;
-  float *cbuf[3], *craw[3], *rbuf[3], *sbuf[3];  // cbuf/sbuf/rbuf hold ELU'd values, craw the raw skip input
-  long c_stride[3], s_stride[3];
+  float *zl, *u0, *u, *h, *ao, *ff, *q, *part, *rope;
+  // The rings.  tr_out: the transformer's hand-over to SEANet's first conv (fp32 codec: 4 slots, frame f in slot f & 3, so
+  // that a frame pair fits beside the frame before it; reduced-precision codecs: the two parity halves).  The others have
+  // two slots, the frame parities: zq, SEANet's conv inputs a0 / cbuf / sbuf (ELU'd values), and the fused last stage's
+  // ("fuse_pcm") pcm_carry, what each 64-row tile leaves for the first two rows of the next
+  Ring zq, tr_out, a0, cbuf[3], sbuf[3], pcm_carry;
+  std::array<Ring *, 10> rings() { return {&zq, &tr_out, &a0, &cbuf[0], &sbuf[0], &cbuf[1], &sbuf[1], &cbuf[2], &sbuf[2], &pcm_carry}; }
+  float *craw[3], *rbuf[3];  // the raw skip input of a residual block, its hidden activation
   int rows[4];  // rows per sequence at each SEANet stage
   float *pcm_dbg;
   int16_t *pcm_i16 = nullptr;
+  float *pcm_part = nullptr;  // fused last stage: per-row partial PCM
   // the output stages behind the codec (ptts_mimi_set_*), one link per kind in launch order.  A link is empty (stage == nullptr)
   // or holds the stage, the f32 device buffer it reads (`in`; nullptr: the frame's PCM) and what it writes (`out`, int16 with
-  // `i16`, else f32; the encoder's bytes; the packer reads the encoder's bytes through `in` and writes ring lines).  mimi_frame_enqueue in ptts.hip states the two cases in which a stage writes
-  // another link's `in` instead
+  // `i16`, else f32; the encoder's bytes; the packer reads the encoder's bytes through `in` and writes ring lines).
+  // mimi_frame_enqueue in ptts_codec.hip states the two cases in which a stage writes another link's `in` instead
   ChainLink chain[CH_N];
-  // fused last stage ("fuse_pcm"): per-row partial PCM + what each 64-row tile leaves for the first two rows of the next
-  float *pcm_part = nullptr, *pcm_carry = nullptr;
-  long pcm_cstride = 0;
   size_t kv_plane() const { return (size_t)B * e->cfg.m_heads * e->ring * 64; }
   float *K(int l) { return kv + (size_t)(2 * l) * kv_plane(); }
   float *V(int l) { return kv + (size_t)(2 * l + 1) * kv_plane(); }
 };
+
+// ---- the Mimi codec (ptts_codec.hip) ----------------------------------------------------------------------------------
+// parts of a frame: PART_TR the transformer (one frame, or a pair with a second latent), PART_SEANET one SEANet frame
+// (with the PCM and the int16 copy); both = the whole frame.  The reduced-precision codecs take single frames only.
+enum { PART_TR = 1, PART_SEANET = 2, PART_ALL = 3 };
+int mimi_frame_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, const float *d_latent, float *d_pcm,
+                       int parts = PART_ALL, const float *d_latent2 = nullptr);
+int mimi_parts_check(const ptts_mimi_state *s, int parts, int frames);
+void mimi_parts_done(ptts_mimi_state *s, int parts, int frames);
+int calibrate_fp8_codec(ptts_engine *e);  // build_fp8_codec: fills e->d_f8s from a run of the bf16 codec
+bool seanet_single_store(const ptts_engine *e, int i);  // stage i's transposed conv stores its raw output only
+bool seanet_fuses_pcm(const ptts_mimi_state *s);  // the last conv rides in the last block: sbuf[2] is written with "debug_taps" only
+
+// ---- the transformer layer (ptts.hip; the FlowLM, the codec and the voice encoder run it) -----------------------------
+struct TrCtx {
+  int D, H, FF, MT, M, Tq, QB, cap, ring, ctx, splits;
+  float *x_in;       // residual stream input (FM, F = D/16)
+  float *x;          // residual stream after attention (may equal x_in)
+  float *x_out;      // residual stream output of the layer (dbl-buffered if out_ds != 0)
+  long out_ds;
+  const int *par;
+  int out_ring = 0;  // x_out is the codec's hand-over ring (GemmArgs::yring): frames in the launch, 0: parity halves
+  float *h, *ao, *ff, *q, *part;
+  float *Kc, *Vc;
+  const int *offset;
+  const KvPrefix *pre = nullptr;  // shared voice prefixes of the sequences (FlowLM states) or null
+  int layer = 0;
+  int cascade = 0;                // decode steps: attn_cascade_kernel tile shape (10 R + PW) or 0
+  const int *qlen = nullptr;      // ragged prefill: real rows of each sequence (GemmArgs::qlen, AttnArgs::qlen) or null
+  const float *rope;  // [M][32][2]
+  float *tap_x = nullptr;  // test hook: receives a copy of the stream after attention (x), which x_out may overwrite
+  double kv_keys;  // sum over sequences of the keys attended (profiling only)
+  const char *tag;
+};
+
+void run_tr_layer(hipStream_t st, const TrLayer &T, const TrCtx &c);
 
 // ---- entry-point frame, allocation and packing ------------------------------------------------------------------------
 hipStream_t S(ptts_engine *e, void *stream);

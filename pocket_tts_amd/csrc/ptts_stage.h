@@ -1,13 +1,13 @@
 // What the host sides of the nine output stages share (ptts_resample.hip .. ptts_flac.hip): the head of every ptts_<stage>
 // struct, its device buffers, the refusals and the entry frame of its C ABI, and the drain flag.  The units keep their
-// extern "C" definitions, their plan validation and their kernels; ptts.hip's output chain reads a stage through StageBase.
+// extern "C" definitions, their plan validation and their kernels; ptts_codec.hip's output chain reads a stage through StageBase.
 #pragma once
 #include "ptts_host.h"
 
 #pragma GCC visibility push(hidden)
 
 // Every ptts_<stage> derives from this and from nothing else, without virtual functions: a stage's address is its
-// StageBase's, which is how ptts.hip reads the void * of a ChainLink.
+// StageBase's, which is how ptts_codec.hip reads the void * of a ChainLink.
 struct StageBase {
   ptts_engine *e = nullptr;
   int B = 0, n_plans = 0;

@@ -557,7 +557,7 @@ def test_the_header_holds_the_rule_modules_constants():
 
     names = ["ptts_dynamics_create", "ptts_dynamics_destroy", "ptts_dynamics_set_row", "ptts_dynamics_frame", "ptts_mimi_set_dynamics"]
     public = (REPO / "include" / "ptts.h").read_text()
-    unit = (REPO / "pocket_tts_amd" / "csrc" / "ptts_dyn.hip").read_text() + (REPO / "pocket_tts_amd" / "csrc" / "ptts.hip").read_text()
+    unit = (REPO / "pocket_tts_amd" / "csrc" / "ptts_dyn.hip").read_text() + (REPO / "pocket_tts_amd" / "csrc" / "ptts_codec.hip").read_text()
     for name in names:
         assert name in _lib.PROTOTYPES and f"{name}(" in public and f'extern "C" ' in unit and f" {name}(" in unit, name
 
