@@ -229,6 +229,23 @@ int ptts_lm_state_reserve_row_lsd(ptts_lm_state *s, int32_t K, void *stream);
 int ptts_lm_state_set_row_lsd(ptts_lm_state *s, int32_t row, int32_t n, void *stream);
 /* row `row` returns to the step's lsd_steps; stream-ordered */
 int ptts_lm_state_clear_row_lsd(ptts_lm_state *s, int32_t row, void *stream);
+/* Flow fold (per state, default off): with on != 0 later steps of the state skip the AdaLN modulation GEMM (`flow.adaln`)
+ * and the single-launch flow MLP computes the modulations itself while its workgroups wait for each other (kernel label
+ * `flow_cluster_mod@<threads>` under the site `flow.cluster`).  Taken only where the single-launch flow MLP runs with one
+ * row tile per cluster, flow_dim <= 256 or in 400..512 (1, 2 or 4 k-fragments per worker wave), fp32 flow weights and no per-row LSD capacity; a state
+ * outside of that enqueues exactly the launches it did before.  Results agree with the unfolded step within fp32
+ * rounding (another summation order).  The state's exchange buffers are re-allocated, so:
+ *   -1 for a state with captured graphs when the call would change the switch (set it before capturing). */
+int ptts_lm_state_set_flow_fold(ptts_lm_state *s, int32_t on, void *stream);
+/* Offset, in floats, of fragment `f` (of `nf` per slot) of producer `j`'s exchange slot for (row group, phase, row tile) of
+ * the single-launch flow MLP, with `fdf` producers, `rt` row tiles per group and `nph` phases; (fdf, rt, nph, nf, grp = number
+ * of groups, 0, 0, 0, 0) is the buffer's size.  The function the kernels and the allocation use; no GPU needed. */
+int64_t ptts_flow_slot_offset(int32_t fdf, int32_t rt, int32_t nph, int32_t nf, int32_t grp, int32_t p, int32_t t, int32_t j,
+                              int32_t f);
+/* The folded kernel's schedule: the 16-column tiles of the AdaLN output (blocks' [shift | scale | gate], then the final
+ * layer's [shift | scale], `fdf` tiles each) that workgroup `j` computes at the top of phase `ph` (0 .. 2 depth + 1) of an
+ * LSD step: *n tiles (0 .. 2), the first at the returned tile, the second `fdf` tiles later.  No GPU needed. */
+int32_t ptts_flow_mod_tiles(int32_t fdf, int32_t depth, int32_t ph, int32_t j, int32_t *n);
 /* device pointer of the state's own copy of the latest latent f32[B, ldim] */
 const float *ptts_lm_latent_ptr(ptts_lm_state *s);
 
@@ -655,7 +672,9 @@ int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
  * their own beside the production host side (csrc/ptts.hip). */
 /* Test hook: copies an internal activation buffer, converted to row-major f32[rows, cols], to
  * d_out (capacity in floats).  Names: see DESIGN.md; FlowLM name "noise" = the last step's LSD start point (the noise)
- * f32[B, ldim] (only kept when that step ran the single-launch flow MLP, "flow_cluster"; -1 otherwise).
+ * f32[B, ldim] (only kept when that step ran the single-launch flow MLP, "flow_cluster"; -1 otherwise); FlowLM name "mod" =
+ * the AdaLN modulations of the last step's first LSD iteration, f32[B, (3 flow_depth + 2) flow_dim] (-1 after a step that
+ * ran with the flow fold, ptts_lm_state_set_flow_fold: it computes them on chip and the buffer would be stale).
  * Returns rows*cols or <0. */
 int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi, const char *name, float *d_out,
                         int64_t capacity, int32_t *rows, int32_t *cols, void *stream);

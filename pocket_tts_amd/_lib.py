@@ -102,6 +102,9 @@ PROTOTYPES = {
     "ptts_lm_state_reserve_row_lsd": (C.c_int, [_P, C.c_int32, _P]),
     "ptts_lm_state_set_row_lsd": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ptts_lm_state_clear_row_lsd": (C.c_int, [_P, C.c_int32, _P]),
+    "ptts_lm_state_set_flow_fold": (C.c_int, [_P, C.c_int32, _P]),
+    "ptts_flow_slot_offset": (C.c_int64, [C.c_int32] * 9),
+    "ptts_flow_mod_tiles": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ptts_profile_start": (C.c_int, [_P]),
     "ptts_profile_stop": (C.c_int64, [_P, C.c_char_p, C.c_int64]),
     "ptts_mimi_state_create": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),

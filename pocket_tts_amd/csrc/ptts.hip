@@ -1211,6 +1211,33 @@ extern "C" int ptts_lm_state_reserve_row_lsd(ptts_lm_state *s, int32_t K, void *
   return 0;
 }
 
+// Per-state switch of the folded flow cluster (flow_cluster_mod_kernel): the exchange slots grow to FLOW_MOD_FRAGS
+// fragments, so the buffers are re-allocated here and the switch cannot change under captured graphs
+extern "C" int ptts_lm_state_set_flow_fold(ptts_lm_state *s, int32_t on, void *stream) {
+  if (!s) return fail(-1, "set_flow_fold: null state");
+  ptts_engine *e = s->e;
+  ENGINE_LOCK(e);
+  HIPCHK(hipSetDevice(e->device));
+  if ((on != 0) == s->flow_fold) return 0;
+  if (s->n_graphs > 0) return fail(-1, "set_flow_fold: the state has captured graphs (they hold its flow buffers): set it before capturing");
+  const int steps = s->flow_steps;
+  s->flow_fold = on != 0;
+  s->flow_steps = 0;  // ensure_flow re-allocates the exchange at the new slot size
+  return ensure_flow(e, s, std::max(1, steps), S(e, stream));
+}
+
+extern "C" int64_t ptts_flow_slot_offset(int32_t fdf, int32_t rt, int32_t nph, int32_t nf, int32_t grp, int32_t p, int32_t t,
+                                         int32_t j, int32_t f) {
+  return (int64_t)flow_slot(fdf, rt, nph, nf, grp, p, t, j, f);
+}
+
+extern "C" int32_t ptts_flow_mod_tiles(int32_t fdf, int32_t depth, int32_t ph, int32_t j, int32_t *n) {
+  int nn = 0;
+  const int t0 = flow_mod_tiles(fdf, depth, ph, j, &nn);
+  if (n) *n = nn;
+  return t0;
+}
+
 extern "C" int ptts_lm_state_set_row_lsd(ptts_lm_state *s, int32_t row, int32_t n, void *stream) {
   if (!s || row < 0 || row >= s->B) return fail(-1, "set_row_lsd: row out of range");
   if (s->lsd_cap < 1) return fail(-1, "set_row_lsd: the state has no per-row LSD capacity (ptts_lm_state_reserve_row_lsd)");
@@ -1285,6 +1312,14 @@ static bool flow_cluster_ok(const ptts_engine *e, const ptts_lm_state *s) {
   // CU: the grid is capped at opt_flow_max_cus workgroups (default 128: half the chip, so a codec kernel always has CUs left) (larger batches loop over row groups inside the kernel)
   return FDF <= std::min(e->opt_flow_max_cus, e->n_cus);
 }
+// the state's steps run flow_cluster_mod_kernel: its switch is on, one schedule for all rows, one row tile per cluster
+// and a plain fp32 AdaLN matrix in the tile order the kernel assumes.  Anything else takes the flow.adaln launch.
+static bool flow_fold_ok(const ptts_engine *e, const ptts_lm_state *s) {
+  const int FDF = e->cfg.flow_dim / 16;
+  const Lin &m = e->adaln;
+  return s->flow_fold && flow_cluster_ok(e, s) && s->lsd_cap == 0 && s->flow_rt == 1 && m.w && m.bias && !m.wq && !m.wb16 &&
+         m.KF == FDF && m.NT == (3 * e->cfg.flow_depth + 2) * FDF;
+}
 // (re)allocates the per-state buffers whose size depends on the number of LSD steps; never called during capture
 static int ensure_flow(ptts_engine *e, ptts_lm_state *s, int steps, hipStream_t st) {
   if (steps <= s->flow_steps) return 0;
@@ -1306,7 +1341,7 @@ static int ensure_flow(ptts_engine *e, ptts_lm_state *s, int steps, hipStream_t 
   const size_t rt = (size_t)s->MT * 256;
   const int nph = steps * (2 * c.flow_depth + 2);
   CHK(dallocT(nullptr, &s->mod, (size_t)steps * rt * e->adaln.NT));
-  CHK(dallocT(nullptr, &s->fexch, (size_t)s->flow_ng * nph * s->flow_rt * FDF * 256));
+  CHK(dallocT(nullptr, &s->fexch, flow_slot(FDF, s->flow_rt, nph, s->flow_fold ? FLOW_MOD_FRAGS : 1, s->flow_ng, 0, 0, 0, 0)));
   CHK(dallocT(nullptr, &s->fflags, (size_t)s->flow_ng * nph * FDF));
   HIPCHK(hipStreamSynchronize(st));
   s->flow_steps = steps;
@@ -1328,7 +1363,10 @@ static int flow_steps_of(const ptts_lm_state *s, int lsd_steps) { return std::ma
 
 // with per-row schedules (s->lsd_cap > 0) `lsd_steps` is the count of rows without an override and the slots are laid out
 // for flow_steps_of(s, lsd_steps) steps
-static void launch_flow_cluster(hipStream_t st, ptts_engine *e, ptts_lm_state *s, int lsd_steps, float *d_latent_out) {
+// `fold` (flow_fold_ok): flow_cluster_mod_kernel, which reads `ce` and the AdaLN matrix instead of `mod`; ce_silu: `ce`
+// already holds silu(ce + tcomb[0])
+static void launch_flow_cluster(hipStream_t st, ptts_engine *e, ptts_lm_state *s, int lsd_steps, float *d_latent_out,
+                                bool fold = false, const float *tcomb = nullptr, bool ce_silu = false) {
   const ptts_config &c = e->cfg;
   const int FDF = c.flow_dim / 16, LF = c.ldim / 16;
   FlowArgs fa;
@@ -1349,13 +1387,24 @@ static void launch_flow_cluster(hipStream_t st, ptts_engine *e, ptts_lm_state *s
   fa.inv_steps = 1.0f / (float)lsd_steps;
   fa.exch = s->fexch; fa.flags = s->fflags; fa.ctr = s->rng_ctr; fa.err = s->ferr;
   fa.row_n = rowlsd ? s->lsd_n : nullptr; fa.row_ndef = lsd_steps;
+  if (fold) { fa.mod = nullptr; fa.ce = s->ce; fa.w_mod = e->adaln.w; fa.b_mod = e->adaln.bias; fa.tcomb = tcomb; fa.ce_silu = ce_silu; }
   // weights of the chain once per cluster-set (L2 / Infinity Cache absorb the clusters' re-reads) + modulations + io
-  const double wbytes = 4.0 * 256 * ((double)FDF * LF + 2.0 * c.flow_depth * FDF * FDF + (double)LF * FDF);
-  const double flops = 2.0 * s->B * 256.0 * ((double)FDF * LF + 2.0 * c.flow_depth * FDF * FDF + (double)LF * FDF) * lsd_steps;
-  ProfScope ps(st, std::string(rowlsd ? "flow_cluster_rowlsd@" : "flow_cluster@") + std::to_string((long)fa.NCL * FDF * FLOW_THREADS),
-               lsd_steps * (wbytes + 4.0 * s->B * 16.0 * e->adaln.NT), flops);
+  // folded: + the AdaLN matrix, and `ce` in place of the modulations
+  const double wbytes = 4.0 * 256 * ((double)FDF * LF + 2.0 * c.flow_depth * FDF * FDF + (double)LF * FDF + (fold ? (double)e->adaln.NT * FDF : 0.0));
+  const double flops = 2.0 * s->B * 256.0 * ((double)FDF * LF + 2.0 * c.flow_depth * FDF * FDF + (double)LF * FDF + (fold ? (double)e->adaln.NT * FDF : 0.0)) * lsd_steps;
+  ProfScope ps(st, std::string(fold ? "flow_cluster_mod@" : rowlsd ? "flow_cluster_rowlsd@" : "flow_cluster@") + std::to_string((long)fa.NCL * FDF * FLOW_THREADS),
+               lsd_steps * (wbytes + 4.0 * s->B * 16.0 * (fold ? FDF : e->adaln.NT)), flops);
   const int kpw = cdiv(std::max(FDF, LF), FLOW_WORKERS);
   s->coop_wgs = std::max(s->coop_wgs, fa.NCL * FDF);
+  if (fold) {
+    const dim3 grid(fa.NCL * fa.FDF), block(FLOW_THREADS);
+    switch (kpw) {
+      case 1: flow_cluster_mod_kernel<1><<<grid, block, 0, st>>>(fa); break;
+      case 2: flow_cluster_mod_kernel<2><<<grid, block, 0, st>>>(fa); break;
+      default: flow_cluster_mod_kernel<4><<<grid, block, 0, st>>>(fa); break;
+    }
+    return;
+  }
   if (rowlsd) {
     if (s->flow_rt == 2) launch_flow_rt<2, true>(st, fa, kpw);
     else launch_flow_rt<1, true>(st, fa, kpw);
@@ -1628,7 +1677,14 @@ static int lm_step_enqueue(hipStream_t st, ptts_engine *e, ptts_lm_state *s, con
   auto row_lsd = [&](GemmArgs &g, int i) {  // per-row schedules of step i (GemmArgs::row_n)
     g.row_n = s->lsd_n; g.row_tab = s->lsd_tab; g.row_ndef = lsd_steps; g.row_i = i;
   };
-  if (flow_cluster_ok(e, s) && nit <= s->flow_steps) {
+  s->mod_stale = false;
+  if (flow_fold_ok(e, s) && nit <= s->flow_steps) {
+    // the modulations are computed inside the cluster's hand-off waits: no flow.adaln launch, `mod` is not written
+    SITE("flow.cluster");
+    launch_flow_cluster(st, e, s, lsd_steps, d_latent_out, true, tcomb, silu_in_head);
+    s->latfm_noise = true;
+    s->mod_stale = true;
+  } else if (flow_cluster_ok(e, s) && nit <= s->flow_steps) {
     // the AdaLN modulations of every LSD step (they depend on the step's (s, t) only through t_emb), then the whole
     // chain + Euler loop in ONE launch
     if (rowlsd) {  // every step in one launch (grid.z), each row with its own schedule

@@ -78,6 +78,11 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
     if (n == "x") { src = s->dec.x; M = s->B; K = c.d_model; }
     else if (n == "ce") { src = s->ce; M = s->B; K = c.flow_dim; }
     else if (n == "fx") { src = s->fx; M = s->B; K = c.flow_dim; }
+    else if (n == "mod") {  // AdaLN modulations of the last step's first LSD iteration, [B][(3 depth + 2) flow_dim]
+      if (s->mod_stale) return fail(-1, "debug_read: mod is not materialised by a step with the flow fold (ptts_lm_state_set_flow_fold): the cluster computes it on chip");
+      if (!s->mod) return fail(-1, "debug_read: mod is not allocated");
+      src = s->mod; M = s->B; K = e->adaln.NT * 16;
+    }
     else if (n == "prefill_x") { src = s->pre.x; M = s->pre.MT * 16; K = c.d_model; }
     else if (n == "noise") {  // the last step's LSD start point (noise), [B][ldim]
       if (!s->latfm_noise) return fail(-1, "debug_read: noise is only kept by steps that ran the flow cluster");

@@ -50,7 +50,33 @@ struct FlowArgs {
   // per-row LSD schedules (flow_cluster_kernel<.., true>): row m runs row_lsd_n(row_n, row_ndef, m) <= steps Euler steps
   const int *row_n;
   int row_ndef;
+  // flow_cluster_mod_kernel only: the modulations are computed inside the launch from the conditioning `ce` (FM [MT][FDF])
+  const float *ce, *w_mod, *b_mod;  // AdaLN linear, packed [AF][FDF][64][4], and its bias
+  const float *tcomb;               // time embeddings of the LSD steps [steps][flow_dim], added before the SiLU
+  int ce_silu;                      // 1: `ce` already holds silu(ce + tcomb[0]) (the head's epilogue, lsd_steps 1)
 };
+
+// Exchange layout, in floats from the start of the buffer: every (row group, phase, row tile, producer) owns one slot of
+// `nf` fragments of 256 floats.  nf = 1: the layer output (flow_cluster_kernel); nf = FLOW_MOD_FRAGS: layer output, then
+// the AdaLN shift and scale fragments the next phase's LayerNorm consumes (flow_cluster_mod_kernel).
+#define FLOW_MOD_FRAGS 3
+__host__ __device__ inline size_t flow_slot(int FDF, int RT, int NPH, int nf, int grp, int p, int t, int j, int f) {
+  return ((((((size_t)grp * NPH + p) * RT + t) * FDF + j) * nf) + f) * 256;
+}
+
+// flow_cluster_mod_kernel: the modulation column tiles workgroup j computes at the top of phase ph (0 .. 2 depth + 1) of an
+// LSD step: *n of them (0 .. 2), the first at the returned tile of the AdaLN output, the second FDF tiles later.  The
+// AdaLN output is [block 0: shift | scale | gate] .. [block depth - 1: ..] [final layer: shift | scale], FDF tiles each.
+//   phase 0 (input_proj): shift, scale of block 0;  linear 0 of block r: gate of block r;
+//   linear 2 of block r: shift, scale of block r + 1, or of the final layer;  final layer: none
+__host__ __device__ inline int flow_mod_tiles(int FDF, int depth, int ph, int j, int *n) {
+  const int r = (ph - 1) >> 1;
+  if (ph == 0) { *n = 2; return j; }
+  if (ph == 2 * depth + 1) { *n = 0; return 0; }
+  if ((ph - 1) & 1) { *n = 2; return (r + 1) * 3 * FDF + j; }
+  *n = 1;
+  return r * 3 * FDF + 2 * FDF + j;
+}
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t flow_rsrc(const void *p) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0x7ffffff0, 0x00020000);
@@ -60,6 +86,19 @@ __device__ __forceinline__ f32x4 flow_ld_sc1(__amdgpu_buffer_rsrc_t r, unsigned 
 }
 __device__ __forceinline__ void flow_st_sc1(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)byte_off, 0, 16);
+}
+
+// 16 bytes per lane at a wave-uniform address + the lane's byte offset, as buffer loads / stores: the address takes no vector
+// registers, and nothing per-lane is left for the compiler to hoist out of the phase loop (flow_cluster_mod_kernel: with
+// plain pointers it kept some forty 64-bit addresses alive around the loop and spilled them)
+__device__ __forceinline__ f32x4 flow_ldu(const void *base, unsigned voff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(flow_rsrc(base), (int)voff, 0, 0));
+}
+__device__ __forceinline__ f32x4 flow_ldu_sc1(__amdgpu_buffer_rsrc_t r, unsigned soff, unsigned voff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 16));
+}
+__device__ __forceinline__ void flow_stu_sc1(__amdgpu_buffer_rsrc_t r, unsigned soff, unsigned voff, f32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, 16);
 }
 
 // one wave polls the flags of `np` producers (np <= 64) until all carry `epoch`; bounded
@@ -327,5 +366,279 @@ __global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_kernel(FlowArgs a) 
 #pragma unroll
     for (int t = 0; t < RT; ++t) e_gate[t] = n_gate[t];
   }
+  }  // row groups
+}
+
+// The same chain with the AdaLN modulation GEMM (mod = Linear(silu(ce + t_emb)), reference mlp.py:107,127,210) folded
+// into the hand-off waits: no `mod` buffer, no launch in front of the cluster.  Same geometry, flags, epochs, spin limit
+// and error word as flow_cluster_kernel<1, KPW>; one row tile per cluster, one schedule for all rows.
+//
+// Workgroup j owns column tile j of each of the 3 depth + 2 modulation vectors (tile r 3 FDF + j = shift of block r,
+// + FDF = scale, + 2 FDF = gate; depth 3 FDF + j and + FDF = the final layer's shift and scale).  A tile is a K = flow_dim
+// product like a layer's, split over the workers the same way; its operand silu(ce + t_emb) stays on chip (LDS).  Workers
+// compute, at the top of phase p and before the barrier behind the coordinator's poll (i.e. while they would wait):
+//   kind 0 (input_proj): shift and scale of block 0          -> published with slot p, read by phase p + 1
+//   kind 1 (linear 0 of block r): gate of block r            -> stays in the coordinator's registers for phase p + 1
+//   kind 2 (linear 2 of block r): shift and scale of the next LayerNorm (block r + 1 or the final layer) -> slot p
+// Their weight fragments are requested with load_w of the phase before.  The coordinator sums the partials in fixed
+// order, adds the bias and issues the write-through stores of shift and scale BEFORE it waits for the layer partials;
+// the one flag per (phase, producer) is raised behind `s_waitcnt vmcnt(0)` over all three fragments of the slot.
+template <int KPW>
+__global__ __launch_bounds__(FLOW_THREADS) void flow_cluster_mod_kernel(FlowArgs a) {
+  // the wave index as a scalar: the coordinator / worker branches are then uniform branches, and the registers of one
+  // role are not kept alive through the code of the other
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int FDF = a.FDF, LF = a.LF;
+  const int cl = blockIdx.x / a.FDF, j = blockIdx.x % a.FDF;  // resident cluster, column tile (see flow_cluster_kernel)
+  const bool coord = wave == FLOW_WORKERS;
+  const int PPS = 2 * a.depth + 2, NPH = a.steps * PPS;
+  __shared__ f32x4 red[FLOW_WORKERS][64];
+  __shared__ f32x4 mred[FLOW_WORKERS][2][64];  // partial sums of the phase's modulation tiles
+  // the modulation operand silu(ce + t_emb) of the row group, each worker's own k-fragments: written and read by that
+  // wave only; in LDS, not in registers: the LayerNorm part of a KPW = 4 phase has none to spare
+  __shared__ f32x4 cxs[FLOW_WORKERS][KPW][64];
+  __shared__ float st[FLOW_WORKERS][16][2];
+  const u64 ebase = ((u64)(unsigned)(*a.ctr) + 1ull) << 16;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  bool dead = false;
+  // byte offset of fragment f of producer q's slot of phase p inside the row group's part of the exchange (a scalar)
+  auto slot = [&](int p, int q, int f) { return (unsigned)flow_slot(FDF, 1, NPH, FLOW_MOD_FRAGS, 0, p, 0, q, f) * 4u; };
+  const unsigned l16 = (unsigned)lane * 16u, q16 = (unsigned)(lane >> 4) * 16u;  // a lane's bytes in a fragment / in 16 columns
+  for (int grp = cl; grp < a.NG; grp += a.NCL) {
+  float *ex = a.exch + flow_slot(FDF, 1, NPH, FLOW_MOD_FRAGS, grp, 0, 0, 0, 0);
+  u64 *fl = a.flags + (size_t)grp * NPH * FDF;
+  const __amdgpu_buffer_rsrc_t rs = flow_rsrc(ex);
+  __syncthreads();  // LDS of the previous group is free
+  const int mtc = min(grp, a.MT - 1);
+  const int nph = NPH;
+
+  auto kind_of = [&](int ph) { return ph == 0 ? 0 : ph == PPS - 1 ? 3 : 1 + ((ph - 1) & 1); };
+  auto wtile = [&](int ph, int &KF, bool &use) -> const float * {
+    const int k = kind_of(ph), r = (ph - 1) >> 1;
+    use = true;
+    if (k == 0) { KF = LF; return a.w_in + (size_t)j * LF * 256; }
+    KF = FDF;
+    if (k == 1) return a.w_l0[r] + (size_t)j * FDF * 256;
+    if (k == 2) return a.w_l2[r] + (size_t)j * FDF * 256;
+    use = j < LF;
+    return a.w_fin + (size_t)(use ? j : 0) * FDF * 256;
+  };
+  auto bias_of = [&](int ph) -> const float * {
+    const int k = kind_of(ph), r = (ph - 1) >> 1;
+    return (k == 0 ? a.b_in : k == 1 ? a.b_l0[r] : k == 2 ? a.b_l2[r] : a.b_fin) + (k == 3 && j >= LF ? 0 : 16 * j);
+  };
+  // modulation tiles of phase ph: n of them, the first at the returned column tile, the second FDF tiles later
+  auto mtiles = [&](int ph, int &n) { return flow_mod_tiles(FDF, a.depth, ph, j, &n); };
+
+  // ---- worker state: weight fragments of the current phase and of its modulation tiles
+  f32x4 w[KPW], mw[2][KPW];
+  auto load_w = [&](int ph) {
+    int n;
+    const int t0 = mtiles(ph, n);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int u = 0; u < KPW; ++u) mw[s][u] = zero4;  // (assigned on every path: nothing is carried from phase to phase)
+      if (s < n) {  // the same in every lane
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const int kf = wave * KPW + u;
+          const f32x4 v = flow_ldu(a.w_mod + ((size_t)(t0 + s * FDF) * FDF + min(kf, FDF - 1)) * 256, l16);
+          if (kf < FDF) mw[s][u] = v;
+        }
+      }
+    }
+    int KF;
+    bool use;
+    const float *Wt = wtile(ph, KF, use);
+#pragma unroll
+    for (int u = 0; u < KPW; ++u) {
+      const int kf = wave * KPW + u;
+      const f32x4 v = flow_ldu(Wt + (size_t)min(kf, KF - 1) * 256, l16);
+      w[u] = (use && kf < KF) ? v : zero4;
+    }
+  };
+  // The two roles run their own copy of the phase loop, each with the phase's barriers A, (B,) C in it: the branch is
+  // uniform per wave and all nine waves meet every barrier, but no register of one role is live in the other's code.
+  if (coord) {
+    // ---- coordinator state: residual stream tile, latent tile, the gate of the next epilogue (the biases are requested
+    // in front of the poll, phase by phase)
+    f32x4 xres = zero4, latv = zero4, e_gate = zero4;
+    if (j < LF) latv = flow_ldu(a.latfm + ((size_t)mtc * LF + j) * 256, l16);
+    for (int p = 0; p < nph; ++p) {
+      const int i = p / PPS, ph = p - i * PPS;
+      const int kind = kind_of(ph);
+      const bool lnmod = kind == 1 || kind == 3;
+      int nmt;
+      const int t0 = mtiles(ph, nmt);
+      // ---- A: the inputs of phase p are published (slot p - 1)
+      const f32x4 e_bias = flow_ldu(bias_of(ph), q16);
+      f32x4 mbias[2] = {zero4, zero4};  // biases of the phase's modulation tiles
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        if (s < nmt) mbias[s] = flow_ldu(a.b_mod + 16 * (t0 + s * FDF), q16);
+      if (p > 0 && !dead) {
+        const int np = ph == 0 ? LF : FDF;
+        if (!flow_wait(fl + (size_t)(p - 1) * FDF, np, ebase | (u64)p, lane, a.err)) dead = true;
+      }
+      __syncthreads();
+      // the phase's modulation tiles: fixed-order sum + bias; shift and scale leave before the layer partials are waited for
+      if (nmt > 0) {
+        auto msum = [&](int s) {
+          f32x4 m = mred[0][s][lane];
+#pragma unroll
+          for (int q = 1; q < FLOW_WORKERS; ++q) m += mred[q][s][lane];
+          return m + mbias[s];
+        };
+        const f32x4 m0 = msum(0);
+        if (nmt == 2) {
+          flow_stu_sc1(rs, slot(p, j, 1), l16, m0);
+          flow_stu_sc1(rs, slot(p, j, 2), l16, msum(1));
+        } else {
+          e_gate = m0;  // the gate of this block: the next phase's epilogue (this phase's has none)
+        }
+      }
+      if (lnmod) __syncthreads();  // B
+      __syncthreads();             // C: partial accumulators are in LDS
+      // ---- reduce (fixed order), epilogue, publish
+      const bool publish = p + 1 < nph && (kind != 3 || j < LF);
+      f32x4 s = red[0][lane];
+#pragma unroll
+      for (int q = 1; q < FLOW_WORKERS; ++q) s += red[q][lane];
+      s += e_bias;
+      f32x4 out;
+      if (kind == 0) { xres = s; out = s; }
+      else if (kind == 1) out = act4(s, ACT_SILU);
+      else if (kind == 2) { xres = xres + e_gate * s; out = xres; }
+      else {
+        latv = latv + s * a.inv_steps;  // Euler update of lsd_decode (reference flow_lm.py:39)
+        out = latv;
+        const int m = 16 * grp + (lane & 15);
+        if (i == a.steps - 1 && j < LF && m < a.M) {
+          const size_t o = (size_t)m * a.ldim + 16 * j + 4 * (lane >> 4);
+          *(f32x4 *)(a.lat + o) = out;
+          if (a.lat_out1) *(f32x4 *)(a.lat_out1 + o) = out;
+          if (a.lat_out2) *(f32x4 *)(a.lat_out2 + o) = out;
+        }
+      }
+      if (publish) {
+        flow_stu_sc1(rs, slot(p, j, 0), l16, out);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // all three fragments of the slot have left the CU
+        if (lane == 0) __hip_atomic_store(fl + (size_t)p * FDF + j, ebase | (u64)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  } else {
+    load_w(0);
+    for (int p = 0; p < nph; ++p) {
+      const int i = p / PPS, ph = p - i * PPS;
+      const int kind = kind_of(ph);
+      const int KF = kind == 0 ? LF : FDF;
+      const bool lnmod = kind == 1 || kind == 3;
+      int nmt;
+      mtiles(ph, nmt);
+      // ---- in front of A: the wait for the phase's inputs is filled with the modulation tiles
+      if (ph == 0) {  // the operand of this LSD step's modulations: silu(ce + t_emb_i), this wave's k-fragments
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const int kf = wave * KPW + u, kc = min(kf, FDF - 1);
+          f32x4 v = flow_ldu(a.ce + ((size_t)mtc * FDF + kc) * 256, l16);
+          if (!a.ce_silu) {
+            const f32x4 t = flow_ldu(a.tcomb + (size_t)i * FDF * 16 + 16 * kc, q16);
+            v.x = silu_f(v.x + t.x); v.y = silu_f(v.y + t.y); v.z = silu_f(v.z + t.z); v.w = silu_f(v.w + t.w);
+          }
+          cxs[wave][u][lane] = kf < FDF ? v : zero4;
+        }
+      }
+      if (nmt > 0) {
+        f32x4 m0 = zero4, m1 = zero4, cx[KPW];
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) cx[u] = cxs[wave][u][lane];
+#pragma unroll
+        for (int u = 0; u < KPW; ++u)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) m0 = __builtin_amdgcn_mfma_f32_16x16x4f32(mw[0][u][c], cx[u][c], m0, 0, 0, 0);
+        mred[wave][0][lane] = m0;
+        if (nmt == 2) {
+#pragma unroll
+          for (int u = 0; u < KPW; ++u)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) m1 = __builtin_amdgcn_mfma_f32_16x16x4f32(mw[1][u][c], cx[u][c], m1, 0, 0, 0);
+          mred[wave][1][lane] = m1;
+        }
+      }
+      __syncthreads();  // A
+      f32x4 x[KPW], ma[KPW], mb[KPW];  // operand fragments; modulation as x' = LN0(x) * ma + mb
+      const int r = (ph - 1) >> 1;
+      if (p == 0) {
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const int kf = wave * KPW + u;
+          const f32x4 v = flow_ldu(a.latfm + ((size_t)mtc * LF + min(kf, KF - 1)) * 256, l16);
+          x[u] = kf < KF ? v : zero4;
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const int kf = wave * KPW + u;
+          const f32x4 v = flow_ldu_sc1(rs, slot(p - 1, min(kf, KF - 1), 0), l16);
+          x[u] = kf < KF ? v : zero4;
+        }
+      }
+      if (lnmod) {
+        // AdaLN-modulated LayerNorm on load (reference mlp.py:107-109, 127-129): statistics over the whole row; shift
+        // and scale fragment kf come from producer kf's slot, behind the same poll as the operand
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const int kf = min(wave * KPW + u, KF - 1);
+          f32x4 lw = {1.f, 1.f, 1.f, 1.f}, lb = zero4;
+          if (kind == 1) {
+            lw = flow_ldu(a.ln_w[r] + 16 * kf, q16);
+            lb = flow_ldu(a.ln_b[r] + 16 * kf, q16);
+          }
+          const f32x4 shv = flow_ldu_sc1(rs, slot(p - 1, kf, 1), l16), scv = 1.0f + flow_ldu_sc1(rs, slot(p - 1, kf, 2), l16);
+          // (n * w + b) * (1 + scale) + shift  ==  n * [w (1 + scale)] + [b (1 + scale) + shift]
+          ma[u] = lw * scv;
+          mb[u] = lb * scv + shv;
+        }
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const f32x4 v = x[u];
+          s1 += (v.x + v.y) + (v.z + v.w);
+          s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        }
+        s1 += __shfl_xor(s1, 16); s1 += __shfl_xor(s1, 32);
+        s2 += __shfl_xor(s2, 16); s2 += __shfl_xor(s2, 32);
+        if (lane < 16) { st[wave][lane][0] = s1; st[wave][lane][1] = s2; }
+      }
+      if (lnmod) __syncthreads();  // B: row statistics of all workers are in LDS
+      if (lnmod) {
+        const float invK = 1.0f / (float)(KF * 16);
+        float t0 = 0.f, t1 = 0.f;
+#pragma unroll
+        for (int q = 0; q < FLOW_WORKERS; ++q) { t0 += st[q][lane & 15][0]; t1 += st[q][lane & 15][1]; }
+        const float mu = t0 * invK;
+        const float rsd = 1.0f / sqrtf(fmaxf(t1 * invK - mu * mu, 0.f) + 1e-6f);  // flow-MLP LayerNorm eps (mlp.py:95)
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) {
+          const f32x4 v = ((x[u] - mu) * rsd) * ma[u] + mb[u];
+          x[u] = (wave * KPW + u) < KF ? v : zero4;
+        }
+      }
+      f32x4 acc = zero4;
+#pragma unroll
+      for (int u = 0; u < KPW; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[u][c], x[u][c], acc, 0, 0, 0);
+      red[wave][lane] = acc;
+      __syncthreads();  // C: partial accumulators are in LDS
+      if (p + 1 < nph) {
+        load_w((p + 1) % PPS);  // in flight while the hand-off completes
+      } else {  // (assigned on every path: no fragment is carried around the loop, which would pin 48 registers)
+#pragma unroll
+        for (int u = 0; u < KPW; ++u) w[u] = mw[0][u] = mw[1][u] = zero4;
+      }
+    }  // phases
+  }  // worker
   }  // row groups
 }

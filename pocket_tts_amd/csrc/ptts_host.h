@@ -208,6 +208,10 @@ struct ptts_lm_state {
   unsigned long long *fflags = nullptr;
   int *ferr = nullptr;
   int flow_steps = 0, flow_rt = 1, flow_ng = 1;
+  // ptts_lm_state_set_flow_fold: steps of this state compute the AdaLN modulations inside the cluster launch
+  // (flow_cluster_mod_kernel) where flow_fold_ok() holds; the exchange slots are then FLOW_MOD_FRAGS fragments wide
+  bool flow_fold = false;
+  bool mod_stale = false;  // the last enqueued step was folded: `mod` was not written
   // per-row LSD schedules (ptts_lm_state_reserve_row_lsd): capacity K (0: none), packed time-embedding table of
   // schedules 1..K, each row's own step count (0: the step's lsd_steps)
   int lsd_cap = 0;

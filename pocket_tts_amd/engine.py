@@ -150,6 +150,11 @@ class LMState:
         """row `row` returns to the step's lsd_steps"""
         _lib.check(self.engine.lib.ptts_lm_state_clear_row_lsd(self.handle, row, self.engine._sp))
 
+    def set_flow_fold(self, on: bool):
+        """Flow fold (include/ptts.h): the flow cluster computes the AdaLN modulations inside its hand-off waits and the
+        `flow.adaln` launch goes, where the state qualifies; before any graph of this state is captured"""
+        _lib.check(self.engine.lib.ptts_lm_state_set_flow_fold(self.handle, int(bool(on)), self.engine._sp))
+
     def error(self) -> bool:
         """True after a cooperative kernel of this state gave up waiting for a peer workgroup"""
         r = self.engine.lib.ptts_lm_state_error(self.handle, self.engine._sp)
@@ -1517,7 +1522,8 @@ class StepPipeline:
 
     def __init__(self, eng: Engine, lm_state: LMState, mimi_state: MimiState, noise=None, lsd_steps: int = 1,
                  eos_threshold: float = -4.0, mode: str | None = None, pcm_i16: bool = False,
-                 lm_stream: torch.cuda.Stream | None = None, spec=None, codec_pair: bool | None = None, **chain):
+                 lm_stream: torch.cuda.Stream | None = None, spec=None, codec_pair: bool | None = None, flow_fold: bool | None = None,
+                 **chain):
         from .output_chain import ChainSpec, OutputChain
 
         self.eng, self.st, self.ms = eng, lm_state, mimi_state
@@ -1530,6 +1536,13 @@ class StepPipeline:
             codec_pair = os.environ.get("PTTS_CODEC_PAIR", "1") != "0" and B > 8
         self.codec_pair = bool(codec_pair) and self.mode == "events" and not (
             {"codec_bf16", "codec_fp8"} & set(eng.quantize_groups))
+        # AdaLN modulations inside the flow cluster's hand-off waits (LMState.set_flow_fold): None = PTTS_FLOW_FOLD (default
+        # 1) for throughput batches with an fp32 FlowLM; set on the state before its graphs are captured.  The library
+        # still takes today's launches where the state does not qualify (per-row LSD capacity, flow_dim, weight format).
+        if flow_fold is None:
+            flow_fold = os.environ.get("PTTS_FLOW_FOLD", "1") != "0" and B > 8
+        self.flow_fold = bool(flow_fold) and self.mode == "events" and not (
+            {"lm_bf16", "attention", "ffn", "codec_split"} & set(eng.quantize_groups))
         # the plan table first: what the rules refuse is refused before anything is allocated
         table = ChainSpec.of(spec, **chain).table(eng.sample_rate, eng.frame_samples)
         if not table.empty and self.mode == "fork":
@@ -1558,6 +1571,11 @@ class StepPipeline:
         torch.cuda.synchronize(dev)
         eng.tune(B)  # before capture: graphs freeze the tile choices
         lib, H = eng.lib, eng.handle
+        if self.flow_fold:  # (never switched off here: another pipeline's graphs of this state may carry it)
+            try:
+                lm_state.set_flow_fold(True)
+            except _lib.PttsError:  # the state already has graphs captured without it: this pipeline runs as they do
+                self.flow_fold = False
         self.g_first = [eng.capture_lm_step(lm_state, noise, lsd_steps, eos_threshold, self.lat[p], self.logit[p],
                                             self.flag[p]) for p in range(nb)]
         # optional 16-bit PCM beside the fp32 one (the WAV sample format, data/audio.py:79), also pinned
