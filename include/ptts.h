@@ -93,9 +93,13 @@ int ptts_create(const ptts_config *cfg, const ptts_tensor *tensors, int32_t n_te
  * FlowLM stays fp32.  Exclusive with PTTS_CODEC_BF16.  Quality: tests/test_gpu_fp8.py. */
 #define PTTS_CODEC_FP8 8
 /* bf16 WEIGHTS for the FlowLM transformer's Linear layers (SURVEY 8(f).4 "bf16 / int8 per-channel LM weights"; same
- * hook as the int8 groups: quantization.py:91-128): weights rounded to bf16 once at load, activations and accumulation
- * fp32 (the bf16 image is widened in registers and fed to the fp32 MFMA), half the weight bytes of a decode step.
- * Exclusive with the int8 groups.  Quality: tests/test_gpu_quant.py. */
+ * hook as the int8 groups: quantization.py:91-128): weights rounded to bf16 once at load (a LayerNorm gain multiplied in
+ * first), and the activation operand of each of the four Linear layers rounded to bf16 in registers, both fed to
+ * v_mfma_f32_16x16x32_bf16; the residual stream, the LayerNorm statistics (taken from the unrounded row), q / k / v, the
+ * KV cache, attention, accumulation and every epilogue stay fp32.  Half the weight bytes of a decode step.  The
+ * single-launch stack (lm_cluster) is fp32 only: with this flag or an int8 group the option falls back to the per-layer
+ * launches.  Exclusive with the int8 groups.  Quality: tests/test_gpu_quant.py; every call against fp64:
+ * tests/test_gpu_lm_formats.py. */
 #define PTTS_LM_BF16 16
 /* ERROR-COMPENSATED bf16 for the codec's GEMMs (an experiment reported beside the fp32 headline): every Linear / conv of the
  * Mimi decoder as hi*hi + hi*lo + lo*hi of bf16 halves (hi = bf16(v), lo = bf16(v - hi)) on the bf16 MFMA with fp32

@@ -96,13 +96,15 @@ def pre_of(kernel):
     return kernel.split("@")[0].split("+")[1:]
 
 
-def check_kernels(prof, kind, attn, L):
-    """the kernels of the backbone that ran are those of the expected path (fp32 weights everywhere)"""
+def check_kernels(prof, kind, attn, L, suffix=(None, None)):
+    """the kernels of the backbone that ran are those of the expected path.  `suffix`: the weight-format suffix of the
+    attention Linears (lm.qkv, lm.out) and of the FFN Linears (lm.ff1, lm.ff2); None: fp32 weights"""
     at = lambda site: [(k, n) for s, k, n in prof if s == site]  # noqa: E731
     count = lambda site: sum(n for _, n in at(site))  # noqa: E731
+    fmt = {"lm.qkv": suffix[0], "lm.out": suffix[0], "lm.ff1": suffix[1], "lm.ff2": suffix[1]}
     for s, k, _ in prof:
         if s.startswith("lm."):
-            assert not {"q8", "b16", "split"} & set(pre_of(k)), (s, k)
+            assert {"q8", "b16", "split"} & set(pre_of(k)) == {fmt.get(s)} - {None}, (s, k)
     if kind == "decode":
         assert at("lm.prep") == [("prep_in", 1)] and not at("lm.rope") and not at("lm.in_linear"), prof
     else:
@@ -113,8 +115,11 @@ def check_kernels(prof, kind, attn, L):
             assert not at(site), prof
         return
     assert not at("lm.cluster"), prof
+    sites = {"lm.prep" if kind == "decode" else "lm.rope", "lm.qkv", "lm.attn", "lm.out", "lm.ff1", "lm.ff2"}
+    assert {s for s, _, _ in prof if s.startswith("lm.")} == sites, prof
     for site, pre in (("lm.qkv", ["ln"]), ("lm.out", []), ("lm.ff1", ["ln"]), ("lm.ff2", [])):
-        assert count(site) == L and all(pre_of(k) == pre for k, _ in at(site)), (site, prof)
+        want = pre + ([fmt[site]] if fmt[site] else [])
+        assert count(site) == L and all(pre_of(k) == want for k, _ in at(site)), (site, prof)
     fam = [(k.split("@")[0], n) for k, n in at("lm.attn") if not k.startswith("attn_combine")]
     assert {f for f, _ in fam} == {attn} and sum(n for _, n in fam) == L, (attn, prof)
 
@@ -252,7 +257,7 @@ class GpuDriver:
         s.off += grow
         self.offsets_are(s)
         if n.any():
-            check_kernels(prof, kind, attn, self.L)
+            self.check_kernels(prof, kind, attn)
         else:
             assert not [r for r in prof if r[0].startswith("lm.")], prof
         # every position the call did not write is bit-identical
@@ -264,12 +269,20 @@ class GpuDriver:
             assert same[:, ~wrote].all(), (l, np.argwhere(~same & ~wrote[None, :, :, None, None])[:4])
         if not judge:
             return
-        res64, e32, ref64 = lm_e32(self.cfg, self.W, snap, op)
-        assert list(ref64.off) == list(s.off) and list(res64.start) == list(start) and list(res64.n) == list(n)
         got = {"x": np.concatenate([x[b, :n[b]].reshape(-1) for b in range(B)])}
         for l in range(self.L):
             for j, name in enumerate("KV"):
                 got[f"{name}{l}"] = np.concatenate([after[l][j, b, start[b]:start[b] + n[b]].reshape(-1) for b in range(B)])
+        self.judge(s, snap, op, attn, got, start, n)
+
+    def check_kernels(self, prof, kind, attn):
+        check_kernels(prof, kind, attn, self.L)
+
+    def judge(self, s, snap, op, attn, got, start, n):
+        """the call's outputs `got` (as Written.outputs() names them) against the reference on the operands `snap`"""
+        kind, B = op[0], s.B
+        res64, e32, ref64 = lm_e32(self.cfg, self.W, snap, op)
+        assert list(ref64.off) == list(s.off) and list(res64.start) == list(start) and list(res64.n) == list(n)
         y64 = res64.outputs()
         ratios = {}
         for name, ref in y64.items():

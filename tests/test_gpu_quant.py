@@ -2,7 +2,10 @@
 weights against the numpy oracle running the same dequantised weights, plus the reference's quality metric
 (SNR against the fp32 model, scripts/evaluate_quantization.py:215-228).  The reference's own int8 arithmetic is
 torch.ao / torchao CPU code outside /root/reference (dynamic activation quantisation): parity against THAT is
-unpinned; tests/golden/int8_reference_snr.json holds the SNR it reaches on the same synthetic weights."""
+unpinned; tests/golden/int8_reference_snr.json holds the SNR it reaches on the same synthetic weights.
+
+These are end-to-end and quality checks.  Every call of the int8 and bf16 backbones against fp64, layer by layer, with the
+weight images and fold vectors against their stated rule, is tests/test_gpu_lm_formats.py."""
 
 import json
 import os
