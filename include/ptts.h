@@ -679,6 +679,37 @@ int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
  * f32[B, ldim] (only kept when that step ran the single-launch flow MLP, "flow_cluster"; -1 otherwise); FlowLM name "mod" =
  * the AdaLN modulations of the last step's first LSD iteration, f32[B, (3 flow_depth + 2) flow_dim] (-1 after a step that
  * ran with the flow fold, ptts_lm_state_set_flow_fold: it computes them on chip and the buffer would be stale).
+ * Mimi names (every codec format; B sequences, rows b * T + t).  A tap is decoded from the layout and element type its
+ * buffer has in the engine's codec format: fp32 fragments, bf16 blocks, or e4m3 bytes, which come back as the decoded
+ * CODES, unscaled (the reader multiplies by the scale "f8_scales" holds for the tap).  A name whose buffer the format or
+ * the options do not keep is refused with a message (-1), never reinterpreted:
+ *   "upsample"            [16 B, m_dim]        the transformer's input (fp32 | bf16)
+ *   "tr_in<l>"            [16 B, m_dim]        the input of layer l; l = 0 is "upsample", l >= 1 is a copy made only while
+ *                                              the engine option "debug_taps" is set (the next layer overwrites the stream)
+ *   "tr_q"                [16 B, 64 heads]     the LAST layer's queries after RoPE (fp32 in every format)
+ *   "tr_k<l>", "tr_v<l>"  [ring B, 64 heads]   EVERY slot of layer l's key / value ring, row b * ring + slot (fp32)
+ *   "tr_attn", "tr_resid", "tr_ff"             the LAST layer's attention output, stream after attention, GELU(linear1)
+ *   "tr_q<l>", "tr_attn<l>", "tr_resid<l>", "tr_ff<l>"  the same of layer l: an earlier layer's are copies made only while
+ *                                              "debug_taps" is set, like "tr_in<l>"
+ *   "dec_tr", "dec_tr_slot<k>" [16 B, m_dim]   the transformer's output of the last frame; slot k of the hand-over ring
+ *                                              (fp32: 4 slots, reduced precision: the 2 parity halves)
+ *   "seanet0"             [16 B, 8 nf]         ELU(conv0) (fp32 | bf16 | e4m3, scale index 0)
+ *   "seanet2/5/8"         [rows_i B, cout_i]   stage i's transposed conv, RAW: the block's skip input (fp32 | bf16)
+ *   "seanet_c<i>"         [rows_i B, cout_i]   the same as the k3 conv reads it: ELU'd (fp32 | bf16 | e4m3, index 3 i - 2);
+ *                                              the fp32 codec's "single_store" keeps the raw value there
+ *   "seanet_h<i>"         [rows_i B, cout_i / compress]  the block's hidden activation (fp32 | bf16 | e4m3, index 3 i - 1);
+ *                                              refused where the fp32 codec's fused block keeps it on chip
+ *   "seanet3/6/9"         [rows_i B, cout_i]   the block's output, ELU'd (fp32 | bf16 | e4m3 for i < 3, index 3 i; the last
+ *                                              block's is bf16 on the fp8 codec too: the last conv reads bf16)
+ *   "seanet11"            [B, frame samples]   the PCM (fp32)
+ *   "w_<site>"            [N, taps C]          the weight image a reduced-precision launch multiplies by (refused on the fp32
+ *                                              codec), site = qkv<l> | out<l> | ff1<l> | ff2<l> | conv0 | convtr<i> | res_a<i> |
+ *                                              res_b<i>; k = tap C + c in the packer's tap order (a transposed conv: tap 0 the
+ *                                              previous input row); bf16 values, or at the fp8 convolutions of an fp8 engine the
+ *                                              e4m3 codes, whose per-row scales are "ws_<site>" [1, N]
+ *   "f8_scales"           [1, 16]            the activation scales of an fp8 codec engine (refused on any other)
+ *   "calib_latent<f>"     [8, ldim]            f = 0..5, on a state of batch 8: the latents the fp8 calibration run decoded
+ *                                              in frame f, generated again by the same kernel
  * Returns rows*cols or <0. */
 int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi, const char *name, float *d_out,
                         int64_t capacity, int32_t *rows, int32_t *cols, void *stream);

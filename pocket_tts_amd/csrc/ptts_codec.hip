@@ -87,7 +87,7 @@ extern "C" void ptts_mimi_state_destroy(ptts_mimi_state *s) {
   hipDeviceSynchronize();
   hipFree(s->frame); hipFree(s->offset); hipFree(s->kv); hipFree(s->zl); hipFree(s->u0);
   hipFree(s->u); hipFree(s->h); hipFree(s->ao); hipFree(s->ff); hipFree(s->q); hipFree(s->part);
-  hipFree(s->pcm_dbg); hipFree(s->pcm_part); hipFree(s->rope);
+  hipFree(s->pcm_dbg); hipFree(s->pcm_part); hipFree(s->rope); hipFree(s->tap_tr);
   for (const Ring *r : s->rings()) hipFree(r->p);
   for (int i = 0; i < 3; ++i) { hipFree(s->craw[i]); hipFree(s->rbuf[i]); }
   delete s;
@@ -139,7 +139,7 @@ static const char *const kSeanetSite[3][3] = {{"seanet.convtr1", "seanet.res1a",
                                               {"seanet.convtr3", "seanet.res3a", "seanet.res3b"}};
 
 // SEANet stage i's residual block runs as one launch
-static bool resblock_fused(const ptts_mimi_state *s, int i) {
+bool resblock_fused(const ptts_mimi_state *s, int i) {
   const ptts_engine *e = s->e;
   const int MTout = s->B * s->rows[i + 1] / 16;
   return e->opt_fuse_res && resblock_fusable(e->res_a[i], e->res_b[i], MTout) && (long)MTout * 16 >= e->fuse_res_min_rows;
@@ -160,6 +160,42 @@ static void mimi_tail(hipStream_t st, const ptts_mimi_state *s, int rows, int tr
   SITE("mimi.tail");
   ProfScope ps(st, "step_tail", 8.0 * s->B, 0);
   mimi_tail_kernel<<<cdiv(s->B, 256), 256, 0, st>>>(s->offset, s->B, rows, s->frame, tr_frames, seanet);
+}
+
+// "debug_taps": a transformer of two or more layers overwrites u, ao, ff and q layer by layer; ptts_debug_read reaches the
+// earlier layers' through copies (ptts_mimi_state::tr_tap).  The buffer exists only after an eager decode with the option
+// (ensure_tr_taps): without it nothing is allocated or enqueued
+static int ensure_tr_taps(ptts_engine *e, ptts_mimi_state *s) {
+  const ptts_config &c = e->cfg;
+  if (!e->opt_debug_taps || s->tap_tr || c.m_layers < 2) return 0;
+  AllocScope alloc_scope(e->stream);
+  const size_t pair = e->codec_bf16 ? 1 : 2;  // as build_mimi_state sizes u, ff and q
+  s->tap_nu = (size_t)s->MT16 * 256 * pair * (c.m_dim / 16);
+  s->tap_nff = (size_t)s->MT16 * 256 * pair * (c.m_ff / 16);
+  s->tap_nq = (size_t)s->B * c.m_heads * 4 * 256 * pair;
+  s->tap_stride = 3 * s->tap_nu + s->tap_nff + s->tap_nq;
+  CHK(dallocT(nullptr, &s->tap_tr, (size_t)(c.m_layers - 1) * s->tap_stride));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+static bool tr_taps_on(const ptts_engine *e, const ptts_mimi_state *s) { return e->opt_debug_taps && s->tap_tr; }
+static int tap_copy(hipStream_t st, float *dst, const float *src, size_t n) {
+  HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+// before layer l >= 1 reads u
+static int tap_layer_input(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, int l) {
+  if (l < 1 || !tr_taps_on(e, s)) return 0;
+  s->tap_frame = s->h_tr;  // host stamp of an eager enqueue: a replayed graph does not renew it, its copies are refused
+  return tap_copy(st, s->tr_tap(l).in, s->u, s->tap_nu);
+}
+// after the last launch of layer l < layers - 1 (its stream after attention is copied before linear2 overwrites it)
+static int tap_layer_end(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, int l) {
+  if (l >= e->cfg.m_layers - 1 || !tr_taps_on(e, s)) return 0;
+  const ptts_mimi_state::TrTap t = s->tr_tap(l + 1);
+  CHK(tap_copy(st, t.ao, s->ao, s->tap_nu));
+  CHK(tap_copy(st, t.ff, s->ff, s->tap_nff));
+  return tap_copy(st, t.q, s->q, s->tap_nq);
 }
 
 // the codec frame with bf16 activations: same dataflow, buffers and carries as mimi_enqueue (the fp32 buffers are
@@ -185,6 +221,7 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     const TrLayer &T = e->mm[l];
     float *x_in = l == 0 ? s->u0 : s->u;
     const bool last = l == c.m_layers - 1;
+    CHK(tap_layer_input(st, e, s, l));
     SITE("mimi.qkv");
     a = mk_gemm(T.qkv, x_in, CB, MT16, M16);
     a.epi = EPI_QKV;
@@ -206,6 +243,7 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     a = mk_gemm(T.out, s->ao, CB, MT16, M16);
     a.epi = EPI_RES; a.R = x_in; a.RF = CB; a.Y = s->u; a.YF = CB; a.ls = T.ls1;
     launch_gemm_h(st, a, PRE_NONE, T.out);
+    if (!last && tr_taps_on(e, s)) CHK(tap_copy(st, s->tr_tap(l + 1).resid, s->u, s->tap_nu));
     SITE("mimi.ff1");
     a = mk_gemm(T.ff1, s->u, CB, MT16, M16);
     a.epi = EPI_STORE; a.act = ACT_GELU; a.Y = s->ff; a.YF = c.m_ff / 32;
@@ -215,6 +253,7 @@ static int mimi_enqueue_h(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, co
     a.epi = EPI_RES; a.R = s->u; a.RF = CB; a.ls = T.ls2;
     a.Y = last ? s->tr_out.p : s->u; a.YF = CB; a.Ydstride = last ? s->tr_out.step() : 0; a.par = last ? s->trf() : nullptr;
     launch_gemm_h(st, a, PRE_NONE, T.ff2);
+    CHK(tap_layer_end(st, e, s, l));
   }
   if (parts == 1) mimi_tail(st, s, st16, 1, 0);
   }
@@ -319,7 +358,10 @@ static int mimi_tr_enqueue(hipStream_t st, ptts_engine *e, ptts_mimi_state *s, c
     t.Kc = s->K(l); t.Vc = s->V(l); t.offset = s->offset; t.rope = s->rope;
     t.kv_keys = (double)B * std::min(e->ring, (s->h_tr + frames) * st16);
     t.tag = "mimi";
+    CHK(tap_layer_input(st, e, s, l));
+    if (!last && tr_taps_on(e, s)) t.tap_x = s->tr_tap(l + 1).resid;
     run_tr_layer(st, e->mm[l], t);
+    CHK(tap_layer_end(st, e, s, l));
   }
   if (tail) mimi_tail(st, s, Tq, frames, 0);
   SITE("");
@@ -435,7 +477,7 @@ int mimi_parts_check(const ptts_mimi_state *s, int parts, int frames) {
   return 0;
 }
 void mimi_parts_done(ptts_mimi_state *s, int parts, int frames) {
-  if (parts & PART_TR) s->h_tr += frames;
+  if (parts & PART_TR) { s->h_tr += frames; s->h_tr_last = frames; }
   if (parts & PART_SEANET) s->h_frame += 1;
 }
 
@@ -444,6 +486,9 @@ void mimi_parts_done(ptts_mimi_state *s, int parts, int frames) {
 __global__ void calib_latent_kernel(float *lat, int n, unsigned frame) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) lat[i] = counter_normal(0x5EEDull, frame, (unsigned)i);
+}
+void calib_latent(hipStream_t st, float *lat, int n, unsigned frame) {
+  calib_latent_kernel<<<cdiv(n, 256), 256, 0, st>>>(lat, n, frame);
 }
 int calibrate_fp8_codec(ptts_engine *e) {
   const ptts_config &c = e->cfg;
@@ -457,7 +502,7 @@ int calibrate_fp8_codec(ptts_engine *e) {
   if (rc == 0) {
     (void)hipMemsetAsync(amax, 0, 64, st);
     for (int f = 0; f < frames && rc == 0; ++f) {
-      calib_latent_kernel<<<cdiv(B * c.ldim, 256), 256, 0, st>>>(lat, B * c.ldim, (unsigned)f);
+      calib_latent(st, lat, B * c.ldim, (unsigned)f);
       rc = mimi_enqueue_h(st, e, ms, lat, nullptr);
       mimi_parts_done(ms, PART_ALL, 1);
       // both parity slots hold bf16 data in their first half (see mimi_enqueue_h); scan them after every frame
@@ -662,6 +707,7 @@ extern "C" int ptts_mimi_decode(ptts_engine *e, ptts_mimi_state *s, const float 
   HIPCHK(hipSetDevice(e->device));
   if (!d_latent) return fail(-1, "null latent");
   CHK(mimi_parts_check(s, PART_ALL, 1));
+  CHK(ensure_tr_taps(e, s));
   CHK(mimi_frame_enqueue(S(e, stream), e, s, d_latent, d_pcm));
   mimi_parts_done(s, PART_ALL, 1);
   LAUNCHCHK();
@@ -676,6 +722,7 @@ extern "C" int ptts_mimi_decode_tr(ptts_engine *e, ptts_mimi_state *s, const flo
   if (!d_latent) return fail(-1, "null latent");
   const int frames = d_latent_b ? 2 : 1;
   CHK(mimi_parts_check(s, PART_TR, frames));
+  CHK(ensure_tr_taps(e, s));
   CHK(mimi_frame_enqueue(S(e, stream), e, s, d_latent, nullptr, PART_TR, d_latent_b));
   mimi_parts_done(s, PART_TR, frames);
   LAUNCHCHK();

@@ -30,6 +30,29 @@ static __global__ void dbg_from_codec_kernel(const void *src, float *dst, int M,
   dst[i] = fmt == 0 ? (float)((const __bf16 *)src)[o] : dbg_e4m3(((const uint8_t *)src)[o]);
 }
 
+static __global__ void dbg_unpack_codec_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KBt);
+// ptts_debug_read on a Mimi state: the element type of a tap, and the two buffers that are fp32 in every codec format
+enum { TAP_F32, TAP_BF16, TAP_E4M3 };
+// the query blocks [B * H][QB][4][64 lanes][4] -> [B * Tq][H * 64] (Tq = 16 QB)
+static __global__ void dbg_from_q_kernel(const float *Q, float *dst, int M, int H, int Tq, int QB) {
+  const int D = H * 64;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)M * D) return;
+  const int m = i / D, n = i - (long)m * D, h = n >> 6, d = n & 63;
+  const int b = m / Tq, t = m - b * Tq;
+  const size_t bh = (size_t)b * H + h;
+  dst[i] = Q[(((bh * QB + (t >> 4)) * 4 + (d >> 4)) * 64 + 16 * ((d & 15) >> 2) + (t & 15)) * 4 + (d & 3)];
+}
+// one plane [B][H][cap][64] of the key / value ring -> [B * cap][H * 64], row b * cap + slot
+static __global__ void dbg_from_kv_kernel(const float *Kc, float *dst, int B, int H, int cap) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * cap * H * 64) return;
+  const int d = i & 63, h = (i >> 6) % H;
+  const long r = (i >> 6) / H;
+  const int slot = r % cap, b = r / cap;
+  dst[i] = Kc[(((size_t)b * H + h) * cap + slot) * 64 + d];
+}
+
 // Runs one case on the engine's stream (or `stream`) under the engine lock, with a scratch engine that owns whatever the
 // case packs and allocates: freed here whatever the outcome
 template <typename Fn>
@@ -94,23 +117,140 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
     ptts_mimi_state *s = (ptts_mimi_state *)state;
     const int par = (s->h_frame - 1) & 1;  // parity of the frame decoded last
     const int B = s->B;
-    if (n == "upsample") { src = s->u0; M = B * 16; K = c.m_dim; }
-    else if (n == "dec_tr") { src = s->tr_out.slot((s->h_frame - 1) & (s->tr_out.slots - 1)); M = B * 16; K = c.m_dim; }
+    // the element type a buffer really has: the transformer's buffers and SEANet's skip / last-block buffers follow the
+    // codec format (fp32 or bf16), the inputs of the fp8 convolutions are e4m3 (build_mimi_state's e_tr / e_sn)
+    const int f_tr = e->codec_bf16 ? TAP_BF16 : TAP_F32, f_sn = e->codec_fp8 ? TAP_E4M3 : f_tr;
+    const int trM = B * 16 * s->h_tr_last;  // rows of the last transformer launch
+    int fmt = f_tr;
+    const void *p = nullptr;
+    auto index_of = [&](size_t prefix, int lo, int hi) {  // the decimal index behind the prefix, or -1
+      if (n.size() <= prefix || n.size() > prefix + 2) return -1;
+      for (size_t i = prefix; i < n.size(); ++i)
+        if (n[i] < '0' || n[i] > '9') return -1;
+      const int k = atoi(n.c_str() + prefix);
+      return k >= lo && k <= hi ? k : -1;
+    };
+    auto plain = [&](int r, int k) -> int64_t {  // d_out already holds f32[r][k]
+      LAUNCHCHK();
+      *rows = r; *cols = k;
+      return (int64_t)r * k;
+    };
+    if (n == "upsample" || n == "tr_in0") { p = s->u0; M = n == "upsample" ? B * 16 : trM; K = c.m_dim; }
+    else if (n == "dec_tr") { p = s->tr_out.slot((s->h_frame - 1) & (s->tr_out.slots - 1)); M = B * 16; K = c.m_dim; }
     else if (n.compare(0, 11, "dec_tr_slot") == 0) {  // slot k of the hand-over ring (frame f lies in slot f & (slots - 1))
-      const int k = atoi(n.c_str() + 11);
-      if (n.size() != 12 || k < 0 || k >= s->tr_out.slots) return fail(-1, "unknown buffer " + n);
-      src = s->tr_out.slot(k); M = B * 16; K = c.m_dim;
+      const int k = index_of(11, 0, 3);
+      if (k < 0) return fail(-1, "unknown buffer " + n);
+      if (k >= s->tr_out.slots) return fail(-1, "debug_read: " + n + ": the hand-over ring of this codec format has " + std::to_string(s->tr_out.slots) + " slots");
+      p = s->tr_out.slot(k); M = B * 16; K = c.m_dim;
     }
-    else if (n == "seanet0") { src = s->a0.slot(par); M = B * 16; K = 8 * c.n_filters; }
-    else if (n == "tr_attn") { src = s->ao; M = B * 16; K = c.m_dim; }       // last layer's attention output
-    else if (n == "tr_resid") { src = s->u; M = B * 16; K = c.m_dim; }       // last layer's stream after attention
-    else if (n == "tr_ff") { src = s->ff; M = B * 16; K = c.m_ff; }          // last layer's GELU(linear1)
+    else if (n == "seanet0") { p = s->a0.slot(par); fmt = f_sn; M = B * 16; K = 8 * c.n_filters; }
+    else if (n == "tr_attn") { p = s->ao; M = B * 16; K = c.m_dim; }       // last layer's attention output
+    else if (n == "tr_resid") { p = s->u; M = B * 16; K = c.m_dim; }       // last layer's stream after attention
+    else if (n == "tr_ff") { p = s->ff; M = B * 16; K = c.m_ff; }          // last layer's GELU(linear1)
+    else if (n.compare(0, 5, "tr_in") == 0 || n.compare(0, 7, "tr_attn") == 0 || n.compare(0, 8, "tr_resid") == 0 ||
+             n.compare(0, 5, "tr_ff") == 0 || n.compare(0, 4, "tr_q") == 0) {
+      // the same of layer l: the last layer's are the buffers themselves, an earlier layer's (and the input of a layer
+      // >= 1) the copies made while "debug_taps" is set
+      const size_t pre = n[3] == 'i' ? 5 : n[3] == 'a' ? 7 : n[3] == 'r' ? 8 : n[3] == 'f' ? 5 : 4;
+      const char kind = n[3];
+      const int last = c.m_layers - 1;
+      const int l = n.size() == pre && kind == 'q' ? last : index_of(pre, kind == 'i' ? 1 : 0, last);
+      if (l < 0) return fail(-1, "unknown buffer " + n);
+      const bool copy = kind == 'i' || l < last;
+      if (copy && (!s->tap_tr || !e->opt_debug_taps))
+        return fail(-1, "debug_read: " + n + " is only kept with the engine option \"debug_taps\" set before decoding");
+      if (copy && s->tap_frame != s->h_tr - s->h_tr_last)
+        return fail(-1, "debug_read: " + n + " is stale: the last frame was not decoded eagerly with \"debug_taps\" set");
+      const ptts_mimi_state::TrTap t = copy ? s->tr_tap(kind == 'i' ? l : l + 1) : ptts_mimi_state::TrTap{nullptr, s->u, s->ao, s->ff, s->q};
+      M = trM; K = kind == 'f' ? c.m_ff : c.m_dim;
+      p = kind == 'i' ? t.in : kind == 'a' ? t.ao : kind == 'r' ? t.resid : t.ff;
+      if (kind == 'q') {  // the query blocks after RoPE: fp32 in every format
+        K = c.m_heads * 64;
+        if ((int64_t)M * K > capacity) return fail(-1, "debug_read: capacity too small");
+        dbg_from_q_kernel<<<cdiv((long)M * K, 256), 256, 0, st>>>(t.q, d_out, M, c.m_heads, 16 * s->h_tr_last, s->h_tr_last);
+        return plain(M, K);
+      }
+    }
+    else if (n.compare(0, 4, "tr_k") == 0 || n.compare(0, 4, "tr_v") == 0) {  // every slot of a layer's ring, row b * ring + slot
+      const int l = index_of(4, 0, c.m_layers - 1);
+      if (l < 0) return fail(-1, "unknown buffer " + n);
+      M = B * e->ring; K = c.m_heads * 64;
+      if ((int64_t)M * K > capacity) return fail(-1, "debug_read: capacity too small");
+      dbg_from_kv_kernel<<<cdiv((long)M * K, 256), 256, 0, st>>>(n[3] == 'k' ? s->K(l) : s->V(l), d_out, B, c.m_heads, e->ring);
+      return plain(M, K);
+    }
+    else if (n.compare(0, 2, "w_") == 0 || n.compare(0, 3, "ws_") == 0) {
+      // the weight image a reduced-precision launch multiplies by, [16 NT][ntaps * C] (k = tap * C + c in the packer's tap
+      // order): bf16 values, or at the fp8 convolutions of an fp8 engine e4m3 codes, whose per-row scales are "ws_<site>"
+      if (!e->codec_bf16) return fail(-1, "debug_read: " + n + ": the fp32 codec has no reduced-precision weight image");
+      const bool scale = n[1] == 's';
+      const size_t off = scale ? 3 : 2;
+      const std::string site = n.substr(off);
+      const Lin *L = nullptr;
+      bool conv = false;  // a SEANet convolution that the fp8 codec runs on e4m3
+      auto layer = [&](const char *pre) {
+        const size_t k = strlen(pre);
+        return site.compare(0, k, pre) == 0 ? index_of(off + k, 0, c.m_layers - 1) : -1;
+      };
+      auto stage = [&](const char *pre) {
+        const size_t k = strlen(pre);
+        return site.compare(0, k, pre) == 0 ? index_of(off + k, 1, 3) - 1 : -1;
+      };
+      int i;
+      if ((i = layer("qkv")) >= 0) L = &e->mm[i].qkv;
+      else if ((i = layer("out")) >= 0) L = &e->mm[i].out;
+      else if ((i = layer("ff1")) >= 0) L = &e->mm[i].ff1;
+      else if ((i = layer("ff2")) >= 0) L = &e->mm[i].ff2;
+      else if (site == "conv0") L = &e->conv0;
+      else if ((i = stage("convtr")) >= 0) { L = &e->convtr[i]; conv = true; }
+      else if ((i = stage("res_a")) >= 0) { L = &e->res_a[i]; conv = true; }
+      else if ((i = stage("res_b")) >= 0) { L = &e->res_b[i]; conv = true; }
+      if (!L) return fail(-1, "unknown buffer " + n);
+      const bool f8w = conv && e->codec_fp8;
+      if (scale && !f8w) return fail(-1, "debug_read: " + n + ": the site has no e4m3 weight image in this codec format");
+      const int Nn = L->NT * 16, KBt = (L->C / 32) * L->ntaps;
+      if (scale) {
+        if (capacity < Nn) return fail(-1, "debug_read: capacity too small");
+        HIPCHK(hipMemcpyAsync(d_out, L->wscale8, (size_t)Nn * 4, hipMemcpyDeviceToDevice, st));
+        return plain(1, Nn);
+      }
+      if ((int64_t)Nn * KBt * 32 > capacity) return fail(-1, "debug_read: capacity too small");
+      dbg_unpack_codec_weight_kernel<<<cdiv((long)Nn * KBt * 32, 256), 256, 0, st>>>(f8w ? L->wf8 : (const void *)L->wh, nullptr, f8w ? 2 : 0,
+                                                                                    d_out, Nn, KBt);
+      return plain(Nn, KBt * 32);
+    }
+    else if (n == "f8_scales") {  // the activation scales the fp8 convolutions run with (the host mirror the launches read)
+      if (!e->codec_fp8) return fail(-1, "debug_read: f8_scales: the engine has no fp8 codec");
+      if (capacity < 16) return fail(-1, "debug_read: capacity too small");
+      HIPCHK(hipMemcpyAsync(d_out, e->f8s, sizeof(e->f8s), hipMemcpyHostToDevice, st));
+      return plain(1, 16);
+    }
+    else if (n.compare(0, 12, "calib_latent") == 0) {  // what calibrate_fp8_codec fed in frame f (its state has batch 8)
+      const int f = index_of(12, 0, 5);
+      if (f < 0) return fail(-1, "unknown buffer " + n);
+      if (B != 8) return fail(-1, "debug_read: " + n + " needs a state of batch 8, the calibration run's");
+      if (capacity < (int64_t)B * c.ldim) return fail(-1, "debug_read: capacity too small");
+      calib_latent(st, d_out, B * c.ldim, (unsigned)f);
+      return plain(B, c.ldim);
+    }
     else if (n == "seanet11") {
       M = B; K = s->rows[3];
       if ((int64_t)M * K > capacity) return fail(-1, "capacity");
       if (hipMemcpyAsync(d_out, s->pcm_dbg, (size_t)M * K * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(-2, "memcpy");
       *rows = M; *cols = K;
       return (int64_t)M * K;
+    } else if (n.compare(0, 8, "seanet_c") == 0 || n.compare(0, 8, "seanet_h") == 0) {
+      // stage i's transposed-conv output as the k3 conv reads it (ELU'd; the fp32 codec's "single_store" keeps it raw), and
+      // the block's hidden activation
+      const int i = index_of(8, 1, 3) - 1;
+      if (i < 0) return fail(-1, "unknown buffer " + n);
+      const int cout = (8 >> i) * c.n_filters / 2;
+      M = B * s->rows[i + 1]; fmt = f_sn;
+      if (n[7] == 'c') { p = s->cbuf[i].slot(par); K = cout; }
+      else {
+        if (!e->codec_bf16 && resblock_fused(s, i)) return fail(-1, "debug_read: " + n + " stays on chip in the fused residual block");
+        p = s->rbuf[i]; K = cout / c.compress;
+      }
     } else {
       int idx = atoi(n.c_str() + 6);
       if (n.compare(0, 6, "seanet") != 0 || idx < 2 || idx > 9) return fail(-1, "unknown buffer " + n);
@@ -122,8 +262,18 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
       M = B * s->rows[stage + 1];
       if (is_res && stage == 2 && seanet_fuses_pcm(s) && !s->e->opt_debug_taps)
         return fail(-1, "debug_read: " + n + " stays on chip with \"fuse_pcm\"; set the engine option \"debug_taps\" before decoding");
-      src = is_res ? s->sbuf[stage].slot(par) : seanet_single_store(s->e, stage) ? s->cbuf[stage].slot(par) : s->craw[stage];
+      // the reduced-precision codecs always keep the raw skip input in craw (bf16); their block outputs are e4m3 where an
+      // fp8 convolution reads them (stages 1 and 2) and bf16 in front of the last conv
+      if (is_res) { p = s->sbuf[stage].slot(par); fmt = stage == 2 ? f_tr : f_sn; }
+      else p = e->codec_bf16 ? s->craw[stage] : seanet_single_store(s->e, stage) ? s->cbuf[stage].slot(par) : s->craw[stage];
     }
+    if (fmt != TAP_F32) {  // FMH bf16 / FM8 e4m3 (decoded codes, unscaled: the reader applies the scale)
+      if (K % 32) return fail(-1, "debug_read: " + n + ": the reduced-precision layouts hold 32-column blocks");
+      if ((int64_t)M * K > capacity) return fail(-1, "debug_read: capacity too small");
+      dbg_from_codec_kernel<<<cdiv((long)M * K, 256), 256, 0, st>>>(p, d_out, M, K, K / 32, fmt == TAP_BF16 ? 0 : 1);
+      return plain(M, K);
+    }
+    src = (const float *)p;
     F = K / 16;
   }
   if ((int64_t)M * K > capacity) return fail(-1, "debug_read: capacity too small");
@@ -496,14 +646,15 @@ static __global__ void dbg_to_codec_kernel(const float *src, void *dst, float *e
   }
   if (eff && m < M) *(f32x4 *)(eff + (size_t)m * C + c0) = d;
 }
-// weights of a codec image [NT][KBt][64][8] as [N][KBt * 32] f32 (k = tap * C + c): fmt 0 bf16, 1 e4m3 times scale[n]
+// weights of a codec image [NT][KBt][64][8] as [N][KBt * 32] f32 (k = tap * C + c): fmt 0 bf16, 1 e4m3 times scale[n], 2 e4m3
+// codes
 static __global__ void dbg_unpack_codec_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KBt) {
   const long K = (long)KBt * 32;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)N * K) return;
   const int n = i / K, k = i - (long)n * K;
   const size_t o = (((size_t)(n >> 4) * KBt + (k >> 5)) * 64 + 16 * ((k & 31) >> 3) + (n & 15)) * 8 + (k & 7);
-  dst[i] = fmt == 0 ? (float)((const __bf16 *)img)[o] : dbg_e4m3(((const uint8_t *)img)[o]) * scale[n];
+  dst[i] = fmt == 0 ? (float)((const __bf16 *)img)[o] : fmt == 2 ? dbg_e4m3(((const uint8_t *)img)[o]) : dbg_e4m3(((const uint8_t *)img)[o]) * scale[n];
 }
 // EPI_QKV outputs -> [M][3 * H * 64]: q from its block layout, k / v from cache slot pos % ring (ring 0: pos)
 static __global__ void dbg_from_qkv_kernel(const float *Q, const float *Kc, const float *Vc, const int *offset, float *dst, int M,

@@ -299,6 +299,19 @@ struct ptts_mimi_state {
   Ring zq, tr_out, a0, cbuf[3], sbuf[3], pcm_carry;
   std::array<Ring *, 10> rings() { return {&zq, &tr_out, &a0, &cbuf[0], &sbuf[0], &cbuf[1], &sbuf[1], &cbuf[2], &sbuf[2], &pcm_carry}; }
   float *craw[3], *rbuf[3];  // the raw skip input of a residual block, its hidden activation
+  // test hook ("debug_taps", ptts_debug_read "tr_in<l>", "tr_resid<l>", ...): what the next transformer layer overwrites,
+  // copied aside.  Block l - 1 of tap_tr (tap_stride floats) holds the input of layer l >= 1 and layer l - 1's stream after
+  // attention, attention output, GELU(linear1) and query blocks: tr_tap().  Allocated by the first eager decode that runs
+  // with the option; without it nothing is allocated, copied or launched
+  float *tap_tr = nullptr;
+  size_t tap_nu = 0, tap_nff = 0, tap_nq = 0, tap_stride = 0;  // floats of u / ff / q as build_mimi_state allocates them
+  struct TrTap { float *in, *resid, *ao, *ff, *q; };
+  TrTap tr_tap(int l) const {  // l = 1 .. layers - 1
+    float *p = tap_tr + (size_t)(l - 1) * tap_stride;
+    return TrTap{p, p + tap_nu, p + 2 * tap_nu, p + 3 * tap_nu, p + 3 * tap_nu + tap_nff};
+  }
+  int h_tr_last = 1;  // frames of the last transformer launch (the query blocks hold that many 16-query blocks per head)
+  int tap_frame = -1;  // h_tr when the copies in tap_tr were last enqueued: they are the last launch's iff == h_tr - h_tr_last
   int rows[4];  // rows per sequence at each SEANet stage
   float *pcm_dbg;
   int16_t *pcm_i16 = nullptr;
@@ -324,6 +337,8 @@ void mimi_parts_done(ptts_mimi_state *s, int parts, int frames);
 int calibrate_fp8_codec(ptts_engine *e);  // build_fp8_codec: fills e->d_f8s from a run of the bf16 codec
 bool seanet_single_store(const ptts_engine *e, int i);  // stage i's transposed conv stores its raw output only
 bool seanet_fuses_pcm(const ptts_mimi_state *s);  // the last conv rides in the last block: sbuf[2] is written with "debug_taps" only
+bool resblock_fused(const ptts_mimi_state *s, int i);  // fp32 codec: stage i's residual block is one launch, rbuf[i] is not written
+void calib_latent(hipStream_t st, float *lat, int n, unsigned frame);  // the latents of calibration frame `frame`, [8][ldim]
 
 // ---- the transformer layer (ptts.hip; the FlowLM, the codec and the voice encoder run it) -----------------------------
 struct TrCtx {

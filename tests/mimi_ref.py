@@ -561,3 +561,506 @@ def seeded_latents(cfg, F, B, seed, scale=1.0):
     """[F, B, ldim] float32 ~ scale * N(0, 1): different latents per frame and sequence"""
     rng = np.random.default_rng(seed)
     return (rng.standard_normal((F, B, cfg.mimi.quantizer.dimension)) * scale).astype(np.float32)
+
+
+# ---- the reduced-precision codecs (codec_bf16, codec_fp8): one stateless function per LAUNCH ----------------------------
+# mimi_enqueue_h (csrc/ptts_codec.hip) launches, per transformer layer l, Q (+ln GEMM with EPI_QKV), A (attention), B
+# (out_proj + residual), C (+ln GEMM, GELU), D (linear2 + residual), after the prologue P; then S0 (conv0), per SEANet stage
+# i = 1..3 Cv (transposed conv, raw and ELU'd outputs), Ra (k3 conv), Rb (1x1 conv + skip), and L (the last conv).
+#
+# Every input is what was read back from the device (`Engine.debug_read`), so it is exactly representable: bf16 values, or
+# for the operands of the fp8 convolutions e4m3 CODES (value = code * scales[k], k from SC_IN).  A function returns the
+# launch's outputs BEFORE the output rounding (`OUT_KIND`, `out_round`), in `dtype`.  The only roundings inside are the ones
+# the kernels make:
+#   * the weight image: bf16 RNE of the fp32 weight (pack_weight_h_kernel, ptts_bf16.h:40), for a +ln site of the fp32
+#     product w * ln_w (ptts_bf16.h:34); or e4m3 of w * (1 / scale) with scale = amax / 448 per output row, all fp32
+#     (pack_weight_f8_kernel, ptts_fp8.hip:46,53-55);
+#   * +ln sites: y = rs * (W' x - mu * sum_k W'[n][k]) + c with the sum over the ROUNDED image (fold_s_h_kernel,
+#     ptts_bf16.h:44-55; restated as W' ((x - mu) rs) + c, which is the same number when the two sums agree), c = W ln_b from
+#     the unrounded weights (fold_ln_kernel), and fp32 statistics mu, E[x^2] - mu^2 of the bf16 operand (ptts_bf16.h:171-179,
+#     207-210);
+#   * fp8 sites: acc * (wscale * xs), the fp32 product wscale * xs first (gemm_f8_epilogue, ptts_fp8.hip:90);
+#   * the output: bf16 RNE (to_bf16x4, ptts_bf16.h:70,75,108); or v * yinv, yinv = 1 / scales[k] in fp32, clamped to +-448 and
+#     rounded to e4m3 (to_f8x4, ptts_kernels.h:37; ptts_bf16.h:69, ptts_fp8.hip:83); the PCM stays fp32.
+# `ident=True` replaces every one of these roundings by the identity: the functions are then the fp64 stages above.
+import torch  # noqa: E402  (bf16 / e4m3 conversions)
+
+import codec_ref as _CR  # noqa: E402
+from gemm_ref import bf16_round as _bf16_round  # noqa: E402
+
+FMTS = ("bf16", "fp8")
+E4M3_MAX = 448.0
+FMT_MUTANTS = {
+    "sc_in_next": "sc_in of a transposed conv read from the next scale index",
+    "no_yinv": "yinv left at 1 on one conv",
+    "wrap": "an e4m3 output converted without the clamp to +-448 (magnitudes past the format's top come out as 0x7f, NaN)",
+    "skip_elu": "the residual block's skip taken from the ELU'd copy instead of the raw one",
+    "elu_twice": "ELU applied again on the operand of a transposed or k3 conv",
+    "no_bias2": "the 1x1 conv's bias dropped",
+    "tensor_scale": "one weight scale per tensor instead of one per output channel",
+    "trunc": "a bf16 output truncated instead of rounded to nearest even",
+    "ln_s_unrounded": "the LayerNorm fold's ln_s summed from the unrounded weights",
+    "parity": "the halo read from the current frame's parity slot",
+    "k_layer0": "layer 1 attending over layer 0's K ring",
+}
+# index of the activation scale an fp8 convolution reads its operand with / writes its e4m3 output with (ptts_host.h:142:
+# 0 conv0's output, 3 i - 2 stage i's transposed conv (ELU'd), 3 i - 1 its hidden activation, 3 i its block output, i < 3)
+SC_IN = {("convtr", 1): 0, ("convtr", 2): 3, ("convtr", 3): 6, **{("res_a", i): 3 * i - 2 for i in (1, 2, 3)},
+         **{("res_b", i): 3 * i - 1 for i in (1, 2, 3)}}
+SC_OUT = {("conv0",): 0, **{("convtr", i): 3 * i - 2 for i in (1, 2, 3)}, **{("res_a", i): 3 * i - 1 for i in (1, 2, 3)},
+          ("res_b", 1): 3, ("res_b", 2): 6}
+SC_USED = sorted(set(SC_OUT.values()))
+_CONFIG_EDITS["nf64x2"] = dict(n_filters=64, mimi_layers=2)  # nf64 with two layers: the layer-to-layer hand-over
+
+
+def bf16(x, trunc=False):
+    """fp32 -> bf16 values (float64): round to nearest even, or (a seeded defect) truncation"""
+    x32 = np.ascontiguousarray(x, dtype=np.float32)
+    if trunc:
+        return (x32.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32).astype(np.float64)
+    return _bf16_round(torch.from_numpy(x32)).numpy()  # gemm_ref's
+
+
+def e4m3(x, clamp=True):
+    """fp32 -> OCP e4m3fn codes (float64), after the kernels' clamp to +-448"""
+    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if clamp:
+        return _CR.e4m3(t).numpy()  # codec_ref's
+    return t.to(torch.float8_e4m3fn).to(torch.float64).numpy()  # the seeded defect: no clamp
+
+
+def f32_div(a, b):
+    return (np.asarray(a, np.float64) / np.asarray(b, np.float64)).astype(np.float32)
+
+
+def is_bf16(x):
+    x = np.asarray(x, np.float32)
+    return bool(np.array_equal(bf16(x), x.astype(np.float64)))
+
+
+def is_e4m3(x):
+    x = np.asarray(x, np.float32)
+    return bool(np.isfinite(x).all() and np.array_equal(e4m3(x), x.astype(np.float64)))
+
+
+def yinv_of(scales, k):
+    """1.0f / f8s[k] (ptts_codec.hip, f8_conv)"""
+    return f32_div(1.0, np.float32(scales[k]))
+
+
+def out_round(pre, kind, yinv=None, mutate=None):
+    """the output rounding of a launch: kind "bf16", "e4m3" (codes of pre * yinv) or "f32" -> float64"""
+    if kind == "f32":
+        return np.asarray(pre, np.float32).astype(np.float64)
+    if kind == "bf16":
+        return bf16(pre, trunc=mutate == "trunc")
+    y = np.asarray(pre, np.float32) * (np.float32(1) if mutate == "no_yinv" else np.float32(yinv))
+    return e4m3(y, clamp=mutate != "wrap")
+
+
+_SITES = {}
+
+
+def _lp(l):
+    return f"mimi.decoder_transformer.transformer.layers.{l}"
+
+
+def site_weights(cfg, W, site, mode, mutate=None):
+    """(w [N, K] float64, bias or ln_c [N] float64 or None, wscale [N] float32 or None) of one GEMM site; mode "ident"
+    (the unrounded weights), "f32" (what the packer rounds), "bf16" or "fp8" (e4m3 CODES and their per-row scale; the same
+    arithmetic as codec_ref.quant_weight_f8, which returns the codes times the scale: compared bitwise on the CPU).  K runs tap-major, oldest input row first;
+    a transposed conv's rows are j * cout + o, its first C columns multiply the current input row"""
+    key = (id(W), site, mode, mutate)
+    if key in _SITES:
+        return _SITES[key][1:]
+    P = params(cfg, W, F32)
+    kind = site[0]
+    bias = None
+    if kind in ("qkv", "ff1"):
+        p = _lp(site[1])
+        wn, nn = (".self_attn.in_proj.weight", ".norm1") if kind == "qkv" else (".linear1.weight", ".norm2")
+        w0 = P.vec(p + wn)
+        w32 = w0 * P.vec(p + nn + ".weight")[None, :]  # the fp32 product
+        if mode == "ident":
+            w32 = w0.astype(F64) * P.vec(p + nn + ".weight").astype(F64)[None, :]
+        bias = w0.astype(F64) @ P.vec(p + nn + ".bias").astype(F64)
+    elif kind in ("out", "ff2"):
+        w32 = P.vec(_lp(site[1]) + (".self_attn.out_proj.weight" if kind == "out" else ".linear2.weight"))
+    elif kind == "conv0":
+        w32, b = P.conv(f"mimi.decoder.model.{_layer_of(cfg, 'conv', 0)[0]}.conv")
+        bias = b.astype(F64)
+    elif kind == "convtr":
+        idx, _, _, _, s = _layer_of(cfg, "convtr", site[1])
+        w32, b = P.convtr(f"mimi.decoder.model.{idx}.convtr", s)
+        bias = np.tile(b, s).astype(F64)
+    else:
+        p = f"mimi.decoder.model.{_layer_of(cfg, 'res', site[1])[0]}.block" + (".1.conv" if kind == "res_a" else ".3.conv")
+        w32, b = P.conv(p)
+        bias = b.astype(F64)
+    ws = None
+    if mode in ("ident", "f32"):  # "f32": the fp32 matrix the packer rounds (a +ln site's fp32 product)
+        w = w32.astype(F64)
+    elif mode == "bf16":
+        w = bf16(w32)
+    else:
+        amax = np.abs(w32).max(axis=1)
+        if mutate == "tensor_scale":
+            amax = np.full_like(amax, amax.max())
+        ws = np.where(amax > 0, f32_div(amax, 448.0), np.float32(1)).astype(F32)
+        inv = f32_div(1.0, ws)
+        w = e4m3((w32.astype(F64) * inv.astype(F64)[:, None]).astype(F32))
+    _SITES[key] = (W, w, bias, ws)
+    return w, bias, ws
+
+
+def _fmode(fmt, site, ident):
+    return "ident" if ident else "fp8" if fmt == "fp8" and site in SC_IN else "bf16"
+
+
+def _fgemm(cfg, W, fmt, site, x, scales, dtype, order, ident, mutate):
+    """x [..., K] times the site's weight image, plus its bias: x holds bf16 values, or at an fp8 site e4m3 codes"""
+    w, b, ws = site_weights(cfg, W, site, _fmode(fmt, site, ident), mutate if mutate == "tensor_scale" else None)
+    x = _in(x, dtype)
+    dt = np.dtype(dtype).type
+    if fmt == "fp8" and site in SC_IN:
+        k = SC_IN[site] + (1 if mutate == "sc_in_next" and site[0] == "convtr" else 0)
+        xs = np.float32(scales[k])
+        if ws is None:  # identity roundings: the operand's value times the unrounded weight
+            acc = _mm(x * dt(xs), w.astype(dtype), None, order)
+        else:
+            acc = _mm(x, w.astype(dtype), None, order) * (ws * xs).astype(dtype)  # the fp32 product wscale * xs first
+    else:
+        acc = _mm(x, w.astype(dtype), None, order)
+    return acc if b is None else acc + b.astype(dtype)
+
+
+def _fold(cfg, W, fmt, site, x, dtype, order, alt, ident, mutate):
+    """the +ln GEMM: fp32 statistics of the operand, the folded image, ln_c"""
+    x = _in(x, dtype)
+    dt = np.dtype(dtype).type
+    mu = x.mean(axis=-1, keepdims=True)
+    if alt:
+        var = np.maximum((x * x).mean(axis=-1, keepdims=True) - mu * mu, dt(0))
+    else:
+        var = ((x - mu) * (x - mu)).mean(axis=-1, keepdims=True)
+    rs = dt(1) / np.sqrt(var + dt(1e-5))
+    if mutate == "ln_s_unrounded":
+        w, c, _ = site_weights(cfg, W, site, _fmode(fmt, site, ident))
+        s = site_weights(cfg, W, site, "ident")[0].sum(axis=1).astype(dtype)
+        return (_mm(x, w.astype(dtype), None, order) - mu * s) * rs + c.astype(dtype)
+    return _fgemm(cfg, W, fmt, site, (x - mu) * rs, None, dtype, order, ident, None)
+
+
+def _tr_cfg(cfg):
+    tr = cfg.mimi.transformer
+    return tr, tr.num_heads, tr.d_model // tr.num_heads
+
+
+def fstage_P(cfg, W, fmt, lat, lat_prev, live, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """mimi_prologue_kernel (last argument 1): fp32 weights and arithmetic, bf16 output"""
+    return {"upsample": stage_P(cfg, W, lat, lat_prev, live, dtype, order, alt, mutate)}
+
+
+def fstage_Q(cfg, W, fmt, l, x, pos, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """layer l's +ln GEMM with EPI_QKV on its bf16 input x [B, T, C] at the positions pos [B, T]: the queries and the K / V
+    rows it writes, after RoPE, [B, T, H * 64] each; fp32 outputs (no output rounding)"""
+    _check(mutate, ("ln_s_unrounded", "rope_ring"))
+    tr, H, Dh = _tr_cfg(cfg)
+    B, T, _ = np.asarray(x).shape
+    qkv = _fold(cfg, W, fmt, ("qkv", l), x, dtype, order, alt, ident, mutate).reshape(B, T, 3, H, Dh)
+    rp = pos % engine_ring(cfg) if mutate == "rope_ring" else pos
+    q = _rope(qkv[:, :, 0], rp, float(tr.max_period), dtype)
+    k = _rope(qkv[:, :, 1], rp, float(tr.max_period), dtype)
+    return {"q": q.reshape(B, T, H * Dh), "k": k.reshape(B, T, H * Dh), "v": np.ascontiguousarray(qkv[:, :, 2]).reshape(B, T, H * Dh)}
+
+
+def engine_ring(cfg):
+    """slots of the engine's K / V ring (build_engine): the context in whole 16-row frames plus two frames being written"""
+    return ((cfg.mimi.transformer.context - 1 + 15) // 16 + 2) * 16
+
+
+def ring_positions(ring, pos0, T=16):
+    """[B, ring]: the position whose key slot s holds once the frame at positions pos0 .. pos0 + T - 1 is written (the
+    newest position of the slot's class), negative where the sequence has not written the slot"""
+    top = np.asarray(pos0, np.int64)[:, None] + T - 1
+    s = np.arange(ring)[None, :]
+    return top - ((top - s) % ring)
+
+
+def fstage_A(cfg, W, fmt, q, K, V, pos0, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """attention of the queries q [B, T, H * 64] (positions pos0[b] + t) over the rings K, V [B, ring, H * 64] as read back
+    after the Q launch: key position p is attended when 0 <= pos_q - p < context; -> attention output (bf16 output)"""
+    _check(mutate, ("window",))
+    tr, H, Dh = _tr_cfg(cfg)
+    B, T, C = np.asarray(q).shape
+    dt = np.dtype(dtype).type
+    q, K, V = (_in(a, dtype).reshape(B, -1, H, Dh) for a in (q, K, V))
+    pk = ring_positions(K.shape[1], pos0, T)  # [B, ring]
+    pq = np.asarray(pos0, np.int64)[:, None] + np.arange(T)[None, :]
+    delta = pq[:, :, None] - pk[:, None, :]
+    mask = (delta >= 0) & (delta < tr.context + (1 if mutate == "window" else 0)) & (pk >= 0)[:, None, :]
+    sc = np.einsum("bqhd,bkhd->bhqk", q, K) * dt(1.0 / math.sqrt(Dh))
+    sc = np.where(mask[:, None], sc, dt(-np.inf))
+    sc = sc - sc.max(axis=-1, keepdims=True)
+    pr = np.exp(sc)
+    pr = pr / pr.sum(axis=-1, keepdims=True)
+    Vz = np.where(np.isfinite(V), V, dt(0))  # slots never written may hold anything: their weight is exactly 0
+    out = np.einsum("bhqk,bkhd->bqhd", pr, Vz).reshape(B, T, C)
+    assert out.dtype == dt
+    return {"attn": out}
+
+
+def fstage_B(cfg, W, fmt, l, attn, x, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """x + layer_scale_1 * out_proj(attention output): EPI_RES with the layer scale, bf16 output"""
+    _check(mutate, ("no_ls",))
+    ls = 1 if mutate == "no_ls" else params(cfg, W, dtype).vec(_lp(l) + ".layer_scale_1.scale")
+    return {"resid": _in(x, dtype) + ls * _fgemm(cfg, W, fmt, ("out", l), attn, None, dtype, order, ident, None)}
+
+
+def fstage_C(cfg, W, fmt, l, resid, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """GELU(+ln GEMM of linear1), bf16 output"""
+    _check(mutate, ("tanh_gelu", "ln_s_unrounded"))
+    return {"ff": _gelu(_fold(cfg, W, fmt, ("ff1", l), resid, dtype, order, alt, ident, mutate), mutate == "tanh_gelu")}
+
+
+def fstage_D(cfg, W, fmt, l, ff, resid, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """x + layer_scale_2 * linear2(ff): the layer's output, bf16"""
+    _check(mutate, ("no_ls",))
+    ls = 1 if mutate == "no_ls" else params(cfg, W, dtype).vec(_lp(l) + ".layer_scale_2.scale")
+    return {"out": _in(resid, dtype) + ls * _fgemm(cfg, W, fmt, ("ff2", l), ff, None, dtype, order, ident, None)}
+
+
+def _elu_again(xx, fmt, scales, site, alt):
+    """the seeded defect "elu_twice": ELU applied once more to the (already ELU'd) operand's value"""
+    xs = xx.dtype.type(np.float32(scales[SC_IN[site]])) if fmt == "fp8" else xx.dtype.type(1)
+    return _elu(xx * xs, alt) / xs
+
+
+def fstage_S0(cfg, W, fmt, x, tail, scales=None, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """ELU(k7 conv of the transformer's bf16 output), gemm_h in both formats; output bf16 or e4m3 (scale 0)"""
+    _check(mutate, ("parity", "seqcut", "no_yinv", "wrap", "trunc"))
+    K = _layer_of(cfg, "conv", 0)[3]
+    cols = _im2col(_halo(_in(x, dtype), tail, K - 1, mutate), K)
+    return {"a0": _elu(_fgemm(cfg, W, fmt, ("conv0",), cols, scales, dtype, order, ident, None), alt)}
+
+
+def fstage_Cv(cfg, W, fmt, i, x, tail, scales=None, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """stage i's transposed conv of the ELU'd input (bf16 values or e4m3 codes): the raw output (bf16, the block's skip) and
+    ELU of it (bf16 or e4m3), [B, T * s, cout]"""
+    _check(mutate, ("parity", "seqcut", "elu_twice", "sc_in_next", "tensor_scale", "no_yinv", "wrap", "trunc"))
+    _, _, cout, _, s = _layer_of(cfg, "convtr", i)
+    xx = _halo(_in(x, dtype), tail, 1, mutate)
+    if mutate == "elu_twice":
+        xx = _elu_again(xx, fmt, scales, ("convtr", i), alt)
+    B, T = np.asarray(x).shape[:2]
+    v = _fgemm(cfg, W, fmt, ("convtr", i), np.concatenate([xx[:, 1:], xx[:, :-1]], axis=-1), scales, dtype, order, ident, mutate)
+    v = v.reshape(B, T * s, cout)
+    return {"raw": v, "elu": _elu(v, alt)}
+
+
+def fstage_Ra(cfg, W, fmt, i, x, tail, scales=None, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """stage i's k3 conv of the ELU'd transposed-conv output (tail: its last 2 rows of the previous frame), ELU'd: the
+    block's hidden activation (bf16 or e4m3)"""
+    _check(mutate, ("parity", "seqcut", "elu_twice", "tensor_scale", "no_yinv", "wrap", "trunc"))
+    xx = _halo(_in(x, dtype), tail, 2, mutate)
+    if mutate == "elu_twice":
+        xx = _elu_again(xx, fmt, scales, ("res_a", i), alt)
+    cols = _im2col(xx, 3)
+    return {"h": _elu(_fgemm(cfg, W, fmt, ("res_a", i), cols, scales, dtype, order, ident, mutate), alt)}
+
+
+def fstage_Rb(cfg, W, fmt, i, h, skip, scales=None, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """ELU(raw skip + 1x1 conv of the hidden activation): the block's output (bf16; e4m3 for i < 3 on the fp8 codec)"""
+    _check(mutate, ("skip_elu", "no_bias2", "tensor_scale", "no_yinv", "wrap", "trunc"))
+    skip = _in(skip, dtype)
+    v = _fgemm(cfg, W, fmt, ("res_b", i), h, scales, dtype, order, ident, mutate)
+    if mutate == "no_bias2":
+        v = v - site_weights(cfg, W, ("res_b", i), "ident")[1].astype(dtype)
+    return {"out": _elu((_elu(skip, alt) if mutate == "skip_elu" else skip) + v, alt)}
+
+
+def fstage_L(cfg, W, fmt, x, tail, dtype=F64, order="np", alt=False, mutate=None, ident=False):
+    """pcm_conv_h_kernel: the last conv with its fp32 weights on the bf16 block output -> fp32 PCM [B, T]"""
+    return {"pcm": stage_L(cfg, W, x, tail, dtype, order, alt, mutate)}
+
+
+def out_kind(fmt, site):
+    """(kind, scale index or None) of the output rounding of the launch at `site` ("raw": a transposed conv's skip copy)"""
+    if fmt == "fp8" and site in SC_OUT:
+        return "e4m3", SC_OUT[site]
+    return "bf16", None
+
+
+def fstage_e32(fn, kw):
+    """-> ({name: y64}, {name: E32}) of a format stage: the fp64 result and the worst float32 error of the same formulas
+    on the same inputs over F32_VARIANTS, per output.  From the reference alone."""
+    y64 = fn(**kw)
+    e32 = {k: 0.0 for k in y64}
+    for order, alt in F32_VARIANTS:
+        y32 = fn(**kw, dtype=F32, order=order, alt=alt)
+        for k, v in y32.items():
+            assert v.dtype == np.float32 and y64[k].dtype == np.float64 and v.shape == y64[k].shape, (k, v.dtype)
+            e32[k] = max(e32[k], float(np.abs(v.astype(np.float64) - y64[k]).max()))
+    return y64, e32
+
+
+class FChain:
+    """the format stages chained on their own ROUNDED outputs: the whole decoder on the CPU in the format's arithmetic.
+    decode(lat) -> the taps of the frame as the device holds them (bf16 values, e4m3 codes) under the engine's tap names.
+    fmt "fp8" takes `scales` (16 floats), e.g. from `calibrate`"""
+
+    def __init__(self, cfg, W, B, fmt, scales=None, mutate=None, mutate_at=None):
+        assert fmt in FMTS and (fmt == "bf16" or scales is not None)
+        self.cfg, self.W, self.B, self.fmt, self.scales = cfg, W, B, fmt, scales
+        self.mutate, self.mutate_at = mutate, mutate_at  # a seeded defect at one launch (stage name)
+        tr, H, Dh = _tr_cfg(cfg)
+        self.L, self.ring = tr.num_layers, engine_ring(cfg)
+        self.K = [np.zeros((B, self.ring, H * Dh)) for _ in range(self.L)]
+        self.V = [np.zeros((B, self.ring, H * Dh)) for _ in range(self.L)]
+        self.frame, self.start = 0, np.zeros(B, np.int64)
+        self.lat_prev, self.prev = None, None
+
+    def reset_row(self, row):
+        self.start[row] = self.frame
+
+    def _m(self, stage):
+        return self.mutate if stage == self.mutate_at else None
+
+    def _rnd(self, pre, site, stage):
+        kind, k = out_kind(self.fmt, site)
+        return out_round(pre, kind, None if k is None else yinv_of(self.scales, k), self._m(stage))
+
+    def decode(self, lat):
+        cfg, W, fmt, sc = self.cfg, self.W, self.fmt, self.scales
+        live = self.start < self.frame
+        pos0 = 16 * (self.frame - self.start)
+        pos = pos0[:, None] + np.arange(16)[None, :]
+        t = {"latent": np.asarray(lat), "pos0": pos0}
+        x = bf16(fstage_P(cfg, W, fmt, lat, lat if self.lat_prev is None else self.lat_prev, live)["upsample"])
+        t["upsample"] = t["tr_in0"] = x
+        for l in range(self.L):
+            qkv = fstage_Q(cfg, W, fmt, l, x, pos, mutate=self._m(f"Q{l}"))
+            slots = pos % self.ring
+            for b in range(self.B):
+                self.K[l][b, slots[b]] = out_round(qkv["k"][b], "f32")
+                self.V[l][b, slots[b]] = out_round(qkv["v"][b], "f32")
+            t[f"tr_q{l}"] = out_round(qkv["q"], "f32")
+            t[f"tr_k{l}"], t[f"tr_v{l}"] = self.K[l].copy(), self.V[l].copy()
+            Kr = self.K[0] if self._m(f"A{l}") == "k_layer0" else self.K[l]
+            t[f"tr_attn{l}"] = bf16(fstage_A(cfg, W, fmt, t[f"tr_q{l}"], Kr, self.V[l], pos0)["attn"])
+            t[f"tr_resid{l}"] = bf16(fstage_B(cfg, W, fmt, l, t[f"tr_attn{l}"], x)["resid"])
+            t[f"tr_ff{l}"] = bf16(fstage_C(cfg, W, fmt, l, t[f"tr_resid{l}"], mutate=self._m(f"C{l}"))["ff"])
+            x = bf16(fstage_D(cfg, W, fmt, l, t[f"tr_ff{l}"], t[f"tr_resid{l}"])["out"], trunc=self._m(f"D{l}") == "trunc")
+            t[f"tr_in{l + 1}" if l < self.L - 1 else "dec_tr"] = x
+        keep = live[:, None, None].astype(np.float64)
+
+        def tail(name, n):
+            return np.zeros_like(t[name][:, :n]) if self.prev is None else self.prev[name][:, -n:] * keep
+
+        kw = dict(scales=sc)
+        t["seanet0"] = self._rnd(fstage_S0(cfg, W, fmt, t["dec_tr"], tail("dec_tr", 6), mutate=self._m("S0"), **kw)["a0"], ("conv0",), "S0")
+        src = "seanet0"
+        for i in (1, 2, 3):
+            c = fstage_Cv(cfg, W, fmt, i, t[src], tail(src, 1), mutate=self._m(f"Cv{i}"), **kw)
+            t[f"seanet{3 * i - 1}"] = bf16(c["raw"])
+            t[f"seanet_c{i}"] = self._rnd(c["elu"], ("convtr", i), f"Cv{i}")
+            h = fstage_Ra(cfg, W, fmt, i, t[f"seanet_c{i}"], tail(f"seanet_c{i}", 2), mutate=self._m(f"Ra{i}"), **kw)["h"]
+            t[f"seanet_h{i}"] = self._rnd(h, ("res_a", i), f"Ra{i}")
+            o = fstage_Rb(cfg, W, fmt, i, t[f"seanet_h{i}"], t[f"seanet{3 * i - 1}"], mutate=self._m(f"Rb{i}"), **kw)["out"]
+            t[f"seanet{3 * i}"] = self._rnd(o, ("res_b", i), f"Rb{i}")
+            src = f"seanet{3 * i}"
+        t["pcm"] = out_round(fstage_L(cfg, W, fmt, t["seanet9"], tail("seanet9", 2))["pcm"], "f32")
+        self.prev, self.lat_prev = t, np.asarray(lat)
+        self.frame += 1
+        return t
+
+
+# the tap whose amax fixes each activation scale of the fp8 codec (calibrate_fp8_codec scans the bf16 codec's buffers)
+SCALE_TAP = {0: "seanet0", 1: "seanet_c1", 2: "seanet_h1", 3: "seanet3", 4: "seanet_c2", 5: "seanet_h2", 6: "seanet6",
+             7: "seanet_c3", 8: "seanet_h3"}
+
+
+def scales_from_amax(amax):
+    """2.0f * amax / 448.0f in fp32 per used index, 1 elsewhere (calibrate_fp8_codec)"""
+    out = np.ones(16, np.float32)
+    for k, a in amax.items():
+        if a > 0:
+            out[k] = f32_div(np.float32(2.0) * np.float32(a), 448.0)
+    return out
+
+
+def calibrate(cfg, W, latents):
+    """the reference's own calibration: the bf16 chain on latents [F, B, ldim], amax of every SCALE_TAP over all frames,
+    scale = 2 amax / 448"""
+    ch = FChain(cfg, W, latents.shape[1], "bf16")
+    amax = {k: 0.0 for k in SCALE_TAP}
+    for lat in latents:
+        t = ch.decode(lat)
+        for k, name in SCALE_TAP.items():
+            amax[k] = max(amax[k], float(np.abs(t[name]).max()))
+    return scales_from_amax(amax)
+
+
+# ---- the bound of tests/test_gpu_codec_formats.py, shared with the seeded defects of the CPU test ----------------------
+def bf16_ulp(v):
+    _, e = np.frexp(np.maximum(np.abs(v), 2.0 ** -126))
+    return np.ldexp(1.0, e - 8)
+
+
+def ratio_of(got, y64, tol, kind, yinv=None):
+    """worst distance of `got` from the bounded interval [y64 - tol, y64 + tol] after the output rounding, in units of the
+    bound (<= 1 passes); inf for an e4m3 code outside the neighbours of the interval's ends"""
+    got = np.asarray(got).astype(np.float64)
+    assert got.shape == y64.shape, (got.shape, y64.shape)
+    if not np.isfinite(got).all():
+        return float("inf")
+    err = np.abs(got - y64)
+    if kind == "f32":
+        return float((err / tol).max())
+    if kind == "bf16":
+        return float((np.maximum(err - 0.5 * bf16_ulp(got), 0) / tol).max())
+    yinv = float(yinv)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+    lo, _ = _CR.e4m3_neighbours(t((y64 - tol) * yinv))
+    _, hi = _CR.e4m3_neighbours(t((y64 + tol) * yinv))
+    lo, hi = lo.numpy(), hi.numpy()
+    if not ((got >= lo) & (got <= hi)).all():
+        return float("inf")
+    sat_hi, sat_lo = (y64 - tol) * yinv >= _CR.E4M3_MAX, (y64 + tol) * yinv <= -_CR.E4M3_MAX
+    if not ((got[sat_hi] == _CR.E4M3_MAX).all() and (got[sat_lo] == -_CR.E4M3_MAX).all()):
+        return float("inf")
+    d = np.abs(got / yinv - np.clip(y64, -_CR.E4M3_MAX / yinv, _CR.E4M3_MAX / yinv))
+    w = tol + (hi - lo) / yinv
+    return float(np.where(w > 0, d / np.maximum(w, 1e-300), 0.0).max())
+
+
+def f8_bound_codes(cx, cw, s):
+    """codec_ref.f8_mfma_bound on the raw e4m3 codes cx [M][K], cw [N][K] and the operands' scale s [N], in float32: a
+    product of two codes has at most 8 significant bits and the group quantum is a power of two, so every term is exact
+    in float32; only the sum over K terms rounds, which the factor 1 + K 2^-23 covers (an upper bound of that function's
+    float64 result, within 1 + K 2^-22 of it: tests/test_codec_formats_reference_cpu.py).  Half the memory traffic and no
+    logarithm: the GPU test visits every product of every fp8 GEMM."""
+    G, KEEP = _CR.F8_GROUP, _CR.F8_KEEP
+    X = torch.from_numpy(np.ascontiguousarray(np.abs(cx), dtype=np.float32))
+    Wc = torch.from_numpy(np.ascontiguousarray(np.abs(cw), dtype=np.float32))
+    M, K = X.shape
+    N = Wc.shape[0]
+    wg = Wc.reshape(1, N, K // G, G)
+    out = torch.empty(M, N, dtype=torch.float32)
+    step = max(1, (1 << 25) // (N * K))
+    for r0 in range(0, M, step):
+        p = X[r0:r0 + step].reshape(-1, 1, K // G, G) * wg
+        mx = p.amax(dim=-1, keepdim=True)
+        _, e = torch.frexp(mx)  # mx = m 2^e, 0.5 <= m < 1: floor(log2 mx) = e - 1
+        q = torch.where(mx > 0, torch.ldexp(torch.ones_like(mx), e - 1 - KEEP), torch.zeros_like(mx))
+        out[r0:r0 + step] = torch.minimum(p, q).sum(dim=(-1, -2))
+    return out.to(torch.float64).numpy() * (1 + K * 2.0 ** -23) * np.asarray(s, np.float64)[None, :]
+
+
+def f8_extra(cfg, W, site, cols, scales, y64, mutate=None):
+    """what the e4m3 MFMA drops at this site (codec_ref.f8_mfma_bound's model on the codes of the launch's operands, see
+    f8_bound_codes) plus the fp8 epilogue's two fp32 roundings, shaped as the site's output before any reshape"""
+    w, _, ws = site_weights(cfg, W, site, "fp8")
+    xs = float(np.float32(scales[SC_IN[site]]))
+    b = f8_bound_codes(cols.reshape(-1, cols.shape[-1]), w, ws.astype(np.float64) * xs)
+    return b.reshape(y64.shape) + 2 * 2.0 ** -24 * np.abs(y64)

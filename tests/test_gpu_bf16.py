@@ -2,7 +2,9 @@
 build's fp32 codec.  BASELINE.json config #5 has NO reference counterpart for the codec (docs/quantization.md:76: "Mimi
 is never quantized"), so parity is UNPINNED; quality is reported the way the reference's own quantisation harness
 does: SNR against the full-precision output (scripts/evaluate_quantization.py:215-228).  EOS decisions / frame counts
-come from the FlowLM, which stays fp32: they are identical by construction and checked end to end.  `-m gpu`."""
+come from the FlowLM, which stays fp32: they are identical by construction and checked end to end.  `-m gpu`.
+The SNR floors here report the format's quality; the decoder's CORRECTNESS is judged launch by launch against fp64 in
+tests/test_gpu_codec_formats.py."""
 
 import numpy as np
 import pytest

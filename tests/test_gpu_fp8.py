@@ -4,7 +4,8 @@ build's fp32 codec and against the numpy oracle.  BASELINE.json configs[4] names
 NO counterpart (docs/quantization.md:67-76: Mimi is never quantised), so parity is UNPINNED and quality is reported the way
 the reference's quantisation harness does: SNR against the full-precision output (scripts/evaluate_quantization.py:215-228).
 EOS decisions / frame counts come from the FlowLM, which is untouched: identical by construction, checked end to end.
-`-m gpu`."""
+The SNR floors here report the format's quality; the decoder's CORRECTNESS, its scale indices and its calibration are judged
+launch by launch against fp64 in tests/test_gpu_codec_formats.py.  `-m gpu`."""
 
 from pathlib import Path
 
