@@ -707,6 +707,10 @@ int ptts_timer_stop_ms(ptts_engine *e, void *stream, float *h_ms);
  *                                              res_b<i>; k = tap C + c in the packer's tap order (a transposed conv: tap 0 the
  *                                              previous input row); bf16 values, or at the fp8 convolutions of an fp8 engine the
  *                                              e4m3 codes, whose per-row scales are "ws_<site>" [1, N]
+ *   "wh_<site>", "wl_<site>" [N, taps C]       the hi = bf16(w) and lo = bf16(w - hi) images a PTTS_CODEC_SPLIT engine's
+ *                                              launches multiply by, same sites and tap order (refused on every other engine)
+ *   "lns_<site>", "lnc_<site>" [1, N]          the LayerNorm fold vectors ln_s, ln_c of site = qkv<l> | ff1<l> of the fp32 and
+ *                                              split-bf16 codecs (fp32; refused on the reduced-precision codecs)
  *   "f8_scales"           [1, 16]            the activation scales of an fp8 codec engine (refused on any other)
  *   "calib_latent<f>"     [8, ldim]            f = 0..5, on a state of batch 8: the latents the fp8 calibration run decoded
  *                                              in frame f, generated again by the same kernel

@@ -31,6 +31,7 @@ static __global__ void dbg_from_codec_kernel(const void *src, float *dst, int M,
 }
 
 static __global__ void dbg_unpack_codec_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KBt);
+static __global__ void dbg_unpack_weight_kernel(const void *img, const float *scale, int fmt, float *dst, int N, int KF);
 // ptts_debug_read on a Mimi state: the element type of a tap, and the two buffers that are fp32 in every codec format
 enum { TAP_F32, TAP_BF16, TAP_E4M3 };
 // the query blocks [B * H][QB][4][64 lanes][4] -> [B * Tq][H * 64] (Tq = 16 QB)
@@ -179,12 +180,18 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
       dbg_from_kv_kernel<<<cdiv((long)M * K, 256), 256, 0, st>>>(n[3] == 'k' ? s->K(l) : s->V(l), d_out, B, c.m_heads, e->ring);
       return plain(M, K);
     }
-    else if (n.compare(0, 2, "w_") == 0 || n.compare(0, 3, "ws_") == 0) {
+    else if (n.compare(0, 2, "w_") == 0 || n.compare(0, 3, "ws_") == 0 || n.compare(0, 3, "wh_") == 0 || n.compare(0, 3, "wl_") == 0 ||
+             n.compare(0, 4, "lns_") == 0 || n.compare(0, 4, "lnc_") == 0) {
       // the weight image a reduced-precision launch multiplies by, [16 NT][ntaps * C] (k = tap * C + c in the packer's tap
-      // order): bf16 values, or at the fp8 convolutions of an fp8 engine e4m3 codes, whose per-row scales are "ws_<site>"
-      if (!e->codec_bf16) return fail(-1, "debug_read: " + n + ": the fp32 codec has no reduced-precision weight image");
+      // order): bf16 values, or at the fp8 convolutions of an fp8 engine e4m3 codes, whose per-row scales are "ws_<site>";
+      // "wh_<site>" / "wl_<site>": the hi and lo images of a split-bf16 engine, in the same order; "lns_<site>" /
+      // "lnc_<site>": the LayerNorm fold vectors of a +ln site of the fp32 and split-bf16 codecs, [1][16 NT]
+      const bool split_img = n[0] == 'w' && (n[1] == 'h' || n[1] == 'l'), fold = n[0] == 'l';
+      if (split_img && !e->codec_split) return fail(-1, "debug_read: " + n + ": only a split-bf16 engine has hi / lo weight images");
+      if (fold && e->codec_bf16) return fail(-1, "debug_read: " + n + ": the reduced-precision codecs keep their own fold vectors");
+      if (!split_img && !fold && !e->codec_bf16) return fail(-1, "debug_read: " + n + ": the fp32 codec has no reduced-precision weight image");
       const bool scale = n[1] == 's';
-      const size_t off = scale ? 3 : 2;
+      const size_t off = fold ? 4 : scale || split_img ? 3 : 2;
       const std::string site = n.substr(off);
       const Lin *L = nullptr;
       bool conv = false;  // a SEANet convolution that the fp8 codec runs on e4m3
@@ -206,6 +213,19 @@ extern "C" int64_t ptts_debug_read(ptts_engine *e, void *state, int32_t is_mimi,
       else if ((i = stage("res_a")) >= 0) { L = &e->res_a[i]; conv = true; }
       else if ((i = stage("res_b")) >= 0) { L = &e->res_b[i]; conv = true; }
       if (!L) return fail(-1, "unknown buffer " + n);
+      if (fold) {
+        if (!L->ln_s || !L->ln_c) return fail(-1, "debug_read: " + n + ": the site folds no LayerNorm");
+        if (capacity < L->NT * 16) return fail(-1, "debug_read: capacity too small");
+        HIPCHK(hipMemcpyAsync(d_out, n[2] == 's' ? L->ln_s : L->ln_c, (size_t)L->NT * 16 * 4, hipMemcpyDeviceToDevice, st));
+        return plain(1, L->NT * 16);
+      }
+      if (split_img) {
+        if (!L->wsh || !L->wsl) return fail(-1, "debug_read: " + n + ": the site has no split image");
+        const long nk = (long)L->NT * 16 * L->KF * 16;
+        if (nk > capacity) return fail(-1, "debug_read: capacity too small");
+        dbg_unpack_weight_kernel<<<cdiv(nk, 256), 256, 0, st>>>(n[1] == 'h' ? L->wsh : L->wsl, nullptr, 2, d_out, L->NT * 16, L->KF);
+        return plain(L->NT * 16, L->KF * 16);
+      }
       const bool f8w = conv && e->codec_fp8;
       if (scale && !f8w) return fail(-1, "debug_read: " + n + ": the site has no e4m3 weight image in this codec format");
       const int Nn = L->NT * 16, KBt = (L->C / 32) * L->ntaps;

@@ -68,6 +68,15 @@ MUTANTS = {
     "tanh_gelu": "the tanh approximation of GELU instead of the erf form",
 }
 
+# seeded defects of the split-bf16 matrix product (`_mms`, `_ln_mm`; tests/test_codec_split_reference_cpu.py)
+SPLIT_MUTANTS = {
+    "no_wlo": "the xh.wl term dropped (the weight's lo image never multiplied)",
+    "no_xlo": "the xl.wh term dropped (the activation's residual never multiplied)",
+    "fp32_w": "the site multiplies by the fp32 matrix instead of hi + lo (a silent fall-back to the fp32 kernel)",
+    "lns_hi": "the LayerNorm fold's ln_s summed from the hi image alone",
+    "lo_of_x_trunc": "xl formed from a truncated xh while the product uses the rounded xh",
+}
+
 CONFIG_NAMES = ("tiny", "tiny1", "nf64")
 _CONFIG_EDITS = {"tiny": {}, "tiny1": dict(mimi_layers=1), "nf64": dict(n_filters=64, mimi_layers=1)}
 SEQ_ELEMS = 16384  # outputs the sequential-order evaluation covers per GEMM (at least 32 rows)
@@ -139,8 +148,11 @@ def _seq_rows(M, N):
     return np.unique(np.linspace(0, M - 1, n).astype(np.int64))
 
 
-def _mm(x, w, b, order):
-    """x [..., K] @ w[N, K]^T + b in x's dtype; order "seq": rows `_seq_rows` by a plain sequential sum over k"""
+def _mm(x, w, b, order, split=None):
+    """x [..., K] @ w[N, K]^T + b in x's dtype; order "seq": rows `_seq_rows` by a plain sequential sum over k.
+    split: None, or the product in the split-bf16 model (`_mms`)"""
+    if split is not None:
+        return _mms(x, w, b, order, split)
     lead, K = x.shape[:-1], x.shape[-1]
     X = np.ascontiguousarray(x.reshape(-1, K))
     y = X @ w.T
@@ -157,6 +169,83 @@ def _mm(x, w, b, order):
         y = y + b
     assert y.dtype == x.dtype
     return y.reshape(lead + (w.shape[0],))
+
+
+def split_parts(v, lo_of_trunc=False):
+    """fp32 v -> (hi, lo) as float64: hi = bf16(v), lo = bf16(v - hi), round to nearest even (v - hi is exact in fp32:
+    to_bf16x4(a - from_bf16x4(ah)), ptts_split.hip / ptts_kernels.h).  lo_of_trunc (a seeded defect): lo formed from the
+    TRUNCATED hi while the rounded hi is returned"""
+    v32 = np.ascontiguousarray(v, dtype=np.float32)
+    hi = bf16(v32)
+    base = bf16(v32, trunc=True) if lo_of_trunc else hi
+    return hi, bf16((v32.astype(np.float64) - base).astype(np.float32))
+
+
+_WSPLIT = {}
+
+
+def _wsplit(w):
+    """the hi / lo images of a weight matrix in its own dtype (remembered per array)"""
+    if id(w) not in _WSPLIT:
+        hi, lo = split_parts(w)
+        _WSPLIT[id(w)] = (w, hi.astype(w.dtype), lo.astype(w.dtype))
+    return _WSPLIT[id(w)][1:]
+
+
+def _mms(x, w, b, order, split=""):
+    """the matrix product of gemm_kernel<.., WF = 3> (include/ptts.h PTTS_CODEC_SPLIT, the header of ptts_split.hip): with
+    xh = bf16(x), xl = bf16(x - xh), wh = bf16(w), wl = bf16(w - wh):  xh.wh + xl.wh + xh.wl  (no xl.wl term), summed in x's
+    dtype; every product of two bf16 values is exact in float32.  split: "" or a SPLIT_MUTANTS name"""
+    assert split == "" or split in SPLIT_MUTANTS, split
+    if split == "fp32_w":
+        return _mm(x, w, b, order)
+    xh, xl = (a.astype(x.dtype) for a in split_parts(x, split == "lo_of_x_trunc"))
+    wh, wl = _wsplit(w)
+    acc = _mm(xh, wh, None, order)
+    if split != "no_xlo":
+        acc = acc + _mm(xl, wh, None, order)
+    if split != "no_wlo":
+        acc = acc + _mm(xh, wl, None, order)
+    return acc if b is None else acc + b
+
+
+def _ln_site(cfg, W, site, dtype):
+    """(in-projection or linear1 weight, LayerNorm gain, LayerNorm bias) of the +ln site ("qkv" | "ff1", layer)"""
+    P, p = params(cfg, W, dtype), f"mimi.decoder_transformer.transformer.layers.{site[1]}"
+    wn, nn = (".self_attn.in_proj.weight", ".norm1") if site[0] == "qkv" else (".linear1.weight", ".norm2")
+    return P, p + wn, P.vec(p + wn), P.vec(p + nn + ".weight"), P.vec(p + nn + ".bias")
+
+
+def _stats(x, alt):
+    dt = x.dtype.type
+    mu = x.mean(axis=-1, keepdims=True)
+    if alt:
+        var = np.maximum((x * x).mean(axis=-1, keepdims=True) - mu * mu, dt(0))
+    else:
+        var = ((x - mu) * (x - mu)).mean(axis=-1, keepdims=True)
+    return mu, dt(1) / np.sqrt(var + dt(1e-5))
+
+
+def fold_image(cfg, W, site, dtype):
+    """the matrix a +ln site multiplies by: the FLOAT32 product w * ln_w (pack_lin), in `dtype`"""
+    _, key, w0, g, _ = _ln_site(cfg, W, site, F32)
+    return params(cfg, W, dtype).get(key + "#fold", lambda: w0 * g[None, :])
+
+
+def _ln_mm(cfg, W, site, x, dtype, order, alt, split):
+    """linear(norm(x)) of a +ln site, no bias.  split None: LayerNorm, then the product.  Else what a split engine's +ln
+    launch evaluates: statistics mu, rs of the UNROUNDED row, the split product of the raw row with the folded image, then
+    (acc - ln_s mu) rs + ln_c with ln_s = sum_k of the fp32 image and ln_c = W ln_b (fold_ln_kernel; build_engine leaves
+    both as the fp32 codec has them).  "lns_hi" (a seeded defect): ln_s summed from the hi image alone"""
+    _, _, w0, g, beta = _ln_site(cfg, W, site, dtype)
+    if split is None:
+        return _mm(_layer_norm(x, g, beta, alt), w0, None, order)
+    wf = fold_image(cfg, W, site, dtype)
+    mu, rs = _stats(x, alt)
+    acc = _mms(x, wf, None, order, "" if split == "lns_hi" else split)
+    s = (_wsplit(wf)[0] if split == "lns_hi" else wf).sum(axis=1)
+    c = _mm(beta[None, :], w0, None, order)[0]
+    return (acc - mu * s) * rs + c
 
 
 def _elu(x, alt):
@@ -251,12 +340,13 @@ def _rope(x, pos, max_period, dtype):
 _TR_MEMO = {}
 
 
-def _transformer(cfg, W, ups, start, dtype, order, alt, mutate, n_layers=None):
+def _transformer(cfg, W, ups, start, dtype, order, alt, mutate, n_layers=None, split=None):
     """the decoder transformer on the frames `ups` (upsample taps [B, 16, C] of frames 0 .. f), streaming: every frame
     attends to the keys of the frames before it.  start[b]: the frame sequence b's utterance began at (position 0; keys
     of earlier frames are not its own).  -> the last layer's taps of frame f.
     A pure function of its arguments; the K / V of a prefix of frames it has already seen (the same arrays at the same
-    positions) are remembered, so that judging frame after frame costs one frame each."""
+    positions) are remembered, so that judging frame after frame costs one frame each.
+    split: None, or the four GEMMs of every layer in the split-bf16 model (`_mms`, `_fold_split`; "" or a SPLIT_MUTANTS name)"""
     P = params(cfg, W, dtype)
     tr = cfg.mimi.transformer
     H, Dh, ctx = tr.num_heads, tr.d_model // tr.num_heads, tr.context
@@ -264,7 +354,7 @@ def _transformer(cfg, W, ups, start, dtype, order, alt, mutate, n_layers=None):
     B, T, C = np.asarray(ups[0]).shape
     start = np.zeros(B, np.int64) if start is None else np.asarray(start, np.int64)
     dt = np.dtype(dtype).type
-    key = (id(W), np.dtype(dtype).str, order, alt, mutate, L)
+    key = (id(W), np.dtype(dtype).str, order, alt, mutate, L, split)
     done = []  # per frame: dict(pos, kv = [(k, v) per layer], taps)
     for f, u in enumerate(ups):
         new = f >= start  # [B]: the frame belongs to the sequence's current utterance (else to the one before it)
@@ -278,8 +368,8 @@ def _transformer(cfg, W, ups, start, dtype, order, alt, mutate, n_layers=None):
         fr = dict(pos=pos, kv=[])
         for l in range(L):
             p = f"mimi.decoder_transformer.transformer.layers.{l}"
-            h = _layer_norm(x, P.vec(p + ".norm1.weight"), P.vec(p + ".norm1.bias"), alt)
-            qkv = _mm(h, P.vec(p + ".self_attn.in_proj.weight"), None, order).reshape(B, T, 3, H, Dh)
+            x_in = x
+            qkv = _ln_mm(cfg, W, ("qkv", l), x, dtype, order, alt, split).reshape(B, T, 3, H, Dh)
             q = _rope(qkv[:, :, 0], rp, float(tr.max_period), dtype)
             fr["kv"].append((_rope(qkv[:, :, 1], rp, float(tr.max_period), dtype), qkv[:, :, 2]))
             hist = done + [fr]
@@ -296,11 +386,10 @@ def _transformer(cfg, W, ups, start, dtype, order, alt, mutate, n_layers=None):
             pr = np.exp(sc)
             pr = pr / pr.sum(axis=-1, keepdims=True)
             ao = np.einsum("bhqk,bkhd->bqhd", pr, V).reshape(B, T, C)
-            resid = x + P.vec(p + ".layer_scale_1.scale") * _mm(ao, P.vec(p + ".self_attn.out_proj.weight"), None, order)
-            ff = _gelu(_mm(_layer_norm(resid, P.vec(p + ".norm2.weight"), P.vec(p + ".norm2.bias"), alt),
-                           P.vec(p + ".linear1.weight"), None, order))
-            x = resid + P.vec(p + ".layer_scale_2.scale") * _mm(ff, P.vec(p + ".linear2.weight"), None, order)
-        fr["taps"] = dict(attn=ao, resid=resid, ff=ff, out=x)
+            resid = x + P.vec(p + ".layer_scale_1.scale") * _mm(ao, P.vec(p + ".self_attn.out_proj.weight"), None, order, split)
+            ff = _gelu(_ln_mm(cfg, W, ("ff1", l), resid, dtype, order, alt, split))
+            x = resid + P.vec(p + ".layer_scale_2.scale") * _mm(ff, P.vec(p + ".linear2.weight"), None, order, split)
+        fr["taps"] = dict(attn=ao, resid=resid, ff=ff, out=x, inp=x_in)
         done = done + [fr]
         if len(_TR_MEMO) > 256:
             _TR_MEMO.clear()
@@ -310,43 +399,42 @@ def _transformer(cfg, W, ups, start, dtype, order, alt, mutate, n_layers=None):
     return taps
 
 
-def stage_A(cfg, W, ups, start=None, dtype=F64, order="np", alt=False, mutate=None):
+def stage_A(cfg, W, ups, start=None, dtype=F64, order="np", alt=False, mutate=None, split=None):
     """one-layer configurations: LayerNorm + in_proj + RoPE + the K / V history + attention -> attention output"""
     _check(mutate, ("rope_ring", "window"))
     assert cfg.mimi.transformer.num_layers == 1, "stage A is defined on the one-layer configurations"
-    return _transformer(cfg, W, ups, start, dtype, order, alt, mutate)["attn"]
+    return _transformer(cfg, W, ups, start, dtype, order, alt, mutate, split=split)["attn"]
 
 
-def stage_T(cfg, W, ups, start=None, dtype=F64, order="np", alt=False, mutate=None):
+def stage_T(cfg, W, ups, start=None, dtype=F64, order="np", alt=False, mutate=None, split=None):
     """the whole decoder transformer: upsample history -> dec_tr"""
     _check(mutate, ("rope_ring", "window"))
-    return _transformer(cfg, W, ups, start, dtype, order, alt, mutate)["out"]
+    return _transformer(cfg, W, ups, start, dtype, order, alt, mutate, split=split)["out"]
 
 
 def _last(cfg):
     return f"mimi.decoder_transformer.transformer.layers.{cfg.mimi.transformer.num_layers - 1}"
 
 
-def stage_B(cfg, W, attn, x, dtype=F64, order="np", alt=False, mutate=None):
-    """x + layer_scale_1 * out_proj(attention output) (one-layer configurations: x = upsample)"""
+def stage_B(cfg, W, attn, x, dtype=F64, order="np", alt=False, mutate=None, split=None):
+    """x + layer_scale_1 * out_proj(attention output) of the last layer (one-layer configurations: x = upsample)"""
     _check(mutate, ("no_ls",))
     P, p = params(cfg, W, dtype), _last(cfg)
-    return _in(x, dtype) + (1 if mutate == "no_ls" else P.vec(p + ".layer_scale_1.scale")) * _mm(_in(attn, dtype), P.vec(p + ".self_attn.out_proj.weight"), None, order)
+    return _in(x, dtype) + (1 if mutate == "no_ls" else P.vec(p + ".layer_scale_1.scale")) * _mm(_in(attn, dtype), P.vec(p + ".self_attn.out_proj.weight"), None, order, split)
 
 
-def stage_C(cfg, W, resid, dtype=F64, order="np", alt=False, mutate=None):
+def stage_C(cfg, W, resid, dtype=F64, order="np", alt=False, mutate=None, split=None):
     """GELU(linear1(norm2(x))) of the last layer"""
     _check(mutate, ("tanh_gelu",))
-    P, p = params(cfg, W, dtype), _last(cfg)
-    h = _layer_norm(_in(resid, dtype), P.vec(p + ".norm2.weight"), P.vec(p + ".norm2.bias"), alt)
-    return _gelu(_mm(h, P.vec(p + ".linear1.weight"), None, order), mutate == "tanh_gelu")
+    l = cfg.mimi.transformer.num_layers - 1
+    return _gelu(_ln_mm(cfg, W, ("ff1", l), _in(resid, dtype), dtype, order, alt, split), mutate == "tanh_gelu")
 
 
-def stage_D(cfg, W, ff, resid, dtype=F64, order="np", alt=False, mutate=None):
+def stage_D(cfg, W, ff, resid, dtype=F64, order="np", alt=False, mutate=None, split=None):
     """x + layer_scale_2 * linear2(ff) of the last layer: the transformer's output"""
     _check(mutate, ("no_ls",))
     P, p = params(cfg, W, dtype), _last(cfg)
-    return _in(resid, dtype) + (1 if mutate == "no_ls" else P.vec(p + ".layer_scale_2.scale")) * _mm(_in(ff, dtype), P.vec(p + ".linear2.weight"), None, order)
+    return _in(resid, dtype) + (1 if mutate == "no_ls" else P.vec(p + ".layer_scale_2.scale")) * _mm(_in(ff, dtype), P.vec(p + ".linear2.weight"), None, order, split)
 
 
 def _layer_of(cfg, kind, i):
@@ -356,16 +444,16 @@ def _layer_of(cfg, kind, i):
     return idx, cin, cout, k, stride
 
 
-def stage_S0(cfg, W, x, tail, dtype=F64, order="np", alt=False, mutate=None):
+def stage_S0(cfg, W, x, tail, dtype=F64, order="np", alt=False, mutate=None, split=None):
     """ELU(k7 streaming conv of the transformer's output); tail: the last 6 rows of the previous frame's dec_tr"""
     _check(mutate, ("parity", "seqcut"))
     P = params(cfg, W, dtype)
     idx, _, _, K, _ = _layer_of(cfg, "conv", 0)
     w, b = P.conv(f"mimi.decoder.model.{idx}.conv")
-    return _elu(_mm(_im2col(_halo(_in(x, dtype), tail, K - 1, mutate), K), w, b, order), alt)
+    return _elu(_mm(_im2col(_halo(_in(x, dtype), tail, K - 1, mutate), K), w, b, order, split), alt)
 
 
-def stage_Cv(cfg, W, i, x, tail, dtype=F64, order="np", alt=False, mutate=None):
+def stage_Cv(cfg, W, i, x, tail, dtype=F64, order="np", alt=False, mutate=None, split=None):
     """stage i's transposed conv (kernel 2s, stride s) of the ELU'd input: raw output [B, T * s, cout]; tail: the last
     row of the previous frame's input"""
     _check(mutate, ("parity", "seqcut", "elu_twice"))
@@ -376,7 +464,7 @@ def stage_Cv(cfg, W, i, x, tail, dtype=F64, order="np", alt=False, mutate=None):
     if mutate == "elu_twice":
         xx = _elu(xx, alt)
     B, T = x.shape[0], x.shape[1]
-    y = _mm(np.concatenate([xx[:, 1:], xx[:, :-1]], axis=-1), w, np.tile(b, s), order)
+    y = _mm(np.concatenate([xx[:, 1:], xx[:, :-1]], axis=-1), w, np.tile(b, s), order, split)
     return y.reshape(B, T * s, cout)
 
 
@@ -504,10 +592,14 @@ class Chain:
     it is `np_oracle.MimiDecoder.decode` (tests/test_mimi_reference_cpu.py); in float64 the reference of the decodes
     whose intermediate buffers stay on chip."""
 
-    def __init__(self, cfg, W, B, dtype=F64, order="np", alt=False, fused_tail=False):
+    def __init__(self, cfg, W, B, dtype=F64, order="np", alt=False, fused_tail=False, split=None, split_res=()):
         self.cfg, self.W, self.B = cfg, W, B
         self.kw = dict(dtype=dtype, order=order, alt=alt)
         self.fused_tail = fused_tail  # PCM through stage R3L instead of R3 and L
+        # a split-bf16 engine: the transformer's GEMMs, conv0, the transposed convs and the residual blocks of the stages
+        # in split_res (the unfused Ra / Rb pair) in the split model, everything else as the fp32 stages
+        self.split, self.split_res = split, tuple(split_res)
+        assert split is None or not fused_tail
         self.frame = 0
         self.start = np.zeros(B, np.int64)
         self.ups, self.lat_prev, self.prev = [], None, None
@@ -522,8 +614,10 @@ class Chain:
         t = {"latent": np.asarray(lat)}
         t["upsample"] = stage_P(cfg, W, lat, lat if self.lat_prev is None else self.lat_prev, live, **kw)
         self.ups.append(t["upsample"])
-        tr = _transformer(cfg, W, self.ups, self.start, mutate=None, **kw)  # stage T, with the last layer's taps
+        tr = _transformer(cfg, W, self.ups, self.start, mutate=None, split=self.split, **kw)  # stage T, with the last layer's taps
         t.update(tr_attn=tr["attn"], tr_resid=tr["resid"], tr_ff=tr["ff"], dec_tr=tr["out"])
+        if cfg.mimi.transformer.num_layers > 1:
+            t[f"tr_in{cfg.mimi.transformer.num_layers - 1}"] = tr["inp"]  # the last layer's input
         keep = live[:, None, None].astype(t["dec_tr"].dtype)
 
         def tail(name, n):
@@ -531,7 +625,15 @@ class Chain:
             return np.zeros_like(cur[:, :n]) if self.prev is None else self.prev[name][:, -n:] * keep
 
         for stage, src, n in CONV_CHAIN[:-2] if self.fused_tail else CONV_CHAIN:
-            t[OUTPUT_TAP[stage]] = STAGES[stage](cfg, W, t[src], tail(src, n), **kw)
+            if self.split is not None and stage[0] == "R" and int(stage[1]) in self.split_res:
+                i, c = int(stage[1]), f"seanet_c{stage[1]}"
+                t[c] = _elu(t[src], kw["alt"])  # the ELU'd copy the transposed conv stores beside the raw one
+                h = stage_Ra(cfg, W, i, t[c], tail(c, 2), split=self.split, **kw)
+                t[OUTPUT_TAP[stage]] = stage_Rb(cfg, W, i, h, t[src], split=self.split, **kw)
+            elif self.split is not None and stage in ("S0", "C1", "C2", "C3"):
+                t[OUTPUT_TAP[stage]] = STAGES[stage](cfg, W, t[src], tail(src, n), split=self.split, **kw)
+            else:
+                t[OUTPUT_TAP[stage]] = STAGES[stage](cfg, W, t[src], tail(src, n), **kw)
         if self.fused_tail:
             t["pcm"] = stage_R3L(cfg, W, t["seanet8"], tail("seanet8", 4), live, **kw)
         self.prev, self.lat_prev = t, np.asarray(lat)
@@ -539,11 +641,13 @@ class Chain:
         return t
 
 
-def chain_e32(cfg, W, latents, fused_tail=False, resets=()):
+def chain_e32(cfg, W, latents, fused_tail=False, resets=(), **split_kw):
     """latents [F, B, ldim] -> per frame (pcm64, E32): the fp64 chain's PCM and the worst float32 error of the same chain
-    over F32_VARIANTS.  resets: (frame, row) pairs of `reset_row` calls issued before that frame"""
+    over F32_VARIANTS.  resets: (frame, row) pairs of `reset_row` calls issued before that frame; split_kw: `Chain`'s
+    split / split_res"""
     B = latents.shape[1]
-    chains = [Chain(cfg, W, B, fused_tail=fused_tail)] + [Chain(cfg, W, B, F32, o, a, fused_tail) for o, a in F32_VARIANTS]
+    chains = [Chain(cfg, W, B, fused_tail=fused_tail, **split_kw)] + \
+        [Chain(cfg, W, B, F32, o, a, fused_tail, **split_kw) for o, a in F32_VARIANTS]
     out = []
     for f, lat in enumerate(latents):
         for fr, row in resets:
@@ -1064,3 +1168,171 @@ def f8_extra(cfg, W, site, cols, scales, y64, mutate=None):
     xs = float(np.float32(scales[SC_IN[site]]))
     b = f8_bound_codes(cols.reshape(-1, cols.shape[-1]), w, ws.astype(np.float64) * xs)
     return b.reshape(y64.shape) + 2 * 2.0 ** -24 * np.abs(y64)
+
+
+# ---- the split-bf16 codec (codec_split, gemm_kernel<.., WF = 3>): the fp32 stages with a split matrix product ------------
+# A split engine runs the fp32 codec's launches on fp32 buffers; only the matrix product of its GEMM launches differs
+# (`_mms`: xh.wh + xl.wh + xh.wl, hi = bf16(v), lo = bf16(v - hi), include/ptts.h and the header of ptts_split.hip).  The
+# stage functions above take `split=""` for that product (or a SPLIT_MUTANTS name); the prologue P, the attention proper,
+# the fused residual block R (fp32 weights, mimi_seanet_enqueue) and the last conv L stay the fp32 stages.  Launches the
+# fp32 stages lump together are judged apart here, on the taps between them:
+#   Q    the last layer's input, positions          tr_q / tr_k / tr_v   the +ln GEMM with EPI_QKV alone ([3, B, T, H 64])
+#   Ci   as above                                   seanet(3i-1), seanet_c<i>   raw and ELU'd copies ([2, B, T s, cout])
+#   Rai  seanet_c<i>, its last 2 rows before         seanet_h<i>          the k3 conv of an unfused block
+#   Rbi  seanet_h<i>, seanet(3i-1)                   seanet(3i)           the 1x1 conv + raw skip
+# E32s (`split_e32`) is E32 of the same split formulas: the float32 evaluations differ from the float64 one by the
+# summation and the epilogue only, since every bf16 x bf16 product is exact in float32.
+def stage_Q(cfg, W, x, pos, dtype=F64, order="np", alt=False, mutate=None, split=None):
+    """the last layer's in-projection of norm1(x) with RoPE at the positions pos [B, T]: queries, key rows and value rows
+    as the launch writes them, stacked [3, B, T, H * 64]"""
+    _check(mutate, ())
+    tr, H, Dh = _tr_cfg(cfg)
+    x = _in(x, dtype)
+    B, T, _ = x.shape
+    qkv = _ln_mm(cfg, W, ("qkv", tr.num_layers - 1), x, dtype, order, alt, split).reshape(B, T, 3, H, Dh)
+    q = _rope(qkv[:, :, 0], pos, float(tr.max_period), dtype)
+    k = _rope(qkv[:, :, 1], pos, float(tr.max_period), dtype)
+    return np.stack([q.reshape(B, T, H * Dh), k.reshape(B, T, H * Dh), np.ascontiguousarray(qkv[:, :, 2]).reshape(B, T, H * Dh)])
+
+
+def stage_Cv2(cfg, W, i, x, tail, dtype=F64, order="np", alt=False, mutate=None, split=None):
+    """stage i's transposed conv as a launch without "single_store" writes it: the raw output (the block's skip) and its
+    ELU'd copy (the k3 conv's operand), stacked [2, B, T * s, cout]"""
+    raw = stage_Cv(cfg, W, i, x, tail, dtype, order, alt, mutate, split)
+    return np.stack([raw, _elu(raw, alt)])
+
+
+def _res_convs(cfg, W, i, dtype):
+    P = params(cfg, W, dtype)
+    p = f"mimi.decoder.model.{_layer_of(cfg, 'res', i)[0]}.block"
+    return P.conv(p + ".1.conv"), P.conv(p + ".3.conv")
+
+
+def stage_Ra(cfg, W, i, x, tail, dtype=F64, order="np", alt=False, mutate=None, split=None):
+    """the k3 conv of stage i's unfused residual block on the ELU'd transposed-conv output (tail: its last 2 rows of the
+    previous frame), ELU'd: the hidden activation"""
+    _check(mutate, ("parity", "seqcut"))
+    (w1, b1), _ = _res_convs(cfg, W, i, dtype)
+    return _elu(_mm(_im2col(_halo(_in(x, dtype), tail, 2, mutate), 3), w1, b1, order, split), alt)
+
+
+def stage_Rb(cfg, W, i, h, skip, dtype=F64, order="np", alt=False, mutate=None, split=None):
+    """ELU(raw skip + 1x1 conv of the hidden activation): the unfused block's output (EPI_RES from craw)"""
+    _check(mutate, ("skip_elu", "no_bias2"))
+    _, (w2, b2) = _res_convs(cfg, W, i, dtype)
+    skip = _in(skip, dtype)
+    v = _mm(_in(h, dtype), w2, None if mutate == "no_bias2" else b2, order, split)
+    return _elu((_elu(skip, alt) if mutate == "skip_elu" else skip) + v, alt)
+
+
+SSTAGES = {"Q": stage_Q, "A": stage_A, "T": stage_T, "B": stage_B, "C": stage_C, "D": stage_D, "S0": stage_S0,
+           **{f"C{i}": _conv_stage(stage_Cv2, i) for i in (1, 2, 3)},
+           **{f"Ra{i}": _conv_stage(stage_Ra, i) for i in (1, 2, 3)}, **{f"Rb{i}": _conv_stage(stage_Rb, i) for i in (1, 2, 3)}}
+SPLIT_TAPS = {"Q": ("tr_q", "tr_krows", "tr_vrows"), "A": ("tr_attn",), "T": ("dec_tr",), "B": ("tr_resid",), "C": ("tr_ff",),
+              "D": ("dec_tr",), "S0": ("seanet0",), **{f"C{i}": (f"seanet{3 * i - 1}", f"seanet_c{i}") for i in (1, 2, 3)},
+              **{f"Ra{i}": (f"seanet_h{i}",) for i in (1, 2, 3)}, **{f"Rb{i}": (f"seanet{3 * i}",) for i in (1, 2, 3)}}
+
+
+def split_e32(stage, inputs, split=""):
+    """-> (y64s, E32s) of `SSTAGES[stage](**inputs, split=split)`: the float64 evaluation of the split formulas and the
+    worst float32 error of the same formulas on the same inputs over F32_VARIANTS.  From the reference alone."""
+    fn = SSTAGES[stage]
+    y64 = fn(**inputs, split=split)
+    assert y64.dtype == np.float64
+    e32 = 0.0
+    for order, alt in F32_VARIANTS:
+        y32 = fn(**inputs, dtype=F32, order=order, alt=alt, split=split)
+        assert y32.dtype == np.float32 and y32.shape == y64.shape, (stage, y32.dtype)
+        e32 = max(e32, float(np.abs(y32.astype(np.float64) - y64).max()))
+    assert e32 > 0, stage
+    return y64, e32
+
+
+def split_inputs(stage, cfg, W, frames, f, start=None):
+    """keyword arguments of `SSTAGES[stage]` at frame f; frames[g] as for `stage_inputs`, with the taps of SPLIT_TAPS and,
+    for more than one layer, "tr_in<last>" (the last layer's input)"""
+    cur = frames[f]
+    L = cfg.mimi.transformer.num_layers
+    B = np.asarray(cur["latent"]).shape[0]
+    st = np.zeros(B, np.int64) if start is None else np.asarray(start, np.int64)
+    live = st < f
+
+    def x_last():
+        return cur["upsample"] if L == 1 else cur[f"tr_in{L - 1}"]
+
+    def tail(name, n):
+        x = np.asarray(cur[name])
+        return np.zeros_like(x[:, :n]) if f == 0 else np.asarray(frames[f - 1][name])[:, -n:] * live[:, None, None].astype(x.dtype)
+
+    if stage == "Q":
+        return dict(cfg=cfg, W=W, x=x_last(), pos=(16 * (f - st))[:, None] + np.arange(16)[None, :])
+    if stage == "B":
+        return dict(cfg=cfg, W=W, attn=cur["tr_attn"], x=x_last())
+    if stage[:2] == "Ra":
+        return dict(cfg=cfg, W=W, x=cur[f"seanet_c{stage[2]}"], tail=tail(f"seanet_c{stage[2]}", 2))
+    if stage[:2] == "Rb":
+        return dict(cfg=cfg, W=W, h=cur[f"seanet_h{stage[2]}"], skip=cur[f"seanet{3 * int(stage[2]) - 1}"])
+    return stage_inputs(stage, cfg, W, frames, f, start)
+
+
+def _mag(x, w):
+    x = np.abs(np.asarray(x, np.float64))
+    return x.reshape(-1, x.shape[-1]) @ np.abs(w).T
+
+
+def split_scale(stage, inputs):
+    """what the mode's promise is measured against, shaped as the stage's output: rs * sum_k |x_k| |w_k| over the GEMM's
+    operands (x after any prologue, w the fp32 matrix; a +ln site adds rs |mu| sum_k |w_k|, the fold's second product),
+    carried through the epilogue's multiplications (the layer scale; RoPE's cosine and sine, in magnitude) as
+    gemm_ref.gemm_ref carries its `scale`, without the bias and the residual, which the split leaves exact.  The
+    activations' slopes are taken as 1 (ELU's is at most 1; GELU's reaches 1.13, inside the slack between the three
+    dropped terms' 3 x 2^-16 and the promise's 2^-14).  Stages A and T have none: their GEMMs' errors pass through a
+    softmax and further layers."""
+    cfg, W = inputs["cfg"], inputs["W"]
+    P = params(cfg, W, F64)
+    tr, H, Dh = _tr_cfg(cfg)
+    l = tr.num_layers - 1
+    if stage in ("Q", "C"):
+        x = np.asarray(inputs["x" if stage == "Q" else "resid"], np.float64)
+        wf = fold_image(cfg, W, ("qkv" if stage == "Q" else "ff1", l), F64)
+        mu, rs = _stats(x, False)
+        sc = (rs.reshape(-1, 1) * (_mag(x, wf) + np.abs(mu).reshape(-1, 1) * np.abs(wf).sum(axis=1)[None, :])).reshape(x.shape[:2] + (-1,))
+        if stage == "C":
+            return sc
+        B, T = x.shape[:2]
+        sc = sc.reshape(B, T, 3, H, Dh)
+        ds = np.arange(Dh // 2, dtype=F32)
+        freqs = np.exp((ds * F32(-math.log(float(tr.max_period)) * 2 / Dh)).astype(F64)).astype(F32)
+        ang = (freqs[None, None, :] * inputs["pos"].astype(F32)[:, :, None]).astype(F32).astype(F64)
+        c, s = np.abs(np.cos(ang))[:, :, None, :], np.abs(np.sin(ang))[:, :, None, :]
+        out = []
+        for j in (0, 1):
+            r, im = sc[:, :, j, :, 0::2], sc[:, :, j, :, 1::2]
+            o = np.empty_like(sc[:, :, j])
+            o[..., 0::2] = r * c + im * s
+            o[..., 1::2] = r * s + im * c
+            out.append(o.reshape(B, T, H * Dh))
+        return np.stack(out + [sc[:, :, 2].reshape(B, T, H * Dh)])
+    if stage in ("B", "D"):
+        x = inputs["attn" if stage == "B" else "ff"]
+        w = P.vec(_lp(l) + (".self_attn.out_proj.weight" if stage == "B" else ".linear2.weight"))
+        ls = np.abs(P.vec(_lp(l) + (".layer_scale_1.scale" if stage == "B" else ".layer_scale_2.scale")))
+        return (_mag(x, w) * ls[None, :]).reshape(np.asarray(x).shape[:2] + (-1,))
+    x, tl = np.asarray(inputs["h" if stage[:2] == "Rb" else "x"], np.float64), inputs.get("tail")
+    B, T = x.shape[:2]
+    if stage == "S0":
+        idx, _, _, K, _ = _layer_of(cfg, "conv", 0)
+        return _mag(_im2col(_halo(x, tl, K - 1, None), K), P.conv(f"mimi.decoder.model.{idx}.conv")[0]).reshape(B, T, -1)
+    i = int(stage[-1])
+    if stage[0] == "C":
+        idx, _, cout, _, s = _layer_of(cfg, "convtr", i)
+        xx = _halo(x, tl, 1, None)
+        m = _mag(np.concatenate([xx[:, 1:], xx[:, :-1]], axis=-1), P.convtr(f"mimi.decoder.model.{idx}.convtr", s)[0]).reshape(B, T * s, cout)
+        return np.stack([m, m])
+    (w1, _), (w2, _) = _res_convs(cfg, W, i, F64)
+    if stage[:2] == "Ra":
+        return _mag(_im2col(_halo(x, tl, 2, None), 3), w1).reshape(B, T, -1)
+    return _mag(x, w2).reshape(B, T, -1)
+
+
+PROMISE = 2.0 ** -14  # include/ptts.h: about 2^-16 per product; wl xl, (w - wh - wl) x and w (x - xh - xl) are each <= 2^-16 |w| |x|

@@ -116,7 +116,8 @@ def test_bf16_codec_end_to_end_frame_counts():
 
 @pytest.mark.parametrize("cfg_name,groups", [("tiny", None), ("tiny", {"attention", "ffn"}),
                                              ("en100m", {"attention", "ffn", "codec_bf16"}),
-                                             ("en100m", {"lm_bf16", "codec_fp8"})])
+                                             ("en100m", {"lm_bf16", "codec_fp8"}),
+                                             ("en100m", {"codec_split"})])  # the hi / lo images are build allocations the file carries
 def test_packed_engine_roundtrip(tmp_path, cfg_name, groups):
     """Offline packer: an engine rebuilt from its packed file (no checkpoint, no packing / quantisation pass)
     reproduces the original engine bit for bit, for the fp32 and for the int8 + bf16 weight formats."""
